@@ -32,6 +32,11 @@ One JSON line on stdout (rank 0).  Besides the contract's keys:
   `secondary`      the other BASELINE shapes, a few steps each AFTER the headline and outside its timed region:
                    N = 1: `c5shard` (north_star's ">= 50 % of the HBM-read roofline on the 2-bit unpack" lives here:
                    `read_only_frac`), `chr22`, `basic2`;  N > 1: `c5` (configs[4]) on the ranks' resident c4 records
+  `dump_outputs`   with `--dump-outputs DIR` only: what the headline's last timed step wrote, as DIR/gt_text.npy
+                   (float32 text bytes) and DIR/gt_text_offset.npy (their float64 byte offsets into the workload's
+                   V x (4K+1) bytes of GT text); every byte when the text fits DUMP_MAX_SAMPLES, else a fixed seeded sample of
+                   positions, so two builds run with the same arguments can be compared byte for byte.  With N > 1
+                   ranks each rank writes its share as gt_text.rank<r>.npy / gt_text_offset.rank<r>.npy.
 """
 from __future__ import annotations
 
@@ -49,6 +54,8 @@ sys.path.insert(0, str(REPO_ROOT))
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec (MI355X_MICROARCH.md)
 PCIE_PEAK_GBS = 63.0    # PCIe Gen5 x16 per GPU (MI355X_MICROARCH.md)
 SEED_DATA = 0x5047454E
+SEED_DUMP = 0x44554D50
+DUMP_MAX_SAMPLES = 1 << 22  # a float32 byte + a float64 offset each: 48 MiB, inside the 64 MB a dump may take
 
 # name -> (total variants, samples, keep modulus (0 = all samples kept), what it is)
 CONFIGS = {
@@ -285,14 +292,43 @@ def self_launch(argv: list[str], n_ranks: int) -> int:
     return child.wait()
 
 
-def time_steps(torch, dist, eng, recs, out, v: int, v_launch: int, r: int, steps: int, warmup: int, kernel: int, dev, world: int) -> dict:
-    """W untimed warm-up steps, then exactly `steps` steps between barrier + synchronize on both sides.  Wall clock for
-    `value`; the ctx's hipEvent pair on the kernels' stream for the roofline; one torch event pair per step for the spread."""
+def output_sample(torch, dev, v_total: int, begin: int, end: int, row_bytes: int):
+    """The `--dump-outputs` sample of this rank's GT text -> (offsets, grab, values).  Positions are drawn over the whole
+    workload's text, so they depend neither on the rank count nor on the launch plan; `offsets` are this rank's share, in
+    bytes from its first variant.  grab(out, b0, nb) gathers into `values` the samples of variants [b0, b0 + nb) of the
+    range, which `out` holds from byte 0, on torch's current stream: the engine's, so before a later launch re-uses `out`."""
+    import numpy as np
 
-    def step() -> None:
+    total = v_total * row_bytes
+    if total <= DUMP_MAX_SAMPLES:
+        pos = np.arange(total, dtype=np.int64)
+    else:
+        pos = np.unique(np.random.default_rng(SEED_DUMP).integers(0, total, size=DUMP_MAX_SAMPLES, dtype=np.int64))
+    lo, hi = np.searchsorted(pos, [begin * row_bytes, end * row_bytes])
+    offsets = pos[lo:hi] - begin * row_bytes
+    d_off = torch.as_tensor(offsets, device=dev)
+    values = torch.empty(len(offsets), dtype=torch.uint8, device=dev)
+
+    def grab(out, b0: int, nb: int) -> None:
+        i, j = np.searchsorted(offsets, [b0 * row_bytes, (b0 + nb) * row_bytes])
+        if j > i:
+            values[i:j] = out.index_select(0, d_off[i:j] - b0 * row_bytes)
+
+    return offsets, grab, values
+
+
+def time_steps(torch, dist, eng, recs, out, v: int, v_launch: int, r: int, steps: int, warmup: int, kernel: int, dev, world: int,
+               grab=None) -> dict:
+    """W untimed warm-up steps, then exactly `steps` steps between barrier + synchronize on both sides.  Wall clock for
+    `value`; the ctx's hipEvent pair on the kernels' stream for the roofline; one torch event pair per step for the spread.
+    `grab` (see output_sample) runs after each launch of the last step but its final one, whose rows stay in `out`."""
+
+    def step(grab=None) -> None:
         for b0 in range(0, v, v_launch):
             nb = min(v_launch, v - b0)
             eng.decode_emit(recs, nb, out=out, kernel=kernel, records_offset=b0 * r)
+            if grab is not None and b0 + nb < v:
+                grab(out, b0, nb)
 
     for _ in range(warmup):
         step()
@@ -304,9 +340,9 @@ def time_steps(torch, dist, eng, recs, out, v: int, v_launch: int, r: int, steps
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     eng.timer_start()                      # hipEvent pair of the ctx, same stream, around the whole timed region
-    for e0, e1 in evs:
+    for i, (e0, e1) in enumerate(evs):
         e0.record()
-        step()
+        step(grab if i == steps - 1 else None)
         e1.record()
     event_ms = eng.timer_stop()            # records + synchronises the stop event
     torch.cuda.synchronize(dev)
@@ -437,7 +473,11 @@ def main() -> int:
     ap.add_argument("--all-ranks-on-device0", action="store_true",
                     help="rehearsal only: every rank uses cuda:0 (with --dist-backend gloo) so the N>1 code path can run on a 1-GPU box")
     ap.add_argument("--kernel", type=int, default=0, help="PGENHIP_KERNEL_* override for A/B runs (0 = automatic, the measured default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the GT text the last one computed (a fixed seeded sample of it) as DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(sys.argv[1:], args.gpus)   # before `import torch`: the parent never touches a GPU
@@ -499,13 +539,32 @@ def main() -> int:
 
     # the rank's records, resident before the timed region; then as many output rows as fit beside them
     recs = eng.synth_records(v, first_variant=begin, seed=SEED_DATA, hwe=hwe)
+    grab = None
+    if args.dump_outputs:
+        dump_offsets, grab, dump_values = output_sample(torch, dev, v_total, begin, end, row_bytes)
     torch.cuda.synchronize(dev)
     share = world if args.all_ranks_on_device0 else 1
     v_launch, n_launch = launch_plan(torch, dev, v, row_bytes, share, args.max_launch_variants)
     out = torch.empty(max(v_launch, 1) * row_bytes, dtype=torch.uint8, device=dev)
 
-    t = time_steps(torch, dist, eng, recs, out, v, v_launch, r, args.steps, args.warmup, args.kernel, dev, world)
+    t = time_steps(torch, dist, eng, recs, out, v, v_launch, r, args.steps, args.warmup, args.kernel, dev, world, grab)
     dt, event_ms, step_ms = t["dt"], t["event_ms"], t["step_ms"]
+
+    dump = None
+    if args.dump_outputs:
+        import numpy as np
+
+        if v > 0:
+            last_b0 = (v - 1) // v_launch * v_launch  # the last step's final launch, still in `out`
+            grab(out, last_b0, v - last_b0)
+        dump_dir = Path(args.dump_outputs)
+        dump_dir.mkdir(parents=True, exist_ok=True)
+        suffix = "" if world == 1 else f".rank{rank}"
+        files = [f"gt_text{suffix}.npy", f"gt_text_offset{suffix}.npy"]
+        np.save(dump_dir / files[0], dump_values.cpu().numpy().astype(np.float32))
+        np.save(dump_dir / files[1], (dump_offsets + begin * row_bytes).astype(np.float64))
+        dump = {"dir": str(dump_dir), "files": files, "bytes_sampled": len(dump_offsets), "text_bytes": v_total * row_bytes,
+                "row_bytes": row_bytes}
     t_all = torch.tensor([dt, event_ms, max(step_ms), -min(step_ms)], dtype=torch.float64, device=red_dev)
     if world > 1:
         dist.all_reduce(t_all, op=dist.ReduceOp.MAX)
@@ -647,6 +706,8 @@ def main() -> int:
             line["secondary"] = secondary
         if hd is not None:
             line["host_delivered"] = hd
+        if dump is not None:
+            line["dump_outputs"] = dump
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(n, kept)
         print(json.dumps(line), flush=True)
