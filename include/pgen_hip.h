@@ -194,7 +194,10 @@ int pgenhip_decode_emit_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t 
  * d_prefix_off/d_line_off are device arrays of n_variants+1 u64 with
  * d_line_off[j+1]-d_line_off[j] == prefix_len(j) + 4K + 1 (lines packed back to back);
  * max_prefix_bytes is a host-known upper bound of any prefix length.  It must be a TRUE bound: the kernels size their LDS staging
- * and their seam passes by it; with a smaller value lines come out wrong (nothing is read or written out of bounds).
+ * and their seam passes by it; with a smaller value lines come out wrong (nothing is read or written out of bounds: blob loads
+ * are sized by d_prefix_off, stores addressed from d_line_off and kept inside [d_line_off[0], d_line_off[n_variants])).  A loose
+ * bound is legal and exact.  A bound with max_prefix_bytes + 4K + 1 >= 2^31 is PGENHIP_ERR_TOO_LARGE before any launch.
+ * d_prefix_blob may be NULL only with max_prefix_bytes == 0 (every prefix empty; d_prefix_off entries then need not be 0).
  * flags: PGENHIP_KERNEL_AUTO picks by shape — all samples kept: the work-queue stream kernel from 1 400 samples (GT segments
  * in place behind their prefixes), below it runs of whole lines assembled in LDS (short prefixes, N < 1 000) or the pick
  * family's interiors + seams kernel; a kept subset: the pick family on records of up to 4 096 samples, the segment kernels or

@@ -83,6 +83,9 @@ constexpr size_t kWorkBlockWords = kWorkBlockBytes / sizeof(uint64_t);
 // ctx on different streams may overlap: include/pgen_hip.h, "Streams").  A slice holds one chunk of rows between the two passes;
 // a chunk stays in the 256-MiB Infinity Cache, so a smaller one costs only its two extra kernel launches.
 constexpr size_t kCompactSliceBytes = 32u << 20;
+// pgenhip_emit_lines: a bound on the line length (max_prefix_bytes + 4K + 1) below which every kernel can plan its tiles, batches and
+// seams; larger bounds are PGENHIP_ERR_TOO_LARGE before any launch
+constexpr uint64_t kMaxLineBytes = 1ull << 31;
 
 }  // namespace
 
@@ -502,6 +505,9 @@ int pgenhip_emit_lines(pgenhip_ctx *ctx, const void *d_records, uint64_t record_
     if (n_variants == 0) return PGENHIP_OK;
     if (!d_prefix_off || !d_line_off) return fail(PGENHIP_ERR_BAD_ARG, "offset arrays are NULL");
     if (max_prefix_bytes && !d_prefix_blob) return fail(PGENHIP_ERR_BAD_ARG, "d_prefix_blob is NULL");
+    // the kernels plan tiles, batches and seams from the bound in 32 bits (gt_rows.hip: tiles per row, grid-stride over V x tiles)
+    if (max_prefix_bytes >= kMaxLineBytes || max_prefix_bytes + 4ull * ctx->kept_count + 1ull >= kMaxLineBytes)
+        return fail(PGENHIP_ERR_TOO_LARGE, "max_prefix_bytes + 4K + 1 >= 2^31");
     a.prefix_blob = static_cast<const uint8_t *>(d_prefix_blob);
     a.prefix_off = d_prefix_off;
     a.line_off = d_line_off;

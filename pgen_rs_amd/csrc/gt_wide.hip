@@ -1028,7 +1028,8 @@ __global__ __launch_bounds__(64 * (NS + 1)) void gt_lineruns_kernel(EmitArgs a, 
                 const uint8_t *const pb = a.prefix_blob + p_start;
                 const uint32_t pmis = (uint32_t)((uint64_t)(uintptr_t)pb & 15ull);
                 const uint32_t p_pieces = (pmis + (uint32_t)(p_end - p_start) + 15u) / 16u;   // <= kLrPfxBytes / 16
-                if (lane < p_pieces) pin[w] = *reinterpret_cast<const v4u *>(pb - pmis + lane * 16u);
+                // (no prefix bytes: nothing to load — the blob may then be NULL, and its offsets need not be multiples of 16)
+                if (p_end > p_start && lane < p_pieces) pin[w] = *reinterpret_cast<const v4u *>(pb - pmis + lane * 16u);
                 pmis_w[w] = pmis;
                 if (lane == 0u) {
                     uint8_t *d = s_desc[w][step % DS];

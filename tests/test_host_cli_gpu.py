@@ -271,3 +271,61 @@ def test_bgzf_lines_longer_than_a_member(tmp_path):
     assert plain.read_bytes() == expected_vcf(pfx)
     assert run("filter", str(pfx), "-o", str(gz), "--block-mib", "8").returncode == 0
     check_bgzf(gz, plain.read_bytes())
+
+
+# ---- the reference's dataset shape (N = 300) with real INFO columns: the 1000 Genomes rows of basic1.pvar, cycled ----------------
+def _pvar_rows_of_basic1():
+    lines = (GOLDEN / "basic1" / "basic1.pvar").read_bytes().split(b"\n")
+    return [ln for ln in lines if ln.startswith(b"#")], [ln for ln in lines if ln and not ln.startswith(b"#")]
+
+
+def _write_n300(d, name, rows, hdr):
+    shutil.copy(GOLDEN / "basic2" / "basic2.psam", d / f"{name}.psam")
+    (d / f"{name}.pvar").write_bytes(b"".join(h + b"\n" for h in hdr) + b"".join(r + b"\n" for r in rows))
+    n, v = 300, len(rows)
+    recs = oracle.synth_records(n, v, first_variant=3, hwe=True)
+    (d / f"{name}.pgen").write_bytes(bytes([0x6C, 0x1B, 0x02]) + v.to_bytes(4, "little") + n.to_bytes(4, "little") + b"\x40" + recs.tobytes())
+    return d / name
+
+
+@pytest.fixture(scope="module")
+def n300_info(tmp_path_factory):
+    """N = 300 (basic2.psam), 20 000 variants whose pvar rows are basic1.pvar's 1000 Genomes rows cycled: body-line prefixes of
+    ~130-250 bytes (AUTO: the pick family's full-line kernel for all samples, its interiors + seams with a sample filter)."""
+    hdr, rows = _pvar_rows_of_basic1()
+    return _write_n300(tmp_path_factory.mktemp("n300_info"), "n300_info", [rows[i % len(rows)] for i in range(20_000)], hdr)
+
+
+@pytest.fixture(scope="module")
+def n300_short_info(tmp_path_factory):
+    """Same rows with the INFO column trimmed so that the prefixes are 60-94 bytes: AUTO takes the line-run kernel for all samples
+    (seven lines per item) with five-lane-shift seams (prefixes of 64 bytes and more)."""
+    hdr, rows = _pvar_rows_of_basic1()
+    out = []
+    for i in range(20_000):
+        cols = rows[i % len(rows)].split(b"\t")
+        base = sum(len(c) + 1 for c in cols[:-1]) + 1 + 2                 # the other columns + their tabs, INFO's tab, "GT"
+        want = 60 + (i * 7) % 35                                         # 60 .. 94
+        cols[-1] = cols[-1][: want - base]
+        assert base + len(cols[-1]) == want, "INFO column too short to trim to length"
+        out.append(b"\t".join(cols))
+    return _write_n300(tmp_path_factory.mktemp("n300_short"), "n300_short", out, hdr)
+
+
+_TENTH = " || ".join(f'IID == "per{i}"' for i in range(3, 300, 10))
+
+
+@pytest.mark.parametrize("fixture", ["n300_info", "n300_short_info"])
+@pytest.mark.parametrize("how", ["whole", "tenth", "one", "block1"])
+def test_n300_with_real_info_columns(request, fixture, how, tmp_path):
+    """pgen-hip filter on the reference's dataset shape with real INFO columns: the whole file, a 10 % and a one-sample filter, and
+    1-MiB blocks, each against the expected file."""
+    pf = request.getfixturevalue(fixture)
+    out = tmp_path / "o.vcf"
+    args = {"whole": [], "tenth": ["--include-sam", _TENTH], "one": ["--include-sam", 'IID == "per123"'], "block1": ["--block-mib", "1"]}[how]
+    p = run("filter", str(pf), *args, "-o", str(out))
+    assert p.returncode == 0, p.stderr
+    keep = {"whole": None, "block1": None, "tenth": {b"per%d" % i for i in range(3, 300, 10)}, "one": {b"per123"}}[how]
+    want = expected_vcf(pf, sam_pred=None if keep is None else (lambda r: r[b"IID"] in keep))
+    got = out.read_bytes()
+    assert len(got) == len(want) and got == want
