@@ -209,6 +209,25 @@ int pgenhip_emit_lines(pgenhip_ctx *ctx, const void *d_records, uint64_t record_
                        const uint64_t *d_line_off, uint64_t max_prefix_bytes,
                        void *d_out, uint32_t flags);
 
+/* ---- per-variant genotype counts (device-resident, asynchronous on the ctx stream) ----
+ * For row j (records selected exactly as in pgenhip_decode_emit / pgenhip_decode_emit_at) writes four u32 at
+ * d_counts[4*j + c]: the number of the ctx's kept samples with code c — 0 hom-ref ("0/0"), 1 het ("0/1"),
+ * 2 hom-alt ("1/1"), 3 missing ("./.") — i.e. the GT fields pgenhip_decode_emit writes for that row, counted
+ * (src/pfile.rs:172-183).  The pad bits of a record's last byte are never counted.  Records may start at any byte
+ * alignment; with record_stride >= R (or n_variants <= 1).  Nothing outside d_counts[0 .. 4*n_variants) is written.
+ * n_variants == 0 is a no-op.  Same launch contract as pgenhip_decode_emit: device pointers only, no allocation, no
+ * synchronisation, queued on the ctx stream, graph-capturable.
+ * flags: PGENHIP_COUNT_AUTO picks the shape by N (a wave per row above 6 084 samples); the other two force one. */
+#define PGENHIP_COUNT_AUTO 0u
+#define PGENHIP_COUNT_WAVE_PER_ROW 1u    /* long rows: one wave per row, wave reduction, one 16-byte store */
+#define PGENHIP_COUNT_ROWS_PER_WAVE 2u   /* short rows: 4 .. 32 lanes per row, several rows per wave */
+int pgenhip_genotype_counts(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                            uint32_t n_variants, uint32_t *d_counts, uint32_t flags);
+/* Same, with the record of row j at d_base + d_record_off[j] (DEVICE array of u64 byte offsets): the plain records of a
+ * variable-width file staged as they lie on disk. */
+int pgenhip_genotype_counts_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
+                               uint32_t *d_counts, uint32_t flags);
+
 /* Launch-shape knobs of one ctx (tests force small grids to exercise ring re-use; A/B probes).
  * value 0 restores the built-in default of a knob unless noted. */
 typedef enum pgenhip_knob {

@@ -24,6 +24,7 @@ struct pgenhip_ctx {
     bool subset = false;
     bool identity = false;             // a kept list that names every sample: AUTO takes the all-samples kernels
     uint32_t *d_kept = nullptr;
+    uint8_t *d_count_mask = nullptr;   // genotype counts with a kept subset: the kept samples as a 2-bit mask (gt_count.hip)
     uint32_t *d_seg_rank = nullptr;    // segment kernels: kept samples before each segment
     uint32_t max_seg_count = 0;        // segment kernels: most kept samples in one segment
     uint8_t *d_compact = nullptr;      // two-pass path for sparse keeps on long records: compact records of one chunk of rows,
@@ -164,6 +165,14 @@ int pgenhip_create(pgenhip_ctx **out, int device_ordinal, uint32_t sample_count,
             }
             if ((e = hipMalloc(reinterpret_cast<void **>(&ctx->d_seg_rank), seg_rank.size() * sizeof(uint32_t))) != hipSuccess) { rc = fail_hip(e, "hipMalloc(segment ranks)"); break; }
             if ((e = hipMemcpy(ctx->d_seg_rank, seg_rank.data(), seg_rank.size() * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess) { rc = fail_hip(e, "hipMemcpy(segment ranks)"); break; }
+            // genotype counts: the kept list as a record-shaped mask (0b01 per kept sample) behind 16 zero bytes, so that the count kernel
+            // ANDs it into the record words; an identity list counts like "all samples" and needs none
+            if (!ctx->identity) {
+                std::vector<uint8_t> mask(gt_count_mask_bytes(ctx->record_size), 0u);
+                for (uint32_t k = 0; k < kept_count; k++) mask[16u + kept_idx[k] / 4u] |= (uint8_t)(1u << (2u * (kept_idx[k] % 4u)));
+                if ((e = hipMalloc(reinterpret_cast<void **>(&ctx->d_count_mask), mask.size())) != hipSuccess) { rc = fail_hip(e, "hipMalloc(count mask)"); break; }
+                if ((e = hipMemcpy(ctx->d_count_mask, mask.data(), mask.size(), hipMemcpyHostToDevice)) != hipSuccess) { rc = fail_hip(e, "hipMemcpy(count mask)"); break; }
+            }
             // two-pass path (sparse keeps on long records): scratch for the compact records of one chunk of rows per launch in flight
             // (config 5's per-GPU shard, 125 000 rows x 1 250 bytes, is five chunks; a chunk stays in the 256-MiB Infinity Cache
             // between the two passes); allocated here so that no launch ever allocates
@@ -189,6 +198,7 @@ int pgenhip_destroy(pgenhip_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     if (ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
     if (ctx->d_kept) (void)hipFree(ctx->d_kept);
+    if (ctx->d_count_mask) (void)hipFree(ctx->d_count_mask);
     if (ctx->d_work) (void)hipFree(ctx->d_work);
     if (ctx->d_seg_rank) (void)hipFree(ctx->d_seg_rank);
     if (ctx->d_compact) (void)hipFree(ctx->d_compact);
@@ -568,6 +578,47 @@ int pgenhip_emit_lines(pgenhip_ctx *ctx, const void *d_records, uint64_t record_
         default:
             return fail(PGENHIP_ERR_BAD_ARG, "pgenhip_emit_lines supports kernel flags AUTO, ROWS, WIDE, SCAN, PICK, RUNS and ROWPICK");
     }
+}
+
+static int genotype_counts_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                                const uint64_t *d_record_off, uint32_t n_variants, uint32_t *d_counts, uint32_t flags)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (flags > PGENHIP_COUNT_ROWS_PER_WAVE) return fail(PGENHIP_ERR_BAD_ARG, "unknown genotype_counts flag");
+    if (n_variants == 0) return PGENHIP_OK;
+    if (!d_counts) return fail(PGENHIP_ERR_BAD_ARG, "d_counts is NULL");
+    if (ctx->record_size && !d_records) return fail(PGENHIP_ERR_BAD_ARG, "d_records is NULL");
+    if (n_variants > 1 && !d_variant_idx && !d_record_off && record_stride < ctx->record_size)
+        return fail(PGENHIP_ERR_BAD_ARG, "record_stride < record size");
+    CountArgs a;
+    a.records = static_cast<const uint8_t *>(d_records);
+    a.record_stride = record_stride;
+    a.variant_idx = d_variant_idx;
+    a.record_off = d_record_off;
+    a.n_variants = n_variants;
+    a.sample_count = ctx->sample_count;
+    a.record_size = ctx->record_size;
+    a.kept_count = ctx->kept_count;
+    a.kept_mask = ctx->d_count_mask;   // NULL with all samples kept or an identity list
+    a.counts = d_counts;
+    // AUTO: a wave per row once a row spans more chunks than 32 lanes take in three passes (N > 6 084), else several rows per wave
+    const bool wave_per_row = flags == PGENHIP_COUNT_WAVE_PER_ROW || (flags == PGENHIP_COUNT_AUTO && gt_count_lanes_per_row(ctx->record_size) == 64u);
+    HIP_TRY(launch_gt_count(a, wave_per_row, ctx->num_cus, ctx->stream));
+    return PGENHIP_OK;
+}
+
+int pgenhip_genotype_counts(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                            uint32_t n_variants, uint32_t *d_counts, uint32_t flags)
+{
+    return genotype_counts_core(ctx, d_records, record_stride, d_variant_idx, nullptr, n_variants, d_counts, flags);
+}
+
+int pgenhip_genotype_counts_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
+                               uint32_t *d_counts, uint32_t flags)
+{
+    if (ctx && n_variants && !d_record_off) return fail(PGENHIP_ERR_BAD_ARG, "d_record_off is NULL");
+    return genotype_counts_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, d_counts, flags);
 }
 
 int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)

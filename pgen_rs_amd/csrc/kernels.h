@@ -106,6 +106,26 @@ hipError_t launch_gt_rowpick(const EmitArgs &a, const ScanArgs &sc, const Tuning
 bool gt_pick_applicable(const EmitArgs &a);
 hipError_t launch_gt_pick(const EmitArgs &a, const Tuning &t, int num_cus, hipStream_t stream);
 
+// Per-variant genotype counts (gt_count.hip): four u32 per selected row at counts + 4 * j (hom-ref, het, hom-alt, missing).
+struct CountArgs {
+    const uint8_t *records;       // device; row r at records + r*record_stride
+    uint64_t record_stride;
+    const uint32_t *variant_idx;  // device or nullptr (identity)
+    const uint64_t *record_off;   // device or nullptr; when set, row j's record starts at records + record_off[j]
+    uint32_t n_variants;
+    uint32_t sample_count;        // N
+    uint32_t record_size;         // R = ceil(N/4)
+    uint32_t kept_count;          // K (== N without a mask)
+    const uint8_t *kept_mask;     // device or nullptr (all samples): 16 zero bytes, then 2 bits per sample like a record (0b01 = kept), then zeros
+    uint32_t *counts;             // device
+};
+// Bytes of the ctx's kept mask buffer for records of R bytes: the mask behind 16 zero bytes, zeros up to the last chunk a row can touch
+inline size_t gt_count_mask_bytes(uint32_t record_size) { return 16u * ((size_t)(record_size + 30u) / 16u + 2u); }
+// lanes per row of the short-row shape for records of R bytes (64: rows this long take the wave-per-row shape under AUTO)
+uint32_t gt_count_lanes_per_row(uint32_t record_size);
+// wave_per_row: one wave per row (long rows); else 4 .. 32 lanes per row, several rows per wave (short rows)
+hipError_t launch_gt_count(const CountArgs &a, bool wave_per_row, int num_cus, hipStream_t stream);
+
 // Deterministic synthetic records (SURVEY.md §8d counter-based generator).
 hipError_t launch_synth_records(uint8_t *dst, uint64_t record_stride, uint32_t sample_count,
                                 uint64_t first_variant, uint32_t n_variants, uint64_t seed,

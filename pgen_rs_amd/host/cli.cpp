@@ -4,6 +4,8 @@
 //   pgen-hip query  <PFILE_PREFIX> -f|--fstring <EXPR> [-i|--include <EXPR>] [-s|--samples]
 //   pgen-hip filter <PFILE_PREFIX> [--include-var <EXPR>] [--include-sam <EXPR>] [-o|--out <FILE>]
 //
+// `pgen-hip freq <PFILE_PREFIX> [--include-var <EXPR>] [--include-sam <EXPR>] [-o|--out <FILE>]` (not in the reference): per-variant
+// genotype counts of the kept samples with filter's selection, counted on the GPU; tab-separated to stdout or FILE.
 // Additions (opt-in, not in the reference): --gpus <N>, --block-mib <M>, --launch-mib <M>, --filter-threads <T>, --stats, --dry-run
 // (filter: write the VCF header only and report the body geometry; needs no GPU); BGZF output (`-o x.vcf.gz` or --bgzf,
 // --bgzf-level <1-9>, --compress-threads <T>) and `pgen-hip bgzf <IN> <OUT>`, the same writer on a file.
@@ -94,11 +96,16 @@ const char *kUsage =
     "Commands:\n"
     "  query   Queries the pgen, outputting to stdout\n"
     "  filter  Filters the pgen, outputting to a VCF\n"
+    "  freq    Per-variant genotype counts of the kept samples, outputting to stdout\n"
     "  help    Print this message\n\n"
     "query  <PFILE_PREFIX> -f, --fstring <QUERY_FSTRING> [-i, --include <QUERY>] [-s, --samples]\n"
     "filter <PFILE_PREFIX> [--include-var <VAR_QUERY>] [--include-sam <SAM_QUERY>] [-o, --out <OUT_FILE>]\n"
     "       [--gpus <N>] [--shards <S>] [--block-mib <M>] [--launch-mib <M>] [--write-threads <T>] [--read-threads <T>] [--filter-threads <T>] [--stats] [--dry-run]\n"
     "       [--bgzf] [--bgzf-level <1-9>] [--compress-threads <T>]   (BGZF `.vcf.gz`; implied by an OUT_FILE ending in .gz)\n"
+    "freq   <PFILE_PREFIX> [--include-var <VAR_QUERY>] [--include-sam <SAM_QUERY>] [-o, --out <OUT_FILE>]\n"
+    "       [--gpus <N>] [--shards <S>] [--block-mib <M>] [--read-threads <T>] [--filter-threads <T>] [--stats]\n"
+    "       one line per kept variant: CHROM POS ID REF ALT HOM_REF_CT HET_REF_ALT_CTS TWO_ALT_GENO_CTS MISSING_CT (plink2 .gcount\n"
+    "       column names, diploid columns only; byte parity with plink2 is not claimed)\n"
     "bgzf   <IN_FILE> <OUT_FILE> [--level <1-9>] [--threads <T>] [--chunk-mib <M>]\n";
 
 [[noreturn]] void usage_error(const std::string &msg)
@@ -277,6 +284,28 @@ int main(int argc, char **argv)
                              (unsigned long long)st.variants, (unsigned long long)st.samples_kept, (unsigned long long)st.header_bytes,
                              (unsigned long long)st.body_bytes, (unsigned long long)st.file_bytes, st.seconds_filter, st.seconds_body, st.seconds_setup, st.seconds_kernel,
                              std::chrono::duration<double>(std::chrono::steady_clock::now() - t_main).count());
+            }
+            return 0;
+        }
+        if (cmd == "freq") {
+            Args a = parse(argc, argv, 2, {{"include-var", 0}, {"include-sam", 0}, {"out", 'o'}, {"gpus", 0}, {"shards", 0}, {"block-mib", 0}, {"read-threads", 0}, {"filter-threads", 0}},
+                           {{"stats", 0}});
+            if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
+            const Pfile pfile = Pfile::from_prefix(a.positional[0]);
+            OutputOptions opt;
+            if (auto f = a.get("filter-threads")) opt.filter_threads = std::max(1, std::atoi(f->c_str()));
+            if (auto g = a.get("gpus")) opt.n_gpus = std::max(1, std::atoi(g->c_str()));
+            if (auto sh = a.get("shards")) opt.n_shards = std::max(1, std::atoi(sh->c_str()));
+            if (auto w = a.get("read-threads")) opt.read_threads = std::max(1, std::atoi(w->c_str()));
+            if (auto m = a.get("block-mib")) opt.block_text_bytes = (uint64_t)std::max(1, std::atoi(m->c_str())) << 20;
+            const OutputStats st = pfile.output_freq(a.get("include-sam"), a.get("include-var"), a.get("out").value_or(""), opt);
+            if (a.has("stats")) {
+                std::fprintf(stderr,
+                             "{\"variants_kept\": %llu, \"samples_kept\": %llu, \"header_bytes\": %llu, \"body_bytes\": %llu, \"file_bytes\": %llu, "
+                             "\"seconds_filter\": %.6f, \"seconds_body\": %.6f, \"seconds_setup\": %.6f, \"seconds_kernel\": %.6f, \"seconds_main\": %.6f}\n",
+                             (unsigned long long)st.variants, (unsigned long long)st.samples_kept, (unsigned long long)st.header_bytes,
+                             (unsigned long long)st.body_bytes, (unsigned long long)st.file_bytes, st.seconds_filter, st.seconds_body, st.seconds_setup,
+                             st.seconds_kernel, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_main).count());
             }
             return 0;
         }

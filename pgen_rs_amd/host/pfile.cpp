@@ -832,6 +832,232 @@ OutputStats Pfile::output_vcf(const std::optional<std::string> &sam_query, const
     return st;
 }
 
+namespace {
+
+// `count` bytes at `off` of the .pgen into dst: one pread, or a few at once for long spans (one thread copies ~2-3 GB/s out of the
+// page cache; output_vcf's staging does the same)
+void pread_span(int fd, uint8_t *dst, size_t count, uint64_t off, const std::string &path, int read_threads)
+{
+    const unsigned n_readers = count >= (64u << 20) ? (unsigned)std::max(1, read_threads) : 1u;
+    if (n_readers <= 1) {
+        pread_exact(fd, dst, count, off, path);
+        return;
+    }
+    std::vector<std::thread> rs;
+    std::string rerr;
+    std::mutex rmu;
+    const size_t slice = (count + n_readers - 1) / n_readers;
+    for (unsigned t = 0; t < n_readers; t++) {
+        const size_t lo = std::min(count, (size_t)t * slice), hi = std::min(count, lo + slice);
+        if (lo == hi) continue;
+        rs.emplace_back([&, lo, hi] {
+            try {
+                pread_exact(fd, dst + lo, hi - lo, off + lo, path);
+            } catch (const std::exception &e) {
+                std::lock_guard<std::mutex> lk(rmu);
+                rerr = e.what();
+            }
+        });
+    }
+    for (auto &t : rs) t.join();
+    if (!rerr.empty()) throw PfileError(rerr);
+}
+
+void append_u64(std::string &s, uint64_t v)
+{
+    char buf[24];
+    int n = 0;
+    do {
+        buf[n++] = (char)('0' + v % 10);
+        v /= 10;
+    } while (v);
+    while (n) s += buf[--n];
+}
+
+}  // namespace
+
+OutputStats Pfile::output_freq(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
+                               const std::string &filename, const OutputOptions &opt) const
+{
+    OutputStats st;
+    const double t0 = now_s();
+    const std::string psam = read_file(psam_path());
+    TsvReader psam_reader(psam, find_metadata_file_header_start(psam));
+    const std::string pvar = read_file(pvar_path());
+    TsvReader pvar_reader(pvar, find_metadata_file_header_start(pvar));
+    const StringRecord pvar_header = pvar_reader.headers();
+    const IdxRecords var_idx_rcds = filter_metadata(pvar_reader, var_query, opt.filter_threads);
+    const IdxRecords sam_idx_rcs = filter_metadata(psam_reader, sam_query, opt.filter_threads);
+    // the five leading columns, copied verbatim from the pvar columns of these names
+    static const char *const kCols[5] = {"CHROM", "POS", "ID", "REF", "ALT"};
+    size_t col[5];
+    for (int c = 0; c < 5; c++) {
+        col[c] = std::find(pvar_header.begin(), pvar_header.end(), std::string(kCols[c])) - pvar_header.begin();
+        if (col[c] == pvar_header.size()) throw PfileError(std::string(kCols[c]) + " not among the headers of " + pvar_path());
+    }
+    st.seconds_filter = now_s() - t0;
+
+    const uint32_t N = num_samples;
+    const uint32_t R = variant_record_size();
+    const size_t V = var_idx_rcds.size();
+    std::vector<uint32_t> kept;
+    kept.reserve(sam_idx_rcs.size());
+    for (const auto &ir : sam_idx_rcs) {
+        if (ir.first >= N) throw PfileError("index out of bounds: sample row " + std::to_string(ir.first) + " but the .pgen holds " + std::to_string(N) + " samples");
+        kept.push_back((uint32_t)ir.first);
+    }
+    const bool all_samples = kept.size() == (size_t)N;
+    for (size_t j = 0; j < V; j++) {
+        const size_t vi = var_idx_rcds[j].first;
+        if (vi >= num_variants)
+            throw PfileError("variant row " + std::to_string(vi) + " is past the " + std::to_string(num_variants) + " records of " + pgen_path());
+        if (variable_width() && ((*vw_record_type)[vi] != 0 || (*vw_record_len)[vi] != R))
+            throw PfileError(pgen_path() + ": variant row " + std::to_string(vi) + " is stored compressed (record type " +
+                             std::to_string((*vw_record_type)[vi]) + ", " + std::to_string((*vw_record_len)[vi]) + " bytes); only uncompressed 2-bit records are supported");
+    }
+    st.variants = V;
+    st.samples_kept = kept.size();
+
+    std::vector<uint32_t> counts(4 * V, 0u);
+    const double t_body = now_s();
+    if (V != 0 && R != 0) {
+        int n_dev = 0;
+        check(pgenhip_device_count(&n_dev), "pgenhip_device_count");
+        if (n_dev <= 0) throw PfileError("no HIP device: the genotype count path has no CPU fallback");
+        const int n_use = std::max(1, std::min(opt.n_gpus, n_dev));
+        const int G = opt.n_shards > 0 ? opt.n_shards : n_use;   // variant ranges (shards), dealt round-robin over the devices
+        std::vector<double> kernel_s((size_t)G, 0.0), setup_s((size_t)G, 0.0);
+        std::mutex err_mu;
+        std::string err;
+        const std::string pgen = pgen_path();
+        const bool vw = variable_width();
+
+        // Per shard: blocks of bv variants.  Block k's records are read into pinned buffer k % 2 while the device copies, counts and
+        // returns block k - 1; each block's H2D copy, count launch and 16-byte-per-variant D2H copy are queued on the ctx stream.
+        // Fixed-width files: runs of consecutive records are read in one go and packed at stride R.  Variable-width files: the plain
+        // records are staged as they lie on disk (a span grows over gaps of up to R bytes, so a block stages at most 2R bytes per
+        // variant) and counted through their offsets in the staged bytes (pgenhip_genotype_counts_at).
+        auto worker = [&](int g) {
+            try {
+                const double t_worker = now_s();
+                uint64_t begin64 = 0, end64 = 0;
+                check(pgenhip_shard_range(V, (uint32_t)G, (uint32_t)g, &begin64, &end64), "pgenhip_shard_range");
+                const size_t begin = (size_t)begin64, end = (size_t)end64;
+                if (begin == end) return;
+                int pfd = open(pgen.c_str(), O_RDONLY);
+                if (pfd < 0) throw PfileError("open " + pgen + ": " + std::strerror(errno));
+                struct FdGuard {
+                    int fd;
+                    ~FdGuard() { close(fd); }
+                } pg{pfd};
+                const uint64_t bv = std::max<uint64_t>(1, std::min<uint64_t>(opt.block_text_bytes / R, end - begin));
+                const size_t stage_bytes = (size_t)(bv * R) * (vw ? 2u : 1u);
+                DeviceBuffers B;   // h_rec / h_text2: the two pinned record buffers; h_off: pinned offsets + counts; d_text: device counts
+                check(pgenhip_create(&B.ctx, g % n_use, N, all_samples ? nullptr : kept.data(), (uint32_t)kept.size(),
+                                     all_samples ? 0u : PGENHIP_CREATE_KEEP_LIST), "pgenhip_create");
+                check(pgenhip_device_malloc(B.ctx, &B.d_rec, stage_bytes), "device records");
+                check(pgenhip_device_malloc(B.ctx, &B.d_text, (size_t)(16 * bv)), "device counts");
+                if (vw) check(pgenhip_device_malloc(B.ctx, &B.d_off, (size_t)(8 * bv)), "device record offsets");
+                check(pgenhip_host_malloc_pinned(B.ctx, &B.h_rec, stage_bytes), "pinned records");
+                check(pgenhip_host_malloc_pinned(B.ctx, &B.h_text2, stage_bytes), "pinned records");
+                check(pgenhip_host_malloc_pinned(B.ctx, &B.h_off, (size_t)(16 * bv + (vw ? 16 * bv : 0))), "pinned counts");
+                uint32_t *h_counts = static_cast<uint32_t *>(B.h_off);
+                uint64_t *h_off[2] = {reinterpret_cast<uint64_t *>(h_counts + 4 * bv), reinterpret_cast<uint64_t *>(h_counts + 4 * bv) + bv};
+                uint8_t *h_rec[2] = {static_cast<uint8_t *>(B.h_rec), static_cast<uint8_t *>(B.h_text2)};
+                setup_s[(size_t)g] = now_s() - t_worker;
+
+                size_t prev_b0 = 0, prev_nv = 0;   // the block in flight on the device
+                auto collect = [&] {
+                    if (!prev_nv) return;
+                    check(pgenhip_wait(B.ctx), "pgenhip_wait");
+                    float ms = 0;
+                    if (pgenhip_timer_read(B.ctx, &ms) == PGENHIP_OK) kernel_s[(size_t)g] += ms * 1e-3;
+                    std::memcpy(counts.data() + 4 * prev_b0, h_counts, prev_nv * 16);
+                    prev_nv = 0;
+                };
+                for (size_t b0 = begin, k = 0; b0 < end; b0 += (size_t)bv, k++) {
+                    const size_t nv = std::min<size_t>((size_t)bv, end - b0);
+                    uint8_t *dst = h_rec[k % 2];
+                    size_t staged = 0;
+                    for (size_t j = 0; j < nv;) {
+                        const uint64_t off0 = record_offset(var_idx_rcds[b0 + j].first);
+                        size_t run = 1;
+                        uint64_t span = R;   // bytes of the file from off0 this run covers
+                        if (vw) {
+                            h_off[k % 2][j] = staged;
+                            while (j + run < nv) {
+                                const uint64_t off = record_offset(var_idx_rcds[b0 + j + run].first);
+                                if (off > off0 + span + R) break;
+                                h_off[k % 2][j + run] = staged + (off - off0);
+                                span = off + R - off0;
+                                run++;
+                            }
+                        } else {
+                            while (j + run < nv && var_idx_rcds[b0 + j + run].first == var_idx_rcds[b0 + j].first + run) run++;
+                            span = (uint64_t)run * R;
+                        }
+                        pread_span(pfd, dst + staged, (size_t)span, off0, pgen, opt.read_threads);
+                        staged += (size_t)span;
+                        j += run;
+                    }
+                    collect();   // block k - 1 has been counted and its counts are back; its pinned records are free again
+                    check(pgenhip_memcpy_h2d(B.ctx, B.d_rec, dst, staged), "H2D records");
+                    if (vw) check(pgenhip_memcpy_h2d(B.ctx, B.d_off, h_off[k % 2], nv * sizeof(uint64_t)), "H2D record offsets");
+                    check(pgenhip_timer_start(B.ctx), "timer");
+                    if (vw)
+                        check(pgenhip_genotype_counts_at(B.ctx, B.d_rec, static_cast<const uint64_t *>(B.d_off), (uint32_t)nv,
+                                                         static_cast<uint32_t *>(B.d_text), PGENHIP_COUNT_AUTO), "pgenhip_genotype_counts_at");
+                    else
+                        check(pgenhip_genotype_counts(B.ctx, B.d_rec, R, nullptr, (uint32_t)nv, static_cast<uint32_t *>(B.d_text), PGENHIP_COUNT_AUTO),
+                              "pgenhip_genotype_counts");
+                    check(pgenhip_timer_mark(B.ctx), "timer");
+                    check(pgenhip_memcpy_d2h(B.ctx, h_counts, B.d_text, nv * 16), "D2H counts");
+                    prev_b0 = b0;
+                    prev_nv = nv;
+                }
+                collect();
+            } catch (const std::exception &e) {
+                std::lock_guard<std::mutex> lk(err_mu);
+                if (err.empty()) err = e.what();
+            }
+        };
+        std::vector<std::thread> threads;
+        for (int g = 1; g < G; g++) threads.emplace_back(worker, g);
+        worker(0);
+        for (auto &t : threads) t.join();
+        if (!err.empty()) throw PfileError(err);
+        st.seconds_kernel = *std::max_element(kernel_s.begin(), kernel_s.end());
+        st.seconds_setup = *std::max_element(setup_s.begin(), setup_s.end());
+    }
+
+    std::string text = "#CHROM\tPOS\tID\tREF\tALT\tHOM_REF_CT\tHET_REF_ALT_CTS\tTWO_ALT_GENO_CTS\tMISSING_CT\n";
+    st.header_bytes = text.size();
+    for (size_t j = 0; j < V; j++) {
+        const StringRecord &r = var_idx_rcds[j].second;
+        for (int c = 0; c < 5; c++) {
+            text += r.at(col[c]);
+            text += '\t';
+        }
+        for (int c = 0; c < 4; c++) {
+            append_u64(text, counts[4 * j + (size_t)c]);
+            text += c < 3 ? '\t' : '\n';
+        }
+    }
+    st.body_bytes = text.size() - st.header_bytes;
+    st.file_bytes = text.size();
+    if (filename.empty()) {
+        if (std::fwrite(text.data(), 1, text.size(), stdout) != text.size() || std::fflush(stdout) != 0)
+            throw PfileError(std::string("write stdout: ") + std::strerror(errno));
+    } else {
+        int fd = open(filename.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (fd < 0) throw PfileError("create " + filename + ": " + std::strerror(errno));
+        pwrite_exact(fd, text.data(), text.size(), 0, filename);
+        if (close(fd) != 0) throw PfileError("close " + filename + ": " + std::strerror(errno));
+    }
+    st.seconds_body = now_s() - t_body;
+    return st;
+}
+
 
 namespace {
 uint64_t splitmix64(uint64_t x)

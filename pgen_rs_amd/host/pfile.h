@@ -91,6 +91,14 @@ class Pfile {
     OutputStats output_vcf(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
                            const std::string &filename, const OutputOptions &opt = OutputOptions()) const;
 
+    // `freq` (not in the reference): per-variant genotype counts of the kept samples, one tab-separated line per kept variant
+    // (CHROM POS ID REF ALT, then the counts of 0/0, 0/1, 1/1 and ./.) behind plink2 .gcount-style column names.  Variant and
+    // sample selection are output_vcf's (filter_metadata); records are staged like output_vcf's and counted on the GPU(s)
+    // (pgenhip_genotype_counts / _at); 16 bytes per variant come back.  filename empty: stdout.
+    // Uses n_gpus, n_shards, block_text_bytes (bytes of records per block), read_threads and filter_threads of `opt`.
+    OutputStats output_freq(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
+                            const std::string &filename, const OutputOptions &opt = OutputOptions()) const;
+
     // the header part of output_vcf (:110-146) on its own: used by output_vcf and by the CPU tests
     std::string vcf_header(const IdxRecords &sam_idx_rcs, const StringRecord &sam_header) const;
 };
