@@ -307,3 +307,43 @@ int pgo_decode_emit_at(const uint8_t *base, const uint64_t *record_off, uint32_t
     }
     return 0;
 }
+
+/* Per-variant genotype counts: src/pfile.rs:171-175 with the GT text of :177-190 replaced by a tally of the code.  The same
+ * literal per-sample loop as pgo_decode_emit (byte s/4, bits 2*(s%4), the kept list or every sample), counted into u64: no
+ * lookup tables, no word-wide masks or popcounts, nothing shared with the count kernel. */
+int pgo_genotype_counts(const uint8_t *records, uint64_t record_stride,
+                        const uint32_t *variant_idx, uint32_t n_variants,
+                        uint32_t num_samples,
+                        const uint32_t *kept_idx, uint32_t kept_count,
+                        uint64_t *counts)
+{
+    uint32_t k_total = kept_idx ? kept_count : num_samples;
+    for (uint32_t j = 0; j < n_variants; j++) {
+        uint64_t row = variant_idx ? (uint64_t)variant_idx[j] : (uint64_t)j;
+        const uint8_t *record_buf = records + row * record_stride;
+        uint64_t tally[4] = {0, 0, 0, 0};
+        for (uint32_t k = 0; k < k_total; k++) {
+            uint32_t sam_idx = kept_idx ? kept_idx[k] : k;            /* :171 */
+            if (sam_idx >= num_samples) return -1;
+            uint32_t sample_offset = sam_idx / 4;                     /* :172 */
+            uint8_t host_byte = record_buf[sample_offset];            /* :173 */
+            uint32_t in_byte_offset = sam_idx % 4;                    /* :174 */
+            uint8_t encoded_genotype = (uint8_t)((host_byte >> (in_byte_offset * 2)) & 0x3); /* :175 */
+            tally[encoded_genotype] += 1;
+        }
+        for (int c = 0; c < 4; c++) counts[4 * (uint64_t)j + (uint64_t)c] = tally[c];
+    }
+    return 0;
+}
+
+/* pgo_genotype_counts on records addressed by byte offset: row j's record starts at base + record_off[j]. */
+int pgo_genotype_counts_at(const uint8_t *base, const uint64_t *record_off, uint32_t n_variants,
+                           uint32_t num_samples, const uint32_t *kept_idx, uint32_t kept_count,
+                           uint64_t *counts)
+{
+    for (uint32_t j = 0; j < n_variants; j++) {
+        int rc = pgo_genotype_counts(base + record_off[j], 0, NULL, 1, num_samples, kept_idx, kept_count, counts + 4 * (uint64_t)j);
+        if (rc) return rc;
+    }
+    return 0;
+}

@@ -3,8 +3,9 @@
  *
  * TEST INFRASTRUCTURE ONLY.  Nothing in the product path (pgen_rs_amd/, the
  * libpgen_hip.so C-ABI, the host CLI) may include, link, dlopen or call this.
- * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use it,
- * and only as the checker / the timed CPU baseline.
+ * Only tests/, __graft_entry__.smoke(), bench.py's cpu_baseline leg and
+ * tools/count_bench.py's sampled check use it, and only as the checker / the
+ * timed CPU baseline.
  *
  * It is a plain-C restatement of the reference's algorithm; every function
  * cites the reference lines (teoremma/pgen-rs, /root/reference) it follows.
@@ -129,6 +130,20 @@ int pgo_vw_index(const pgo_vw_header *h, const uint8_t *file, uint64_t file_len,
 int pgo_decode_emit_at(const uint8_t *base, const uint64_t *record_off, uint32_t n_variants,
                        uint32_t num_samples, const uint32_t *kept_idx, uint32_t kept_count,
                        uint8_t *out, uint64_t out_stride);
+
+/* Per-variant genotype counts (the checker of pgenhip_genotype_counts[_at]): for output row j, selected as in
+ * pgo_decode_emit, counts[4j + c] = the number of kept samples whose code (rec[s/4] >> (s%4*2)) & 3 is c (c = 0 "0/0",
+ * 1 "0/1", 2 "1/1", 3 "./."), i.e. row j's GT text counted.  The same literal per-sample loop as pgo_decode_emit, counted
+ * into u64.  Returns 0, or -1 on a kept index >= num_samples. */
+int pgo_genotype_counts(const uint8_t *records, uint64_t record_stride,
+                        const uint32_t *variant_idx, uint32_t n_variants,
+                        uint32_t num_samples,
+                        const uint32_t *kept_idx, uint32_t kept_count,
+                        uint64_t *counts);
+/* the same on records addressed by BYTE OFFSET: row j's record starts at base + record_off[j] */
+int pgo_genotype_counts_at(const uint8_t *base, const uint64_t *record_off, uint32_t n_variants,
+                           uint32_t num_samples, const uint32_t *kept_idx, uint32_t kept_count,
+                           uint64_t *counts);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,8 @@
 """ctypes wrapper of the CPU oracle (``oracle/libpgen_oracle.so``).
 
-TEST INFRASTRUCTURE ONLY: imported by ``tests/``, ``__graft_entry__.smoke()`` and the
-``cpu_baseline`` leg of ``bench.py`` — never by ``pgen_rs_amd``.  See ``pgen_oracle.h`` for the
+TEST INFRASTRUCTURE ONLY: imported by ``tests/``, ``__graft_entry__.smoke()``, the
+``cpu_baseline`` leg of ``bench.py`` and the check of ``tools/count_bench.py`` — never by ``pgen_rs_amd``.
+ctypes releases the GIL around every call, so tests may split rows over a thread pool.  See ``pgen_oracle.h`` for the
 reference citations and the "parity unpinned" statement.
 """
 from __future__ import annotations
@@ -58,6 +59,10 @@ def _load() -> C.CDLL:
     h.pgo_vw_index.argtypes = [C.POINTER(VwHeader), vp, C.c_uint64, vp, vp, vp]
     h.pgo_decode_emit_at.restype = C.c_int
     h.pgo_decode_emit_at.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, C.c_uint64]
+    h.pgo_genotype_counts.restype = C.c_int
+    h.pgo_genotype_counts.argtypes = [vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp]
+    h.pgo_genotype_counts_at.restype = C.c_int
+    h.pgo_genotype_counts_at.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp]
     return h
 
 
@@ -136,6 +141,46 @@ def emit_lines(records: np.ndarray, n_variants: int, num_samples: int, prefix_bl
     if rc != 0:
         raise ValueError(f"oracle emit_lines failed: {rc}")
     return out[: int(line_off[n_variants])]
+
+
+def genotype_counts(records: np.ndarray, n_variants: int, num_samples: int, kept_idx=None, record_stride: Optional[int] = None,
+                    variant_idx=None, records_offset: int = 0) -> np.ndarray:
+    """Per-variant genotype counts of the kept samples, rows selected as in ``decode_emit``: an ``(n_variants, 4)`` int64
+    array of the number of codes 0..3 (hom-ref, het, hom-alt, missing) — each row's GT text, counted."""
+    records = np.ascontiguousarray(records, dtype=np.uint8)
+    R = variant_record_size(num_samples)
+    if record_stride is None:
+        record_stride = R
+    kept = _u32(kept_idx)
+    K = num_samples if kept is None else int(kept.size)
+    vidx = _u32(variant_idx)
+    if vidx is not None and vidx.size < n_variants:
+        raise ValueError("variant_idx has fewer than n_variants entries")
+    if n_variants:
+        last = int(vidx[:n_variants].max()) if vidx is not None else n_variants - 1
+        if records_offset + last * record_stride + R > records.size:
+            raise ValueError("records too small for the selected rows")
+    out = np.zeros((max(n_variants, 1), 4), dtype=np.uint64)
+    base = records[records_offset:]
+    rc = lib.pgo_genotype_counts(_vp(base), record_stride, _vp(vidx), n_variants, num_samples, _vp(kept), K, _vp(out))
+    if rc != 0:
+        raise IndexError(f"oracle genotype_counts failed: {rc}")
+    return out[:n_variants].astype(np.int64)
+
+
+def genotype_counts_at(base: np.ndarray, record_off, num_samples: int, kept_idx=None) -> np.ndarray:
+    """``genotype_counts`` of the records at byte offsets ``record_off`` of ``base``."""
+    base = np.ascontiguousarray(base, dtype=np.uint8)
+    off = np.ascontiguousarray(np.asarray(record_off, dtype=np.uint64))
+    if off.size and int(off.max()) + variant_record_size(num_samples) > base.size:
+        raise ValueError("a record offset runs past the end of base")
+    kept = _u32(kept_idx)
+    K = num_samples if kept is None else int(kept.size)
+    out = np.zeros((max(off.size, 1), 4), dtype=np.uint64)
+    rc = lib.pgo_genotype_counts_at(_vp(base), _vp(off), off.size, num_samples, _vp(kept), K, _vp(out))
+    if rc != 0:
+        raise IndexError(f"oracle genotype_counts_at failed: {rc}")
+    return out[: off.size].astype(np.int64)
 
 
 def output_vcf_body_file(pgen_path: str, num_samples: int, out_path: str, var_idx=None, n_var: Optional[int] = None,

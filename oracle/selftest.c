@@ -33,6 +33,10 @@ int main(void)
         for (uint32_t j = 0; j < v; j++) CHECK(o[(size_t)j * (4u * k + 1u) + 4u * k] == '\n');
         uint8_t *o2 = malloc((size_t)v * (4u * n + 1u) + 1);
         CHECK(pgo_decode_emit(recs, r, NULL, v, n, NULL, 0, o2, 4u * n + 1u) == 0);
+        uint64_t *cts = malloc(sizeof(uint64_t) * 4u * v);
+        CHECK(pgo_genotype_counts(recs, r, NULL, v, n, kept, k, cts) == 0);
+        for (uint32_t j = 0; j < v; j++) CHECK(cts[4 * j] + cts[4 * j + 1] + cts[4 * j + 2] + cts[4 * j + 3] == k);
+        free(cts);
         free(o2);
         free(o);
         free(kept);

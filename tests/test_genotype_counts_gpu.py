@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+import count_plan as CP
 import pgen_rs_amd
 from helpers import case_names, load_case
 from pgen_rs_amd import _capi
@@ -74,8 +75,9 @@ def test_golden_cases_equal_counted_gt_text(name):
             assert (got == want).all(), f"kernel {kern}"
 
 
-# each shape threshold of the AUTO rule (lanes per row 4 / 8 / 16 / 32 / a wave) +- 1: N = 708, 1476, 3012, 6084 are the last of a class
-N_LIST = [1, 2, 3, 4, 5, 6, 7, 63, 64, 65, 255, 257, 300, 708, 709, 1476, 1477, 2504, 3012, 3013, 6084, 6085, 500_000]
+# each shape threshold of the AUTO rule (lanes per row 4 / 8 / 16 / 32 / a wave) +- 1, from the launch plan's mirror: the last N
+# of a class and the first of the next (708, 1476, 3012, 6084 today; test_count_plan.py pins them to gt_count.hip)
+N_LIST = sorted({1, 2, 3, 4, 5, 6, 7, 63, 64, 65, 255, 257, 300, 2504, 500_000} | {n + d for n in CP.CLASS_EDGES for d in (0, 1)})
 
 
 @pytest.mark.parametrize("n", N_LIST)

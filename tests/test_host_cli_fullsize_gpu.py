@@ -7,7 +7,11 @@ restatement of the reference's file loop (`pgo_output_vcf_body_file`, src/pfile.
 This is the only place that runs the product host's large-file branches: file offsets past 4 GiB through `file_off` /
 `pwrite`, the default 128-MiB block with ~85 blocks, `--write-threads 4`, and (few samples kept: little text per record,
 so a block is bounded by its RECORD bytes) runs of >= 64 MiB read by parallel `pread`s.  The sha256 of the 11.1-GB file is
-pinned in tests/golden/chr22_synth_known.json (the bytes are a pure function of the seeds of SURVEY.md 8(d))."""
+pinned in tests/golden/chr22_synth_known.json (the bytes are a pure function of the seeds of SURVEY.md 8(d)).
+
+`pgen-hip freq` runs on the same triple: all samples with the default blocks, and the KEEP mask with 8-MiB blocks over three
+shards (about 80 blocks through the double-buffered staging).  Its 46-MB table is compared byte for byte with one built from
+the .pgen by the C oracle's counting loop and the synth pvar columns."""
 import hashlib
 import json
 import os
@@ -20,6 +24,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import count_ref as CR
 import pgen_oracle as oracle
 from helpers import GOLDEN
 
@@ -146,3 +151,59 @@ def test_chr22_keep_mask_forces_parallel_preads(chr22):
     digest = compare_with_oracle(chr22, out, kept, block=120_000)
     out.unlink()
     assert digest == KNOWN["keep_mask_1pct"]["sha256"], digest
+
+
+FREQ_HEADER = b"#CHROM\tPOS\tID\tREF\tALT\tHOM_REF_CT\tHET_REF_ALT_CTS\tTWO_ALT_GENO_CTS\tMISSING_CT\n"
+
+
+def expected_freq_table(prefix: Path, kept) -> bytes:
+    """The freq table of the synth triple: the oracle's counts of every record of the .pgen (read from tmpfs) after the synth
+    pvar's CHROM, POS, ID, REF and ALT columns."""
+    recs = np.fromfile(str(prefix) + ".pgen", dtype=np.uint8, offset=12)
+    assert recs.size == V * 626
+    with CR.pool() as ex:
+        cts = CR.oracle_counts_dense(recs.reshape(V, 626), N, {"k": kept}, ex)["k"]
+    k = N if kept is None else len(kept)
+    assert (cts.sum(axis=1) == k).all()
+    return FREQ_HEADER + b"".join(b"22\t%d\tsnp%d\tA\tG\t%d\t%d\t%d\t%d\n" % (16050000 + 7 * i, i, *c) for i, c in enumerate(cts.tolist()))
+
+
+def assert_same_table(got: bytes, want: bytes, what: str):
+    if got == want:
+        return
+    n = min(len(got), len(want))
+    a = np.frombuffer(got, dtype=np.uint8, count=n)
+    b = np.frombuffer(want, dtype=np.uint8, count=n)
+    diff = np.flatnonzero(a != b)
+    first = int(diff[0]) if diff.size else n
+    line = want.count(b"\n", 0, first)
+    g = got[got.rfind(b"\n", 0, first) + 1:].split(b"\n", 1)[0]
+    w = want[want.rfind(b"\n", 0, first) + 1:].split(b"\n", 1)[0]
+    raise AssertionError(f"{what}: differs from line {line} (variant {line - 1}) on: got {g!r}, expected {w!r} "
+                         f"({len(got)} vs {len(want)} bytes)")
+
+
+def test_chr22_freq_all_samples_default_blocks(chr22):
+    out = chr22.parent / "freq_all.tsv"
+    p = subprocess.run([str(CLI), "freq", str(chr22), "-o", str(out), "--stats"], capture_output=True)
+    assert p.returncode == 0, p.stderr
+    stats = json.loads(p.stderr.decode().strip().splitlines()[-1])
+    assert stats["variants_kept"] == V and stats["samples_kept"] == N
+    got = out.read_bytes()
+    out.unlink()
+    assert_same_table(got, expected_freq_table(chr22, None), "freq, all samples")
+
+
+def test_chr22_freq_keep_mask_small_blocks_three_shards(chr22):
+    kept = oracle.synth_keep(N, modulus=100)
+    bv = (8 << 20) // 626
+    assert 3 * (V // 3 // bv) >= 75   # ~28 blocks per shard: the staging's buffer hand-off, many times over
+    out = chr22.parent / "freq_keep.tsv"
+    p = subprocess.run([str(CLI), "freq", str(chr22), "--include-sam", 'KEEP == "1"', "--block-mib", "8", "--shards", "3", "-o", str(out),
+                        "--stats"], capture_output=True)
+    assert p.returncode == 0, p.stderr
+    stats = json.loads(p.stderr.decode().strip().splitlines()[-1])
+    assert stats["variants_kept"] == V and stats["samples_kept"] == len(kept)
+    got = out.read_bytes()
+    out.unlink()
+    assert_same_table(got, expected_freq_table(chr22, kept), "freq, KEEP mask, 8-MiB blocks, 3 shards")
