@@ -30,55 +30,30 @@ using namespace pgenhost;
 
 namespace {
 
-struct Fd {
-    int fd;
-    ~Fd()
-    {
-        if (fd >= 0) close(fd);
-    }
-};
-
-void close_or_throw(Fd &f, const std::string &path)
-{
-    const int fd = f.fd;
-    f.fd = -1;
-    if (close(fd) != 0) throw PfileError("close " + path + ": " + std::strerror(errno));
-}
-
 // --dry-run: the VCF header alone, as text or as a complete BGZF file (header members + EOF marker)
 void write_header_only(const std::string &out_file, const std::string &header, bool bgzf, int level)
 {
-    Fd f{open(out_file.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644)};
-    if (f.fd < 0) throw PfileError("create " + out_file + ": " + std::strerror(errno));
+    Fd f(out_file, O_WRONLY | O_CREAT | O_TRUNC);
     if (bgzf) {
-        BgzfWriter w(f.fd, out_file, level, 1);
+        BgzfWriter w(f.get(), out_file, level, 1);
         w.write(header.data(), header.size());
         w.finish();
     } else {
-        const char *p = header.data();
-        for (size_t left = header.size(); left;) {
-            ssize_t n = write(f.fd, p, left);
-            if (n < 0 && errno == EINTR) continue;
-            if (n <= 0) throw PfileError("write " + out_file + ": " + std::strerror(errno));
-            p += n;
-            left -= (size_t)n;
-        }
+        f.write_all(header.data(), header.size());
     }
-    close_or_throw(f, out_file);
+    f.close();
 }
 
 void bgzf_file(const std::string &in, const std::string &out, int level, unsigned threads, size_t chunk)
 {
-    Fd i{open(in.c_str(), O_RDONLY)};
-    if (i.fd < 0) throw PfileError("open " + in + ": " + std::strerror(errno));
-    Fd o{open(out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644)};
-    if (o.fd < 0) throw PfileError("create " + out + ": " + std::strerror(errno));
-    BgzfWriter w(o.fd, out, level, threads);
+    const Fd i(in, O_RDONLY);
+    Fd o(out, O_WRONLY | O_CREAT | O_TRUNC);
+    BgzfWriter w(o.get(), out, level, threads);
     std::vector<uint8_t> buf(chunk);
     for (;;) {
         size_t got = 0;
         while (got < buf.size()) {
-            ssize_t r = read(i.fd, buf.data() + got, buf.size() - got);
+            ssize_t r = read(i.get(), buf.data() + got, buf.size() - got);
             if (r < 0 && errno == EINTR) continue;
             if (r < 0) throw PfileError("read " + in + ": " + std::strerror(errno));
             if (r == 0) break;
@@ -88,7 +63,7 @@ void bgzf_file(const std::string &in, const std::string &out, int level, unsigne
         w.write(buf.data(), got);
     }
     w.finish();
-    close_or_throw(o, out);
+    o.close();
 }
 
 const char *kUsage =
@@ -204,6 +179,29 @@ Args parse(int argc, char **argv, int first, const std::vector<std::pair<std::st
     return a;
 }
 
+// the options filter and freq share
+OutputOptions output_options(const Args &a)
+{
+    OutputOptions opt;
+    if (auto f = a.get("filter-threads")) opt.filter_threads = std::max(1, std::atoi(f->c_str()));
+    if (auto g = a.get("gpus")) opt.n_gpus = std::max(1, std::atoi(g->c_str()));
+    if (auto sh = a.get("shards")) opt.n_shards = std::max(1, std::atoi(sh->c_str()));
+    if (auto w = a.get("read-threads")) opt.read_threads = std::max(1, std::atoi(w->c_str()));
+    if (auto m = a.get("block-mib")) opt.block_text_bytes = (uint64_t)std::max(1, std::atoi(m->c_str())) << 20;
+    return opt;
+}
+
+// --stats: one JSON line on stderr
+void print_stats(const OutputStats &st, std::chrono::steady_clock::time_point t_main)
+{
+    std::fprintf(stderr,
+                 "{\"variants_kept\": %llu, \"samples_kept\": %llu, \"header_bytes\": %llu, \"body_bytes\": %llu, \"file_bytes\": %llu, "
+                 "\"seconds_filter\": %.6f, \"seconds_body\": %.6f, \"seconds_setup\": %.6f, \"seconds_kernel\": %.6f, \"seconds_main\": %.6f}\n",
+                 (unsigned long long)st.variants, (unsigned long long)st.samples_kept, (unsigned long long)st.header_bytes,
+                 (unsigned long long)st.body_bytes, (unsigned long long)st.file_bytes, st.seconds_filter, st.seconds_body, st.seconds_setup,
+                 st.seconds_kernel, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_main).count());
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -243,17 +241,12 @@ int main(int argc, char **argv)
             const std::string out_file = a.get("out").value_or(pfile.pfile_prefix + (bgzf ? ".pgen-rs.vcf.gz" : ".pgen-rs.vcf"));  // :121-122
             const int bgzf_level = a.get("bgzf-level") ? std::atoi(a.get("bgzf-level")->c_str()) : 6;
             if (bgzf_level < 1 || bgzf_level > 9) usage_error("--bgzf-level takes 1 .. 9");
-            const int filter_threads = a.get("filter-threads") ? std::max(1, std::atoi(a.get("filter-threads")->c_str())) : 0;
+            OutputOptions opt = output_options(a);
             if (a.has("dry-run")) {
                 // header + geometry only: the plumbing of BASELINE config 1 without touching a GPU
-                const std::string psam = read_file(pfile.psam_path());
-                TsvReader psam_reader(psam, Pfile::find_metadata_file_header_start(psam));
-                const StringRecord sam_header = psam_reader.headers();
-                const std::string pvar = read_file(pfile.pvar_path());
-                TsvReader pvar_reader(pvar, Pfile::find_metadata_file_header_start(pvar));
-                const auto vars = Pfile::filter_metadata(pvar_reader, a.get("include-var"), filter_threads);
-                const auto sams = Pfile::filter_metadata(psam_reader, a.get("include-sam"), filter_threads);
-                const std::string header = pfile.vcf_header(sams, sam_header);
+                const Pfile::Selection sel = pfile.select(a.get("include-sam"), a.get("include-var"), opt.filter_threads);
+                const auto &vars = sel.var_idx_rcds, &sams = sel.sam_idx_rcs;
+                const std::string header = pfile.vcf_header(sams, sel.sam_header);
                 write_header_only(out_file, header, bgzf, bgzf_level);
                 unsigned long long prefix = 0;
                 for (const auto &v : vars) {
@@ -265,26 +258,13 @@ int main(int argc, char **argv)
                             vars.size(), sams.size(), header.size(), prefix, body, (unsigned long long)header.size() + body);
                 return 0;
             }
-            OutputOptions opt;
-            opt.filter_threads = filter_threads;
             opt.bgzf = bgzf;
             opt.bgzf_level = bgzf_level;
             if (auto c = a.get("compress-threads")) opt.compress_threads = std::max(1, std::atoi(c->c_str()));
-            if (auto g = a.get("gpus")) opt.n_gpus = std::max(1, std::atoi(g->c_str()));
-            if (auto sh = a.get("shards")) opt.n_shards = std::max(1, std::atoi(sh->c_str()));
             if (auto w = a.get("write-threads")) opt.write_threads = std::max(1, std::atoi(w->c_str()));
-            if (auto w = a.get("read-threads")) opt.read_threads = std::max(1, std::atoi(w->c_str()));
-            if (auto m = a.get("block-mib")) opt.block_text_bytes = (uint64_t)std::max(1, std::atoi(m->c_str())) << 20;
             if (auto m = a.get("launch-mib")) opt.launch_bytes = (uint64_t)std::max(1, std::atoi(m->c_str())) << 20;
             const OutputStats st = pfile.output_vcf(a.get("include-sam"), a.get("include-var"), out_file, opt);  // :123
-            if (a.has("stats")) {
-                std::fprintf(stderr,
-                             "{\"variants_kept\": %llu, \"samples_kept\": %llu, \"header_bytes\": %llu, \"body_bytes\": %llu, "
-                             "\"file_bytes\": %llu, \"seconds_filter\": %.6f, \"seconds_body\": %.6f, \"seconds_setup\": %.6f, \"seconds_kernel\": %.6f, \"seconds_main\": %.6f}\n",
-                             (unsigned long long)st.variants, (unsigned long long)st.samples_kept, (unsigned long long)st.header_bytes,
-                             (unsigned long long)st.body_bytes, (unsigned long long)st.file_bytes, st.seconds_filter, st.seconds_body, st.seconds_setup, st.seconds_kernel,
-                             std::chrono::duration<double>(std::chrono::steady_clock::now() - t_main).count());
-            }
+            if (a.has("stats")) print_stats(st, t_main);
             return 0;
         }
         if (cmd == "freq") {
@@ -292,21 +272,8 @@ int main(int argc, char **argv)
                            {{"stats", 0}});
             if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
-            OutputOptions opt;
-            if (auto f = a.get("filter-threads")) opt.filter_threads = std::max(1, std::atoi(f->c_str()));
-            if (auto g = a.get("gpus")) opt.n_gpus = std::max(1, std::atoi(g->c_str()));
-            if (auto sh = a.get("shards")) opt.n_shards = std::max(1, std::atoi(sh->c_str()));
-            if (auto w = a.get("read-threads")) opt.read_threads = std::max(1, std::atoi(w->c_str()));
-            if (auto m = a.get("block-mib")) opt.block_text_bytes = (uint64_t)std::max(1, std::atoi(m->c_str())) << 20;
-            const OutputStats st = pfile.output_freq(a.get("include-sam"), a.get("include-var"), a.get("out").value_or(""), opt);
-            if (a.has("stats")) {
-                std::fprintf(stderr,
-                             "{\"variants_kept\": %llu, \"samples_kept\": %llu, \"header_bytes\": %llu, \"body_bytes\": %llu, \"file_bytes\": %llu, "
-                             "\"seconds_filter\": %.6f, \"seconds_body\": %.6f, \"seconds_setup\": %.6f, \"seconds_kernel\": %.6f, \"seconds_main\": %.6f}\n",
-                             (unsigned long long)st.variants, (unsigned long long)st.samples_kept, (unsigned long long)st.header_bytes,
-                             (unsigned long long)st.body_bytes, (unsigned long long)st.file_bytes, st.seconds_filter, st.seconds_body, st.seconds_setup,
-                             st.seconds_kernel, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_main).count());
-            }
+            const OutputStats st = pfile.output_freq(a.get("include-sam"), a.get("include-var"), a.get("out").value_or(""), output_options(a));
+            if (a.has("stats")) print_stats(st, t_main);
             return 0;
         }
         if (cmd == "bgzf") {

@@ -102,6 +102,165 @@ void pwrite_exact(int fd, const void *src, size_t bytes, uint64_t offset, const 
     }
 }
 
+// fn(lo, hi) over [0, bytes) cut into n slices, each on a thread of its own (n <= 1: on this thread); the first error is rethrown
+// once every slice has ended
+template <class Fn>
+void split_span(size_t bytes, unsigned n, const Fn &fn)
+{
+    if (n <= 1) return fn(0, bytes);
+    std::vector<std::thread> ts;
+    std::string err;
+    std::mutex mu;
+    const size_t slice = (bytes + n - 1) / n;
+    for (unsigned t = 0; t < n; t++) {
+        const size_t lo = std::min(bytes, (size_t)t * slice), hi = std::min(bytes, lo + slice);
+        if (lo == hi) continue;
+        ts.emplace_back([&, lo, hi] {
+            try {
+                fn(lo, hi);
+            } catch (const std::exception &e) {
+                std::lock_guard<std::mutex> lk(mu);
+                if (err.empty()) err = e.what();
+            }
+        });
+    }
+    for (auto &t : ts) t.join();
+    if (!err.empty()) throw PfileError(err);
+}
+
+// `bytes` of the file at `off` into dst: one pread, or a few at once for long spans (one thread copies ~2-3 GB/s out of the page cache)
+void pread_span(int fd, uint8_t *dst, size_t bytes, uint64_t off, const std::string &path, int read_threads)
+{
+    const unsigned n = bytes >= (64u << 20) ? (unsigned)std::max(1, read_threads) : 1u;
+    split_span(bytes, n, [&](size_t lo, size_t hi) { pread_exact(fd, dst + lo, hi - lo, off + lo, path); });
+}
+
+// the same for writes: parallel pwrite()s of one block measured on tmpfs only fight over the page-allocation lock (8 writers:
+// sys 9.6 s vs 2.3 s, wall unchanged), so the default is one writer
+void pwrite_span(int fd, const uint8_t *src, size_t bytes, uint64_t off, const std::string &path, int write_threads)
+{
+    const unsigned n = bytes >= (8u << 20) ? (unsigned)std::max(1, write_threads) : 1u;
+    split_span(bytes, n, [&](size_t lo, size_t hi) { pwrite_exact(fd, src + lo, hi - lo, off + lo, path); });
+}
+
+// runs f when it goes out of scope
+template <class F>
+struct OnExit {
+    F f;
+    ~OnExit() { f(); }
+};
+template <class F>
+OnExit(F) -> OnExit<F>;
+
+struct KeptSamples {
+    std::vector<uint32_t> rows;
+    bool all;   // every row kept: the K = N fast path
+};
+
+// The kept sample rows (:173: a row past the .pgen's samples is the reference's index panic) and a check of every kept variant
+// row: past the .pgen's records, or (variable-width files) not stored as a plain 2-bit record of R bytes, the only kind that can
+// take the path of :165-190
+KeptSamples check_selection(const Pfile &pf, const Pfile::Selection &sel)
+{
+    const uint32_t N = pf.num_samples, R = pf.variant_record_size();
+    KeptSamples kept;
+    kept.rows.reserve(sel.sam_idx_rcs.size());
+    for (const auto &ir : sel.sam_idx_rcs) {
+        if (ir.first >= N) throw PfileError("index out of bounds: sample row " + std::to_string(ir.first) + " but the .pgen holds " + std::to_string(N) + " samples");
+        kept.rows.push_back((uint32_t)ir.first);
+    }
+    kept.all = kept.rows.size() == (size_t)N;
+    for (const auto &vr : sel.var_idx_rcds) {
+        const size_t vi = vr.first;
+        if (vi >= pf.num_variants)
+            throw PfileError("variant row " + std::to_string(vi) + " is past the " + std::to_string(pf.num_variants) + " records of " + pf.pgen_path());
+        if (pf.variable_width() && ((*pf.vw_record_type)[vi] != 0 || (*pf.vw_record_len)[vi] != R))
+            throw PfileError(pf.pgen_path() + ": variant row " + std::to_string(vi) + " is stored compressed (record type " +
+                             std::to_string((*pf.vw_record_type)[vi]) + ", " + std::to_string((*pf.vw_record_len)[vi]) + " bytes); only uncompressed 2-bit records are supported");
+    }
+    return kept;
+}
+
+// One ctx and the device and pinned buffers allocated through it.  The destructor frees the pinned buffers, then the device
+// buffers, each in the order of allocation, and destroys the ctx last.
+class DeviceCtx {
+  public:
+    // kept: null (or every sample) decodes all samples
+    DeviceCtx(int device, uint32_t n_samples, const KeptSamples *kept = nullptr)
+    {
+        const bool all = !kept || kept->all;
+        // a filter that kept NOBODY is an empty list, not "all samples": say so with the flag (rows.data() is NULL then)
+        check(pgenhip_create(&ctx_, device, n_samples, all ? nullptr : kept->rows.data(), kept ? (uint32_t)kept->rows.size() : 0u,
+                             all ? 0u : PGENHIP_CREATE_KEEP_LIST), "pgenhip_create");
+    }
+    DeviceCtx(const DeviceCtx &) = delete;
+    DeviceCtx &operator=(const DeviceCtx &) = delete;
+    ~DeviceCtx()
+    {
+        for (void *p : pinned_) pgenhip_host_free_pinned(ctx_, p);
+        for (void *p : device_) pgenhip_device_free(ctx_, p);
+        pgenhip_destroy(ctx_);
+    }
+    pgenhip_ctx *get() const { return ctx_; }
+    template <class T>
+    T *device(size_t bytes, const char *what)
+    {
+        void *p = nullptr;
+        check(pgenhip_device_malloc(ctx_, &p, bytes), what);
+        device_.push_back(p);
+        return static_cast<T *>(p);
+    }
+    template <class T>
+    T *pinned(size_t bytes, const char *what)
+    {
+        void *p = nullptr;
+        check(pgenhip_host_malloc_pinned(ctx_, &p, bytes), what);
+        pinned_.push_back(p);
+        return static_cast<T *>(p);
+    }
+
+  private:
+    pgenhip_ctx *ctx_ = nullptr;
+    std::vector<void *> device_, pinned_;
+};
+
+// The variant shards of a run: opt.n_shards contiguous ranges of the kept-variant list (0: one per device used), dealt round-robin
+// over the devices.  run() calls fn(g, device, begin, end) for every non-empty shard, each on a thread of its own and shard 0 on
+// the calling thread, and rethrows the first error once every shard has ended.
+struct Shards {
+    int n_use, G;   // devices used, shards
+    Shards(const OutputOptions &opt, const char *no_device)
+    {
+        int n_dev = 0;
+        check(pgenhip_device_count(&n_dev), "pgenhip_device_count");
+        if (n_dev <= 0) throw PfileError(no_device);
+        n_use = std::max(1, std::min(opt.n_gpus, n_dev));
+        G = opt.n_shards > 0 ? opt.n_shards : n_use;
+    }
+    template <class Fn>
+    void run(size_t V, const Fn &fn) const
+    {
+        std::string err;
+        std::mutex mu;
+        auto worker = [&](int g) {
+            try {
+                // sizes differ by <= 1: the one partitioner
+                uint64_t begin = 0, end = 0;
+                check(pgenhip_shard_range(V, (uint32_t)G, (uint32_t)g, &begin, &end), "pgenhip_shard_range");
+                if (begin != end) fn(g, g % n_use, (size_t)begin, (size_t)end);
+            } catch (const std::exception &e) {
+                std::lock_guard<std::mutex> lk(mu);
+                if (err.empty()) err = e.what();
+            }
+        };
+        std::vector<std::thread> threads;
+        for (int g = 1; g < G; g++) threads.emplace_back(worker, g);
+        worker(0);
+        for (auto &t : threads) t.join();
+        if (!err.empty()) throw PfileError(err);
+    }
+};
+
 }  // namespace
 
 std::string read_file(const std::string &path)
@@ -119,12 +278,8 @@ Pfile Pfile::from_prefix(const std::string &pfile_prefix)
     Pfile pf;
     pf.pfile_prefix = pfile_prefix;
     const std::string path = pf.pgen_path();
-    int fd = open(path.c_str(), O_RDONLY);
-    if (fd < 0) throw PfileError("open " + path + ": " + std::strerror(errno));  // :41
-    struct FdCloser {
-        int fd;
-        ~FdCloser() { close(fd); }
-    } closer{fd};
+    const Fd file(path, O_RDONLY);  // :41
+    const int fd = file.get();
     uint8_t hdr[12];
     ssize_t got = pread(fd, hdr, sizeof hdr, 0);
     if (got != (ssize_t)sizeof hdr) throw PfileError("read " + path + ": failed to fill whole buffer");  // :45 read_exact
@@ -302,6 +457,20 @@ Pfile::IdxRecords Pfile::filter_metadata(TsvReader &reader, const std::optional<
     return all;
 }
 
+Pfile::Selection Pfile::select(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query, int filter_threads) const
+{
+    Selection sel;
+    const std::string psam = read_file(psam_path());  // :111
+    TsvReader psam_reader(psam, find_metadata_file_header_start(psam));
+    sel.sam_header = psam_reader.headers();  // :112
+    const std::string pvar = read_file(pvar_path());
+    TsvReader pvar_reader(pvar, find_metadata_file_header_start(pvar));
+    sel.var_header = pvar_reader.headers();
+    sel.var_idx_rcds = filter_metadata(pvar_reader, var_query, filter_threads);  // :127
+    sel.sam_idx_rcs = filter_metadata(psam_reader, sam_query, filter_threads);   // :128
+    return sel;
+}
+
 void Pfile::query_metadata(TsvReader &reader, const std::optional<std::string> &query, const std::string &f_string, std::string &out)
 {
     std::optional<Expr> filter;
@@ -345,30 +514,6 @@ std::string Pfile::vcf_header(const IdxRecords &sam_idx_rcs, const StringRecord 
     return h;
 }
 
-namespace {
-
-struct DeviceBuffers {
-    pgenhip_ctx *ctx = nullptr;
-    void *h_rec = nullptr, *h_blob = nullptr, *h_off = nullptr, *h_text = nullptr, *h_text2 = nullptr;
-    void *d_rec = nullptr, *d_blob = nullptr, *d_off = nullptr, *d_text = nullptr;
-    ~DeviceBuffers()
-    {
-        if (!ctx) return;
-        pgenhip_host_free_pinned(ctx, h_rec);
-        pgenhip_host_free_pinned(ctx, h_blob);
-        pgenhip_host_free_pinned(ctx, h_off);
-        pgenhip_host_free_pinned(ctx, h_text);
-        pgenhip_host_free_pinned(ctx, h_text2);
-        pgenhip_device_free(ctx, d_rec);
-        pgenhip_device_free(ctx, d_blob);
-        pgenhip_device_free(ctx, d_off);
-        pgenhip_device_free(ctx, d_text);
-        pgenhip_destroy(ctx);
-    }
-};
-
-}  // namespace
-
 // :104-194
 OutputStats Pfile::output_vcf(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
                               const std::string &filename, const OutputOptions &opt) const
@@ -386,38 +531,16 @@ OutputStats Pfile::output_vcf(const std::optional<std::string> &sam_query, const
             if (pgenhip_create(&c, d, 4, nullptr, 0, 0) == PGENHIP_OK) pgenhip_destroy(c);
         }
     });
-    struct WarmUpJoin {
-        std::thread &t;
-        ~WarmUpJoin()
-        {
-            if (t.joinable()) t.join();
-        }
-    } warm_up_join{hip_warm_up};
-    const std::string psam = read_file(psam_path());  // :111
-    TsvReader psam_reader(psam, find_metadata_file_header_start(psam));
-    const StringRecord sam_header = psam_reader.headers();  // :112
-    const std::string pvar = read_file(pvar_path());
-    TsvReader pvar_reader(pvar, find_metadata_file_header_start(pvar));
-    const IdxRecords var_idx_rcds = filter_metadata(pvar_reader, var_query, opt.filter_threads);  // :127
-    const IdxRecords sam_idx_rcs = filter_metadata(psam_reader, sam_query, opt.filter_threads);   // :128
-    const std::string header = vcf_header(sam_idx_rcs, sam_header);
+    OnExit warm_up_join{[&] {
+        if (hip_warm_up.joinable()) hip_warm_up.join();
+    }};
+    const Selection sel = select(sam_query, var_query, opt.filter_threads);
+    const IdxRecords &var_idx_rcds = sel.var_idx_rcds;
+    const std::string header = vcf_header(sel.sam_idx_rcs, sel.sam_header);
     st.seconds_filter = now_s() - t0;
 
-    int fd = open(filename.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);  // :136 File::create
-    if (fd < 0) throw PfileError("create " + filename + ": " + std::strerror(errno));
-    struct FdGuard {
-        int fd;
-        ~FdGuard()
-        {
-            if (fd >= 0) close(fd);
-        }
-    } guard{fd};
-    // a short or failed close (ENOSPC/EIO surfacing late) must not leave a truncated VCF behind an exit code 0
-    auto close_checked = [&] {
-        const int cfd = guard.fd;
-        guard.fd = -1;
-        if (close(cfd) != 0) throw PfileError("close " + filename + ": " + std::strerror(errno));
-    };
+    Fd out(filename, O_WRONLY | O_CREAT | O_TRUNC);  // :136 File::create
+    const int fd = out.get();
     const unsigned n_compress = (unsigned)(opt.compress_threads > 0 ? opt.compress_threads : std::min(32u, std::max(1u, std::thread::hardware_concurrency())));
     if (opt.bgzf) {
         BgzfWriter hw(fd, filename, opt.bgzf_level, 1);
@@ -427,31 +550,31 @@ OutputStats Pfile::output_vcf(const std::optional<std::string> &sam_query, const
         pwrite_exact(fd, header.data(), header.size(), 0, filename);  // :139-146
     }
     // BGZF: every member is independent, so the shards' streams simply follow each other; shard 0 appends to the file itself, the
-    // others to temporary files that are appended in shard order at the end (one device: no temporary file)
-    auto shard_tmp = [&](int g) { return filename + ".shard" + std::to_string(g) + ".tmp"; };
-    auto finish_bgzf = [&](int n_shards) {
+    // others to temporary files that are appended in shard order at the end (one device: no temporary file).  A shard creates its
+    // file with O_EXCL after every name has been unlinked, so nothing found at a name is followed or appended, and every file this
+    // run created is unlinked on the way out.
+    auto shard_tmp = [&](size_t g) { return filename + ".shard" + std::to_string(g) + ".tmp"; };
+    std::vector<char> tmp_made;   // per shard: its temporary file exists
+    OnExit unlink_tmps{[&] {
+        for (size_t g = 1; g < tmp_made.size(); g++)
+            if (tmp_made[g]) unlink(shard_tmp(g).c_str());
+    }};
+    auto finish_bgzf = [&] {
         std::vector<uint8_t> buf(8u << 20);
-        for (int g = 1; g < n_shards; g++) {
+        for (size_t g = 1; g < tmp_made.size(); g++) {
+            if (!tmp_made[g]) continue;   // a shard without variants made none
             const std::string tmp = shard_tmp(g);
-            int tfd = open(tmp.c_str(), O_RDONLY);
-            if (tfd < 0) continue;   // a shard without variants wrote nothing
+            const Fd in(tmp, O_RDONLY);
             for (;;) {
-                ssize_t r = read(tfd, buf.data(), buf.size());
+                ssize_t r = read(in.get(), buf.data(), buf.size());
                 if (r < 0 && errno == EINTR) continue;
-                if (r < 0) { close(tfd); throw PfileError("read " + tmp + ": " + std::strerror(errno)); }
+                if (r < 0) throw PfileError("read " + tmp + ": " + std::strerror(errno));
                 if (r == 0) break;
-                const uint8_t *p = buf.data();
-                for (size_t left = (size_t)r; left;) {
-                    ssize_t w = write(fd, p, left);
-                    if (w < 0 && errno == EINTR) continue;
-                    if (w <= 0) { close(tfd); throw PfileError("write " + filename + ": " + std::strerror(errno)); }
-                    p += w;
-                    left -= (size_t)w;
-                }
+                out.write_all(buf.data(), (size_t)r);
                 st.file_bytes += (uint64_t)r;
             }
-            close(tfd);
             unlink(tmp.c_str());
+            tmp_made[g] = 0;
         }
         BgzfWriter ew(fd, filename, opt.bgzf_level, 1);
         ew.finish();
@@ -459,17 +582,10 @@ OutputStats Pfile::output_vcf(const std::optional<std::string> &sam_query, const
     };
 
     // ---- geometry of the body (:156-192): line j = prefix_j + K x "\tA/B" + "\n"
-    const uint32_t N = num_samples;
+    const KeptSamples kept = check_selection(*this, sel);
     const uint32_t R = variant_record_size();
     const size_t V = var_idx_rcds.size();
-    std::vector<uint32_t> kept;
-    kept.reserve(sam_idx_rcs.size());
-    for (const auto &ir : sam_idx_rcs) {
-        if (ir.first >= N) throw PfileError("index out of bounds: sample row " + std::to_string(ir.first) + " but the .pgen holds " + std::to_string(N) + " samples");  // :173
-        kept.push_back((uint32_t)ir.first);
-    }
-    const bool all_samples = kept.size() == (size_t)N;  // every row kept: the K = N fast path
-    const uint64_t K = kept.size();
+    const uint64_t K = kept.rows.size();
     std::vector<uint64_t> file_off(V + 1, 0);  // body-relative offset of each line
     uint64_t max_prefix = 0;
     for (size_t j = 0; j < V; j++) {
@@ -477,355 +593,262 @@ OutputStats Pfile::output_vcf(const std::optional<std::string> &sam_query, const
         for (const auto &col : var_idx_rcds[j].second) plen += col.size() + 1;  // col + '\t' (:157-160)
         max_prefix = std::max(max_prefix, plen);
         file_off[j + 1] = file_off[j] + plen + 4ull * K + 1ull;
-        if (var_idx_rcds[j].first >= num_variants)
-            throw PfileError("variant row " + std::to_string(var_idx_rcds[j].first) + " is past the " + std::to_string(num_variants) + " records of " + pgen_path());
-        if (variable_width()) {
-            // only records stored as plain 2-bit hard calls (type 0, length R) can take the path of :165-190; anything else is reported
-            const size_t vi = var_idx_rcds[j].first;
-            if ((*vw_record_type)[vi] != 0 || (*vw_record_len)[vi] != R)
-                throw PfileError(pgen_path() + ": variant row " + std::to_string(vi) + " is stored compressed (record type " +
-                                 std::to_string((*vw_record_type)[vi]) + ", " + std::to_string((*vw_record_len)[vi]) + " bytes); only uncompressed 2-bit records are supported");
-        }
     }
+    const uint64_t max_line = max_prefix + 4ull * K + 1ull;
     st.variants = V;
     st.samples_kept = K;
     st.header_bytes = header.size();
     st.body_bytes = file_off[V];
     if (!opt.bgzf) st.file_bytes = st.header_bytes + st.body_bytes;
     if (V == 0) {
-        if (opt.bgzf) finish_bgzf(0);
-        close_checked();
+        if (opt.bgzf) finish_bgzf();
+        out.close();
         return st;
     }
 
     if (hip_warm_up.joinable()) hip_warm_up.join();
-    int n_dev = 0;
-    check(pgenhip_device_count(&n_dev), "pgenhip_device_count");
-    if (n_dev <= 0) throw PfileError("no HIP device: the GT decode/emit path has no CPU fallback");
-    const int n_use = std::max(1, std::min(opt.n_gpus, n_dev));      // devices actually used
-    const int G = opt.n_shards > 0 ? opt.n_shards : n_use;            // variant ranges (shards)
+    const Shards shards(opt, "no HIP device: the GT decode/emit path has no CPU fallback");
+    const size_t G = (size_t)shards.G;
     const double t_body = now_s();
-    std::mutex err_mu;
-    std::string err;
-    std::vector<double> kernel_s((size_t)G, 0.0), setup_s((size_t)G, 0.0);
-    std::vector<uint64_t> shard_out((size_t)G, 0);   // BGZF: compressed bytes per shard
+    std::vector<double> kernel_s(G, 0.0), setup_s(G, 0.0);
+    std::vector<uint64_t> shard_out(G, 0);   // BGZF: compressed bytes per shard
+    if (opt.bgzf) {
+        for (size_t g = 1; g < G; g++) unlink(shard_tmp(g).c_str());
+        tmp_made.assign(G, 0);
+    }
     const std::string pgen = pgen_path();
+    const unsigned compress_threads = std::max(1u, n_compress / (unsigned)std::max(1, std::min(shards.G, shards.n_use)));
 
-    // Per device: two buffer sets, each with its own ctx/stream.  The producer (this thread) reads
-    // records + builds prefixes for block k and queues H2D -> kernel -> D2H on set k%2; a consumer
-    // thread waits for that set, writes its text with a few parallel pwrite()s at the precomputed
-    // file offset, and hands the set back.  File staging, PCIe copies, the kernel and the file
-    // writes of neighbouring blocks overlap.
-    // parallel pwrite()s of one block: measured on tmpfs they only fight over the page-allocation lock
-    // (8 writers: sys 9.6 s vs 2.3 s, wall unchanged), so the default is one writer per device
-    const unsigned n_writers = (unsigned)std::max(1, opt.write_threads);
+    // Per shard: two buffer sets, each with its own ctx/stream.  The producer (the shard's thread) reads records + builds prefixes
+    // for block k and queues H2D -> kernel -> D2H on set k%2; a consumer thread waits for that set, writes its text at the
+    // precomputed file offset, and hands the set back.  File staging, PCIe copies, the kernel and the file writes of neighbouring
+    // blocks overlap.
+    shards.run(V, [&](int g, int device, size_t begin, size_t end) {
+        const double t_worker = now_s();
+        const Fd pgen_fd(pgen, O_RDONLY);  // :149 (unbuffered on purpose, :150-152)
+        // BGZF: this shard's ordered, parallel deflate writer (shard 0: the output file behind the header; others: a temporary file)
+        std::optional<Fd> tmp;
+        std::optional<BgzfWriter> zw;
+        if (opt.bgzf && g > 0) {
+            tmp.emplace(shard_tmp((size_t)g), O_WRONLY | O_CREAT | O_EXCL);
+            tmp_made[(size_t)g] = 1;
+        }
+        if (opt.bgzf) zw.emplace(tmp ? tmp->get() : fd, tmp ? shard_tmp((size_t)g) : filename, opt.bgzf_level, compress_threads);
 
-    auto worker = [&](int g) {
-        try {
-            const double t_worker = now_s();
-            // contiguous range of the kept-variant list per device, sizes differ by <= 1: the one partitioner
-            uint64_t begin64 = 0, end64 = 0;
-            check(pgenhip_shard_range(V, (uint32_t)G, (uint32_t)g, &begin64, &end64), "pgenhip_shard_range");
-            const size_t begin = (size_t)begin64, end = (size_t)end64;
-            if (begin == end) return;
-            int pfd = open(pgen.c_str(), O_RDONLY);  // :149 (unbuffered on purpose, :150-152)
-            if (pfd < 0) throw PfileError("open " + pgen + ": " + std::strerror(errno));
-            FdGuard pg{pfd};
-            // BGZF: this shard's ordered, parallel deflate writer (shard 0: the output file behind the header; others: a temporary file)
-            int zfd = -1;
-            if (opt.bgzf) {
-                zfd = g == 0 ? fd : open(shard_tmp(g).c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-                if (zfd < 0) throw PfileError("create " + shard_tmp(g) + ": " + std::strerror(errno));
-            }
-            FdGuard zg{g == 0 ? -1 : zfd};
-            std::unique_ptr<BgzfWriter> zw;
-            if (opt.bgzf) zw.reset(new BgzfWriter(zfd, g == 0 ? filename : shard_tmp(g), opt.bgzf_level, std::max(1u, n_compress / (unsigned)std::max(1, std::min(G, n_use)))));
-            // variants per block: bounded by the text budget — and by the same budget of RECORD bytes, so that a run that keeps few
-            // samples (little text per record) still moves in several blocks and its file reads overlap the copies and the kernel
-            const uint64_t max_line = max_prefix + 4ull * K + 1ull;
-            const uint64_t bv = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(opt.block_text_bytes / max_line, opt.block_text_bytes / std::max<uint32_t>(R, 1u)), end - begin));
-            const size_t n_blocks = (end - begin + (size_t)bv - 1) / (size_t)bv;
-            // A block is the unit of file staging, of the D2H copy and of the file write.  A LAUNCH covers several consecutive blocks
-            // (up to the launch budget of text or record bytes): its records are staged block by block while the blocks of the launch
-            // before it are copied out and written, so the host pipeline keeps the cadence of small blocks and the kernel sees launches
-            // of up to 2 GiB (a 128-MiB launch of the chr22 shape is two work items deep: 39 us where its share of a large launch costs
-            // 25 us, profiles/r03_cli_kernels.md).  Launch sizes ramp 1, 2, 4, ... blocks so the first byte leaves as early as before.
-            const uint64_t blocks_per_launch_max = std::max<uint64_t>(1, std::min<uint64_t>(opt.launch_bytes / std::max<uint64_t>(1, std::max<uint64_t>(bv * max_line, bv * R)), n_blocks));
-            struct LaunchPlan {
-                size_t first_block, n_blocks;
-            };
-            std::vector<LaunchPlan> plan;
-            size_t widest = 1;
-            for (size_t k = 0, step = 1; k < n_blocks; step = (size_t)std::min<uint64_t>(2 * (uint64_t)step, blocks_per_launch_max)) {
-                const size_t n = (size_t)std::min<uint64_t>(std::min<uint64_t>(step, blocks_per_launch_max), n_blocks - k);
-                plan.push_back(LaunchPlan{k, n});
-                widest = std::max(widest, n);
-                k += n;
-            }
-            const uint64_t lv = std::min<uint64_t>(bv * widest, end - begin);   // variants of the widest launch
-            const size_t rec_bytes = (size_t)(bv * R), blob_bytes = (size_t)(bv * max_prefix), text_bytes = (size_t)(bv * max_line);
-            const size_t off_bytes = (size_t)(2 * (bv + 1) * sizeof(uint64_t));
-            const int n_sets = plan.size() > 1 ? 2 : 1;     // device-side sets (one launch each), each with its own ctx / stream
-            const int n_text = n_blocks > 1 ? 2 : 1;        // pinned text buffers (one block each)
-            DeviceBuffers sets[2];
-            void *h_text[2] = {nullptr, nullptr};
-            for (int s = 0; s < n_sets; s++) {
-                DeviceBuffers &B = sets[s];
-                // a filter that kept NOBODY is an empty list, not "all samples": say so with the flag (kept.data() is NULL then)
-                check(pgenhip_create(&B.ctx, g % n_use, N, all_samples ? nullptr : kept.data(), (uint32_t)K,
-                                     all_samples ? 0u : PGENHIP_CREATE_KEEP_LIST), "pgenhip_create");
-                check(pgenhip_device_malloc(B.ctx, &B.d_rec, (size_t)(lv * R)), "device records");
-                check(pgenhip_device_malloc(B.ctx, &B.d_blob, (size_t)(lv * max_prefix)), "device prefixes");
-                check(pgenhip_device_malloc(B.ctx, &B.d_off, (size_t)(2 * (lv + 1) * sizeof(uint64_t))), "device offsets");
-                check(pgenhip_device_malloc(B.ctx, &B.d_text, (size_t)(lv * max_line)), "device text");
-            }
-            // pinned staging: ONE set of input buffers (each block's H2D is waited for before the next block is staged) ...
-            check(pgenhip_host_malloc_pinned(sets[0].ctx, &sets[0].h_rec, rec_bytes), "pinned records");
-            check(pgenhip_host_malloc_pinned(sets[0].ctx, &sets[0].h_blob, blob_bytes), "pinned prefixes");
-            check(pgenhip_host_malloc_pinned(sets[0].ctx, &sets[0].h_off, off_bytes), "pinned offsets");
-            // ... and two text buffers (freed with the sets: DeviceBuffers owns h_text)
-            for (int t = 0; t < n_text; t++) {
-                check(pgenhip_host_malloc_pinned(sets[0].ctx, &h_text[t], text_bytes), "pinned text");
-                (t == 0 ? sets[0].h_text : sets[0].h_text2) = h_text[t];
-            }
-            struct InFlight {
-                int text;      // pinned text buffer
-                int set;       // device set (stream) the copy was queued on
-                bool first;    // first block of its launch: the kernel's time is read here
-                size_t b0;
-                uint64_t bytes;
-            };
-            std::mutex mu;
-            std::condition_variable cv;
-            std::deque<InFlight> inflight;
-            bool text_busy[2] = {false, false};
-            uint64_t pushed[2] = {0, 0}, consumed[2] = {0, 0};   // blocks per device set
-            bool producer_done = false;
-            std::string consumer_err;
+        // ---- block and launch plan
+        // variants per block: bounded by the text budget — and by the same budget of RECORD bytes, so that a run that keeps few
+        // samples (little text per record) still moves in several blocks and its file reads overlap the copies and the kernel
+        const uint64_t bv = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(opt.block_text_bytes / max_line, opt.block_text_bytes / std::max<uint32_t>(R, 1u)), end - begin));
+        const size_t n_blocks = (end - begin + (size_t)bv - 1) / (size_t)bv;
+        // A block is the unit of file staging, of the D2H copy and of the file write.  A LAUNCH covers several consecutive blocks
+        // (up to the launch budget of text or record bytes): its records are staged block by block while the blocks of the launch
+        // before it are copied out and written, so the host pipeline keeps the cadence of small blocks and the kernel sees launches
+        // of up to 2 GiB (a 128-MiB launch of the chr22 shape is two work items deep: 39 us where its share of a large launch costs
+        // 25 us, profiles/r03_cli_kernels.md).  Launch sizes ramp 1, 2, 4, ... blocks so the first byte leaves as early as before.
+        const uint64_t blocks_per_launch_max = std::max<uint64_t>(1, std::min<uint64_t>(opt.launch_bytes / std::max<uint64_t>(1, std::max<uint64_t>(bv * max_line, bv * R)), n_blocks));
+        struct LaunchPlan {
+            size_t first_block, n_blocks;
+        };
+        std::vector<LaunchPlan> plan;
+        size_t widest = 1;
+        for (size_t k = 0, step = 1; k < n_blocks; step = (size_t)std::min<uint64_t>(2 * (uint64_t)step, blocks_per_launch_max)) {
+            const size_t n = (size_t)std::min<uint64_t>(std::min<uint64_t>(step, blocks_per_launch_max), n_blocks - k);
+            plan.push_back(LaunchPlan{k, n});
+            widest = std::max(widest, n);
+            k += n;
+        }
+        const uint64_t lv = std::min<uint64_t>(bv * widest, end - begin);   // variants of the widest launch
+        auto launch_b0 = [&](size_t u) { return begin + plan[u].first_block * (size_t)bv; };
+        auto launch_nv = [&](size_t u) { return std::min<size_t>(plan[u].n_blocks * (size_t)bv, end - launch_b0(u)); };
 
-            std::thread consumer([&] {
-                try {
-                    for (;;) {
-                        InFlight job;
-                        {
-                            std::unique_lock<std::mutex> lk(mu);
-                            cv.wait(lk, [&] { return !inflight.empty() || producer_done; });
-                            if (inflight.empty()) return;
-                            job = inflight.front();
-                            inflight.pop_front();
-                        }
-                        DeviceBuffers &B = sets[job.set];
-                        check(pgenhip_wait(B.ctx), "pgenhip_wait");
-                        float ms = 0;
-                        if (job.first && pgenhip_timer_read(B.ctx, &ms) == PGENHIP_OK) kernel_s[(size_t)g] += ms * 1e-3;
-                        // every line has a known length, so ranges land at precomputed offsets in any order
-                        const uint64_t file_pos = header.size() + file_off[job.b0];
-                        const uint8_t *text = static_cast<const uint8_t *>(h_text[job.text]);
-                        if (zw) {
-                            zw->write(text, (size_t)job.bytes);   // blocks arrive in order: the members are appended in order
-                        } else if (n_writers <= 1 || job.bytes < (8ull << 20)) {
-                            pwrite_exact(fd, text, (size_t)job.bytes, file_pos, filename);
-                        } else {
-                            std::vector<std::thread> ws;
-                            std::string werr;
-                            std::mutex wmu;
-                            const uint64_t slice = (job.bytes + n_writers - 1) / n_writers;
-                            for (unsigned t = 0; t < n_writers; t++) {
-                                const uint64_t lo = std::min<uint64_t>((uint64_t)t * slice, job.bytes), hi = std::min<uint64_t>(lo + slice, job.bytes);
-                                if (lo == hi) continue;
-                                ws.emplace_back([&, lo, hi] {
-                                    try {
-                                        pwrite_exact(fd, text + lo, (size_t)(hi - lo), file_pos + lo, filename);
-                                    } catch (const std::exception &e) {
-                                        std::lock_guard<std::mutex> lk(wmu);
-                                        werr = e.what();
-                                    }
-                                });
-                            }
-                            for (auto &t : ws) t.join();
-                            if (!werr.empty()) throw PfileError(werr);
-                        }
-                        {
-                            std::lock_guard<std::mutex> lk(mu);
-                            text_busy[job.text] = false;
-                            consumed[job.set]++;
-                        }
-                        cv.notify_all();
+        // ---- buffers: device sets (one launch each) with their own ctx / stream, sized for the widest launch
+        const int n_sets = plan.size() > 1 ? 2 : 1;
+        const int n_text = n_blocks > 1 ? 2 : 1;   // pinned text buffers (one block each)
+        struct DeviceSet {
+            pgenhip_ctx *ctx;
+            uint8_t *rec;
+            char *blob;
+            uint64_t *poff, *loff;   // prefix and line offsets of the launch
+            uint8_t *text;
+        };
+        std::optional<DeviceCtx> ctxs[2];
+        DeviceSet sets[2] = {};
+        for (int s = 0; s < n_sets; s++) {
+            DeviceCtx &c = ctxs[s].emplace(device, num_samples, &kept);
+            sets[s].ctx = c.get();
+            sets[s].rec = c.device<uint8_t>((size_t)(lv * R), "device records");
+            sets[s].blob = c.device<char>((size_t)(lv * max_prefix), "device prefixes");
+            sets[s].poff = c.device<uint64_t>((size_t)(2 * (lv + 1) * sizeof(uint64_t)), "device offsets");
+            sets[s].loff = sets[s].poff + (lv + 1);
+            sets[s].text = c.device<uint8_t>((size_t)(lv * max_line), "device text");
+        }
+        // pinned staging through set 0's ctx: ONE set of input buffers (each block's H2D is waited for before the next block is
+        // staged) and the text buffers
+        uint8_t *h_rec = ctxs[0]->pinned<uint8_t>((size_t)(bv * R), "pinned records");
+        char *h_blob = ctxs[0]->pinned<char>((size_t)(bv * max_prefix), "pinned prefixes");
+        uint64_t *h_poff = ctxs[0]->pinned<uint64_t>((size_t)(2 * (bv + 1) * sizeof(uint64_t)), "pinned offsets");
+        uint64_t *h_loff = h_poff + (bv + 1);
+        uint8_t *h_text[2] = {nullptr, nullptr};
+        for (int t = 0; t < n_text; t++) h_text[t] = ctxs[0]->pinned<uint8_t>((size_t)(bv * max_line), "pinned text");
+
+        // ---- consumer: waits for a block's D2H copy, writes its text and hands the text buffer back
+        struct InFlight {
+            int text;      // pinned text buffer
+            int set;       // device set (stream) the copy was queued on
+            bool first;    // first block of its launch: the kernel's time is read here
+            size_t b0;
+            uint64_t bytes;
+        };
+        std::mutex mu;
+        std::condition_variable cv;
+        std::deque<InFlight> inflight;
+        bool text_busy[2] = {false, false};
+        uint64_t pushed[2] = {0, 0}, consumed[2] = {0, 0};   // blocks per device set
+        bool producer_done = false;
+        std::string consumer_err;
+        std::thread consumer([&] {
+            try {
+                for (;;) {
+                    InFlight job;
+                    {
+                        std::unique_lock<std::mutex> lk(mu);
+                        cv.wait(lk, [&] { return !inflight.empty() || producer_done; });
+                        if (inflight.empty()) return;
+                        job = inflight.front();
+                        inflight.pop_front();
                     }
-                } catch (const std::exception &e) {
-                    std::lock_guard<std::mutex> lk(mu);
-                    consumer_err = e.what();
-                    text_busy[0] = text_busy[1] = false;
-                    cv.notify_all();
-                }
-            });
-            struct Joiner {
-                std::thread &t;
-                std::mutex &mu;
-                std::condition_variable &cv;
-                bool &done;
-                ~Joiner()
-                {
+                    check(pgenhip_wait(sets[job.set].ctx), "pgenhip_wait");
+                    float ms = 0;
+                    if (job.first && pgenhip_timer_read(sets[job.set].ctx, &ms) == PGENHIP_OK) kernel_s[(size_t)g] += ms * 1e-3;
+                    if (zw)
+                        zw->write(h_text[job.text], (size_t)job.bytes);   // blocks arrive in order: the members are appended in order
+                    else   // every line has a known length, so ranges land at precomputed offsets in any order
+                        pwrite_span(fd, h_text[job.text], (size_t)job.bytes, header.size() + file_off[job.b0], filename, opt.write_threads);
                     {
                         std::lock_guard<std::mutex> lk(mu);
-                        done = true;
+                        text_busy[job.text] = false;
+                        consumed[job.set]++;
                     }
                     cv.notify_all();
-                    if (t.joinable()) t.join();
                 }
-            } joiner{consumer, mu, cv, producer_done};
-
-            uint8_t *h_rec = static_cast<uint8_t *>(sets[0].h_rec);
-            char *h_blob = static_cast<char *>(sets[0].h_blob);
-            uint64_t *h_poff = static_cast<uint64_t *>(sets[0].h_off);
-            uint64_t *h_loff = h_poff + (bv + 1);
-            std::vector<uint64_t> blob_len(plan.size(), 0);   // prefix bytes staged so far, per launch
-            auto launch_b0 = [&](size_t u) { return begin + plan[u].first_block * (size_t)bv; };
-            auto launch_nv = [&](size_t u) { return std::min<size_t>(plan[u].n_blocks * (size_t)bv, end - launch_b0(u)); };
-
-            // block j of launch u: records from the file, prefixes joined, offsets — into the pinned staging set, then to their place
-            // in the launch's device buffers (on the launch's own stream, idle by now: see the wait in the schedule below)
-            auto stage_block = [&](size_t u, size_t j) {
-                DeviceBuffers &B = sets[u % (size_t)n_sets];
-                const size_t r0 = j * (size_t)bv, b0 = launch_b0(u) + r0;
-                const size_t nv = std::min<size_t>((size_t)bv, end - b0);
-                // :165-170 once per run of consecutive variant indices instead of once per variant
-                for (size_t j2 = 0; j2 < nv;) {
-                    size_t run = 1;
-                    // (variable-width files: consecutive plain records are adjacent on disk too when nothing compressed lies between them)
-                    while (j2 + run < nv && var_idx_rcds[b0 + j2 + run].first == var_idx_rcds[b0 + j2].first + run &&
-                           record_offset(var_idx_rcds[b0 + j2 + run].first) == record_offset(var_idx_rcds[b0 + j2].first) + run * (uint64_t)R)
-                        run++;
-                    // (a long run is read by a few threads at once: one thread copies ~2-3 GB/s out of the page cache)
-                    const size_t run_bytes = run * (size_t)R;
-                    const uint64_t run_off = record_offset(var_idx_rcds[b0 + j2].first);
-                    const unsigned n_readers = run_bytes >= (64u << 20) ? (unsigned)std::max(1, opt.read_threads) : 1u;
-                    if (n_readers <= 1) {
-                        pread_exact(pfd, h_rec + j2 * R, run_bytes, run_off, pgen);
-                    } else {
-                        std::vector<std::thread> rs;
-                        std::string rerr;
-                        std::mutex rmu;
-                        const size_t slice = (run_bytes + n_readers - 1) / n_readers;
-                        for (unsigned t = 0; t < n_readers; t++) {
-                            const size_t lo = std::min(run_bytes, (size_t)t * slice), hi = std::min(run_bytes, lo + slice);
-                            if (lo == hi) continue;
-                            rs.emplace_back([&, lo, hi] {
-                                try {
-                                    pread_exact(pfd, h_rec + j2 * R + lo, hi - lo, run_off + lo, pgen);
-                                } catch (const std::exception &e) {
-                                    std::lock_guard<std::mutex> lk(rmu);
-                                    rerr = e.what();
-                                }
-                            });
-                        }
-                        for (auto &t : rs) t.join();
-                        if (!rerr.empty()) throw PfileError(rerr);
-                    }
-                    j2 += run;
-                }
-                // :157-161 joined once per variant: col '\t' col '\t' ... "GT"; offsets count from the start of the LAUNCH's blob / text
-                const uint64_t blob0 = blob_len[u], text0 = file_off[launch_b0(u)];
-                uint64_t bp = 0;
-                for (size_t i = 0; i < nv; i++) {
-                    h_poff[i] = blob0 + bp;
-                    h_loff[i] = file_off[b0 + i] - text0;
-                    for (const auto &col : var_idx_rcds[b0 + i].second) {
-                        std::memcpy(h_blob + bp, col.data(), col.size());
-                        bp += col.size();
-                        h_blob[bp++] = '\t';
-                    }
-                    h_blob[bp++] = 'G';
-                    h_blob[bp++] = 'T';
-                }
-                h_poff[nv] = blob0 + bp;                       // (the next block's first entry, or the launch's end)
-                h_loff[nv] = file_off[b0 + nv] - text0;
-                blob_len[u] = blob0 + bp;
-                uint64_t *d_poff = static_cast<uint64_t *>(B.d_off), *d_loff = d_poff + (lv + 1);
-                check(pgenhip_memcpy_h2d(B.ctx, static_cast<uint8_t *>(B.d_rec) + r0 * (size_t)R, h_rec, nv * (size_t)R), "H2D records");
-                check(pgenhip_memcpy_h2d(B.ctx, static_cast<char *>(B.d_blob) + blob0, h_blob, (size_t)bp), "H2D prefixes");
-                check(pgenhip_memcpy_h2d(B.ctx, d_poff + r0, h_poff, (nv + 1) * sizeof(uint64_t)), "H2D prefix offsets");
-                check(pgenhip_memcpy_h2d(B.ctx, d_loff + r0, h_loff, (nv + 1) * sizeof(uint64_t)), "H2D line offsets");
-                check(pgenhip_wait(B.ctx), "pgenhip_wait");   // the staging set is free again
-            };
-            auto launch = [&](size_t u) {
-                DeviceBuffers &B = sets[u % (size_t)n_sets];
-                uint64_t *d_poff = static_cast<uint64_t *>(B.d_off), *d_loff = d_poff + (lv + 1);
-                check(pgenhip_timer_start(B.ctx), "timer");
-                check(pgenhip_emit_lines(B.ctx, B.d_rec, R, nullptr, (uint32_t)launch_nv(u), B.d_blob, d_poff, d_loff, max_prefix, B.d_text, 0), "pgenhip_emit_lines");
-                check(pgenhip_timer_mark(B.ctx), "timer");
-            };
-            // block j of launch u leaves: D2H into a free pinned text buffer, then the consumer's
-            auto drain_block = [&](size_t u, size_t j) {
-                const int si = (int)(u % (size_t)n_sets), ti = (int)((plan[u].first_block + j) % (size_t)n_text);
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return !text_busy[ti] || !consumer_err.empty(); });
-                    if (!consumer_err.empty()) throw PfileError(consumer_err);
-                    text_busy[ti] = true;
-                }
-                const size_t b0 = launch_b0(u) + j * (size_t)bv, nv = std::min<size_t>((size_t)bv, end - b0);
-                const uint64_t block_bytes = file_off[b0 + nv] - file_off[b0];
-                check(pgenhip_memcpy_d2h(sets[si].ctx, h_text[ti], static_cast<uint8_t *>(sets[si].d_text) + (file_off[b0] - file_off[launch_b0(u)]), (size_t)block_bytes), "D2H text");
-                {
-                    std::lock_guard<std::mutex> lk(mu);
-                    inflight.push_back(InFlight{ti, si, j == 0, b0, block_bytes});
-                    pushed[si]++;
-                }
+            } catch (const std::exception &e) {
+                std::lock_guard<std::mutex> lk(mu);
+                consumer_err = e.what();
+                text_busy[0] = text_busy[1] = false;
                 cv.notify_all();
-            };
-            // a device set is staged into again only once every block of its previous launch has been written: its stream is idle
-            // then, so the producer's waits in stage_block never meet the consumer's on the same stream
-            auto wait_set_idle = [&](size_t u) {
-                const int si = (int)(u % (size_t)n_sets);
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return consumed[si] == pushed[si] || !consumer_err.empty(); });
-                if (!consumer_err.empty()) throw PfileError(consumer_err);
-            };
-
-            setup_s[(size_t)g] = now_s() - t_worker;
-            for (size_t j = 0; j < plan[0].n_blocks; j++) stage_block(0, j);
-            launch(0);
-            for (size_t u = 0; u < plan.size(); u++) {
-                const size_t n_u = plan[u].n_blocks, n_next = u + 1 < plan.size() ? plan[u + 1].n_blocks : 0;
-                size_t staged = 0;
-                for (size_t j = 0; j < n_u; j++) {
-                    drain_block(u, j);
-                    // the next launch's share of staging, so that it is complete when this launch's last block has been queued
-                    while (staged < n_next && staged * n_u < (j + 1) * n_next) {
-                        if (staged == 0) wait_set_idle(u + 1);
-                        stage_block(u + 1, staged++);
-                    }
-                }
-                if (n_next) launch(u + 1);
             }
+        });
+        auto join_consumer = [&] {
+            {
+                std::lock_guard<std::mutex> lk(mu);
+                producer_done = true;
+            }
+            cv.notify_all();
+            if (consumer.joinable()) consumer.join();
+        };
+        OnExit consumer_join{join_consumer};   // before the buffers it reads are freed
+
+        // ---- block j of launch u: records from the file, prefixes joined, offsets — into the pinned staging set, then to their
+        // place in the launch's device buffers (on the launch's own stream, idle by now: see wait_set_idle)
+        std::vector<uint64_t> blob_len(plan.size(), 0);   // prefix bytes staged so far, per launch
+        auto stage_block = [&](size_t u, size_t j) {
+            const DeviceSet &D = sets[u % (size_t)n_sets];
+            const size_t r0 = j * (size_t)bv, b0 = launch_b0(u) + r0;
+            const size_t nv = std::min<size_t>((size_t)bv, end - b0);
+            // :165-170 once per run of consecutive variant indices instead of once per variant
+            for (size_t j2 = 0; j2 < nv;) {
+                size_t run = 1;
+                // (variable-width files: consecutive plain records are adjacent on disk too when nothing compressed lies between them)
+                while (j2 + run < nv && var_idx_rcds[b0 + j2 + run].first == var_idx_rcds[b0 + j2].first + run &&
+                       record_offset(var_idx_rcds[b0 + j2 + run].first) == record_offset(var_idx_rcds[b0 + j2].first) + run * (uint64_t)R)
+                    run++;
+                pread_span(pgen_fd.get(), h_rec + j2 * R, run * (size_t)R, record_offset(var_idx_rcds[b0 + j2].first), pgen, opt.read_threads);
+                j2 += run;
+            }
+            // :157-161 joined once per variant: col '\t' col '\t' ... "GT"; offsets count from the start of the LAUNCH's blob / text
+            const uint64_t blob0 = blob_len[u], text0 = file_off[launch_b0(u)];
+            uint64_t bp = 0;
+            for (size_t i = 0; i < nv; i++) {
+                h_poff[i] = blob0 + bp;
+                h_loff[i] = file_off[b0 + i] - text0;
+                for (const auto &col : var_idx_rcds[b0 + i].second) {
+                    std::memcpy(h_blob + bp, col.data(), col.size());
+                    bp += col.size();
+                    h_blob[bp++] = '\t';
+                }
+                h_blob[bp++] = 'G';
+                h_blob[bp++] = 'T';
+            }
+            h_poff[nv] = blob0 + bp;                       // (the next block's first entry, or the launch's end)
+            h_loff[nv] = file_off[b0 + nv] - text0;
+            blob_len[u] = blob0 + bp;
+            check(pgenhip_memcpy_h2d(D.ctx, D.rec + r0 * (size_t)R, h_rec, nv * (size_t)R), "H2D records");
+            check(pgenhip_memcpy_h2d(D.ctx, D.blob + blob0, h_blob, (size_t)bp), "H2D prefixes");
+            check(pgenhip_memcpy_h2d(D.ctx, D.poff + r0, h_poff, (nv + 1) * sizeof(uint64_t)), "H2D prefix offsets");
+            check(pgenhip_memcpy_h2d(D.ctx, D.loff + r0, h_loff, (nv + 1) * sizeof(uint64_t)), "H2D line offsets");
+            check(pgenhip_wait(D.ctx), "pgenhip_wait");   // the staging set is free again
+        };
+        auto launch = [&](size_t u) {
+            const DeviceSet &D = sets[u % (size_t)n_sets];
+            check(pgenhip_timer_start(D.ctx), "timer");
+            check(pgenhip_emit_lines(D.ctx, D.rec, R, nullptr, (uint32_t)launch_nv(u), D.blob, D.poff, D.loff, max_prefix, D.text, 0), "pgenhip_emit_lines");
+            check(pgenhip_timer_mark(D.ctx), "timer");
+        };
+        // block j of launch u leaves: D2H into a free pinned text buffer, then the consumer's
+        auto drain_block = [&](size_t u, size_t j) {
+            const int si = (int)(u % (size_t)n_sets), ti = (int)((plan[u].first_block + j) % (size_t)n_text);
             {
                 std::unique_lock<std::mutex> lk(mu);
-                producer_done = true;
-                cv.notify_all();
+                cv.wait(lk, [&] { return !text_busy[ti] || !consumer_err.empty(); });
+                if (!consumer_err.empty()) throw PfileError(consumer_err);
+                text_busy[ti] = true;
             }
-            if (consumer.joinable()) consumer.join();
+            const size_t b0 = launch_b0(u) + j * (size_t)bv, nv = std::min<size_t>((size_t)bv, end - b0);
+            const uint64_t block_bytes = file_off[b0 + nv] - file_off[b0];
+            check(pgenhip_memcpy_d2h(sets[si].ctx, h_text[ti], sets[si].text + (file_off[b0] - file_off[launch_b0(u)]), (size_t)block_bytes), "D2H text");
+            {
+                std::lock_guard<std::mutex> lk(mu);
+                inflight.push_back(InFlight{ti, si, j == 0, b0, block_bytes});
+                pushed[si]++;
+            }
+            cv.notify_all();
+        };
+        // a device set is staged into again only once every block of its previous launch has been written: its stream is idle
+        // then, so the producer's waits in stage_block never meet the consumer's on the same stream
+        auto wait_set_idle = [&](size_t u) {
+            const int si = (int)(u % (size_t)n_sets);
+            std::unique_lock<std::mutex> lk(mu);
+            cv.wait(lk, [&] { return consumed[si] == pushed[si] || !consumer_err.empty(); });
             if (!consumer_err.empty()) throw PfileError(consumer_err);
-            if (zw) shard_out[(size_t)g] = zw->bytes_out();
-        } catch (const std::exception &e) {
-            std::lock_guard<std::mutex> lk(err_mu);
-            if (err.empty()) err = e.what();
+        };
+
+        // ---- schedule
+        setup_s[(size_t)g] = now_s() - t_worker;
+        for (size_t j = 0; j < plan[0].n_blocks; j++) stage_block(0, j);
+        launch(0);
+        for (size_t u = 0; u < plan.size(); u++) {
+            const size_t n_u = plan[u].n_blocks, n_next = u + 1 < plan.size() ? plan[u + 1].n_blocks : 0;
+            size_t staged = 0;
+            for (size_t j = 0; j < n_u; j++) {
+                drain_block(u, j);
+                // the next launch's share of staging, so that it is complete when this launch's last block has been queued
+                while (staged < n_next && staged * n_u < (j + 1) * n_next) {
+                    if (staged == 0) wait_set_idle(u + 1);
+                    stage_block(u + 1, staged++);
+                }
+            }
+            if (n_next) launch(u + 1);
         }
-    };
-    std::vector<std::thread> threads;
-    for (int g = 1; g < G; g++) threads.emplace_back(worker, g);
-    worker(0);
-    for (auto &t : threads) t.join();
-    if (!err.empty()) {
-        if (opt.bgzf)
-            for (int g = 1; g < G; g++) unlink(shard_tmp(g).c_str());
-        throw PfileError(err);
-    }
+        join_consumer();
+        if (!consumer_err.empty()) throw PfileError(consumer_err);
+        if (zw) shard_out[(size_t)g] = zw->bytes_out();
+        if (tmp) tmp->close();
+    });
     if (opt.bgzf) {
         st.file_bytes += shard_out[0];
-        finish_bgzf(G);
+        finish_bgzf();
     }
-    close_checked();
+    out.close();
     st.seconds_body = now_s() - t_body;
     st.seconds_kernel = *std::max_element(kernel_s.begin(), kernel_s.end());
     st.seconds_setup = *std::max_element(setup_s.begin(), setup_s.end());
@@ -833,35 +856,6 @@ OutputStats Pfile::output_vcf(const std::optional<std::string> &sam_query, const
 }
 
 namespace {
-
-// `count` bytes at `off` of the .pgen into dst: one pread, or a few at once for long spans (one thread copies ~2-3 GB/s out of the
-// page cache; output_vcf's staging does the same)
-void pread_span(int fd, uint8_t *dst, size_t count, uint64_t off, const std::string &path, int read_threads)
-{
-    const unsigned n_readers = count >= (64u << 20) ? (unsigned)std::max(1, read_threads) : 1u;
-    if (n_readers <= 1) {
-        pread_exact(fd, dst, count, off, path);
-        return;
-    }
-    std::vector<std::thread> rs;
-    std::string rerr;
-    std::mutex rmu;
-    const size_t slice = (count + n_readers - 1) / n_readers;
-    for (unsigned t = 0; t < n_readers; t++) {
-        const size_t lo = std::min(count, (size_t)t * slice), hi = std::min(count, lo + slice);
-        if (lo == hi) continue;
-        rs.emplace_back([&, lo, hi] {
-            try {
-                pread_exact(fd, dst + lo, hi - lo, off + lo, path);
-            } catch (const std::exception &e) {
-                std::lock_guard<std::mutex> lk(rmu);
-                rerr = e.what();
-            }
-        });
-    }
-    for (auto &t : rs) t.join();
-    if (!rerr.empty()) throw PfileError(rerr);
-}
 
 void append_u64(std::string &s, uint64_t v)
 {
@@ -881,54 +875,28 @@ OutputStats Pfile::output_freq(const std::optional<std::string> &sam_query, cons
 {
     OutputStats st;
     const double t0 = now_s();
-    const std::string psam = read_file(psam_path());
-    TsvReader psam_reader(psam, find_metadata_file_header_start(psam));
-    const std::string pvar = read_file(pvar_path());
-    TsvReader pvar_reader(pvar, find_metadata_file_header_start(pvar));
-    const StringRecord pvar_header = pvar_reader.headers();
-    const IdxRecords var_idx_rcds = filter_metadata(pvar_reader, var_query, opt.filter_threads);
-    const IdxRecords sam_idx_rcs = filter_metadata(psam_reader, sam_query, opt.filter_threads);
+    const Selection sel = select(sam_query, var_query, opt.filter_threads);
+    const IdxRecords &var_idx_rcds = sel.var_idx_rcds;
     // the five leading columns, copied verbatim from the pvar columns of these names
     static const char *const kCols[5] = {"CHROM", "POS", "ID", "REF", "ALT"};
     size_t col[5];
     for (int c = 0; c < 5; c++) {
-        col[c] = std::find(pvar_header.begin(), pvar_header.end(), std::string(kCols[c])) - pvar_header.begin();
-        if (col[c] == pvar_header.size()) throw PfileError(std::string(kCols[c]) + " not among the headers of " + pvar_path());
+        col[c] = std::find(sel.var_header.begin(), sel.var_header.end(), std::string(kCols[c])) - sel.var_header.begin();
+        if (col[c] == sel.var_header.size()) throw PfileError(std::string(kCols[c]) + " not among the headers of " + pvar_path());
     }
     st.seconds_filter = now_s() - t0;
 
-    const uint32_t N = num_samples;
+    const KeptSamples kept = check_selection(*this, sel);
     const uint32_t R = variant_record_size();
     const size_t V = var_idx_rcds.size();
-    std::vector<uint32_t> kept;
-    kept.reserve(sam_idx_rcs.size());
-    for (const auto &ir : sam_idx_rcs) {
-        if (ir.first >= N) throw PfileError("index out of bounds: sample row " + std::to_string(ir.first) + " but the .pgen holds " + std::to_string(N) + " samples");
-        kept.push_back((uint32_t)ir.first);
-    }
-    const bool all_samples = kept.size() == (size_t)N;
-    for (size_t j = 0; j < V; j++) {
-        const size_t vi = var_idx_rcds[j].first;
-        if (vi >= num_variants)
-            throw PfileError("variant row " + std::to_string(vi) + " is past the " + std::to_string(num_variants) + " records of " + pgen_path());
-        if (variable_width() && ((*vw_record_type)[vi] != 0 || (*vw_record_len)[vi] != R))
-            throw PfileError(pgen_path() + ": variant row " + std::to_string(vi) + " is stored compressed (record type " +
-                             std::to_string((*vw_record_type)[vi]) + ", " + std::to_string((*vw_record_len)[vi]) + " bytes); only uncompressed 2-bit records are supported");
-    }
     st.variants = V;
-    st.samples_kept = kept.size();
+    st.samples_kept = kept.rows.size();
 
     std::vector<uint32_t> counts(4 * V, 0u);
     const double t_body = now_s();
     if (V != 0 && R != 0) {
-        int n_dev = 0;
-        check(pgenhip_device_count(&n_dev), "pgenhip_device_count");
-        if (n_dev <= 0) throw PfileError("no HIP device: the genotype count path has no CPU fallback");
-        const int n_use = std::max(1, std::min(opt.n_gpus, n_dev));
-        const int G = opt.n_shards > 0 ? opt.n_shards : n_use;   // variant ranges (shards), dealt round-robin over the devices
-        std::vector<double> kernel_s((size_t)G, 0.0), setup_s((size_t)G, 0.0);
-        std::mutex err_mu;
-        std::string err;
+        const Shards shards(opt, "no HIP device: the genotype count path has no CPU fallback");
+        std::vector<double> kernel_s((size_t)shards.G, 0.0), setup_s((size_t)shards.G, 0.0);
         const std::string pgen = pgen_path();
         const bool vw = variable_width();
 
@@ -937,95 +905,69 @@ OutputStats Pfile::output_freq(const std::optional<std::string> &sam_query, cons
         // Fixed-width files: runs of consecutive records are read in one go and packed at stride R.  Variable-width files: the plain
         // records are staged as they lie on disk (a span grows over gaps of up to R bytes, so a block stages at most 2R bytes per
         // variant) and counted through their offsets in the staged bytes (pgenhip_genotype_counts_at).
-        auto worker = [&](int g) {
-            try {
-                const double t_worker = now_s();
-                uint64_t begin64 = 0, end64 = 0;
-                check(pgenhip_shard_range(V, (uint32_t)G, (uint32_t)g, &begin64, &end64), "pgenhip_shard_range");
-                const size_t begin = (size_t)begin64, end = (size_t)end64;
-                if (begin == end) return;
-                int pfd = open(pgen.c_str(), O_RDONLY);
-                if (pfd < 0) throw PfileError("open " + pgen + ": " + std::strerror(errno));
-                struct FdGuard {
-                    int fd;
-                    ~FdGuard() { close(fd); }
-                } pg{pfd};
-                const uint64_t bv = std::max<uint64_t>(1, std::min<uint64_t>(opt.block_text_bytes / R, end - begin));
-                const size_t stage_bytes = (size_t)(bv * R) * (vw ? 2u : 1u);
-                DeviceBuffers B;   // h_rec / h_text2: the two pinned record buffers; h_off: pinned offsets + counts; d_text: device counts
-                check(pgenhip_create(&B.ctx, g % n_use, N, all_samples ? nullptr : kept.data(), (uint32_t)kept.size(),
-                                     all_samples ? 0u : PGENHIP_CREATE_KEEP_LIST), "pgenhip_create");
-                check(pgenhip_device_malloc(B.ctx, &B.d_rec, stage_bytes), "device records");
-                check(pgenhip_device_malloc(B.ctx, &B.d_text, (size_t)(16 * bv)), "device counts");
-                if (vw) check(pgenhip_device_malloc(B.ctx, &B.d_off, (size_t)(8 * bv)), "device record offsets");
-                check(pgenhip_host_malloc_pinned(B.ctx, &B.h_rec, stage_bytes), "pinned records");
-                check(pgenhip_host_malloc_pinned(B.ctx, &B.h_text2, stage_bytes), "pinned records");
-                check(pgenhip_host_malloc_pinned(B.ctx, &B.h_off, (size_t)(16 * bv + (vw ? 16 * bv : 0))), "pinned counts");
-                uint32_t *h_counts = static_cast<uint32_t *>(B.h_off);
-                uint64_t *h_off[2] = {reinterpret_cast<uint64_t *>(h_counts + 4 * bv), reinterpret_cast<uint64_t *>(h_counts + 4 * bv) + bv};
-                uint8_t *h_rec[2] = {static_cast<uint8_t *>(B.h_rec), static_cast<uint8_t *>(B.h_text2)};
-                setup_s[(size_t)g] = now_s() - t_worker;
+        shards.run(V, [&](int g, int device, size_t begin, size_t end) {
+            const double t_worker = now_s();
+            const Fd pgen_fd(pgen, O_RDONLY);
+            const uint64_t bv = std::max<uint64_t>(1, std::min<uint64_t>(opt.block_text_bytes / R, end - begin));
+            const size_t stage_bytes = (size_t)(bv * R) * (vw ? 2u : 1u);
+            DeviceCtx ctx(device, num_samples, &kept);
+            uint8_t *d_rec = ctx.device<uint8_t>(stage_bytes, "device records");
+            uint32_t *d_counts = ctx.device<uint32_t>((size_t)(16 * bv), "device counts");
+            uint64_t *d_off = vw ? ctx.device<uint64_t>((size_t)(8 * bv), "device record offsets") : nullptr;
+            uint8_t *h_rec[2] = {ctx.pinned<uint8_t>(stage_bytes, "pinned records"), ctx.pinned<uint8_t>(stage_bytes, "pinned records")};
+            uint32_t *h_counts = ctx.pinned<uint32_t>((size_t)(16 * bv + (vw ? 16 * bv : 0)), "pinned counts");
+            uint64_t *h_off[2] = {reinterpret_cast<uint64_t *>(h_counts + 4 * bv), reinterpret_cast<uint64_t *>(h_counts + 4 * bv) + bv};
+            setup_s[(size_t)g] = now_s() - t_worker;
 
-                size_t prev_b0 = 0, prev_nv = 0;   // the block in flight on the device
-                auto collect = [&] {
-                    if (!prev_nv) return;
-                    check(pgenhip_wait(B.ctx), "pgenhip_wait");
-                    float ms = 0;
-                    if (pgenhip_timer_read(B.ctx, &ms) == PGENHIP_OK) kernel_s[(size_t)g] += ms * 1e-3;
-                    std::memcpy(counts.data() + 4 * prev_b0, h_counts, prev_nv * 16);
-                    prev_nv = 0;
-                };
-                for (size_t b0 = begin, k = 0; b0 < end; b0 += (size_t)bv, k++) {
-                    const size_t nv = std::min<size_t>((size_t)bv, end - b0);
-                    uint8_t *dst = h_rec[k % 2];
-                    size_t staged = 0;
-                    for (size_t j = 0; j < nv;) {
-                        const uint64_t off0 = record_offset(var_idx_rcds[b0 + j].first);
-                        size_t run = 1;
-                        uint64_t span = R;   // bytes of the file from off0 this run covers
-                        if (vw) {
-                            h_off[k % 2][j] = staged;
-                            while (j + run < nv) {
-                                const uint64_t off = record_offset(var_idx_rcds[b0 + j + run].first);
-                                if (off > off0 + span + R) break;
-                                h_off[k % 2][j + run] = staged + (off - off0);
-                                span = off + R - off0;
-                                run++;
-                            }
-                        } else {
-                            while (j + run < nv && var_idx_rcds[b0 + j + run].first == var_idx_rcds[b0 + j].first + run) run++;
-                            span = (uint64_t)run * R;
+            size_t prev_b0 = 0, prev_nv = 0;   // the block in flight on the device
+            auto collect = [&] {
+                if (!prev_nv) return;
+                check(pgenhip_wait(ctx.get()), "pgenhip_wait");
+                float ms = 0;
+                if (pgenhip_timer_read(ctx.get(), &ms) == PGENHIP_OK) kernel_s[(size_t)g] += ms * 1e-3;
+                std::memcpy(counts.data() + 4 * prev_b0, h_counts, prev_nv * 16);
+                prev_nv = 0;
+            };
+            for (size_t b0 = begin, k = 0; b0 < end; b0 += (size_t)bv, k++) {
+                const size_t nv = std::min<size_t>((size_t)bv, end - b0);
+                uint8_t *dst = h_rec[k % 2];
+                size_t staged = 0;
+                for (size_t j = 0; j < nv;) {
+                    const uint64_t off0 = record_offset(var_idx_rcds[b0 + j].first);
+                    size_t run = 1;
+                    uint64_t span = R;   // bytes of the file from off0 this run covers
+                    if (vw) {
+                        h_off[k % 2][j] = staged;
+                        while (j + run < nv) {
+                            const uint64_t off = record_offset(var_idx_rcds[b0 + j + run].first);
+                            if (off > off0 + span + R) break;
+                            h_off[k % 2][j + run] = staged + (off - off0);
+                            span = off + R - off0;
+                            run++;
                         }
-                        pread_span(pfd, dst + staged, (size_t)span, off0, pgen, opt.read_threads);
-                        staged += (size_t)span;
-                        j += run;
+                    } else {
+                        while (j + run < nv && var_idx_rcds[b0 + j + run].first == var_idx_rcds[b0 + j].first + run) run++;
+                        span = (uint64_t)run * R;
                     }
-                    collect();   // block k - 1 has been counted and its counts are back; its pinned records are free again
-                    check(pgenhip_memcpy_h2d(B.ctx, B.d_rec, dst, staged), "H2D records");
-                    if (vw) check(pgenhip_memcpy_h2d(B.ctx, B.d_off, h_off[k % 2], nv * sizeof(uint64_t)), "H2D record offsets");
-                    check(pgenhip_timer_start(B.ctx), "timer");
-                    if (vw)
-                        check(pgenhip_genotype_counts_at(B.ctx, B.d_rec, static_cast<const uint64_t *>(B.d_off), (uint32_t)nv,
-                                                         static_cast<uint32_t *>(B.d_text), PGENHIP_COUNT_AUTO), "pgenhip_genotype_counts_at");
-                    else
-                        check(pgenhip_genotype_counts(B.ctx, B.d_rec, R, nullptr, (uint32_t)nv, static_cast<uint32_t *>(B.d_text), PGENHIP_COUNT_AUTO),
-                              "pgenhip_genotype_counts");
-                    check(pgenhip_timer_mark(B.ctx), "timer");
-                    check(pgenhip_memcpy_d2h(B.ctx, h_counts, B.d_text, nv * 16), "D2H counts");
-                    prev_b0 = b0;
-                    prev_nv = nv;
+                    pread_span(pgen_fd.get(), dst + staged, (size_t)span, off0, pgen, opt.read_threads);
+                    staged += (size_t)span;
+                    j += run;
                 }
-                collect();
-            } catch (const std::exception &e) {
-                std::lock_guard<std::mutex> lk(err_mu);
-                if (err.empty()) err = e.what();
+                collect();   // block k - 1 has been counted and its counts are back; its pinned records are free again
+                check(pgenhip_memcpy_h2d(ctx.get(), d_rec, dst, staged), "H2D records");
+                if (vw) check(pgenhip_memcpy_h2d(ctx.get(), d_off, h_off[k % 2], nv * sizeof(uint64_t)), "H2D record offsets");
+                check(pgenhip_timer_start(ctx.get()), "timer");
+                if (vw)
+                    check(pgenhip_genotype_counts_at(ctx.get(), d_rec, d_off, (uint32_t)nv, d_counts, PGENHIP_COUNT_AUTO), "pgenhip_genotype_counts_at");
+                else
+                    check(pgenhip_genotype_counts(ctx.get(), d_rec, R, nullptr, (uint32_t)nv, d_counts, PGENHIP_COUNT_AUTO), "pgenhip_genotype_counts");
+                check(pgenhip_timer_mark(ctx.get()), "timer");
+                check(pgenhip_memcpy_d2h(ctx.get(), h_counts, d_counts, nv * 16), "D2H counts");
+                prev_b0 = b0;
+                prev_nv = nv;
             }
-        };
-        std::vector<std::thread> threads;
-        for (int g = 1; g < G; g++) threads.emplace_back(worker, g);
-        worker(0);
-        for (auto &t : threads) t.join();
-        if (!err.empty()) throw PfileError(err);
+            collect();
+        });
         st.seconds_kernel = *std::max_element(kernel_s.begin(), kernel_s.end());
         st.seconds_setup = *std::max_element(setup_s.begin(), setup_s.end());
     }
@@ -1049,10 +991,9 @@ OutputStats Pfile::output_freq(const std::optional<std::string> &sam_query, cons
         if (std::fwrite(text.data(), 1, text.size(), stdout) != text.size() || std::fflush(stdout) != 0)
             throw PfileError(std::string("write stdout: ") + std::strerror(errno));
     } else {
-        int fd = open(filename.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-        if (fd < 0) throw PfileError("create " + filename + ": " + std::strerror(errno));
-        pwrite_exact(fd, text.data(), text.size(), 0, filename);
-        if (close(fd) != 0) throw PfileError("close " + filename + ": " + std::strerror(errno));
+        Fd out(filename, O_WRONLY | O_CREAT | O_TRUNC);
+        pwrite_exact(out.get(), text.data(), text.size(), 0, filename);
+        out.close();
     }
     st.seconds_body = now_s() - t_body;
     return st;
@@ -1085,30 +1026,24 @@ void synth_pfile(const std::string &prefix, uint32_t variants, uint32_t samples,
             std::fprintf(f, "S%06u\tNA\t%d\n", i, keep_modulus && splitmix64(0x4D41534Bull ^ (uint64_t)i) % keep_modulus == 0 ? 1 : 0);
         std::fclose(f);
     }
-    int fd = open((prefix + ".pgen").c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-    if (fd < 0) throw PfileError("create " + prefix + ".pgen: " + std::strerror(errno));
-    struct FdGuard {
-        int fd;
-        ~FdGuard() { close(fd); }
-    } guard{fd};
+    const Fd out(prefix + ".pgen", O_WRONLY | O_CREAT | O_TRUNC);
     uint8_t hdr[12] = {0x6C, 0x1B, 0x02, 0, 0, 0, 0, 0, 0, 0, 0, 0x40};
     for (int b = 0; b < 4; b++) {
         hdr[3 + b] = (uint8_t)(variants >> (8 * b));
         hdr[7 + b] = (uint8_t)(samples >> (8 * b));
     }
-    pwrite_exact(fd, hdr, sizeof hdr, 0, prefix + ".pgen");
+    pwrite_exact(out.get(), hdr, sizeof hdr, 0, prefix + ".pgen");
     if (variants == 0 || R == 0) return;
-    DeviceBuffers B;
-    check(pgenhip_create(&B.ctx, 0, samples, nullptr, 0, 0), "pgenhip_create");
+    DeviceCtx ctx(0, samples);
     const uint64_t bv = std::max<uint64_t>(1, std::min<uint64_t>((256ull << 20) / R, variants));
-    check(pgenhip_host_malloc_pinned(B.ctx, &B.h_rec, (size_t)(bv * R)), "pinned records");
-    check(pgenhip_device_malloc(B.ctx, &B.d_rec, (size_t)(bv * R)), "device records");
+    uint8_t *h_rec = ctx.pinned<uint8_t>((size_t)(bv * R), "pinned records");
+    uint8_t *d_rec = ctx.device<uint8_t>((size_t)(bv * R), "device records");
     for (uint64_t v0 = 0; v0 < variants; v0 += bv) {
         const uint32_t nv = (uint32_t)std::min<uint64_t>(bv, variants - v0);
-        check(pgenhip_synth_records(B.ctx, B.d_rec, R, v0, nv, seed, 0), "pgenhip_synth_records");
-        check(pgenhip_memcpy_d2h(B.ctx, B.h_rec, B.d_rec, (size_t)nv * R), "D2H records");
-        check(pgenhip_wait(B.ctx), "pgenhip_wait");
-        pwrite_exact(fd, B.h_rec, (size_t)nv * R, 12ull + v0 * R, prefix + ".pgen");
+        check(pgenhip_synth_records(ctx.get(), d_rec, R, v0, nv, seed, 0), "pgenhip_synth_records");
+        check(pgenhip_memcpy_d2h(ctx.get(), h_rec, d_rec, (size_t)nv * R), "D2H records");
+        check(pgenhip_wait(ctx.get()), "pgenhip_wait");
+        pwrite_exact(out.get(), h_rec, (size_t)nv * R, 12ull + v0 * R, prefix + ".pgen");
     }
 }
 

@@ -4,7 +4,12 @@
 // on the GPU through pgenhip_emit_lines.  The reference is compiled Rust and no Rust toolchain
 // exists in this image, hence C++.
 #pragma once
+#include <fcntl.h>
+#include <unistd.h>
+
+#include <cerrno>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <optional>
 #include <stdexcept>
@@ -19,6 +24,44 @@ namespace pgenhost {
 // What the reference expresses as panic!/unwrap()/assert! (exit status 101).
 struct PfileError : std::runtime_error {
     using std::runtime_error::runtime_error;
+};
+
+// An open file, closed when it goes out of scope.  close() is the checked close: a failed close (ENOSPC/EIO surfacing late) must
+// not leave a truncated file behind an exit code 0.
+class Fd {
+  public:
+    Fd(const std::string &path, int flags) : path_(path), fd_(::open(path.c_str(), flags, 0644))
+    {
+        if (fd_ < 0) throw PfileError(((flags & O_CREAT) ? "create " : "open ") + path + ": " + std::strerror(errno));
+    }
+    Fd(const Fd &) = delete;
+    Fd &operator=(const Fd &) = delete;
+    ~Fd()
+    {
+        if (fd_ >= 0) ::close(fd_);
+    }
+    int get() const { return fd_; }
+    // all n bytes at the file's current position
+    void write_all(const void *data, size_t n)
+    {
+        for (const char *p = static_cast<const char *>(data); n;) {
+            const ssize_t w = ::write(fd_, p, n);
+            if (w < 0 && errno == EINTR) continue;
+            if (w <= 0) throw PfileError("write " + path_ + ": " + std::strerror(errno));
+            p += w;
+            n -= (size_t)w;
+        }
+    }
+    void close()
+    {
+        const int fd = fd_;
+        fd_ = -1;
+        if (::close(fd) != 0) throw PfileError("close " + path_ + ": " + std::strerror(errno));
+    }
+
+  private:
+    std::string path_;
+    int fd_;
 };
 
 struct OutputOptions {
@@ -82,6 +125,13 @@ class Pfile {
     // :312-335 — rows (file order) whose predicate is true; all rows without a query
     // (filter_threads: 0 = as many pieces as the file size and the host's cores suggest, 1 = the reference's serial walk)
     static IdxRecords filter_metadata(TsvReader &reader, const std::optional<std::string> &query, int filter_threads = 0);
+
+    // :111-128 — the kept variant and sample rows (.psam read first, .pvar filtered first) and the two header rows
+    struct Selection {
+        IdxRecords var_idx_rcds, sam_idx_rcs;
+        StringRecord sam_header, var_header;
+    };
+    Selection select(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query, int filter_threads) const;
 
     // :78-102 — prints f_string evaluated on each kept row to `out` (stdout in the CLI)
     static void query_metadata(TsvReader &reader, const std::optional<std::string> &query, const std::string &f_string,

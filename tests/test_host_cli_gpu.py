@@ -171,11 +171,12 @@ def test_basic2_launches_of_several_blocks(basic2, tmp_path, block_mib, launch_m
     assert len(got) == len(want) and hashlib.sha256(got).digest() == hashlib.sha256(want).digest()
 
 
-@pytest.mark.parametrize("extra", [[], ["--launch-mib", "4"], ["--bgzf", "--bgzf-level", "1"], ["--shards", "2"]])
+@pytest.mark.parametrize("extra", [[], ["--launch-mib", "4"], ["--bgzf", "--bgzf-level", "1"], ["--shards", "2"], ["--bgzf", "--bgzf-level", "1", "--shards", "4"]])
 def test_write_error_in_the_middle_of_the_body_ends_the_run(basic2, tmp_path, extra):
     """The consumer thread's write fails once the output passes 16 MiB (RLIMIT_FSIZE with SIGXFSZ ignored: EFBIG) while the producer is
     staging / launching / queueing copies ahead of it: the run must end with the reference's panic status and the errno text — not hang
-    in one of the pipeline's waits, not exit 0 with a short file."""
+    in one of the pipeline's waits, not exit 0 with a short file.  BGZF over 4 shards: every shard's part (~10 MB) fits under the
+    limit, so the write that fails is the append of shard 1's temporary file behind shard 0's part; no temporary file may be left."""
     import resource
     import signal
 
@@ -188,6 +189,7 @@ def test_write_error_in_the_middle_of_the_body_ends_the_run(basic2, tmp_path, ex
     p = subprocess.run([str(CLI), "filter", str(basic2), "-o", str(out), "--block-mib", "4", *extra], capture_output=True, timeout=300, preexec_fn=limit)
     assert p.returncode == 101, (p.returncode, p.stderr[-500:])
     assert b"File too large" in p.stderr or b"EFBIG" in p.stderr, p.stderr[-500:]
+    assert not list(tmp_path.glob("*.shard*.tmp"))
 
 
 # ---- a variable-width (mode 0x10) file through the CLI ---------------------------------------------
@@ -258,6 +260,33 @@ def test_bgzf_output_round_trips_to_the_plain_file(basic1, tmp_path):
     default = Path(str(basic1) + ".pgen-rs.vcf.gz")
     assert gzip.decompress(default.read_bytes()) == expected_vcf(basic1, var_pred=lambda r: r[b"ID"] == b"rs8100066", sam_pred=lambda r: r[b"IID"] == b"NA20900")
     default.unlink()
+
+
+@pytest.mark.parametrize("plant", ["leftover", "symlink"])
+def test_bgzf_shard_files_ignore_what_lies_at_their_names(basic1, tmp_path, plant):
+    """The shards' temporary files are the run's own: a leftover at the name of an empty shard's file is not appended, a symlink at the
+    name of a busy shard's file is not followed, and no name is left behind."""
+    import gzip
+
+    from test_bgzf import check_bgzf
+
+    out = tmp_path / "t.vcf.gz"
+    victim = tmp_path / "victim.txt"
+    victim.write_bytes(b"not the run's file\n")
+    if plant == "leftover":
+        var = 'ID == "rs2312724" || ID == "rs7815"'   # 2 variants over 3 shards: shard 2 is empty
+        Path(f"{out}.shard2.tmp").write_bytes(gzip.compress(b"left over from an earlier run\n"))
+    else:
+        var = 'ALT=="G"'
+        Path(f"{out}.shard1.tmp").symlink_to(victim)
+    plain = tmp_path / "t.vcf"
+    p = run("filter", str(basic1), "--include-var", var, "--shards", "3", "-o", str(plain))
+    assert p.returncode == 0, p.stderr
+    p = run("filter", str(basic1), "--include-var", var, "--shards", "3", "--bgzf", "-o", str(out))
+    assert p.returncode == 0, p.stderr
+    check_bgzf(out, plain.read_bytes())
+    assert not list(tmp_path.glob("*.tmp"))
+    assert victim.read_bytes() == b"not the run's file\n"
 
 
 def test_bgzf_lines_longer_than_a_member(tmp_path):
