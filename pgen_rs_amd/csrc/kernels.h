@@ -42,7 +42,7 @@ struct Tuning {
     int pick_line_seams = 1;       // pick family, full lines of dense records: interiors + seams in one kernel (0 = round 2's row-by-row flush)
     int pick_batch_bytes = 32768;  // short-record pick kernel: text per batch (one store drain per batch)
     int scan_xcd_map = 1;          // segment kernels: all blocks of a row group on one XCD (seam lines merge in one L2); 0 = plain map
-    int scan_chunk_rows = 0;       // two-pass path: rows per chunk (0 = as many as the 64-MiB compact scratch holds; tests force small chunks)
+    int scan_chunk_rows = 0;       // two-pass path: rows per chunk (0 = as many as the launch's 32-MiB compact-scratch slice holds; tests force small chunks)
     int scan_two_pass = 1;         // sparse keeps on long records: compact pass + all-samples pass (0 = single-pass segment kernel)
     int rowpick_blocks_per_cu = 0; // row-owner kernel: cap on resident blocks per CU (0 = what the occupancy API says)
     int scan_rowpick = 1;          // (1: row-owner compact pass + all-samples pass; 2: row-owner single pass; 0: segment compact pass)
