@@ -59,9 +59,6 @@ KNOB_SCAN_TWO_PASS = 9
 KNOB_SCAN_CHUNK_ROWS = 10
 KNOB_ROWPICK_BLOCKS_PER_CU = 11
 KNOB_SCAN_ROWPICK = 12
-KNOB_PICK_LINE_SEAMS = 13
-KNOB_FLUSH_UNROLL = 14
-KNOB_SCAN_FOUR_PICKS = 15
 KNOB_ALIGN_STORES = 16
 
 

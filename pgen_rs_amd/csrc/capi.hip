@@ -293,12 +293,11 @@ static bool very_sparse(const pgenhip_ctx *ctx)
 //     N = 500 000 3.2 % 0.62 / 0.58 (level from ~20 %: N = 60 000 25 % 0.565 / 0.571; behind at 50 %).
 // Below 2 % the two passes keep the sparse band (BASELINE configs[4], 1 % of 500 000: one pass reads 86 % and writes 14 % of its bytes
 // everywhere at once and runs at the copy ceiling, 3-6 % behind; N = 200 000 1 %: 0.635 against 0.658).
-// PGENHIP_KNOB_SCAN_ROWPICK = 2 takes the one pass wherever it is applicable in the two-pass band too (A/B), -1 nowhere.
+// PGENHIP_KNOB_SCAN_ROWPICK = -1 takes it nowhere.
 static bool rowpick_shape(const pgenhip_ctx *ctx, const EmitArgs &a)
 {
     if (ctx->tune.scan_rowpick == 0 || ctx->sample_count <= kScanSegmentSamples || very_sparse(ctx) || !gt_rowpick_applicable(a, ctx->num_cus)) return false;
     const uint64_t N = ctx->sample_count, K = ctx->kept_count;
-    if (ctx->tune.scan_rowpick == 2 && two_pass_shape(ctx->sample_count, ctx->kept_count)) return true;
     if (N < 24576ull) return true;
     return K * 50ull >= N && K * 5ull <= N;
 }
@@ -639,10 +638,7 @@ int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)
         case PGENHIP_KNOB_SCAN_CHUNK_ROWS: t.scan_chunk_rows = value > 0 ? value : d.scan_chunk_rows; break;
         case PGENHIP_KNOB_SCAN_TWO_PASS: t.scan_two_pass = value < 0 ? 0 : 1; break;
         case PGENHIP_KNOB_ROWPICK_BLOCKS_PER_CU: t.rowpick_blocks_per_cu = value > 0 ? value : d.rowpick_blocks_per_cu; break;
-        case PGENHIP_KNOB_SCAN_ROWPICK: t.scan_rowpick = value < 0 ? 0 : (value == 2 ? 2 : 1); break;
-        case PGENHIP_KNOB_PICK_LINE_SEAMS: t.pick_line_seams = value < 0 ? 0 : 1; break;
-        case PGENHIP_KNOB_FLUSH_UNROLL: t.flush_unroll = value == 1 || value == 2 || value == 4 ? value : d.flush_unroll; break;
-        case PGENHIP_KNOB_SCAN_FOUR_PICKS: t.scan_four_picks = value < 0 ? 0 : 1; break;
+        case PGENHIP_KNOB_SCAN_ROWPICK: t.scan_rowpick = value < 0 ? 0 : 1; break;
         case PGENHIP_KNOB_ALIGN_STORES: t.align_stores = value < 0 ? 0 : 1; break;
         case PGENHIP_KNOB_RUNS_ROWS: t.runs_rows = value > 0 ? value : d.runs_rows; break;
         default: return fail(PGENHIP_ERR_BAD_ARG, "unknown knob");

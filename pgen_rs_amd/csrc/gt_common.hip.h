@@ -154,10 +154,7 @@ __device__ __forceinline__ uint8_t *row_text(const EmitArgs &a, uint64_t j)
 // whoever writes the neighbouring bytes) go out as ONE byte-store instruction: lanes 0-15 the head bytes, lanes
 // 16-31 the tail bytes.  All 64-bit arithmetic is wave-uniform (scalar unit); a lane only adds a 32-bit offset.
 // `code_of(x)` yields the 2-bit code at position x = base + segment rank (ring position, or rank for the pick kernel).
-// U chunks per lane and loop step: their 5 U table reads, then their 5 U staged-byte reads leave together, so a step costs two LDS
-// round trips whatever U is (the compiler does not unroll this loop by itself; with the segment kernel's two waves per SIMD the
-// round trips of U = 1 are exposed).
-template <uint32_t U = 1, typename CodeFn>
+template <typename CodeFn>
 __device__ __forceinline__ void flush_codes(CodeFn code_of, uint32_t base, uint8_t *row_out, uint64_t emitted, uint64_t hi_emit,
                                             uint32_t seg_k0, uint32_t K, uint32_t lane)
 {
@@ -172,29 +169,21 @@ __device__ __forceinline__ void flush_codes(CodeFn code_of, uint32_t base, uint8
     const uint32_t em = (uint32_t)emitted & 3u;
     const uint64_t nl64 = 4ull * K - emitted;                          // flush offset of the row's '\n' (row byte 4K)
     const uint32_t nl = nl64 < (uint64_t)len ? (uint32_t)nl64 : 0xFFFFFFFFu;
-    for (uint32_t i0 = 0; i0 < n_chunks; i0 += 64u * U) {
-        uint32_t offv[U], shv[U], c[U][5];
-        bool ok[U];
+    for (uint32_t i0 = 0; i0 < n_chunks; i0 += 64u) {
+        const uint32_t i = i0 + lane;
+        const bool ok = i < n_chunks;
+        const uint32_t offv = head + ((ok ? i : 0u) << 4);             // (a lane without a chunk re-reads chunk 0's codes and stores nothing)
+        const uint32_t x = em + offv;                                  // byte offset from the dword boundary under `emitted`
+        const uint32_t rel = e4 + (x >> 2);
+        const uint32_t sh = x & 3u;
+        uint32_t c[5];
 #pragma unroll
-        for (uint32_t u = 0; u < U; u++) {
-            const uint32_t i = i0 + u * 64u + lane;
-            ok[u] = i < n_chunks;
-            offv[u] = head + ((ok[u] ? i : 0u) << 4);                  // (a lane without a chunk re-reads chunk 0's codes and stores nothing)
-            const uint32_t x = em + offv[u];                           // byte offset from the dword boundary under `emitted`
-            const uint32_t rel = e4 + (x >> 2);
-            shv[u] = x & 3u;
-#pragma unroll
-            for (uint32_t k = 0; k < 5u; k++) c[u][k] = code_of(rel + k);  // the fifth may be past the flush: then it feeds no byte (sh = 0) or only '\n''s place
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < U; u++) {
-            const uint32_t t0 = gt_text(c[u][0]), t1 = gt_text(c[u][1]), t2 = gt_text(c[u][2]), t3 = gt_text(c[u][3]), t4 = gt_text(c[u][4]);
-            const uint32_t sh = shv[u];
-            gt_v4u v = {funnel_bytes(t0, t1, sh), funnel_bytes(t1, t2, sh), funnel_bytes(t2, t3, sh), funnel_bytes(t3, t4, sh)};
-            // the row's '\n' can only be a whole chunk's last byte (hi_emit <= 4K + 1)
-            if (offv[u] + 15u == nl) v.w = (v.w & 0x00FFFFFFu) | 0x0A000000u;
-            if (ok[u]) subset_store16(out0 + offv[u], v);
-        }
+        for (uint32_t k = 0; k < 5u; k++) c[k] = code_of(rel + k);     // the fifth may be past the flush: then it feeds no byte (sh = 0) or only '\n''s place
+        const uint32_t t0 = gt_text(c[0]), t1 = gt_text(c[1]), t2 = gt_text(c[2]), t3 = gt_text(c[3]), t4 = gt_text(c[4]);
+        gt_v4u v = {funnel_bytes(t0, t1, sh), funnel_bytes(t1, t2, sh), funnel_bytes(t2, t3, sh), funnel_bytes(t3, t4, sh)};
+        // the row's '\n' can only be a whole chunk's last byte (hi_emit <= 4K + 1)
+        if (offv + 15u == nl) v.w = (v.w & 0x00FFFFFFu) | 0x0A000000u;
+        if (ok) subset_store16(out0 + offv, v);
     }
     const uint32_t off = lane < 16u ? lane : tail_off + (lane - 16u);
     const bool on = lane < 16u ? lane < head : (lane < 32u && lane - 16u < tail);
@@ -223,7 +212,9 @@ __device__ __forceinline__ uint32_t gt_vars2(uint32_t ca, uint32_t cb)
 // extra single pick per step, for the chunk behind the step).  The four table entries of a chunk are consecutive:
 // `codes4(c0, g, a, b, c, d)` gets the flush-uniform C0 = rel & 3 as a std::integral_constant (four copies of the loop, chosen per
 // flush by a scalar branch) and the aligned group g = rel >> 2, and returns the 2-bit codes of ranks 4g + C0 .. 4g + C0 + 3;
-// `code1(rel)` returns one.
+// `code1(rel)` returns one.  U chunks per lane and loop step (the kernels use 2): their table reads, then their staged-byte reads
+// leave together, so a step costs two LDS round trips whatever U is (with the segment kernel's two waves per SIMD those of U = 1
+// are exposed).
 // Lane <-> chunk: lane l of group u of a step takes chunk i0 + 64 u + l - lead, where `lead` = the chunks between the 128-byte line
 // boundary at or below chunk 0 and chunk 0: every store instruction then covers eight WHOLE lines (a store that starts mid-line
 // touches nine, two of them partially).  `part` of `n_parts` cooperating waves takes the steps part, part + n_parts, ...

@@ -607,7 +607,7 @@ hipError_t launch_gt_pick(const EmitArgs &a, const Tuning &t, int num_cus, hipSt
     p.magic = (uint32_t)(0x100000000ull / p.row_bytes) + 1u;    // exact up to one compare for run offsets < 2^20 (<= 12 rows of <= 16 385 bytes, or <= 64 rows within 32 KiB + one row)
     p.n_batches = (uint32_t)(((uint64_t)a.n_variants + b - 1u) / b);
     // full lines of dense records: interiors + seams, every byte written once as part of a whole chunk (gt_pick_lines_kernel)
-    if (a.line_off != nullptr && p.packed && t.pick_line_seams != 0 && a.kept_count >= 4u && a.prefix_blob != nullptr) {
+    if (a.line_off != nullptr && p.packed && a.kept_count >= 4u && a.prefix_blob != nullptr) {
         const uint64_t max_prefix = a.max_line_bytes - (uint64_t)p.row_bytes;
         PickLinesParams lp;
         uint32_t bl = b;

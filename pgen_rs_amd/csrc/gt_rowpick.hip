@@ -16,7 +16,7 @@
 //     row's COMPACT record in LDS (four codes to a byte: lane <-> byte, a byte that straddles two segments is completed
 //     by the second one);
 //   * after the last segment the compact record is a mode-0x02 record of K samples sitting in LDS: the wave writes the row's
-//     whole text (:177-190) from it with 16-byte-aligned chunk stores (flush_codes) — 20 KB of whole 128-B lines, the only
+//     whole text (:177-190) from it with 16-byte-aligned chunk stores (flush_text4) — 20 KB of whole 128-B lines, the only
 //     partial lines are the two row ends — and, in full-line mode, the row's prefix (:157-161) as well.
 // One pass, no scratch, no second kernel; HBM traffic per row: the record once + the text once; the kept list once per block.
 #include "gt_common.hip.h"
@@ -47,7 +47,7 @@ __host__ __device__ inline uint32_t codes_bytes(uint32_t K) { return ((K + 3u) /
 // COMPACT instantiation: instead of text the wave writes the row's compact record itself — ceil(K / 4) bytes at a.out + row *
 // a.out_stride, whole 16-byte chunks — the first pass of the two-pass path (capi.hip): an almost pure record reader, the text is
 // then written by the all-samples kernels from those records in a second, write-only pass.
-template <bool HAS_VIDX, bool COMPACT, uint32_t U, bool FOUR>
+template <bool HAS_VIDX, bool COMPACT>
 __global__ __launch_bounds__(kThreads) void gt_rowpick_kernel(EmitArgs a, ScanArgs sc, uint32_t n_seg)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_mem[];
@@ -191,22 +191,18 @@ __global__ __launch_bounds__(kThreads) void gt_rowpick_kernel(EmitArgs a, ScanAr
             row_out = a.out + row * a.out_stride;
         }
         const uint8_t *cd = codes;
-        if (FOUR) {
-            // four picks per chunk from ONE or two compact bytes, the fifth text from the next lane (flush_text4, gt_common.hip.h)
-            flush_text4<U>(
-                [cd](auto c0, uint32_t g, uint32_t &k0, uint32_t &k1, uint32_t &k2, uint32_t &k3) {
-                    constexpr uint32_t C0 = decltype(c0)::value;
-                    const uint32_t win = C0 == 0u ? (uint32_t)cd[g] : (uint32_t)cd[g] | ((uint32_t)cd[g + 1u] << 8);   // (the byte behind the record is slack)
-                    k0 = __builtin_amdgcn_ubfe(win, 2u * C0, 2u);
-                    k1 = __builtin_amdgcn_ubfe(win, 2u * C0 + 2u, 2u);
-                    k2 = __builtin_amdgcn_ubfe(win, 2u * C0 + 4u, 2u);
-                    k3 = __builtin_amdgcn_ubfe(win, 2u * C0 + 6u, 2u);
-                },
-                [cd](uint32_t r) -> uint32_t { return ((uint32_t)cd[r >> 2] >> ((r & 3u) * 2u)) & 3u; },
-                0u, row_out, 0ull, 4ull * K + 1ull, 0u, K, lane, sc.align_stores != 0u);
-        } else {
-            flush_codes<U>([cd](uint32_t r) { return ((uint32_t)cd[r >> 2] >> ((r & 3u) * 2u)) & 3u; }, 0u, row_out, 0ull, 4ull * K + 1ull, 0u, K, lane);
-        }
+        // four picks per chunk from ONE or two compact bytes, the fifth text from the next lane (flush_text4, gt_common.hip.h)
+        flush_text4<2>(
+            [cd](auto c0, uint32_t g, uint32_t &k0, uint32_t &k1, uint32_t &k2, uint32_t &k3) {
+                constexpr uint32_t C0 = decltype(c0)::value;
+                const uint32_t win = C0 == 0u ? (uint32_t)cd[g] : (uint32_t)cd[g] | ((uint32_t)cd[g + 1u] << 8);   // (the byte behind the record is slack)
+                k0 = __builtin_amdgcn_ubfe(win, 2u * C0, 2u);
+                k1 = __builtin_amdgcn_ubfe(win, 2u * C0 + 2u, 2u);
+                k2 = __builtin_amdgcn_ubfe(win, 2u * C0 + 4u, 2u);
+                k3 = __builtin_amdgcn_ubfe(win, 2u * C0 + 6u, 2u);
+            },
+            [cd](uint32_t r) -> uint32_t { return ((uint32_t)cd[r >> 2] >> ((r & 3u) * 2u)) & 3u; },
+            0u, row_out, 0ull, 4ull * K + 1ull, 0u, K, lane, sc.align_stores != 0u);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
     };
@@ -287,13 +283,8 @@ bool plan(const EmitArgs &a, const Tuning &t, int num_cus, bool compact, RowPick
     if (L.n_seg < 1u || L.n_seg > 4096u || a.record_size < 16u) return false;
     L.lds = table_bytes(a.kept_count) + rank_bytes(L.n_seg) + (uint32_t)kWaves * (kStageBytes + codes_bytes(a.kept_count));
     const bool g = gathered(a);
-    if (compact) L.kern = g ? gt_rowpick_kernel<true, true, 1, false> : gt_rowpick_kernel<false, true, 1, false>;
-    else if (t.scan_four_picks != 0)
-        L.kern = t.flush_unroll == 1 ? (g ? gt_rowpick_kernel<true, false, 1, true> : gt_rowpick_kernel<false, false, 1, true>)
-                                     : (g ? gt_rowpick_kernel<true, false, 2, true> : gt_rowpick_kernel<false, false, 2, true>);
-    else
-        L.kern = t.flush_unroll == 1 ? (g ? gt_rowpick_kernel<true, false, 1, false> : gt_rowpick_kernel<false, false, 1, false>)
-                                     : (g ? gt_rowpick_kernel<true, false, 2, false> : gt_rowpick_kernel<false, false, 2, false>);
+    if (compact) L.kern = g ? gt_rowpick_kernel<true, true> : gt_rowpick_kernel<false, true>;
+    else L.kern = g ? gt_rowpick_kernel<true, false> : gt_rowpick_kernel<false, false>;
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, L.kern, kThreads, L.lds) != hipSuccess || per_cu < 1) per_cu = 1;
     // two blocks per CU measure best on long records (the loads of 8 waves per CU already saturate the read path: tools/readbench.hip; 3:

@@ -7,10 +7,10 @@
 // three, gather kernel) and stages ITS SLICE of the kept list once, as u16 offsets in LDS: that
 // slice is the rank -> sample table.  Waves then walk rows: wide 16-B-per-lane loads of the
 // segment's record bytes (next row's loads in flight while this row's text goes out), parked in
-// the wave's LDS stage; the output-driven flush (flush_codes, gt_common.hip.h) gives every lane a
-// 16-byte-ALIGNED chunk of the row's output bytes: five table reads + five staged-byte reads,
-// text, funnel shift by the row's phase, one 16-B store — whole-line coalesced stores however
-// irregular the mask is.  Segment and row edges (partial chunks, '\n') go out as one byte-store
+// the wave's LDS stage; the output-driven flush (flush_text4, gt_common.hip.h) gives every lane a
+// 16-byte-ALIGNED chunk of the row's output bytes: four table entries in one LDS read, four
+// staged-byte reads, text aligned to the row's phase, one 16-B store — whole-line coalesced
+// stores however irregular the mask is.  Segment and row edges (partial chunks, '\n') go out as one byte-store
 // instruction per row piece.
 //
 // HBM traffic per row: the record once (R bytes, wide loads) + 4K+1 bytes of text; the kept list
@@ -18,8 +18,6 @@
 // (Round 1's first subset kernel — keep bitmap + popcount prefix in LDS, per-lane ctz compaction
 // into a code ring — measured 5-10 % behind the table pick at every density
 // (profiles/r01_kernel_sweeps.md) and was removed in round 2.)
-#include <type_traits>
-
 #include "gt_common.hip.h"
 #include "kernels.h"
 
@@ -57,8 +55,8 @@ constexpr uint32_t kStageBytes = kSegSamples / 4u;                   // one row'
 // cost 150-300 VALU instructions per store step there; this kernel has no
 // compaction at all (the idea of gt_pick.hip, per segment): the block's slice of the context's
 // kept list, as u16 offsets into the segment, IS the rank -> sample table in LDS; a wave parks a
-// row's 4 KiB of record bytes in its LDS stage and the output-driven flush (flush_codes) picks
-// every genotype straight from there: one table read + one staged-byte read per genotype.
+// row's 4 KiB of record bytes in its LDS stage and the output-driven flush (flush_text4) picks
+// every genotype straight from there: a quarter table read + one staged-byte read per genotype.
 // A row piece is >= 4 KiB of text here, so the one store drain per row piece is amortised.  Against the DENSE
 // instantiation of that kernel (> 75 % kept: whole record bytes per step) it was 4-6 % faster as well
 // (0.545 -> 0.566 of roofline at all-but-7 kept).
@@ -66,12 +64,12 @@ constexpr uint32_t kStageBytes = kSegSamples / 4u;                   // one row'
 // SLOWER at 0.33-5 % kept: this kernel wants few, fat waves; profiles/r02_kernel_sweeps.md.)
 constexpr uint32_t kPickMaxSegCodes = kSegSamples;             // up to a fully kept segment: 32 KiB of LDS for the table
 
-// FOUR (default): a table entry is 2 x position << 12 | byte offset (code by one v_bfe_u32); a chunk's four entries come with ONE
-// LDS read, it makes FOUR picks and takes its fifth genotype from the next lane (flush_text4, gt_common.hip.h): 40 VALU + 6.5 LDS
-// instructions per chunk where round 2's form (FOUR = false, kept for the A/B: entry = sample offset, five picks by shifts) has 70 +
-// 10.  Also tried (profiles/r03_kernel_sweeps.md §8): a 4-KiB byte -> text table in LDS (36 VALU + 15 LDS reads, LDS-bound),
-// bit-field extract alone (59 + 10), and a block-cooperative form with a loader wave (level).
-template <bool HAS_VIDX, uint32_t U, bool FOUR>
+// A table entry is 2 x position << 12 | byte offset (code by one v_bfe_u32); a chunk's four entries come with ONE LDS read, it makes
+// FOUR picks and takes its fifth genotype from the next lane (flush_text4, gt_common.hip.h): 40 VALU + 6.5 LDS instructions per
+// chunk where round 2's form (entry = sample offset, five picks by shifts; retired) had 70 + 10.  Also tried
+// (profiles/r03_kernel_sweeps.md §8): a 4-KiB byte -> text table in LDS (36 VALU + 15 LDS reads, LDS-bound), bit-field extract
+// alone (59 + 10), and a block-cooperative form with a loader wave (level).
+template <bool HAS_VIDX>
 __global__ __launch_bounds__(kThreads) void gt_scan_pick_kernel(EmitArgs a, ScanArgs sc, uint32_t n_seg, uint32_t row_groups, uint32_t xcd_groups, uint32_t bands)
 {
     __shared__ __attribute__((aligned(16))) uint16_t s_idx[kPickMaxSegCodes + 16];
@@ -117,7 +115,7 @@ __global__ __launch_bounds__(kThreads) void gt_scan_pick_kernel(EmitArgs a, Scan
     }
     for (uint32_t r = tid; r < seg_cnt + 16u; r += (uint32_t)kThreads) {
         const uint32_t s16 = r < seg_cnt ? a.kept_idx[seg_k0 + r] - seg * kSegSamples : 0u;  // 16 entries of slack for the flush's fifth code / second group
-        s_idx[r] = (uint16_t)(FOUR ? ((s16 & 3u) << 13) | (s16 >> 2) : s16);
+        s_idx[r] = (uint16_t)(((s16 & 3u) << 13) | (s16 >> 2));
     }
     __syncthreads();
     if (rows == 0ull) return;
@@ -163,37 +161,28 @@ __global__ __launch_bounds__(kThreads) void gt_scan_pick_kernel(EmitArgs a, Scan
         const uint64_t lo_emit = 4ull * seg_k0;
         const uint64_t hi_emit = 4ull * ((uint64_t)seg_k0 + seg_cnt) + (last_seg ? 1ull : 0ull);  // '\n' closes the row (:190)
         const uint16_t *idx = s_idx;
-        if (FOUR) {
-            auto code_of = [stage](uint32_t e, uint32_t byte_lo, uint32_t shift_lo) {   // entry in bits [byte_lo, byte_lo + 12) and [shift_lo, shift_lo + 3)
-                return __builtin_amdgcn_ubfe((uint32_t)stage[__builtin_amdgcn_ubfe(e, byte_lo, 12u)], __builtin_amdgcn_ubfe(e, shift_lo, 3u), 2u);   // src/pfile.rs:171-175
-            };
-            flush_text4<U>(
-                [idx, code_of](auto c0, uint32_t g, uint32_t &k0, uint32_t &k1, uint32_t &k2, uint32_t &k3) {
-                    constexpr uint32_t C0 = decltype(c0)::value;
-                    const uint32_t *grp = reinterpret_cast<const uint32_t *>(idx) + 2u * g;     // 8-byte aligned; the second group may be slack
-                    uint32_t p01, p23;                                                            // entries (r, r+1), (r+2, r+3)
-                    if (C0 == 0u) { p01 = grp[0]; p23 = grp[1]; }
-                    else if (C0 == 2u) { p01 = grp[1]; p23 = grp[2]; }
-                    else {
-                        const uint32_t w0 = grp[C0 == 1u ? 0 : 1], w1 = grp[C0 == 1u ? 1 : 2], w2 = grp[C0 == 1u ? 2 : 3];
-                        p01 = __builtin_amdgcn_alignbyte(w1, w0, 2u);
-                        p23 = __builtin_amdgcn_alignbyte(w2, w1, 2u);
-                    }
-                    k0 = code_of(p01, 0u, 12u);
-                    k1 = code_of(p01, 16u, 28u);
-                    k2 = code_of(p23, 0u, 12u);
-                    k3 = code_of(p23, 16u, 28u);
-                },
-                [idx, code_of](uint32_t r) -> uint32_t { return code_of(idx[r], 0u, 12u); },
-                0u, row_out, lo_emit, hi_emit, seg_k0, K, lane, sc.align_stores != 0u);
-        } else {
-            flush_codes<U>(
-                [stage, idx](uint32_t r) -> uint32_t {
-                    const uint32_t s16 = idx[r];  // r <= seg_cnt + 4: inside the slack
-                    return ((uint32_t)stage[s16 >> 2] >> ((s16 & 3u) * 2u)) & 3u;  // src/pfile.rs:171-175
-                },
-                0u, row_out, lo_emit, hi_emit, seg_k0, K, lane);
-        }
+        auto code_of = [stage](uint32_t e, uint32_t byte_lo, uint32_t shift_lo) {   // entry in bits [byte_lo, byte_lo + 12) and [shift_lo, shift_lo + 3)
+            return __builtin_amdgcn_ubfe((uint32_t)stage[__builtin_amdgcn_ubfe(e, byte_lo, 12u)], __builtin_amdgcn_ubfe(e, shift_lo, 3u), 2u);   // src/pfile.rs:171-175
+        };
+        flush_text4<2>(
+            [idx, code_of](auto c0, uint32_t g, uint32_t &k0, uint32_t &k1, uint32_t &k2, uint32_t &k3) {
+                constexpr uint32_t C0 = decltype(c0)::value;
+                const uint32_t *grp = reinterpret_cast<const uint32_t *>(idx) + 2u * g;     // 8-byte aligned; the second group may be slack
+                uint32_t p01, p23;                                                            // entries (r, r+1), (r+2, r+3)
+                if (C0 == 0u) { p01 = grp[0]; p23 = grp[1]; }
+                else if (C0 == 2u) { p01 = grp[1]; p23 = grp[2]; }
+                else {
+                    const uint32_t w0 = grp[C0 == 1u ? 0 : 1], w1 = grp[C0 == 1u ? 1 : 2], w2 = grp[C0 == 1u ? 2 : 3];
+                    p01 = __builtin_amdgcn_alignbyte(w1, w0, 2u);
+                    p23 = __builtin_amdgcn_alignbyte(w2, w1, 2u);
+                }
+                k0 = code_of(p01, 0u, 12u);
+                k1 = code_of(p01, 16u, 28u);
+                k2 = code_of(p23, 0u, 12u);
+                k3 = code_of(p23, 16u, 28u);
+            },
+            [idx, code_of](uint32_t r) -> uint32_t { return code_of(idx[r], 0u, 12u); },
+            0u, row_out, lo_emit, hi_emit, seg_k0, K, lane, sc.align_stores != 0u);
         // the stage is rewritten by the next row: this row's reads must have returned first
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -391,14 +380,7 @@ hipError_t launch_gt_scan(const EmitArgs &a, const ScanArgs &sc, const Tuning &t
         hipLaunchKernelGGL(ckern, dim3((uint32_t)(groups * n_seg_eff)), dim3(kThreads), 0, stream, a, sc, n_seg_eff, (uint32_t)groups, xcd_groups);
         return hipGetLastError();
     }
-    typedef void (*Kern)(EmitArgs, ScanArgs, uint32_t, uint32_t, uint32_t, uint32_t);
-    const bool g = gathered(a);
-    auto by_mode = [&](auto u) -> Kern {
-        constexpr uint32_t U = decltype(u)::value;
-        if (t.scan_four_picks != 0) return g ? gt_scan_pick_kernel<true, U, true> : gt_scan_pick_kernel<false, U, true>;
-        return g ? gt_scan_pick_kernel<true, U, false> : gt_scan_pick_kernel<false, U, false>;
-    };
-    Kern kern = t.flush_unroll == 1 ? by_mode(std::integral_constant<uint32_t, 1>{}) : t.flush_unroll == 4 ? by_mode(std::integral_constant<uint32_t, 4>{}) : by_mode(std::integral_constant<uint32_t, 2>{});
+    void (*kern)(EmitArgs, ScanArgs, uint32_t, uint32_t, uint32_t, uint32_t) = gathered(a) ? gt_scan_pick_kernel<true> : gt_scan_pick_kernel<false>;
     const int preferred = (uint64_t)a.kept_count * 170ull >= (uint64_t)a.sample_count ? 2 : 0;
     uint64_t groups = (uint64_t)resident_blocks(kern, kThreads, num_cus, t, preferred) / n_seg_eff;  // floor: never a partial second round
     if (groups < 1ull) groups = 1ull;  // more segments than resident blocks (N > ~16 M samples): rounds are unavoidable

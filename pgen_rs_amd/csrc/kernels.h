@@ -39,16 +39,13 @@ struct Tuning {
     int wide_ranges = 0;           // stream kernel: work-queue ranges = write fronts of a launch (power of two <= 64); 0 = by shape (8 for rows of several spans, else 2)
     int flat_blocks_per_cu = 64;   // flat kernel: grid cap
     int scan_blocks_per_cu = 0;    // segment kernel: 0 = the measured rule (2 from ~0.6 % kept, else what the occupancy API says)
-    int pick_line_seams = 1;       // pick family, full lines of dense records: interiors + seams in one kernel (0 = round 2's row-by-row flush)
     int pick_batch_bytes = 32768;  // short-record pick kernel: text per batch (one store drain per batch)
     int scan_xcd_map = 1;          // segment kernels: all blocks of a row group on one XCD (seam lines merge in one L2); 0 = plain map
     int scan_chunk_rows = 0;       // two-pass path: rows per chunk (0 = as many as the launch's 32-MiB compact-scratch slice holds; tests force small chunks)
     int scan_two_pass = 1;         // sparse keeps on long records: compact pass + all-samples pass (0 = single-pass segment kernel)
     int rowpick_blocks_per_cu = 0; // row-owner kernel: cap on resident blocks per CU (0 = what the occupancy API says)
-    int scan_rowpick = 1;          // (1: row-owner compact pass + all-samples pass; 2: row-owner single pass; 0: segment compact pass)
-         // sparse keeps on long records, many rows: one wave per row, one pass (0 = the segment kernels / two passes)
-    int flush_unroll = 2;          // segment / row-owner kernels: 16-byte chunks per lane and step of the text flush (1 or 2)
-    int scan_four_picks = 1;       // segment / row-owner kernels' text flush: four picks per chunk + the fifth text from the next lane (0 = round 2's five picks)
+    int scan_rowpick = 1;          // kept subsets on long records, many rows: the row-owner kernel where it measures ahead (its single pass, or its
+                                   // compact pass of the two passes); 0 = never (the segment kernels: single pass or segment compact pass)
     int align_stores = 1;          // subset kernels: lanes <-> chunks shifted so that every store instruction covers whole 128-byte lines (0 = from the first whole chunk)
     int runs_rows = 0;             // RUNS mode of the stream kernel: rows per work item (0 = as many as one wide load / one span holds)
 };

@@ -136,10 +136,10 @@ class Tune:
     scan_chunk_rows: int = 0
     scan_xcd_map: int = 0        # < 0: plain block map
     scan_two_pass: int = 0       # < 0: single pass
-    scan_rowpick: int = 0        # < 0: never the row owner, 2: also across the two-pass band
+    scan_rowpick: int = 0        # < 0: never the row owner
 
     def rowpick_mode(self) -> int:
-        return 0 if self.scan_rowpick < 0 else 2 if self.scan_rowpick == 2 else 1
+        return 0 if self.scan_rowpick < 0 else 1
 
     def knobs(self) -> dict:
         return {name: value for name, value in self.__dict__.items() if value}
@@ -190,8 +190,6 @@ def very_sparse(n: int, k: int) -> bool:
 def rowpick_shape(n: int, k: int, v: int, tune: Tune, num_cus: int) -> bool:
     if tune.rowpick_mode() == 0 or n <= SEG_SAMPLES or very_sparse(n, k) or not rowpick_applicable(n, k, v, num_cus):
         return False
-    if tune.rowpick_mode() == 2 and two_pass_shape(n, k):
-        return True
     if n < 24576:
         return True
     return k * 50 >= n and k * 5 <= n

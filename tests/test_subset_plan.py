@@ -47,7 +47,7 @@ def test_mirrored_constants_match_the_sources():
     assert (SP.SCAN_OCCUPANCY, SP.COMPACT_OCCUPANCY) == (3, 5)
 
 
-def test_mirrored_dispatch_matches_the_source():
+def test_mirrored_dispatch_matches_capi():
     """capi.hip: the literals of two_pass_shape, very_sparse, rowpick_shape and two_pass, the chunk rounding of dispatch_two_pass,
     and the AUTO arms; a new condition in any of them changes its branch count and fails here until subset_plan.py and the cells
     follow."""
@@ -60,9 +60,8 @@ def test_mirrored_dispatch_matches_the_source():
     b = _body("capi.hip", "static bool rowpick_shape(const pgenhip_ctx *ctx, const EmitArgs &a)")
     assert ("if (ctx->tune.scan_rowpick == 0 || ctx->sample_count <= kScanSegmentSamples || very_sparse(ctx) || "
             "!gt_rowpick_applicable(a, ctx->num_cus)) return false;") in b
-    assert "if (ctx->tune.scan_rowpick == 2 && two_pass_shape(ctx->sample_count, ctx->kept_count)) return true;" in b
     assert "if (N < 24576ull) return true;" in b and "return K * 50ull >= N && K * 5ull <= N;" in b
-    assert _conditions(b) == 8
+    assert _conditions(b) == 6
     b = _body("capi.hip", "static bool two_pass(const pgenhip_ctx *ctx, const EmitArgs &a)")
     assert ("ctx->tune.scan_two_pass != 0 && ctx->d_compact != nullptr && a.kept_idx != nullptr && a.record_size >= 16u &&\n"
             "           ctx->max_seg_count <= kCompactMaxSegCodes &&\n"
@@ -95,7 +94,7 @@ def test_mirrored_dispatch_matches_the_source():
     assert _src("capi.hip").count("if (!ctx->subset || ctx->record_size < 16u || ctx->kept_count < 1u || ctx->kept_count > kRowPickMaxKept)") == 2
 
 
-def test_mirrored_segment_plan_matches_the_source():
+def test_mirrored_segment_plan_and_knobs_match_the_source():
     b = _body("gt_scan.hip", "hipError_t launch_gt_scan(")
     assert "const uint32_t n_seg = (a.sample_count + kSegSamples - 1u) / kSegSamples;" in b
     assert "const uint64_t groups_needed = ((uint64_t)a.n_variants + kWaves - 1ull) / kWaves;" in b
@@ -115,7 +114,7 @@ def test_mirrored_segment_plan_matches_the_source():
     tune = _src("capi.hip")
     assert "case PGENHIP_KNOB_SCAN_XCD_MAP: t.scan_xcd_map = value < 0 ? 0 : 1; break;" in tune
     assert "case PGENHIP_KNOB_SCAN_TWO_PASS: t.scan_two_pass = value < 0 ? 0 : 1; break;" in tune
-    assert "case PGENHIP_KNOB_SCAN_ROWPICK: t.scan_rowpick = value < 0 ? 0 : (value == 2 ? 2 : 1); break;" in tune
+    assert "case PGENHIP_KNOB_SCAN_ROWPICK: t.scan_rowpick = value < 0 ? 0 : 1; break;" in tune
 
 
 def test_mirrored_row_owner_plan_matches_the_source():
