@@ -3,6 +3,7 @@
 
     python bench.py --gpus 1 --steps K --warmup W                      # BASELINE configs[2]: 100 000 x 500 000, K = N
     python bench.py --config {c3,chr22,c4,c5,c4shard,c5shard,basic2}   # the other named shapes
+    python bench.py --gpus 1 --steps K --warmup W --full               # + every measurement and check outside the headline
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W         # BASELINE configs[3]: 1 M x 500 000, variant-sharded
 
@@ -19,17 +20,23 @@ as a D2H pipeline would).
 never imports torch or touches a GPU — runs `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a
 CHILD process, relays its output and returns its exit code (never a re-exec).
 
+A plain run does only what the headline needs: it sets up the records and the output buffer, warms up, times the steps,
+writes `--dump-outputs` if asked and prints the line.  `--full` adds, outside the timed region, `host_delivered`,
+`self_check`, `secondary`, `cpu_baseline` and the live `roofline.traffic` passes (each can still be left out with its
+`--no-*` flag); without it `roofline.traffic` comes from the committed profile of the same shape, if there is one.
+
 One JSON line on stdout (rank 0).  Besides the contract's keys:
   `roofline`       HBM; algorithmic bytes (R + 4K + 1 per variant) / hipEvent time on the
                    kernel's stream; per-step event pairs give min / median / max (the output buffer's
                    physical placement moves a launch by 5-9 % between processes, DESIGN.md §4);
-                   `traffic` MEASURED IN THE RUN by two child passes under rocprofv3 --pmc (FETCH_SIZE, WRITE_SIZE);
-                   if the profiler is not available: from the committed PMC passes of the same shape (profiles/r0*/pmc_summary.json)
-  `cpu_baseline`   the oracle's literal restatement of the reference loop, 1 core, same N, bounded V
-  `host_delivered` PCIe-inclusive rate (pinned host records -> H2D || kernel || D2H -> pinned host text),
+                   `traffic` with --full MEASURED IN THE RUN by two child passes under rocprofv3 --pmc (FETCH_SIZE, WRITE_SIZE);
+                   otherwise, or if the profiler is not available: from the committed PMC passes of the same shape
+                   (profiles/r0*/pmc_summary.json)
+  `cpu_baseline`   --full: the oracle's literal restatement of the reference loop, 1 core, same N, bounded V
+  `host_delivered` --full: PCIe-inclusive rate (pinned host records -> H2D || kernel || D2H -> pinned host text),
                    measured OUTSIDE the timed region; it is never `value`
-  `self_check`     structure of every row + a torch re-encode round trip on sampled rows (no oracle here)
-  `secondary`      the other BASELINE shapes, a few steps each AFTER the headline and outside its timed region:
+  `self_check`     --full: structure of every row + a torch re-encode round trip on sampled rows (no oracle here)
+  `secondary`      --full: the other BASELINE shapes, a few steps each AFTER the headline and outside its timed region:
                    N = 1: `c5shard` (north_star's ">= 50 % of the HBM-read roofline on the 2-bit unpack" lives here:
                    `read_only_frac`), `chr22`, `basic2`;  N > 1: `c5` (configs[4]) on the ranks' resident c4 records
   `dump_outputs`   with `--dump-outputs DIR` only: what the headline's last timed step wrote, as DIR/gt_text.npy
@@ -420,8 +427,7 @@ def measure_traffic_live(argv_shape: list[str], timeout_s: int = 300):
     if not Path(rocprof).exists():
         raise RuntimeError("rocprofv3 not found")
     per_call = {}
-    child_args = [sys.executable, str(Path(__file__).resolve()), *argv_shape, "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-host-delivered",
-                  "--no-secondary", "--no-live-traffic"]
+    child_args = [sys.executable, str(Path(__file__).resolve()), *argv_shape, "--steps", "2", "--warmup", "1"]  # a plain run: the workload alone
     env = dict(os.environ, TMPDIR="/tmp")
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix=f"pgenhip_pmc_{counter.lower()}_", dir="/tmp")
@@ -464,11 +470,13 @@ def main() -> int:
                     help="value distribution of the synthetic records (SURVEY.md §8d): uniform 2-bit codes, or per-variant allele "
                          "frequencies with Hardy-Weinberg genotype proportions and 0.1 %% missing (mostly 0/0, like real data)")
     ap.add_argument("--max-launch-variants", type=int, default=0, help="cap on variants per launch (0 = as many as fit in HBM)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-delivered", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: host_delivered, self_check, secondary, cpu_baseline and the live roofline.traffic passes")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-host-delivered", action="store_true", help="with --full: skip host_delivered")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not measure roofline.traffic with child rocprofv3 --pmc passes; read it from the committed profile of the same shape")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the `secondary` block (the other BASELINE shapes after the headline)")
+                    help="with --full: do not measure roofline.traffic with child rocprofv3 --pmc passes; read it from the committed profile of the same shape")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the `secondary` block (the other BASELINE shapes after the headline)")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, one rank per GPU) or gloo (rehearsal of the N>1 path)")
     ap.add_argument("--all-ranks-on-device0", action="store_true",
                     help="rehearsal only: every rank uses cuda:0 (with --dist-backend gloo) so the N>1 code path can run on a 1-GPU box")
@@ -532,7 +540,7 @@ def main() -> int:
     # PCIe-inclusive rate first, on its own small buffers (measured outside the timed region; done before the big
     # allocations so that it does not run beside the driver unmapping 200 GB of freed output buffer)
     hd = None
-    if world == 1 and rank == 0 and not args.no_host_delivered and v > 0:
+    if args.full and world == 1 and rank == 0 and not args.no_host_delivered and v > 0:
         hd = host_delivered(torch, pgen_rs_amd, local_rank, n, kept, v, hwe=hwe)
         torch.cuda.synchronize(dev)
         torch.cuda.empty_cache()
@@ -571,13 +579,13 @@ def main() -> int:
     dt_max, event_ms_max = float(t_all[0]), float(t_all[1])
 
     check = None
-    if rank == 0 and v > 0:
+    if args.full and rank == 0 and v > 0:
         last_nb = v - (n_launch - 1) * v_launch  # rows the last launch of a step left in `out`
         check = self_check(torch, recs[(n_launch - 1) * v_launch * r :], out, last_nb, n, r, k, kept, row_bytes)
 
     # ---- secondary: the other BASELINE shapes, after the headline and outside its timed region ------------------
     secondary = None
-    if not args.no_secondary and not custom_geometry and args.kernel == 0:  # (a custom VARIANT count keeps it: tests rehearse it small)
+    if args.full and not args.no_secondary and not custom_geometry and args.kernel == 0:  # (a custom VARIANT count keeps it: tests rehearse it small)
         sec_steps = max(3, min(args.steps, 5))
         if world == 1 and cfg_name == "c3":
             # one GPU: north_star's second target (>= 50 % of the HBM-READ roofline on the unpack) is physical only where few samples are
@@ -630,7 +638,7 @@ def main() -> int:
         launch_ms = event_ms_max / launches                    # max-over-ranks event time / launches per rank
         achieved_gbs = alg_bytes_per_step / (event_ms_max / args.steps * 1e-3) / 1e9
         traffic, traffic_note = None, None
-        if world == 1 and not args.no_live_traffic:
+        if args.full and world == 1 and not args.no_live_traffic:
             # live: free this process's buffers first, the children need the same HBM
             recs = out = None
             torch.cuda.synchronize(dev)
@@ -700,15 +708,16 @@ def main() -> int:
                 "frac_step_median": alg_bytes_per_step / (med * 1e-3) / 1e9 / HBM_PEAK_GBS,
                 "frac_step_worst": alg_bytes_per_step / (max(step_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS,
             },
-            "self_check": check,
         }
+        if check is not None:
+            line["self_check"] = check
         if secondary is not None:
             line["secondary"] = secondary
         if hd is not None:
             line["host_delivered"] = hd
         if dump is not None:
             line["dump_outputs"] = dump
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(n, kept)
         print(json.dumps(line), flush=True)
 

@@ -23,8 +23,8 @@ REPO = Path(__file__).resolve().parent.parent
 ])
 def test_dump_outputs_equal_the_oracle(tmp_path, config, n, v, keep_mod, max_launch):
     p = subprocess.run([sys.executable, str(REPO / "bench.py"), "--config", config, "--variants", str(v), "--keep-modulus", str(keep_mod),
-                        "--max-launch-variants", str(max_launch), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-host-delivered",
-                        "--no-live-traffic", "--no-secondary", "--dump-outputs", str(tmp_path / "dump")],
+                        "--max-launch-variants", str(max_launch), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
+                        "--no-host-delivered", "--no-live-traffic", "--no-secondary", "--dump-outputs", str(tmp_path / "dump")],
                        capture_output=True, text=True, timeout=600, cwd=str(REPO))
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])

@@ -55,7 +55,7 @@ def test_bench_multi_rank_path_rehearsal():
     """bench.py's N > 1 code path (strong-scaled shards of one workload, barrier, MAX-reduce of the timings, one JSON
     line on rank 0) with 2 ranks on device 0 over gloo, on a small custom shape."""
     p = _torchrun(2, REPO / "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--dist-backend", "gloo", "--all-ranks-on-device0",
-                  "--config", "chr22", "--variants", "200001", "--no-cpu-baseline", "--no-host-delivered")
+                  "--config", "chr22", "--variants", "200001", "--full", "--no-cpu-baseline", "--no-host-delivered")
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["steps"] == 3
@@ -74,7 +74,8 @@ def test_bench_plain_invocation_starts_its_own_ranks():
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--dist-backend", "gloo",
-                        "--all-ranks-on-device0", "--config", "c4", "--variants", "4001"], capture_output=True, text=True, timeout=900, cwd=str(REPO), env=env)
+                        "--all-ranks-on-device0", "--config", "c4", "--variants", "4001", "--full"], capture_output=True, text=True, timeout=900, cwd=str(REPO),
+                       env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -93,8 +94,8 @@ def test_bench_plain_invocation_starts_its_own_ranks():
 def test_bench_single_gpu_line_carries_the_secondary_shapes():
     """N = 1 on the c3 preset (small variant count): `secondary` holds configs[4]'s per-GPU shard (north_star's HBM-read target),
     the chr22 block and the reference's own dataset shape, each self-checked, measured after the headline."""
-    p = subprocess.run([sys.executable, str(REPO / "bench.py"), "--steps", "2", "--warmup", "1", "--variants", "3001", "--no-cpu-baseline", "--no-host-delivered"],
-                       capture_output=True, text=True, timeout=900, cwd=str(REPO))
+    p = subprocess.run([sys.executable, str(REPO / "bench.py"), "--steps", "2", "--warmup", "1", "--variants", "3001", "--full", "--no-cpu-baseline",
+                        "--no-host-delivered"], capture_output=True, text=True, timeout=900, cwd=str(REPO))
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     # roofline.traffic is measured IN the run (two child passes under rocprofv3 --pmc) when the profiler is there: within a few per cent
@@ -111,6 +112,19 @@ def test_bench_single_gpu_line_carries_the_secondary_shapes():
         assert s["self_check_ok"] and s["ms_per_step"] > 0 and 0 < s["frac"] < 1, name
     assert sec["c5shard"]["variants"] == 125_000 and sec["c5shard"]["samples"] == 500_000 and 4000 < sec["c5shard"]["kept_samples"] < 6000
     assert sec["c5shard"]["read_only_frac"] > 0.3   # the target is 0.5; this only guards against a broken measurement
+
+
+def test_bench_plain_line_is_the_headline_alone():
+    """Without --full the same N = 1 c3 run is the headline alone: no self-check, no secondary shapes, no PCIe or CPU runs and no
+    profiler passes; roofline.traffic falls back to the committed profile (none matches this custom shape)."""
+    p = subprocess.run([sys.executable, str(REPO / "bench.py"), "--steps", "2", "--warmup", "1", "--variants", "3001"],
+                       capture_output=True, text=True, timeout=600, cwd=str(REPO))
+    assert p.returncode == 0, p.stderr[-3000:]
+    line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["config"]["variants_total"] == 3001 and line["config"]["samples"] == 500_000
+    assert not {"self_check", "secondary", "host_delivered", "cpu_baseline", "dump_outputs"} & set(line)
+    assert line["roofline"]["traffic"] is None and "measured in this run" not in line["roofline"]["traffic_note"]
 
 
 def test_cli_two_gpus_two_shards(tmp_path):
