@@ -228,6 +228,33 @@ int pgenhip_genotype_counts(pgenhip_ctx *ctx, const void *d_records, uint64_t re
 int pgenhip_genotype_counts_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
                                uint32_t *d_counts, uint32_t flags);
 
+/* ---- per-sample genotype counts (device-resident, asynchronous on the ctx stream) ----
+ * The other half of pgenhip_genotype_counts: for every kept sample, the number of selected rows in which it has each code.
+ * Rows are selected exactly as in pgenhip_genotype_counts / pgenhip_genotype_counts_at (and pgenhip_decode_emit); each selected
+ * row counts once per appearance, so a gather that repeats a row counts it twice.  Writes four u32 per kept sample at
+ * d_counts[4*k + c]: k is the sample's rank in the ctx's kept list (its index when all samples are kept), c is 0 hom-ref ("0/0"),
+ * 1 het ("0/1"), 2 hom-alt ("1/1"), 3 missing ("./."), the order of the per-variant counts.  The pad bits of a record's last
+ * byte are never counted.  Records may start at any byte alignment, with record_stride >= R (or n_variants <= 1).
+ *   - Without PGENHIP_SCOUNT_ACCUMULATE the call overwrites d_counts[0 .. 4K) (zeros when n_variants == 0).  With it the counts
+ *     are added to what d_counts holds, so a host can sum blocks of rows in place; n_variants == 0 is then a no-op.
+ *   - Nothing outside d_counts[0 .. 4K) is written; K == 0 writes nothing.  d_counts must be 4-byte aligned, else
+ *     PGENHIP_ERR_BAD_ARG.
+ *   - Counts wrap modulo 2^32 only if one sample is counted more than 2^32 - 1 times, which takes repeated rows (a file's
+ *     variant count is a u32).
+ * Same launch contract as pgenhip_genotype_counts: device pointers only, no allocation, no synchronisation, queued on the ctx
+ * stream, graph-capturable.
+ * flags: a shape (PGENHIP_SCOUNT_AUTO or a forced one) | PGENHIP_SCOUNT_ACCUMULATE. */
+#define PGENHIP_SCOUNT_AUTO 0u
+/* 1u is reserved for a dense byte-stream shape (columns fixed modulo lcm(R, 16)); not built */
+#define PGENHIP_SCOUNT_ROWS 2u        /* row by row, any layout (variant_idx, record_off, padded strides): what AUTO takes */
+#define PGENHIP_SCOUNT_SHAPE_MASK 0xFu
+#define PGENHIP_SCOUNT_ACCUMULATE 0x10u
+int pgenhip_sample_counts(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                          uint32_t n_variants, uint32_t *d_counts, uint32_t flags);
+/* Same, with the record of row j at d_base + d_record_off[j] (DEVICE array of u64 byte offsets). */
+int pgenhip_sample_counts_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
+                             uint32_t *d_counts, uint32_t flags);
+
 /* Launch-shape knobs of one ctx (tests force small grids to exercise ring re-use; A/B probes).
  * value 0 restores the built-in default of a knob unless noted. */
 typedef enum pgenhip_knob {
@@ -245,6 +272,7 @@ typedef enum pgenhip_knob {
     /* 13-15 selected flush forms AUTO never took (row-by-row full lines, 1 / 4 chunks per lane and step, five picks per chunk):
        retired, refused with PGENHIP_ERR_BAD_ARG, never reused */
     PGENHIP_KNOB_ALIGN_STORES = 16,      /* subset kernels (segment, row-owner, pick): 1 (default) lanes <-> chunks shifted so that every store instruction covers whole 128-byte lines, -1 from the run's first whole chunk */
+    PGENHIP_KNOB_SCOUNT_SLICES = 17,     /* per-sample counts: row ranges per column tile, each summed by one block (default 0 = as many as fill the chip's resident blocks) */
     PGENHIP_KNOB_RUNS_ROWS = 7           /* RUNS kernel: rows per work item (default: as many as one wide load / one span holds) */
 } pgenhip_knob;
 int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value);

@@ -43,6 +43,11 @@ KERNEL_ROWPICK = 8
 COUNT_AUTO = 0
 COUNT_WAVE_PER_ROW = 1
 COUNT_ROWS_PER_WAVE = 2
+
+SCOUNT_AUTO = 0
+SCOUNT_ROWS = 2
+SCOUNT_SHAPE_MASK = 0xF
+SCOUNT_ACCUMULATE = 0x10
 SYNTH_DIRTY_PAD = 1
 SYNTH_HWE = 2
 CREATE_KEEP_LIST = 1
@@ -60,6 +65,7 @@ KNOB_SCAN_CHUNK_ROWS = 10
 KNOB_ROWPICK_BLOCKS_PER_CU = 11
 KNOB_SCAN_ROWPICK = 12
 KNOB_ALIGN_STORES = 16
+KNOB_SCOUNT_SLICES = 17
 
 
 
@@ -101,6 +107,8 @@ PROTOTYPES = {
     "pgenhip_emit_lines": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]),
     "pgenhip_genotype_counts": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_genotype_counts_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
+    "pgenhip_sample_counts": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
+    "pgenhip_sample_counts_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_tune": (C.c_int, [ctx_p, C.c_uint32, C.c_int32]),
     "pgenhip_wait": (C.c_int, [ctx_p]),
     "pgenhip_timer_start": (C.c_int, [ctx_p]),

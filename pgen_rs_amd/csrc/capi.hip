@@ -25,6 +25,7 @@ struct pgenhip_ctx {
     bool identity = false;             // a kept list that names every sample: AUTO takes the all-samples kernels
     uint32_t *d_kept = nullptr;
     uint8_t *d_count_mask = nullptr;   // genotype counts with a kept subset: the kept samples as a 2-bit mask (gt_count.hip)
+    uint32_t *d_scount_rank = nullptr; // per-sample counts with that mask: kept samples before each 64-sample chunk (gt_scount.hip)
     uint32_t *d_seg_rank = nullptr;    // segment kernels: kept samples before each segment
     uint32_t max_seg_count = 0;        // segment kernels: most kept samples in one segment
     uint8_t *d_compact = nullptr;      // two-pass path for sparse keeps on long records: compact records of one chunk of rows,
@@ -172,6 +173,12 @@ int pgenhip_create(pgenhip_ctx **out, int device_ordinal, uint32_t sample_count,
                 for (uint32_t k = 0; k < kept_count; k++) mask[16u + kept_idx[k] / 4u] |= (uint8_t)(1u << (2u * (kept_idx[k] % 4u)));
                 if ((e = hipMalloc(reinterpret_cast<void **>(&ctx->d_count_mask), mask.size())) != hipSuccess) { rc = fail_hip(e, "hipMalloc(count mask)"); break; }
                 if ((e = hipMemcpy(ctx->d_count_mask, mask.data(), mask.size(), hipMemcpyHostToDevice)) != hipSuccess) { rc = fail_hip(e, "hipMemcpy(count mask)"); break; }
+                // per-sample counts: a sample's rank = kept samples before its 64-sample chunk + the mask bits below it in the chunk
+                std::vector<uint32_t> rank((size_t)(sample_count + 63u) / 64u + 1u, 0u);
+                for (uint32_t k = 0; k < kept_count; k++) rank[(size_t)(kept_idx[k] / 64u) + 1u]++;
+                for (size_t q = 1; q < rank.size(); q++) rank[q] += rank[q - 1u];
+                if ((e = hipMalloc(reinterpret_cast<void **>(&ctx->d_scount_rank), rank.size() * sizeof(uint32_t))) != hipSuccess) { rc = fail_hip(e, "hipMalloc(sample ranks)"); break; }
+                if ((e = hipMemcpy(ctx->d_scount_rank, rank.data(), rank.size() * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess) { rc = fail_hip(e, "hipMemcpy(sample ranks)"); break; }
             }
             // two-pass path (sparse keeps on long records): scratch for the compact records of one chunk of rows per launch in flight
             // (config 5's per-GPU shard, 125 000 rows x 1 250 bytes, is five chunks; a chunk stays in the 256-MiB Infinity Cache
@@ -199,6 +206,7 @@ int pgenhip_destroy(pgenhip_ctx *ctx)
     if (ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
     if (ctx->d_kept) (void)hipFree(ctx->d_kept);
     if (ctx->d_count_mask) (void)hipFree(ctx->d_count_mask);
+    if (ctx->d_scount_rank) (void)hipFree(ctx->d_scount_rank);
     if (ctx->d_work) (void)hipFree(ctx->d_work);
     if (ctx->d_seg_rank) (void)hipFree(ctx->d_seg_rank);
     if (ctx->d_compact) (void)hipFree(ctx->d_compact);
@@ -620,6 +628,52 @@ int pgenhip_genotype_counts_at(pgenhip_ctx *ctx, const void *d_base, const uint6
     return genotype_counts_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, d_counts, flags);
 }
 
+static int sample_counts_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                              const uint64_t *d_record_off, uint32_t n_variants, uint32_t *d_counts, uint32_t flags)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (flags & ~(PGENHIP_SCOUNT_SHAPE_MASK | PGENHIP_SCOUNT_ACCUMULATE)) return fail(PGENHIP_ERR_BAD_ARG, "unknown sample_counts flag");
+    const uint32_t shape = flags & PGENHIP_SCOUNT_SHAPE_MASK;
+    if (shape != PGENHIP_SCOUNT_AUTO && shape != PGENHIP_SCOUNT_ROWS) return fail(PGENHIP_ERR_BAD_ARG, "sample_counts supports shapes AUTO and ROWS");
+    const bool accumulate = (flags & PGENHIP_SCOUNT_ACCUMULATE) != 0u;
+    const uint32_t K = ctx->kept_count;
+    if (K == 0u) return PGENHIP_OK;   // nothing to write
+    if (!d_counts) return fail(PGENHIP_ERR_BAD_ARG, "d_counts is NULL");
+    if ((uintptr_t)d_counts & 3u) return fail(PGENHIP_ERR_BAD_ARG, "d_counts is not 4-byte aligned");
+    if (n_variants && ctx->record_size && !d_records) return fail(PGENHIP_ERR_BAD_ARG, "d_records is NULL");
+    if (n_variants > 1 && !d_variant_idx && !d_record_off && record_stride < ctx->record_size)
+        return fail(PGENHIP_ERR_BAD_ARG, "record_stride < record size");
+    if (!accumulate) HIP_TRY(hipMemsetAsync(d_counts, 0, 16ull * K, ctx->stream));   // the kernel only adds
+    if (n_variants == 0) return PGENHIP_OK;
+    ScountArgs a;
+    a.records = static_cast<const uint8_t *>(d_records);
+    a.record_stride = record_stride;
+    a.variant_idx = d_variant_idx;
+    a.record_off = d_record_off;
+    a.n_variants = n_variants;
+    a.sample_count = ctx->sample_count;
+    a.record_size = ctx->record_size;
+    a.kept_mask = ctx->d_count_mask;   // NULL with all samples kept or an identity list
+    a.kept_rank = ctx->d_scount_rank;
+    a.counts = d_counts;
+    HIP_TRY(launch_gt_scount(a, ctx->tune.scount_slices, ctx->num_cus, ctx->stream));
+    return PGENHIP_OK;
+}
+
+int pgenhip_sample_counts(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                          uint32_t n_variants, uint32_t *d_counts, uint32_t flags)
+{
+    return sample_counts_core(ctx, d_records, record_stride, d_variant_idx, nullptr, n_variants, d_counts, flags);
+}
+
+int pgenhip_sample_counts_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
+                             uint32_t *d_counts, uint32_t flags)
+{
+    if (ctx && n_variants && !d_record_off) return fail(PGENHIP_ERR_BAD_ARG, "d_record_off is NULL");
+    return sample_counts_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, d_counts, flags);
+}
+
 int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)
 {
     if (!ctx) return fail(PGENHIP_ERR_BAD_ARG, "ctx is NULL");
@@ -641,6 +695,7 @@ int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)
         case PGENHIP_KNOB_SCAN_ROWPICK: t.scan_rowpick = value < 0 ? 0 : 1; break;
         case PGENHIP_KNOB_ALIGN_STORES: t.align_stores = value < 0 ? 0 : 1; break;
         case PGENHIP_KNOB_RUNS_ROWS: t.runs_rows = value > 0 ? value : d.runs_rows; break;
+        case PGENHIP_KNOB_SCOUNT_SLICES: t.scount_slices = value > 0 ? value : d.scount_slices; break;
         default: return fail(PGENHIP_ERR_BAD_ARG, "unknown knob");
     }
     return PGENHIP_OK;

@@ -139,6 +139,39 @@ typedef uint32_t gt_v4u __attribute__((ext_vector_type(4)));
 // alternated on one box, profiles/r03_logs/subset_nt_stores_ab.log: level to +3 %)
 __device__ __forceinline__ void subset_store16(uint8_t *dst, gt_v4u v) { __builtin_nontemporal_store(v, reinterpret_cast<gt_v4u *>(dst)); }
 
+// ---- shared by the count kernels (gt_count.hip, gt_scount.hip) ---------------------------------
+// aligned non-temporal 16-byte record load
+__device__ __forceinline__ gt_v4u load_nt16(const uint8_t *p) { return __builtin_nontemporal_load(reinterpret_cast<const gt_v4u *>(p)); }
+
+// 16 bytes at byte offset o (0 .. 16) of the 32-byte pair {a (low), b (high)}: whole dwords first, then v_alignbyte_b32
+__device__ __forceinline__ gt_v4u funnel16(gt_v4u a, gt_v4u b, uint32_t o)
+{
+    const uint32_t q = o >> 2, s = o & 3u;
+    uint32_t e[5];
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+        const uint32_t d0 = j == 0 ? a[0] : j == 1 ? a[1] : j == 2 ? a[2] : j == 3 ? a[3] : b[0];
+        const uint32_t d1 = j == 0 ? a[1] : j == 1 ? a[2] : j == 2 ? a[3] : j == 3 ? b[0] : b[1];
+        const uint32_t d2 = j == 0 ? a[2] : j == 1 ? a[3] : j == 2 ? b[0] : j == 3 ? b[1] : b[2];
+        const uint32_t d3 = j == 0 ? a[3] : j == 1 ? b[0] : j == 2 ? b[1] : j == 3 ? b[2] : b[3];
+        const uint32_t d4 = j == 0 ? b[0] : j == 1 ? b[1] : j == 2 ? b[2] : j == 3 ? b[3] : 0u;
+        e[j] = q == 0 ? d0 : q == 1 ? d1 : q == 2 ? d2 : q == 3 ? d3 : d4;
+    }
+    gt_v4u r;
+#pragma unroll
+    for (int j = 0; j < 4; j++) r[j] = __builtin_amdgcn_alignbyte(e[j + 1], e[j], s);
+    return r;
+}
+
+// lane i gets lane i-1's v (DPP wave_shr:1); lane 0 keeps old
+__device__ __forceinline__ gt_v4u dpp_from_lower_lane(gt_v4u v, gt_v4u old)
+{
+    gt_v4u r;
+#pragma unroll
+    for (int j = 0; j < 4; j++) r[j] = (uint32_t)__builtin_amdgcn_update_dpp((int)old[j], (int)v[j], 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
+    return r;
+}
+
 // Byte 0 of row j's GT segment: out + j * out_stride, or — full-line mode (src/pfile.rs:156-192), any kept
 // subset — behind the line's prefix at out + line_off[j] + prefix length (the prefixes are copied by
 // copy_prefix_rows below, run by the GT kernels' own waves).  j is wave-uniform or per-lane.

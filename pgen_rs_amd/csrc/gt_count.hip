@@ -26,8 +26,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr uint32_t kBlocksPerCu = 8;   // 32 waves per CU: up to 128 KiB of record loads in flight per CU on long rows
 
-__device__ __forceinline__ gt_v4u load_nt16(const uint8_t *p) { return __builtin_nontemporal_load(reinterpret_cast<const gt_v4u *>(p)); }
-
 // bits [0, 2n) of a word, n in [0, 16]
 __device__ __forceinline__ uint32_t low_sample_bits(int32_t n) { return n >= 16 ? 0xFFFFFFFFu : ((1u << (2 * n)) - 1u); }
 
@@ -39,34 +37,6 @@ __device__ __forceinline__ uint32_t row_mask(int64_t i0, uint32_t j, uint32_t N)
     const int32_t lo = (int32_t)min<int64_t>(max<int64_t>(-s0, 0), 16);
     const int32_t hi = (int32_t)min<int64_t>(max<int64_t>((int64_t)N - s0, 0), 16);
     return 0x55555555u & low_sample_bits(hi) & ~low_sample_bits(lo);
-}
-
-// 16 bytes at byte offset o (1 .. 16) of the 32-byte pair {a (low), b (high)}: whole dwords first, then v_alignbyte_b32
-__device__ __forceinline__ gt_v4u funnel16(gt_v4u a, gt_v4u b, uint32_t o)
-{
-    const uint32_t q = o >> 2, s = o & 3u;
-    uint32_t e[5];
-#pragma unroll
-    for (int j = 0; j < 5; j++) {
-        const uint32_t d0 = j == 0 ? a[0] : j == 1 ? a[1] : j == 2 ? a[2] : j == 3 ? a[3] : b[0];
-        const uint32_t d1 = j == 0 ? a[1] : j == 1 ? a[2] : j == 2 ? a[3] : j == 3 ? b[0] : b[1];
-        const uint32_t d2 = j == 0 ? a[2] : j == 1 ? a[3] : j == 2 ? b[0] : j == 3 ? b[1] : b[2];
-        const uint32_t d3 = j == 0 ? a[3] : j == 1 ? b[0] : j == 2 ? b[1] : j == 3 ? b[2] : b[3];
-        const uint32_t d4 = j == 0 ? b[0] : j == 1 ? b[1] : j == 2 ? b[2] : j == 3 ? b[3] : 0u;
-        e[j] = q == 0 ? d0 : q == 1 ? d1 : q == 2 ? d2 : q == 3 ? d3 : d4;
-    }
-    gt_v4u r;
-#pragma unroll
-    for (int j = 0; j < 4; j++) r[j] = __builtin_amdgcn_alignbyte(e[j + 1], e[j], s);
-    return r;
-}
-
-__device__ __forceinline__ gt_v4u dpp_from_lower_lane(gt_v4u v, gt_v4u old)
-{
-    gt_v4u r;
-#pragma unroll
-    for (int j = 0; j < 4; j++) r[j] = (uint32_t)__builtin_amdgcn_update_dpp((int)old[j], (int)v[j], 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
-    return r;
 }
 
 struct Acc {

@@ -48,6 +48,7 @@ struct Tuning {
                                    // compact pass of the two passes); 0 = never (the segment kernels: single pass or segment compact pass)
     int align_stores = 1;          // subset kernels: lanes <-> chunks shifted so that every store instruction covers whole 128-byte lines (0 = from the first whole chunk)
     int runs_rows = 0;             // RUNS mode of the stream kernel: rows per work item (0 = as many as one wide load / one span holds)
+    int scount_slices = 0;         // per-sample counts: row ranges per column tile (0 = as many as fill the chip's resident blocks)
 };
 
 // rows are gathered (variant list or byte offsets): the HAS_VIDX instantiations
@@ -122,6 +123,23 @@ inline size_t gt_count_mask_bytes(uint32_t record_size) { return 16u * ((size_t)
 uint32_t gt_count_lanes_per_row(uint32_t record_size);
 // wave_per_row: one wave per row (long rows); else 4 .. 32 lanes per row, several rows per wave (short rows)
 hipError_t launch_gt_count(const CountArgs &a, bool wave_per_row, int num_cus, hipStream_t stream);
+
+// Per-sample genotype counts (gt_scount.hip): the counts of the selected rows added into counts[4 * k + c] for every kept
+// sample k (hom-ref, het, hom-alt, missing; u32 modular).  Rows as in CountArgs.
+struct ScountArgs {
+    const uint8_t *records;       // device; row r at records + r*record_stride
+    uint64_t record_stride;
+    const uint32_t *variant_idx;  // device or nullptr (identity)
+    const uint64_t *record_off;   // device or nullptr; when set, row j's record starts at records + record_off[j]
+    uint32_t n_variants;
+    uint32_t sample_count;        // N
+    uint32_t record_size;         // R = ceil(N/4)
+    const uint8_t *kept_mask;     // device or nullptr (all samples): the ctx's count mask (CountArgs::kept_mask)
+    const uint32_t *kept_rank;    // device, with kept_mask: kept samples before each 64-sample chunk
+    uint32_t *counts;             // device, 4-byte aligned
+};
+// slices_per_tile: row ranges per column tile (0 = as many as fill the chip's resident blocks)
+hipError_t launch_gt_scount(const ScountArgs &a, int slices_per_tile, int num_cus, hipStream_t stream);
 
 // Deterministic synthetic records (SURVEY.md §8d counter-based generator).
 hipError_t launch_synth_records(uint8_t *dst, uint64_t record_stride, uint32_t sample_count,

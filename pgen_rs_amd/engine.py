@@ -337,8 +337,75 @@ class GtEngine:
               "pgenhip_genotype_counts_at")
         return out[: 4 * n_variants].view(n_variants, 4)
 
-    def _counts_out(self, out: Optional[torch.Tensor], n_variants: int) -> torch.Tensor:
+    def sample_counts(
+        self,
+        records: torch.Tensor,
+        record_stride: Optional[int] = None,
+        variant_idx: Optional[torch.Tensor] = None,
+        n_variants: Optional[int] = None,
+        out: Optional[torch.Tensor] = None,
+        kernel: int = _capi.SCOUNT_AUTO,
+        accumulate: bool = False,
+        records_offset: int = 0,
+    ) -> torch.Tensor:
+        """Per-sample genotype counts over the selected rows: a ``(K, 4)`` int32 CUDA tensor holding, for kept sample k, the u32
+        numbers of rows in which it has code 0-3 (hom-ref, het, hom-alt, missing).
+
+        Rows are selected as in ``genotype_counts`` (a row named twice in ``variant_idx`` counts twice).  ``out``: optional int32
+        CUDA tensor of >= 4K entries (written from its first element; nothing else is touched).  ``accumulate``: add to what
+        ``out`` holds instead of overwriting it."""
+        if record_stride is None:
+            record_stride = self.record_size
+        self._check_dev(records, "records")
+        if variant_idx is not None:
+            self._check_dev(variant_idx, "variant_idx")
+            if variant_idx.dtype not in (torch.int32, torch.uint32):
+                raise ValueError("variant_idx must be a 32-bit integer tensor")
+        if n_variants is None:
+            if variant_idx is not None:
+                n_variants = variant_idx.numel()
+            else:
+                avail = records.numel() - records_offset
+                if self.record_size == 0 or avail < self.record_size:
+                    n_variants = 0
+                else:
+                    n_variants = (avail - self.record_size) // max(record_stride, 1) + 1
+        if variant_idx is not None and variant_idx.numel() < n_variants:
+            raise ValueError("variant_idx has fewer than n_variants entries")
+        if n_variants and variant_idx is None:
+            need_in = records_offset + (n_variants - 1) * record_stride + self.record_size
+            if records.numel() < need_in:
+                raise ValueError(f"records too small: {records.numel()} < {need_in}")
+        out = self._counts_out(out, self.kept_count, accumulate)
+        flags = kernel | (_capi.SCOUNT_ACCUMULATE if accumulate else 0)
+        check(
+            lib.pgenhip_sample_counts(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants,
+                                      _ptr(out), flags),
+            "pgenhip_sample_counts",
+        )
+        return out[: 4 * self.kept_count].view(self.kept_count, 4)
+
+    def sample_counts_at(self, base: torch.Tensor, record_off: torch.Tensor, n_variants: Optional[int] = None,
+                         out: Optional[torch.Tensor] = None, kernel: int = _capi.SCOUNT_AUTO, accumulate: bool = False) -> torch.Tensor:
+        """``sample_counts`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
+        self._check_dev(base, "base")
+        self._check_dev(record_off, "record_off")
+        if record_off.dtype != torch.int64:
+            raise ValueError("record_off must be an int64 tensor (u64 byte offsets)")
+        if n_variants is None:
+            n_variants = record_off.numel()
+        if record_off.numel() < n_variants:
+            raise ValueError("record_off has fewer than n_variants entries")
+        out = self._counts_out(out, self.kept_count, accumulate)
+        flags = kernel | (_capi.SCOUNT_ACCUMULATE if accumulate else 0)
+        check(lib.pgenhip_sample_counts_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, _ptr(out), flags),
+              "pgenhip_sample_counts_at")
+        return out[: 4 * self.kept_count].view(self.kept_count, 4)
+
+    def _counts_out(self, out: Optional[torch.Tensor], n_variants: int, accumulate: bool = False) -> torch.Tensor:
         if out is None:
+            if accumulate:
+                return torch.zeros(max(4 * n_variants, 4), dtype=torch.int32, device=self.torch_device)
             return torch.empty(max(4 * n_variants, 4), dtype=torch.int32, device=self.torch_device)
         self._check_dev(out, "out")
         if out.dtype != torch.int32 or out.numel() < 4 * n_variants:

@@ -6,6 +6,8 @@
 //
 // `pgen-hip freq <PFILE_PREFIX> [--include-var <EXPR>] [--include-sam <EXPR>] [-o|--out <FILE>]` (not in the reference): per-variant
 // genotype counts of the kept samples with filter's selection, counted on the GPU; tab-separated to stdout or FILE.
+// `pgen-hip sample-counts <PFILE_PREFIX> [--include-var <EXPR>] [--include-sam <EXPR>] [-o|--out <FILE>]` (not in the reference): the
+// other half, per-sample genotype counts over the kept variants (IID, then the four counts), same selection, staging and output.
 // Additions (opt-in, not in the reference): --gpus <N>, --block-mib <M>, --launch-mib <M>, --filter-threads <T>, --stats, --dry-run
 // (filter: write the VCF header only and report the body geometry; needs no GPU); BGZF output (`-o x.vcf.gz` or --bgzf,
 // --bgzf-level <1-9>, --compress-threads <T>) and `pgen-hip bgzf <IN> <OUT>`, the same writer on a file.
@@ -72,6 +74,7 @@ const char *kUsage =
     "  query   Queries the pgen, outputting to stdout\n"
     "  filter  Filters the pgen, outputting to a VCF\n"
     "  freq    Per-variant genotype counts of the kept samples, outputting to stdout\n"
+    "  sample-counts  Per-sample genotype counts over the kept variants, outputting to stdout\n"
     "  help    Print this message\n\n"
     "query  <PFILE_PREFIX> -f, --fstring <QUERY_FSTRING> [-i, --include <QUERY>] [-s, --samples]\n"
     "filter <PFILE_PREFIX> [--include-var <VAR_QUERY>] [--include-sam <SAM_QUERY>] [-o, --out <OUT_FILE>]\n"
@@ -81,6 +84,10 @@ const char *kUsage =
     "       [--gpus <N>] [--shards <S>] [--block-mib <M>] [--read-threads <T>] [--filter-threads <T>] [--stats]\n"
     "       one line per kept variant: CHROM POS ID REF ALT HOM_REF_CT HET_REF_ALT_CTS TWO_ALT_GENO_CTS MISSING_CT (plink2 .gcount\n"
     "       column names, diploid columns only; byte parity with plink2 is not claimed)\n"
+    "sample-counts <PFILE_PREFIX> [--include-var <VAR_QUERY>] [--include-sam <SAM_QUERY>] [-o, --out <OUT_FILE>]\n"
+    "       [--gpus <N>] [--shards <S>] [--block-mib <M>] [--read-threads <T>] [--filter-threads <T>] [--stats]\n"
+    "       one line per kept sample in psam order: IID HOM_REF_CT HET_CT HOM_ALT_CT MISSING_CT (the counts of 0/0, 0/1, 1/1 and\n"
+    "       ./. over the kept variants; no byte parity with plink2's .scount / .smiss is claimed)\n"
     "bgzf   <IN_FILE> <OUT_FILE> [--level <1-9>] [--threads <T>] [--chunk-mib <M>]\n";
 
 [[noreturn]] void usage_error(const std::string &msg)
@@ -273,6 +280,15 @@ int main(int argc, char **argv)
             if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
             const OutputStats st = pfile.output_freq(a.get("include-sam"), a.get("include-var"), a.get("out").value_or(""), output_options(a));
+            if (a.has("stats")) print_stats(st, t_main);
+            return 0;
+        }
+        if (cmd == "sample-counts") {
+            Args a = parse(argc, argv, 2, {{"include-var", 0}, {"include-sam", 0}, {"out", 'o'}, {"gpus", 0}, {"shards", 0}, {"block-mib", 0}, {"read-threads", 0}, {"filter-threads", 0}},
+                           {{"stats", 0}});
+            if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
+            const Pfile pfile = Pfile::from_prefix(a.positional[0]);
+            const OutputStats st = pfile.output_sample_counts(a.get("include-sam"), a.get("include-var"), a.get("out").value_or(""), output_options(a));
             if (a.has("stats")) print_stats(st, t_main);
             return 0;
         }

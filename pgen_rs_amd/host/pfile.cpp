@@ -868,6 +868,151 @@ void append_u64(std::string &s, uint64_t v)
     while (n) s += buf[--n];
 }
 
+// The block loop of freq and sample-counts.  Per shard: blocks of bv variants.  Block k's records are read into pinned buffer k % 2
+// while the device copies and counts block k - 1; each block's H2D copy and count launch are queued on the ctx stream.
+// Fixed-width files: runs of consecutive records are read in one go and packed at stride R.  Variable-width files: the plain
+// records are staged as they lie on disk (a span grows over gaps of up to R bytes, so a block stages at most 2R bytes per
+// variant) and counted through their offsets in the staged bytes (the `_at` entry points).
+// make(ctx, bv) builds a shard's counter, which provides
+//   launch(ctx, d_rec, d_off, nv): queue the block's count launch (d_off NULL: records packed at stride R);
+//   copy(ctx, nv): queue what goes back after it (outside the kernel timer);
+//   collect(b0, nv): the block's work on the stream has finished (b0: index of its first variant in `vars`);
+//   finish(ctx): after the shard's last block has been collected.
+template <class Make>
+void count_blocks(const Pfile &pf, const Pfile::IdxRecords &vars, const KeptSamples &kept, const OutputOptions &opt, const char *no_device,
+                  OutputStats &st, const Make &make)
+{
+    const uint32_t R = pf.variant_record_size();
+    const Shards shards(opt, no_device);
+    std::vector<double> kernel_s((size_t)shards.G, 0.0), setup_s((size_t)shards.G, 0.0);
+    const std::string pgen = pf.pgen_path();
+    const bool vw = pf.variable_width();
+    shards.run(vars.size(), [&](int g, int device, size_t begin, size_t end) {
+        const double t_worker = now_s();
+        const Fd pgen_fd(pgen, O_RDONLY);
+        const uint64_t bv = std::max<uint64_t>(1, std::min<uint64_t>(opt.block_text_bytes / R, end - begin));
+        const size_t stage_bytes = (size_t)(bv * R) * (vw ? 2u : 1u);
+        DeviceCtx ctx(device, pf.num_samples, &kept);
+        uint8_t *d_rec = ctx.device<uint8_t>(stage_bytes, "device records");
+        uint64_t *d_off = vw ? ctx.device<uint64_t>((size_t)(8 * bv), "device record offsets") : nullptr;
+        uint8_t *h_rec[2] = {ctx.pinned<uint8_t>(stage_bytes, "pinned records"), ctx.pinned<uint8_t>(stage_bytes, "pinned records")};
+        uint64_t *h_off[2] = {nullptr, nullptr};
+        if (vw) {
+            h_off[0] = ctx.pinned<uint64_t>((size_t)(16 * bv), "pinned record offsets");
+            h_off[1] = h_off[0] + bv;
+        }
+        auto counter = make(ctx, bv);
+        setup_s[(size_t)g] = now_s() - t_worker;
+
+        size_t prev_b0 = 0, prev_nv = 0;   // the block in flight on the device
+        auto collect = [&] {
+            if (!prev_nv) return;
+            check(pgenhip_wait(ctx.get()), "pgenhip_wait");
+            float ms = 0;
+            if (pgenhip_timer_read(ctx.get(), &ms) == PGENHIP_OK) kernel_s[(size_t)g] += ms * 1e-3;
+            counter.collect(prev_b0, prev_nv);
+            prev_nv = 0;
+        };
+        for (size_t b0 = begin, k = 0; b0 < end; b0 += (size_t)bv, k++) {
+            const size_t nv = std::min<size_t>((size_t)bv, end - b0);
+            uint8_t *dst = h_rec[k % 2];
+            size_t staged = 0;
+            for (size_t j = 0; j < nv;) {
+                const uint64_t off0 = pf.record_offset(vars[b0 + j].first);
+                size_t run = 1;
+                uint64_t span = R;   // bytes of the file from off0 this run covers
+                if (vw) {
+                    h_off[k % 2][j] = staged;
+                    while (j + run < nv) {
+                        const uint64_t off = pf.record_offset(vars[b0 + j + run].first);
+                        if (off > off0 + span + R) break;
+                        h_off[k % 2][j + run] = staged + (off - off0);
+                        span = off + R - off0;
+                        run++;
+                    }
+                } else {
+                    while (j + run < nv && vars[b0 + j + run].first == vars[b0 + j].first + run) run++;
+                    span = (uint64_t)run * R;
+                }
+                pread_span(pgen_fd.get(), dst + staged, (size_t)span, off0, pgen, opt.read_threads);
+                staged += (size_t)span;
+                j += run;
+            }
+            collect();   // block k - 1 has been counted and what it returns is back; its pinned records are free again
+            check(pgenhip_memcpy_h2d(ctx.get(), d_rec, dst, staged), "H2D records");
+            if (vw) check(pgenhip_memcpy_h2d(ctx.get(), d_off, h_off[k % 2], nv * sizeof(uint64_t)), "H2D record offsets");
+            check(pgenhip_timer_start(ctx.get()), "timer");
+            counter.launch(ctx.get(), d_rec, d_off, (uint32_t)nv);
+            check(pgenhip_timer_mark(ctx.get()), "timer");
+            counter.copy(ctx.get(), nv);
+            prev_b0 = b0;
+            prev_nv = nv;
+        }
+        collect();
+        counter.finish(ctx.get());
+    });
+    st.seconds_kernel = *std::max_element(kernel_s.begin(), kernel_s.end());
+    st.seconds_setup = *std::max_element(setup_s.begin(), setup_s.end());
+}
+
+// freq's counter: 16 bytes per variant, copied back block by block
+struct VariantCounter {
+    uint32_t R;
+    std::vector<uint32_t> &counts;   // 4 per kept variant
+    uint32_t *d_counts, *h_counts;
+    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, uint32_t nv) const
+    {
+        if (d_off)
+            check(pgenhip_genotype_counts_at(ctx, d_rec, d_off, nv, d_counts, PGENHIP_COUNT_AUTO), "pgenhip_genotype_counts_at");
+        else
+            check(pgenhip_genotype_counts(ctx, d_rec, R, nullptr, nv, d_counts, PGENHIP_COUNT_AUTO), "pgenhip_genotype_counts");
+    }
+    void copy(pgenhip_ctx *ctx, size_t nv) const { check(pgenhip_memcpy_d2h(ctx, h_counts, d_counts, nv * 16), "D2H counts"); }
+    void collect(size_t b0, size_t nv) const { std::memcpy(counts.data() + 4 * b0, h_counts, nv * 16); }
+    void finish(pgenhip_ctx *) const {}
+};
+
+// sample-counts' counter: every block of the shard accumulates into one device buffer of 16 bytes per kept sample (the first
+// overwrites it), copied back once; the host sums the shards in u64
+struct SampleCounter {
+    uint32_t R;
+    size_t K;
+    std::vector<uint64_t> &totals;   // 4 per kept sample
+    std::mutex &mu;
+    uint32_t *d_counts, *h_counts;
+    bool first = true;
+    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, uint32_t nv)
+    {
+        const uint32_t flags = PGENHIP_SCOUNT_AUTO | (first ? 0u : PGENHIP_SCOUNT_ACCUMULATE);
+        first = false;
+        if (d_off)
+            check(pgenhip_sample_counts_at(ctx, d_rec, d_off, nv, d_counts, flags), "pgenhip_sample_counts_at");
+        else
+            check(pgenhip_sample_counts(ctx, d_rec, R, nullptr, nv, d_counts, flags), "pgenhip_sample_counts");
+    }
+    void copy(pgenhip_ctx *, size_t) const {}
+    void collect(size_t, size_t) const {}
+    void finish(pgenhip_ctx *ctx) const
+    {
+        check(pgenhip_memcpy_d2h(ctx, h_counts, d_counts, K * 16), "D2H counts");
+        check(pgenhip_wait(ctx), "pgenhip_wait");
+        std::lock_guard<std::mutex> lk(mu);
+        for (size_t i = 0; i < 4 * K; i++) totals[i] += h_counts[i];
+    }
+};
+
+void write_text(const std::string &text, const std::string &filename)
+{
+    if (filename.empty()) {
+        if (std::fwrite(text.data(), 1, text.size(), stdout) != text.size() || std::fflush(stdout) != 0)
+            throw PfileError(std::string("write stdout: ") + std::strerror(errno));
+    } else {
+        Fd out(filename, O_WRONLY | O_CREAT | O_TRUNC);
+        pwrite_exact(out.get(), text.data(), text.size(), 0, filename);
+        out.close();
+    }
+}
+
 }  // namespace
 
 OutputStats Pfile::output_freq(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
@@ -895,81 +1040,9 @@ OutputStats Pfile::output_freq(const std::optional<std::string> &sam_query, cons
     std::vector<uint32_t> counts(4 * V, 0u);
     const double t_body = now_s();
     if (V != 0 && R != 0) {
-        const Shards shards(opt, "no HIP device: the genotype count path has no CPU fallback");
-        std::vector<double> kernel_s((size_t)shards.G, 0.0), setup_s((size_t)shards.G, 0.0);
-        const std::string pgen = pgen_path();
-        const bool vw = variable_width();
-
-        // Per shard: blocks of bv variants.  Block k's records are read into pinned buffer k % 2 while the device copies, counts and
-        // returns block k - 1; each block's H2D copy, count launch and 16-byte-per-variant D2H copy are queued on the ctx stream.
-        // Fixed-width files: runs of consecutive records are read in one go and packed at stride R.  Variable-width files: the plain
-        // records are staged as they lie on disk (a span grows over gaps of up to R bytes, so a block stages at most 2R bytes per
-        // variant) and counted through their offsets in the staged bytes (pgenhip_genotype_counts_at).
-        shards.run(V, [&](int g, int device, size_t begin, size_t end) {
-            const double t_worker = now_s();
-            const Fd pgen_fd(pgen, O_RDONLY);
-            const uint64_t bv = std::max<uint64_t>(1, std::min<uint64_t>(opt.block_text_bytes / R, end - begin));
-            const size_t stage_bytes = (size_t)(bv * R) * (vw ? 2u : 1u);
-            DeviceCtx ctx(device, num_samples, &kept);
-            uint8_t *d_rec = ctx.device<uint8_t>(stage_bytes, "device records");
-            uint32_t *d_counts = ctx.device<uint32_t>((size_t)(16 * bv), "device counts");
-            uint64_t *d_off = vw ? ctx.device<uint64_t>((size_t)(8 * bv), "device record offsets") : nullptr;
-            uint8_t *h_rec[2] = {ctx.pinned<uint8_t>(stage_bytes, "pinned records"), ctx.pinned<uint8_t>(stage_bytes, "pinned records")};
-            uint32_t *h_counts = ctx.pinned<uint32_t>((size_t)(16 * bv + (vw ? 16 * bv : 0)), "pinned counts");
-            uint64_t *h_off[2] = {reinterpret_cast<uint64_t *>(h_counts + 4 * bv), reinterpret_cast<uint64_t *>(h_counts + 4 * bv) + bv};
-            setup_s[(size_t)g] = now_s() - t_worker;
-
-            size_t prev_b0 = 0, prev_nv = 0;   // the block in flight on the device
-            auto collect = [&] {
-                if (!prev_nv) return;
-                check(pgenhip_wait(ctx.get()), "pgenhip_wait");
-                float ms = 0;
-                if (pgenhip_timer_read(ctx.get(), &ms) == PGENHIP_OK) kernel_s[(size_t)g] += ms * 1e-3;
-                std::memcpy(counts.data() + 4 * prev_b0, h_counts, prev_nv * 16);
-                prev_nv = 0;
-            };
-            for (size_t b0 = begin, k = 0; b0 < end; b0 += (size_t)bv, k++) {
-                const size_t nv = std::min<size_t>((size_t)bv, end - b0);
-                uint8_t *dst = h_rec[k % 2];
-                size_t staged = 0;
-                for (size_t j = 0; j < nv;) {
-                    const uint64_t off0 = record_offset(var_idx_rcds[b0 + j].first);
-                    size_t run = 1;
-                    uint64_t span = R;   // bytes of the file from off0 this run covers
-                    if (vw) {
-                        h_off[k % 2][j] = staged;
-                        while (j + run < nv) {
-                            const uint64_t off = record_offset(var_idx_rcds[b0 + j + run].first);
-                            if (off > off0 + span + R) break;
-                            h_off[k % 2][j + run] = staged + (off - off0);
-                            span = off + R - off0;
-                            run++;
-                        }
-                    } else {
-                        while (j + run < nv && var_idx_rcds[b0 + j + run].first == var_idx_rcds[b0 + j].first + run) run++;
-                        span = (uint64_t)run * R;
-                    }
-                    pread_span(pgen_fd.get(), dst + staged, (size_t)span, off0, pgen, opt.read_threads);
-                    staged += (size_t)span;
-                    j += run;
-                }
-                collect();   // block k - 1 has been counted and its counts are back; its pinned records are free again
-                check(pgenhip_memcpy_h2d(ctx.get(), d_rec, dst, staged), "H2D records");
-                if (vw) check(pgenhip_memcpy_h2d(ctx.get(), d_off, h_off[k % 2], nv * sizeof(uint64_t)), "H2D record offsets");
-                check(pgenhip_timer_start(ctx.get()), "timer");
-                if (vw)
-                    check(pgenhip_genotype_counts_at(ctx.get(), d_rec, d_off, (uint32_t)nv, d_counts, PGENHIP_COUNT_AUTO), "pgenhip_genotype_counts_at");
-                else
-                    check(pgenhip_genotype_counts(ctx.get(), d_rec, R, nullptr, (uint32_t)nv, d_counts, PGENHIP_COUNT_AUTO), "pgenhip_genotype_counts");
-                check(pgenhip_timer_mark(ctx.get()), "timer");
-                check(pgenhip_memcpy_d2h(ctx.get(), h_counts, d_counts, nv * 16), "D2H counts");
-                prev_b0 = b0;
-                prev_nv = nv;
-            }
-            collect();
+        count_blocks(*this, var_idx_rcds, kept, opt, "no HIP device: the genotype count path has no CPU fallback", st, [&](DeviceCtx &ctx, uint64_t bv) {
+            return VariantCounter{R, counts, ctx.device<uint32_t>((size_t)(16 * bv), "device counts"), ctx.pinned<uint32_t>((size_t)(16 * bv), "pinned counts")};
         });
-        st.seconds_kernel = *std::max_element(kernel_s.begin(), kernel_s.end());
-        st.seconds_setup = *std::max_element(setup_s.begin(), setup_s.end());
     }
 
     std::string text = "#CHROM\tPOS\tID\tREF\tALT\tHOM_REF_CT\tHET_REF_ALT_CTS\tTWO_ALT_GENO_CTS\tMISSING_CT\n";
@@ -987,18 +1060,58 @@ OutputStats Pfile::output_freq(const std::optional<std::string> &sam_query, cons
     }
     st.body_bytes = text.size() - st.header_bytes;
     st.file_bytes = text.size();
-    if (filename.empty()) {
-        if (std::fwrite(text.data(), 1, text.size(), stdout) != text.size() || std::fflush(stdout) != 0)
-            throw PfileError(std::string("write stdout: ") + std::strerror(errno));
-    } else {
-        Fd out(filename, O_WRONLY | O_CREAT | O_TRUNC);
-        pwrite_exact(out.get(), text.data(), text.size(), 0, filename);
-        out.close();
-    }
+    write_text(text, filename);
     st.seconds_body = now_s() - t_body;
     return st;
 }
 
+OutputStats Pfile::output_sample_counts(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
+                                        const std::string &filename, const OutputOptions &opt) const
+{
+    OutputStats st;
+    const double t0 = now_s();
+    const Selection sel = select(sam_query, var_query, opt.filter_threads);
+    size_t iid = sel.sam_header.size();   // vcf_header's rule (:114-126): the first column named IID
+    for (size_t c = 0; c < sel.sam_header.size(); c++) {
+        if (sel.sam_header[c] == "IID") {
+            iid = c;
+            break;
+        }
+    }
+    if (iid == sel.sam_header.size()) throw PfileError("IID not among the headers of " + psam_path());
+    st.seconds_filter = now_s() - t0;
+
+    const KeptSamples kept = check_selection(*this, sel);
+    const size_t V = sel.var_idx_rcds.size(), K = kept.rows.size();
+    st.variants = V;
+    st.samples_kept = K;
+
+    std::vector<uint64_t> totals(4 * K, 0u);
+    const double t_body = now_s();
+    if (V != 0 && K != 0) {   // else every count is zero and no device is touched
+        const uint32_t R = variant_record_size();
+        std::mutex mu;
+        count_blocks(*this, sel.var_idx_rcds, kept, opt, "no HIP device: the sample count path has no CPU fallback", st, [&](DeviceCtx &ctx, uint64_t) {
+            return SampleCounter{R, K, totals, mu, ctx.device<uint32_t>(16 * K, "device counts"), ctx.pinned<uint32_t>(16 * K, "pinned counts")};
+        });
+    }
+
+    std::string text = "#IID\tHOM_REF_CT\tHET_CT\tHOM_ALT_CT\tMISSING_CT\n";
+    st.header_bytes = text.size();
+    for (size_t k = 0; k < K; k++) {
+        text += sel.sam_idx_rcs[k].second.at(iid);
+        for (int c = 0; c < 4; c++) {
+            text += '\t';
+            append_u64(text, totals[4 * k + (size_t)c]);
+        }
+        text += '\n';
+    }
+    st.body_bytes = text.size() - st.header_bytes;
+    st.file_bytes = text.size();
+    write_text(text, filename);
+    st.seconds_body = now_s() - t_body;
+    return st;
+}
 
 namespace {
 uint64_t splitmix64(uint64_t x)

@@ -149,6 +149,14 @@ class Pfile {
     OutputStats output_freq(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
                             const std::string &filename, const OutputOptions &opt = OutputOptions()) const;
 
+    // `sample-counts` (not in the reference): per-sample genotype counts over the kept variants, one tab-separated line per kept
+    // sample in psam order (the IID column verbatim, then the counts of 0/0, 0/1, 1/1 and ./.).  Selection and staging are freq's;
+    // each shard's blocks accumulate on the device (pgenhip_sample_counts / _at), 16 bytes per kept sample come back once per
+    // shard and the host sums the shards in u64.  No kept variant or no kept sample: zero lines / the header alone, no device.
+    // A psam without an IID column is vcf_header's error.  filename empty: stdout.
+    OutputStats output_sample_counts(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
+                                     const std::string &filename, const OutputOptions &opt = OutputOptions()) const;
+
     // the header part of output_vcf (:110-146) on its own: used by output_vcf and by the CPU tests
     std::string vcf_header(const IdxRecords &sam_idx_rcs, const StringRecord &sam_header) const;
 };
