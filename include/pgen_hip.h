@@ -255,6 +255,42 @@ int pgenhip_sample_counts(pgenhip_ctx *ctx, const void *d_records, uint64_t reco
 int pgenhip_sample_counts_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
                              uint32_t *d_counts, uint32_t flags);
 
+/* ---- numeric genotype matrix (device-resident, asynchronous on the ctx stream) ----
+ * The GT text with the fixed bytes removed: element (j, k) is the code pgenhip_decode_emit prints as the k-th field of row j,
+ * mapped through a four-entry table.  Rows are selected exactly as in pgenhip_decode_emit / pgenhip_decode_emit_at; a gather that
+ * repeats a row writes it twice.  k is the sample's rank in the ctx's kept list (its index when all samples are kept), c the
+ * 2-bit code of that sample in that row (src/pfile.rs:172-175; the pad bits of a record's last byte are never read as samples).
+ *   - elem_bytes is 1, 2 or 4.  code_values is a HOST pointer to four elements of elem_bytes bytes, the bit patterns written for
+ *     codes 0, 1, 2, 3; it is read during the call and passed as kernel arguments (no device copy, no allocation; a captured
+ *     graph keeps the patterns it was captured with).  NULL means 0, 1, 2 and all bits set (-1 as a signed integer).  The library
+ *     does not interpret the elements: int8, uint8, fp16, bf16, fp32 and int32 are all "a size and four patterns", and results
+ *     compare byte for byte.
+ *   - Variant-major (default): element (j, k) at d_out + j*out_stride + k*elem_bytes, out_stride >= K*elem_bytes (or
+ *     n_variants <= 1).  Sample-major (PGENHIP_MATRIX_SAMPLE_MAJOR): at d_out + k*out_stride + j*elem_bytes, out_stride >=
+ *     n_variants*elem_bytes (or K <= 1).  out_stride is in bytes; d_out and out_stride must be multiples of elem_bytes, else
+ *     PGENHIP_ERR_BAD_ARG.  Bytes of d_out outside the n_variants x K elements (row padding included) are not touched.
+ *     n_variants == 0 or K == 0 writes nothing.
+ *   - Shapes.  GENERAL applies always.  STREAM: all samples kept (no list, or the identity list), variant-major, any d_out /
+ *     out_stride the contract allows.  TILE: all samples kept, sample-major, d_out and out_stride multiples of 16 bytes (its stores
+ *     cover whole 128-byte lines when they are multiples of 128: pad the row pitch).  A forced shape that does not apply is
+ *     PGENHIP_ERR_BAD_ARG with a detail string; AUTO takes STREAM / TILE where they apply and GENERAL everywhere else.
+ *   - An offset that does not fit the kernels' index types (2^52 bytes or more) is PGENHIP_ERR_TOO_LARGE before any launch.
+ * Same launch contract as pgenhip_genotype_counts: device pointers only, no allocation, no synchronisation, queued on the ctx
+ * stream, graph-capturable.
+ * flags: a shape (low 4 bits) | orientation. */
+#define PGENHIP_MATRIX_AUTO 0u
+#define PGENHIP_MATRIX_GENERAL 1u     /* any K, any strides, both orientations: the correctness baseline */
+#define PGENHIP_MATRIX_STREAM 2u      /* variant-major, all samples kept */
+#define PGENHIP_MATRIX_TILE 3u        /* sample-major, all samples kept, 16-byte-aligned rows: tile transpose */
+#define PGENHIP_MATRIX_SHAPE_MASK 0xFu
+#define PGENHIP_MATRIX_SAMPLE_MAJOR 0x10u
+int pgenhip_decode_matrix(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                          uint32_t n_variants, void *d_out, uint64_t out_stride, uint32_t elem_bytes,
+                          const void *code_values, uint32_t flags);
+/* Same, with the record of row j at d_base + d_record_off[j] (DEVICE array of u64 byte offsets). */
+int pgenhip_decode_matrix_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
+                             void *d_out, uint64_t out_stride, uint32_t elem_bytes, const void *code_values, uint32_t flags);
+
 /* Launch-shape knobs of one ctx (tests force small grids to exercise ring re-use; A/B probes).
  * value 0 restores the built-in default of a knob unless noted. */
 typedef enum pgenhip_knob {
@@ -273,6 +309,7 @@ typedef enum pgenhip_knob {
        retired, refused with PGENHIP_ERR_BAD_ARG, never reused */
     PGENHIP_KNOB_ALIGN_STORES = 16,      /* subset kernels (segment, row-owner, pick): 1 (default) lanes <-> chunks shifted so that every store instruction covers whole 128-byte lines, -1 from the run's first whole chunk */
     PGENHIP_KNOB_SCOUNT_SLICES = 17,     /* per-sample counts: row ranges per column tile, each summed by one block (default 0 = as many as fill the chip's resident blocks) */
+    PGENHIP_KNOB_MATRIX_BLOCKS = 18,     /* genotype matrix kernels: grid size in blocks (default 0 = by shape: the work, capped at 8 blocks per CU, 4 for TILE); tests force small grids */
     PGENHIP_KNOB_RUNS_ROWS = 7           /* RUNS kernel: rows per work item (default: as many as one wide load / one span holds) */
 } pgenhip_knob;
 int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value);

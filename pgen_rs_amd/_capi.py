@@ -48,6 +48,12 @@ SCOUNT_AUTO = 0
 SCOUNT_ROWS = 2
 SCOUNT_SHAPE_MASK = 0xF
 SCOUNT_ACCUMULATE = 0x10
+MATRIX_AUTO = 0
+MATRIX_GENERAL = 1
+MATRIX_STREAM = 2
+MATRIX_TILE = 3
+MATRIX_SHAPE_MASK = 0xF
+MATRIX_SAMPLE_MAJOR = 0x10
 SYNTH_DIRTY_PAD = 1
 SYNTH_HWE = 2
 CREATE_KEEP_LIST = 1
@@ -66,6 +72,7 @@ KNOB_ROWPICK_BLOCKS_PER_CU = 11
 KNOB_SCAN_ROWPICK = 12
 KNOB_ALIGN_STORES = 16
 KNOB_SCOUNT_SLICES = 17
+KNOB_MATRIX_BLOCKS = 18
 
 
 
@@ -109,6 +116,8 @@ PROTOTYPES = {
     "pgenhip_genotype_counts_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_sample_counts": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_sample_counts_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
+    "pgenhip_decode_matrix": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
+    "pgenhip_decode_matrix_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_tune": (C.c_int, [ctx_p, C.c_uint32, C.c_int32]),
     "pgenhip_wait": (C.c_int, [ctx_p]),
     "pgenhip_timer_start": (C.c_int, [ctx_p]),

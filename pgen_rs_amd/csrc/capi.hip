@@ -674,6 +674,86 @@ int pgenhip_sample_counts_at(pgenhip_ctx *ctx, const void *d_base, const uint64_
     return sample_counts_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, d_counts, flags);
 }
 
+static int decode_matrix_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                              const uint64_t *d_record_off, uint32_t n_variants, void *d_out, uint64_t out_stride, uint32_t elem_bytes,
+                              const void *code_values, uint32_t flags)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (flags & ~(PGENHIP_MATRIX_SHAPE_MASK | PGENHIP_MATRIX_SAMPLE_MAJOR)) return fail(PGENHIP_ERR_BAD_ARG, "unknown decode_matrix flag");
+    const uint32_t shape = flags & PGENHIP_MATRIX_SHAPE_MASK;
+    if (shape > PGENHIP_MATRIX_TILE) return fail(PGENHIP_ERR_BAD_ARG, "decode_matrix supports shapes AUTO, GENERAL, STREAM and TILE");
+    if (elem_bytes != 1u && elem_bytes != 2u && elem_bytes != 4u) return fail(PGENHIP_ERR_BAD_ARG, "elem_bytes must be 1, 2 or 4");
+    const bool sample_major = (flags & PGENHIP_MATRIX_SAMPLE_MAJOR) != 0u;
+    const uint32_t K = ctx->kept_count;
+    const bool all_kept = !ctx->subset || ctx->identity;
+    if (shape == PGENHIP_MATRIX_STREAM && (!all_kept || sample_major))
+        return fail(PGENHIP_ERR_BAD_ARG, "PGENHIP_MATRIX_STREAM needs all samples kept and the variant-major orientation");
+    if (shape == PGENHIP_MATRIX_TILE && (!all_kept || !sample_major))
+        return fail(PGENHIP_ERR_BAD_ARG, "PGENHIP_MATRIX_TILE needs all samples kept and the sample-major orientation");
+    if (n_variants == 0 || K == 0u) return PGENHIP_OK;   // nothing to write
+    if (!d_out) return fail(PGENHIP_ERR_BAD_ARG, "d_out is NULL");
+    if ((uintptr_t)d_out % elem_bytes || out_stride % elem_bytes) return fail(PGENHIP_ERR_BAD_ARG, "d_out and out_stride must be multiples of elem_bytes");
+    if (ctx->record_size && !d_records) return fail(PGENHIP_ERR_BAD_ARG, "d_records is NULL");
+    if (n_variants > 1 && !d_variant_idx && !d_record_off && record_stride < ctx->record_size)
+        return fail(PGENHIP_ERR_BAD_ARG, "record_stride < record size");
+    const uint64_t rows = sample_major ? K : n_variants, inner = sample_major ? n_variants : K;
+    if (rows > 1 && out_stride < inner * elem_bytes) return fail(PGENHIP_ERR_BAD_ARG, "out_stride < one output row");
+    // the kernels index elements and 16-byte chunks in 64 bits and divide through a double reciprocal: exact below 2^52
+    constexpr uint64_t kMaxSpan = 1ull << 52;
+    if ((uint64_t)n_variants * K >= kMaxSpan / 16u || (rows > 1 && out_stride >= kMaxSpan / rows) ||
+        (n_variants > 1 && !d_record_off && record_stride >= kMaxSpan / (d_variant_idx ? 0xFFFFFFFFull : n_variants)))
+        return fail(PGENHIP_ERR_TOO_LARGE, "matrix offsets do not fit the kernels' index types");
+    MatrixArgs a;
+    a.records = static_cast<const uint8_t *>(d_records);
+    a.record_stride = record_stride;
+    a.variant_idx = d_variant_idx;
+    a.record_off = d_record_off;
+    a.n_variants = n_variants;
+    a.sample_count = ctx->sample_count;
+    a.record_size = ctx->record_size;
+    a.kept_idx = all_kept ? nullptr : ctx->d_kept;
+    a.kept_count = K;
+    a.out = static_cast<uint8_t *>(d_out);
+    a.out_stride = out_stride;
+    a.elem_bytes = elem_bytes;
+    a.sample_major = sample_major ? 1u : 0u;
+    const uint32_t all_ones = elem_bytes == 4u ? 0xFFFFFFFFu : (1u << (8u * elem_bytes)) - 1u;
+    for (uint32_t c = 0; c < 4u; c++) {
+        uint32_t v = c == 3u ? all_ones : c;
+        if (code_values) {
+            const uint8_t *p = static_cast<const uint8_t *>(code_values) + (size_t)c * elem_bytes;
+            v = 0u;
+            for (uint32_t b = 0; b < elem_bytes; b++) v |= (uint32_t)p[b] << (8u * b);
+        }
+        a.tab[c] = v;
+    }
+    if (shape == PGENHIP_MATRIX_TILE && !gt_matrix_tile_applicable(a))
+        return fail(PGENHIP_ERR_BAD_ARG, "PGENHIP_MATRIX_TILE needs d_out and out_stride to be multiples of 16 bytes");
+    const int blocks = ctx->tune.matrix_blocks;
+    if (shape == PGENHIP_MATRIX_STREAM || (shape == PGENHIP_MATRIX_AUTO && gt_matrix_stream_applicable(a)))
+        HIP_TRY(launch_gt_matrix_stream(a, blocks, ctx->num_cus, ctx->stream));
+    else if (shape == PGENHIP_MATRIX_TILE || (shape == PGENHIP_MATRIX_AUTO && gt_matrix_tile_applicable(a)))
+        HIP_TRY(launch_gt_matrix_tile(a, blocks, ctx->num_cus, ctx->stream));
+    else
+        HIP_TRY(launch_gt_matrix_general(a, blocks, ctx->num_cus, ctx->stream));
+    return PGENHIP_OK;
+}
+
+int pgenhip_decode_matrix(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                          uint32_t n_variants, void *d_out, uint64_t out_stride, uint32_t elem_bytes,
+                          const void *code_values, uint32_t flags)
+{
+    return decode_matrix_core(ctx, d_records, record_stride, d_variant_idx, nullptr, n_variants, d_out, out_stride, elem_bytes, code_values, flags);
+}
+
+int pgenhip_decode_matrix_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
+                             void *d_out, uint64_t out_stride, uint32_t elem_bytes, const void *code_values, uint32_t flags)
+{
+    if (ctx && n_variants && !d_record_off) return fail(PGENHIP_ERR_BAD_ARG, "d_record_off is NULL");
+    return decode_matrix_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, d_out, out_stride, elem_bytes, code_values, flags);
+}
+
 int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)
 {
     if (!ctx) return fail(PGENHIP_ERR_BAD_ARG, "ctx is NULL");
@@ -696,6 +776,7 @@ int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)
         case PGENHIP_KNOB_ALIGN_STORES: t.align_stores = value < 0 ? 0 : 1; break;
         case PGENHIP_KNOB_RUNS_ROWS: t.runs_rows = value > 0 ? value : d.runs_rows; break;
         case PGENHIP_KNOB_SCOUNT_SLICES: t.scount_slices = value > 0 ? value : d.scount_slices; break;
+        case PGENHIP_KNOB_MATRIX_BLOCKS: t.matrix_blocks = value > 0 ? value : d.matrix_blocks; break;
         default: return fail(PGENHIP_ERR_BAD_ARG, "unknown knob");
     }
     return PGENHIP_OK;

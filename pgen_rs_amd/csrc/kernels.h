@@ -49,6 +49,7 @@ struct Tuning {
     int align_stores = 1;          // subset kernels: lanes <-> chunks shifted so that every store instruction covers whole 128-byte lines (0 = from the first whole chunk)
     int runs_rows = 0;             // RUNS mode of the stream kernel: rows per work item (0 = as many as one wide load / one span holds)
     int scount_slices = 0;         // per-sample counts: row ranges per column tile (0 = as many as fill the chip's resident blocks)
+    int matrix_blocks = 0;         // genotype matrix kernels: grid size in blocks (0 = by shape, capped per CU)
 };
 
 // rows are gathered (variant list or byte offsets): the HAS_VIDX instantiations
@@ -140,6 +141,31 @@ struct ScountArgs {
 };
 // slices_per_tile: row ranges per column tile (0 = as many as fill the chip's resident blocks)
 hipError_t launch_gt_scount(const ScountArgs &a, int slices_per_tile, int num_cus, hipStream_t stream);
+
+// Numeric genotype matrix (gt_matrix.hip): element (j, k) = the pattern of the code of kept sample k in selected row j.  Rows as in
+// CountArgs.
+struct MatrixArgs {
+    const uint8_t *records;       // device; row r at records + r*record_stride
+    uint64_t record_stride;
+    const uint32_t *variant_idx;  // device or nullptr (identity)
+    const uint64_t *record_off;   // device or nullptr; when set, row j's record starts at records + record_off[j]
+    uint32_t n_variants;
+    uint32_t sample_count;        // N
+    uint32_t record_size;         // R = ceil(N/4)
+    const uint32_t *kept_idx;     // device or nullptr (all samples, or an identity list)
+    uint32_t kept_count;          // K (== N when kept_idx is nullptr)
+    uint8_t *out;                 // device, a multiple of elem_bytes
+    uint64_t out_stride;          // bytes between output rows (variant-major: rows are variants; sample-major: kept samples)
+    uint32_t elem_bytes;          // 1, 2 or 4
+    uint32_t sample_major;        // 0: (j, k) at out + j*out_stride + k*elem_bytes; 1: at out + k*out_stride + j*elem_bytes
+    uint32_t tab[4];              // the patterns of codes 0-3, zero-extended
+};
+bool gt_matrix_stream_applicable(const MatrixArgs &a);   // variant-major, all samples kept
+bool gt_matrix_tile_applicable(const MatrixArgs &a);     // sample-major, all samples kept, out and out_stride multiples of 16
+// blocks: forced grid size (0 = by shape; tests force small grids to walk the grid-stride loops)
+hipError_t launch_gt_matrix_general(const MatrixArgs &a, int blocks, int num_cus, hipStream_t stream);
+hipError_t launch_gt_matrix_stream(const MatrixArgs &a, int blocks, int num_cus, hipStream_t stream);
+hipError_t launch_gt_matrix_tile(const MatrixArgs &a, int blocks, int num_cus, hipStream_t stream);
 
 // Deterministic synthetic records (SURVEY.md §8d counter-based generator).
 hipError_t launch_synth_records(uint8_t *dst, uint64_t record_stride, uint32_t sample_count,

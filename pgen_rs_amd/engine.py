@@ -402,6 +402,116 @@ class GtEngine:
               "pgenhip_sample_counts_at")
         return out[: 4 * self.kept_count].view(self.kept_count, 4)
 
+    # -- numeric genotype matrix ---------------------------------------------------------------
+    def decode_matrix(
+        self,
+        records: torch.Tensor,
+        n_variants: Optional[int] = None,
+        *,
+        dtype: torch.dtype = torch.int8,
+        sample_major: bool = False,
+        values=None,
+        out: Optional[torch.Tensor] = None,
+        variant_idx: Optional[torch.Tensor] = None,
+        record_stride: Optional[int] = None,
+        kernel: int = _capi.MATRIX_AUTO,
+        records_offset: int = 0,
+    ) -> torch.Tensor:
+        """The genotypes as numbers: a ``(V, K)`` tensor (``(K, V)`` with ``sample_major``) of ``dtype`` (int8, uint8, int16, int32,
+        float16, bfloat16, float32) whose element for row j and kept sample k is ``values[code]``: the GT field ``decode_emit``
+        prints there, mapped through a four-entry table.
+
+        Rows are selected as in ``decode_emit`` (``variant_idx`` / ``record_stride``; ``n_variants`` defaults as in
+        ``genotype_counts``).  ``values``: four numbers (or a 4-element tensor / array of ``dtype``) for codes 0-3, default 0, 1, 2
+        and -1 for signed integers, all bits set for unsigned ones, NaN for floating dtypes.  ``out``: any 2-D CUDA tensor of the
+        result's shape and dtype with unit stride in its last dimension (its row stride may be padded; the padding is not touched).
+        Without ``out`` the variant-major result is contiguous; the sample-major result is a ``[:, :V]`` view of rows allocated at
+        a pitch rounded up to 128 bytes, so that the transpose kernel stores whole lines: ``.contiguous()`` is the caller's choice
+        and cost."""
+        if record_stride is None:
+            record_stride = self.record_size
+        self._check_dev(records, "records")
+        if variant_idx is not None:
+            self._check_dev(variant_idx, "variant_idx")
+            if variant_idx.dtype not in (torch.int32, torch.uint32):
+                raise ValueError("variant_idx must be a 32-bit integer tensor")
+        if n_variants is None:
+            if variant_idx is not None:
+                n_variants = variant_idx.numel()
+            else:
+                avail = records.numel() - records_offset
+                if self.record_size == 0 or avail < self.record_size:
+                    n_variants = 0
+                else:
+                    n_variants = (avail - self.record_size) // max(record_stride, 1) + 1
+        if variant_idx is not None and variant_idx.numel() < n_variants:
+            raise ValueError("variant_idx has fewer than n_variants entries")
+        if n_variants and variant_idx is None:
+            need_in = records_offset + (n_variants - 1) * record_stride + self.record_size
+            if records.numel() < need_in:
+                raise ValueError(f"records too small: {records.numel()} < {need_in}")
+        out, res, stride, tab = self._matrix_out(out, n_variants, dtype, sample_major, values)
+        flags = kernel | (_capi.MATRIX_SAMPLE_MAJOR if sample_major else 0)
+        check(lib.pgenhip_decode_matrix(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants,
+                                        out.data_ptr(), stride, out.element_size(), tab.ctypes.data_as(C.c_void_p), flags),
+              "pgenhip_decode_matrix")
+        return res
+
+    def decode_matrix_at(self, base: torch.Tensor, record_off: torch.Tensor, n_variants: Optional[int] = None, *,
+                         dtype: torch.dtype = torch.int8, sample_major: bool = False, values=None,
+                         out: Optional[torch.Tensor] = None, kernel: int = _capi.MATRIX_AUTO) -> torch.Tensor:
+        """``decode_matrix`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
+        self._check_dev(base, "base")
+        self._check_dev(record_off, "record_off")
+        if record_off.dtype != torch.int64:
+            raise ValueError("record_off must be an int64 tensor (u64 byte offsets)")
+        if n_variants is None:
+            n_variants = record_off.numel()
+        if record_off.numel() < n_variants:
+            raise ValueError("record_off has fewer than n_variants entries")
+        out, res, stride, tab = self._matrix_out(out, n_variants, dtype, sample_major, values)
+        flags = kernel | (_capi.MATRIX_SAMPLE_MAJOR if sample_major else 0)
+        check(lib.pgenhip_decode_matrix_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, out.data_ptr(), stride,
+                                           out.element_size(), tab.ctypes.data_as(C.c_void_p), flags), "pgenhip_decode_matrix_at")
+        return res
+
+    _MATRIX_DTYPES = {torch.int8: np.int8, torch.uint8: np.uint8, torch.int16: np.int16, torch.int32: np.int32,
+                      torch.float16: np.float16, torch.bfloat16: None, torch.float32: np.float32}
+
+    @classmethod
+    def matrix_values(cls, dtype: torch.dtype, values=None) -> np.ndarray:
+        """The four bit patterns of codes 0-3 as ``4 * itemsize`` bytes (what ``code_values`` of the C ABI points at)."""
+        if dtype not in cls._MATRIX_DTYPES:
+            raise ValueError(f"decode_matrix does not support {dtype}")
+        if values is None:
+            values = [0, 1, 2, float("nan") if dtype.is_floating_point else (-1 if dtype.is_signed else torch.iinfo(dtype).max)]
+        t = values.detach().cpu().to(dtype) if isinstance(values, torch.Tensor) else torch.tensor(list(values)).to(dtype)
+        if t.numel() != 4:
+            raise ValueError("values must hold four elements (codes 0, 1, 2, 3)")
+        return np.ascontiguousarray(t.contiguous().view(torch.uint8).numpy())
+
+    def _matrix_out(self, out: Optional[torch.Tensor], n_variants: int, dtype: torch.dtype, sample_major: bool, values):
+        """(the tensor that owns the memory, the result view, row stride in bytes, the four patterns)"""
+        if out is not None:
+            dtype = out.dtype
+        tab = self.matrix_values(dtype, values)
+        rows, cols = (self.kept_count, n_variants) if sample_major else (n_variants, self.kept_count)
+        if out is None:
+            item = tab.size // 4
+            pitch = cols
+            if sample_major:
+                pitch = (cols * item + 127) // 128 * 128 // item
+            out = torch.empty((rows, max(pitch, 1)), dtype=dtype, device=self.torch_device)
+            return out, out[:, :cols], max(pitch, 1) * item, tab
+        if not out.is_cuda or out.device.index != self.device:
+            raise ValueError(f"out must live on cuda:{self.device}")
+        if out.dim() != 2 or tuple(out.shape) != (rows, cols):
+            raise ValueError(f"out must have shape {(rows, cols)}")
+        if cols > 1 and out.stride(1) != 1:
+            raise ValueError("out must have unit stride in its last dimension")
+        stride = out.stride(0) * out.element_size() if rows > 1 else cols * out.element_size()
+        return out, out, stride, tab
+
     def _counts_out(self, out: Optional[torch.Tensor], n_variants: int, accumulate: bool = False) -> torch.Tensor:
         if out is None:
             if accumulate:

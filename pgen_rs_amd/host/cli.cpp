@@ -8,11 +8,16 @@
 // genotype counts of the kept samples with filter's selection, counted on the GPU; tab-separated to stdout or FILE.
 // `pgen-hip sample-counts <PFILE_PREFIX> [--include-var <EXPR>] [--include-sam <EXPR>] [-o|--out <FILE>]` (not in the reference): the
 // other half, per-sample genotype counts over the kept variants (IID, then the four counts), same selection, staging and output.
+// `pgen-hip matrix <PFILE_PREFIX> [--include-var <EXPR>] [--include-sam <EXPR>] [--dtype i8|f16|f32] [--missing <X>] [--sample-major]
+// -o|--out <FILE.npy>` (not in the reference): the additive-coded genotype matrix (0 / 1 / 2 alternate alleles, --missing for
+// "./.") of the kept variants and samples as a NumPy .npy file, decoded on the GPU; FILE.npy.variants / FILE.npy.samples hold the ids.
 // Additions (opt-in, not in the reference): --gpus <N>, --block-mib <M>, --launch-mib <M>, --filter-threads <T>, --stats, --dry-run
 // (filter: write the VCF header only and report the body geometry; needs no GPU); BGZF output (`-o x.vcf.gz` or --bgzf,
 // --bgzf-level <1-9>, --compress-threads <T>) and `pgen-hip bgzf <IN> <OUT>`, the same writer on a file.
 // Exit codes: 0 ok; 2 usage error (clap's code); 101 where the reference would panic.
+#include <cerrno>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -75,6 +80,7 @@ const char *kUsage =
     "  filter  Filters the pgen, outputting to a VCF\n"
     "  freq    Per-variant genotype counts of the kept samples, outputting to stdout\n"
     "  sample-counts  Per-sample genotype counts over the kept variants, outputting to stdout\n"
+    "  matrix  Numeric genotype matrix of the kept variants and samples, outputting to a NumPy .npy file\n"
     "  help    Print this message\n\n"
     "query  <PFILE_PREFIX> -f, --fstring <QUERY_FSTRING> [-i, --include <QUERY>] [-s, --samples]\n"
     "filter <PFILE_PREFIX> [--include-var <VAR_QUERY>] [--include-sam <SAM_QUERY>] [-o, --out <OUT_FILE>]\n"
@@ -88,6 +94,11 @@ const char *kUsage =
     "       [--gpus <N>] [--shards <S>] [--block-mib <M>] [--read-threads <T>] [--filter-threads <T>] [--stats]\n"
     "       one line per kept sample in psam order: IID HOM_REF_CT HET_CT HOM_ALT_CT MISSING_CT (the counts of 0/0, 0/1, 1/1 and\n"
     "       ./. over the kept variants; no byte parity with plink2's .scount / .smiss is claimed)\n"
+    "matrix <PFILE_PREFIX> [--include-var <VAR_QUERY>] [--include-sam <SAM_QUERY>] [--dtype i8|f16|f32] [--missing <X>] [--sample-major]\n"
+    "       -o, --out <OUT_FILE.npy> [--gpus <N>] [--shards <S>] [--block-mib <M>] [--read-threads <T>] [--filter-threads <T>] [--stats]\n"
+    "       NumPy .npy (version 1.0, C order) of shape (variants kept, samples kept), or (samples, variants) with --sample-major:\n"
+    "       0 / 1 / 2 alternate alleles, --missing (default -1 for i8, nan for f16 / f32) for ./.; the kept variants' ID column in\n"
+    "       OUT_FILE.npy.variants and the kept samples' IID column in OUT_FILE.npy.samples, one per line\n"
     "bgzf   <IN_FILE> <OUT_FILE> [--level <1-9>] [--threads <T>] [--chunk-mib <M>]\n";
 
 [[noreturn]] void usage_error(const std::string &msg)
@@ -198,6 +209,87 @@ OutputOptions output_options(const Args &a)
     return opt;
 }
 
+// IEEE binary32 -> binary16 bits, round to nearest even; out_of_range: a finite value that does not stay finite
+uint16_t f32_to_f16(float f, bool &out_of_range)
+{
+    uint32_t x;
+    std::memcpy(&x, &f, 4);
+    const uint32_t sign = (x >> 16) & 0x8000u, mant = x & 0x7FFFFFu;
+    const int32_t exp = (int32_t)((x >> 23) & 0xFFu);
+    out_of_range = false;
+    if (exp == 0xFF) return (uint16_t)(sign | 0x7C00u | (mant ? 0x200u | (mant >> 13) : 0u));   // inf / nan (quiet)
+    const int32_t e = exp - 127 + 15;
+    if (e >= 0x1F) {
+        out_of_range = true;
+        return (uint16_t)(sign | 0x7C00u);
+    }
+    if (e <= 0) {   // subnormal or zero
+        if (e < -10) return (uint16_t)sign;
+        const uint32_t m = mant | 0x800000u;
+        const uint32_t shift = (uint32_t)(14 - e);
+        uint32_t h = m >> shift;
+        const uint32_t rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1u);
+        if (rem > half || (rem == half && (h & 1u))) h++;
+        return (uint16_t)(sign | h);
+    }
+    uint32_t h = ((uint32_t)e << 10) | (mant >> 13);
+    const uint32_t rem = mant & 0x1FFFu;
+    if (rem > 0x1000u || (rem == 0x1000u && (h & 1u))) h++;
+    if (h >= 0x7C00u) out_of_range = true;
+    return (uint16_t)(sign | h);
+}
+
+// --dtype / --missing of `matrix`: the element type and the four patterns (0, 1, 2, missing)
+MatrixOptions matrix_options(const Args &a)
+{
+    MatrixOptions m;
+    const std::string dtype = a.get("dtype").value_or("i8");
+    const std::optional<std::string> missing = a.get("missing");
+    m.sample_major = a.has("sample-major");
+    std::memset(m.values, 0, sizeof m.values);
+    if (dtype == "i8") {
+        long v = -1;
+        if (missing) {
+            char *end = nullptr;
+            errno = 0;
+            v = std::strtol(missing->c_str(), &end, 10);
+            if (missing->empty() || *end != '\0' || errno != 0 || v < -128 || v > 127)
+                usage_error("invalid value '" + *missing + "' for '--missing <X>': i8 takes an integer in -128 .. 127");
+        }
+        m.elem_bytes = 1;
+        m.descr = "|i1";
+        const int8_t vals[4] = {0, 1, 2, (int8_t)v};
+        std::memcpy(m.values, vals, 4);
+    } else if (dtype == "f16" || dtype == "f32") {
+        float v = std::nanf("");
+        if (missing) {
+            char *end = nullptr;
+            errno = 0;
+            v = std::strtof(missing->c_str(), &end);
+            if (missing->empty() || *end != '\0' || (errno == ERANGE && std::isinf(v)))
+                usage_error("invalid value '" + *missing + "' for '--missing <X>': " + dtype + " takes a number it can hold, inf or nan");
+        }
+        const float vals[4] = {0.0f, 1.0f, 2.0f, v};
+        if (dtype == "f32") {
+            m.elem_bytes = 4;
+            m.descr = "<f4";
+            std::memcpy(m.values, vals, 16);
+        } else {
+            m.elem_bytes = 2;
+            m.descr = "<f2";
+            for (int c = 0; c < 4; c++) {
+                bool range = false;
+                const uint16_t h = f32_to_f16(vals[c], range);
+                if (range) usage_error("invalid value '" + *missing + "' for '--missing <X>': f16 takes a number it can hold, inf or nan");
+                std::memcpy(m.values + 2 * c, &h, 2);
+            }
+        }
+    } else {
+        usage_error("invalid value '" + dtype + "' for '--dtype <DTYPE>' [possible values: i8, f16, f32]");
+    }
+    return m;
+}
+
 // --stats: one JSON line on stderr
 void print_stats(const OutputStats &st, std::chrono::steady_clock::time_point t_main)
 {
@@ -289,6 +381,17 @@ int main(int argc, char **argv)
             if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
             const OutputStats st = pfile.output_sample_counts(a.get("include-sam"), a.get("include-var"), a.get("out").value_or(""), output_options(a));
+            if (a.has("stats")) print_stats(st, t_main);
+            return 0;
+        }
+        if (cmd == "matrix") {
+            Args a = parse(argc, argv, 2, {{"include-var", 0}, {"include-sam", 0}, {"out", 'o'}, {"dtype", 0}, {"missing", 0}, {"gpus", 0}, {"shards", 0}, {"block-mib", 0}, {"read-threads", 0}, {"filter-threads", 0}},
+                           {{"stats", 0}, {"sample-major", 0}});
+            if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
+            if (!a.has("out") || a.get("out")->empty()) usage_error("the following required arguments were not provided: --out <OUT_FILE.npy>");
+            const MatrixOptions m = matrix_options(a);
+            const Pfile pfile = Pfile::from_prefix(a.positional[0]);
+            const OutputStats st = pfile.output_matrix(a.get("include-sam"), a.get("include-var"), *a.get("out"), m, output_options(a));
             if (a.has("stats")) print_stats(st, t_main);
             return 0;
         }

@@ -1001,6 +1001,44 @@ struct SampleCounter {
     }
 };
 
+// matrix's "counter": every block is decoded into one device buffer, copied back and written to its place in the .npy file.
+// Variant-major: a block is nv consecutive rows of the file, one pwrite.  Sample-major: a block is a column band, K pieces of
+// nv elements, written from a few threads.
+constexpr unsigned kMatrixWriteThreads = 4;   // a constant like the BGZF pool's cap, never the machine's CPU count
+struct MatrixWriter {
+    uint32_t R;
+    size_t K, V;
+    const MatrixOptions &m;
+    uint64_t pitch;   // sample-major: bytes between the device buffer's rows (a multiple of 128)
+    uint8_t *d_out, *h_out;
+    int fd;
+    const std::string &path;
+    uint64_t data_off;
+    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, uint32_t nv) const
+    {
+        const uint32_t flags = PGENHIP_MATRIX_AUTO | (m.sample_major ? PGENHIP_MATRIX_SAMPLE_MAJOR : 0u);
+        const uint64_t stride = m.sample_major ? pitch : (uint64_t)K * m.elem_bytes;
+        if (d_off)
+            check(pgenhip_decode_matrix_at(ctx, d_rec, d_off, nv, d_out, stride, m.elem_bytes, m.values, flags), "pgenhip_decode_matrix_at");
+        else
+            check(pgenhip_decode_matrix(ctx, d_rec, R, nullptr, nv, d_out, stride, m.elem_bytes, m.values, flags), "pgenhip_decode_matrix");
+    }
+    void copy(pgenhip_ctx *ctx, size_t nv) const
+    {
+        const size_t bytes = m.sample_major ? (size_t)((K - 1) * pitch) + nv * m.elem_bytes : nv * K * m.elem_bytes;
+        check(pgenhip_memcpy_d2h(ctx, h_out, d_out, bytes), "D2H matrix");
+    }
+    void collect(size_t b0, size_t nv) const
+    {
+        const size_t E = m.elem_bytes;
+        if (!m.sample_major) return pwrite_exact(fd, h_out, nv * K * E, data_off + (uint64_t)b0 * K * E, path);
+        split_span(K, K >= 64 ? kMatrixWriteThreads : 1u, [&](size_t lo, size_t hi) {
+            for (size_t k = lo; k < hi; k++) pwrite_exact(fd, h_out + k * pitch, nv * E, data_off + ((uint64_t)k * V + b0) * E, path);
+        });
+    }
+    void finish(pgenhip_ctx *) const {}
+};
+
 void write_text(const std::string &text, const std::string &filename)
 {
     if (filename.empty()) {
@@ -1109,6 +1147,71 @@ OutputStats Pfile::output_sample_counts(const std::optional<std::string> &sam_qu
     st.body_bytes = text.size() - st.header_bytes;
     st.file_bytes = text.size();
     write_text(text, filename);
+    st.seconds_body = now_s() - t_body;
+    return st;
+}
+
+OutputStats Pfile::output_matrix(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
+                                 const std::string &filename, const MatrixOptions &mopt, const OutputOptions &opt) const
+{
+    OutputStats st;
+    const double t0 = now_s();
+    const Selection sel = select(sam_query, var_query, opt.filter_threads);
+    auto column = [](const StringRecord &header, const char *name, const std::string &file) {
+        for (size_t c = 0; c < header.size(); c++)
+            if (header[c] == name) return c;
+        throw PfileError(std::string(name) + " not among the headers of " + file);
+    };
+    const size_t id_col = column(sel.var_header, "ID", pvar_path()), iid_col = column(sel.sam_header, "IID", psam_path());
+    st.seconds_filter = now_s() - t0;
+
+    const KeptSamples kept = check_selection(*this, sel);
+    const size_t V = sel.var_idx_rcds.size(), K = kept.rows.size(), E = mopt.elem_bytes;
+    st.variants = V;
+    st.samples_kept = K;
+
+    // .npy version 1.0: magic, version, u16 header length, the dict padded with spaces and ended by a newline so that the data
+    // starts on a multiple of 64 bytes
+    std::string dict = "{'descr': '" + mopt.descr + "', 'fortran_order': False, 'shape': (" +
+                       std::to_string(mopt.sample_major ? K : V) + ", " + std::to_string(mopt.sample_major ? V : K) + "), }";
+    while ((10 + dict.size() + 1) % 64 != 0) dict += ' ';
+    dict += '\n';
+    std::string header("\x93NUMPY\x01\x00", 8);
+    header += (char)(dict.size() & 0xFF);
+    header += (char)(dict.size() >> 8);
+    header += dict;
+    st.header_bytes = header.size();
+    st.body_bytes = (uint64_t)V * K * E;
+    st.file_bytes = st.header_bytes + st.body_bytes;
+
+    const double t_body = now_s();
+    static const char *const kNoDevice = "no HIP device: the genotype matrix path has no CPU fallback";
+    if (V != 0 && K != 0) const Shards probe(opt, kNoDevice);   // before the output file exists
+    Fd out(filename, O_WRONLY | O_CREAT | O_TRUNC);
+    pwrite_exact(out.get(), header.data(), header.size(), 0, filename);
+    if (V != 0 && K != 0) {   // else a zero dimension: the header alone, no device touched
+        const uint32_t R = variant_record_size();
+        // variants per block: block_text_bytes of matrix; a sample-major block is a column band whose row pieces hold at least
+        // 4 096 elements where a 1-GiB buffer allows
+        uint64_t bv = std::max<uint64_t>(1, opt.block_text_bytes / ((uint64_t)K * E));
+        if (mopt.sample_major) bv = std::max<uint64_t>(bv, std::max<uint64_t>(1, std::min<uint64_t>(4096, (1ull << 30) / ((uint64_t)K * E))));
+        bv = std::min<uint64_t>(bv, V);
+        OutputOptions blocks = opt;
+        blocks.block_text_bytes = bv * R;   // count_blocks sizes its blocks by record bytes
+        count_blocks(*this, sel.var_idx_rcds, kept, blocks, kNoDevice, st, [&](DeviceCtx &ctx, uint64_t n) {
+            const uint64_t pitch = (n * E + 127) / 128 * 128;
+            const size_t bytes = (size_t)(mopt.sample_major ? (uint64_t)K * pitch : n * K * E);
+            return MatrixWriter{R, K, V, mopt, pitch, ctx.device<uint8_t>(bytes, "device matrix"), ctx.pinned<uint8_t>(bytes, "pinned matrix"),
+                                out.get(), filename, (uint64_t)header.size()};
+        });
+    }
+    out.close();
+    std::string ids;
+    for (const auto &vr : sel.var_idx_rcds) ids += vr.second.at(id_col) + "\n";
+    write_text(ids, filename + ".variants");
+    ids.clear();
+    for (const auto &sr : sel.sam_idx_rcs) ids += sr.second.at(iid_col) + "\n";
+    write_text(ids, filename + ".samples");
     st.seconds_body = now_s() - t_body;
     return st;
 }

@@ -80,6 +80,14 @@ struct OutputOptions {
     bool verbose = false;
 };
 
+// `matrix`: the element type of the output (.npy 'descr'), the bit patterns written for codes 0-3 and the orientation
+struct MatrixOptions {
+    uint32_t elem_bytes = 1;          // 1, 2 or 4
+    std::string descr = "|i1";        // NumPy dtype string
+    uint8_t values[16] = {0, 1, 2, 0xFF};   // four elements of elem_bytes bytes, little-endian
+    bool sample_major = false;        // shape (K, V_kept) instead of (V_kept, K)
+};
+
 struct OutputStats {
     uint64_t variants = 0, samples_kept = 0, header_bytes = 0, body_bytes = 0;   // header / body: bytes of VCF text
     uint64_t file_bytes = 0;                                                     // what the output file holds (BGZF: compressed)
@@ -156,6 +164,15 @@ class Pfile {
     // A psam without an IID column is vcf_header's error.  filename empty: stdout.
     OutputStats output_sample_counts(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
                                      const std::string &filename, const OutputOptions &opt = OutputOptions()) const;
+
+    // `matrix` (not in the reference): the additive-coded genotype matrix of the kept variants and samples as a NumPy .npy file
+    // (version 1.0, C order, data on a multiple of 64 bytes), decoded on the GPU(s) (pgenhip_decode_matrix / _at) block by block and
+    // written with pwrite at offsets computed up front, so shards and blocks write independently; with sample_major a block is a
+    // column band of the file.  Beside it FILE.variants (the ID column of the kept variants, one per line) and FILE.samples (IID).
+    // Selection and staging are freq's.  No kept variant or no kept sample: a valid file with a zero dimension, no device.
+    // Uses n_gpus, n_shards, block_text_bytes (bytes of matrix per block), read_threads and filter_threads of `opt`.
+    OutputStats output_matrix(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
+                              const std::string &filename, const MatrixOptions &mopt, const OutputOptions &opt = OutputOptions()) const;
 
     // the header part of output_vcf (:110-146) on its own: used by output_vcf and by the CPU tests
     std::string vcf_header(const IdxRecords &sam_idx_rcs, const StringRecord &sam_header) const;
