@@ -235,20 +235,37 @@ uint32_t pgenhip_sample_count(const pgenhip_ctx *ctx) { return ctx ? ctx->sample
 uint32_t pgenhip_kept_count(const pgenhip_ctx *ctx) { return ctx ? ctx->kept_count : 0u; }
 uint64_t pgenhip_gt_row_bytes(const pgenhip_ctx *ctx) { return ctx ? 4ull * ctx->kept_count + 1ull : 0ull; }
 
-static int fill_args(pgenhip_ctx *ctx, EmitArgs &a, const void *d_records, uint64_t record_stride,
-                     const uint32_t *d_variant_idx, uint32_t n_variants, void *d_out)
+// The selected rows of a call (kernels.h, RowSource), checked and filled in for every entry point: by stride, by stride and
+// d_variant_idx, or by d_record_off (the *_at entries; record_stride is then not used).
+static int select_rows(const pgenhip_ctx *ctx, RowSource &a, const void *d_records, uint64_t record_stride,
+                       const uint32_t *d_variant_idx, const uint64_t *d_record_off, uint32_t n_variants)
 {
-    if (n_variants && (!d_out)) return fail(PGENHIP_ERR_BAD_ARG, "d_out is NULL");
     if (n_variants && ctx->record_size && !d_records) return fail(PGENHIP_ERR_BAD_ARG, "d_records is NULL");
-    if (n_variants > 1 && !d_variant_idx && record_stride < ctx->record_size)
+    if (n_variants > 1 && !d_variant_idx && !d_record_off && record_stride < ctx->record_size)
         return fail(PGENHIP_ERR_BAD_ARG, "record_stride < record size");
     a.records = static_cast<const uint8_t *>(d_records);
     a.record_stride = record_stride;
     a.variant_idx = d_variant_idx;
-    a.record_off = nullptr;
+    a.record_off = d_record_off;
     a.n_variants = n_variants;
     a.sample_count = ctx->sample_count;
     a.record_size = ctx->record_size;
+    return PGENHIP_OK;
+}
+
+// the *_at entries' own check, in front of their core (which reports a NULL ctx)
+static int check_record_off(const pgenhip_ctx *ctx, const uint64_t *d_record_off, uint32_t n_variants)
+{
+    if (ctx && n_variants && !d_record_off) return fail(PGENHIP_ERR_BAD_ARG, "d_record_off is NULL");
+    return PGENHIP_OK;
+}
+
+static int fill_args(pgenhip_ctx *ctx, EmitArgs &a, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                     const uint64_t *d_record_off, uint32_t n_variants, void *d_out)
+{
+    if (n_variants && (!d_out)) return fail(PGENHIP_ERR_BAD_ARG, "d_out is NULL");
+    const int rc = select_rows(ctx, a, d_records, record_stride, d_variant_idx, d_record_off, n_variants);
+    if (rc) return rc;
     a.kept_idx = ctx->subset ? ctx->d_kept : nullptr;
     a.kept_count = ctx->kept_count;
     a.out = static_cast<uint8_t *>(d_out);
@@ -429,9 +446,8 @@ static int decode_emit_core(pgenhip_ctx *ctx, const void *d_records, uint64_t re
     int rc = bind(ctx);
     if (rc) return rc;
     EmitArgs a;
-    rc = fill_args(ctx, a, d_records, d_record_off ? (uint64_t)ctx->record_size : record_stride, d_variant_idx, n_variants, d_out);
+    rc = fill_args(ctx, a, d_records, record_stride, d_variant_idx, d_record_off, n_variants, d_out);
     if (rc) return rc;
-    a.record_off = d_record_off;
     if (n_variants > 1 && out_stride < 4ull * ctx->kept_count + 1ull)
         return fail(PGENHIP_ERR_BAD_ARG, "out_stride < 4K+1");
     if (flags & ~PGENHIP_KERNEL_MASK) return fail(PGENHIP_ERR_BAD_ARG, "unknown decode_emit flag");
@@ -504,7 +520,7 @@ int pgenhip_decode_emit(pgenhip_ctx *ctx, const void *d_records, uint64_t record
 int pgenhip_decode_emit_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
                            void *d_out, uint64_t out_stride, uint32_t flags)
 {
-    if (n_variants && !d_record_off) return fail(PGENHIP_ERR_BAD_ARG, "d_record_off is NULL");
+    if (const int rc = check_record_off(ctx, d_record_off, n_variants)) return rc;
     return decode_emit_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, d_out, out_stride, flags);
 }
 
@@ -517,7 +533,7 @@ int pgenhip_emit_lines(pgenhip_ctx *ctx, const void *d_records, uint64_t record_
     int rc = bind(ctx);
     if (rc) return rc;
     EmitArgs a;
-    rc = fill_args(ctx, a, d_records, record_stride, d_variant_idx, n_variants, d_out);
+    rc = fill_args(ctx, a, d_records, record_stride, d_variant_idx, nullptr, n_variants, d_out);
     if (rc) return rc;
     if (n_variants == 0) return PGENHIP_OK;
     if (!d_prefix_off || !d_line_off) return fail(PGENHIP_ERR_BAD_ARG, "offset arrays are NULL");
@@ -595,17 +611,9 @@ static int genotype_counts_core(pgenhip_ctx *ctx, const void *d_records, uint64_
     if (flags > PGENHIP_COUNT_ROWS_PER_WAVE) return fail(PGENHIP_ERR_BAD_ARG, "unknown genotype_counts flag");
     if (n_variants == 0) return PGENHIP_OK;
     if (!d_counts) return fail(PGENHIP_ERR_BAD_ARG, "d_counts is NULL");
-    if (ctx->record_size && !d_records) return fail(PGENHIP_ERR_BAD_ARG, "d_records is NULL");
-    if (n_variants > 1 && !d_variant_idx && !d_record_off && record_stride < ctx->record_size)
-        return fail(PGENHIP_ERR_BAD_ARG, "record_stride < record size");
     CountArgs a;
-    a.records = static_cast<const uint8_t *>(d_records);
-    a.record_stride = record_stride;
-    a.variant_idx = d_variant_idx;
-    a.record_off = d_record_off;
-    a.n_variants = n_variants;
-    a.sample_count = ctx->sample_count;
-    a.record_size = ctx->record_size;
+    rc = select_rows(ctx, a, d_records, record_stride, d_variant_idx, d_record_off, n_variants);
+    if (rc) return rc;
     a.kept_count = ctx->kept_count;
     a.kept_mask = ctx->d_count_mask;   // NULL with all samples kept or an identity list
     a.counts = d_counts;
@@ -624,7 +632,7 @@ int pgenhip_genotype_counts(pgenhip_ctx *ctx, const void *d_records, uint64_t re
 int pgenhip_genotype_counts_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
                                uint32_t *d_counts, uint32_t flags)
 {
-    if (ctx && n_variants && !d_record_off) return fail(PGENHIP_ERR_BAD_ARG, "d_record_off is NULL");
+    if (const int rc = check_record_off(ctx, d_record_off, n_variants)) return rc;
     return genotype_counts_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, d_counts, flags);
 }
 
@@ -641,19 +649,11 @@ static int sample_counts_core(pgenhip_ctx *ctx, const void *d_records, uint64_t 
     if (K == 0u) return PGENHIP_OK;   // nothing to write
     if (!d_counts) return fail(PGENHIP_ERR_BAD_ARG, "d_counts is NULL");
     if ((uintptr_t)d_counts & 3u) return fail(PGENHIP_ERR_BAD_ARG, "d_counts is not 4-byte aligned");
-    if (n_variants && ctx->record_size && !d_records) return fail(PGENHIP_ERR_BAD_ARG, "d_records is NULL");
-    if (n_variants > 1 && !d_variant_idx && !d_record_off && record_stride < ctx->record_size)
-        return fail(PGENHIP_ERR_BAD_ARG, "record_stride < record size");
+    ScountArgs a;
+    rc = select_rows(ctx, a, d_records, record_stride, d_variant_idx, d_record_off, n_variants);
+    if (rc) return rc;
     if (!accumulate) HIP_TRY(hipMemsetAsync(d_counts, 0, 16ull * K, ctx->stream));   // the kernel only adds
     if (n_variants == 0) return PGENHIP_OK;
-    ScountArgs a;
-    a.records = static_cast<const uint8_t *>(d_records);
-    a.record_stride = record_stride;
-    a.variant_idx = d_variant_idx;
-    a.record_off = d_record_off;
-    a.n_variants = n_variants;
-    a.sample_count = ctx->sample_count;
-    a.record_size = ctx->record_size;
     a.kept_mask = ctx->d_count_mask;   // NULL with all samples kept or an identity list
     a.kept_rank = ctx->d_scount_rank;
     a.counts = d_counts;
@@ -670,7 +670,7 @@ int pgenhip_sample_counts(pgenhip_ctx *ctx, const void *d_records, uint64_t reco
 int pgenhip_sample_counts_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
                              uint32_t *d_counts, uint32_t flags)
 {
-    if (ctx && n_variants && !d_record_off) return fail(PGENHIP_ERR_BAD_ARG, "d_record_off is NULL");
+    if (const int rc = check_record_off(ctx, d_record_off, n_variants)) return rc;
     return sample_counts_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, d_counts, flags);
 }
 
@@ -694,9 +694,9 @@ static int decode_matrix_core(pgenhip_ctx *ctx, const void *d_records, uint64_t 
     if (n_variants == 0 || K == 0u) return PGENHIP_OK;   // nothing to write
     if (!d_out) return fail(PGENHIP_ERR_BAD_ARG, "d_out is NULL");
     if ((uintptr_t)d_out % elem_bytes || out_stride % elem_bytes) return fail(PGENHIP_ERR_BAD_ARG, "d_out and out_stride must be multiples of elem_bytes");
-    if (ctx->record_size && !d_records) return fail(PGENHIP_ERR_BAD_ARG, "d_records is NULL");
-    if (n_variants > 1 && !d_variant_idx && !d_record_off && record_stride < ctx->record_size)
-        return fail(PGENHIP_ERR_BAD_ARG, "record_stride < record size");
+    MatrixArgs a;
+    rc = select_rows(ctx, a, d_records, record_stride, d_variant_idx, d_record_off, n_variants);
+    if (rc) return rc;
     const uint64_t rows = sample_major ? K : n_variants, inner = sample_major ? n_variants : K;
     if (rows > 1 && out_stride < inner * elem_bytes) return fail(PGENHIP_ERR_BAD_ARG, "out_stride < one output row");
     // the kernels index elements and 16-byte chunks in 64 bits and divide through a double reciprocal: exact below 2^52
@@ -704,14 +704,6 @@ static int decode_matrix_core(pgenhip_ctx *ctx, const void *d_records, uint64_t 
     if ((uint64_t)n_variants * K >= kMaxSpan / 16u || (rows > 1 && out_stride >= kMaxSpan / rows) ||
         (n_variants > 1 && !d_record_off && record_stride >= kMaxSpan / (d_variant_idx ? 0xFFFFFFFFull : n_variants)))
         return fail(PGENHIP_ERR_TOO_LARGE, "matrix offsets do not fit the kernels' index types");
-    MatrixArgs a;
-    a.records = static_cast<const uint8_t *>(d_records);
-    a.record_stride = record_stride;
-    a.variant_idx = d_variant_idx;
-    a.record_off = d_record_off;
-    a.n_variants = n_variants;
-    a.sample_count = ctx->sample_count;
-    a.record_size = ctx->record_size;
     a.kept_idx = all_kept ? nullptr : ctx->d_kept;
     a.kept_count = K;
     a.out = static_cast<uint8_t *>(d_out);
@@ -750,7 +742,7 @@ int pgenhip_decode_matrix(pgenhip_ctx *ctx, const void *d_records, uint64_t reco
 int pgenhip_decode_matrix_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
                              void *d_out, uint64_t out_stride, uint32_t elem_bytes, const void *code_values, uint32_t flags)
 {
-    if (ctx && n_variants && !d_record_off) return fail(PGENHIP_ERR_BAD_ARG, "d_record_off is NULL");
+    if (const int rc = check_record_off(ctx, d_record_off, n_variants)) return rc;
     return decode_matrix_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, d_out, out_stride, elem_bytes, code_values, flags);
 }
 

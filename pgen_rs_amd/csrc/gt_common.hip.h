@@ -60,11 +60,22 @@ struct alignas(16) u32x4 {
 };
 
 // Record of output row r when rows are gathered: byte offsets (uncompressed records of a variable-width .pgen,
-// src/pgen.rs's tables) or the kept-variant list (src/pfile.rs:165 with var_idx from the list).
-__device__ __forceinline__ const uint8_t *gathered_record(const EmitArgs &a, uint64_t r)
+// src/pgen.rs's tables) or the kept-variant list (src/pfile.rs:165 with var_idx from the list).  gathered_offset: relative to a.records.
+__device__ __forceinline__ uint64_t gathered_offset(const RowSource &a, uint64_t r)
 {
-    if (a.record_off != nullptr) return a.records + a.record_off[r];
-    return a.records + (uint64_t)a.variant_idx[r] * a.record_stride;
+    return a.record_off != nullptr ? a.record_off[r] : (uint64_t)a.variant_idx[r] * a.record_stride;
+}
+
+__device__ __forceinline__ const uint8_t *gathered_record(const RowSource &a, uint64_t r) { return a.records + gathered_offset(a, r); }
+
+// Record of row r whichever way the rows are selected, decided at run time (the count and matrix kernels).  Spelled as one flat
+// three-way conditional, not as `gathered(a) ? gathered_record(a, r) : dense` like gt_rows.hip's line: the two compile to different
+// code in their kernels, and each kernel keeps the spelling it was measured with.
+__device__ __forceinline__ const uint8_t *row_record(const RowSource &a, uint64_t r)
+{
+    return a.record_off != nullptr ? a.records + a.record_off[r]
+           : a.variant_idx != nullptr ? a.records + (uint64_t)a.variant_idx[r] * a.record_stride
+                                      : a.records + r * a.record_stride;
 }
 
 // ---- all-samples text from a 16-bit record window ---------------------------------------------

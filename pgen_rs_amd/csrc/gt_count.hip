@@ -74,10 +74,7 @@ __global__ __launch_bounds__(kThreads) void gt_count_kernel(CountArgs a)
         for (int k = 0; k < RU; k++) {
             const uint64_t row = r0 + (uint64_t)k * kGroups + grp;   // groups of a wave on neighbouring rows
             const bool live = row < a.n_variants;
-            const uint8_t *rec = !live ? a.records
-                                 : a.record_off != nullptr ? a.records + a.record_off[row]
-                                 : a.variant_idx != nullptr ? a.records + (uint64_t)a.variant_idx[row] * a.record_stride
-                                                            : a.records + row * a.record_stride;
+            const uint8_t *rec = !live ? a.records : row_record(a, row);
             const uint64_t p = (uint64_t)(uintptr_t)rec;
             d[k] = (uint32_t)p & 15u;
             base[k] = rec - d[k];   // (pointer arithmetic on the argument keeps the loads global, not flat)

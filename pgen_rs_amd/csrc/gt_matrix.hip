@@ -46,13 +46,6 @@ constexpr uint32_t kWaveSamples = 128;       // TILE: samples of one wave (16 pe
 constexpr uint32_t kTileSamples = 512;       // TILE: samples of a block's tile = 128 record bytes, one line per row
 constexpr uint32_t kTileBlocksPerCu = 4;     // TILE: grid cap (16 KiB of LDS per block)
 
-__device__ __forceinline__ const uint8_t *row_record(const MatrixArgs &a, uint64_t row)
-{
-    return a.record_off != nullptr ? a.records + a.record_off[row]
-           : a.variant_idx != nullptr ? a.records + (uint64_t)a.variant_idx[row] * a.record_stride
-                                      : a.records + row * a.record_stride;
-}
-
 // the four patterns as the lookup registers of one element size
 template <int E>
 struct Table {

@@ -182,7 +182,7 @@ __global__ __launch_bounds__(kThreads) void gt_pick_kernel(EmitArgs a, PickParam
         uint64_t place = 0ull;
         {
             const uint64_t row = min(row0 + (uint64_t)lane, (uint64_t)a.n_variants - 1ull);  // rows past the end re-load the last row
-            place = HAS_VIDX ? (uint64_t)(gathered_record(a, row) - a.records) : row * a.record_stride;
+            place = HAS_VIDX ? gathered_offset(a, row) : row * a.record_stride;
         }
 #pragma unroll
         for (int i = 0; i < kMaxBatchRows; i++) {

@@ -89,13 +89,6 @@ __device__ __forceinline__ uint32_t value(const Slice &s, uint32_t p, int n_hi)
     return (v << 1) | ((s.ones >> p) & 1u);
 }
 
-__device__ __forceinline__ const uint8_t *row_record(const ScountArgs &a, uint64_t row)
-{
-    return a.record_off != nullptr ? a.records + a.record_off[row]
-           : a.variant_idx != nullptr ? a.records + (uint64_t)a.variant_idx[row] * a.record_stride
-                                      : a.records + row * a.record_stride;
-}
-
 template <int G>
 __global__ __launch_bounds__(kThreads) void gt_scount_kernel(ScountArgs a, uint32_t tiles, uint32_t slices, uint32_t cols)
 {

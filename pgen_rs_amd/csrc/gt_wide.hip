@@ -617,7 +617,7 @@ __global__ __launch_bounds__(64 * (NS + 1)) void gt_stream_dyn_kernel(EmitArgs a
             uint32_t go_lo = 0u, go_hi = 0u;
             if (HAS_VIDX && !RUNS && t0 != kNoItem) {
                 const uint64_t jr = min(j_it + (uint64_t)lane, (uint64_t)a.n_variants - 1ull);
-                const uint64_t off = a.record_off != nullptr ? a.record_off[jr] : (uint64_t)a.variant_idx[jr] * a.record_stride;
+                const uint64_t off = gathered_offset(a, jr);
                 asm volatile("v_mov_b32 %1, %3\n\tv_mov_b32 %0, %2" : "=v"(go_lo), "=v"(go_hi) : "v"((uint32_t)off), "v"((uint32_t)(off >> 32)));
             }
             auto gathered_at = [&](uint32_t r) -> const uint8_t * {

@@ -5,8 +5,8 @@
 
 namespace pgenhip {
 
-// One launch = one block of kept variants (src/pfile.rs:156 outer loop, many iterations at once).
-struct EmitArgs {
+// Which records a launch reads: the selected rows of every kernel family (each argument struct below starts with these fields).
+struct RowSource {
     const uint8_t *records;       // device; row r at records + r*record_stride
     uint64_t record_stride;
     const uint32_t *variant_idx;  // device or nullptr (identity)
@@ -15,6 +15,10 @@ struct EmitArgs {
     uint32_t n_variants;
     uint32_t sample_count;        // N
     uint32_t record_size;         // R = ceil(N/4)
+};
+
+// One launch = one block of kept variants (src/pfile.rs:156 outer loop, many iterations at once).
+struct EmitArgs : RowSource {
     const uint32_t *kept_idx;     // device or nullptr (all samples)
     uint32_t kept_count;          // K (== N when kept_idx is nullptr)
     uint8_t *out;                 // device
@@ -53,7 +57,7 @@ struct Tuning {
 };
 
 // rows are gathered (variant list or byte offsets): the HAS_VIDX instantiations
-__host__ __device__ inline bool gathered(const EmitArgs &a) { return a.variant_idx != nullptr || a.record_off != nullptr; }
+__host__ __device__ inline bool gathered(const RowSource &a) { return a.variant_idx != nullptr || a.record_off != nullptr; }
 
 // General row-tiled kernel: any alignment, any strides, list gather for kept subsets.
 hipError_t launch_gt_rows(const EmitArgs &a, int num_cus, hipStream_t stream);
@@ -106,14 +110,7 @@ bool gt_pick_applicable(const EmitArgs &a);
 hipError_t launch_gt_pick(const EmitArgs &a, const Tuning &t, int num_cus, hipStream_t stream);
 
 // Per-variant genotype counts (gt_count.hip): four u32 per selected row at counts + 4 * j (hom-ref, het, hom-alt, missing).
-struct CountArgs {
-    const uint8_t *records;       // device; row r at records + r*record_stride
-    uint64_t record_stride;
-    const uint32_t *variant_idx;  // device or nullptr (identity)
-    const uint64_t *record_off;   // device or nullptr; when set, row j's record starts at records + record_off[j]
-    uint32_t n_variants;
-    uint32_t sample_count;        // N
-    uint32_t record_size;         // R = ceil(N/4)
+struct CountArgs : RowSource {
     uint32_t kept_count;          // K (== N without a mask)
     const uint8_t *kept_mask;     // device or nullptr (all samples): 16 zero bytes, then 2 bits per sample like a record (0b01 = kept), then zeros
     uint32_t *counts;             // device
@@ -126,15 +123,8 @@ uint32_t gt_count_lanes_per_row(uint32_t record_size);
 hipError_t launch_gt_count(const CountArgs &a, bool wave_per_row, int num_cus, hipStream_t stream);
 
 // Per-sample genotype counts (gt_scount.hip): the counts of the selected rows added into counts[4 * k + c] for every kept
-// sample k (hom-ref, het, hom-alt, missing; u32 modular).  Rows as in CountArgs.
-struct ScountArgs {
-    const uint8_t *records;       // device; row r at records + r*record_stride
-    uint64_t record_stride;
-    const uint32_t *variant_idx;  // device or nullptr (identity)
-    const uint64_t *record_off;   // device or nullptr; when set, row j's record starts at records + record_off[j]
-    uint32_t n_variants;
-    uint32_t sample_count;        // N
-    uint32_t record_size;         // R = ceil(N/4)
+// sample k (hom-ref, het, hom-alt, missing; u32 modular).
+struct ScountArgs : RowSource {
     const uint8_t *kept_mask;     // device or nullptr (all samples): the ctx's count mask (CountArgs::kept_mask)
     const uint32_t *kept_rank;    // device, with kept_mask: kept samples before each 64-sample chunk
     uint32_t *counts;             // device, 4-byte aligned
@@ -142,16 +132,8 @@ struct ScountArgs {
 // slices_per_tile: row ranges per column tile (0 = as many as fill the chip's resident blocks)
 hipError_t launch_gt_scount(const ScountArgs &a, int slices_per_tile, int num_cus, hipStream_t stream);
 
-// Numeric genotype matrix (gt_matrix.hip): element (j, k) = the pattern of the code of kept sample k in selected row j.  Rows as in
-// CountArgs.
-struct MatrixArgs {
-    const uint8_t *records;       // device; row r at records + r*record_stride
-    uint64_t record_stride;
-    const uint32_t *variant_idx;  // device or nullptr (identity)
-    const uint64_t *record_off;   // device or nullptr; when set, row j's record starts at records + record_off[j]
-    uint32_t n_variants;
-    uint32_t sample_count;        // N
-    uint32_t record_size;         // R = ceil(N/4)
+// Numeric genotype matrix (gt_matrix.hip): element (j, k) = the pattern of the code of kept sample k in selected row j.
+struct MatrixArgs : RowSource {
     const uint32_t *kept_idx;     // device or nullptr (all samples, or an identity list)
     uint32_t kept_count;          // K (== N when kept_idx is nullptr)
     uint8_t *out;                 // device, a multiple of elem_bytes

@@ -163,6 +163,48 @@ class GtEngine:
         check(lib.pgenhip_timer_stop(self._ctx, C.byref(ms)), "pgenhip_timer_stop")
         return float(ms.value)
 
+    # -- which rows a call reads: one contract for every method below (csrc/kernels.h, RowSource) ------------
+    def _rows(self, records: torch.Tensor, record_stride: Optional[int], variant_idx: Optional[torch.Tensor],
+              n_variants: Optional[int], records_offset: int, vidx_msg: Optional[str] = None) -> tuple[int, int]:
+        """Checks a selection by stride or ``variant_idx`` and returns ``(record_stride, n_variants)`` with their defaults filled in:
+        the record size, and ``variant_idx``'s length or else the rows ``records`` holds.  ``vidx_msg``: the caller's one message
+        for both ``variant_idx`` refusals."""
+        if record_stride is None:
+            record_stride = self.record_size
+        self._check_dev(records, "records")
+        if variant_idx is not None:
+            self._check_dev(variant_idx, "variant_idx")
+            if variant_idx.dtype not in (torch.int32, torch.uint32):
+                raise ValueError(vidx_msg or "variant_idx must be a 32-bit integer tensor")
+        if n_variants is None:
+            if variant_idx is not None:
+                n_variants = variant_idx.numel()
+            else:
+                avail = records.numel() - records_offset
+                if self.record_size == 0 or avail < self.record_size:
+                    n_variants = 0
+                else:
+                    n_variants = (avail - self.record_size) // max(record_stride, 1) + 1
+        if variant_idx is not None and variant_idx.numel() < n_variants:
+            raise ValueError(vidx_msg or "variant_idx has fewer than n_variants entries")
+        if n_variants and variant_idx is None:
+            need_in = records_offset + (n_variants - 1) * record_stride + self.record_size
+            if records.numel() < need_in:
+                raise ValueError(f"records too small: {records.numel()} < {need_in}")
+        return record_stride, n_variants
+
+    def _rows_at(self, base: torch.Tensor, record_off: torch.Tensor, n_variants: Optional[int], msg: Optional[str] = None) -> int:
+        """Checks a selection by byte offsets into ``base`` and returns ``n_variants`` (default: ``record_off``'s length)."""
+        self._check_dev(base, "base")
+        self._check_dev(record_off, "record_off")
+        if record_off.dtype != torch.int64:
+            raise ValueError(msg or "record_off must be an int64 tensor (u64 byte offsets)")
+        if n_variants is None:
+            n_variants = record_off.numel()
+        if record_off.numel() < n_variants:
+            raise ValueError(msg or "record_off has fewer than n_variants entries")
+        return n_variants
+
     # -- the hot path -----------------------------------------------------------------------
     def decode_emit(
         self,
@@ -182,26 +224,17 @@ class GtEngine:
         ``variant_idx``: optional int32/uint32 CUDA tensor of row numbers (gapped kept-variant lists).
         Row j is written at byte ``out_offset + j*out_stride`` of ``out`` (dense 4K+1 by default).
         """
-        if record_stride is None:
-            record_stride = self.record_size
+        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset,
+                                               "variant_idx must be a 32-bit integer tensor with >= n_variants entries")
         if out_stride is None:
             out_stride = self.gt_row_bytes
         if out is None:
             out = torch.empty(out_offset + n_variants * out_stride, dtype=torch.uint8, device=self.torch_device)
-        self._check_dev(records, "records")
         self._check_dev(out, "out")
         if n_variants:
             need_out = out_offset + (n_variants - 1) * out_stride + self.gt_row_bytes
             if out.numel() < need_out:
                 raise ValueError(f"out too small: {out.numel()} < {need_out}")
-            if variant_idx is None:
-                need_in = records_offset + (n_variants - 1) * record_stride + self.record_size
-                if records.numel() < need_in:
-                    raise ValueError(f"records too small: {records.numel()} < {need_in}")
-        if variant_idx is not None:
-            self._check_dev(variant_idx, "variant_idx")
-            if variant_idx.dtype not in (torch.int32, torch.uint32) or variant_idx.numel() < n_variants:
-                raise ValueError("variant_idx must be a 32-bit integer tensor with >= n_variants entries")
         check(
             lib.pgenhip_decode_emit(
                 self._ctx,
@@ -225,10 +258,8 @@ class GtEngine:
             out_stride = self.gt_row_bytes
         if out is None:
             out = torch.empty(max(n_variants, 1) * out_stride, dtype=torch.uint8, device=self.torch_device)
-        for t, name in ((base, "base"), (record_off, "record_off"), (out, "out")):
-            self._check_dev(t, name)
-        if record_off.dtype != torch.int64 or record_off.numel() < n_variants:
-            raise ValueError("record_off must be an int64 tensor (u64 byte offsets) with >= n_variants entries")
+        self._rows_at(base, record_off, n_variants, "record_off must be an int64 tensor (u64 byte offsets) with >= n_variants entries")
+        self._check_dev(out, "out")
         if n_variants and out.numel() < (n_variants - 1) * out_stride + self.gt_row_bytes:
             raise ValueError("out too small")
         check(lib.pgenhip_decode_emit_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, _ptr(out), out_stride, kernel), "pgenhip_decode_emit_at")
@@ -291,28 +322,7 @@ class GtEngine:
         Rows are selected as in ``decode_emit``: row j's record is at byte ``records_offset + r*record_stride`` of ``records``,
         ``r = variant_idx[j]`` or ``j``.  ``n_variants`` defaults to ``variant_idx``'s length, else to the rows ``records`` holds.
         ``out``: optional int32 CUDA tensor of >= 4n entries (written from its first element; nothing else is touched)."""
-        if record_stride is None:
-            record_stride = self.record_size
-        self._check_dev(records, "records")
-        if variant_idx is not None:
-            self._check_dev(variant_idx, "variant_idx")
-            if variant_idx.dtype not in (torch.int32, torch.uint32):
-                raise ValueError("variant_idx must be a 32-bit integer tensor")
-        if n_variants is None:
-            if variant_idx is not None:
-                n_variants = variant_idx.numel()
-            else:
-                avail = records.numel() - records_offset
-                if self.record_size == 0 or avail < self.record_size:
-                    n_variants = 0
-                else:
-                    n_variants = (avail - self.record_size) // max(record_stride, 1) + 1
-        if variant_idx is not None and variant_idx.numel() < n_variants:
-            raise ValueError("variant_idx has fewer than n_variants entries")
-        if n_variants and variant_idx is None:
-            need_in = records_offset + (n_variants - 1) * record_stride + self.record_size
-            if records.numel() < need_in:
-                raise ValueError(f"records too small: {records.numel()} < {need_in}")
+        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
         out = self._counts_out(out, n_variants)
         check(
             lib.pgenhip_genotype_counts(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants,
@@ -324,14 +334,7 @@ class GtEngine:
     def genotype_counts_at(self, base: torch.Tensor, record_off: torch.Tensor, n_variants: Optional[int] = None,
                            out: Optional[torch.Tensor] = None, kernel: int = _capi.COUNT_AUTO) -> torch.Tensor:
         """``genotype_counts`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
-        self._check_dev(base, "base")
-        self._check_dev(record_off, "record_off")
-        if record_off.dtype != torch.int64:
-            raise ValueError("record_off must be an int64 tensor (u64 byte offsets)")
-        if n_variants is None:
-            n_variants = record_off.numel()
-        if record_off.numel() < n_variants:
-            raise ValueError("record_off has fewer than n_variants entries")
+        n_variants = self._rows_at(base, record_off, n_variants)
         out = self._counts_out(out, n_variants)
         check(lib.pgenhip_genotype_counts_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, _ptr(out), kernel),
               "pgenhip_genotype_counts_at")
@@ -354,28 +357,7 @@ class GtEngine:
         Rows are selected as in ``genotype_counts`` (a row named twice in ``variant_idx`` counts twice).  ``out``: optional int32
         CUDA tensor of >= 4K entries (written from its first element; nothing else is touched).  ``accumulate``: add to what
         ``out`` holds instead of overwriting it."""
-        if record_stride is None:
-            record_stride = self.record_size
-        self._check_dev(records, "records")
-        if variant_idx is not None:
-            self._check_dev(variant_idx, "variant_idx")
-            if variant_idx.dtype not in (torch.int32, torch.uint32):
-                raise ValueError("variant_idx must be a 32-bit integer tensor")
-        if n_variants is None:
-            if variant_idx is not None:
-                n_variants = variant_idx.numel()
-            else:
-                avail = records.numel() - records_offset
-                if self.record_size == 0 or avail < self.record_size:
-                    n_variants = 0
-                else:
-                    n_variants = (avail - self.record_size) // max(record_stride, 1) + 1
-        if variant_idx is not None and variant_idx.numel() < n_variants:
-            raise ValueError("variant_idx has fewer than n_variants entries")
-        if n_variants and variant_idx is None:
-            need_in = records_offset + (n_variants - 1) * record_stride + self.record_size
-            if records.numel() < need_in:
-                raise ValueError(f"records too small: {records.numel()} < {need_in}")
+        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
         out = self._counts_out(out, self.kept_count, accumulate)
         flags = kernel | (_capi.SCOUNT_ACCUMULATE if accumulate else 0)
         check(
@@ -388,14 +370,7 @@ class GtEngine:
     def sample_counts_at(self, base: torch.Tensor, record_off: torch.Tensor, n_variants: Optional[int] = None,
                          out: Optional[torch.Tensor] = None, kernel: int = _capi.SCOUNT_AUTO, accumulate: bool = False) -> torch.Tensor:
         """``sample_counts`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
-        self._check_dev(base, "base")
-        self._check_dev(record_off, "record_off")
-        if record_off.dtype != torch.int64:
-            raise ValueError("record_off must be an int64 tensor (u64 byte offsets)")
-        if n_variants is None:
-            n_variants = record_off.numel()
-        if record_off.numel() < n_variants:
-            raise ValueError("record_off has fewer than n_variants entries")
+        n_variants = self._rows_at(base, record_off, n_variants)
         out = self._counts_out(out, self.kept_count, accumulate)
         flags = kernel | (_capi.SCOUNT_ACCUMULATE if accumulate else 0)
         check(lib.pgenhip_sample_counts_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, _ptr(out), flags),
@@ -428,28 +403,7 @@ class GtEngine:
         Without ``out`` the variant-major result is contiguous; the sample-major result is a ``[:, :V]`` view of rows allocated at
         a pitch rounded up to 128 bytes, so that the transpose kernel stores whole lines: ``.contiguous()`` is the caller's choice
         and cost."""
-        if record_stride is None:
-            record_stride = self.record_size
-        self._check_dev(records, "records")
-        if variant_idx is not None:
-            self._check_dev(variant_idx, "variant_idx")
-            if variant_idx.dtype not in (torch.int32, torch.uint32):
-                raise ValueError("variant_idx must be a 32-bit integer tensor")
-        if n_variants is None:
-            if variant_idx is not None:
-                n_variants = variant_idx.numel()
-            else:
-                avail = records.numel() - records_offset
-                if self.record_size == 0 or avail < self.record_size:
-                    n_variants = 0
-                else:
-                    n_variants = (avail - self.record_size) // max(record_stride, 1) + 1
-        if variant_idx is not None and variant_idx.numel() < n_variants:
-            raise ValueError("variant_idx has fewer than n_variants entries")
-        if n_variants and variant_idx is None:
-            need_in = records_offset + (n_variants - 1) * record_stride + self.record_size
-            if records.numel() < need_in:
-                raise ValueError(f"records too small: {records.numel()} < {need_in}")
+        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
         out, res, stride, tab = self._matrix_out(out, n_variants, dtype, sample_major, values)
         flags = kernel | (_capi.MATRIX_SAMPLE_MAJOR if sample_major else 0)
         check(lib.pgenhip_decode_matrix(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants,
@@ -461,14 +415,7 @@ class GtEngine:
                          dtype: torch.dtype = torch.int8, sample_major: bool = False, values=None,
                          out: Optional[torch.Tensor] = None, kernel: int = _capi.MATRIX_AUTO) -> torch.Tensor:
         """``decode_matrix`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
-        self._check_dev(base, "base")
-        self._check_dev(record_off, "record_off")
-        if record_off.dtype != torch.int64:
-            raise ValueError("record_off must be an int64 tensor (u64 byte offsets)")
-        if n_variants is None:
-            n_variants = record_off.numel()
-        if record_off.numel() < n_variants:
-            raise ValueError("record_off has fewer than n_variants entries")
+        n_variants = self._rows_at(base, record_off, n_variants)
         out, res, stride, tab = self._matrix_out(out, n_variants, dtype, sample_major, values)
         flags = kernel | (_capi.MATRIX_SAMPLE_MAJOR if sample_major else 0)
         check(lib.pgenhip_decode_matrix_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, out.data_ptr(), stride,
