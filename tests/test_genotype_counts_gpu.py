@@ -113,6 +113,30 @@ def test_seeded_layouts_against_numpy(n, keep):
             assert (got == want[-1:]).all(), f"one row, kernel {kern}"
 
 
+# rows in which every sample has the same code: one category is K, the others 0, and with 0xFF the set pad bits are not counted
+# (6 084 / 6 085: the last N of the 32-lanes class and the first that AUTO gives a wave per row)
+@pytest.mark.parametrize("n", [1, 5, 63, 64, 65, 300, 2504, 6084, 6085, 70_001])
+@pytest.mark.parametrize("keep", ["all", "p50"])
+def test_constant_rows(n, keep):
+    rng = np.random.default_rng(n * 17 + len(keep))
+    kept = kept_sets(n, rng)[keep]
+    k = n if kept is None else len(kept)
+    r, v = rsize(n), 9
+    stride = r + 5
+    with pgen_rs_amd.GtEngine(n, kept_idx=kept, device=0) as eng:
+        for fill, code in ((0x55, 1), (0xAA, 2), (0xFF, 3), (0x00, 0)):
+            # strided rows from byte 3, the bytes around them the opposite pattern
+            raw = np.full(3 + v * stride, fill ^ 0xFF, dtype=np.uint8)
+            raw[3:].reshape(v, stride)[:, :r] = fill
+            want = np.zeros((v, 4), dtype=np.int64)
+            want[:, code] = k
+            assert (np_counts(np.full((v, r), fill, dtype=np.uint8), n, kept) == want).all()
+            d_raw = torch.from_numpy(raw).to(DEV)
+            for kern in KERNELS:
+                got = run_counts(eng, kern, v, records=d_raw, record_stride=stride, records_offset=3)
+                assert (got == want).all(), f"fill {fill:#04x}, kernel {kern}"
+
+
 def test_n_variants_zero_is_a_no_op_and_bad_flags():
     with pgen_rs_amd.GtEngine(300, device=0) as eng:
         buf = torch.full((8,), SENT, dtype=torch.int32, device=DEV)

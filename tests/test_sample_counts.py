@@ -70,9 +70,15 @@ def test_plan_mirror_matches_the_source():
         "const uint32_t C = (a.record_size + 15u) / 16u;",
         "const uint64_t rbeg = V * slice / slices, rend = V * (slice + 1u) / slices;",
         "constexpr uint32_t kSlots = kWaves * kGroups;",
+        "const int n_hi = 32 - __builtin_clz(batches | 1u);",
     ]:
         assert line in src, line
     assert SP.WINDOW_BATCHES == (1 << 8) - 1 and SP.THREADS == 256 and SP.BATCH == 8
+    # a flush window fits a counter, and its last batch is the first to need the top hi plane
+    assert SP.HI_BITS == 8 and SP.counter_capacity() == 2047
+    assert SP.BATCH * SP.WINDOW_BATCHES <= SP.counter_capacity()
+    assert SP.hi_planes(SP.WINDOW_BATCHES) == SP.HI_BITS
+    assert [SP.hi_planes(b) for b in (0, 1, 2, 3, 4, 127, 128, 255)] == [1, 1, 2, 2, 3, 7, 8, 8]
     assert [SP.lanes_per_row(n) for n in (1, 256, 257, 512, 513, 1024, 1025, 2048, 2049, 4096, 4097)] == [4, 4, 8, 8, 16, 16, 32, 32, 64, 64, 64]
     assert [SP.tiles(n) for n in (4096, 4097, 8192, 8193, 500_000)] == [1, 2, 2, 3, 123]
 
