@@ -327,57 +327,45 @@ static bool rowpick_shape(const pgenhip_ctx *ctx, const EmitArgs &a)
     return K * 50ull >= N && K * 5ull <= N;
 }
 
-// AUTO for all samples kept, GT segments at a.out + j * a.out_stride
-static int dispatch_all_samples(pgenhip_ctx *ctx, const EmitArgs &a)
-{
-    const Tuning &t = ctx->tune;
-    if (gt_runs_preferred(a))
-        // short rows, dense records (8 <= N <= 1915): runs of rows as one work item, text staged through LDS in 4-KiB groups
-        // so that every 128-B line leaves whole: 0.68-0.71 of roofline from N = 100 to 1500 where the flat kernel had
-        // 0.42-0.56, the pick kernel 0.31-0.62 and the row-item stream kernel 0.51-0.65 (profiles/r02_kernel_sweeps.md)
-        LAUNCH_TRY(launch_gt_runs(a, t, ctx->num_cus, ctx->stream));
-    else if (gt_pick_applicable(a) && a.sample_count < 2000u)
-        // short rows that are gathered or padded (no contiguous runs): batches of rows through gt_pick.hip with the identity for a
-        // table, several rows per load instruction.  Gathered rows, fraction of roofline, pick / flat / row-item stream kernel:
-        // N = 64 0.46 / 0.28 / -, 300 0.49 / 0.31 / -, 1 399 0.58 / 0.40 / 0.52, 1 500 0.58 / 0.40 / 0.54, 2 504 0.59 / 0.41 / 0.68
-        LAUNCH_TRY(launch_gt_pick(a, t, ctx->num_cus, ctx->stream));
-    else if (gt_wide_applicable(a))
-        LAUNCH_TRY(launch_gt_wide(a, t, ctx->num_cus, ctx->stream));
-    else if (gt_flat_applicable(a))
-        LAUNCH_TRY(launch_gt_flat(a, t, ctx->num_cus, ctx->stream));
-    else
-        LAUNCH_TRY(launch_gt_rows(a, ctx->num_cus, ctx->stream));
-    return PGENHIP_OK;
-}
+// What an emit call runs: one of the launchers of kernels.h (run() below), or the two passes (dispatch_two_pass)
+enum class Emit { Rows, Flat, Wide, Runs, LineRuns, Pick, Scan, RowPick, TwoPass };
 
-// AUTO for all samples kept, full lines (a.line_off / a.prefix_off set)
-static int dispatch_all_samples_lines(pgenhip_ctx *ctx, const EmitArgs &a)
+// AUTO for all samples kept: GT segments at a.out + j * a.out_stride, or full lines (a.line_off / a.prefix_off set).  Two chains:
+// their sample thresholds were measured per mode.
+static Emit choose_all_samples(const EmitArgs &a)
 {
-    const Tuning &t = ctx->tune;
-    if (gt_wide_lines_applicable(a) && a.sample_count >= 1400u) {
+    if (a.line_off != nullptr) {
         // long rows: the work-queue stream kernel writes the GT segments in place behind their prefixes (+ a small prefix copy).
         // From N = 1 400: at N = 1 024 / 1 200 it runs at 0.45 / 0.49 of roofline against 0.48-0.51 for the two kernels below, at
         // N = 1 500 / 1 900 at 0.56 / 0.60 against 0.49-0.55 (profiles/r02_kernel_sweeps.md)
-        LAUNCH_TRY(launch_gt_wide(a, t, ctx->num_cus, ctx->stream));
-    } else if (gt_lineruns_applicable(a) && gt_lineruns_rows(a) >= 7u && a.sample_count < 1000u) {
+        if (gt_wide_lines_applicable(a) && a.sample_count >= 1400u) return Emit::Wide;
         // short rows, dense records: runs of whole lines (prefix + GT + '\n') assembled in LDS and stored as whole 128-B lines.
         // Ahead of the pick family's full-line kernel while a run holds seven lines or more (prefixes up to ~90 bytes) and N < 1 000:
         // 30-byte prefixes, N = 100 / 300 / 500: 0.41 / 0.51 / 0.53 of roofline against 0.36 / 0.44 / 0.49; with 166-byte prefixes a run
         // is three or four lines and the pick family is ahead at every N (0.37-0.52 against 0.14-0.50); from N = 1 000 it is level or
         // ahead with short prefixes too (profiles/r03_logs/lines_sweep_after.log)
-        LAUNCH_TRY(launch_gt_lineruns(a, t, ctx->num_cus, ctx->stream));
-    } else if (gt_pick_applicable(a)) {
-        // the pick family (identity for a table): rows' interiors + batched seams (gt_pick_lines_kernel); gathered / padded records: row by row
-        LAUNCH_TRY(launch_gt_pick(a, t, ctx->num_cus, ctx->stream));   // (writes the prefixes too)
-    } else {
-        LAUNCH_TRY(launch_gt_rows(a, ctx->num_cus, ctx->stream));
+        if (gt_lineruns_applicable(a) && gt_lineruns_rows(a) >= 7u && a.sample_count < 1000u) return Emit::LineRuns;
+        // the pick family (identity for a table): rows' interiors + batched seams (gt_pick_lines_kernel); gathered / padded records:
+        // row by row (it writes the prefixes too)
+        if (gt_pick_applicable(a)) return Emit::Pick;
+        return Emit::Rows;
     }
-    return PGENHIP_OK;
+    // short rows, dense records (8 <= N <= 1915): runs of rows as one work item, text staged through LDS in 4-KiB groups
+    // so that every 128-B line leaves whole: 0.68-0.71 of roofline from N = 100 to 1500 where the flat kernel had
+    // 0.42-0.56, the pick kernel 0.31-0.62 and the row-item stream kernel 0.51-0.65 (profiles/r02_kernel_sweeps.md)
+    if (gt_runs_preferred(a)) return Emit::Runs;
+    // short rows that are gathered or padded (no contiguous runs): batches of rows through gt_pick.hip with the identity for a
+    // table, several rows per load instruction.  Gathered rows, fraction of roofline, pick / flat / row-item stream kernel:
+    // N = 64 0.46 / 0.28 / -, 300 0.49 / 0.31 / -, 1 399 0.58 / 0.40 / 0.52, 1 500 0.58 / 0.40 / 0.54, 2 504 0.59 / 0.41 / 0.68
+    if (gt_pick_applicable(a) && a.sample_count < 2000u) return Emit::Pick;
+    if (gt_wide_applicable(a)) return Emit::Wide;
+    if (gt_flat_applicable(a)) return Emit::Flat;
+    return Emit::Rows;
 }
 
 // Two passes for sparse keeps on long records, chunk by chunk of as many rows as the compact scratch holds: (1) the row-owner kernel
-// (chunks of many rows; else the segment kernel) compacts each row's kept codes into a K-sample record, (2) the all-samples
-// dispatch above turns those records into text.
+// (chunks of many rows; else the segment kernel) compacts each row's kept codes into a K-sample record, (2) what
+// choose_all_samples above picks for those records turns them into text.
 static bool two_pass(const pgenhip_ctx *ctx, const EmitArgs &a)
 {
     // (full lines: only where the second pass is the stream kernel's LINES mode, K >= 1 024 — below that it would flush row by row)
@@ -385,6 +373,73 @@ static bool two_pass(const pgenhip_ctx *ctx, const EmitArgs &a)
            ctx->max_seg_count <= kCompactMaxSegCodes &&
            (a.line_off != nullptr ? a.kept_count >= 1024u : (a.n_variants <= 1u || a.out_stride == 4ull * a.kept_count + 1ull));
 }
+
+// AUTO for a kept subset that is not the identity: one chain for GT segments and full lines (where a kernel writes full lines it
+// writes the prefixes too)
+static Emit choose_subset(const pgenhip_ctx *ctx, const EmitArgs &a)
+{
+    if (rowpick_shape(ctx, a)) return Emit::RowPick;
+    if (two_pass(ctx, a) && !very_sparse(ctx)) return Emit::TwoPass;
+    // full lines only (the line-run kernel needs a.line_off): kept subset on VERY short dense records: runs of whole lines, picks through
+    // its LDS kept table (N = 100, 30-byte prefixes, 50 / 10 % kept: 0.28 / 0.13 of roofline against 0.23 / 0.10 for the pick family's
+    // full-line kernel; from N = 300 that kernel is level or ahead — N = 500: 0.48 / 0.27 against 0.39 / 0.15 — and with long prefixes
+    // always: profiles/r03_logs/lines_sweep_after.log)
+    if (gt_lineruns_applicable(a) && gt_lineruns_rows(a) >= 7u && a.sample_count < 300u) return Emit::LineRuns;
+    // short records (the 1000 Genomes shape with a sample filter): output-driven pick, any density (full lines: interiors + batched
+    // seams; gathered / padded records: row by row)
+    if (gt_pick_applicable(a)) return Emit::Pick;
+    if (very_sparse(ctx) || ctx->record_size < 16u) return Emit::Rows;
+    // the segment kernel (full lines: each GT segment behind its prefix, the prefix kernel the rest)
+    return Emit::Scan;
+}
+
+// The one place a kernel id (the flags of the emit entry points) becomes what runs: AUTO by shape, a forced id where its kernel takes
+// the shape.  Only AUTO treats an identity list (`--include-sam` that keeps everybody: same bytes) as all samples: forced kernels see the list.
+static int choose(const pgenhip_ctx *ctx, EmitArgs &a, uint32_t kernel, Emit &out)
+{
+    const bool lines = a.line_off != nullptr;
+    const char *needs = nullptr;   // a forced kernel's refusal
+    switch (kernel) {
+        case PGENHIP_KERNEL_AUTO:
+            if (ctx->identity) a.kept_idx = nullptr;
+            out = a.kept_idx == nullptr ? choose_all_samples(a) : choose_subset(ctx, a);
+            break;
+        case PGENHIP_KERNEL_ROWS: out = Emit::Rows; break;
+        case PGENHIP_KERNEL_FLAT:
+            out = Emit::Flat;
+            if (!gt_flat_applicable(a)) needs = "PGENHIP_KERNEL_FLAT needs GT segments, all samples kept, N >= 8 and out_stride == 4N+1";
+            break;
+        case PGENHIP_KERNEL_SCAN:
+            out = Emit::Scan;
+            if (!ctx->subset || ctx->record_size < 16u) needs = "PGENHIP_KERNEL_SCAN needs a kept-sample list and N >= 61 (records of >= 16 bytes)";
+            break;
+        case PGENHIP_KERNEL_WIDE:
+            out = Emit::Wide;
+            if (!(lines ? gt_wide_lines_applicable(a) : gt_wide_applicable(a)))
+                needs = "PGENHIP_KERNEL_WIDE needs all samples kept, N >= 1024 and (GT segments) out_stride == 4N+1";
+            break;
+        case PGENHIP_KERNEL_PICK:
+            out = Emit::Pick;
+            if (!gt_pick_applicable(a)) needs = "PGENHIP_KERNEL_PICK needs K >= 1, 61 <= N <= 4096 and (GT segments) out_stride == 4K+1";
+            break;
+        case PGENHIP_KERNEL_RUNS:
+            out = lines ? Emit::LineRuns : Emit::Runs;
+            if (!(lines ? gt_lineruns_applicable(a) : gt_runs_applicable(a)))
+                needs = lines ? "PGENHIP_KERNEL_RUNS (lines) needs dense records, >= 8 kept samples (of <= 4096 with a keep list) and two lines per item"
+                              : "PGENHIP_KERNEL_RUNS needs all samples kept, 8 <= N <= 3831, dense records and text, no variant gather";
+            break;
+        case PGENHIP_KERNEL_ROWPICK:
+            out = Emit::RowPick;   // (the launcher refuses more than 4 096 segments: PGENHIP_ERR_HIP)
+            if (!ctx->subset || ctx->record_size < 16u || ctx->kept_count < 1u || ctx->kept_count > kRowPickMaxKept)
+                needs = "PGENHIP_KERNEL_ROWPICK needs a kept-sample list of 1 .. 16384 samples and N >= 61";
+            break;
+        default:
+            needs = "not a kernel id: the emit entry points take PGENHIP_KERNEL_AUTO, _ROWS, _FLAT, _SCAN, _WIDE, _PICK, _RUNS or _ROWPICK";
+    }
+    return needs ? fail(PGENHIP_ERR_BAD_ARG, needs) : PGENHIP_OK;
+}
+
+static int run(pgenhip_ctx *ctx, const EmitArgs &a, const ScanArgs &sc, Emit choice);
 
 static int dispatch_two_pass(pgenhip_ctx *ctx, const EmitArgs &a, const ScanArgs &sc)
 {
@@ -429,99 +484,88 @@ static int dispatch_two_pass(pgenhip_ctx *ctx, const EmitArgs &a, const ScanArgs
         if (a.line_off) {
             d.prefix_off = a.prefix_off + row0;  // offsets are absolute: the same blob and output base
             d.line_off = a.line_off + row0;
-            const int rc = dispatch_all_samples_lines(ctx, d);
-            if (rc) return rc;
         } else {
             d.out = a.out + row0 * a.out_stride;
-            const int rc = dispatch_all_samples(ctx, d);
-            if (rc) return rc;
         }
+        const int rc = run(ctx, d, sc, choose_all_samples(d));
+        if (rc) return rc;
     }
     return PGENHIP_OK;
 }
 
-static int decode_emit_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
-                            const uint64_t *d_record_off, uint32_t n_variants, void *d_out, uint64_t out_stride, uint32_t flags)
+// The only launches of the emit kernels (beside the compact passes above), each under LAUNCH_TRY: a failed launch marks the counter ring dirty
+static int run(pgenhip_ctx *ctx, const EmitArgs &a, const ScanArgs &sc, Emit choice)
+{
+    const Tuning &t = ctx->tune;
+    switch (choice) {
+        case Emit::Rows: LAUNCH_TRY(launch_gt_rows(a, ctx->num_cus, ctx->stream)); break;
+        case Emit::Flat: LAUNCH_TRY(launch_gt_flat(a, t, ctx->num_cus, ctx->stream)); break;
+        case Emit::Wide: LAUNCH_TRY(launch_gt_wide(a, t, ctx->num_cus, ctx->stream)); break;
+        case Emit::Runs: LAUNCH_TRY(launch_gt_runs(a, t, ctx->num_cus, ctx->stream)); break;
+        case Emit::LineRuns: LAUNCH_TRY(launch_gt_lineruns(a, t, ctx->num_cus, ctx->stream)); break;
+        case Emit::Pick: LAUNCH_TRY(launch_gt_pick(a, t, ctx->num_cus, ctx->stream)); break;
+        case Emit::Scan: LAUNCH_TRY(launch_gt_scan(a, sc, t, ctx->num_cus, ctx->stream)); break;
+        case Emit::RowPick: LAUNCH_TRY(launch_gt_rowpick(a, sc, t, ctx->num_cus, ctx->stream)); break;
+        case Emit::TwoPass: return dispatch_two_pass(ctx, a, sc);
+    }
+    return PGENHIP_OK;
+}
+
+// pgenhip_emit_lines' own inputs
+struct LineInputs {
+    const void *prefix_blob;
+    const uint64_t *prefix_off, *line_off;
+    uint64_t max_prefix_bytes;
+};
+
+// The three emit entry points: GT segments at d_out + j * out_stride (lines == nullptr), or full lines at d_out + line_off[j].
+// A refused forced kernel has claimed its counter block already (the applicability predicates look at a.work_counters).
+static int emit_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                     const uint64_t *d_record_off, uint32_t n_variants, void *d_out, uint64_t out_stride, const LineInputs *lines, uint32_t flags)
 {
     int rc = bind(ctx);
     if (rc) return rc;
     EmitArgs a;
     rc = fill_args(ctx, a, d_records, record_stride, d_variant_idx, d_record_off, n_variants, d_out);
     if (rc) return rc;
-    if (n_variants > 1 && out_stride < 4ull * ctx->kept_count + 1ull)
-        return fail(PGENHIP_ERR_BAD_ARG, "out_stride < 4K+1");
-    if (flags & ~PGENHIP_KERNEL_MASK) return fail(PGENHIP_ERR_BAD_ARG, "unknown decode_emit flag");
-    a.out_stride = out_stride;
-    if (n_variants == 0) return PGENHIP_OK;
+    if (lines) {
+        if (n_variants == 0) return PGENHIP_OK;
+        if (!lines->prefix_off || !lines->line_off) return fail(PGENHIP_ERR_BAD_ARG, "offset arrays are NULL");
+        if (lines->max_prefix_bytes && !lines->prefix_blob) return fail(PGENHIP_ERR_BAD_ARG, "d_prefix_blob is NULL");
+        // the kernels plan tiles, batches and seams from the bound in 32 bits (gt_rows.hip: tiles per row, grid-stride over V x tiles)
+        if (lines->max_prefix_bytes >= kMaxLineBytes || lines->max_prefix_bytes + 4ull * ctx->kept_count + 1ull >= kMaxLineBytes)
+            return fail(PGENHIP_ERR_TOO_LARGE, "max_prefix_bytes + 4K + 1 >= 2^31");
+        a.prefix_blob = static_cast<const uint8_t *>(lines->prefix_blob);
+        a.prefix_off = lines->prefix_off;
+        a.line_off = lines->line_off;
+        a.max_line_bytes = lines->max_prefix_bytes + 4ull * ctx->kept_count + 1ull;
+    } else {
+        if (n_variants > 1 && out_stride < 4ull * ctx->kept_count + 1ull) return fail(PGENHIP_ERR_BAD_ARG, "out_stride < 4K+1");
+        if (flags & ~PGENHIP_KERNEL_MASK) return fail(PGENHIP_ERR_BAD_ARG, "unknown decode_emit flag");
+        a.out_stride = out_stride;
+        if (n_variants == 0) return PGENHIP_OK;
+    }
     rc = claim_counters(ctx, a);
     if (rc) return rc;
-    const Tuning &t = ctx->tune;
+    Emit choice;
+    rc = choose(ctx, a, flags, choice);
+    if (rc) return rc;
     const ScanArgs sc{ctx->d_seg_rank, ctx->max_seg_count, (uint32_t)ctx->tune.align_stores};
-
-    switch (flags & PGENHIP_KERNEL_MASK) {
-        case PGENHIP_KERNEL_AUTO:
-            if (ctx->identity) a.kept_idx = nullptr;  // `--include-sam` that keeps everybody: same bytes, the all-samples kernels
-            if (a.kept_idx == nullptr) return dispatch_all_samples(ctx, a);
-            if (rowpick_shape(ctx, a)) {
-                LAUNCH_TRY(launch_gt_rowpick(a, sc, t, ctx->num_cus, ctx->stream));
-                return PGENHIP_OK;
-            }
-            if (two_pass(ctx, a) && !very_sparse(ctx))
-                return dispatch_two_pass(ctx, a, sc);
-            if (gt_pick_applicable(a))
-                // short records (the 1000 Genomes shape with a sample filter): output-driven pick, any density
-                LAUNCH_TRY(launch_gt_pick(a, t, ctx->num_cus, ctx->stream));
-            else if (very_sparse(ctx) || ctx->record_size < 16u)
-                LAUNCH_TRY(launch_gt_rows(a, ctx->num_cus, ctx->stream));
-            else
-                LAUNCH_TRY(launch_gt_scan(a, sc, t, ctx->num_cus, ctx->stream));
-            return PGENHIP_OK;
-        case PGENHIP_KERNEL_ROWS:
-            LAUNCH_TRY(launch_gt_rows(a, ctx->num_cus, ctx->stream));
-            return PGENHIP_OK;
-        case PGENHIP_KERNEL_SCAN:
-            if (!ctx->subset) return fail(PGENHIP_ERR_BAD_ARG, "segment kernels need a kept-sample list");
-            if (ctx->record_size < 16u) return fail(PGENHIP_ERR_BAD_ARG, "segment kernels need N >= 61 (records of >= 16 bytes)");
-            LAUNCH_TRY(launch_gt_scan(a, sc, t, ctx->num_cus, ctx->stream));
-            return PGENHIP_OK;
-        case PGENHIP_KERNEL_ROWPICK:
-            if (!ctx->subset || ctx->record_size < 16u || ctx->kept_count < 1u || ctx->kept_count > kRowPickMaxKept)
-                return fail(PGENHIP_ERR_BAD_ARG, "row-owner kernel needs a kept-sample list of 1 .. 16384 samples and N >= 61");
-            LAUNCH_TRY(launch_gt_rowpick(a, sc, t, ctx->num_cus, ctx->stream));
-            return PGENHIP_OK;
-        case PGENHIP_KERNEL_PICK:
-            if (!gt_pick_applicable(a)) return fail(PGENHIP_ERR_BAD_ARG, "pick kernel needs K >= 1, 61 <= N <= 4096 and out_stride == 4K+1");
-            LAUNCH_TRY(launch_gt_pick(a, t, ctx->num_cus, ctx->stream));
-            return PGENHIP_OK;
-        case PGENHIP_KERNEL_WIDE:
-            if (!gt_wide_applicable(a)) return fail(PGENHIP_ERR_BAD_ARG, "wide kernel needs all samples kept, N >= 1024 and out_stride == 4N+1");
-            LAUNCH_TRY(launch_gt_wide(a, t, ctx->num_cus, ctx->stream));
-            return PGENHIP_OK;
-        case PGENHIP_KERNEL_RUNS:
-            if (!gt_runs_applicable(a)) return fail(PGENHIP_ERR_BAD_ARG, "runs kernel needs all samples kept, 8 <= N <= ~2000, dense records and text, no variant gather");
-            LAUNCH_TRY(launch_gt_runs(a, t, ctx->num_cus, ctx->stream));
-            return PGENHIP_OK;
-        case PGENHIP_KERNEL_FLAT:
-            if (!gt_flat_applicable(a)) return fail(PGENHIP_ERR_BAD_ARG, "flat kernel needs all samples kept and out_stride == 4N+1");
-            LAUNCH_TRY(launch_gt_flat(a, t, ctx->num_cus, ctx->stream));
-            return PGENHIP_OK;
-        default:
-            return fail(PGENHIP_ERR_BAD_ARG, "unknown kernel id");
-    }
+    return run(ctx, a, sc, choice);
 }
 
 int pgenhip_decode_emit(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride,
                         const uint32_t *d_variant_idx, uint32_t n_variants,
                         void *d_out, uint64_t out_stride, uint32_t flags)
 {
-    return decode_emit_core(ctx, d_records, record_stride, d_variant_idx, nullptr, n_variants, d_out, out_stride, flags);
+    return emit_core(ctx, d_records, record_stride, d_variant_idx, nullptr, n_variants, d_out, out_stride, nullptr, flags);
 }
 
 int pgenhip_decode_emit_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
                            void *d_out, uint64_t out_stride, uint32_t flags)
 {
     if (const int rc = check_record_off(ctx, d_record_off, n_variants)) return rc;
-    return decode_emit_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, d_out, out_stride, flags);
+    return emit_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, d_out, out_stride, nullptr, flags);
 }
 
 int pgenhip_emit_lines(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride,
@@ -530,77 +574,8 @@ int pgenhip_emit_lines(pgenhip_ctx *ctx, const void *d_records, uint64_t record_
                        const uint64_t *d_line_off, uint64_t max_prefix_bytes,
                        void *d_out, uint32_t flags)
 {
-    int rc = bind(ctx);
-    if (rc) return rc;
-    EmitArgs a;
-    rc = fill_args(ctx, a, d_records, record_stride, d_variant_idx, nullptr, n_variants, d_out);
-    if (rc) return rc;
-    if (n_variants == 0) return PGENHIP_OK;
-    if (!d_prefix_off || !d_line_off) return fail(PGENHIP_ERR_BAD_ARG, "offset arrays are NULL");
-    if (max_prefix_bytes && !d_prefix_blob) return fail(PGENHIP_ERR_BAD_ARG, "d_prefix_blob is NULL");
-    // the kernels plan tiles, batches and seams from the bound in 32 bits (gt_rows.hip: tiles per row, grid-stride over V x tiles)
-    if (max_prefix_bytes >= kMaxLineBytes || max_prefix_bytes + 4ull * ctx->kept_count + 1ull >= kMaxLineBytes)
-        return fail(PGENHIP_ERR_TOO_LARGE, "max_prefix_bytes + 4K + 1 >= 2^31");
-    a.prefix_blob = static_cast<const uint8_t *>(d_prefix_blob);
-    a.prefix_off = d_prefix_off;
-    a.line_off = d_line_off;
-    a.max_line_bytes = max_prefix_bytes + 4ull * ctx->kept_count + 1ull;
-    rc = claim_counters(ctx, a);
-    if (rc) return rc;
-    const Tuning &t = ctx->tune;
-    const ScanArgs sc{ctx->d_seg_rank, ctx->max_seg_count, (uint32_t)ctx->tune.align_stores};
-    switch (flags) {
-        case PGENHIP_KERNEL_AUTO:
-            if (ctx->identity) a.kept_idx = nullptr;
-            if (a.kept_idx == nullptr) return dispatch_all_samples_lines(ctx, a);
-            if (rowpick_shape(ctx, a)) {
-                LAUNCH_TRY(launch_gt_rowpick(a, sc, t, ctx->num_cus, ctx->stream));   // (writes the prefixes too)
-                return PGENHIP_OK;
-            }
-            if (two_pass(ctx, a) && !very_sparse(ctx)) return dispatch_two_pass(ctx, a, sc);
-            if (gt_lineruns_applicable(a) && gt_lineruns_rows(a) >= 7u && a.sample_count < 300u) {
-                // kept subset on VERY short dense records: runs of whole lines through the line-run kernel, picks through its LDS kept table
-                // (N = 100, 30-byte prefixes, 50 / 10 % kept: 0.28 / 0.13 of roofline against 0.23 / 0.10 for the pick family's full-line
-                // kernel; from N = 300 that kernel is level or ahead — N = 500: 0.48 / 0.27 against 0.39 / 0.15 — and with long prefixes
-                // always: profiles/r03_logs/lines_sweep_after.log)
-                LAUNCH_TRY(launch_gt_lineruns(a, t, ctx->num_cus, ctx->stream));
-            } else if (gt_pick_applicable(a)) {
-                // kept subset on short records: the pick family (interiors + batched seams; gathered / padded records: row by row)
-                LAUNCH_TRY(launch_gt_pick(a, t, ctx->num_cus, ctx->stream));   // (writes the prefixes too)
-            } else if (ctx->record_size >= 16u && !very_sparse(ctx)) {
-                // kept subset: the segment kernel writes each GT segment behind its prefix, the prefix kernel the rest
-                LAUNCH_TRY(launch_gt_scan(a, sc, t, ctx->num_cus, ctx->stream));   // (writes the prefixes too)
-            } else {
-                LAUNCH_TRY(launch_gt_rows(a, ctx->num_cus, ctx->stream));
-            }
-            return PGENHIP_OK;
-        case PGENHIP_KERNEL_ROWS:
-            LAUNCH_TRY(launch_gt_rows(a, ctx->num_cus, ctx->stream));
-            return PGENHIP_OK;
-        case PGENHIP_KERNEL_WIDE:
-            if (!gt_wide_lines_applicable(a)) return fail(PGENHIP_ERR_BAD_ARG, "PGENHIP_KERNEL_WIDE needs all samples kept and sample_count >= 1024");
-            LAUNCH_TRY(launch_gt_wide(a, t, ctx->num_cus, ctx->stream));
-            return PGENHIP_OK;
-        case PGENHIP_KERNEL_SCAN:
-            if (!ctx->subset || ctx->record_size < 16u) return fail(PGENHIP_ERR_BAD_ARG, "PGENHIP_KERNEL_SCAN needs a kept-sample list and N >= 61");
-            LAUNCH_TRY(launch_gt_scan(a, sc, t, ctx->num_cus, ctx->stream));
-            return PGENHIP_OK;
-        case PGENHIP_KERNEL_RUNS:
-            if (!gt_lineruns_applicable(a)) return fail(PGENHIP_ERR_BAD_ARG, "PGENHIP_KERNEL_RUNS (lines) needs dense records, >= 8 kept samples (of <= 4096 with a keep list) and two lines per item");
-            LAUNCH_TRY(launch_gt_lineruns(a, t, ctx->num_cus, ctx->stream));
-            return PGENHIP_OK;
-        case PGENHIP_KERNEL_ROWPICK:
-            if (!ctx->subset || ctx->record_size < 16u || ctx->kept_count < 1u || ctx->kept_count > kRowPickMaxKept)
-                return fail(PGENHIP_ERR_BAD_ARG, "PGENHIP_KERNEL_ROWPICK needs a kept-sample list of 1 .. 16384 samples and N >= 61");
-            LAUNCH_TRY(launch_gt_rowpick(a, sc, t, ctx->num_cus, ctx->stream));
-            return PGENHIP_OK;
-        case PGENHIP_KERNEL_PICK:
-            if (!gt_pick_applicable(a)) return fail(PGENHIP_ERR_BAD_ARG, "PGENHIP_KERNEL_PICK needs K >= 1 and 61 <= N <= 4096");
-            LAUNCH_TRY(launch_gt_pick(a, t, ctx->num_cus, ctx->stream));
-            return PGENHIP_OK;
-        default:
-            return fail(PGENHIP_ERR_BAD_ARG, "pgenhip_emit_lines supports kernel flags AUTO, ROWS, WIDE, SCAN, PICK, RUNS and ROWPICK");
-    }
+    const LineInputs lines{d_prefix_blob, d_prefix_off, d_line_off, max_prefix_bytes};
+    return emit_core(ctx, d_records, record_stride, d_variant_idx, nullptr, n_variants, d_out, 0, &lines, flags);
 }
 
 static int genotype_counts_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,

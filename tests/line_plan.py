@@ -6,9 +6,11 @@ Mirrors (keep in step; test_line_plan.py checks the constants against the source
   * pick family, full lines: the ``gt_pick_lines_kernel`` plan at the end of ``launch_gt_pick`` (gt_pick.hip)
   * prefix copy of the stream / segment / row-owner / pick row-by-row kernels: ``prefix_copy_shift`` (gt_common.hip.h)
   * row-owner kernel: ``table_bytes`` / ``rank_bytes`` / ``codes_bytes`` and ``plan`` (gt_rowpick.hip), ``kRowPickMaxKept`` (kernels.h)
-  * AUTO's choice between them: ``dispatch_all_samples_lines`` and ``pgenhip_emit_lines`` (capi.hip)
+  * AUTO's choice between them: ``choose_all_samples`` and ``choose_subset`` (capi.hip)
 """
 from __future__ import annotations
+
+from subset_plan import ROWPICK_MAX_KEPT, SEG_SAMPLES, record_size, rowpick_lds_bytes  # noqa: F401  (kernels.h, gt_rowpick.hip)
 
 # gt_wide.hip
 LR_PFX_BYTES = 768          # kLrPfxBytes: LDS area of the prefixes of B + 1 lines
@@ -21,13 +23,6 @@ PICK_STAGE_BYTES = 8192     # kStageBytes: record stage of a batch
 PICK_MAX_PACKED_ROWS = 64   # kMaxPackedRows
 PICK_MAX_SAMPLES = 4096     # kMaxSamples
 PICK_BATCH_BYTES = 32768    # default text bytes per batch (PGENHIP_KNOB_PICK_BATCH_BYTES)
-# kernels.h
-ROWPICK_MAX_KEPT = 16384    # kRowPickMaxKept
-SEG_SAMPLES = 16384         # kScanSegmentSamples
-
-
-def record_size(n: int) -> int:
-    return (2 * n + 7) // 8
 
 
 def lineruns_rows(n: int, k: int, subset: bool, p: int) -> int:
@@ -84,14 +79,6 @@ def pick_cps_shift(p: int) -> int:
 
 def prefix_copy_shift(p: int) -> int:
     return 3 if p <= 48 else 4
-
-
-def rowpick_lds_bytes(n: int, k: int) -> int:
-    """Dynamic LDS of one row-owner block (four waves)."""
-    def r16(x):
-        return (x + 15) & ~15
-    n_seg = (n + SEG_SAMPLES - 1) // SEG_SAMPLES
-    return r16(2 * (k + 8)) + r16(4 * (n_seg + 1)) + 4 * (SEG_SAMPLES // 4 + r16((k + 3) // 4 + 16))
 
 
 # ---- the edges, derived from the functions above (each is the LAST P before the planned value changes) ------------------------

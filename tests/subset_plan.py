@@ -3,9 +3,10 @@ sides of every edge AUTO and the kernels' launch plans derive from N, K, V and t
 coverage test imports the cell table from here.
 
 Mirrors (keep in step; test_subset_plan.py checks the constants and literals against the sources):
-  * AUTO's kept-subset dispatch in capi.hip: ``two_pass_shape``, ``very_sparse``, ``rowpick_shape``, ``two_pass``, the AUTO arms of
-    ``decode_emit_core`` and ``pgenhip_emit_lines``, ``kCompactSliceBytes`` and the chunking of ``dispatch_two_pass`` (chunk rows,
+  * AUTO's kept-subset dispatch in capi.hip: ``two_pass_shape``, ``very_sparse``, ``rowpick_shape``, ``two_pass``, the one chain of
+    ``choose_subset`` (GT segments and full lines), ``kCompactSliceBytes`` and the chunking of ``dispatch_two_pass`` (chunk rows,
     rounding to whole row-owner rounds, the short last chunk that goes to the segment kernel);
+  * the forced kernel ids' checks in ``choose`` (capi.hip) and the ``gt_*_applicable`` predicates behind them: ``accepts``;
   * the segment kernel's launch plan, ``launch_gt_scan`` (gt_scan.hip): ``n_seg``, ``groups`` (clamped to 1 when one resident round
     cannot hold a block per segment: the grid then runs in rounds), ``xcd_groups``, ``bands``; the compact pass's plan;
   * the row-owner kernel's ``plan`` / ``gt_rowpick_applicable`` (gt_rowpick.hip): LDS bytes, blocks per CU, ``max_blocks``;
@@ -225,6 +226,50 @@ def two_pass_chunks(n: int, k: int, v: int, tune: Tune, num_cus: int):
     return chunk, tuple(out)
 
 
+# include/pgen_hip.h: PGENHIP_KERNEL_* (test_subset_plan.py checks them against the header)
+KERNEL_IDS = {"auto": 0, "rows": 1, "flat": 2, "scan": 3, "wide": 4, "pick": 6, "runs": 7, "rowpick": 8}
+
+
+def runs_rows(n: int) -> int:
+    """Rows per work item of the RUNS mode, all samples kept (gt_wide.hip run_rows_for): one wide load of the run's records and one
+    span of its text; 0 from N = 3 832 (no whole row of 4N + 1 bytes in a span)."""
+    import line_plan as LP
+
+    r = record_size(n)
+    return min(LP.LR_LOAD_BYTES // r, LP.SPAN_BYTES // (4 * n + 1)) if r else 0
+
+
+def accepts(kernel: int, n: int, k: int, subset: bool, bound: int = 0, gather: bool = False, mode: str = "lines",
+            dense_pitch: bool = True) -> bool:
+    """Does a call of more than one row take this kernel id: pgenhip_emit_lines (mode "lines", `bound` = max_prefix_bytes) or
+    pgenhip_decode_emit / _at (mode "segments", `dense_pitch`: out_stride == 4K + 1)?  capi.hip's ``choose`` and the kernels'
+    applicability, for dense records.  `subset`: the ctx has a kept list (an identity list is one: forced kernels see it);
+    `gather`: a variant list or record byte offsets.  False for AUTO's neighbours that are no kernel id (5, 9 .. 15, bits above
+    the mask)."""
+    import line_plan as LP   # (it imports this module's constants: not at the top)
+
+    lines = mode == "lines"
+    name = {v: key for key, v in KERNEL_IDS.items()}.get(kernel)
+    if name is None:
+        return False
+    if name in ("auto", "rows"):
+        return True
+    if name == "scan":
+        return subset and record_size(n) >= 16
+    if name == "rowpick":
+        return subset and record_size(n) >= 16 and 1 <= k <= ROWPICK_MAX_KEPT
+    if name == "pick":
+        return record_size(n) >= 16 and n <= LP.PICK_MAX_SAMPLES and k >= 1 and (lines or dense_pitch)
+    if name == "wide":
+        return not subset and n >= 1024 and (lines or dense_pitch)
+    if name == "flat":
+        return not lines and not subset and n >= 8 and dense_pitch
+    assert name == "runs"
+    if lines:
+        return not gather and LP.lineruns_accepts(n, k, subset, bound)
+    return not subset and not gather and n >= 8 and runs_rows(n) >= 1 and dense_pitch
+
+
 KERNELS = ("auto", "rows", "scan", "rowpick")
 
 
@@ -236,15 +281,13 @@ def arm(n: int, k: int, v: int, *, mode: str = "segments", kernel: str = "auto",
     lines = mode == "lines"
     if msc is None:
         msc = min(k, SEG_SAMPLES)
+    if kernel != "auto" and not accepts(KERNEL_IDS[kernel], n, k, True, mode=mode):
+        return Plan(kernel, status="bad_arg")
     if kernel == "rows":
         return Plan("rows")
     if kernel == "scan":
-        if record_size(n) < 16:
-            return Plan("scan", status="bad_arg")
         return Plan("scan", scan=scan_plan(n, k, v, tune, num_cus))
     if kernel == "rowpick":
-        if record_size(n) < 16 or not 1 <= k <= ROWPICK_MAX_KEPT:
-            return Plan("rowpick", status="bad_arg")
         rp = rowpick_plan(n, k, v, tune, num_cus)
         return Plan("rowpick", status="ok" if rp else "hip", rowpick=rp)
     assert kernel == "auto"

@@ -37,6 +37,7 @@ import pgen_oracle as oracle
 import pgen_rs_amd
 from helpers import GOLDEN
 from pgen_rs_amd import _capi
+from subset_plan import accepts
 
 pytestmark = pytest.mark.gpu
 
@@ -46,23 +47,6 @@ K_AUTO, K_ROWS, K_WIDE, K_SCAN, K_PICK, K_RUNS, K_ROWPICK = (_capi.KERNEL_AUTO, 
                                                               _capi.KERNEL_PICK, _capi.KERNEL_RUNS, _capi.KERNEL_ROWPICK)
 ALL_KERNELS = (K_AUTO, K_ROWS, K_WIDE, K_SCAN, K_PICK, K_RUNS, K_ROWPICK)
 KNAME = {K_AUTO: "AUTO", K_ROWS: "ROWS", K_WIDE: "WIDE", K_SCAN: "SCAN", K_PICK: "PICK", K_RUNS: "RUNS", K_ROWPICK: "ROWPICK"}
-
-
-def accepts(kernel, n, k, subset, bound, gather):
-    """Does pgenhip_emit_lines take the shape with this forced kernel (capi.hip's checks + the kernels' applicability)?"""
-    if kernel in (K_AUTO, K_ROWS):
-        return True
-    if kernel == K_WIDE:
-        return not subset and n >= 1024
-    if kernel == K_SCAN:
-        return subset and n >= 61
-    if kernel == K_PICK:
-        return 61 <= n <= LP.PICK_MAX_SAMPLES and k >= 1
-    if kernel == K_RUNS:
-        return not gather and LP.lineruns_accepts(n, k, subset, bound)
-    if kernel == K_ROWPICK:
-        return subset and n >= 61 and 1 <= k <= LP.ROWPICK_MAX_KEPT
-    raise AssertionError(kernel)
 
 
 def prefix_lengths(rng, v, p, dist, batch=8):

@@ -49,8 +49,9 @@ def test_mirrored_constants_match_the_sources():
 
 def test_mirrored_dispatch_matches_capi():
     """capi.hip: the literals of two_pass_shape, very_sparse, rowpick_shape and two_pass, the chunk rounding of dispatch_two_pass,
-    and the AUTO arms; a new condition in any of them changes its branch count and fails here until subset_plan.py and the cells
-    follow."""
+    the AUTO arms (choose_subset: one chain for GT segments and full lines; choose_all_samples: one per mode) and the one place
+    that maps a kernel id (choose) for the three entry points; a new condition in any of them changes its branch count and fails
+    here until subset_plan.py, line_plan.py and the cells follow."""
     b = _body("capi.hip", "bool two_pass_shape(uint32_t sample_count, uint32_t kept_count)")
     assert ("sample_count > 4096u && kept_count >= 8u && (uint64_t)kept_count * 170ull >= (uint64_t)sample_count &&\n"
             "           (uint64_t)kept_count * 22ull <= (uint64_t)sample_count;") in b
@@ -77,21 +78,47 @@ def test_mirrored_dispatch_matches_capi():
     assert "if (row_owner && round && chunk_rows > round && ctx->tune.scan_chunk_rows <= 0) chunk_rows -= chunk_rows % round;" in b
     assert "if (row_owner && (uint64_t)n * 2ull >= chunk_rows)" in b
     assert "if (a.record_off) c.record_off = a.record_off + row0;" in b and "else if (a.variant_idx) c.variant_idx = a.variant_idx + row0;" in b
-    assert _conditions(b) == 13
-    # the AUTO arms for kept subsets, GT segments and full lines, in this order
-    seg = _body("capi.hip", "static int decode_emit_core(")
-    seg = seg[seg.index("case PGENHIP_KERNEL_AUTO:"): seg.index("case PGENHIP_KERNEL_ROWS:")]
-    order = ["if (ctx->identity) a.kept_idx = nullptr;", "if (rowpick_shape(ctx, a))", "if (two_pass(ctx, a) && !very_sparse(ctx))",
-             "if (gt_pick_applicable(a))", "else if (very_sparse(ctx) || ctx->record_size < 16u)", "launch_gt_rows(", "launch_gt_scan("]
-    assert [seg.index(s) for s in order] == sorted(seg.index(s) for s in order) and _conditions(seg) == 8
-    lines = _body("capi.hip", "int pgenhip_emit_lines(")
-    lines = lines[lines.index("case PGENHIP_KERNEL_AUTO:"): lines.index("case PGENHIP_KERNEL_ROWS:")]
-    order = ["if (ctx->identity) a.kept_idx = nullptr;", "if (rowpick_shape(ctx, a))", "if (two_pass(ctx, a) && !very_sparse(ctx))",
-             "if (gt_lineruns_applicable(a) && gt_lineruns_rows(a) >= 7u && a.sample_count < 300u)", "} else if (gt_pick_applicable(a)) {",
-             "} else if (ctx->record_size >= 16u && !very_sparse(ctx)) {", "launch_gt_scan(", "launch_gt_rows("]
-    assert [lines.index(s) for s in order] == sorted(lines.index(s) for s in order) and _conditions(lines) == 11
-    # forced ROWPICK: capi.hip's own checks (the launcher refuses more than 4 096 segments: PGENHIP_ERR_HIP)
-    assert _src("capi.hip").count("if (!ctx->subset || ctx->record_size < 16u || ctx->kept_count < 1u || ctx->kept_count > kRowPickMaxKept)") == 2
+    assert _conditions(b) == 12
+    # the AUTO arms for kept subsets: one chain for GT segments and full lines, in this order
+    b = _body("capi.hip", "static Emit choose_subset(const pgenhip_ctx *ctx, const EmitArgs &a)")
+    order = ["if (rowpick_shape(ctx, a)) return Emit::RowPick;", "if (two_pass(ctx, a) && !very_sparse(ctx)) return Emit::TwoPass;",
+             "if (gt_lineruns_applicable(a) && gt_lineruns_rows(a) >= 7u && a.sample_count < 300u) return Emit::LineRuns;",
+             "if (gt_pick_applicable(a)) return Emit::Pick;", "if (very_sparse(ctx) || ctx->record_size < 16u) return Emit::Rows;",
+             "return Emit::Scan;"]
+    assert [b.index(s) for s in order] == sorted(b.index(s) for s in order) and _conditions(b) == 9
+    # the AUTO arms for all samples kept (tests/line_plan.py): the full-line chain, then the GT-segment chain
+    b = _body("capi.hip", "static Emit choose_all_samples(const EmitArgs &a)")
+    order = ["if (a.line_off != nullptr) {", "if (gt_wide_lines_applicable(a) && a.sample_count >= 1400u) return Emit::Wide;",
+             "if (gt_lineruns_applicable(a) && gt_lineruns_rows(a) >= 7u && a.sample_count < 1000u) return Emit::LineRuns;",
+             "if (gt_pick_applicable(a)) return Emit::Pick;", "return Emit::Rows;\n    }", "if (gt_runs_preferred(a)) return Emit::Runs;",
+             "if (gt_pick_applicable(a) && a.sample_count < 2000u) return Emit::Pick;", "if (gt_wide_applicable(a)) return Emit::Wide;",
+             "if (gt_flat_applicable(a)) return Emit::Flat;", "return Emit::Rows;"]
+    at = []
+    for s in order:
+        at.append(b.index(s, at[-1] + 1 if at else 0))   # each behind the one before it
+    assert _conditions(b) == 12
+    # AUTO: an identity list goes with all samples, a kept list through the chain above; forced kernels see the list
+    b = _body("capi.hip", "static int choose(const pgenhip_ctx *ctx, EmitArgs &a, uint32_t kernel, Emit &out)")
+    auto = b[b.index("case PGENHIP_KERNEL_AUTO:"): b.index("case PGENHIP_KERNEL_ROWS:")]
+    assert "if (ctx->identity) a.kept_idx = nullptr;\n            out = a.kept_idx == nullptr ? choose_all_samples(a) : choose_subset(ctx, a);" in auto
+    assert b.count("a.kept_idx = nullptr") == 1 and _conditions(b) == 17
+    # forced ROWPICK: capi.hip's own checks (the launcher refuses more than 4 096 segments: PGENHIP_ERR_HIP), once for every entry point
+    src = _src("capi.hip")
+    assert src.count("if (!ctx->subset || ctx->record_size < 16u || ctx->kept_count < 1u || ctx->kept_count > kRowPickMaxKept)") == 1
+    assert all(src.count(f"case PGENHIP_KERNEL_{k.upper()}:") == 1 for k in SP.KERNEL_IDS)
+    # the three entry points reach the one core, which chooses once and launches through the one switch
+    for sig in ("int pgenhip_decode_emit(", "int pgenhip_decode_emit_at(", "int pgenhip_emit_lines("):
+        b = _body("capi.hip", sig)
+        assert b.count("return emit_core(ctx, ") == 1 and "launch_gt_" not in b and "choose" not in b and "PGENHIP_KERNEL_" not in b, sig
+    core = _body("capi.hip", "static int emit_core(")
+    steps = ["bind(ctx)", "fill_args(ctx, a, ", "claim_counters(ctx, a)", "choose(ctx, a, flags, choice)", "return run(ctx, a, sc, choice);"]
+    assert [core.index(s) for s in steps] == sorted(core.index(s) for s in steps) and all(core.count(s) == 1 for s in steps)
+    assert src.count("const ScanArgs sc{") == 1 and "launch_gt_" not in core
+    run = _body("capi.hip", "static int run(pgenhip_ctx *ctx, const EmitArgs &a, const ScanArgs &sc, Emit choice)\n{")
+    emit_launches = re.findall(r"LAUNCH_TRY\(launch_gt_(\w+)\(", src)
+    assert sorted(re.findall(r"LAUNCH_TRY\(launch_gt_(\w+)\(", run)) == sorted(["rows", "flat", "wide", "runs", "lineruns", "pick", "scan", "rowpick"])
+    assert len(emit_launches) == 10   # + the two compact passes of dispatch_two_pass
+    assert "const int rc = run(ctx, d, sc, choose_all_samples(d));" in _body("capi.hip", "static int dispatch_two_pass(")
 
 
 def test_mirrored_segment_plan_and_knobs_match_the_source():
@@ -134,6 +161,28 @@ def test_mirrored_row_owner_plan_matches_the_source():
     assert (SP.ROWPICK_MAX_SEGS, SP.ROWPICK_ROWS_PER_WAVE) == (4096, 8)
     l = _body("gt_rowpick.hip", "hipError_t launch_gt_rowpick(")
     assert "dim3((uint32_t)(need < L.max_blocks ? need : L.max_blocks))" in l
+
+
+def test_forced_kernel_acceptance_table():
+    """accepts(): the kernel ids as include/pgen_hip.h numbers them, and where each forced kernel is taken on the shapes of
+    test_emit_kernel_ids_gpu.py (GT segments at the dense pitch; at pitch 4K + 4 only ROWS, SCAN and ROWPICK; no id that is not a kernel)."""
+    header = (CSRC.parent.parent / "include" / "pgen_hip.h").read_text()
+    ids = {m[0].lower(): int(m[1]) for m in re.findall(r"#define PGENHIP_KERNEL_([A-Z]+) (\d+)u", header)}
+    assert ids == SP.KERNEL_IDS and "#define PGENHIP_KERNEL_MASK 0xFu" in header
+    shapes = {"40": (40, 40, False), "40/5": (40, 5, True), "300": (300, 300, False), "300/30": (300, 30, True), "300/id": (300, 300, True),
+              "1024": (1024, 1024, False), "5000/50": (5000, 50, True), "20000/16385": (20_000, 16_385, True)}
+    lists = {"300/30", "300/id", "5000/50", "20000/16385"}
+    table = {"rows": set(shapes), "flat": {"40", "300", "1024"}, "wide": {"1024"}, "runs": {"40", "300", "1024"},
+             "pick": {"300", "300/30", "300/id", "1024"}, "scan": lists, "rowpick": lists - {"20000/16385"}}
+    for name, taken in table.items():
+        for tag, (n, k, subset) in shapes.items():
+            seg = dict(mode="segments")
+            assert SP.accepts(SP.KERNEL_IDS[name], n, k, subset, **seg) == (tag in taken), (name, tag)
+            assert SP.accepts(SP.KERNEL_IDS[name], n, k, subset, dense_pitch=False, **seg) == (tag in taken and name in ("rows", "scan", "rowpick"))
+            assert SP.accepts(SP.KERNEL_IDS[name], n, k, subset, gather=True, **seg) == (tag in taken and name != "runs")
+            assert not SP.accepts(SP.KERNEL_IDS["flat"], n, k, subset, 10, False)   # full lines: never FLAT
+    assert not any(SP.accepts(i, 300, 300, False, mode=m) for i in (5, 9, 10, 11, 12, 13, 14, 15, 0x10, 0x13) for m in ("segments", "lines"))
+    assert (SP.runs_rows(3831), SP.runs_rows(3832)) == (1, 0) and SP.accepts(7, 3831, 3831, False, mode="segments") and not SP.accepts(7, 3832, 3832, False, mode="segments")
 
 
 def test_derived_edges():
