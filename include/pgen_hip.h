@@ -274,7 +274,9 @@ int pgenhip_sample_counts_at(pgenhip_ctx *ctx, const void *d_base, const uint64_
  *     out_stride the contract allows.  TILE: all samples kept, sample-major, d_out and out_stride multiples of 16 bytes (its stores
  *     cover whole 128-byte lines when they are multiples of 128: pad the row pitch).  A forced shape that does not apply is
  *     PGENHIP_ERR_BAD_ARG with a detail string; AUTO takes STREAM / TILE where they apply and GENERAL everywhere else.
- *   - An offset that does not fit the kernels' index types (2^52 bytes or more) is PGENHIP_ERR_TOO_LARGE before any launch.
+ *   - An offset that does not fit the kernels' index types (2^52 bytes or more) is PGENHIP_ERR_TOO_LARGE before any launch: the
+ *     n_variants x K elements, out_stride times the output rows, record_stride times n_variants.  With d_variant_idx only record_stride
+ *     itself is bounded: the row numbers live on the device, like d_record_off's offsets, and a record's address is 64-bit arithmetic.
  * Same launch contract as pgenhip_genotype_counts: device pointers only, no allocation, no synchronisation, queued on the ctx
  * stream, graph-capturable.
  * flags: a shape (low 4 bits) | orientation. */

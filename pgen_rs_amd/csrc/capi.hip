@@ -674,10 +674,13 @@ static int decode_matrix_core(pgenhip_ctx *ctx, const void *d_records, uint64_t 
     if (rc) return rc;
     const uint64_t rows = sample_major ? K : n_variants, inner = sample_major ? n_variants : K;
     if (rows > 1 && out_stride < inner * elem_bytes) return fail(PGENHIP_ERR_BAD_ARG, "out_stride < one output row");
-    // the kernels index elements and 16-byte chunks in 64 bits and divide through a double reciprocal: exact below 2^52
+    // the kernels index elements and 16-byte chunks in 64 bits and divide through a double reciprocal: exact below 2^52.  A record's
+    // address is plain 64-bit pointer arithmetic (row_record, gt_common.hip.h): by stride, all rows' records lie inside the span; with
+    // a variant list the row numbers live on the device (as record_off's offsets do) and only the stride itself is bounded
     constexpr uint64_t kMaxSpan = 1ull << 52;
+    const bool by_stride = n_variants > 1 && !d_record_off;
     if ((uint64_t)n_variants * K >= kMaxSpan / 16u || (rows > 1 && out_stride >= kMaxSpan / rows) ||
-        (n_variants > 1 && !d_record_off && record_stride >= kMaxSpan / (d_variant_idx ? 0xFFFFFFFFull : n_variants)))
+        (by_stride && !d_variant_idx && record_stride >= kMaxSpan / n_variants) || (by_stride && d_variant_idx && record_stride >= kMaxSpan))
         return fail(PGENHIP_ERR_TOO_LARGE, "matrix offsets do not fit the kernels' index types");
     a.kept_idx = all_kept ? nullptr : ctx->d_kept;
     a.kept_count = K;

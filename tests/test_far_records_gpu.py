@@ -1,0 +1,283 @@
+"""Records whose byte offset from d_records / d_base is 2^32 or more, through every entry point that selects rows and every kernel
+that takes the shape (the per-variant counts have test_genotype_counts_gpu.py::test_row_past_4_gib).
+
+One shared buffer of 2^32 + 4 099 + 8 * R_max + 64 bytes: random bytes in its first MiB (the near rows, and the place every far
+offset lands on when it is cut to 32 bits: a wrong record, read in bounds) and from 64 bytes before FAR to its end (the far rows).
+Each call mixes near and far rows through (i) d_variant_idx with record_stride = FAR, (ii) a small stride with d_variant_idx values
+near FAR / stride, (iii) d_record_off.  Expected bytes: the CPU oracle and the numpy references on the few records involved.
+
+The kernels that cannot gather (RUNS, the pick family's packed path, the line-run kernel) get dense records that cross 2^32
+themselves, 70 GB of text each, checked as test_gt_parity_gpu.py::test_gt_segments_past_4_gib checks: a line feed at the end of
+every row (on the device), sentinels behind the last row, windows of 100 rows against the oracle at the start, around the row whose
+record holds byte 2^32, at the end and at six seeded places.
+"""
+import numpy as np
+import pytest
+import torch
+
+import longrow_ref as LR
+import matrix_ref as MR
+import pgen_oracle as oracle
+import pgen_rs_amd
+import subset_plan as SP
+from pgen_rs_amd import _capi
+
+pytestmark = pytest.mark.gpu
+
+from longrow_ref import BACK, GIB, SENT, need_gib
+
+DEV = "cuda:0"
+FAR = (1 << 32) + 4099
+R_MAX = MR.rsize(20_000)
+NEAR_BYTES = 1 << 20
+FAR_LO = FAR - 64
+BUF_BYTES = FAR + 8 * R_MAX + 64
+
+
+class FarBuffer:
+    def __init__(self):
+        g = torch.Generator(device=DEV)
+        g.manual_seed(4099)
+        self.dev = torch.empty(BUF_BYTES, dtype=torch.uint8, device=DEV)
+        self.dev[:NEAR_BYTES] = torch.randint(0, 256, (NEAR_BYTES,), dtype=torch.uint8, device=DEV, generator=g)
+        self.dev[FAR_LO:] = torch.randint(0, 256, (BUF_BYTES - FAR_LO,), dtype=torch.uint8, device=DEV, generator=g)
+        self.near = self.dev[:NEAR_BYTES].cpu().numpy()
+        self.far = self.dev[FAR_LO:].cpu().numpy()
+
+    def record(self, off: int, r: int) -> np.ndarray:
+        """The r bytes at byte `off` of the buffer (host copy)."""
+        if off + r <= NEAR_BYTES:
+            return self.near[off: off + r]
+        assert off >= FAR_LO and off + r <= BUF_BYTES
+        return self.far[off - FAR_LO: off - FAR_LO + r]
+
+    def records(self, offs, r: int) -> np.ndarray:
+        """(V, r) records at the byte offsets; every far record differs from what its offset cut to 32 bits would read."""
+        for o in offs:
+            if o >= 1 << 32:
+                assert not np.array_equal(self.record(o, r), self.record(o - (1 << 32), r))
+        return np.stack([self.record(int(o), r) for o in offs])
+
+
+@pytest.fixture(scope="module")
+def far():
+    need_gib(BUF_BYTES / GIB + 1)   # 5 GiB
+    fb = FarBuffer()
+    yield fb
+    del fb
+    torch.cuda.empty_cache()
+
+
+def sources(n: int):
+    """-> [(name, byte offsets of the rows, kwargs of a stride / gather call or None, record_off tensor or None)]: near and far rows mixed."""
+    r = MR.rsize(n)
+    out = []
+    vidx = [0, 1, 1, 0, 1]
+    out.append(("idx x FAR", [3 + i * FAR for i in vidx], dict(record_stride=FAR, records_offset=3, variant_idx=vidx), None))
+    stride = r + 5
+    q = -(-FAR // stride)
+    vidx = [q + 1, 0, q, 1, q + 3, q + 2]
+    offs = [3 + i * stride for i in vidx]
+    assert max(offs) + r <= BUF_BYTES and min(o for o in offs if o > NEAR_BYTES) >= FAR
+    out.append(("far idx x stride", offs, dict(record_stride=stride, records_offset=3, variant_idx=vidx), None))
+    offs = [FAR + 7, 3, FAR + 9 + r, 4 + r, FAR + 6 + 3 * r]
+    out.append(("record_off", offs, None, offs))
+    return out
+
+
+def tensors(kw, offs_at):
+    if kw is not None:
+        kw = dict(kw, variant_idx=torch.tensor(kw["variant_idx"], dtype=torch.int64, device=DEV).to(torch.int32))
+    at = None if offs_at is None else torch.tensor(offs_at, dtype=torch.int64, device=DEV)
+    return kw, at
+
+
+def framed(nbytes: int, align: int = 1):
+    return LR.framed(nbytes, DEV, align)
+
+
+def payload(buf, front, nbytes, what) -> np.ndarray:
+    h = buf.cpu().numpy()
+    assert (h[:front] == SENT).all() and (h[front + nbytes:] == SENT).all(), f"{what}: bytes outside the output were written"
+    return h[front: front + nbytes]
+
+
+def first_diff(got: np.ndarray, want: np.ndarray, what: str):
+    if got.shape == want.shape and (got == want).all():
+        return
+    assert got.shape == want.shape, f"{what}: {got.shape} != {want.shape}"
+    bad = np.flatnonzero(got.reshape(-1) != want.reshape(-1))
+    raise AssertionError(f"{what}: {bad.size} of {want.size} bytes differ, first at byte {int(bad[0])}: got {int(got.reshape(-1)[bad[0]])}, "
+                         f"want {int(want.reshape(-1)[bad[0]])}")
+
+
+# (N, kept samples or None, the kernels the shape must reach: capi.hip's `choose`, tests/subset_plan.py `accepts`)
+EMIT_SHAPES = [(40, None, ("rows", "flat")), (300, None, ("pick", "flat", "rows")), (300, 30, ("pick", "rows")),
+               (2504, None, ("wide", "pick", "rows")), (2504, 1252, ("pick", "scan", "rows")), (20_000, 2000, ("scan", "rowpick", "rows"))]
+
+
+def kept_for(n: int, k):
+    return None if k is None else np.sort(np.random.default_rng(n + k).choice(n, size=k, replace=False)).astype(np.uint32)
+
+
+@pytest.mark.parametrize("n,k,must", EMIT_SHAPES, ids=[f"N{n}-{'all' if k is None else k}" for n, k, _ in EMIT_SHAPES])
+def test_emit_far_records(far, n, k, must):
+    """pgenhip_decode_emit, pgenhip_decode_emit_at and pgenhip_emit_lines (10-byte prefixes), AUTO and every forced kernel id that takes the
+    shape with gathered rows.  Needs 5 GiB (the shared buffer)."""
+    kept = kept_for(n, k)
+    kk = n if kept is None else k
+    r, row = MR.rsize(n), 4 * kk + 1
+    rng = np.random.default_rng(n)
+    with pgen_rs_amd.GtEngine(n, kept_idx=kept, device=0) as eng:
+        for mode in ("segments", "lines"):
+            ids = [(name, kid) for name, kid in SP.KERNEL_IDS.items()
+                   if SP.accepts(kid, n, kk, kept is not None, bound=10, gather=True, mode=mode)]
+            names = {name for name, _ in ids}
+            assert "auto" in names and set(must) - {"flat"} <= names and (mode == "lines" or set(must) <= names), (mode, names)
+            for sname, offs, kw, offs_at in sources(n):
+                if mode == "lines" and kw is None:
+                    continue   # (pgenhip_emit_lines has no byte-offset form)
+                v = len(offs)
+                recs = far.records(offs, r)
+                want_gt = oracle.decode_emit(recs.reshape(-1), v, n, kept_idx=kept).reshape(v, row)
+                kw_t, at_t = tensors(kw, offs_at)
+                if mode == "lines":
+                    blob = rng.integers(33, 127, size=10 * v, dtype=np.uint8)
+                    poff = np.arange(v + 1, dtype=np.int64) * 10
+                    loff = np.arange(v + 1, dtype=np.int64) * (10 + row)
+                    want = np.concatenate([blob.reshape(v, 10), want_gt], axis=1).reshape(-1)
+                    d_blob, d_poff, d_loff = (torch.from_numpy(x).to(DEV) for x in (blob, poff, loff))
+                else:
+                    want = want_gt.reshape(-1)
+                for name, kid in ids:
+                    buf, front = framed(want.size)
+                    if mode == "lines":
+                        eng.emit_lines(far.dev, v, d_blob, d_poff, d_loff, 10, buf[front:], record_stride=kw_t["record_stride"],
+                                       variant_idx=kw_t["variant_idx"], kernel=kid, records_offset=kw_t["records_offset"])
+                    elif at_t is None:
+                        eng.decode_emit(far.dev, v, out=buf, out_offset=front, kernel=kid, **kw_t)
+                    else:
+                        eng.decode_emit_at(far.dev, at_t, v, out=buf[front:], kernel=kid)
+                    eng.wait()
+                    what = f"N={n} K={kk} {mode} {sname} kernel {name}"
+                    first_diff(payload(buf, front, want.size, what), want, what)
+
+
+COUNT_SHAPES = [(40, None), (300, 30), (2504, None), (2504, 1252), (20_000, 2000)]
+
+
+@pytest.mark.parametrize("n,k", COUNT_SHAPES, ids=[f"N{n}-{'all' if k is None else k}" for n, k in COUNT_SHAPES])
+def test_sample_counts_far_records(far, n, k):
+    """pgenhip_sample_counts and pgenhip_sample_counts_at: AUTO and ROWS, with and without ACCUMULATE (onto 0xFFFFFFF0).  Needs 5 GiB."""
+    kept = kept_for(n, k)
+    kk = n if kept is None else k
+    r = MR.rsize(n)
+    prefill = 0xFFFFFFF0
+    with pgen_rs_amd.GtEngine(n, kept_idx=kept, device=0) as eng:
+        for sname, offs, kw, offs_at in sources(n):
+            codes = MR.codes(far.records(offs, r), n, kept)
+            counts = np.stack([(codes == c).sum(axis=0) for c in range(4)], axis=1).astype(np.int64)
+            kw_t, at_t = tensors(kw, offs_at)
+            for kern in (_capi.SCOUNT_AUTO, _capi.SCOUNT_ROWS):
+                for accumulate in (False, True):
+                    buf, front = framed(16 * kk, align=4)
+                    out = buf[front: front + 16 * kk].view(torch.int32)
+                    if accumulate:
+                        out.fill_(prefill - (1 << 32))
+                    if at_t is None:
+                        eng.sample_counts(far.dev, out=out, n_variants=len(offs), kernel=kern, accumulate=accumulate, **kw_t)
+                    else:
+                        eng.sample_counts_at(far.dev, at_t, len(offs), out=out, kernel=kern, accumulate=accumulate)
+                    eng.wait()
+                    what = f"N={n} K={kk} {sname} kernel {kern} accumulate={accumulate}"
+                    got = payload(buf, front, 16 * kk, what).view(np.uint32).astype(np.int64).reshape(kk, 4)
+                    want = (counts + (prefill if accumulate else 0)) & 0xFFFFFFFF
+                    assert (got == want).all(), f"{what}: first differing rank {int(np.flatnonzero((got != want).any(axis=1))[0])}"
+
+
+PAD = 0x5A   # fills the matrix rows and their padding before the call
+MATRIX_SHAPES = [(40, None), (300, 30), (2504, None), (20_000, 2000)]
+
+
+@pytest.mark.parametrize("dtype", [torch.int8, torch.float32], ids=["int8", "f32"])
+@pytest.mark.parametrize("n,k", MATRIX_SHAPES, ids=[f"N{n}-{'all' if k is None else k}" for n, k in MATRIX_SHAPES])
+def test_decode_matrix_far_records(far, n, k, dtype):
+    """pgenhip_decode_matrix and pgenhip_decode_matrix_at: GENERAL in both orientations, STREAM and TILE (all samples kept), AUTO; int8 and
+    f32, compared as bytes.  Needs 5 GiB."""
+    kept = kept_for(n, k)
+    r = MR.rsize(n)
+    np_dtype = np.int8 if dtype == torch.int8 else np.float32
+    vals = MR.default_values(np_dtype)
+    shapes = [(_capi.MATRIX_GENERAL, False), (_capi.MATRIX_GENERAL, True), (_capi.MATRIX_AUTO, False), (_capi.MATRIX_AUTO, True)]
+    if kept is None:
+        shapes += [(_capi.MATRIX_STREAM, False), (_capi.MATRIX_TILE, True)]
+    with pgen_rs_amd.GtEngine(n, kept_idx=kept, device=0) as eng:
+        for sname, offs, kw, offs_at in sources(n):
+            recs = far.records(offs, r)
+            kw_t, at_t = tensors(kw, offs_at)
+            for shape, sample_major in shapes:
+                want = MR.raw(MR.matrix(recs, n, kept, vals, sample_major))
+                # the output: a framed buffer, rows at a pitch of 16 bytes more than they hold, rounded up to 16 (what TILE needs)
+                rows, row_bytes = want.shape
+                eb = vals.itemsize
+                pitch = -(-(row_bytes + 16) // 16) * 16
+                buf, front = framed(rows * pitch, align=16)
+                buf[front: front + rows * pitch] = PAD
+                out = buf[front: front + rows * pitch].view(dtype).view(rows, pitch // eb)[:, : row_bytes // eb]
+                if at_t is None:
+                    eng.decode_matrix(far.dev, len(offs), sample_major=sample_major, kernel=shape, out=out, **kw_t)
+                else:
+                    eng.decode_matrix_at(far.dev, at_t, len(offs), sample_major=sample_major, kernel=shape, out=out)
+                eng.wait()
+                what = f"N={n} {'all' if k is None else k} {sname} shape {shape} sample_major={sample_major} {np_dtype.__name__}"
+                h = payload(buf, front, rows * pitch, what).reshape(rows, pitch)
+                assert (h[:, row_bytes:] == PAD).all(), f"{what}: row padding was written"
+                got = h[:, :row_bytes]
+                first_diff(got, want, what)
+
+
+# ---- dense records that cross 2^32 themselves ---------------------------------------------------------------------------------------
+DENSE = [("runs", 1900, 9_100_000, _capi.KERNEL_RUNS, False), ("pick-packed", 2504, 6_900_000, _capi.KERNEL_PICK, False),
+         ("line-runs", 900, 19_200_000, _capi.KERNEL_RUNS, True)]
+
+
+@pytest.mark.parametrize("name,n,v,kernel,lines", DENSE, ids=[d[0] for d in DENSE])
+def test_dense_records_past_4_gib(name, n, v, kernel, lines):
+    """RUNS (N = 1 900), the pick family's packed path (N = 2 504, all samples) and the line-run kernel (N = 900, 12-byte prefixes)
+    on 4.32 GB of dense records: V x R > 2^32, about 70 GB of text.  Needs 80 GiB."""
+    need_gib(80)
+    r = MR.rsize(n)
+    plen = 12 if lines else 0
+    row = plen + 4 * n + 1
+    total = v * row
+    assert v * r > (1 << 32) + (1 << 24) and total < 75 * 10**9
+    assert SP.accepts(kernel, n, n, False, bound=plen, gather=False, mode="lines" if lines else "segments")
+    rng = np.random.default_rng(n)
+    with pgen_rs_amd.GtEngine(n, device=0) as eng:
+        recs = eng.synth_records(v, dirty_pad=True)
+        out = torch.full((total + BACK,), SENT, dtype=torch.uint8, device=DEV)
+        if lines:
+            g = torch.Generator(device=DEV)
+            g.manual_seed(n)
+            blob = torch.randint(33, 127, (plen * v,), dtype=torch.uint8, device=DEV, generator=g)
+            poff = torch.arange(v + 1, dtype=torch.int64, device=DEV) * plen
+            loff = torch.arange(v + 1, dtype=torch.int64, device=DEV) * row
+            eng.emit_lines(recs, v, blob, poff, loff, plen, out, kernel=kernel)
+        else:
+            eng.decode_emit(recs, v, out=out, kernel=kernel)
+        eng.wait()
+        assert bool((out[total:] == SENT).all()), "bytes behind the last row were written"
+        rows2d = out[:total].view(v, row)
+        assert bool((rows2d[:, row - 1] == 10).all()), "a row does not end in LF"
+        j_4g = (1 << 32) // r
+        starts = [0, j_4g - 50, v - 100] + [int(q) for q in rng.integers(0, v - 100, size=6)]
+        for j0 in starts:
+            j1 = j0 + 100
+            h_recs = recs[j0 * r: j1 * r].cpu().numpy()
+            want = oracle.decode_emit(h_recs, 100, n).reshape(100, 4 * n + 1)
+            got = rows2d[j0:j1].cpu().numpy()
+            if lines:
+                first_diff(got[:, :plen], blob[j0 * plen: j1 * plen].cpu().numpy().reshape(100, plen), f"{name}: prefixes of rows {j0}..{j1}")
+            first_diff(got[:, plen:], want, f"{name}: rows {j0}..{j1} (records at bytes {j0 * r:#x}..)")
+        del out, rows2d, recs
+    torch.cuda.empty_cache()
