@@ -293,6 +293,39 @@ int pgenhip_decode_matrix(pgenhip_ctx *ctx, const void *d_records, uint64_t reco
 int pgenhip_decode_matrix_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
                              void *d_out, uint64_t out_stride, uint32_t elem_bytes, const void *code_values, uint32_t flags);
 
+/* ---- windowed pairwise genotype tables / r^2 (device-resident, asynchronous on the ctx stream) ----
+ * How two variants go together: for every pair of selected rows (i, i + d) with 0 <= i < n_left, 1 <= d <= window and
+ * i + d < n_variants, the joint table of the two rows' codes over the ctx's kept samples, or the r^2 of that table.
+ * Rows are selected exactly as in pgenhip_genotype_counts / pgenhip_genotype_counts_at: by stride (record_stride >= R, or
+ * n_variants <= 1), through d_variant_idx, or through d_record_off; records may start at any byte alignment.  Samples >= N and the
+ * pad bits of a record's last byte are never counted.  n_variants is the number of selected rows, n_left <= n_variants how many
+ * leading rows own pairs (a host that streams blocks overlapping by `window` rows passes the block's own rows as n_left and computes
+ * no pair twice), window = W >= 1.  The pair (i, i + d) has pair index p = i * W + (d - 1).
+ *   - PGENHIP_PAIR_TABLE: sixteen u32 at d_out[16*p + 4*a + b], the number of kept samples with code a in row i and code b in row
+ *     i + d (0 hom-ref, 1 het, 2 hom-alt, 3 missing: the order of the count entry points).  The sums over b are
+ *     pgenhip_genotype_counts of row i, the sums over a those of row i + d, the whole table sums to K.  d_out must be 16-byte
+ *     aligned (an entry is four 16-byte stores), else PGENHIP_ERR_BAD_ARG.
+ *   - PGENHIP_PAIR_R2: one f32 at d_out[p], from the same table's cells with a, b in {0, 1, 2} (samples called in both rows):
+ *     n = their sum, Sx = sum a*T, Sy = sum b*T, Sxx = sum a^2*T, Syy = sum b^2*T, Sxy = sum a*b*T and
+ *     r^2 = (n*Sxy - Sx*Sy)^2 / ((n*Sxx - Sx^2) * (n*Syy - Sy^2)).  The three bracketed terms are exact 64-bit integers; each is
+ *     converted to double, they are combined in double and the result is rounded once to f32.  A zero denominator (n == 0, or a
+ *     row that is monomorphic among the jointly called samples) gives NaN.  This is the unphased genotype correlation; no byte or
+ *     digit parity with another tool's r^2 is claimed.  d_out must be 4-byte aligned, else PGENHIP_ERR_BAD_ARG.
+ *   - Entries with i + d >= n_variants are NOT touched, nor is anything outside the n_left * W entries: a fresh buffer keeps what
+ *     it held there.  A gather that repeats a row pairs it with itself (a diagonal table).  K == 0 is valid: tables are all zero,
+ *     r^2 is NaN.  n_left == 0 or n_variants <= 1 is a no-op.
+ *   - PGENHIP_ERR_BAD_ARG: window == 0, n_left > n_variants, an unknown flag, and — when at least one pair exists — a NULL or
+ *     misaligned d_out.  PGENHIP_ERR_TOO_LARGE before any launch when n_left * window * 64 >= 2^52.
+ * Same launch contract as pgenhip_genotype_counts: device pointers only, no allocation, no synchronisation, queued on the ctx
+ * stream, graph-capturable.  One pair's samples are not split over blocks: a call with few rows of very long records uses few CUs. */
+#define PGENHIP_PAIR_TABLE 0u   /* 16 u32 per pair */
+#define PGENHIP_PAIR_R2    1u   /* one f32 per pair */
+int pgenhip_pair_stats(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                       uint32_t n_variants, uint32_t n_left, uint32_t window, void *d_out, uint32_t flags);
+/* Same, with the record of row j at d_base + d_record_off[j] (DEVICE array of u64 byte offsets). */
+int pgenhip_pair_stats_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
+                          uint32_t n_left, uint32_t window, void *d_out, uint32_t flags);
+
 /* Launch-shape knobs of one ctx (tests force small grids to exercise ring re-use; A/B probes).
  * value 0 restores the built-in default of a knob unless noted. */
 typedef enum pgenhip_knob {
@@ -312,7 +345,8 @@ typedef enum pgenhip_knob {
     PGENHIP_KNOB_ALIGN_STORES = 16,      /* subset kernels (segment, row-owner, pick): 1 (default) lanes <-> chunks shifted so that every store instruction covers whole 128-byte lines, -1 from the run's first whole chunk */
     PGENHIP_KNOB_SCOUNT_SLICES = 17,     /* per-sample counts: row ranges per column tile, each summed by one block (default 0 = as many as fill the chip's resident blocks) */
     PGENHIP_KNOB_MATRIX_BLOCKS = 18,     /* genotype matrix kernels: grid size in blocks (default 0 = by shape: the work, capped at 8 blocks per CU, 4 for TILE); tests force small grids */
-    PGENHIP_KNOB_RUNS_ROWS = 7           /* RUNS kernel: rows per work item (default: as many as one wide load / one span holds) */
+    PGENHIP_KNOB_PAIR_BLOCKS = 19,       /* pairwise kernel: grid size in blocks (default 0 = by shape: the tiles, capped at 16 one-wave blocks per CU); tests force small grids */
+    PGENHIP_KNOB_RUNS_ROWS = 7          /* RUNS kernel: rows per work item (default: as many as one wide load / one span holds) */
 } pgenhip_knob;
 int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value);
 

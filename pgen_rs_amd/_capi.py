@@ -54,6 +54,8 @@ MATRIX_STREAM = 2
 MATRIX_TILE = 3
 MATRIX_SHAPE_MASK = 0xF
 MATRIX_SAMPLE_MAJOR = 0x10
+PAIR_TABLE = 0
+PAIR_R2 = 1
 SYNTH_DIRTY_PAD = 1
 SYNTH_HWE = 2
 CREATE_KEEP_LIST = 1
@@ -73,6 +75,7 @@ KNOB_SCAN_ROWPICK = 12
 KNOB_ALIGN_STORES = 16
 KNOB_SCOUNT_SLICES = 17
 KNOB_MATRIX_BLOCKS = 18
+KNOB_PAIR_BLOCKS = 19
 
 
 
@@ -118,6 +121,8 @@ PROTOTYPES = {
     "pgenhip_sample_counts_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_decode_matrix": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_decode_matrix_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
+    "pgenhip_pair_stats": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
+    "pgenhip_pair_stats_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_tune": (C.c_int, [ctx_p, C.c_uint32, C.c_int32]),
     "pgenhip_wait": (C.c_int, [ctx_p]),
     "pgenhip_timer_start": (C.c_int, [ctx_p]),

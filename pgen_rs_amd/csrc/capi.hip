@@ -724,6 +724,48 @@ int pgenhip_decode_matrix_at(pgenhip_ctx *ctx, const void *d_base, const uint64_
     return decode_matrix_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, d_out, out_stride, elem_bytes, code_values, flags);
 }
 
+static int pair_stats_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                           const uint64_t *d_record_off, uint32_t n_variants, uint32_t n_left, uint32_t window, void *d_out, uint32_t flags)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (flags > PGENHIP_PAIR_R2) return fail(PGENHIP_ERR_BAD_ARG, "unknown pair_stats flag");
+    if (window == 0u) return fail(PGENHIP_ERR_BAD_ARG, "window is 0");
+    if (n_left > n_variants) return fail(PGENHIP_ERR_BAD_ARG, "n_left > n_variants");
+    if (n_left == 0u || n_variants <= 1u) return PGENHIP_OK;   // no pair exists
+    if (!d_out) return fail(PGENHIP_ERR_BAD_ARG, "d_out is NULL");
+    const bool r2 = flags == PGENHIP_PAIR_R2;
+    if ((uintptr_t)d_out & (r2 ? 3u : 15u))
+        return fail(PGENHIP_ERR_BAD_ARG, r2 ? "d_out is not 4-byte aligned" : "d_out is not 16-byte aligned (PGENHIP_PAIR_TABLE)");
+    // the kernel forms byte offsets of pair entries in 64 bits; the bound is the other kernels' (2^52 bytes), taken on the
+    // table entry's 64 bytes whichever the mode
+    if ((uint64_t)n_left * window >= (1ull << 52) / 64u) return fail(PGENHIP_ERR_TOO_LARGE, "n_left * window * 64 >= 2^52");
+    PairArgs a;
+    rc = select_rows(ctx, a, d_records, record_stride, d_variant_idx, d_record_off, n_variants);
+    if (rc) return rc;
+    a.kept_count = ctx->kept_count;
+    a.kept_mask = ctx->d_count_mask;   // NULL with all samples kept or an identity list
+    a.n_left = n_left;
+    a.window = window;
+    a.out = d_out;
+    a.r2 = r2 ? 1u : 0u;
+    HIP_TRY(launch_gt_pair(a, ctx->tune.pair_blocks, ctx->num_cus, ctx->stream));
+    return PGENHIP_OK;
+}
+
+int pgenhip_pair_stats(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                       uint32_t n_variants, uint32_t n_left, uint32_t window, void *d_out, uint32_t flags)
+{
+    return pair_stats_core(ctx, d_records, record_stride, d_variant_idx, nullptr, n_variants, n_left, window, d_out, flags);
+}
+
+int pgenhip_pair_stats_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
+                          uint32_t n_left, uint32_t window, void *d_out, uint32_t flags)
+{
+    if (const int rc = check_record_off(ctx, d_record_off, n_variants)) return rc;
+    return pair_stats_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, n_left, window, d_out, flags);
+}
+
 int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)
 {
     if (!ctx) return fail(PGENHIP_ERR_BAD_ARG, "ctx is NULL");
@@ -747,6 +789,7 @@ int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)
         case PGENHIP_KNOB_RUNS_ROWS: t.runs_rows = value > 0 ? value : d.runs_rows; break;
         case PGENHIP_KNOB_SCOUNT_SLICES: t.scount_slices = value > 0 ? value : d.scount_slices; break;
         case PGENHIP_KNOB_MATRIX_BLOCKS: t.matrix_blocks = value > 0 ? value : d.matrix_blocks; break;
+        case PGENHIP_KNOB_PAIR_BLOCKS: t.pair_blocks = value > 0 ? value : d.pair_blocks; break;
         default: return fail(PGENHIP_ERR_BAD_ARG, "unknown knob");
     }
     return PGENHIP_OK;

@@ -54,6 +54,7 @@ struct Tuning {
     int runs_rows = 0;             // RUNS mode of the stream kernel: rows per work item (0 = as many as one wide load / one span holds)
     int scount_slices = 0;         // per-sample counts: row ranges per column tile (0 = as many as fill the chip's resident blocks)
     int matrix_blocks = 0;         // genotype matrix kernels: grid size in blocks (0 = by shape, capped per CU)
+    int pair_blocks = 0;           // pairwise kernel: grid size in blocks (0 = by shape, capped per CU)
 };
 
 // rows are gathered (variant list or byte offsets): the HAS_VIDX instantiations
@@ -148,6 +149,19 @@ bool gt_matrix_tile_applicable(const MatrixArgs &a);     // sample-major, all sa
 hipError_t launch_gt_matrix_general(const MatrixArgs &a, int blocks, int num_cus, hipStream_t stream);
 hipError_t launch_gt_matrix_stream(const MatrixArgs &a, int blocks, int num_cus, hipStream_t stream);
 hipError_t launch_gt_matrix_tile(const MatrixArgs &a, int blocks, int num_cus, hipStream_t stream);
+
+// Windowed pairwise tables (gt_pair.hip): pair (i, i + d), i < n_left, 1 <= d <= window, i + d < n_variants, at pair index
+// p = i * window + d - 1: sixteen u32 at out + 64 p (T[a][b] at word 4 a + b), or with r2 one float at out + 4 p.
+struct PairArgs : RowSource {
+    uint32_t kept_count;          // K (== N without a mask)
+    const uint8_t *kept_mask;     // device or nullptr (all samples): the ctx's count mask (CountArgs::kept_mask)
+    uint32_t n_left;              // <= n_variants
+    uint32_t window;              // W >= 1
+    void *out;                    // device; 16-byte aligned for tables, 4-byte aligned for r2
+    uint32_t r2;                  // 0: tables; 1: r^2
+};
+// blocks: forced grid size (0 = by shape; tests force small grids to walk the grid-stride loop)
+hipError_t launch_gt_pair(const PairArgs &a, int blocks, int num_cus, hipStream_t stream);
 
 // Deterministic synthetic records (SURVEY.md §8d counter-based generator).
 hipError_t launch_synth_records(uint8_t *dst, uint64_t record_stride, uint32_t sample_count,

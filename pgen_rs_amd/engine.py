@@ -422,6 +422,71 @@ class GtEngine:
                                            out.element_size(), tab.ctypes.data_as(C.c_void_p), flags), "pgenhip_decode_matrix_at")
         return res
 
+    # -- windowed pairwise tables / r^2 ---------------------------------------------------------
+    def pair_tables(self, records: torch.Tensor, record_stride: Optional[int] = None, variant_idx: Optional[torch.Tensor] = None,
+                    n_variants: Optional[int] = None, *, n_left: Optional[int] = None, window: int,
+                    out: Optional[torch.Tensor] = None, records_offset: int = 0) -> torch.Tensor:
+        """Joint genotype tables of the row pairs inside a sliding window: an int32 ``(n_left, W, 4, 4)`` CUDA tensor whose entry
+        ``[i, d - 1, a, b]`` is the u32 number of kept samples with code ``a`` in row i and code ``b`` in row i + d (codes 0-3:
+        hom-ref, het, hom-alt, missing), for ``1 <= d <= W`` and ``i + d < n_variants``.
+
+        Rows are selected as in ``genotype_counts``.  ``n_left`` (default: all rows) is how many leading rows own pairs, so blocks
+        that overlap by ``window`` rows compute no pair twice.  Entries with ``i + d >= n_variants`` are NOT written by the
+        library: they keep what the buffer held.  Without ``out`` the result is allocated with zeros, so that ragged end reads as
+        empty tables; a caller-supplied ``out`` (int32, >= 16 * n_left * W entries, 16-byte aligned) is used as given."""
+        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
+        n_left, out = self._pair_out(out, n_variants, n_left, window, torch.int32, 16)
+        check(lib.pgenhip_pair_stats(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants, n_left,
+                                     window, _ptr(out), _capi.PAIR_TABLE), "pgenhip_pair_stats")
+        return out[: 16 * n_left * window].view(n_left, window, 4, 4)
+
+    def pair_tables_at(self, base: torch.Tensor, record_off: torch.Tensor, n_variants: Optional[int] = None, *,
+                       n_left: Optional[int] = None, window: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``pair_tables`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
+        n_variants = self._rows_at(base, record_off, n_variants)
+        n_left, out = self._pair_out(out, n_variants, n_left, window, torch.int32, 16)
+        check(lib.pgenhip_pair_stats_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, n_left, window, _ptr(out),
+                                        _capi.PAIR_TABLE), "pgenhip_pair_stats_at")
+        return out[: 16 * n_left * window].view(n_left, window, 4, 4)
+
+    def pair_r2(self, records: torch.Tensor, record_stride: Optional[int] = None, variant_idx: Optional[torch.Tensor] = None,
+                n_variants: Optional[int] = None, *, n_left: Optional[int] = None, window: int,
+                out: Optional[torch.Tensor] = None, records_offset: int = 0) -> torch.Tensor:
+        """Unphased genotype r^2 of the same pairs: a float32 ``(n_left, W)`` CUDA tensor, entry ``[i, d - 1]`` for rows i and
+        i + d, computed from the pair's table over the samples called in both rows; NaN where a row is monomorphic among them (or
+        none is).  Entries with ``i + d >= n_variants`` are not written: NaN in a result allocated here, untouched in ``out``
+        (float32, >= n_left * W entries)."""
+        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
+        n_left, out = self._pair_out(out, n_variants, n_left, window, torch.float32, 1)
+        check(lib.pgenhip_pair_stats(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants, n_left,
+                                     window, _ptr(out), _capi.PAIR_R2), "pgenhip_pair_stats")
+        return out[: n_left * window].view(n_left, window)
+
+    def pair_r2_at(self, base: torch.Tensor, record_off: torch.Tensor, n_variants: Optional[int] = None, *,
+                   n_left: Optional[int] = None, window: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``pair_r2`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
+        n_variants = self._rows_at(base, record_off, n_variants)
+        n_left, out = self._pair_out(out, n_variants, n_left, window, torch.float32, 1)
+        check(lib.pgenhip_pair_stats_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, n_left, window, _ptr(out),
+                                        _capi.PAIR_R2), "pgenhip_pair_stats_at")
+        return out[: n_left * window].view(n_left, window)
+
+    def _pair_out(self, out: Optional[torch.Tensor], n_variants: int, n_left: Optional[int], window: int, dtype: torch.dtype,
+                  per_pair: int):
+        """(n_left with its default, the flat output: given, or zeros for tables / NaN for r^2)"""
+        if n_left is None:
+            n_left = n_variants
+        if window < 1 or not 0 <= n_left <= n_variants:
+            raise ValueError("need window >= 1 and 0 <= n_left <= n_variants")
+        need = per_pair * n_left * window
+        if out is None:
+            fill = 0 if dtype == torch.int32 else float("nan")
+            return n_left, torch.full((max(need, 4),), fill, dtype=dtype, device=self.torch_device)
+        self._check_dev(out, "out")
+        if out.dtype != dtype or out.numel() < need:
+            raise ValueError(f"out must be a {dtype} tensor with >= {need} entries")
+        return n_left, out.view(-1)
+
     _MATRIX_DTYPES = {torch.int8: np.int8, torch.uint8: np.uint8, torch.int16: np.int16, torch.int32: np.int32,
                       torch.float16: np.float16, torch.bfloat16: None, torch.float32: np.float32}
 

@@ -81,6 +81,7 @@ const char *kUsage =
     "  freq    Per-variant genotype counts of the kept samples, outputting to stdout\n"
     "  sample-counts  Per-sample genotype counts over the kept variants, outputting to stdout\n"
     "  matrix  Numeric genotype matrix of the kept variants and samples, outputting to a NumPy .npy file\n"
+    "  ld      Pairwise r^2 of the kept variants inside a sliding window, outputting to stdout\n"
     "  help    Print this message\n\n"
     "query  <PFILE_PREFIX> -f, --fstring <QUERY_FSTRING> [-i, --include <QUERY>] [-s, --samples]\n"
     "filter <PFILE_PREFIX> [--include-var <VAR_QUERY>] [--include-sam <SAM_QUERY>] [-o, --out <OUT_FILE>]\n"
@@ -99,6 +100,12 @@ const char *kUsage =
     "       NumPy .npy (version 1.0, C order) of shape (variants kept, samples kept), or (samples, variants) with --sample-major:\n"
     "       0 / 1 / 2 alternate alleles, --missing (default -1 for i8, nan for f16 / f32) for ./.; the kept variants' ID column in\n"
     "       OUT_FILE.npy.variants and the kept samples' IID column in OUT_FILE.npy.samples, one per line\n"
+    "ld     <PFILE_PREFIX> --window <W> [--min-r2 <X>] [--counts] [--include-var <VAR_QUERY>] [--include-sam <SAM_QUERY>] [-o, --out <OUT_FILE>]\n"
+    "       [--gpus <N>] [--shards <S>] [--block-mib <M>] [--block-rows <B>] [--read-threads <T>] [--filter-threads <T>] [--stats]\n"
+    "       one line per pair of kept variants on one chromosome at most W kept variants apart with r^2 >= X (default 0.2; NaN pairs\n"
+    "       are dropped): CHROM_A POS_A ID_A CHROM_B POS_B ID_B R2, ordered by first variant and distance; --counts appends N_OBS\n"
+    "       and the pair's 4 x 4 genotype table T00 .. T33.  r^2 is the unphased genotype correlation over the kept samples called\n"
+    "       in both variants; no digit parity with plink2 is claimed\n"
     "bgzf   <IN_FILE> <OUT_FILE> [--level <1-9>] [--threads <T>] [--chunk-mib <M>]\n";
 
 [[noreturn]] void usage_error(const std::string &msg)
@@ -392,6 +399,42 @@ int main(int argc, char **argv)
             const MatrixOptions m = matrix_options(a);
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
             const OutputStats st = pfile.output_matrix(a.get("include-sam"), a.get("include-var"), *a.get("out"), m, output_options(a));
+            if (a.has("stats")) print_stats(st, t_main);
+            return 0;
+        }
+        if (cmd == "ld") {
+            Args a = parse(argc, argv, 2, {{"window", 0}, {"min-r2", 0}, {"include-var", 0}, {"include-sam", 0}, {"out", 'o'}, {"gpus", 0}, {"shards", 0}, {"block-mib", 0}, {"block-rows", 0}, {"read-threads", 0}, {"filter-threads", 0}},
+                           {{"stats", 0}, {"counts", 0}});
+            if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
+            if (!a.has("window")) usage_error("the following required arguments were not provided: --window <W>");
+            LdOptions ld;
+            {
+                const std::string w = *a.get("window");
+                char *end = nullptr;
+                errno = 0;
+                const unsigned long long v = std::strtoull(w.c_str(), &end, 10);
+                if (w.empty() || w[0] == '-' || *end != '\0' || errno != 0 || v < 1 || v > 0xFFFFFFFFull)
+                    usage_error("invalid value '" + w + "' for '--window <W>': a number of variants from 1 to 4294967295");
+                ld.window = (uint32_t)v;
+            }
+            if (auto m = a.get("min-r2")) {
+                char *end = nullptr;
+                errno = 0;
+                ld.min_r2 = std::strtod(m->c_str(), &end);
+                if (m->empty() || *end != '\0' || errno != 0 || !(ld.min_r2 >= 0.0 && ld.min_r2 <= 1.0))
+                    usage_error("invalid value '" + *m + "' for '--min-r2 <X>': a number from 0 to 1");
+            }
+            if (auto b = a.get("block-rows")) {
+                char *end = nullptr;
+                errno = 0;
+                const unsigned long long v = std::strtoull(b->c_str(), &end, 10);
+                if (b->empty() || (*b)[0] == '-' || *end != '\0' || errno != 0 || v < 1)
+                    usage_error("invalid value '" + *b + "' for '--block-rows <B>': a number of variants from 1");
+                ld.block_rows = v;
+            }
+            ld.counts = a.has("counts");
+            const Pfile pfile = Pfile::from_prefix(a.positional[0]);
+            const OutputStats st = pfile.output_ld(a.get("include-sam"), a.get("include-var"), a.get("out").value_or(""), ld, output_options(a));
             if (a.has("stats")) print_stats(st, t_main);
             return 0;
         }

@@ -7,12 +7,14 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <condition_variable>
 #include <deque>
 #include <fstream>
+#include <map>
 #include <mutex>
 #include <sstream>
 #include <thread>
@@ -874,13 +876,16 @@ void append_u64(std::string &s, uint64_t v)
 // records are staged as they lie on disk (a span grows over gaps of up to R bytes, so a block stages at most 2R bytes per
 // variant) and counted through their offsets in the staged bytes (the `_at` entry points).
 // make(ctx, bv) builds a shard's counter, which provides
-//   launch(ctx, d_rec, d_off, nv): queue the block's count launch (d_off NULL: records packed at stride R);
+//   launch(ctx, d_rec, d_off, nv, nh): queue the block's count launch over its nv rows (and the nh halo rows staged behind them;
+//     d_off NULL: records packed at stride R);
 //   copy(ctx, nv): queue what goes back after it (outside the kernel timer);
 //   collect(b0, nv): the block's work on the stream has finished (b0: index of its first variant in `vars`);
 //   finish(ctx): after the shard's last block has been collected.
+// halo: rows behind a block's own that are staged with it (ld: a block's left rows and the `window` rows that follow them, which
+// may belong to the next block or shard); launch gets their number as its last argument.  0: a block is its own rows.
 template <class Make>
 void count_blocks(const Pfile &pf, const Pfile::IdxRecords &vars, const KeptSamples &kept, const OutputOptions &opt, const char *no_device,
-                  OutputStats &st, const Make &make)
+                  OutputStats &st, const Make &make, size_t halo = 0)
 {
     const uint32_t R = pf.variant_record_size();
     const Shards shards(opt, no_device);
@@ -891,15 +896,16 @@ void count_blocks(const Pfile &pf, const Pfile::IdxRecords &vars, const KeptSamp
         const double t_worker = now_s();
         const Fd pgen_fd(pgen, O_RDONLY);
         const uint64_t bv = std::max<uint64_t>(1, std::min<uint64_t>(opt.block_text_bytes / R, end - begin));
-        const size_t stage_bytes = (size_t)(bv * R) * (vw ? 2u : 1u);
+        const uint64_t bt = bv + halo;   // rows a block stages at most
+        const size_t stage_bytes = (size_t)(bt * R) * (vw ? 2u : 1u);
         DeviceCtx ctx(device, pf.num_samples, &kept);
         uint8_t *d_rec = ctx.device<uint8_t>(stage_bytes, "device records");
-        uint64_t *d_off = vw ? ctx.device<uint64_t>((size_t)(8 * bv), "device record offsets") : nullptr;
+        uint64_t *d_off = vw ? ctx.device<uint64_t>((size_t)(8 * bt), "device record offsets") : nullptr;
         uint8_t *h_rec[2] = {ctx.pinned<uint8_t>(stage_bytes, "pinned records"), ctx.pinned<uint8_t>(stage_bytes, "pinned records")};
         uint64_t *h_off[2] = {nullptr, nullptr};
         if (vw) {
-            h_off[0] = ctx.pinned<uint64_t>((size_t)(16 * bv), "pinned record offsets");
-            h_off[1] = h_off[0] + bv;
+            h_off[0] = ctx.pinned<uint64_t>((size_t)(16 * bt), "pinned record offsets");
+            h_off[1] = h_off[0] + bt;
         }
         auto counter = make(ctx, bv);
         setup_s[(size_t)g] = now_s() - t_worker;
@@ -915,15 +921,16 @@ void count_blocks(const Pfile &pf, const Pfile::IdxRecords &vars, const KeptSamp
         };
         for (size_t b0 = begin, k = 0; b0 < end; b0 += (size_t)bv, k++) {
             const size_t nv = std::min<size_t>((size_t)bv, end - b0);
+            const size_t nh = std::min<size_t>(halo, vars.size() - (b0 + nv)), nt = nv + nh;
             uint8_t *dst = h_rec[k % 2];
             size_t staged = 0;
-            for (size_t j = 0; j < nv;) {
+            for (size_t j = 0; j < nt;) {
                 const uint64_t off0 = pf.record_offset(vars[b0 + j].first);
                 size_t run = 1;
                 uint64_t span = R;   // bytes of the file from off0 this run covers
                 if (vw) {
                     h_off[k % 2][j] = staged;
-                    while (j + run < nv) {
+                    while (j + run < nt) {
                         const uint64_t off = pf.record_offset(vars[b0 + j + run].first);
                         if (off > off0 + span + R) break;
                         h_off[k % 2][j + run] = staged + (off - off0);
@@ -931,7 +938,7 @@ void count_blocks(const Pfile &pf, const Pfile::IdxRecords &vars, const KeptSamp
                         run++;
                     }
                 } else {
-                    while (j + run < nv && vars[b0 + j + run].first == vars[b0 + j].first + run) run++;
+                    while (j + run < nt && vars[b0 + j + run].first == vars[b0 + j].first + run) run++;
                     span = (uint64_t)run * R;
                 }
                 pread_span(pgen_fd.get(), dst + staged, (size_t)span, off0, pgen, opt.read_threads);
@@ -940,9 +947,9 @@ void count_blocks(const Pfile &pf, const Pfile::IdxRecords &vars, const KeptSamp
             }
             collect();   // block k - 1 has been counted and what it returns is back; its pinned records are free again
             check(pgenhip_memcpy_h2d(ctx.get(), d_rec, dst, staged), "H2D records");
-            if (vw) check(pgenhip_memcpy_h2d(ctx.get(), d_off, h_off[k % 2], nv * sizeof(uint64_t)), "H2D record offsets");
+            if (vw) check(pgenhip_memcpy_h2d(ctx.get(), d_off, h_off[k % 2], nt * sizeof(uint64_t)), "H2D record offsets");
             check(pgenhip_timer_start(ctx.get()), "timer");
-            counter.launch(ctx.get(), d_rec, d_off, (uint32_t)nv);
+            counter.launch(ctx.get(), d_rec, d_off, (uint32_t)nv, (uint32_t)nh);
             check(pgenhip_timer_mark(ctx.get()), "timer");
             counter.copy(ctx.get(), nv);
             prev_b0 = b0;
@@ -960,7 +967,7 @@ struct VariantCounter {
     uint32_t R;
     std::vector<uint32_t> &counts;   // 4 per kept variant
     uint32_t *d_counts, *h_counts;
-    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, uint32_t nv) const
+    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, uint32_t nv, uint32_t) const
     {
         if (d_off)
             check(pgenhip_genotype_counts_at(ctx, d_rec, d_off, nv, d_counts, PGENHIP_COUNT_AUTO), "pgenhip_genotype_counts_at");
@@ -981,7 +988,7 @@ struct SampleCounter {
     std::mutex &mu;
     uint32_t *d_counts, *h_counts;
     bool first = true;
-    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, uint32_t nv)
+    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, uint32_t nv, uint32_t)
     {
         const uint32_t flags = PGENHIP_SCOUNT_AUTO | (first ? 0u : PGENHIP_SCOUNT_ACCUMULATE);
         first = false;
@@ -1014,7 +1021,7 @@ struct MatrixWriter {
     int fd;
     const std::string &path;
     uint64_t data_off;
-    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, uint32_t nv) const
+    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, uint32_t nv, uint32_t) const
     {
         const uint32_t flags = PGENHIP_MATRIX_AUTO | (m.sample_major ? PGENHIP_MATRIX_SAMPLE_MAJOR : 0u);
         const uint64_t stride = m.sample_major ? pitch : (uint64_t)K * m.elem_bytes;
@@ -1035,6 +1042,93 @@ struct MatrixWriter {
         split_span(K, K >= 64 ? kMatrixWriteThreads : 1u, [&](size_t lo, size_t hi) {
             for (size_t k = lo; k < hi; k++) pwrite_exact(fd, h_out + k * pitch, nv * E, data_off + ((uint64_t)k * V + b0) * E, path);
         });
+    }
+    void finish(pgenhip_ctx *) const {}
+};
+
+// r^2 of a 4 x 4 table by the formula of pgenhip_pair_stats (include/pgen_hip.h): exact 64-bit terms, doubles, one rounding to float
+float table_r2(const uint32_t *t, uint64_t &n_obs)
+{
+    uint64_t n = 0, sx = 0, sy = 0, sxx = 0, syy = 0, sxy = 0;
+    for (uint64_t a = 0; a < 3; a++)
+        for (uint64_t b = 0; b < 3; b++) {
+            const uint64_t c = t[4 * a + b];
+            n += c;
+            sx += a * c;
+            sy += b * c;
+            sxx += a * a * c;
+            syy += b * b * c;
+            sxy += a * b * c;
+        }
+    n_obs = n;
+    const uint64_t p = n * sxy, q = sx * sy, cov = p >= q ? p - q : q - p;
+    const uint64_t vx = n * sxx - sx * sx, vy = n * syy - sy * sy;
+    if (vx == 0 || vy == 0) return std::nanf("");
+    const double c = (double)cov;
+    return (float)((c * c) / ((double)vx * (double)vy));
+}
+
+// ld's counter: a block's pair entries (r^2, or tables with --counts) come back and become the block's lines at once; the blocks'
+// texts are joined in variant order at the end, whichever shard made them
+struct PairWriter {
+    uint32_t R, W;
+    const LdOptions &ld;
+    const Pfile::IdxRecords &vars;
+    const size_t (&col)[3];   // CHROM, POS, ID
+    std::map<size_t, std::string> &pieces;
+    std::mutex &mu;
+    uint8_t *d_out, *h_out;
+    size_t entry_bytes() const { return ld.counts ? 64u : 4u; }
+    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, uint32_t nv, uint32_t nh) const
+    {
+        const uint32_t flags = ld.counts ? PGENHIP_PAIR_TABLE : PGENHIP_PAIR_R2;
+        if (d_off)
+            check(pgenhip_pair_stats_at(ctx, d_rec, d_off, nv + nh, nv, W, d_out, flags), "pgenhip_pair_stats_at");
+        else
+            check(pgenhip_pair_stats(ctx, d_rec, R, nullptr, nv + nh, nv, W, d_out, flags), "pgenhip_pair_stats");
+    }
+    void copy(pgenhip_ctx *ctx, size_t nv) const { check(pgenhip_memcpy_d2h(ctx, h_out, d_out, nv * W * entry_bytes()), "D2H pair entries"); }
+    void collect(size_t b0, size_t nv) const
+    {
+        std::string text;
+        char num[32];
+        for (size_t i = 0; i < nv; i++) {
+            const StringRecord &ra = vars[b0 + i].second;
+            // entries with b0 + i + d past the last kept variant were not written by the launch and are not read here
+            for (size_t d = 1; d <= W && b0 + i + d < vars.size(); d++) {
+                const StringRecord &rb = vars[b0 + i + d].second;
+                if (ra.at(col[0]) != rb.at(col[0])) continue;
+                const uint8_t *e = h_out + (i * W + (d - 1)) * entry_bytes();
+                uint32_t t[16];
+                uint64_t n_obs = 0;
+                float r2;
+                if (ld.counts) {
+                    std::memcpy(t, e, 64);
+                    r2 = table_r2(t, n_obs);
+                } else {
+                    std::memcpy(&r2, e, 4);
+                }
+                if (std::isnan(r2) || (double)r2 < ld.min_r2) continue;
+                for (const StringRecord *r : {&ra, &rb})
+                    for (int c = 0; c < 3; c++) {
+                        text += r->at(col[c]);
+                        text += '\t';
+                    }
+                std::snprintf(num, sizeof num, "%.6g", (double)r2);
+                text += num;
+                if (ld.counts) {
+                    text += '\t';
+                    append_u64(text, n_obs);
+                    for (int c = 0; c < 16; c++) {
+                        text += '\t';
+                        append_u64(text, t[c]);
+                    }
+                }
+                text += '\n';
+            }
+        }
+        std::lock_guard<std::mutex> lk(mu);
+        pieces.emplace(b0, std::move(text));
     }
     void finish(pgenhip_ctx *) const {}
 };
@@ -1143,6 +1237,58 @@ OutputStats Pfile::output_sample_counts(const std::optional<std::string> &sam_qu
             append_u64(text, totals[4 * k + (size_t)c]);
         }
         text += '\n';
+    }
+    st.body_bytes = text.size() - st.header_bytes;
+    st.file_bytes = text.size();
+    write_text(text, filename);
+    st.seconds_body = now_s() - t_body;
+    return st;
+}
+
+OutputStats Pfile::output_ld(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
+                             const std::string &filename, const LdOptions &ld, const OutputOptions &opt) const
+{
+    OutputStats st;
+    const double t0 = now_s();
+    const Selection sel = select(sam_query, var_query, opt.filter_threads);
+    static const char *const kCols[3] = {"CHROM", "POS", "ID"};
+    size_t col[3];
+    for (int c = 0; c < 3; c++) {
+        col[c] = std::find(sel.var_header.begin(), sel.var_header.end(), std::string(kCols[c])) - sel.var_header.begin();
+        if (col[c] == sel.var_header.size()) throw PfileError(std::string(kCols[c]) + " not among the headers of " + pvar_path());
+    }
+    st.seconds_filter = now_s() - t0;
+
+    const KeptSamples kept = check_selection(*this, sel);
+    const size_t V = sel.var_idx_rcds.size(), K = kept.rows.size();
+    st.variants = V;
+    st.samples_kept = K;
+
+    std::string text = "#CHROM_A\tPOS_A\tID_A\tCHROM_B\tPOS_B\tID_B\tR2";
+    if (ld.counts) {
+        text += "\tN_OBS";
+        for (int a = 0; a < 4; a++)
+            for (int b = 0; b < 4; b++) text += std::string("\tT") + (char)('0' + a) + (char)('0' + b);
+    }
+    text += '\n';
+    st.header_bytes = text.size();
+    const double t_body = now_s();
+    if (V >= 2 && K != 0) {   // else no pair or nothing to correlate: the header alone, no device touched
+        const uint32_t R = variant_record_size();
+        const uint32_t W = (uint32_t)std::min<uint64_t>(ld.window, V - 1);   // no pair reaches further
+        const uint64_t entry = ld.counts ? 64u : 4u;
+        // left rows per block: their W entries each fill the block budget (or --block-rows)
+        uint64_t bv = ld.block_rows ? ld.block_rows : std::max<uint64_t>(1, opt.block_text_bytes / ((uint64_t)W * entry));
+        bv = std::min<uint64_t>(bv, V);
+        OutputOptions blocks = opt;
+        blocks.block_text_bytes = bv * R;   // count_blocks sizes its blocks by record bytes
+        std::map<size_t, std::string> pieces;
+        std::mutex mu;
+        count_blocks(*this, sel.var_idx_rcds, kept, blocks, "no HIP device: the pairwise path has no CPU fallback", st, [&](DeviceCtx &ctx, uint64_t n) {
+            const size_t bytes = (size_t)(n * W * entry);
+            return PairWriter{R, W, ld, sel.var_idx_rcds, col, pieces, mu, ctx.device<uint8_t>(bytes, "device pair entries"), ctx.pinned<uint8_t>(bytes, "pinned pair entries")};
+        }, W);
+        for (auto &p : pieces) text += p.second;
     }
     st.body_bytes = text.size() - st.header_bytes;
     st.file_bytes = text.size();

@@ -88,6 +88,14 @@ struct MatrixOptions {
     bool sample_major = false;        // shape (K, V_kept) instead of (V_kept, K)
 };
 
+// `ld`: the window in kept variants, the r^2 floor of a printed pair, r^2 alone or the pair's table beside it
+struct LdOptions {
+    uint32_t window = 0;              // W >= 1: pairs (i, i + d), 1 <= d <= W, of the kept variants
+    double min_r2 = 0.2;              // pairs below it (and NaN pairs) are not printed; 0 prints every pair with a defined r^2
+    bool counts = false;              // --counts: N_OBS and the sixteen cells behind R2, r^2 from the table on the host
+    uint64_t block_rows = 0;          // left rows per block (0: as many as fill block_text_bytes with their W entries each)
+};
+
 struct OutputStats {
     uint64_t variants = 0, samples_kept = 0, header_bytes = 0, body_bytes = 0;   // header / body: bytes of VCF text
     uint64_t file_bytes = 0;                                                     // what the output file holds (BGZF: compressed)
@@ -173,6 +181,16 @@ class Pfile {
     // Uses n_gpus, n_shards, block_text_bytes (bytes of matrix per block), read_threads and filter_threads of `opt`.
     OutputStats output_matrix(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
                               const std::string &filename, const MatrixOptions &mopt, const OutputOptions &opt = OutputOptions()) const;
+
+    // `ld` (not in the reference): r^2 of every pair of kept variants at most `window` kept variants apart, over the kept samples
+    // (pgenhip_pair_stats / _at, the unphased genotype correlation over the samples called in both; no digit parity with plink2 is
+    // claimed).  One tab-separated line per pair on one chromosome with r^2 >= min_r2, ordered by (first variant, distance):
+    // CHROM_A POS_A ID_A CHROM_B POS_B ID_B R2 (%.6g), with counts also N_OBS and the table's cells T00 .. T33 (Tab = samples with
+    // code a in A and b in B; 0 hom-ref, 1 het, 2 hom-alt, 3 missing).  Selection and staging are freq's; shards own contiguous
+    // ranges of first variants and every block stages the `window` rows behind its own, so no pair is lost or repeated at a seam.
+    // Fewer than two kept variants or no kept sample: the header alone, no device.  filename empty: stdout.
+    OutputStats output_ld(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
+                          const std::string &filename, const LdOptions &ld, const OutputOptions &opt = OutputOptions()) const;
 
     // the header part of output_vcf (:110-146) on its own: used by output_vcf and by the CPU tests
     std::string vcf_header(const IdxRecords &sam_idx_rcs, const StringRecord &sam_header) const;
