@@ -326,6 +326,42 @@ int pgenhip_pair_stats(pgenhip_ctx *ctx, const void *d_records, uint64_t record_
 int pgenhip_pair_stats_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
                           uint32_t n_left, uint32_t window, void *d_out, uint32_t flags);
 
+/* ---- packed records of the kept samples (device-resident, asynchronous on the ctx stream) ----
+ * The selection written back as records: row j of the output is the mode-0x02 record of a K-sample file that holds the ctx's kept
+ * samples of selected row j, so a host that puts the 12-byte header in front has a .pgen of the subset (src/pfile.rs:172-175 read
+ * backwards).  Rows are selected exactly as in pgenhip_decode_emit / pgenhip_decode_emit_at: by stride (record_stride >= R, or
+ * n_variants <= 1), through d_variant_idx, or through d_record_off; records may start at any byte alignment; a gather that repeats
+ * a row writes it twice.
+ *   - Row j is R_K = ceil(K / 4) bytes (pgenhip_packed_record_size) at d_out + j*out_stride: the code of kept sample k in byte k/4,
+ *     bits 2*(k%4), LSB first; k is the sample's rank in the ctx's kept list (its index when all samples are kept).  The pad bits
+ *     of the last byte are always written as zero, whatever the input's pad bits and code_map hold.  Samples >= N are never read
+ *     as samples.
+ *   - out_stride >= R_K (or n_variants <= 1); any alignment of d_out, any out_stride.  Bytes of d_out outside the n_variants x R_K
+ *     record bytes (row padding included) are not touched.  n_variants == 0 or K == 0 writes nothing and is PGENHIP_OK.
+ *   - code_map is a HOST pointer to four bytes, the 2-bit code written for input codes 0, 1, 2, 3; it is read during the call and
+ *     passed as kernel arguments (no device copy, no allocation; a captured graph keeps the map it was captured with).  NULL is the
+ *     identity; a value > 3 is PGENHIP_ERR_BAD_ARG.  The library does not interpret the map: {3, 2, 0, 1} is the PLINK 1 .bed coding
+ *     with ALT as A1 (00 hom A1, 01 missing, 10 het, 11 hom A2).
+ *   - Shapes (flags; anything else is PGENHIP_ERR_BAD_ARG).  GENERAL applies always: one output byte per lane, four gathered codes.
+ *     DENSE: all samples kept (no list, or the identity list).  GATHER: the ctx was created with a kept list (an identity list
+ *     counts) of K >= 1 samples.  A forced shape that does not apply is PGENHIP_ERR_BAD_ARG with a detail string, also on a call that
+ *     would write nothing; AUTO takes DENSE or GATHER where they apply and GENERAL otherwise.
+ *   - PGENHIP_ERR_TOO_LARGE before any launch for offsets of 2^52 bytes or more, as in pgenhip_decode_matrix: out_stride times
+ *     n_variants, record_stride times n_variants without a gather, record_stride itself with d_variant_idx.
+ * Same launch contract as pgenhip_genotype_counts: device pointers only, no allocation, no synchronisation, queued on the ctx
+ * stream, graph-capturable.  Every output byte has one owner: no atomics and no work counters, so these launches do not count
+ * against PGENHIP_LAUNCHES_IN_FLIGHT. */
+#define PGENHIP_PACK_AUTO 0u
+#define PGENHIP_PACK_GENERAL 1u   /* any K, any layout: the correctness baseline */
+#define PGENHIP_PACK_DENSE 2u     /* all samples kept: a record copy between two byte phases */
+#define PGENHIP_PACK_GATHER 3u    /* a kept list, K >= 1: output-driven, one output dword per lane */
+uint32_t pgenhip_packed_record_size(const pgenhip_ctx *ctx);   /* ceil(K / 4); 0 for a NULL ctx */
+int pgenhip_pack_records(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                         uint32_t n_variants, void *d_out, uint64_t out_stride, const uint8_t *code_map, uint32_t flags);
+/* Same, with the record of row j at d_base + d_record_off[j] (DEVICE array of u64 byte offsets). */
+int pgenhip_pack_records_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
+                            void *d_out, uint64_t out_stride, const uint8_t *code_map, uint32_t flags);
+
 /* Launch-shape knobs of one ctx (tests force small grids to exercise ring re-use; A/B probes).
  * value 0 restores the built-in default of a knob unless noted. */
 typedef enum pgenhip_knob {
@@ -346,6 +382,7 @@ typedef enum pgenhip_knob {
     PGENHIP_KNOB_SCOUNT_SLICES = 17,     /* per-sample counts: row ranges per column tile, each summed by one block (default 0 = as many as fill the chip's resident blocks) */
     PGENHIP_KNOB_MATRIX_BLOCKS = 18,     /* genotype matrix kernels: grid size in blocks (default 0 = by shape: the work, capped at 8 blocks per CU, 4 for TILE); tests force small grids */
     PGENHIP_KNOB_PAIR_BLOCKS = 19,       /* pairwise kernel: grid size in blocks (default 0 = by shape: the tiles, capped at 16 one-wave blocks per CU); tests force small grids */
+    PGENHIP_KNOB_PACK_BLOCKS = 20,       /* pack kernels: grid size in blocks (default 0 = by shape: the work, capped at 8 blocks per CU); tests force small grids */
     PGENHIP_KNOB_RUNS_ROWS = 7          /* RUNS kernel: rows per work item (default: as many as one wide load / one span holds) */
 } pgenhip_knob;
 int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value);

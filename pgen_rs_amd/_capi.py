@@ -54,6 +54,10 @@ MATRIX_STREAM = 2
 MATRIX_TILE = 3
 MATRIX_SHAPE_MASK = 0xF
 MATRIX_SAMPLE_MAJOR = 0x10
+PACK_AUTO = 0
+PACK_GENERAL = 1
+PACK_DENSE = 2
+PACK_GATHER = 3
 PAIR_TABLE = 0
 PAIR_R2 = 1
 SYNTH_DIRTY_PAD = 1
@@ -76,6 +80,7 @@ KNOB_ALIGN_STORES = 16
 KNOB_SCOUNT_SLICES = 17
 KNOB_MATRIX_BLOCKS = 18
 KNOB_PAIR_BLOCKS = 19
+KNOB_PACK_BLOCKS = 20
 
 
 
@@ -123,6 +128,9 @@ PROTOTYPES = {
     "pgenhip_decode_matrix_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_pair_stats": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_pair_stats_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
+    "pgenhip_packed_record_size": (C.c_uint32, [ctx_p]),
+    "pgenhip_pack_records": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]),
+    "pgenhip_pack_records_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]),
     "pgenhip_tune": (C.c_int, [ctx_p, C.c_uint32, C.c_int32]),
     "pgenhip_wait": (C.c_int, [ctx_p]),
     "pgenhip_timer_start": (C.c_int, [ctx_p]),

@@ -766,6 +766,71 @@ int pgenhip_pair_stats_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *
     return pair_stats_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, n_left, window, d_out, flags);
 }
 
+static int pack_records_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                             const uint64_t *d_record_off, uint32_t n_variants, void *d_out, uint64_t out_stride,
+                             const uint8_t *code_map, uint32_t flags)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (flags > PGENHIP_PACK_GATHER) return fail(PGENHIP_ERR_BAD_ARG, "unknown pack_records flag");
+    uint32_t map8 = kPackIdentityMap;
+    if (code_map) {
+        map8 = 0u;
+        for (uint32_t c = 0; c < 4u; c++) {
+            if (code_map[c] > 3u) return fail(PGENHIP_ERR_BAD_ARG, "code_map entry > 3");
+            map8 |= (uint32_t)code_map[c] << (2u * c);
+        }
+    }
+    const uint32_t K = ctx->kept_count, RK = (K + 3u) / 4u;
+    const bool all_kept = !ctx->subset || ctx->identity;
+    if (flags == PGENHIP_PACK_DENSE && !all_kept) return fail(PGENHIP_ERR_BAD_ARG, "PGENHIP_PACK_DENSE needs all samples kept");
+    if (flags == PGENHIP_PACK_GATHER && (!ctx->subset || K == 0u))
+        return fail(PGENHIP_ERR_BAD_ARG, "PGENHIP_PACK_GATHER needs a kept list of at least one sample");
+    if (n_variants == 0 || K == 0u) return PGENHIP_OK;   // nothing to write
+    if (!d_out) return fail(PGENHIP_ERR_BAD_ARG, "d_out is NULL");
+    PackArgs a;
+    rc = select_rows(ctx, a, d_records, record_stride, d_variant_idx, d_record_off, n_variants);
+    if (rc) return rc;
+    if (n_variants > 1 && out_stride < RK) return fail(PGENHIP_ERR_BAD_ARG, "out_stride < one packed record");
+    // byte offsets are 64-bit arithmetic in the kernels; the bound is decode_matrix's (2^52 bytes).  With a variant list the row
+    // numbers live on the device (as record_off's offsets do) and only the stride itself is bounded
+    constexpr uint64_t kMaxSpan = 1ull << 52;
+    const bool by_stride = n_variants > 1 && !d_record_off;
+    if ((n_variants > 1 && out_stride >= kMaxSpan / n_variants) || (by_stride && !d_variant_idx && record_stride >= kMaxSpan / n_variants) ||
+        (by_stride && d_variant_idx && record_stride >= kMaxSpan))
+        return fail(PGENHIP_ERR_TOO_LARGE, "pack offsets do not fit the kernels' index types");
+    a.kept_count = K;
+    a.out = static_cast<uint8_t *>(d_out);
+    a.out_stride = out_stride;
+    a.map8 = map8;
+    const int blocks = ctx->tune.pack_blocks;
+    a.kept_idx = all_kept ? nullptr : ctx->d_kept;
+    if (flags == PGENHIP_PACK_DENSE || (flags == PGENHIP_PACK_AUTO && gt_pack_dense_applicable(a))) {
+        HIP_TRY(launch_gt_pack_dense(a, blocks, ctx->num_cus, ctx->stream));
+    } else if (flags == PGENHIP_PACK_GATHER || (flags == PGENHIP_PACK_AUTO && gt_pack_gather_applicable(a))) {
+        a.kept_idx = ctx->d_kept;   // forced on an identity list: the list is there
+        HIP_TRY(launch_gt_pack_gather(a, blocks, ctx->num_cus, ctx->stream));
+    } else {
+        HIP_TRY(launch_gt_pack_general(a, blocks, ctx->num_cus, ctx->stream));
+    }
+    return PGENHIP_OK;
+}
+
+uint32_t pgenhip_packed_record_size(const pgenhip_ctx *ctx) { return ctx ? (ctx->kept_count + 3u) / 4u : 0u; }
+
+int pgenhip_pack_records(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                         uint32_t n_variants, void *d_out, uint64_t out_stride, const uint8_t *code_map, uint32_t flags)
+{
+    return pack_records_core(ctx, d_records, record_stride, d_variant_idx, nullptr, n_variants, d_out, out_stride, code_map, flags);
+}
+
+int pgenhip_pack_records_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
+                            void *d_out, uint64_t out_stride, const uint8_t *code_map, uint32_t flags)
+{
+    if (const int rc = check_record_off(ctx, d_record_off, n_variants)) return rc;
+    return pack_records_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, d_out, out_stride, code_map, flags);
+}
+
 int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)
 {
     if (!ctx) return fail(PGENHIP_ERR_BAD_ARG, "ctx is NULL");
@@ -790,6 +855,7 @@ int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)
         case PGENHIP_KNOB_SCOUNT_SLICES: t.scount_slices = value > 0 ? value : d.scount_slices; break;
         case PGENHIP_KNOB_MATRIX_BLOCKS: t.matrix_blocks = value > 0 ? value : d.matrix_blocks; break;
         case PGENHIP_KNOB_PAIR_BLOCKS: t.pair_blocks = value > 0 ? value : d.pair_blocks; break;
+        case PGENHIP_KNOB_PACK_BLOCKS: t.pack_blocks = value > 0 ? value : d.pack_blocks; break;
         default: return fail(PGENHIP_ERR_BAD_ARG, "unknown knob");
     }
     return PGENHIP_OK;

@@ -55,6 +55,7 @@ struct Tuning {
     int scount_slices = 0;         // per-sample counts: row ranges per column tile (0 = as many as fill the chip's resident blocks)
     int matrix_blocks = 0;         // genotype matrix kernels: grid size in blocks (0 = by shape, capped per CU)
     int pair_blocks = 0;           // pairwise kernel: grid size in blocks (0 = by shape, capped per CU)
+    int pack_blocks = 0;           // pack kernels: grid size in blocks (0 = by shape, capped per CU)
 };
 
 // rows are gathered (variant list or byte offsets): the HAS_VIDX instantiations
@@ -162,6 +163,23 @@ struct PairArgs : RowSource {
 };
 // blocks: forced grid size (0 = by shape; tests force small grids to walk the grid-stride loop)
 hipError_t launch_gt_pair(const PairArgs &a, int blocks, int num_cus, hipStream_t stream);
+
+// Packed records (gt_pack.hip): row j = the mode-0x02 record of the K kept samples of selected row j, ceil(K / 4) bytes at
+// out + j * out_stride, every code sent through a 2-bit -> 2-bit map, pad bits zero.
+struct PackArgs : RowSource {
+    const uint32_t *kept_idx;     // device or nullptr (all samples, or an identity list)
+    uint32_t kept_count;          // K (== N when kept_idx is nullptr)
+    uint8_t *out;                 // device, any alignment
+    uint64_t out_stride;          // bytes between output rows
+    uint32_t map8;                // the code written for input code c at bits 2c, 2c + 1
+};
+constexpr uint32_t kPackIdentityMap = 0xE4u;
+bool gt_pack_dense_applicable(const PackArgs &a);    // all samples kept
+bool gt_pack_gather_applicable(const PackArgs &a);   // a kept list, K >= 1
+// blocks: forced grid size (0 = by shape; tests force small grids to walk the grid-stride loops)
+hipError_t launch_gt_pack_general(const PackArgs &a, int blocks, int num_cus, hipStream_t stream);
+hipError_t launch_gt_pack_dense(const PackArgs &a, int blocks, int num_cus, hipStream_t stream);
+hipError_t launch_gt_pack_gather(const PackArgs &a, int blocks, int num_cus, hipStream_t stream);
 
 // Deterministic synthetic records (SURVEY.md §8d counter-based generator).
 hipError_t launch_synth_records(uint8_t *dst, uint64_t record_stride, uint32_t sample_count,

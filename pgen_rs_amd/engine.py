@@ -82,6 +82,10 @@ def vw_select_uncompressed(types: np.ndarray, lens: np.ndarray, offs: np.ndarray
     return sel[:n]
 
 
+# pack_records' code_map for PLINK 1 .bed with ALT as A1: 00 hom A1, 01 missing, 10 het, 11 hom A2
+BED_CODE_MAP = (3, 2, 0, 1)
+
+
 def _ptr(t: Optional[torch.Tensor], byte_offset: int = 0) -> Optional[int]:
     if t is None:
         return None
@@ -421,6 +425,63 @@ class GtEngine:
         check(lib.pgenhip_decode_matrix_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, out.data_ptr(), stride,
                                            out.element_size(), tab.ctypes.data_as(C.c_void_p), flags), "pgenhip_decode_matrix_at")
         return res
+
+    # -- packed records of the kept samples -----------------------------------------------------
+    @property
+    def packed_record_size(self) -> int:
+        """``ceil(K / 4)``: bytes of one packed record of the kept samples."""
+        return int(lib.pgenhip_packed_record_size(self._ctx))
+
+    def pack_records(self, records: torch.Tensor, record_stride: Optional[int] = None, variant_idx: Optional[torch.Tensor] = None,
+                     out: Optional[torch.Tensor] = None, *, out_stride: Optional[int] = None, code_map=None,
+                     shape: int = _capi.PACK_AUTO, n_variants: Optional[int] = None, records_offset: int = 0,
+                     out_offset: int = 0) -> torch.Tensor:
+        """The selection written back as records: a ``(n_variants, R_K)`` uint8 view whose row j is the mode-0x02 record of the K
+        kept samples of selected row j (kept sample k in byte k/4, bits 2*(k%4)), pad bits zero; behind a 12-byte header the rows are
+        a .pgen of the subset.
+
+        Rows are selected as in ``decode_emit`` (``n_variants`` defaults as in ``genotype_counts``).  ``code_map``: four codes
+        0-3 written for input codes 0-3 (``BED_CODE_MAP`` for PLINK 1 .bed), default the identity.  ``out``: a flat uint8 CUDA
+        tensor; row j goes to byte ``out_offset + j*out_stride`` (default stride ``R_K``) and nothing else is touched.  The result
+        is a view of ``out`` with row pitch ``out_stride``."""
+        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
+        out, stride, cmap = self._pack_out(out, n_variants, out_stride, out_offset, code_map)
+        check(lib.pgenhip_pack_records(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants,
+                                       _ptr(out, out_offset), stride, cmap, shape), "pgenhip_pack_records")
+        return self._pack_view(out, n_variants, stride, out_offset)
+
+    def pack_records_at(self, base: torch.Tensor, record_off: torch.Tensor, out: Optional[torch.Tensor] = None, *,
+                        out_stride: Optional[int] = None, code_map=None, shape: int = _capi.PACK_AUTO,
+                        n_variants: Optional[int] = None, out_offset: int = 0) -> torch.Tensor:
+        """``pack_records`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
+        n_variants = self._rows_at(base, record_off, n_variants)
+        out, stride, cmap = self._pack_out(out, n_variants, out_stride, out_offset, code_map)
+        check(lib.pgenhip_pack_records_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, _ptr(out, out_offset), stride, cmap,
+                                          shape), "pgenhip_pack_records_at")
+        return self._pack_view(out, n_variants, stride, out_offset)
+
+    def _pack_out(self, out: Optional[torch.Tensor], n_variants: int, out_stride: Optional[int], out_offset: int, code_map):
+        """(the flat output, the row stride, the map as four bytes or None)"""
+        rk = self.packed_record_size
+        if out_stride is None:
+            out_stride = rk
+        if out is None:
+            out = torch.empty(out_offset + max(n_variants * out_stride, rk, 1), dtype=torch.uint8, device=self.torch_device)
+        self._check_dev(out, "out")
+        if out.dtype != torch.uint8:
+            raise ValueError("out must be a uint8 tensor")
+        if n_variants and out.numel() < out_offset + (n_variants - 1) * out_stride + rk:
+            raise ValueError("out too small")
+        cmap = None
+        if code_map is not None:
+            vals = [int(v) for v in code_map]
+            if len(vals) != 4 or any(not 0 <= v <= 255 for v in vals):
+                raise ValueError("code_map must hold four codes (for input codes 0, 1, 2, 3)")
+            cmap = (C.c_uint8 * 4)(*vals)
+        return out.view(-1), out_stride, cmap
+
+    def _pack_view(self, out: torch.Tensor, n_variants: int, stride: int, out_offset: int) -> torch.Tensor:
+        return torch.as_strided(out, (n_variants, self.packed_record_size), (stride, 1), out_offset)
 
     # -- windowed pairwise tables / r^2 ---------------------------------------------------------
     def pair_tables(self, records: torch.Tensor, record_stride: Optional[int] = None, variant_idx: Optional[torch.Tensor] = None,

@@ -11,6 +11,9 @@
 // `pgen-hip matrix <PFILE_PREFIX> [--include-var <EXPR>] [--include-sam <EXPR>] [--dtype i8|f16|f32] [--missing <X>] [--sample-major]
 // -o|--out <FILE.npy>` (not in the reference): the additive-coded genotype matrix (0 / 1 / 2 alternate alleles, --missing for
 // "./.") of the kept variants and samples as a NumPy .npy file, decoded on the GPU; FILE.npy.variants / FILE.npy.samples hold the ids.
+// `pgen-hip export <PFILE_PREFIX> -o|--out <OUT_PREFIX> [--format pgen|bed] [--include-var <EXPR>] [--include-sam <EXPR>]` (not in the
+// reference): the kept variants and samples written back as OUT_PREFIX.pgen / .pvar / .psam (fixed-width), or as PLINK 1 .bed / .bim /
+// .fam; the records are packed on the GPU.
 // Additions (opt-in, not in the reference): --gpus <N>, --block-mib <M>, --launch-mib <M>, --filter-threads <T>, --stats, --dry-run
 // (filter: write the VCF header only and report the body geometry; needs no GPU); BGZF output (`-o x.vcf.gz` or --bgzf,
 // --bgzf-level <1-9>, --compress-threads <T>) and `pgen-hip bgzf <IN> <OUT>`, the same writer on a file.
@@ -82,6 +85,7 @@ const char *kUsage =
     "  sample-counts  Per-sample genotype counts over the kept variants, outputting to stdout\n"
     "  matrix  Numeric genotype matrix of the kept variants and samples, outputting to a NumPy .npy file\n"
     "  ld      Pairwise r^2 of the kept variants inside a sliding window, outputting to stdout\n"
+    "  export  Writes the kept variants and samples back as a .pgen (or PLINK 1 .bed) fileset\n"
     "  help    Print this message\n\n"
     "query  <PFILE_PREFIX> -f, --fstring <QUERY_FSTRING> [-i, --include <QUERY>] [-s, --samples]\n"
     "filter <PFILE_PREFIX> [--include-var <VAR_QUERY>] [--include-sam <SAM_QUERY>] [-o, --out <OUT_FILE>]\n"
@@ -106,6 +110,11 @@ const char *kUsage =
     "       are dropped): CHROM_A POS_A ID_A CHROM_B POS_B ID_B R2, ordered by first variant and distance; --counts appends N_OBS\n"
     "       and the pair's 4 x 4 genotype table T00 .. T33.  r^2 is the unphased genotype correlation over the kept samples called\n"
     "       in both variants; no digit parity with plink2 is claimed\n"
+    "export <PFILE_PREFIX> -o, --out <OUT_PREFIX> [--format pgen|bed] [--include-var <VAR_QUERY>] [--include-sam <SAM_QUERY>]\n"
+    "       [--gpus <N>] [--shards <S>] [--block-mib <M>] [--read-threads <T>] [--filter-threads <T>] [--stats]\n"
+    "       the kept variants and samples as OUT_PREFIX.pgen (fixed-width, storage mode 0x02), .pvar (the header lines and the kept\n"
+    "       rows) and .psam; --format bed: PLINK 1 OUT_PREFIX.bed (variant-major, ALT as A1), .bim (CHROM ID 0 POS ALT REF) and .fam\n"
+    "       (FID IID PAT MAT SEX -9; 0 for a missing column).  OUT_PREFIX must not name the input; no byte parity with plink2 is claimed\n"
     "bgzf   <IN_FILE> <OUT_FILE> [--level <1-9>] [--threads <T>] [--chunk-mib <M>]\n";
 
 [[noreturn]] void usage_error(const std::string &msg)
@@ -399,6 +408,20 @@ int main(int argc, char **argv)
             const MatrixOptions m = matrix_options(a);
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
             const OutputStats st = pfile.output_matrix(a.get("include-sam"), a.get("include-var"), *a.get("out"), m, output_options(a));
+            if (a.has("stats")) print_stats(st, t_main);
+            return 0;
+        }
+        if (cmd == "export") {
+            Args a = parse(argc, argv, 2, {{"include-var", 0}, {"include-sam", 0}, {"out", 'o'}, {"format", 0}, {"gpus", 0}, {"shards", 0}, {"block-mib", 0}, {"read-threads", 0}, {"filter-threads", 0}},
+                           {{"stats", 0}});
+            if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
+            if (!a.has("out") || a.get("out")->empty()) usage_error("the following required arguments were not provided: --out <OUT_PREFIX>");
+            const std::string format = a.get("format").value_or("pgen");
+            if (format != "pgen" && format != "bed") usage_error("invalid value '" + format + "' for '--format <FORMAT>' [possible values: pgen, bed]");
+            ExportOptions e;
+            e.bed = format == "bed";
+            const Pfile pfile = Pfile::from_prefix(a.positional[0]);
+            const OutputStats st = pfile.output_export(a.get("include-sam"), a.get("include-var"), *a.get("out"), e, output_options(a));
             if (a.has("stats")) print_stats(st, t_main);
             return 0;
         }

@@ -13,6 +13,7 @@
 #include <cstring>
 #include <condition_variable>
 #include <deque>
+#include <filesystem>
 #include <fstream>
 #include <map>
 #include <mutex>
@@ -1046,6 +1047,27 @@ struct MatrixWriter {
     void finish(pgenhip_ctx *) const {}
 };
 
+// export's "counter": every block's packed records come back and are written to their place in the .pgen / .bed
+struct PackWriter {
+    uint32_t R;
+    size_t RK;
+    const uint8_t *code_map;   // NULL: the identity
+    uint8_t *d_out, *h_out;
+    int fd;
+    const std::string &path;
+    uint64_t data_off;
+    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, uint32_t nv, uint32_t) const
+    {
+        if (d_off)
+            check(pgenhip_pack_records_at(ctx, d_rec, d_off, nv, d_out, RK, code_map, PGENHIP_PACK_AUTO), "pgenhip_pack_records_at");
+        else
+            check(pgenhip_pack_records(ctx, d_rec, R, nullptr, nv, d_out, RK, code_map, PGENHIP_PACK_AUTO), "pgenhip_pack_records");
+    }
+    void copy(pgenhip_ctx *ctx, size_t nv) const { check(pgenhip_memcpy_d2h(ctx, h_out, d_out, nv * RK), "D2H packed records"); }
+    void collect(size_t b0, size_t nv) const { pwrite_exact(fd, h_out, nv * RK, data_off + (uint64_t)b0 * RK, path); }
+    void finish(pgenhip_ctx *) const {}
+};
+
 // r^2 of a 4 x 4 table by the formula of pgenhip_pair_stats (include/pgen_hip.h): exact 64-bit terms, doubles, one rounding to float
 float table_r2(const uint32_t *t, uint64_t &n_obs)
 {
@@ -1358,6 +1380,108 @@ OutputStats Pfile::output_matrix(const std::optional<std::string> &sam_query, co
     ids.clear();
     for (const auto &sr : sel.sam_idx_rcs) ids += sr.second.at(iid_col) + "\n";
     write_text(ids, filename + ".samples");
+    st.seconds_body = now_s() - t_body;
+    return st;
+}
+
+OutputStats Pfile::output_export(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
+                                 const std::string &out_prefix, const ExportOptions &eopt, const OutputOptions &opt) const
+{
+    OutputStats st;
+    const double t0 = now_s();
+    const std::string out_main = out_prefix + (eopt.bed ? ".bed" : ".pgen");
+    const std::string out_var = out_prefix + (eopt.bed ? ".bim" : ".pvar"), out_sam = out_prefix + (eopt.bed ? ".fam" : ".psam");
+    if (!eopt.bed) {   // the same file by another spelling or through a link is still the input
+        std::error_code ec1, ec2;
+        const auto in = std::filesystem::weakly_canonical(pgen_path(), ec1), out = std::filesystem::weakly_canonical(out_main, ec2);
+        if (out_main == pgen_path() || (!ec1 && !ec2 && in == out))
+            throw PfileError("export would overwrite its input: " + out_main + " is " + pgen_path());
+    }
+    const Selection sel = select(sam_query, var_query, opt.filter_threads);
+    auto column = [](const StringRecord &header, const char *name) {
+        for (size_t c = 0; c < header.size(); c++)
+            if (header[c] == name) return c;
+        return header.size();
+    };
+    auto need = [&](const StringRecord &header, const char *name, const std::string &file) {
+        const size_t c = column(header, name);
+        if (c == header.size()) throw PfileError(std::string(name) + " not among the headers of " + file);
+        return c;
+    };
+    auto join_rows = [](std::string &text, const IdxRecords &rows) {
+        for (const auto &ir : rows) {
+            for (size_t c = 0; c < ir.second.size(); c++) {
+                if (c) text += '\t';
+                text += ir.second[c];
+            }
+            text += '\n';
+        }
+    };
+    std::string var_text, sam_text;
+    if (eopt.bed) {
+        const StringRecord &vh = sel.var_header, &sh = sel.sam_header;
+        const size_t chrom = need(vh, "CHROM", pvar_path()), id = need(vh, "ID", pvar_path()), pos = need(vh, "POS", pvar_path()),
+                     ref = need(vh, "REF", pvar_path()), alt = need(vh, "ALT", pvar_path());
+        for (const auto &vr : sel.var_idx_rcds) {
+            const StringRecord &r = vr.second;
+            if (r.at(alt).find(',') != std::string::npos)
+                throw PfileError("variant " + r.at(id) + " (row " + std::to_string(vr.first) + " of " + pvar_path() + ") has more than one ALT allele (" +
+                                 r.at(alt) + "): a .bed holds biallelic variants only");
+            var_text += r.at(chrom) + '\t' + r.at(id) + "\t0\t" + r.at(pos) + '\t' + r.at(alt) + '\t' + r.at(ref) + '\n';
+        }
+        const size_t iid = need(sh, "IID", psam_path()), fid = column(sh, "FID"), pat = column(sh, "PAT"), mat = column(sh, "MAT"), sex = column(sh, "SEX");
+        for (const auto &sr : sel.sam_idx_rcs) {
+            const StringRecord &r = sr.second;
+            auto or_zero = [&](size_t c) { return c == sh.size() ? std::string("0") : r.at(c); };
+            const std::string sx = sex == sh.size() ? std::string("0") : r.at(sex);
+            sam_text += or_zero(fid) + '\t' + r.at(iid) + '\t' + or_zero(pat) + '\t' + or_zero(mat) + '\t' + (sx == "1" || sx == "2" ? sx : std::string("0")) + "\t-9\n";
+        }
+    } else {
+        const auto [pvar_header, pvar_column_names] = read_pvar_header();
+        var_text = pvar_header + pvar_column_names;
+        if (!var_text.empty() && var_text.back() != '\n') var_text += '\n';
+        join_rows(var_text, sel.var_idx_rcds);
+        const std::string psam = read_file(psam_path());
+        const size_t eol = psam.find('\n', (size_t)find_metadata_file_header_start(psam));
+        sam_text = eol == std::string::npos ? psam + "\n" : psam.substr(0, eol + 1);
+        join_rows(sam_text, sel.sam_idx_rcs);
+    }
+    st.seconds_filter = now_s() - t0;
+
+    const KeptSamples kept = check_selection(*this, sel);
+    const size_t V = sel.var_idx_rcds.size(), K = kept.rows.size(), RK = (K + 3) / 4;
+    st.variants = V;
+    st.samples_kept = K;
+    std::string header;
+    if (eopt.bed) {
+        header.assign("\x6C\x1B\x01", 3);   // variant-major
+    } else {
+        header.assign("\x6C\x1B\x02", 3);
+        for (int b = 0; b < 4; b++) header += (char)(uint8_t)((uint32_t)V >> (8 * b));
+        for (int b = 0; b < 4; b++) header += (char)(uint8_t)((uint32_t)K >> (8 * b));
+        header += '\x40';
+    }
+    st.header_bytes = header.size();
+    st.body_bytes = (uint64_t)V * RK;
+    st.file_bytes = st.header_bytes + st.body_bytes;
+
+    const double t_body = now_s();
+    static const char *const kNoDevice = "no HIP device: the record pack path has no CPU fallback";
+    if (V != 0 && K != 0) const Shards probe(opt, kNoDevice);   // before the output files exist
+    Fd out(out_main, O_WRONLY | O_CREAT | O_TRUNC);
+    pwrite_exact(out.get(), header.data(), header.size(), 0, out_main);
+    if (V != 0 && K != 0) {   // else a zero dimension: the header alone, no device touched
+        static const uint8_t kBedMap[4] = {3, 2, 0, 1};   // ALT as A1: 00 hom A1, 01 missing, 10 het, 11 hom A2
+        const uint32_t R = variant_record_size();
+        count_blocks(*this, sel.var_idx_rcds, kept, opt, kNoDevice, st, [&](DeviceCtx &ctx, uint64_t bv) {
+            const size_t bytes = (size_t)(bv * RK);
+            return PackWriter{R, RK, eopt.bed ? kBedMap : nullptr, ctx.device<uint8_t>(bytes, "device packed records"),
+                              ctx.pinned<uint8_t>(bytes, "pinned packed records"), out.get(), out_main, (uint64_t)header.size()};
+        });
+    }
+    out.close();
+    write_text(var_text, out_var);
+    write_text(sam_text, out_sam);
     st.seconds_body = now_s() - t_body;
     return st;
 }

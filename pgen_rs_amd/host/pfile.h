@@ -96,6 +96,11 @@ struct LdOptions {
     uint64_t block_rows = 0;          // left rows per block (0: as many as fill block_text_bytes with their W entries each)
 };
 
+// `export`: the container written
+struct ExportOptions {
+    bool bed = false;                 // PLINK 1 .bed / .bim / .fam instead of .pgen / .pvar / .psam
+};
+
 struct OutputStats {
     uint64_t variants = 0, samples_kept = 0, header_bytes = 0, body_bytes = 0;   // header / body: bytes of VCF text
     uint64_t file_bytes = 0;                                                     // what the output file holds (BGZF: compressed)
@@ -191,6 +196,19 @@ class Pfile {
     // Fewer than two kept variants or no kept sample: the header alone, no device.  filename empty: stdout.
     OutputStats output_ld(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
                           const std::string &filename, const LdOptions &ld, const OutputOptions &opt = OutputOptions()) const;
+
+    // `export` (not in the reference): the kept variants and samples written back as a fixed-width (mode 0x02) OUT.pgen with OUT.pvar
+    // and OUT.psam, or as PLINK 1 OUT.bed / .bim / .fam (variant-major, ALT as A1; no byte parity with plink2 is claimed).  The records
+    // are packed on the GPU(s) (pgenhip_pack_records / _at) block by block and written with pwrite at 12 + j * R_K (3 + j * R_K for
+    // .bed), so shards and blocks write independently.  The .pvar is the input's header lines verbatim and then each kept row's
+    // fields joined by tabs; the .psam the input's bytes up to and including its column-header line, then the kept rows likewise.
+    // .bim: CHROM ID 0 POS ALT REF (an ALT with a ',' is an error that names the variant); .fam: FID IID PAT MAT SEX -9, with 0 for a
+    // column the .psam lacks and for a SEX other than 1 or 2.  Selection and staging are freq's.  A variable-width input whose kept
+    // records are plain gives a fixed-width output.  No kept variant or no kept sample: valid files with a zero dimension, no
+    // device.  out_prefix naming the input's own .pgen is refused before anything is opened for writing.
+    // Uses n_gpus, n_shards, block_text_bytes (bytes of records per block), read_threads and filter_threads of `opt`.
+    OutputStats output_export(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
+                              const std::string &out_prefix, const ExportOptions &eopt, const OutputOptions &opt = OutputOptions()) const;
 
     // the header part of output_vcf (:110-146) on its own: used by output_vcf and by the CPU tests
     std::string vcf_header(const IdxRecords &sam_idx_rcs, const StringRecord &sam_header) const;
