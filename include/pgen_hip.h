@@ -255,6 +255,48 @@ int pgenhip_sample_counts(pgenhip_ctx *ctx, const void *d_records, uint64_t reco
 int pgenhip_sample_counts_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
                              uint32_t *d_counts, uint32_t flags);
 
+/* ---- per-sample weighted dosage sums: polygenic scores (device-resident, asynchronous on the ctx stream) ----
+ * pgenhip_sample_counts with a weight per row: for every kept sample k and column c < n_columns
+ *     S[k, c] = sum over the selected rows j of (double)d_weights[j * w_stride + c] * D(j, k)
+ * where D is 0, 1, 2 for codes 0, 1, 2 (the number of alternate alleles) and (double)d_miss[j] for code 3 (missing); 0.0 for a
+ * missing call when d_miss is NULL.  Rows are selected exactly as in pgenhip_sample_counts / pgenhip_sample_counts_at; a gather
+ * that repeats a row adds it twice.  d_weights and d_miss are DEVICE arrays of f32 indexed by j, the row's position in the
+ * selection (not the file's row number); w_stride is in floats, >= n_columns (or n_variants <= 1).  The pad bits of a record's
+ * last byte are never read as samples.  Records may start at any byte alignment.
+ *   - Arithmetic: every term is formed in FP64, where it is exact (f32 times 1, 2 or an f32 fits 53 bits), and the terms are
+ *     accumulated in FP64 only; there are no f32 partial sums.  The ORDER of the additions is not fixed (blocks combine through
+ *     FP64 atomics), so the result of any (k, c) is within (n_variants + 1) * 2^-53 * sum|term| of the exact sum, and two runs
+ *     on the same input may differ in the last bits: bitwise run-to-run reproducibility is NOT promised.  Sums whose every
+ *     partial sum is an integer below 2^53 are exact whatever the order.  Non-finite weights or miss values give unspecified
+ *     results.
+ *   - Writes n_columns doubles per kept sample at d_scores[k * n_columns + c]; k is the sample's rank in the ctx's kept list
+ *     (its index when all samples are kept).  Without PGENHIP_SCORE_ACCUMULATE the call overwrites d_scores[0 .. K * n_columns)
+ *     (zeros when n_variants == 0).  With it the sums are added to what d_scores holds; n_variants == 0 is then a no-op.
+ *     Nothing outside d_scores[0 .. K * n_columns) is written; K == 0 writes nothing.
+ *   - d_scores must be ORDINARY device memory (hipMalloc, pgenhip_device_malloc), not fine-grained or host-mapped memory: the
+ *     kernel adds with hardware FP64 atomics, which such memory does not serve.
+ *   - PGENHIP_ERR_BAD_ARG: n_columns == 0 or > PGENHIP_SCORE_MAX_COLUMNS; w_stride < n_columns with n_variants > 1; d_weights
+ *     NULL with n_variants > 0; d_scores NULL or not 8-byte aligned with K > 0; d_weights or d_miss not 4-byte aligned; unknown
+ *     flag bits or shapes.  PGENHIP_ERR_TOO_LARGE, before any launch: byte offsets of 2^52 or more (w_stride * n_variants * 4,
+ *     record_stride * n_variants as in pgenhip_decode_matrix).  A host with more than PGENHIP_SCORE_MAX_COLUMNS scores calls
+ *     once per group of columns (d_weights + first column of the group, the same w_stride).
+ * Same launch contract as pgenhip_sample_counts: device pointers only, no allocation, no synchronisation, queued on the ctx
+ * stream, graph-capturable (the overwrite is a hipMemsetAsync ahead of the kernel).
+ * flags: a shape (PGENHIP_SCORE_AUTO or a forced one) | PGENHIP_SCORE_ACCUMULATE. */
+#define PGENHIP_SCORE_MAX_COLUMNS 8u
+#define PGENHIP_SCORE_AUTO 0u
+#define PGENHIP_SCORE_ROWS 1u         /* row by row, any layout (variant_idx, record_off, padded strides): what AUTO takes */
+/* 2u is reserved for a matrix-core form for many columns (v_mfma_f64_16x16x4_f64); not built */
+#define PGENHIP_SCORE_SHAPE_MASK 0xFu
+#define PGENHIP_SCORE_ACCUMULATE 0x10u
+int pgenhip_sample_scores(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                          uint32_t n_variants, const float *d_weights, uint64_t w_stride, uint32_t n_columns,
+                          const float *d_miss, double *d_scores, uint32_t flags);
+/* Same, with the record of row j at d_base + d_record_off[j] (DEVICE array of u64 byte offsets). */
+int pgenhip_sample_scores_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
+                             const float *d_weights, uint64_t w_stride, uint32_t n_columns,
+                             const float *d_miss, double *d_scores, uint32_t flags);
+
 /* ---- numeric genotype matrix (device-resident, asynchronous on the ctx stream) ----
  * The GT text with the fixed bytes removed: element (j, k) is the code pgenhip_decode_emit prints as the k-th field of row j,
  * mapped through a four-entry table.  Rows are selected exactly as in pgenhip_decode_emit / pgenhip_decode_emit_at; a gather that
@@ -383,7 +425,8 @@ typedef enum pgenhip_knob {
     PGENHIP_KNOB_MATRIX_BLOCKS = 18,     /* genotype matrix kernels: grid size in blocks (default 0 = by shape: the work, capped at 8 blocks per CU, 4 for TILE); tests force small grids */
     PGENHIP_KNOB_PAIR_BLOCKS = 19,       /* pairwise kernel: grid size in blocks (default 0 = by shape: the tiles, capped at 16 one-wave blocks per CU); tests force small grids */
     PGENHIP_KNOB_PACK_BLOCKS = 20,       /* pack kernels: grid size in blocks (default 0 = by shape: the work, capped at 8 blocks per CU); tests force small grids */
-    PGENHIP_KNOB_RUNS_ROWS = 7          /* RUNS kernel: rows per work item (default: as many as one wide load / one span holds) */
+    PGENHIP_KNOB_SCORE_SLICES = 21,      /* per-sample scores: row ranges per column tile, each summed by one block (default 0 = by shape: as many as fill the chip's resident blocks, of at least 512 rows each); tests put the row count on either side of every plan edge */
+    PGENHIP_KNOB_RUNS_ROWS = 7        /* RUNS kernel: rows per work item (default: as many as one wide load / one span holds) */
 } pgenhip_knob;
 int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value);
 

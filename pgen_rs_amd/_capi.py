@@ -48,6 +48,11 @@ SCOUNT_AUTO = 0
 SCOUNT_ROWS = 2
 SCOUNT_SHAPE_MASK = 0xF
 SCOUNT_ACCUMULATE = 0x10
+SCORE_MAX_COLUMNS = 8
+SCORE_AUTO = 0
+SCORE_ROWS = 1
+SCORE_SHAPE_MASK = 0xF
+SCORE_ACCUMULATE = 0x10
 MATRIX_AUTO = 0
 MATRIX_GENERAL = 1
 MATRIX_STREAM = 2
@@ -81,6 +86,7 @@ KNOB_SCOUNT_SLICES = 17
 KNOB_MATRIX_BLOCKS = 18
 KNOB_PAIR_BLOCKS = 19
 KNOB_PACK_BLOCKS = 20
+KNOB_SCORE_SLICES = 21
 
 
 
@@ -124,6 +130,8 @@ PROTOTYPES = {
     "pgenhip_genotype_counts_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_sample_counts": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_sample_counts_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
+    "pgenhip_sample_scores": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "pgenhip_sample_scores_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]),
     "pgenhip_decode_matrix": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_decode_matrix_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_pair_stats": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),

@@ -649,6 +649,63 @@ int pgenhip_sample_counts_at(pgenhip_ctx *ctx, const void *d_base, const uint64_
     return sample_counts_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, d_counts, flags);
 }
 
+static int sample_scores_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                              const uint64_t *d_record_off, uint32_t n_variants, const float *d_weights, uint64_t w_stride,
+                              uint32_t n_columns, const float *d_miss, double *d_scores, uint32_t flags)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (flags & ~(PGENHIP_SCORE_SHAPE_MASK | PGENHIP_SCORE_ACCUMULATE)) return fail(PGENHIP_ERR_BAD_ARG, "unknown sample_scores flag");
+    const uint32_t shape = flags & PGENHIP_SCORE_SHAPE_MASK;
+    if (shape != PGENHIP_SCORE_AUTO && shape != PGENHIP_SCORE_ROWS) return fail(PGENHIP_ERR_BAD_ARG, "sample_scores supports shapes AUTO and ROWS");
+    const bool accumulate = (flags & PGENHIP_SCORE_ACCUMULATE) != 0u;
+    if (n_columns == 0u || n_columns > PGENHIP_SCORE_MAX_COLUMNS) return fail(PGENHIP_ERR_BAD_ARG, "n_columns must be 1 .. PGENHIP_SCORE_MAX_COLUMNS");
+    if (n_variants > 1 && w_stride < n_columns) return fail(PGENHIP_ERR_BAD_ARG, "w_stride < n_columns");
+    if (n_variants && !d_weights) return fail(PGENHIP_ERR_BAD_ARG, "d_weights is NULL");
+    if ((uintptr_t)d_weights & 3u) return fail(PGENHIP_ERR_BAD_ARG, "d_weights is not 4-byte aligned");
+    if ((uintptr_t)d_miss & 3u) return fail(PGENHIP_ERR_BAD_ARG, "d_miss is not 4-byte aligned");
+    const uint32_t K = ctx->kept_count;
+    if (K != 0u && !d_scores) return fail(PGENHIP_ERR_BAD_ARG, "d_scores is NULL");
+    if (K != 0u && ((uintptr_t)d_scores & 7u)) return fail(PGENHIP_ERR_BAD_ARG, "d_scores is not 8-byte aligned");
+    // byte offsets are 64-bit arithmetic in the kernel; the bound is decode_matrix's (2^52 bytes).  With a variant list the row
+    // numbers live on the device (as record_off's offsets do) and only the stride itself is bounded
+    constexpr uint64_t kMaxSpan = 1ull << 52;
+    const bool by_stride = n_variants > 1 && !d_record_off;
+    if ((n_variants > 1 && w_stride >= kMaxSpan / 4u / n_variants) || (by_stride && !d_variant_idx && record_stride >= kMaxSpan / n_variants) ||
+        (by_stride && d_variant_idx && record_stride >= kMaxSpan))
+        return fail(PGENHIP_ERR_TOO_LARGE, "score offsets do not fit the kernel's index types");
+    if (K == 0u) return PGENHIP_OK;   // nothing to write
+    ScoreArgs a;
+    rc = select_rows(ctx, a, d_records, record_stride, d_variant_idx, d_record_off, n_variants);
+    if (rc) return rc;
+    if (!accumulate) HIP_TRY(hipMemsetAsync(d_scores, 0, sizeof(double) * K * n_columns, ctx->stream));   // the kernel only adds
+    if (n_variants == 0) return PGENHIP_OK;
+    a.kept_mask = ctx->d_count_mask;   // NULL with all samples kept or an identity list
+    a.kept_rank = ctx->d_scount_rank;
+    a.weights = d_weights;
+    a.w_stride = w_stride;
+    a.n_columns = n_columns;
+    a.miss = d_miss;
+    a.scores = d_scores;
+    HIP_TRY(launch_gt_score(a, ctx->tune.score_slices, ctx->num_cus, ctx->stream));
+    return PGENHIP_OK;
+}
+
+int pgenhip_sample_scores(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                          uint32_t n_variants, const float *d_weights, uint64_t w_stride, uint32_t n_columns,
+                          const float *d_miss, double *d_scores, uint32_t flags)
+{
+    return sample_scores_core(ctx, d_records, record_stride, d_variant_idx, nullptr, n_variants, d_weights, w_stride, n_columns, d_miss, d_scores, flags);
+}
+
+int pgenhip_sample_scores_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
+                             const float *d_weights, uint64_t w_stride, uint32_t n_columns,
+                             const float *d_miss, double *d_scores, uint32_t flags)
+{
+    if (const int rc = check_record_off(ctx, d_record_off, n_variants)) return rc;
+    return sample_scores_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, d_weights, w_stride, n_columns, d_miss, d_scores, flags);
+}
+
 static int decode_matrix_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
                               const uint64_t *d_record_off, uint32_t n_variants, void *d_out, uint64_t out_stride, uint32_t elem_bytes,
                               const void *code_values, uint32_t flags)
@@ -853,6 +910,7 @@ int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)
         case PGENHIP_KNOB_ALIGN_STORES: t.align_stores = value < 0 ? 0 : 1; break;
         case PGENHIP_KNOB_RUNS_ROWS: t.runs_rows = value > 0 ? value : d.runs_rows; break;
         case PGENHIP_KNOB_SCOUNT_SLICES: t.scount_slices = value > 0 ? value : d.scount_slices; break;
+        case PGENHIP_KNOB_SCORE_SLICES: t.score_slices = value > 0 ? value : d.score_slices; break;
         case PGENHIP_KNOB_MATRIX_BLOCKS: t.matrix_blocks = value > 0 ? value : d.matrix_blocks; break;
         case PGENHIP_KNOB_PAIR_BLOCKS: t.pair_blocks = value > 0 ? value : d.pair_blocks; break;
         case PGENHIP_KNOB_PACK_BLOCKS: t.pack_blocks = value > 0 ? value : d.pack_blocks; break;

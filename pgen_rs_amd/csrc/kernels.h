@@ -53,6 +53,7 @@ struct Tuning {
     int align_stores = 1;          // subset kernels: lanes <-> chunks shifted so that every store instruction covers whole 128-byte lines (0 = from the first whole chunk)
     int runs_rows = 0;             // RUNS mode of the stream kernel: rows per work item (0 = as many as one wide load / one span holds)
     int scount_slices = 0;         // per-sample counts: row ranges per column tile (0 = as many as fill the chip's resident blocks)
+    int score_slices = 0;          // per-sample scores: row ranges per column tile (0 = by shape: the chip's resident blocks, at least 512 rows each)
     int matrix_blocks = 0;         // genotype matrix kernels: grid size in blocks (0 = by shape, capped per CU)
     int pair_blocks = 0;           // pairwise kernel: grid size in blocks (0 = by shape, capped per CU)
     int pack_blocks = 0;           // pack kernels: grid size in blocks (0 = by shape, capped per CU)
@@ -133,6 +134,21 @@ struct ScountArgs : RowSource {
 };
 // slices_per_tile: row ranges per column tile (0 = as many as fill the chip's resident blocks)
 hipError_t launch_gt_scount(const ScountArgs &a, int slices_per_tile, int num_cus, hipStream_t stream);
+
+// Per-sample weighted dosage sums (gt_score.hip): for every kept sample k and column c < n_columns the FP64 sum over the selected
+// rows j of (double)weights[j * w_stride + c] * D(j, k), added into scores[k * n_columns + c]; D = 0, 1, 2 for codes 0, 1, 2 and
+// (double)miss[j] for code 3 (0 without miss).  weights and miss are indexed by the row's position in the selection.
+struct ScoreArgs : RowSource {
+    const uint8_t *kept_mask;     // device or nullptr (all samples): the ctx's count mask (CountArgs::kept_mask)
+    const uint32_t *kept_rank;    // device, with kept_mask: kept samples before each 64-sample chunk
+    const float *weights;         // device, 4-byte aligned
+    uint64_t w_stride;            // floats between the weight rows
+    uint32_t n_columns;           // C, 1 .. 8
+    const float *miss;            // device, 4-byte aligned, or nullptr
+    double *scores;               // device, 8-byte aligned, ordinary device memory (hardware FP64 atomics)
+};
+// slices_per_tile: row ranges per column tile (0 = by shape)
+hipError_t launch_gt_score(const ScoreArgs &a, int slices_per_tile, int num_cus, hipStream_t stream);
 
 // Numeric genotype matrix (gt_matrix.hip): element (j, k) = the pattern of the code of kept sample k in selected row j.
 struct MatrixArgs : RowSource {

@@ -381,6 +381,86 @@ class GtEngine:
               "pgenhip_sample_counts_at")
         return out[: 4 * self.kept_count].view(self.kept_count, 4)
 
+    # -- per-sample weighted dosage sums (polygenic scores) --------------------------------------
+    def sample_scores(
+        self,
+        records: torch.Tensor,
+        weights: torch.Tensor,
+        *,
+        record_stride: Optional[int] = None,
+        variant_idx: Optional[torch.Tensor] = None,
+        miss: Optional[torch.Tensor] = None,
+        out: Optional[torch.Tensor] = None,
+        accumulate: bool = False,
+        flags: int = 0,
+        n_variants: Optional[int] = None,
+        records_offset: int = 0,
+    ) -> torch.Tensor:
+        """Per-sample weighted dosage sums over the selected rows: a ``(K, C)`` float64 CUDA tensor,
+        ``S[k, c] = sum_j float64(weights[j, c]) * D(j, k)`` with D = 0, 1, 2 for codes 0-2 and ``miss[j]`` (0 without ``miss``)
+        for a missing call.  Terms are exact in FP64 and accumulated in FP64 in no fixed order (include/pgen_hip.h).
+
+        ``weights``: float32 CUDA tensor of shape (V, C) or (V,), C <= 8, contiguous along the columns; its row stride is taken
+        from the tensor.  ``miss``: float32 CUDA tensor of V entries, or None.  Both are indexed by the row's position in the
+        selection.  Rows are selected as in ``sample_counts``; ``n_variants`` defaults to ``weights``' rows.  ``out``: optional
+        float64 CUDA tensor of >= K * C entries (written from its first element; nothing else is touched).  ``accumulate``:
+        add to what ``out`` holds instead of overwriting it.  ``flags``: a forced shape (``_capi.SCORE_*``)."""
+        w_stride, n_columns, n_variants = self._score_weights(weights, miss, n_variants)
+        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
+        out = self._scores_out(out, n_columns, accumulate)
+        check(
+            lib.pgenhip_sample_scores(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants,
+                                      _ptr(weights), w_stride, n_columns, _ptr(miss), _ptr(out),
+                                      flags | (_capi.SCORE_ACCUMULATE if accumulate else 0)),
+            "pgenhip_sample_scores",
+        )
+        return out[: self.kept_count * n_columns].view(self.kept_count, n_columns)
+
+    def sample_scores_at(self, base: torch.Tensor, record_off: torch.Tensor, weights: torch.Tensor, *, miss: Optional[torch.Tensor] = None,
+                         out: Optional[torch.Tensor] = None, accumulate: bool = False, flags: int = 0,
+                         n_variants: Optional[int] = None) -> torch.Tensor:
+        """``sample_scores`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
+        w_stride, n_columns, n_variants = self._score_weights(weights, miss, n_variants)
+        n_variants = self._rows_at(base, record_off, n_variants)
+        out = self._scores_out(out, n_columns, accumulate)
+        check(
+            lib.pgenhip_sample_scores_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, _ptr(weights), w_stride, n_columns,
+                                         _ptr(miss), _ptr(out), flags | (_capi.SCORE_ACCUMULATE if accumulate else 0)),
+            "pgenhip_sample_scores_at",
+        )
+        return out[: self.kept_count * n_columns].view(self.kept_count, n_columns)
+
+    def _score_weights(self, weights: torch.Tensor, miss: Optional[torch.Tensor], n_variants: Optional[int]) -> tuple[int, int, int]:
+        """Checks ``weights`` / ``miss`` and returns ``(w_stride, n_columns, n_variants)``."""
+        if not weights.is_cuda or weights.device.index != self.device:
+            raise ValueError(f"weights must live on cuda:{self.device}")
+        if weights.dtype != torch.float32 or weights.dim() not in (1, 2):
+            raise ValueError("weights must be a float32 tensor of shape (V, C) or (V,)")
+        rows = weights.shape[0]
+        n_columns = weights.shape[1] if weights.dim() == 2 else 1
+        if weights.dim() == 2 and n_columns > 1 and weights.stride(1) != 1:
+            raise ValueError("weights must be contiguous along its columns")
+        w_stride = weights.stride(0) if rows > 1 else n_columns
+        if n_variants is None:
+            n_variants = rows
+        if rows < n_variants:
+            raise ValueError("weights has fewer than n_variants rows")
+        if miss is not None:
+            self._check_dev(miss, "miss")
+            if miss.dtype != torch.float32 or miss.numel() < n_variants:
+                raise ValueError("miss must be a float32 tensor with >= n_variants entries")
+        return int(w_stride), int(n_columns), int(n_variants)
+
+    def _scores_out(self, out: Optional[torch.Tensor], n_columns: int, accumulate: bool) -> torch.Tensor:
+        need = self.kept_count * n_columns
+        if out is None:
+            make = torch.zeros if accumulate else torch.empty
+            return make(max(need, 1), dtype=torch.float64, device=self.torch_device)
+        self._check_dev(out, "out")
+        if out.dtype != torch.float64 or out.numel() < need:
+            raise ValueError("out must be a float64 tensor with >= K * C entries")
+        return out.view(-1)
+
     # -- numeric genotype matrix ---------------------------------------------------------------
     def decode_matrix(
         self,

@@ -14,6 +14,9 @@
 // `pgen-hip export <PFILE_PREFIX> -o|--out <OUT_PREFIX> [--format pgen|bed] [--include-var <EXPR>] [--include-sam <EXPR>]` (not in the
 // reference): the kept variants and samples written back as OUT_PREFIX.pgen / .pvar / .psam (fixed-width), or as PLINK 1 .bed / .bim /
 // .fam; the records are packed on the GPU.
+// `pgen-hip score <PFILE_PREFIX> --weights <FILE> [--no-mean-imputation] [--avg] [--include-var <EXPR>] [--include-sam <EXPR>]
+// [-o|--out <FILE>]` (not in the reference): polygenic scores of the kept samples (plink2 --score), the weighted dosage sums of the
+// variants FILE names among the kept ones, summed on the GPU in FP64.
 // Additions (opt-in, not in the reference): --gpus <N>, --block-mib <M>, --launch-mib <M>, --filter-threads <T>, --stats, --dry-run
 // (filter: write the VCF header only and report the body geometry; needs no GPU); BGZF output (`-o x.vcf.gz` or --bgzf,
 // --bgzf-level <1-9>, --compress-threads <T>) and `pgen-hip bgzf <IN> <OUT>`, the same writer on a file.
@@ -83,6 +86,7 @@ const char *kUsage =
     "  filter  Filters the pgen, outputting to a VCF\n"
     "  freq    Per-variant genotype counts of the kept samples, outputting to stdout\n"
     "  sample-counts  Per-sample genotype counts over the kept variants, outputting to stdout\n"
+    "  score   Polygenic scores of the kept samples from a weights file, outputting to stdout\n"
     "  matrix  Numeric genotype matrix of the kept variants and samples, outputting to a NumPy .npy file\n"
     "  ld      Pairwise r^2 of the kept variants inside a sliding window, outputting to stdout\n"
     "  export  Writes the kept variants and samples back as a .pgen (or PLINK 1 .bed) fileset\n"
@@ -99,6 +103,13 @@ const char *kUsage =
     "       [--gpus <N>] [--shards <S>] [--block-mib <M>] [--read-threads <T>] [--filter-threads <T>] [--stats]\n"
     "       one line per kept sample in psam order: IID HOM_REF_CT HET_CT HOM_ALT_CT MISSING_CT (the counts of 0/0, 0/1, 1/1 and\n"
     "       ./. over the kept variants; no byte parity with plink2's .scount / .smiss is claimed)\n"
+    "score  <PFILE_PREFIX> --weights <FILE> [--no-mean-imputation] [--avg] [--include-var <VAR_QUERY>] [--include-sam <SAM_QUERY>] [-o, --out <OUT_FILE>]\n"
+    "       [--gpus <N>] [--shards <S>] [--block-mib <M>] [--read-threads <T>] [--filter-threads <T>] [--stats]\n"
+    "       FILE: tab-separated with a header line: variant ID, effect allele, then one weight column per score (the header cell names it).\n"
+    "       Rows are matched by ID among the kept variants; effect allele == ALT scores w * dosage, == REF w * (2 - dosage), another\n"
+    "       allele or an ID that is not kept skips the row.  A missing call counts as the variant's mean dosage over the kept samples\n"
+    "       (--no-mean-imputation: as 0).  One line per kept sample in psam order: IID ALLELE_CT DENOM <NAME>_SUM ... (--avg: <NAME>_AVG =\n"
+    "       SUM / DENOM); weights are rounded to f32, sums are FP64; no byte or digit parity with plink2's .sscore is claimed\n"
     "matrix <PFILE_PREFIX> [--include-var <VAR_QUERY>] [--include-sam <SAM_QUERY>] [--dtype i8|f16|f32] [--missing <X>] [--sample-major]\n"
     "       -o, --out <OUT_FILE.npy> [--gpus <N>] [--shards <S>] [--block-mib <M>] [--read-threads <T>] [--filter-threads <T>] [--stats]\n"
     "       NumPy .npy (version 1.0, C order) of shape (variants kept, samples kept), or (samples, variants) with --sample-major:\n"
@@ -398,6 +409,23 @@ int main(int argc, char **argv)
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
             const OutputStats st = pfile.output_sample_counts(a.get("include-sam"), a.get("include-var"), a.get("out").value_or(""), output_options(a));
             if (a.has("stats")) print_stats(st, t_main);
+            return 0;
+        }
+        if (cmd == "score") {
+            Args a = parse(argc, argv, 2, {{"weights", 0}, {"include-var", 0}, {"include-sam", 0}, {"out", 'o'}, {"gpus", 0}, {"shards", 0}, {"block-mib", 0}, {"read-threads", 0}, {"filter-threads", 0}},
+                           {{"stats", 0}, {"no-mean-imputation", 0}, {"avg", 0}});
+            if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
+            if (!a.has("weights") || a.get("weights")->empty()) usage_error("the following required arguments were not provided: --weights <FILE>");
+            ScoreOptions s;
+            s.mean_imputation = !a.has("no-mean-imputation");
+            s.average = a.has("avg");
+            const Pfile pfile = Pfile::from_prefix(a.positional[0]);
+            const OutputStats st = pfile.output_score(a.get("include-sam"), a.get("include-var"), *a.get("weights"), a.get("out").value_or(""), s, output_options(a));
+            if (a.has("stats")) {
+                std::fprintf(stderr, "{\"weights_matched\": %llu, \"weights_flipped\": %llu, \"weights_skipped\": %llu}\n",
+                             (unsigned long long)st.score_matched, (unsigned long long)st.score_flipped, (unsigned long long)st.score_skipped);
+                print_stats(st, t_main);
+            }
             return 0;
         }
         if (cmd == "matrix") {

@@ -877,8 +877,8 @@ void append_u64(std::string &s, uint64_t v)
 // records are staged as they lie on disk (a span grows over gaps of up to R bytes, so a block stages at most 2R bytes per
 // variant) and counted through their offsets in the staged bytes (the `_at` entry points).
 // make(ctx, bv) builds a shard's counter, which provides
-//   launch(ctx, d_rec, d_off, nv, nh): queue the block's count launch over its nv rows (and the nh halo rows staged behind them;
-//     d_off NULL: records packed at stride R);
+//   launch(ctx, d_rec, d_off, b0, nv, nh): queue the block's count launch over its nv rows (and the nh halo rows staged behind
+//     them; d_off NULL: records packed at stride R; b0: index of the block's first variant in `vars`);
 //   copy(ctx, nv): queue what goes back after it (outside the kernel timer);
 //   collect(b0, nv): the block's work on the stream has finished (b0: index of its first variant in `vars`);
 //   finish(ctx): after the shard's last block has been collected.
@@ -950,7 +950,7 @@ void count_blocks(const Pfile &pf, const Pfile::IdxRecords &vars, const KeptSamp
             check(pgenhip_memcpy_h2d(ctx.get(), d_rec, dst, staged), "H2D records");
             if (vw) check(pgenhip_memcpy_h2d(ctx.get(), d_off, h_off[k % 2], nt * sizeof(uint64_t)), "H2D record offsets");
             check(pgenhip_timer_start(ctx.get()), "timer");
-            counter.launch(ctx.get(), d_rec, d_off, (uint32_t)nv, (uint32_t)nh);
+            counter.launch(ctx.get(), d_rec, d_off, b0, (uint32_t)nv, (uint32_t)nh);
             check(pgenhip_timer_mark(ctx.get()), "timer");
             counter.copy(ctx.get(), nv);
             prev_b0 = b0;
@@ -968,7 +968,7 @@ struct VariantCounter {
     uint32_t R;
     std::vector<uint32_t> &counts;   // 4 per kept variant
     uint32_t *d_counts, *h_counts;
-    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, uint32_t nv, uint32_t) const
+    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, size_t, uint32_t nv, uint32_t) const
     {
         if (d_off)
             check(pgenhip_genotype_counts_at(ctx, d_rec, d_off, nv, d_counts, PGENHIP_COUNT_AUTO), "pgenhip_genotype_counts_at");
@@ -989,7 +989,7 @@ struct SampleCounter {
     std::mutex &mu;
     uint32_t *d_counts, *h_counts;
     bool first = true;
-    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, uint32_t nv, uint32_t)
+    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, size_t, uint32_t nv, uint32_t)
     {
         const uint32_t flags = PGENHIP_SCOUNT_AUTO | (first ? 0u : PGENHIP_SCOUNT_ACCUMULATE);
         first = false;
@@ -1009,6 +1009,71 @@ struct SampleCounter {
     }
 };
 
+// score's counter: per block the matched rows' weights go up, the rows' mean dosages are computed from their genotype counts
+// (mean imputation) and go up as the miss values, and the score kernel adds the block into the shard's K x C doubles, eight
+// columns per launch; the sample counts of the same rows accumulate beside them (the per-sample missing count).  Both come back
+// once per shard and the host sums the shards in FP64 / u64.
+struct ScoreCounter {
+    uint32_t R;
+    size_t K, C;                      // kept samples, score columns
+    bool impute;
+    const std::vector<float> &w;      // matched rows x C, the sign of REF-effect rows flipped
+    std::vector<double> &sums;        // K x C
+    std::vector<uint64_t> &missing;   // K
+    std::mutex &mu;
+    float *d_w, *d_miss, *h_miss;
+    uint32_t *d_gc, *h_gc, *d_counts, *h_counts;
+    double *d_scores, *h_scores;
+    bool first = true;
+    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, size_t b0, uint32_t nv, uint32_t)
+    {
+        if (impute) {
+            if (d_off)
+                check(pgenhip_genotype_counts_at(ctx, d_rec, d_off, nv, d_gc, PGENHIP_COUNT_AUTO), "pgenhip_genotype_counts_at");
+            else
+                check(pgenhip_genotype_counts(ctx, d_rec, R, nullptr, nv, d_gc, PGENHIP_COUNT_AUTO), "pgenhip_genotype_counts");
+            check(pgenhip_memcpy_d2h(ctx, h_gc, d_gc, (size_t)nv * 16), "D2H counts");
+            check(pgenhip_wait(ctx), "pgenhip_wait");
+            for (uint32_t j = 0; j < nv; j++) {
+                const uint64_t c0 = h_gc[4 * j], c1 = h_gc[4 * j + 1], c2 = h_gc[4 * j + 2], called = c0 + c1 + c2;
+                h_miss[j] = called ? (float)((double)(c1 + 2 * c2) / (double)called) : 0.f;
+            }
+            check(pgenhip_memcpy_h2d(ctx, d_miss, h_miss, (size_t)nv * sizeof(float)), "H2D mean dosages");
+        }
+        check(pgenhip_memcpy_h2d(ctx, d_w, w.data() + b0 * C, (size_t)nv * C * sizeof(float)), "H2D weights");
+        const uint32_t acc = first ? 0u : PGENHIP_SCORE_ACCUMULATE;
+        for (size_t c0 = 0; c0 < C; c0 += PGENHIP_SCORE_MAX_COLUMNS) {
+            const uint32_t cg = (uint32_t)std::min<size_t>(PGENHIP_SCORE_MAX_COLUMNS, C - c0);
+            double *dst = d_scores + K * c0;   // group g's K x cg block behind the blocks of the groups before it
+            if (d_off)
+                check(pgenhip_sample_scores_at(ctx, d_rec, d_off, nv, d_w + c0, C, cg, impute ? d_miss : nullptr, dst, PGENHIP_SCORE_AUTO | acc), "pgenhip_sample_scores_at");
+            else
+                check(pgenhip_sample_scores(ctx, d_rec, R, nullptr, nv, d_w + c0, C, cg, impute ? d_miss : nullptr, dst, PGENHIP_SCORE_AUTO | acc), "pgenhip_sample_scores");
+        }
+        const uint32_t cflags = PGENHIP_SCOUNT_AUTO | (first ? 0u : PGENHIP_SCOUNT_ACCUMULATE);
+        if (d_off)
+            check(pgenhip_sample_counts_at(ctx, d_rec, d_off, nv, d_counts, cflags), "pgenhip_sample_counts_at");
+        else
+            check(pgenhip_sample_counts(ctx, d_rec, R, nullptr, nv, d_counts, cflags), "pgenhip_sample_counts");
+        first = false;
+    }
+    void copy(pgenhip_ctx *, size_t) const {}
+    void collect(size_t, size_t) const {}
+    void finish(pgenhip_ctx *ctx) const
+    {
+        check(pgenhip_memcpy_d2h(ctx, h_scores, d_scores, K * C * sizeof(double)), "D2H scores");
+        check(pgenhip_memcpy_d2h(ctx, h_counts, d_counts, K * 16), "D2H counts");
+        check(pgenhip_wait(ctx), "pgenhip_wait");
+        std::lock_guard<std::mutex> lk(mu);
+        for (size_t c0 = 0; c0 < C; c0 += PGENHIP_SCORE_MAX_COLUMNS) {
+            const size_t cg = std::min<size_t>(PGENHIP_SCORE_MAX_COLUMNS, C - c0);
+            for (size_t k = 0; k < K; k++)
+                for (size_t c = 0; c < cg; c++) sums[k * C + c0 + c] += h_scores[K * c0 + k * cg + c];
+        }
+        for (size_t k = 0; k < K; k++) missing[k] += h_counts[4 * k + 3];
+    }
+};
+
 // matrix's "counter": every block is decoded into one device buffer, copied back and written to its place in the .npy file.
 // Variant-major: a block is nv consecutive rows of the file, one pwrite.  Sample-major: a block is a column band, K pieces of
 // nv elements, written from a few threads.
@@ -1022,7 +1087,7 @@ struct MatrixWriter {
     int fd;
     const std::string &path;
     uint64_t data_off;
-    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, uint32_t nv, uint32_t) const
+    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, size_t, uint32_t nv, uint32_t) const
     {
         const uint32_t flags = PGENHIP_MATRIX_AUTO | (m.sample_major ? PGENHIP_MATRIX_SAMPLE_MAJOR : 0u);
         const uint64_t stride = m.sample_major ? pitch : (uint64_t)K * m.elem_bytes;
@@ -1056,7 +1121,7 @@ struct PackWriter {
     int fd;
     const std::string &path;
     uint64_t data_off;
-    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, uint32_t nv, uint32_t) const
+    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, size_t, uint32_t nv, uint32_t) const
     {
         if (d_off)
             check(pgenhip_pack_records_at(ctx, d_rec, d_off, nv, d_out, RK, code_map, PGENHIP_PACK_AUTO), "pgenhip_pack_records_at");
@@ -1101,7 +1166,7 @@ struct PairWriter {
     std::mutex &mu;
     uint8_t *d_out, *h_out;
     size_t entry_bytes() const { return ld.counts ? 64u : 4u; }
-    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, uint32_t nv, uint32_t nh) const
+    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, size_t, uint32_t nv, uint32_t nh) const
     {
         const uint32_t flags = ld.counts ? PGENHIP_PAIR_TABLE : PGENHIP_PAIR_R2;
         if (d_off)
@@ -1257,6 +1322,171 @@ OutputStats Pfile::output_sample_counts(const std::optional<std::string> &sam_qu
         for (int c = 0; c < 4; c++) {
             text += '\t';
             append_u64(text, totals[4 * k + (size_t)c]);
+        }
+        text += '\n';
+    }
+    st.body_bytes = text.size() - st.header_bytes;
+    st.file_bytes = text.size();
+    write_text(text, filename);
+    st.seconds_body = now_s() - t_body;
+    return st;
+}
+
+ScoreWeights read_score_weights(const std::string &path)
+{
+    const std::string data = read_file(path);
+    ScoreWeights sw;
+    TsvReader reader(data, !data.empty() && data[0] == '#' ? 1 : 0);
+    const StringRecord &head = reader.headers();
+    if (head.size() < 3) throw PfileError(path + " line 1: a weights file has an ID column, an effect allele column and at least one score column");
+    sw.names.assign(head.begin() + 2, head.end());
+    const size_t C = sw.names.size();
+    // the line a record starts on: the newlines in front of it, counted as the reader moves on
+    size_t counted = 0, line = 1;
+    auto line_at = [&](size_t pos) {
+        for (; counted < pos; counted++) line += data[counted] == '\n';
+        for (size_t p = pos; p < data.size() && (data[p] == '\n' || data[p] == '\r'); p++) {   // the empty lines the reader skips
+            line += data[p] == '\n';
+            counted = p + 1;
+        }
+        return line;
+    };
+    std::map<std::string, size_t> seen;   // ID -> line
+    StringRecord rec;
+    for (;;) {
+        const size_t at = line_at(reader.position());
+        bool more;
+        try {
+            more = reader.next(rec);
+        } catch (const CsvError &) {
+            throw PfileError(path + " line " + std::to_string(at) + ": expected " + std::to_string(C + 2) + " tab-separated cells like the header's");
+        }
+        if (!more) break;
+        const auto dup = seen.emplace(rec[0], at);
+        if (!dup.second)
+            throw PfileError(path + " line " + std::to_string(at) + ": variant ID '" + rec[0] + "' occurs twice (first on line " + std::to_string(dup.first->second) + ")");
+        for (size_t c = 0; c < C; c++) {
+            const std::string &cell = rec[2 + c];
+            char *end = nullptr;
+            errno = 0;
+            const double x = std::strtod(cell.c_str(), &end);
+            const bool fits = std::isfinite(x) && std::fabs(x) < 0x1.ffffffp127;   // rounds to a finite f32
+            const float f = fits ? (float)x : 0.f;                                   // rounded to f32 once, here
+            if (cell.empty() || *end != '\0' || !fits)
+                throw PfileError(path + " line " + std::to_string(at) + ": weight '" + cell + "' of score " + sw.names[c] + " is not a finite number");
+            sw.w.push_back(f);
+        }
+        sw.ids.push_back(rec[0]);
+        sw.alleles.push_back(rec[1]);
+        sw.lines.push_back(at);
+    }
+    return sw;
+}
+
+OutputStats Pfile::output_score(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
+                                const std::string &weights_file, const std::string &filename, const ScoreOptions &sopt, const OutputOptions &opt) const
+{
+    OutputStats st;
+    const double t0 = now_s();
+    const ScoreWeights sw = read_score_weights(weights_file);
+    const size_t C = sw.names.size();
+    Selection sel = select(sam_query, var_query, opt.filter_threads);
+    size_t iid = sel.sam_header.size();   // vcf_header's rule (:114-126): the first column named IID
+    for (size_t c = 0; c < sel.sam_header.size(); c++) {
+        if (sel.sam_header[c] == "IID") {
+            iid = c;
+            break;
+        }
+    }
+    if (iid == sel.sam_header.size()) throw PfileError("IID not among the headers of " + psam_path());
+    static const char *const kCols[3] = {"ID", "REF", "ALT"};
+    size_t col[3];
+    for (int c = 0; c < 3; c++) {
+        col[c] = std::find(sel.var_header.begin(), sel.var_header.end(), std::string(kCols[c])) - sel.var_header.begin();
+        if (col[c] == sel.var_header.size()) throw PfileError(std::string(kCols[c]) + " not among the headers of " + pvar_path());
+    }
+
+    // the kept variants the file names, in the .pgen's order: they are the selection of every launch
+    std::map<std::string, size_t> row_of;
+    for (size_t i = 0; i < sw.ids.size(); i++) row_of.emplace(sw.ids[i], i);
+    std::vector<char> used(sw.ids.size(), 0);
+    Selection msel;
+    std::vector<float> w;                 // matched rows x C, REF-effect rows negated
+    std::vector<double> constant(C, 0.0); // the 2w of the REF-effect rows, added to every sample
+    uint64_t flipped = 0, mismatched = 0;
+    for (const auto &vr : sel.var_idx_rcds) {
+        const auto it = row_of.find(vr.second.at(col[0]));
+        if (it == row_of.end()) continue;
+        const size_t i = it->second;
+        if (used[i])
+            throw PfileError(weights_file + " line " + std::to_string(sw.lines[i]) + ": variant ID '" + sw.ids[i] + "' occurs twice among the kept variants of " + pvar_path());
+        used[i] = 1;
+        const bool alt = sw.alleles[i] == vr.second.at(col[2]), ref = !alt && sw.alleles[i] == vr.second.at(col[1]);
+        if (!alt && !ref) {
+            mismatched++;
+            continue;
+        }
+        for (size_t c = 0; c < C; c++) {
+            const float x = sw.w[i * C + c];
+            w.push_back(ref ? -x : x);
+            if (ref) constant[c] += 2.0 * (double)x;
+        }
+        flipped += ref;
+        msel.var_idx_rcds.emplace_back(vr.first, StringRecord());
+    }
+    const size_t M = msel.var_idx_rcds.size();
+    st.score_matched = M;
+    st.score_flipped = flipped;
+    st.score_skipped = sw.ids.size() - M;
+    if (M == 0)
+        throw PfileError("no row of " + weights_file + " names a kept variant of " + pvar_path() + " by ID with its REF or ALT allele (" +
+                         std::to_string(sw.ids.size()) + " rows, " + std::to_string(mismatched) + " with another allele)");
+    msel.sam_idx_rcs = std::move(sel.sam_idx_rcs);
+    st.seconds_filter = now_s() - t0;
+
+    const KeptSamples kept = check_selection(*this, msel);
+    const size_t K = kept.rows.size();
+    st.variants = M;
+    st.samples_kept = K;
+
+    std::vector<double> sums(K * C, 0.0);
+    std::vector<uint64_t> missing(K, 0u);
+    const double t_body = now_s();
+    if (K != 0) {   // else the header alone and no device is touched
+        const uint32_t R = variant_record_size();
+        std::mutex mu;
+        count_blocks(*this, msel.var_idx_rcds, kept, opt, "no HIP device: the score path has no CPU fallback", st, [&](DeviceCtx &ctx, uint64_t bv) {
+            const size_t b = (size_t)bv;
+            return ScoreCounter{R, K, C, sopt.mean_imputation, w, sums, missing, mu,
+                                ctx.device<float>(b * C * sizeof(float), "device weights"), ctx.device<float>(b * sizeof(float), "device mean dosages"),
+                                ctx.pinned<float>(b * sizeof(float), "pinned mean dosages"),
+                                ctx.device<uint32_t>(16 * b, "device variant counts"), ctx.pinned<uint32_t>(16 * b, "pinned variant counts"),
+                                ctx.device<uint32_t>(16 * K, "device counts"), ctx.pinned<uint32_t>(16 * K, "pinned counts"),
+                                ctx.device<double>(K * C * sizeof(double), "device scores"), ctx.pinned<double>(K * C * sizeof(double), "pinned scores")};
+        });
+    }
+
+    std::string text = "#IID\tALLELE_CT\tDENOM";
+    for (const std::string &name : sw.names) text += "\t" + name + (sopt.average ? "_AVG" : "_SUM");
+    text += '\n';
+    st.header_bytes = text.size();
+    char buf[64];
+    for (size_t k = 0; k < K; k++) {
+        const uint64_t allele_ct = 2 * ((uint64_t)M - missing[k]), denom = sopt.mean_imputation ? 2 * (uint64_t)M : allele_ct;
+        text += msel.sam_idx_rcs[k].second.at(iid);
+        text += '\t';
+        append_u64(text, allele_ct);
+        text += '\t';
+        append_u64(text, denom);
+        for (size_t c = 0; c < C; c++) {
+            const double sum = sums[k * C + c] + constant[c];
+            text += '\t';
+            if (sopt.average && denom == 0) {
+                text += "nan";
+            } else {
+                std::snprintf(buf, sizeof buf, "%.12g", sopt.average ? sum / (double)denom : sum);
+                text += buf;
+            }
         }
         text += '\n';
     }

@@ -101,10 +101,28 @@ struct ExportOptions {
     bool bed = false;                 // PLINK 1 .bed / .bim / .fam instead of .pgen / .pvar / .psam
 };
 
+// `score`: how missing calls count and what is printed
+struct ScoreOptions {
+    bool mean_imputation = true;      // a missing call counts as the variant's mean dosage over the kept samples called (else as 0)
+    bool average = false;             // --avg: <NAME>_AVG = SUM / DENOM instead of <NAME>_SUM
+};
+
+// A `score` weights file: tab-separated, a header line (a leading '#' allowed), then one row per variant: ID, effect allele, one
+// weight per score.  read_score_weights throws a PfileError that names the line for a weight that is not a finite number (after
+// rounding to f32), a row with another number of cells than the header, and an ID that occurs twice.
+struct ScoreWeights {
+    std::vector<std::string> names;          // the score columns' header cells
+    std::vector<std::string> ids, alleles;   // per row
+    std::vector<float> w;                    // rows x names.size(), rounded to f32 once, at parse time
+    std::vector<size_t> lines;               // the file line each row starts on
+};
+ScoreWeights read_score_weights(const std::string &path);
+
 struct OutputStats {
     uint64_t variants = 0, samples_kept = 0, header_bytes = 0, body_bytes = 0;   // header / body: bytes of VCF text
     uint64_t file_bytes = 0;                                                     // what the output file holds (BGZF: compressed)
     double seconds_filter = 0, seconds_body = 0, seconds_kernel = 0;
+    uint64_t score_matched = 0, score_flipped = 0, score_skipped = 0;            // `score`: weights rows used, of them REF-effect rows, rows not used
     double seconds_setup = 0;   // inside seconds_body: HIP runtime start, contexts, device and pinned allocations of the slowest shard, before its first block is staged
 };
 
@@ -177,6 +195,22 @@ class Pfile {
     // A psam without an IID column is vcf_header's error.  filename empty: stdout.
     OutputStats output_sample_counts(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
                                      const std::string &filename, const OutputOptions &opt = OutputOptions()) const;
+
+    // `score` (not in the reference): polygenic scores of the kept samples, S[k, c] = sum over the matched variants of w[j, c] * dosage
+    // (plink2 --score; no byte or digit parity with its .sscore is claimed).  The weights file's rows are matched by the .pvar ID
+    // among the kept variants: effect allele == ALT uses the weight as is, == REF scores w * (2 - dosage) (-w on the device, the
+    // constant sum of 2w added on the host in FP64), neither allele or an ID that is not kept skips the row; a matched ID that
+    // occurs twice among the kept variants is an error that names the line, no matched row at all an error before any device is
+    // touched.  Only the matched variants are staged (freq's block loop and shards); per block pgenhip_genotype_counts gives the
+    // mean dosage of every row (mean imputation: miss[j] = (float)((c1 + 2 c2) / (c0 + c1 + c2)), 0 when nobody is called),
+    // pgenhip_sample_scores adds the block into K x C doubles on the device, at most PGENHIP_SCORE_MAX_COLUMNS columns per launch,
+    // and pgenhip_sample_counts accumulates the per-sample missing count; both come back once per shard and shards are summed in
+    // FP64.  One line per kept sample in psam order: IID, ALLELE_CT = 2 (M - missing), DENOM (2 M under mean imputation, else
+    // ALLELE_CT), then <NAME>_SUM per score (%.12g), or with average <NAME>_AVG = SUM / DENOM (nan when DENOM is 0).  No kept
+    // sample: the header alone, no device.  filename empty: stdout.
+    OutputStats output_score(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
+                             const std::string &weights_file, const std::string &filename, const ScoreOptions &sopt,
+                             const OutputOptions &opt = OutputOptions()) const;
 
     // `matrix` (not in the reference): the additive-coded genotype matrix of the kept variants and samples as a NumPy .npy file
     // (version 1.0, C order, data on a multiple of 64 bytes), decoded on the GPU(s) (pgenhip_decode_matrix / _at) block by block and
