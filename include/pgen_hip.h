@@ -368,6 +368,42 @@ int pgenhip_pair_stats(pgenhip_ctx *ctx, const void *d_records, uint64_t record_
 int pgenhip_pair_stats_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
                           uint32_t n_left, uint32_t window, void *d_out, uint32_t flags);
 
+/* ---- pairwise sample tables (device-resident, asynchronous on the ctx stream) ----
+ * The transpose of pgenhip_pair_stats: pairs of kept SAMPLES, summed over the selected rows.  Rows are selected exactly as in
+ * pgenhip_sample_counts / pgenhip_sample_counts_at (by stride with record_stride >= R or n_variants <= 1, through d_variant_idx, or
+ * through d_record_off; any byte alignment; a gather that repeats a row counts it twice).  [a_begin, a_begin + a_count) and
+ * [b_begin, b_begin + b_count) are ranges of RANKS in the ctx's kept list (a rank is the sample index when all samples are kept);
+ * they may be equal, overlap, be disjoint or come in either order.  For a = a_begin + i and b = b_begin + l sixteen u32 go to
+ *     d_out[16 * (i * b_count + l) + 4 * x + y] = the number of selected rows in which sample a has code x and sample b has code y
+ * with codes 0 hom-ref, 1 het, 2 hom-alt, 3 missing (the order of the count entry points).  The sums over y are a's
+ * pgenhip_sample_counts over the same rows, the sums over x are b's, a table sums to n_variants, T(a, a) is diagonal and
+ * T(b, a)[y][x] == T(a, b)[x][y], so a host that covers K x K with rectangles needs the upper block triangle only.  The library
+ * does not interpret the tables: KING kinship, IBS distances and X^T X are host arithmetic on them.  The pad bits of a record's
+ * last byte and samples >= N are never read as samples.
+ *   - Without PGENHIP_SPAIR_ACCUMULATE the call overwrites the 16 * a_count * b_count entries (zeros when n_variants == 0).  With it
+ *     the counts are added to what d_out holds, so a host sums blocks of rows in place; n_variants == 0 is then a no-op.  Counts
+ *     are exact integers, reproducible from run to run whatever order blocks combine in, and wrap modulo 2^32 only past 2^32 - 1
+ *     counted rows.  Nothing outside the entries is written; a_count == 0 or b_count == 0 writes nothing and returns PGENHIP_OK.
+ *   - PGENHIP_ERR_BAD_ARG: a range that ends past K; d_out NULL or not 16-byte aligned when at least one entry exists; unknown flag
+ *     bits or shape ids.  PGENHIP_ERR_TOO_LARGE, before any launch: a_count * b_count * 64 >= 2^52, and the record byte offsets that
+ *     pgenhip_decode_matrix refuses.
+ * Same launch contract as pgenhip_sample_counts: device pointers only, no allocation, no synchronisation, queued on the ctx
+ * stream, graph-capturable (the overwrite is a hipMemsetAsync ahead of the kernel).  The kernels use no work-queue counters, so these
+ * launches do not count against PGENHIP_LAUNCHES_IN_FLIGHT.
+ * flags: a shape (PGENHIP_SPAIR_AUTO or a forced one; both forced shapes take every legal call) | PGENHIP_SPAIR_ACCUMULATE. */
+#define PGENHIP_SPAIR_AUTO 0u
+#define PGENHIP_SPAIR_GENERAL 1u      /* a lane per pair, row by row: the correctness baseline */
+#define PGENHIP_SPAIR_MFMA 2u         /* int8 matrix cores on 0/1 indicator vectors, 64 x 64 samples per block */
+#define PGENHIP_SPAIR_SHAPE_MASK 0xFu
+#define PGENHIP_SPAIR_ACCUMULATE 0x10u
+int pgenhip_sample_pair_stats(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                              uint32_t n_variants, uint32_t a_begin, uint32_t a_count, uint32_t b_begin, uint32_t b_count,
+                              uint32_t *d_out, uint32_t flags);
+/* Same, with the record of row j at d_base + d_record_off[j] (DEVICE array of u64 byte offsets). */
+int pgenhip_sample_pair_stats_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
+                                 uint32_t a_begin, uint32_t a_count, uint32_t b_begin, uint32_t b_count, uint32_t *d_out,
+                                 uint32_t flags);
+
 /* ---- packed records of the kept samples (device-resident, asynchronous on the ctx stream) ----
  * The selection written back as records: row j of the output is the mode-0x02 record of a K-sample file that holds the ctx's kept
  * samples of selected row j, so a host that puts the 12-byte header in front has a .pgen of the subset (src/pfile.rs:172-175 read
@@ -426,6 +462,7 @@ typedef enum pgenhip_knob {
     PGENHIP_KNOB_PAIR_BLOCKS = 19,       /* pairwise kernel: grid size in blocks (default 0 = by shape: the tiles, capped at 16 one-wave blocks per CU); tests force small grids */
     PGENHIP_KNOB_PACK_BLOCKS = 20,       /* pack kernels: grid size in blocks (default 0 = by shape: the work, capped at 8 blocks per CU); tests force small grids */
     PGENHIP_KNOB_SCORE_SLICES = 21,      /* per-sample scores: row ranges per column tile, each summed by one block (default 0 = by shape: as many as fill the chip's resident blocks, of at least 512 rows each); tests put the row count on either side of every plan edge */
+    PGENHIP_KNOB_SPAIR_SLICES = 22,      /* pairwise sample tables: row ranges per sample tile, each summed by one block (default 0 = by shape: as many as fill the chip's resident blocks, of at least 256 rows each); tests put the row count on either side of every slice edge */
     PGENHIP_KNOB_RUNS_ROWS = 7        /* RUNS kernel: rows per work item (default: as many as one wide load / one span holds) */
 } pgenhip_knob;
 int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value);

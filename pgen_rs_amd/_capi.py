@@ -53,6 +53,11 @@ SCORE_AUTO = 0
 SCORE_ROWS = 1
 SCORE_SHAPE_MASK = 0xF
 SCORE_ACCUMULATE = 0x10
+SPAIR_AUTO = 0
+SPAIR_GENERAL = 1
+SPAIR_MFMA = 2
+SPAIR_SHAPE_MASK = 0xF
+SPAIR_ACCUMULATE = 0x10
 MATRIX_AUTO = 0
 MATRIX_GENERAL = 1
 MATRIX_STREAM = 2
@@ -87,6 +92,7 @@ KNOB_MATRIX_BLOCKS = 18
 KNOB_PAIR_BLOCKS = 19
 KNOB_PACK_BLOCKS = 20
 KNOB_SCORE_SLICES = 21
+KNOB_SPAIR_SLICES = 22
 
 
 
@@ -134,6 +140,8 @@ PROTOTYPES = {
     "pgenhip_sample_scores_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]),
     "pgenhip_decode_matrix": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_decode_matrix_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
+    "pgenhip_sample_pair_stats": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
+    "pgenhip_sample_pair_stats_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_pair_stats": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_pair_stats_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_packed_record_size": (C.c_uint32, [ctx_p]),

@@ -823,6 +823,63 @@ int pgenhip_pair_stats_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *
     return pair_stats_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, n_left, window, d_out, flags);
 }
 
+static int sample_pair_stats_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                                  const uint64_t *d_record_off, uint32_t n_variants, uint32_t a_begin, uint32_t a_count,
+                                  uint32_t b_begin, uint32_t b_count, uint32_t *d_out, uint32_t flags)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (flags & ~(PGENHIP_SPAIR_SHAPE_MASK | PGENHIP_SPAIR_ACCUMULATE)) return fail(PGENHIP_ERR_BAD_ARG, "unknown sample_pair_stats flag");
+    const uint32_t shape = flags & PGENHIP_SPAIR_SHAPE_MASK;
+    if (shape > PGENHIP_SPAIR_MFMA) return fail(PGENHIP_ERR_BAD_ARG, "sample_pair_stats supports shapes AUTO, GENERAL and MFMA");
+    const bool accumulate = (flags & PGENHIP_SPAIR_ACCUMULATE) != 0u;
+    const uint64_t K = ctx->kept_count;
+    if ((uint64_t)a_begin + a_count > K || (uint64_t)b_begin + b_count > K) return fail(PGENHIP_ERR_BAD_ARG, "a sample range ends past the kept count");
+    const uint64_t pairs = (uint64_t)a_count * b_count;
+    if (pairs != 0u && !d_out) return fail(PGENHIP_ERR_BAD_ARG, "d_out is NULL");
+    if (pairs != 0u && ((uintptr_t)d_out & 15u)) return fail(PGENHIP_ERR_BAD_ARG, "d_out is not 16-byte aligned");
+    // byte offsets of table entries and records are 64-bit arithmetic in the kernels; the bounds are decode_matrix's (2^52 bytes)
+    constexpr uint64_t kMaxSpan = 1ull << 52;
+    const bool by_stride = n_variants > 1 && !d_record_off;
+    if (pairs >= kMaxSpan / 64u || (by_stride && !d_variant_idx && record_stride >= kMaxSpan / n_variants) ||
+        (by_stride && d_variant_idx && record_stride >= kMaxSpan))
+        return fail(PGENHIP_ERR_TOO_LARGE, "sample_pair_stats offsets do not fit the kernels' index types");
+    if (pairs == 0u) return PGENHIP_OK;   // nothing to write
+    SpairArgs a;
+    rc = select_rows(ctx, a, d_records, record_stride, d_variant_idx, d_record_off, n_variants);
+    if (rc) return rc;
+    if (!accumulate) HIP_TRY(hipMemsetAsync(d_out, 0, 64u * pairs, ctx->stream));   // the kernels only add
+    if (n_variants == 0) return PGENHIP_OK;
+    a.kept_idx = (!ctx->subset || ctx->identity) ? nullptr : ctx->d_kept;
+    a.a_begin = a_begin;
+    a.a_count = a_count;
+    a.b_begin = b_begin;
+    a.b_count = b_count;
+    a.out = d_out;
+    // AUTO: the matrix-core shape.  It measured 2.8-49 x ahead of GENERAL on every shape of tools/spair_bench.py (DESIGN.md §15,
+    // profiles/r10_spair); ranges of a few pairs, where a 64 x 64 tile is mostly padding, were not measured
+    const bool mfma = shape != PGENHIP_SPAIR_GENERAL;
+    if (mfma)
+        HIP_TRY(launch_gt_spair_mfma(a, ctx->tune.spair_slices, ctx->num_cus, ctx->stream));
+    else
+        HIP_TRY(launch_gt_spair_general(a, ctx->tune.spair_slices, ctx->num_cus, ctx->stream));
+    return PGENHIP_OK;
+}
+
+int pgenhip_sample_pair_stats(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                              uint32_t n_variants, uint32_t a_begin, uint32_t a_count, uint32_t b_begin, uint32_t b_count,
+                              uint32_t *d_out, uint32_t flags)
+{
+    return sample_pair_stats_core(ctx, d_records, record_stride, d_variant_idx, nullptr, n_variants, a_begin, a_count, b_begin, b_count, d_out, flags);
+}
+
+int pgenhip_sample_pair_stats_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
+                                 uint32_t a_begin, uint32_t a_count, uint32_t b_begin, uint32_t b_count, uint32_t *d_out, uint32_t flags)
+{
+    if (const int rc = check_record_off(ctx, d_record_off, n_variants)) return rc;
+    return sample_pair_stats_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, a_begin, a_count, b_begin, b_count, d_out, flags);
+}
+
 static int pack_records_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
                              const uint64_t *d_record_off, uint32_t n_variants, void *d_out, uint64_t out_stride,
                              const uint8_t *code_map, uint32_t flags)
@@ -914,6 +971,7 @@ int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)
         case PGENHIP_KNOB_MATRIX_BLOCKS: t.matrix_blocks = value > 0 ? value : d.matrix_blocks; break;
         case PGENHIP_KNOB_PAIR_BLOCKS: t.pair_blocks = value > 0 ? value : d.pair_blocks; break;
         case PGENHIP_KNOB_PACK_BLOCKS: t.pack_blocks = value > 0 ? value : d.pack_blocks; break;
+        case PGENHIP_KNOB_SPAIR_SLICES: t.spair_slices = value > 0 ? value : d.spair_slices; break;
         default: return fail(PGENHIP_ERR_BAD_ARG, "unknown knob");
     }
     return PGENHIP_OK;

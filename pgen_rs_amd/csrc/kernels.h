@@ -57,6 +57,7 @@ struct Tuning {
     int matrix_blocks = 0;         // genotype matrix kernels: grid size in blocks (0 = by shape, capped per CU)
     int pair_blocks = 0;           // pairwise kernel: grid size in blocks (0 = by shape, capped per CU)
     int pack_blocks = 0;           // pack kernels: grid size in blocks (0 = by shape, capped per CU)
+    int spair_slices = 0;          // pairwise sample tables: row ranges per sample tile (0 = by shape: the chip's resident blocks, at least 256 rows each)
 };
 
 // rows are gathered (variant list or byte offsets): the HAS_VIDX instantiations
@@ -179,6 +180,18 @@ struct PairArgs : RowSource {
 };
 // blocks: forced grid size (0 = by shape; tests force small grids to walk the grid-stride loop)
 hipError_t launch_gt_pair(const PairArgs &a, int blocks, int num_cus, hipStream_t stream);
+
+// Pairwise sample tables (gt_spair.hip): for a = a_begin + i, b = b_begin + l (ranks in the kept list) the number of selected rows
+// in which a has code x and b has code y, ADDED to out[16 * (i * b_count + l) + 4 * x + y] (u32, modular).
+struct SpairArgs : RowSource {
+    const uint32_t *kept_idx;     // device or nullptr (all samples, or an identity list): rank -> sample
+    uint32_t a_begin, a_count;    // a_begin + a_count <= K
+    uint32_t b_begin, b_count;    // b_begin + b_count <= K
+    uint32_t *out;                // device, 16-byte aligned
+};
+// slices_per_tile: row ranges per sample tile, each summed by one block (0 = by shape)
+hipError_t launch_gt_spair_general(const SpairArgs &a, int slices_per_tile, int num_cus, hipStream_t stream);
+hipError_t launch_gt_spair_mfma(const SpairArgs &a, int slices_per_tile, int num_cus, hipStream_t stream);
 
 // Packed records (gt_pack.hip): row j = the mode-0x02 record of the K kept samples of selected row j, ceil(K / 4) bytes at
 // out + j * out_stride, every code sent through a 2-bit -> 2-bit map, pad bits zero.

@@ -628,6 +628,53 @@ class GtEngine:
             raise ValueError(f"out must be a {dtype} tensor with >= {need} entries")
         return n_left, out.view(-1)
 
+    # -- pairwise sample tables ------------------------------------------------------------------
+    def sample_pair_tables(self, records: torch.Tensor, record_stride: Optional[int] = None, variant_idx: Optional[torch.Tensor] = None,
+                           n_variants: Optional[int] = None, *, a: Optional[tuple[int, int]] = None, b: Optional[tuple[int, int]] = None,
+                           out: Optional[torch.Tensor] = None, accumulate: bool = False, kernel: int = _capi.SPAIR_AUTO,
+                           records_offset: int = 0) -> torch.Tensor:
+        """Joint genotype tables of pairs of kept samples over the selected rows: an int32 ``(a_count, b_count, 4, 4)`` CUDA view
+        whose entry ``[i, l, x, y]`` is the u32 number of rows in which the sample of rank ``a_begin + i`` has code ``x`` and the
+        sample of rank ``b_begin + l`` has code ``y`` (codes 0-3: hom-ref, het, hom-alt, missing).
+
+        ``a``, ``b``: ``(begin, count)`` ranges of ranks in the kept list (default: all K).  Rows are selected as in
+        ``sample_counts``.  ``out``: optional int32 CUDA tensor of >= 16 * a_count * b_count entries, 16-byte aligned (written from
+        its first element; nothing else is touched).  ``accumulate``: add to what ``out`` holds instead of overwriting it.
+        ``kernel``: a forced shape (``_capi.SPAIR_*``)."""
+        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
+        a, b, out = self._spair_out(a, b, out, accumulate)
+        check(lib.pgenhip_sample_pair_stats(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants,
+                                            a[0], a[1], b[0], b[1], _ptr(out), kernel | (_capi.SPAIR_ACCUMULATE if accumulate else 0)),
+              "pgenhip_sample_pair_stats")
+        return out[: 16 * a[1] * b[1]].view(a[1], b[1], 4, 4)
+
+    def sample_pair_tables_at(self, base: torch.Tensor, record_off: torch.Tensor, n_variants: Optional[int] = None, *,
+                              a: Optional[tuple[int, int]] = None, b: Optional[tuple[int, int]] = None,
+                              out: Optional[torch.Tensor] = None, accumulate: bool = False,
+                              kernel: int = _capi.SPAIR_AUTO) -> torch.Tensor:
+        """``sample_pair_tables`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
+        n_variants = self._rows_at(base, record_off, n_variants)
+        a, b, out = self._spair_out(a, b, out, accumulate)
+        check(lib.pgenhip_sample_pair_stats_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, a[0], a[1], b[0], b[1], _ptr(out),
+                                               kernel | (_capi.SPAIR_ACCUMULATE if accumulate else 0)),
+              "pgenhip_sample_pair_stats_at")
+        return out[: 16 * a[1] * b[1]].view(a[1], b[1], 4, 4)
+
+    def _spair_out(self, a, b, out: Optional[torch.Tensor], accumulate: bool):
+        """(the two ranges with their defaults, the flat output: given, or allocated)"""
+        a = (0, self.kept_count) if a is None else (int(a[0]), int(a[1]))
+        b = (0, self.kept_count) if b is None else (int(b[0]), int(b[1]))
+        if min(a + b) < 0:
+            raise ValueError("sample ranges are (begin, count) with begin, count >= 0")
+        need = 16 * a[1] * b[1]
+        if out is None:
+            make = torch.zeros if accumulate else torch.empty
+            return a, b, make(max(need, 4), dtype=torch.int32, device=self.torch_device)
+        self._check_dev(out, "out")
+        if out.dtype != torch.int32 or out.numel() < need:
+            raise ValueError(f"out must be an int32 tensor with >= {need} entries")
+        return a, b, out.view(-1)
+
     _MATRIX_DTYPES = {torch.int8: np.int8, torch.uint8: np.uint8, torch.int16: np.int16, torch.int32: np.int32,
                       torch.float16: np.float16, torch.bfloat16: None, torch.float32: np.float32}
 

@@ -17,6 +17,9 @@
 // `pgen-hip score <PFILE_PREFIX> --weights <FILE> [--no-mean-imputation] [--avg] [--include-var <EXPR>] [--include-sam <EXPR>]
 // [-o|--out <FILE>]` (not in the reference): polygenic scores of the kept samples (plink2 --score), the weighted dosage sums of the
 // variants FILE names among the kept ones, summed on the GPU in FP64.
+// `pgen-hip kinship <PFILE_PREFIX> [--include-var <EXPR>] [--include-sam <EXPR>] [--min-kinship <X>] [--counts] [-o|--out <FILE>]` (not in
+// the reference): the joint genotype table of every pair of kept samples over the kept variants, counted on the GPU's int8 matrix
+// cores, and the KING-robust kinship estimate from it.
 // Additions (opt-in, not in the reference): --gpus <N>, --block-mib <M>, --launch-mib <M>, --filter-threads <T>, --stats, --dry-run
 // (filter: write the VCF header only and report the body geometry; needs no GPU); BGZF output (`-o x.vcf.gz` or --bgzf,
 // --bgzf-level <1-9>, --compress-threads <T>) and `pgen-hip bgzf <IN> <OUT>`, the same writer on a file.
@@ -89,6 +92,7 @@ const char *kUsage =
     "  score   Polygenic scores of the kept samples from a weights file, outputting to stdout\n"
     "  matrix  Numeric genotype matrix of the kept variants and samples, outputting to a NumPy .npy file\n"
     "  ld      Pairwise r^2 of the kept variants inside a sliding window, outputting to stdout\n"
+    "  kinship Pairwise genotype tables and KING-robust kinship of the kept samples, outputting to stdout\n"
     "  export  Writes the kept variants and samples back as a .pgen (or PLINK 1 .bed) fileset\n"
     "  help    Print this message\n\n"
     "query  <PFILE_PREFIX> -f, --fstring <QUERY_FSTRING> [-i, --include <QUERY>] [-s, --samples]\n"
@@ -126,6 +130,14 @@ const char *kUsage =
     "       the kept variants and samples as OUT_PREFIX.pgen (fixed-width, storage mode 0x02), .pvar (the header lines and the kept\n"
     "       rows) and .psam; --format bed: PLINK 1 OUT_PREFIX.bed (variant-major, ALT as A1), .bim (CHROM ID 0 POS ALT REF) and .fam\n"
     "       (FID IID PAT MAT SEX -9; 0 for a missing column).  OUT_PREFIX must not name the input; no byte parity with plink2 is claimed\n"
+    "kinship <PFILE_PREFIX> [--include-var <VAR_QUERY>] [--include-sam <SAM_QUERY>] [--min-kinship <X>] [--counts] [-o, --out <OUT_FILE>]\n"
+    "       [--gpus <N>] [--shards <S>] [--block-mib <M>] [--block-rows <B>] [--sample-tile <T>] [--read-threads <T>] [--filter-threads <T>] [--stats]\n"
+    "       one line per pair of kept samples in psam order: IID1 IID2 N HETHET IBS0 HET1 HET2 KINSHIP over the kept variants called in\n"
+    "       both samples; KINSHIP = 0.5 - (HET1 + HET2 - 2 HETHET + 4 IBS0) / (4 min(HET1, HET2)) is the KING-robust between-family\n"
+    "       estimator (nan when min(HET1, HET2) is 0); --counts appends the pair's 4 x 4 genotype table T00 .. T33; --min-kinship drops\n"
+    "       the lines below X and the nan lines.  The tables of all pairs (32 bytes x kept samples squared) are held on each device in\n"
+    "       square tiles of T ranks (default 1024): out-of-core sample tiling is not built, and a sample set whose tables do not fit\n"
+    "       fails with an out-of-memory error.  No byte or digit parity with plink2's .kin0 or KING is claimed\n"
     "bgzf   <IN_FILE> <OUT_FILE> [--level <1-9>] [--threads <T>] [--chunk-mib <M>]\n";
 
 [[noreturn]] void usage_error(const std::string &msg)
@@ -486,6 +498,41 @@ int main(int argc, char **argv)
             ld.counts = a.has("counts");
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
             const OutputStats st = pfile.output_ld(a.get("include-sam"), a.get("include-var"), a.get("out").value_or(""), ld, output_options(a));
+            if (a.has("stats")) print_stats(st, t_main);
+            return 0;
+        }
+        if (cmd == "kinship") {
+            Args a = parse(argc, argv, 2, {{"min-kinship", 0}, {"sample-tile", 0}, {"block-rows", 0}, {"include-var", 0}, {"include-sam", 0}, {"out", 'o'}, {"gpus", 0}, {"shards", 0}, {"block-mib", 0}, {"read-threads", 0}, {"filter-threads", 0}},
+                           {{"stats", 0}, {"counts", 0}});
+            if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
+            KinshipOptions k;
+            if (auto m = a.get("min-kinship")) {
+                char *end = nullptr;
+                errno = 0;
+                k.min_kinship = std::strtod(m->c_str(), &end);
+                if (m->empty() || *end != '\0' || errno != 0 || !std::isfinite(k.min_kinship))
+                    usage_error("invalid value '" + *m + "' for '--min-kinship <X>': a finite number");
+                k.has_min = true;
+            }
+            if (auto t = a.get("sample-tile")) {
+                char *end = nullptr;
+                errno = 0;
+                const unsigned long long v = std::strtoull(t->c_str(), &end, 10);
+                if (t->empty() || (*t)[0] == '-' || *end != '\0' || errno != 0 || v < 1 || v > 65536)
+                    usage_error("invalid value '" + *t + "' for '--sample-tile <T>': a number of samples from 1 to 65536");
+                k.tile = (uint32_t)v;
+            }
+            if (auto b = a.get("block-rows")) {
+                char *end = nullptr;
+                errno = 0;
+                const unsigned long long v = std::strtoull(b->c_str(), &end, 10);
+                if (b->empty() || (*b)[0] == '-' || *end != '\0' || errno != 0 || v < 1)
+                    usage_error("invalid value '" + *b + "' for '--block-rows <B>': a number of variants from 1");
+                k.block_rows = v;
+            }
+            k.counts = a.has("counts");
+            const Pfile pfile = Pfile::from_prefix(a.positional[0]);
+            const OutputStats st = pfile.output_kinship(a.get("include-sam"), a.get("include-var"), a.get("out").value_or(""), k, output_options(a));
             if (a.has("stats")) print_stats(st, t_main);
             return 0;
         }

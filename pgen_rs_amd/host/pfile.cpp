@@ -1220,6 +1220,47 @@ struct PairWriter {
     void finish(pgenhip_ctx *) const {}
 };
 
+// kinship's counter: the upper block triangle of sample-pair tables, one device buffer per pair of rank tiles (ta <= tb); the
+// shard's first block overwrites them, the others accumulate; they come back once per shard and the host adds the shards in u32
+// (exact: a cell is at most the number of kept variants, which is a u32)
+struct KinshipCounter {
+    uint32_t R, K, tile, tiles;
+    std::vector<std::vector<uint32_t>> &totals;   // per pair of tiles, in the order of `bufs`
+    std::mutex &mu;
+    std::vector<uint32_t *> bufs;                 // device: 16 u32 per pair of ranks of tiles (ta, tb), ta <= tb, row-major over ta, tb
+    uint32_t *h_buf;                              // pinned, the largest buffer's size
+    bool first = true;
+    uint32_t count(uint32_t t) const { return std::min(tile, K - t * tile); }
+    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, size_t, uint32_t nv, uint32_t)
+    {
+        const uint32_t flags = PGENHIP_SPAIR_AUTO | (first ? 0u : PGENHIP_SPAIR_ACCUMULATE);
+        first = false;
+        size_t p = 0;
+        for (uint32_t ta = 0; ta < tiles; ta++)
+            for (uint32_t tb = ta; tb < tiles; tb++, p++) {
+                if (d_off)
+                    check(pgenhip_sample_pair_stats_at(ctx, d_rec, d_off, nv, ta * tile, count(ta), tb * tile, count(tb), bufs[p], flags), "pgenhip_sample_pair_stats_at");
+                else
+                    check(pgenhip_sample_pair_stats(ctx, d_rec, R, nullptr, nv, ta * tile, count(ta), tb * tile, count(tb), bufs[p], flags), "pgenhip_sample_pair_stats");
+            }
+    }
+    void copy(pgenhip_ctx *, size_t) const {}
+    void collect(size_t, size_t) const {}
+    void finish(pgenhip_ctx *ctx) const
+    {
+        size_t p = 0;
+        for (uint32_t ta = 0; ta < tiles; ta++)
+            for (uint32_t tb = ta; tb < tiles; tb++, p++) {
+                const size_t words = (size_t)16 * count(ta) * count(tb);
+                check(pgenhip_memcpy_d2h(ctx, h_buf, bufs[p], words * 4), "D2H sample-pair tables");
+                check(pgenhip_wait(ctx), "pgenhip_wait");
+                std::lock_guard<std::mutex> lk(mu);
+                uint32_t *dst = totals[p].data();
+                for (size_t i = 0; i < words; i++) dst[i] += h_buf[i];
+            }
+    }
+};
+
 void write_text(const std::string &text, const std::string &filename)
 {
     if (filename.empty()) {
@@ -1541,6 +1582,101 @@ OutputStats Pfile::output_ld(const std::optional<std::string> &sam_query, const 
             return PairWriter{R, W, ld, sel.var_idx_rcds, col, pieces, mu, ctx.device<uint8_t>(bytes, "device pair entries"), ctx.pinned<uint8_t>(bytes, "pinned pair entries")};
         }, W);
         for (auto &p : pieces) text += p.second;
+    }
+    st.body_bytes = text.size() - st.header_bytes;
+    st.file_bytes = text.size();
+    write_text(text, filename);
+    st.seconds_body = now_s() - t_body;
+    return st;
+}
+
+OutputStats Pfile::output_kinship(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
+                                  const std::string &filename, const KinshipOptions &kopt, const OutputOptions &opt) const
+{
+    OutputStats st;
+    const double t0 = now_s();
+    const Selection sel = select(sam_query, var_query, opt.filter_threads);
+    size_t iid = sel.sam_header.size();   // vcf_header's rule (:114-126): the first column named IID
+    for (size_t c = 0; c < sel.sam_header.size(); c++) {
+        if (sel.sam_header[c] == "IID") {
+            iid = c;
+            break;
+        }
+    }
+    if (iid == sel.sam_header.size()) throw PfileError("IID not among the headers of " + psam_path());
+    st.seconds_filter = now_s() - t0;
+
+    const KeptSamples kept = check_selection(*this, sel);
+    const size_t V = sel.var_idx_rcds.size(), K = kept.rows.size();
+    st.variants = V;
+    st.samples_kept = K;
+
+    std::string text = "#IID1\tIID2\tN\tHETHET\tIBS0\tHET1\tHET2\tKINSHIP";
+    if (kopt.counts) {
+        for (int a = 0; a < 4; a++)
+            for (int b = 0; b < 4; b++) text += std::string("\tT") + (char)('0' + a) + (char)('0' + b);
+    }
+    text += '\n';
+    st.header_bytes = text.size();
+    const double t_body = now_s();
+    if (K >= 2) {   // else no pair: the header alone
+        const uint32_t tile = std::max<uint32_t>(1u, kopt.tile), tiles = (uint32_t)((K + tile - 1) / tile);
+        auto count = [&](uint32_t t) { return (size_t)std::min<uint64_t>(tile, K - (uint64_t)t * tile); };
+        std::vector<std::vector<uint32_t>> totals;
+        for (uint32_t ta = 0; ta < tiles; ta++)
+            for (uint32_t tb = ta; tb < tiles; tb++) totals.emplace_back(16 * count(ta) * count(tb), 0u);
+        if (V != 0) {   // else every table is zero and no device is touched
+            const uint32_t R = variant_record_size();
+            std::mutex mu;
+            OutputOptions blocks = opt;
+            if (kopt.block_rows) blocks.block_text_bytes = kopt.block_rows * R;   // count_blocks sizes its blocks by record bytes
+            count_blocks(*this, sel.var_idx_rcds, kept, blocks, "no HIP device: the kinship path has no CPU fallback", st, [&](DeviceCtx &ctx, uint64_t) {
+                KinshipCounter kc{R, (uint32_t)K, tile, tiles, totals, mu, {}, nullptr};
+                for (uint32_t ta = 0; ta < tiles; ta++)
+                    for (uint32_t tb = ta; tb < tiles; tb++) kc.bufs.push_back(ctx.device<uint32_t>(64 * count(ta) * count(tb), "device sample-pair tables"));
+                kc.h_buf = ctx.pinned<uint32_t>(64 * count(0) * count(0), "pinned sample-pair tables");
+                return kc;
+            });
+        }
+        // first buffer of each tile row: pair (ta, tb) is at row_first[ta] + tb - ta
+        std::vector<size_t> row_first(tiles);
+        for (size_t ta = 0, p = 0; ta < tiles; p += tiles - ta, ta++) row_first[ta] = p;
+        char num[32];
+        for (size_t a = 0; a < K; a++) {
+            const size_t ta = a / tile, i = a % tile;
+            for (size_t b = a + 1; b < K; b++) {
+                const size_t tb = b / tile, l = b % tile;
+                const uint32_t *t = totals[row_first[ta] + tb - ta].data() + 16 * (i * count((uint32_t)tb) + l);
+                uint64_t n = 0;
+                for (int x = 0; x < 3; x++)
+                    for (int y = 0; y < 3; y++) n += t[4 * x + y];
+                const uint64_t hethet = t[5], ibs0 = (uint64_t)t[2] + t[8], het1 = (uint64_t)t[4] + t[5] + t[6], het2 = (uint64_t)t[1] + t[5] + t[9];
+                const uint64_t hmin = std::min(het1, het2);
+                const double kin = hmin == 0 ? std::nan("") : 0.5 - ((double)(het1 + het2 - 2 * hethet) + 4.0 * (double)ibs0) / (4.0 * (double)hmin);
+                if (kopt.has_min && !(kin >= kopt.min_kinship)) continue;   // nan lines go with the ones below the floor
+                text += sel.sam_idx_rcs[a].second.at(iid);
+                text += '\t';
+                text += sel.sam_idx_rcs[b].second.at(iid);
+                for (const uint64_t v : {n, hethet, ibs0, het1, het2}) {
+                    text += '\t';
+                    append_u64(text, v);
+                }
+                text += '\t';
+                if (hmin == 0) {
+                    text += "nan";
+                } else {
+                    std::snprintf(num, sizeof num, "%.6g", kin);
+                    text += num;
+                }
+                if (kopt.counts) {
+                    for (int c = 0; c < 16; c++) {
+                        text += '\t';
+                        append_u64(text, t[c]);
+                    }
+                }
+                text += '\n';
+            }
+        }
     }
     st.body_bytes = text.size() - st.header_bytes;
     st.file_bytes = text.size();

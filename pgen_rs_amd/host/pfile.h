@@ -118,6 +118,15 @@ struct ScoreWeights {
 };
 ScoreWeights read_score_weights(const std::string &path);
 
+// `kinship`: what is printed and how the kept samples are cut into rank tiles on the device
+struct KinshipOptions {
+    bool counts = false;              // --counts: the sixteen cells of the pair's table behind KINSHIP
+    bool has_min = false;             // --min-kinship given
+    double min_kinship = 0.0;         // with has_min: lines below it (and nan lines) are not printed
+    uint32_t tile = 1024;             // ranks per square tile: one device buffer of 64 * tile^2 bytes per pair of tiles
+    uint64_t block_rows = 0;          // variants per block (0: as many as fill block_text_bytes with their records)
+};
+
 struct OutputStats {
     uint64_t variants = 0, samples_kept = 0, header_bytes = 0, body_bytes = 0;   // header / body: bytes of VCF text
     uint64_t file_bytes = 0;                                                     // what the output file holds (BGZF: compressed)
@@ -243,6 +252,21 @@ class Pfile {
     // Uses n_gpus, n_shards, block_text_bytes (bytes of records per block), read_threads and filter_threads of `opt`.
     OutputStats output_export(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
                               const std::string &out_prefix, const ExportOptions &eopt, const OutputOptions &opt = OutputOptions()) const;
+
+    // `kinship` (not in the reference): the joint genotype tables of every pair of kept samples over the kept variants
+    // (pgenhip_sample_pair_stats / _at) and the KING-robust between-family kinship estimate from them.  The kept samples are cut into
+    // square tiles of `tile` ranks; the device holds the upper block triangle of tables, one buffer per pair of tiles, overwritten by
+    // the first block of variants and added to by the others (freq's block loop and shards; every staged block is used for every
+    // pair of tiles before the next one is read); the buffers come back once per shard and the host adds the shards' u32 tables.
+    // The whole triangle (32 K^2 bytes) must fit the device: out-of-core sample tiling is not built, and a triangle that does not
+    // fit fails with the library's out-of-memory message.  One line per pair of ranks a < b, ordered by (a, b):
+    // IID1 IID2 N HETHET IBS0 HET1 HET2 KINSHIP, all over the rows called in both samples (cells x, y in {0, 1, 2}): N their sum,
+    // HETHET = T[1][1], IBS0 = T[0][2] + T[2][0], HET1 = T[1][0] + T[1][1] + T[1][2], HET2 = T[0][1] + T[1][1] + T[2][1],
+    // KINSHIP = 0.5 - (HET1 + HET2 - 2 HETHET + 4 IBS0) / (4 min(HET1, HET2)) in double (%.6g; nan when min(HET1, HET2) == 0);
+    // with counts also T00 .. T33.  No byte or digit parity with plink2's .kin0 or KING is claimed.  Fewer than two kept samples:
+    // the header alone; no kept variant: every table is zero; neither touches a device.  filename empty: stdout.
+    OutputStats output_kinship(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
+                               const std::string &filename, const KinshipOptions &kopt, const OutputOptions &opt = OutputOptions()) const;
 
     // the header part of output_vcf (:110-146) on its own: used by output_vcf and by the CPU tests
     std::string vcf_header(const IdxRecords &sam_idx_rcs, const StringRecord &sam_header) const;
