@@ -10,6 +10,7 @@ returns None when all bytes agree, else a tuple that names the first difference 
 offset is what tells which 32-bit quantity wrapped)."""
 from __future__ import annotations
 
+from fractions import Fraction
 from typing import Optional, Sequence
 
 import numpy as np
@@ -156,6 +157,131 @@ def padding_untouched(out: torch.Tensor, rows: int, row_bytes: int, pitch: int, 
         if not bool((pad == fill).all()):
             return False
     return True
+
+
+def check_packed(out_row: torch.Tensor, rec: torch.Tensor, n: int, kept=None, map4=None, slab: int = SLAB):
+    """``out_row``: the ceil(K / 4) bytes of one packed row (pgenhip_pack_records); ``map4``: the four codes written for input codes
+    0..3 (None: the identity).  Compared rank by rank, so slab seams fall inside bytes of both rows.  -> None, or (rank, got code,
+    want code) of the first wrong code = output byte rank >> 2; set pad bits in the last byte are reported as (K, pad bits, 0)."""
+    kept = as_kept(kept, rec.device)
+    k = kept_count(n, kept)
+    m = torch.tensor([0, 1, 2, 3] if map4 is None else [int(x) for x in map4], dtype=torch.uint8, device=rec.device)
+    for a, b in _slabs(k, slab):
+        want = m[codes(rec, a, b, kept).to(torch.int64)]
+        got = codes(out_row, a, b)
+        i = _first_diff(got, want)
+        if i is not None:
+            return a + i, int(got[i]), int(want[i])
+    if k % 4:
+        pad = int(out_row[(k - 1) >> 2]) >> (2 * (k % 4))
+        if pad:
+            return k, pad, 0
+    return None
+
+
+def check_scores(scores: torch.Tensor, recs_rows: Sequence[torch.Tensor], n: int, kept, weights, miss=None, prefill: int = 0,
+                 slab: int = SLAB):
+    """``scores``: the K * C float64 values pgenhip_sample_scores wrote.  ``weights``: (V, C) small integers, ``miss``: V small integers
+    or None, both indexed by the row's position in ``recs_rows``; ``prefill``: the integer every score held before an accumulating call
+    (0 otherwise).  The sums are formed in int64, so the scores must equal them exactly as float64.  -> None or (rank, column, got, want)."""
+    dev = scores.device
+    kept = as_kept(kept, dev)
+    k = kept_count(n, kept)
+    w = torch.from_numpy(np.asarray(weights, dtype=np.int64).reshape(len(recs_rows), -1).copy()).to(dev)
+    c = int(w.shape[1])
+    ms = [0] * len(recs_rows) if miss is None else [int(x) for x in np.asarray(miss).reshape(-1)]
+    flat = scores.reshape(-1)
+    slab = max(1, min(slab, (1 << 26) // c))   # a slab of ranks holds C columns of int64 and of float64: bound its bytes
+    for a, b in _slabs(k, slab):
+        want = torch.full((b - a, c), int(prefill), dtype=torch.int64, device=dev)
+        for j, rec in enumerate(recs_rows):
+            code = codes(rec, a, b, kept).to(torch.int64)
+            d = torch.where(code == 3, torch.full_like(code, ms[j]), code)
+            want += d[:, None] * w[j][None, :]
+        want = want.to(torch.float64)
+        got = flat[c * a: c * b].view(b - a, c)
+        i = _first_diff(got, want)   # (NaN differs from everything, itself included)
+        if i is not None:
+            return a + i // c, i % c, float(got.reshape(-1)[i]), float(want.reshape(-1)[i])
+    return None
+
+
+def pair_table(rec_i: torch.Tensor, rec_j: torch.Tensor, n: int, kept=None, slab: int = SLAB) -> list:
+    """The 4 x 4 table of two records over the kept samples, as Python integers: t[a][b] = samples with code a in ``rec_i`` and code b
+    in ``rec_j`` (sixteen masked sums per slab)."""
+    kept = as_kept(kept, rec_i.device)
+    tot = [0] * 16
+    for a, b in _slabs(kept_count(n, kept), slab):
+        code = 4 * codes(rec_i, a, b, kept) + codes(rec_j, a, b, kept)
+        sums = torch.stack([(code == q).sum() for q in range(16)]).tolist()
+        tot = [x + int(y) for x, y in zip(tot, sums)]
+    return [tot[4 * a: 4 * a + 4] for a in range(4)]
+
+
+def r2_of_table(t) -> np.float32:
+    """r^2 of a 4 x 4 table's cells with a, b in {0, 1, 2} (include/pgen_hip.h), from Python integers: the exact rational
+    (n Sxy - Sx Sy)^2 / ((n Sxx - Sx^2)(n Syy - Sy^2)) rounded ONCE to float32 (to nearest, ties to even, by integer division);
+    NaN when a variance is 0."""
+    n = sx = sy = sxx = syy = sxy = 0
+    for a in range(3):
+        for b in range(3):
+            c = int(t[a][b])
+            n, sx, sy, sxx, syy, sxy = n + c, sx + a * c, sy + b * c, sxx + a * a * c, syy + b * b * c, sxy + a * b * c
+    vx, vy = n * sxx - sx * sx, n * syy - sy * sy
+    if vx == 0 or vy == 0:
+        return np.float32(np.nan)
+    cov = n * sxy - sx * sy
+    x = Fraction(cov * cov, vx * vy)
+    if x == 0:
+        return np.float32(0.0)
+    num, den = x.numerator, x.denominator
+    e = 23 - (num.bit_length() - den.bit_length())      # 2^22 < x 2^e < 2^24
+    if (num << max(e, 0)) < (den << (23 + max(-e, 0))):
+        e += 1                                          # 2^23 <= x 2^e < 2^24: 24 significant bits in front of the point
+    e = min(e, 149)                                     # subnormals: fewer bits
+    top, bottom = num << max(e, 0), den << max(-e, 0)
+    q, rem = divmod(top, bottom)
+    if 2 * rem > bottom or (2 * rem == bottom and q & 1):
+        q += 1
+    return np.float32(np.ldexp(np.float64(q), -e))      # q <= 2^24: exact in both formats
+
+
+def sample_pair_tables(recs_rows: Sequence[torch.Tensor], n: int, kept, a_ranks, b_ranks) -> torch.Tensor:
+    """(a_count, b_count, 4, 4) int64: entry [i, l, x, y] = rows of ``recs_rows`` in which rank a_begin + i has code x and rank
+    b_begin + l has code y.  ``a_ranks``, ``b_ranks``: (begin, count), small ranges of rows of any length."""
+    dev = recs_rows[0].device
+    kept = as_kept(kept, dev)
+    (a0, ac), (b0, bc) = a_ranks, b_ranks
+    out = torch.zeros((ac, bc, 16), dtype=torch.int64, device=dev)
+    cells = torch.arange(16, device=dev)
+    for rec in recs_rows:
+        ca = codes(rec, a0, a0 + ac, kept).to(torch.int64)
+        cb = codes(rec, b0, b0 + bc, kept).to(torch.int64)
+        out += (4 * ca[:, None] + cb[None, :])[:, :, None] == cells
+    return out.view(ac, bc, 4, 4)
+
+
+# ---- periodic rows: a closed form for windows too wide to enumerate ------------------------------------------------------------------
+PERIOD = 45   # shares no factor with the pair kernel's 16-row tile: every tile phase meets every row of the period
+
+
+def periodic_tables(codes_p: np.ndarray) -> np.ndarray:
+    """(P, P, 16) int64 from the (P, K) codes of the P distinct rows (pair_ref.table): the table of rows x and y."""
+    import pair_ref as PR
+
+    p = codes_p.shape[0]
+    return np.stack([np.stack([PR.table(codes_p[x], codes_p[y]).reshape(16) for y in range(p)]) for x in range(p)])
+
+
+def periodic_expected(tab: torch.Tensor, i0: int, i1: int, window: int, v: int, fill) -> torch.Tensor:
+    """Entries [i0, i1) x [0, W) of pgenhip_pair_stats when selected row j is row j mod P: entry (i, d - 1) is ``tab[i % P, (i + d) % P]``
+    (``tab``: (P, P, ...) on the device), and ``fill`` where i + d >= v (the library leaves those untouched)."""
+    p = tab.shape[0]
+    i = torch.arange(i0, i1, device=tab.device)[:, None]
+    j = i + torch.arange(1, window + 1, device=tab.device)[None, :]
+    want = tab[i % p, j % p]
+    want[j >= v] = fill
+    return want
 
 
 # ---- shared by the GPU files: free-memory gate and sentinel frames -----------------------------------------------------------------

@@ -93,3 +93,38 @@ def table_brute(recs: np.ndarray, n: int, kept: Optional[Sequence[int]], i: int,
         b = (int(recs[j, s // 4]) >> (2 * (s % 4))) & 3
         t[a, b] += 1
     return t
+
+
+# ---- how the GPU files compare an output with the reference: one rule, kept in one place ---------------------------------------------
+SENT_U = 0xA5A5A5A5   # the word every output entry holds before a call (the GPU tests' sentinel frames)
+
+
+def r2_close(got, want) -> bool:
+    """Is ``got`` within one float32 ulp of ``want`` (the exact rational rounded once), or NaN where ``want`` is NaN?"""
+    return bool(np.isnan(got)) if np.isnan(want) else abs(float(got) - float(want)) <= float(np.spacing(np.float32(want)))
+
+
+def check_tables(got: np.ndarray, want_tables: np.ndarray, v: int, what: str):
+    """got: (n_left, W, 16) uint32 words; want_tables: pair_tables(..., fill=-1) of at least n_left rows.  Every existing entry must
+    equal the reference; entries with i + d >= V must keep the sentinel."""
+    n_left, w = got.shape[:2]
+    want = want_tables[:n_left].reshape(n_left, w, 16)
+    exists = (np.arange(n_left)[:, None] + np.arange(1, w + 1)[None, :]) < v
+    assert (got[~exists] == SENT_U).all(), f"{what}: an entry with i + d >= V was written"
+    bad = np.argwhere((got.astype(np.int64) != want).any(axis=2) & exists)
+    if bad.size:
+        i, d = bad[0]
+        raise AssertionError(f"{what}: {len(bad)} tables differ; first pair ({i}, {i + d + 1}), pair index {i * w + d}: got {got[i, d].tolist()}, "
+                             f"want {want[i, d].tolist()}")
+
+
+def check_r2(got_bits: np.ndarray, want_tables: np.ndarray, v: int, what: str):
+    """got_bits: (n_left, W) uint32 bit patterns of the r^2 output: ``r2_close`` to pair_r2 of the reference tables wherever the pair
+    exists, the sentinel elsewhere."""
+    n_left, w = got_bits.shape
+    got = got_bits.view(np.float32)
+    exists = (np.arange(n_left)[:, None] + np.arange(1, w + 1)[None, :]) < v
+    assert (got_bits[~exists] == SENT_U).all(), f"{what}: an r^2 entry with i + d >= V was written"
+    want = pair_r2(want_tables[:n_left], v)
+    for i, d in np.argwhere(exists):
+        assert r2_close(got[i, d], want[i, d]), f"{what}: pair ({i}, {i + d + 1}) r^2 {got[i, d]!r}, want {want[i, d]!r}"

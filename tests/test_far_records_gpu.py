@@ -4,12 +4,14 @@ that takes the shape (the per-variant counts have test_genotype_counts_gpu.py::t
 One shared buffer of 2^32 + 4 099 + 8 * R_max + 64 bytes: random bytes in its first MiB (the near rows, and the place every far
 offset lands on when it is cut to 32 bits: a wrong record, read in bounds) and from 64 bytes before FAR to its end (the far rows).
 Each call mixes near and far rows through (i) d_variant_idx with record_stride = FAR, (ii) a small stride with d_variant_idx values
-near FAR / stride, (iii) d_record_off.  Expected bytes: the CPU oracle and the numpy references on the few records involved.
+near FAR / stride, (iii) d_record_off; the packed-record, score, pair-table and sample-pair-table entry points also take (iv) two
+rows by stride alone, FAR bytes apart.  Expected bytes: the CPU oracle and the numpy references on the few records involved.
+test_sample_scores_far_weights does the same for the other pointer a kernel offsets by a row number: d_weights.
 
 The kernels that cannot gather (RUNS, the pick family's packed path, the line-run kernel) get dense records that cross 2^32
 themselves, 70 GB of text each, checked as test_gt_parity_gpu.py::test_gt_segments_past_4_gib checks: a line feed at the end of
 every row (on the device), sentinels behind the last row, windows of 100 rows against the oracle at the start, around the row whose
-record holds byte 2^32, at the end and at six seeded places.
+record holds byte 2^32, at the end and at six seeded places.  pgenhip_pack_records DENSE gets the same 4.32 GB in and out.
 """
 import numpy as np
 import pytest
@@ -17,8 +19,12 @@ import torch
 
 import longrow_ref as LR
 import matrix_ref as MR
+import pack_ref as PK
+import pair_ref as PR
 import pgen_oracle as oracle
 import pgen_rs_amd
+import score_ref as SCR
+import spair_ref as SPR
 import subset_plan as SP
 from pgen_rs_amd import _capi
 
@@ -68,10 +74,14 @@ def far():
     torch.cuda.empty_cache()
 
 
-def sources(n: int):
-    """-> [(name, byte offsets of the rows, kwargs of a stride / gather call or None, record_off tensor or None)]: near and far rows mixed."""
+def sources(n: int, plain: bool = False):
+    """-> [(name, byte offsets of the rows, kwargs of a stride / gather call or None, record_off tensor or None)]: near and far rows mixed.
+    ``plain`` adds two rows by stride alone (no list): bytes 3 and 3 + FAR, the only way to put a far row in front of the
+    `row * record_stride` arm of a kernel."""
     r = MR.rsize(n)
     out = []
+    if plain:
+        out.append(("plain stride FAR", [3, 3 + FAR], dict(record_stride=FAR, records_offset=3, variant_idx=None), None))
     vidx = [0, 1, 1, 0, 1]
     out.append(("idx x FAR", [3 + i * FAR for i in vidx], dict(record_stride=FAR, records_offset=3, variant_idx=vidx), None))
     stride = r + 5
@@ -86,7 +96,7 @@ def sources(n: int):
 
 
 def tensors(kw, offs_at):
-    if kw is not None:
+    if kw is not None and kw["variant_idx"] is not None:
         kw = dict(kw, variant_idx=torch.tensor(kw["variant_idx"], dtype=torch.int64, device=DEV).to(torch.int32))
     at = None if offs_at is None else torch.tensor(offs_at, dtype=torch.int64, device=DEV)
     return kw, at
@@ -236,6 +246,187 @@ def test_decode_matrix_far_records(far, n, k, dtype):
                 first_diff(got, want, what)
 
 
+# ---- packed records, scores, pair tables, sample-pair tables ------------------------------------------------------------------------
+@pytest.mark.parametrize("n,k", COUNT_SHAPES, ids=[f"N{n}-{'all' if k is None else k}" for n, k in COUNT_SHAPES])
+def test_pack_records_far_records(far, n, k):
+    """pgenhip_pack_records and pgenhip_pack_records_at: AUTO, GENERAL and DENSE (all samples) or GATHER (a list), the identity map and
+    [3, 2, 1, 0], rows at an odd address with a pitch of R_K + 5; the padding must come back untouched.  Needs 5 GiB."""
+    kept = kept_for(n, k)
+    kk = n if kept is None else k
+    r, rk = MR.rsize(n), (kk + 3) // 4
+    pitch = rk + 5
+    shapes = [_capi.PACK_AUTO, _capi.PACK_GENERAL, _capi.PACK_DENSE if kept is None else _capi.PACK_GATHER]
+    with pgen_rs_amd.GtEngine(n, kept_idx=kept, device=0) as eng:
+        for sname, offs, kw, offs_at in sources(n, plain=True):
+            v = len(offs)
+            recs = far.records(offs, r)
+            kw_t, at_t = tensors(kw, offs_at)
+            total = (v - 1) * pitch + rk
+            for code_map in (None, [3, 2, 1, 0]):
+                want = PK.pack(recs, n, kept, code_map)
+                for shape in shapes:
+                    buf, front = framed(total)
+                    assert (buf.data_ptr() + front) % 2 == 1
+                    if at_t is None:
+                        eng.pack_records(far.dev, out=buf, out_offset=front, out_stride=pitch, code_map=code_map, shape=shape, n_variants=v, **kw_t)
+                    else:
+                        eng.pack_records_at(far.dev, at_t, out=buf, out_offset=front, out_stride=pitch, code_map=code_map, shape=shape, n_variants=v)
+                    eng.wait()
+                    what = f"N={n} K={kk} {sname} shape {shape} map {code_map}"
+                    h = np.concatenate([payload(buf, front, total, what), np.full(pitch - rk, SENT, dtype=np.uint8)]).reshape(v, pitch)
+                    assert (h[:, rk:] == SENT).all(), f"{what}: row padding was written"
+                    first_diff(h[:, :rk], want, what)
+
+
+@pytest.mark.parametrize("c", [1, 3, 8])
+@pytest.mark.parametrize("n,k", COUNT_SHAPES, ids=[f"N{n}-{'all' if k is None else k}" for n, k in COUNT_SHAPES])
+def test_sample_scores_far_records(far, n, k, c):
+    """pgenhip_sample_scores and pgenhip_sample_scores_at with C = 1, 3, 8 (4, 2 and 1 record bytes per lane): integer weights in
+    [-8, 8] and miss values in {0..3} by position in the selection, overwrite and ACCUMULATE onto an integer prefill; every sum is an
+    integer, so the scores are exact.  Needs 5 GiB."""
+    kept = kept_for(n, k)
+    kk = n if kept is None else k
+    r = MR.rsize(n)
+    rng = np.random.default_rng(n + c)
+    prefill = -1000.0
+    with pgen_rs_amd.GtEngine(n, kept_idx=kept, device=0) as eng:
+        for sname, offs, kw, offs_at in sources(n, plain=True):
+            v = len(offs)
+            weights = rng.integers(-8, 9, size=(v, c)).astype(np.float32)
+            miss = rng.integers(0, 4, size=v).astype(np.float32)
+            want, _ = SCR.score_ref(far.records(offs, r), n, weights, miss, kept)
+            kw_t, at_t = tensors(kw, offs_at)
+            d_w, d_m = torch.from_numpy(weights).to(DEV), torch.from_numpy(miss).to(DEV)
+            for accumulate in (False, True):
+                buf, front = framed(8 * kk * c, align=8)
+                out = buf[front: front + 8 * kk * c].view(torch.float64)
+                if accumulate:
+                    out.fill_(prefill)
+                if at_t is None:
+                    eng.sample_scores(far.dev, d_w, miss=d_m, out=out, accumulate=accumulate, n_variants=v, **kw_t)
+                else:
+                    eng.sample_scores_at(far.dev, at_t, d_w, miss=d_m, out=out, accumulate=accumulate, n_variants=v)
+                eng.wait()
+                what = f"N={n} K={kk} C={c} {sname} accumulate={accumulate}"
+                got = payload(buf, front, 8 * kk * c, what).view(np.float64).reshape(kk, c)
+                exp = want + (prefill if accumulate else 0.0)
+                if not np.array_equal(got, exp):
+                    rank, col = np.argwhere(got != exp)[0]
+                    raise AssertionError(f"{what}: rank {rank} column {col}: got {got[rank, col]!r}, want {exp[rank, col]!r}")
+
+
+def test_sample_scores_far_weights():
+    """Weight rows (1 << 30) + 3 floats apart, five rows: row 1's weights are 2^32 + 12 BYTES into d_weights and row 4's are 2^32 + 12
+    FLOATS in.  Only the touched floats are set.  An offset cut to 32 bits lands on the first 64 floats, which hold 100, 101, ...
+    (row 0's own three among them): weights no other row has.  C = 3, N = 300, near records.  Needs 24 GiB (17.2 GB of weights)."""
+    need_gib(24)
+    n, c, v = 300, 3, 5
+    w_stride = (1 << 30) + 3
+    r = MR.rsize(n)
+    rng = np.random.default_rng(30)
+    recs = rng.integers(0, 256, size=(v, r), dtype=np.uint8)
+    weights = rng.integers(-8, 9, size=(v, c)).astype(np.float32)
+    weights[0] = [100, 101, 102]
+    miss = rng.integers(0, 4, size=v).astype(np.float32)
+    want, _ = SCR.score_ref(recs, n, weights, miss)
+    d_recs = torch.from_numpy(recs.reshape(-1).copy()).to(DEV)
+    big = torch.empty((v - 1) * w_stride + c, dtype=torch.float32, device=DEV)
+    assert 1 * w_stride * 4 == (1 << 32) + 12   # row 1, in bytes
+    assert 4 * w_stride == (1 << 32) + 12       # row 4, in floats
+    big[:64] = torch.arange(100, 164, dtype=torch.float32, device=DEV)
+    d_w = torch.as_strided(big, (v, c), (w_stride, 1))
+    d_w.copy_(torch.from_numpy(weights).to(DEV))
+    assert d_w.stride(0) == w_stride and float(big[4 * w_stride + 2]) == weights[4, 2] and float(big[12]) == 112.0
+    d_m = torch.from_numpy(miss).to(DEV)
+    with pgen_rs_amd.GtEngine(n, device=0) as eng:
+        for accumulate in (False, True):
+            buf, front = framed(8 * n * c, align=8)
+            out = buf[front: front + 8 * n * c].view(torch.float64)
+            if accumulate:
+                out.fill_(7.0)
+            eng.sample_scores(d_recs, d_w, miss=d_m, out=out, accumulate=accumulate, n_variants=v)
+            eng.wait()
+            what = f"far weights, accumulate={accumulate}"
+            got = payload(buf, front, 8 * n * c, what).view(np.float64).reshape(n, c)
+            exp = want + (7.0 if accumulate else 0.0)
+            if not np.array_equal(got, exp):
+                rank, col = np.argwhere(got != exp)[0]
+                raise AssertionError(f"{what}: rank {rank} column {col}: got {got[rank, col]!r}, want {exp[rank, col]!r} (weights of rows 1..4 are "
+                                     f"{4 * w_stride:#x} bytes .. {4 * w_stride:#x} floats into d_weights)")
+    del big, d_w
+    torch.cuda.empty_cache()
+
+
+def pair_call(eng, mode, v, n_left, w, kw_t, at_t, base, what):
+    """One pgenhip_pair_stats / _at call into a framed buffer (16-byte aligned) -> the n_left * W entries as uint32 words."""
+    per = 16 if mode == "table" else 1
+    nbytes = 4 * per * n_left * w
+    buf, front = framed(nbytes, align=16)
+    out = buf[front: front + nbytes].view(torch.int32 if mode == "table" else torch.float32)
+    if at_t is None:
+        fn = eng.pair_tables if mode == "table" else eng.pair_r2
+        fn(base, n_variants=v, n_left=n_left, window=w, out=out, **kw_t)
+    else:
+        fn = eng.pair_tables_at if mode == "table" else eng.pair_r2_at
+        fn(base, at_t, v, n_left=n_left, window=w, out=out)
+    eng.wait()
+    words = payload(buf, front, nbytes, what).view(np.uint32)
+    return words.reshape(n_left, w, 16) if mode == "table" else words.reshape(n_left, w)
+
+
+@pytest.mark.parametrize("n,k", MATRIX_SHAPES, ids=[f"N{n}-{'all' if k is None else k}" for n, k in MATRIX_SHAPES])
+def test_pair_stats_far_records(far, n, k):
+    """pgenhip_pair_stats and pgenhip_pair_stats_at, tables and r^2, n_left = V - 1, W = 1 and W = V - 1.  Needs 5 GiB."""
+    kept = kept_for(n, k)
+    r = MR.rsize(n)
+    with pgen_rs_amd.GtEngine(n, kept_idx=kept, device=0) as eng:
+        for sname, offs, kw, offs_at in sources(n, plain=True):
+            v = len(offs)
+            codes = PR.unpack(far.records(offs, r), n, kept)
+            kw_t, at_t = tensors(kw, offs_at)
+            for w in sorted({1, v - 1}):
+                want = PR.pair_tables(codes, v - 1, w, fill=-1)
+                what = f"N={n} {'all' if k is None else k} {sname} W={w}"
+                PR.check_tables(pair_call(eng, "table", v, v - 1, w, kw_t, at_t, far.dev, what), want, v, what + " tables")
+                PR.check_r2(pair_call(eng, "r2", v, v - 1, w, kw_t, at_t, far.dev, what), want, v, what + " r^2")
+
+
+SPAIR_SHAPES = [(300, 30, (0, 30), (0, 30)), (2504, None, (0, 70), (2400, 104)), (20_000, 2000, (1930, 70), (0, 65))]
+
+
+@pytest.mark.parametrize("kernel", ["general", "mfma", "auto"])
+@pytest.mark.parametrize("n,k,a,b", SPAIR_SHAPES, ids=[f"N{n}-{'all' if k is None else k}" for n, k, _, _ in SPAIR_SHAPES])
+def test_sample_pair_stats_far_records(far, n, k, a, b, kernel):
+    """pgenhip_sample_pair_stats and pgenhip_sample_pair_stats_at: GENERAL, MFMA and AUTO over all four row sources (the MFMA kernel's
+    stride, variant_idx and record_off instantiations each read a far row), overwrite and ACCUMULATE onto 0xFFFFFFF0.  Needs 5 GiB."""
+    kept = kept_for(n, k)
+    r = MR.rsize(n)
+    kid = {"general": _capi.SPAIR_GENERAL, "mfma": _capi.SPAIR_MFMA, "auto": _capi.SPAIR_AUTO}[kernel]
+    prefill = 0xFFFFFFF0
+    nbytes = 64 * a[1] * b[1]
+    with pgen_rs_amd.GtEngine(n, kept_idx=kept, device=0) as eng:
+        for sname, offs, kw, offs_at in sources(n, plain=True):
+            v = len(offs)
+            want = SPR.ranges(SPR.unpack(far.records(offs, r), n, kept), a, b).reshape(-1)
+            kw_t, at_t = tensors(kw, offs_at)
+            for accumulate in (False, True):
+                buf, front = framed(nbytes, align=16)
+                out = buf[front: front + nbytes].view(torch.int32)
+                if accumulate:
+                    out.fill_(prefill - (1 << 32))
+                if at_t is None:
+                    eng.sample_pair_tables(far.dev, n_variants=v, a=a, b=b, out=out, accumulate=accumulate, kernel=kid, **kw_t)
+                else:
+                    eng.sample_pair_tables_at(far.dev, at_t, v, a=a, b=b, out=out, accumulate=accumulate, kernel=kid)
+                eng.wait()
+                what = f"N={n} {'all' if k is None else k} a={a} b={b} {sname} kernel {kernel} accumulate={accumulate}"
+                got = payload(buf, front, nbytes, what).view(np.uint32).astype(np.int64)
+                exp = (want + (prefill if accumulate else 0)) & 0xFFFFFFFF
+                if not (got == exp).all():
+                    word = int(np.flatnonzero(got != exp)[0])
+                    raise AssertionError(f"{what}: word {word} (pair {word // 16}, cell {word % 16}): got {got[word]}, want {exp[word]}")
+
+
 # ---- dense records that cross 2^32 themselves ---------------------------------------------------------------------------------------
 DENSE = [("runs", 1900, 9_100_000, _capi.KERNEL_RUNS, False), ("pick-packed", 2504, 6_900_000, _capi.KERNEL_PICK, False),
          ("line-runs", 900, 19_200_000, _capi.KERNEL_RUNS, True)]
@@ -280,4 +471,34 @@ def test_dense_records_past_4_gib(name, n, v, kernel, lines):
                 first_diff(got[:, :plen], blob[j0 * plen: j1 * plen].cpu().numpy().reshape(100, plen), f"{name}: prefixes of rows {j0}..{j1}")
             first_diff(got[:, plen:], want, f"{name}: rows {j0}..{j1} (records at bytes {j0 * r:#x}..)")
         del out, rows2d, recs
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("n", [2504, 2503], ids=["N2504-one-stream", "N2503-row-by-row"])
+def test_pack_dense_records_past_4_gib(n):
+    """pgenhip_pack_records DENSE on 4.32 GB of dense records into dense output, V x R > 2^32: N = 2 504 (a multiple of 4: the launcher
+    hands runs of rows to the kernel as one byte stream) and N = 2 503 (row by row, the pad bits of every row cleared).  Sentinels
+    around the output; windows of 100 rows against pack_ref at the start, around the row that holds byte 2^32, at the end and at six
+    seeded places.  Needs 10 GiB."""
+    need_gib(10)
+    v = 6_900_000
+    r = MR.rsize(n)
+    assert v * r > (1 << 32) + (1 << 24)
+    rng = np.random.default_rng(n)
+    with pgen_rs_amd.GtEngine(n, device=0) as eng:
+        assert eng.packed_record_size == r
+        recs = eng.synth_records(v, dirty_pad=True)
+        buf, front = framed(v * r)
+        eng.pack_records(recs, n_variants=v, out=buf, out_offset=front, shape=_capi.PACK_DENSE)
+        eng.wait()
+        assert LR.frame_ok(buf, front, v * r), "bytes outside the output were written"
+        rows2d = buf[front: front + v * r].view(v, r)
+        j_4g = (1 << 32) // r
+        starts = [0, j_4g - 50, v - 100] + [int(q) for q in rng.integers(0, v - 100, size=6)]
+        for j0 in starts:
+            h_recs = recs[j0 * r: (j0 + 100) * r].cpu().numpy().reshape(100, r)
+            if n % 4:
+                assert (h_recs[:, -1] >> (2 * (n % 4))).any(), "the input's pad bits are clean: nothing to clear"
+            first_diff(rows2d[j0: j0 + 100].cpu().numpy(), PK.pack(h_recs, n), f"pack N={n}: rows {j0}..{j0 + 100} (records at bytes {j0 * r:#x}..)")
+        del buf, rows2d, recs
     torch.cuda.empty_cache()

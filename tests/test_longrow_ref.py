@@ -1,6 +1,6 @@
 """The slab-wise torch reference of the long-row GPU tests (longrow_ref.py) against the CPU oracle's GT text (pgen_oracle.decode_emit),
-the oracle's counts (count_ref.py) and the numpy matrix reference (matrix_ref.py) — on the CPU, with a slab of 97 samples so that
-slab seams fall inside record bytes, on records with dirty pad bits."""
+the oracle's counts (count_ref.py) and the numpy references (matrix_ref.py, pack_ref.py, score_ref.py, pair_ref.py, spair_ref.py) — on
+the CPU, with a slab of 97 samples so that slab seams fall inside record bytes, on records with dirty pad bits."""
 import numpy as np
 import pytest
 import torch
@@ -8,7 +8,11 @@ import torch
 import count_ref as CR
 import longrow_ref as LR
 import matrix_ref as MR
+import pack_ref as PK
+import pair_ref as PR
 import pgen_oracle as oracle
+import score_ref as SCR
+import spair_ref as SPR
 
 SLAB = 97
 N_LIST = [1, 5, 97, 1003, 70_001]
@@ -121,3 +125,123 @@ def test_matrix_check(n, keep, np_dtype, sample_major):
         bad = out.clone()
         bad[row_bytes] = 0
         assert not LR.padding_untouched(bad, nrow, row_bytes, pitch, 0xA5)
+
+
+# ---- packed rows, scores, pair tables, r^2, sample-pair tables: against pack_ref, score_ref, pair_ref and spair_ref -------------------
+@pytest.mark.parametrize("n,keep", CASES)
+@pytest.mark.parametrize("map4", [None, (3, 2, 1, 0), PK.BED_MAP], ids=["identity", "reversed", "bed"])
+def test_packed_check(n, keep, map4):
+    kept = kept_of(n, keep)
+    recs = records(n)
+    k = LR.kept_count(n, kept)
+    want = PK.pack(recs, n, kept, map4)
+    for j in range(V):
+        rec, row = torch.from_numpy(recs[j].copy()), torch.from_numpy(want[j].copy())
+        assert LR.check_packed(row, rec, n, kept, map4, slab=SLAB) is None
+        for rank in sorted({0, k // 2, k - 1}):
+            bad = row.clone()
+            bad[rank >> 2] ^= 1 << (2 * (rank & 3))
+            found = LR.check_packed(bad, rec, n, kept, map4, slab=SLAB)
+            assert found is not None and found[0] == rank, (rank, found)
+        if k % 4:
+            bad = row.clone()
+            bad[-1] |= 0x80
+            assert LR.check_packed(bad, rec, n, kept, map4, slab=SLAB) == (k, 0x80 >> (2 * (k % 4)), 0)
+
+
+@pytest.mark.parametrize("n,keep", CASES)
+@pytest.mark.parametrize("c", [1, 3, 8])
+def test_scores_check(n, keep, c):
+    kept = kept_of(n, keep)
+    recs = records(n)
+    rows = [0, 2, 1, 2]   # a gather that repeats a row
+    k = LR.kept_count(n, kept)
+    rng = np.random.default_rng(n + c)
+    weights = rng.integers(-8, 9, size=(len(rows), c))
+    recs_rows = [torch.from_numpy(recs[j].copy()) for j in rows]
+    for miss, prefill in ((None, 0), (rng.integers(0, 4, size=len(rows)), 0), (rng.integers(0, 4, size=len(rows)), -37)):
+        want = SCR.score_ref(recs[rows], n, weights.astype(np.float32), None if miss is None else miss.astype(np.float32), kept)[0] + prefill
+        got = torch.from_numpy(want.reshape(-1).copy())
+        assert LR.check_scores(got, recs_rows, n, kept, weights, miss, prefill, slab=SLAB) is None
+        for rank, col in {(0, 0), (k - 1, c - 1), (k // 2, c // 2)}:
+            bad = got.clone()
+            bad[rank * c + col] += 1.0
+            found = LR.check_scores(bad, recs_rows, n, kept, weights, miss, prefill, slab=SLAB)
+            assert found is not None and found[:2] == (rank, col), found
+        bad = got.clone()
+        bad[0] = float("nan")
+        assert LR.check_scores(bad, recs_rows, n, kept, weights, miss, prefill, slab=SLAB)[:2] == (0, 0)
+
+
+def same_f32(a, b) -> bool:
+    return (np.isnan(a) and np.isnan(b)) or np.float32(a).view(np.uint32) == np.float32(b).view(np.uint32)
+
+
+@pytest.mark.parametrize("n,keep", CASES)
+def test_pair_table_and_r2(n, keep):
+    kept = kept_of(n, keep)
+    recs = records(n)
+    codes = PR.unpack(recs, n, kept)
+    for i, j in ((0, 1), (1, 2), (2, 2), (2, 0)):
+        t = LR.pair_table(torch.from_numpy(recs[i].copy()), torch.from_numpy(recs[j].copy()), n, kept, slab=SLAB)
+        want = PR.table(codes[i], codes[j])
+        assert t == want.tolist()
+        assert all(isinstance(x, int) for row in t for x in row)
+        assert same_f32(LR.r2_of_table(t), PR.r2_f32(want)), (t, LR.r2_of_table(t), PR.r2_f32(want))
+
+
+def test_r2_of_table_extremes():
+    """Tables whose terms sit just below 2^64 (K = 2^31 - 1, nearly every sample hom-alt in both rows), monomorphic rows, an empty
+    table, perfect correlation, and seeded tables of every size: the same float32 bits as pair_ref's once-rounded fraction."""
+    big = (1 << 31) - 1
+    tables = [[[0, 0, 0, 0], [0, 0, 0, 0], [0, 0, big, 0], [0, 0, 0, 0]],                       # monomorphic: NaN
+              [[0] * 4] * 4,                                                                  # empty: NaN
+              [[0, 0, 0, 0], [0, 1, 0, 0], [1, 1, big - 3, 0], [0, 0, 0, 0]],                 # n Sxx and Sx^2 within 2^35 of 2^64
+              [[3, 0, 0, 0], [0, 0, 2, 0], [0, 5, big - 10, 0], [0, 0, 0, 0]],
+              [[5, 0, 0, 0], [0, 7, 0, 0], [0, 0, 9, 0], [0, 0, 0, 4]],                         # r^2 = 1
+              [[1, 1, 1, 9], [1, 1, 1, 9], [1, 1, 1, 9], [9, 9, 9, 9]]]                         # cov = 0: r^2 = 0
+    rng = np.random.default_rng(16)
+    for bits in (3, 8, 16, 24, 29):
+        tables += [rng.integers(0, 1 << bits, size=(4, 4)).tolist() for _ in range(40)]
+    for t in tables:
+        got, want = LR.r2_of_table(t), PR.r2_f32(np.asarray(t, dtype=object))
+        assert same_f32(got, want), (t, got, want)
+    assert np.isnan(LR.r2_of_table(tables[0])) and LR.r2_of_table(tables[4]) == np.float32(1.0) and LR.r2_of_table(tables[5]) == 0.0
+    t = tables[2]
+    n, sx, sxx = big, 2 * (big - 1) + 1, 4 * (big - 1) + 1   # row x: one het, hom-alt elsewhere
+    assert 0 < (1 << 64) - n * sxx < 1 << 35 and 0 < (1 << 64) - sx * sx < 1 << 35 and n * sxx > sx * sx
+
+
+@pytest.mark.parametrize("n,keep", CASES)
+def test_sample_pair_tables(n, keep):
+    kept = kept_of(n, keep)
+    recs = records(n)
+    rows = [0, 2, 1, 2, 0]
+    k = LR.kept_count(n, kept)
+    codes = SPR.unpack(recs[rows], n, kept)
+    recs_rows = [torch.from_numpy(recs[j].copy()) for j in rows]
+    for a, b in (((0, min(k, 70)), (max(0, k - 33), min(k, 33))), ((k - 1, 1), (0, min(k, 5))), ((k // 3, min(7, k - k // 3)), (k // 3, min(7, k - k // 3)))):
+        got = LR.sample_pair_tables(recs_rows, n, kept, a, b)
+        assert got.dtype == torch.int64 and (got.numpy() == SPR.ranges(codes, a, b)).all()
+
+
+@pytest.mark.parametrize("v,w", [(2, 1), (46, 45), (100, 1), (100, 7), (137, 50), (137, 136), (137, 200)])
+def test_periodic_closed_form(v, w):
+    """Selected row j = row j mod 45 of 45 distinct records: the closed form equals pair_ref on the V gathered rows, and entries with
+    i + d >= V hold the fill."""
+    n, p = 11, LR.PERIOD
+    kept = np.array([0, 1, 3, 4, 6, 9, 10], dtype=np.uint32)
+    recs = np.random.default_rng(45).integers(0, 256, size=(p, LR.rsize(n)), dtype=np.uint8)
+    codes_p = PR.unpack(recs, n, kept)
+    assert len({c.tobytes() for c in codes_p}) == p
+    tab = torch.from_numpy(LR.periodic_tables(codes_p))
+    codes = codes_p[np.arange(v) % p]
+    for n_left in (v, v - 1, max(1, v // 2)):
+        want = PR.pair_tables(codes, n_left, w, fill=-1).reshape(n_left, w, 16)
+        for i0, i1 in ((0, n_left), (n_left // 3, n_left - n_left // 4)):
+            got = LR.periodic_expected(tab, i0, i1, w, v, -1)
+            assert (got.numpy() == want[i0:i1]).all()
+    r2 = torch.from_numpy(np.array([[PR.r2_f32(t.reshape(4, 4)) for t in row] for row in tab.numpy()], dtype=np.float32).view(np.int32).copy())
+    want = PR.pair_r2(PR.pair_tables(codes, v, w, fill=-1), v, fill=np.float32(0)).view(np.int32)
+    got = LR.periodic_expected(r2, 0, v, w, v, 0).numpy()
+    assert (got == want).all()

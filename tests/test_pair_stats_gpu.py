@@ -60,30 +60,8 @@ def launch(eng, mode, v, n_left, w, **kw):
     return body.reshape(n_left, w, 16) if mode == "table" else body.reshape(n_left, w)
 
 
-def check_tables(got, want_tables, v, what):
-    """got: (n_left, W, 16) uint32 words; want_tables: pair_ref.pair_tables(..., fill=-1)."""
-    n_left, w = got.shape[:2]
-    want = want_tables[:n_left].reshape(n_left, w, 16)
-    exists = (np.arange(n_left)[:, None] + np.arange(1, w + 1)[None, :]) < v
-    assert (got[~exists] == SENT_U).all(), f"{what}: an entry with i + d >= V was written"
-    bad = np.argwhere((got.astype(np.int64) != want)[exists].reshape(-1, 16).any(axis=1))
-    if bad.size:
-        i, d = np.argwhere(exists)[int(bad[0])]
-        raise AssertionError(f"{what}: {len(bad)} tables differ; first pair ({i}, {i + d + 1}): got {got[i, d].tolist()}, want {want[i, d].tolist()}")
-
-
-def check_r2(got_bits, want_tables, v, what):
-    n_left, w = got_bits.shape
-    got = got_bits.view(np.float32)
-    exists = (np.arange(n_left)[:, None] + np.arange(1, w + 1)[None, :]) < v
-    assert (got_bits[~exists] == SENT_U).all(), f"{what}: an r^2 entry with i + d >= V was written"
-    want = PR.pair_r2(want_tables[:n_left], v)
-    for i, d in np.argwhere(exists):
-        g, x = got[i, d], want[i, d]
-        if np.isnan(x):
-            assert np.isnan(g), f"{what}: pair ({i}, {i + d + 1}) r^2 {g}, want NaN"
-        else:
-            assert abs(float(g) - float(x)) <= float(np.spacing(x)), f"{what}: pair ({i}, {i + d + 1}) r^2 {g!r}, want {x!r}"
+# one comparison for every GPU file: exact tables, r^2 within one ulp and NaN where the reference has it, the sentinel where no pair exists
+check_tables, check_r2 = PR.check_tables, PR.check_r2
 
 
 def both_modes(eng, codes, v, n_left, w, what, **kw):
