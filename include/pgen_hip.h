@@ -297,6 +297,50 @@ int pgenhip_sample_scores_at(pgenhip_ctx *ctx, const void *d_base, const uint64_
                              const float *d_weights, uint64_t w_stride, uint32_t n_columns,
                              const float *d_miss, double *d_scores, uint32_t flags);
 
+/* ---- per-variant sums of per-sample values by genotype code (device-resident, asynchronous on the ctx stream) ----
+ * The transpose of pgenhip_sample_scores: for every selected row j, value column c < n_columns and code x in {0, 1, 2, 3}
+ *     d_sums[(j * n_columns + c) * 4 + x] = sum over the kept samples k whose code in row j is x of d_values[k * v_stride + c]
+ * k is the sample's rank in the ctx's kept list (its index when all samples are kept); x is 0 hom-ref, 1 het, 2 hom-alt, 3 missing,
+ * the order of the per-variant counts.  From the four sums of a column a host derives a regression of the column on the genotype
+ * (any missing-call policy), a genotypic model and per-genotype means without touching a genotype again.  d_values is a DEVICE
+ * array of FP64, K x n_columns; v_stride is in doubles, >= n_columns (or K <= 1).  FP64 input is deliberate: a term is the value
+ * itself (there is no product), so FP64 costs nothing in exactness and a host passes residualised phenotypes unrounded.
+ * Rows are selected exactly as in pgenhip_genotype_counts / pgenhip_genotype_counts_at: by stride (record_stride >= R, or
+ * n_variants <= 1), through d_variant_idx, or through d_record_off; records may start at any byte alignment; a gather that repeats
+ * a row writes it twice.  The pad bits of a record's last byte and samples >= N are never read as samples.
+ *   - Arithmetic: every addition is FP64; there are no f32 partial sums.  The ORDER of the additions is not fixed (tiles of one
+ *     row combine through FP64 atomics).  With A_c = sum over all kept k of |d_values[k * v_stride + c]|, each of the four sums
+ *     of (j, c) is within (K + 1) * 2^-53 * A_c of its exact value.  The bound is stated against A_c, not against the class's own
+ *     sum, on purpose: an implementation may obtain one class as the column total minus the other three.  Sums whose every
+ *     partial sum is an integer below 2^53 are exact whatever the order.  Non-finite values give unspecified results.  Two runs
+ *     on the same input may differ in the last bits: bitwise run-to-run reproducibility is NOT promised.
+ *   - The call overwrites exactly the 4 * n_columns * n_variants doubles d_sums[0 .. 4 * n_columns * n_variants); nothing else is
+ *     written.  K == 0 writes zeros.  n_variants == 0 is a no-op.  There is no ACCUMULATE flag: rows are the unit a host blocks
+ *     over, and each row's sums are complete after one call.
+ *   - d_sums must be ORDINARY device memory (hipMalloc, pgenhip_device_malloc), not fine-grained or host-mapped memory: the
+ *     kernel adds with hardware FP64 atomics, which such memory does not serve.
+ *   - PGENHIP_ERR_BAD_ARG: n_columns == 0 or > PGENHIP_VSUM_MAX_COLUMNS; v_stride < n_columns with K > 1; d_values NULL with
+ *     K > 0 and n_variants > 0; d_values or d_sums not 8-byte aligned; d_sums NULL with n_variants > 0; unknown flag bits or
+ *     shape ids; a forced shape that does not apply (with a detail string: PGENHIP_VSUM_MFMA needs K >= 1).
+ *     PGENHIP_ERR_TOO_LARGE, before any launch: byte offsets of 2^52 or more (v_stride * K * 8, n_variants * n_columns * 32,
+ *     record_stride * n_variants as in pgenhip_decode_matrix).  A host with more than PGENHIP_VSUM_MAX_COLUMNS columns calls once
+ *     per group of columns (d_values + first column of the group, the same v_stride).
+ * Same launch contract as pgenhip_genotype_counts: device pointers only, no allocation, no synchronisation, queued on the ctx
+ * stream, graph-capturable (the overwrite is a hipMemsetAsync ahead of the kernel where tiles of a row meet in atomics).  No work
+ * counters: these launches do not count against PGENHIP_LAUNCHES_IN_FLIGHT.
+ * flags: a shape (PGENHIP_VSUM_AUTO or a forced one). */
+#define PGENHIP_VSUM_MAX_COLUMNS 16u
+#define PGENHIP_VSUM_AUTO 0u
+#define PGENHIP_VSUM_GENERAL 1u   /* a wave per (row, column), any K, any layout: the correctness baseline */
+#define PGENHIP_VSUM_MFMA 2u      /* the samples of a row summed by the FP64 matrix core (v_mfma_f64_16x16x4_f64), all samples or a kept list, K >= 1: what AUTO takes */
+#define PGENHIP_VSUM_SHAPE_MASK 0xFu
+int pgenhip_variant_sums(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                         uint32_t n_variants, const double *d_values, uint64_t v_stride, uint32_t n_columns, double *d_sums,
+                         uint32_t flags);
+/* Same, with the record of row j at d_base + d_record_off[j] (DEVICE array of u64 byte offsets). */
+int pgenhip_variant_sums_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
+                            const double *d_values, uint64_t v_stride, uint32_t n_columns, double *d_sums, uint32_t flags);
+
 /* ---- numeric genotype matrix (device-resident, asynchronous on the ctx stream) ----
  * The GT text with the fixed bytes removed: element (j, k) is the code pgenhip_decode_emit prints as the k-th field of row j,
  * mapped through a four-entry table.  Rows are selected exactly as in pgenhip_decode_emit / pgenhip_decode_emit_at; a gather that
@@ -463,7 +507,8 @@ typedef enum pgenhip_knob {
     PGENHIP_KNOB_PACK_BLOCKS = 20,       /* pack kernels: grid size in blocks (default 0 = by shape: the work, capped at 8 blocks per CU); tests force small grids */
     PGENHIP_KNOB_SCORE_SLICES = 21,      /* per-sample scores: row ranges per column tile, each summed by one block (default 0 = by shape: as many as fill the chip's resident blocks, of at least 512 rows each); tests put the row count on either side of every plan edge */
     PGENHIP_KNOB_SPAIR_SLICES = 22,      /* pairwise sample tables: row ranges per sample tile, each summed by one block (default 0 = by shape: as many as fill the chip's resident blocks, of at least 256 rows each); tests put the row count on either side of every slice edge */
-    PGENHIP_KNOB_RUNS_ROWS = 7        /* RUNS kernel: rows per work item (default: as many as one wide load / one span holds) */
+    PGENHIP_KNOB_VSUM_BLOCKS = 23,       /* per-variant sums: grid size in blocks (default 0 = by shape: the work, capped at 8 blocks per CU); the MFMA shape also cuts the rows into that many slices, so tests force small grids and the multi-block combine */
+    PGENHIP_KNOB_RUNS_ROWS = 7       /* RUNS kernel: rows per work item (default: as many as one wide load / one span holds) */
 } pgenhip_knob;
 int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value);
 

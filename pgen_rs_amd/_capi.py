@@ -53,6 +53,11 @@ SCORE_AUTO = 0
 SCORE_ROWS = 1
 SCORE_SHAPE_MASK = 0xF
 SCORE_ACCUMULATE = 0x10
+VSUM_MAX_COLUMNS = 16
+VSUM_AUTO = 0
+VSUM_GENERAL = 1
+VSUM_MFMA = 2
+VSUM_SHAPE_MASK = 0xF
 SPAIR_AUTO = 0
 SPAIR_GENERAL = 1
 SPAIR_MFMA = 2
@@ -93,6 +98,7 @@ KNOB_PAIR_BLOCKS = 19
 KNOB_PACK_BLOCKS = 20
 KNOB_SCORE_SLICES = 21
 KNOB_SPAIR_SLICES = 22
+KNOB_VSUM_BLOCKS = 23
 
 
 
@@ -138,6 +144,8 @@ PROTOTYPES = {
     "pgenhip_sample_counts_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_sample_scores": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]),
     "pgenhip_sample_scores_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "pgenhip_variant_sums": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
+    "pgenhip_variant_sums_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_decode_matrix": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_decode_matrix_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_sample_pair_stats": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),

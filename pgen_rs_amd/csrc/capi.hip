@@ -706,6 +706,68 @@ int pgenhip_sample_scores_at(pgenhip_ctx *ctx, const void *d_base, const uint64_
     return sample_scores_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, d_weights, w_stride, n_columns, d_miss, d_scores, flags);
 }
 
+static int variant_sums_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                             const uint64_t *d_record_off, uint32_t n_variants, const double *d_values, uint64_t v_stride,
+                             uint32_t n_columns, double *d_sums, uint32_t flags)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (flags & ~PGENHIP_VSUM_SHAPE_MASK) return fail(PGENHIP_ERR_BAD_ARG, "unknown variant_sums flag");
+    const uint32_t shape = flags & PGENHIP_VSUM_SHAPE_MASK;
+    if (shape > PGENHIP_VSUM_MFMA) return fail(PGENHIP_ERR_BAD_ARG, "variant_sums supports shapes AUTO, GENERAL and MFMA");
+    if (n_columns == 0u || n_columns > PGENHIP_VSUM_MAX_COLUMNS) return fail(PGENHIP_ERR_BAD_ARG, "n_columns must be 1 .. PGENHIP_VSUM_MAX_COLUMNS");
+    const uint32_t K = ctx->kept_count;
+    if (K > 1u && v_stride < n_columns) return fail(PGENHIP_ERR_BAD_ARG, "v_stride < n_columns");
+    if (K != 0u && n_variants && !d_values) return fail(PGENHIP_ERR_BAD_ARG, "d_values is NULL");
+    if ((uintptr_t)d_values & 7u) return fail(PGENHIP_ERR_BAD_ARG, "d_values is not 8-byte aligned");
+    if (n_variants && !d_sums) return fail(PGENHIP_ERR_BAD_ARG, "d_sums is NULL");
+    if ((uintptr_t)d_sums & 7u) return fail(PGENHIP_ERR_BAD_ARG, "d_sums is not 8-byte aligned");
+    if (shape == PGENHIP_VSUM_MFMA && K == 0u) return fail(PGENHIP_ERR_BAD_ARG, "the MFMA shape needs at least one kept sample");
+    // byte offsets are 64-bit arithmetic in the kernel; the bound is decode_matrix's (2^52 bytes).  With a variant list the row
+    // numbers live on the device (as record_off's offsets do) and only the stride itself is bounded
+    constexpr uint64_t kMaxSpan = 1ull << 52;
+    const bool by_stride = n_variants > 1 && !d_record_off;
+    if ((K > 1u && v_stride >= kMaxSpan / 8u / K) || (uint64_t)n_variants * n_columns >= kMaxSpan / 32u ||
+        (by_stride && !d_variant_idx && record_stride >= kMaxSpan / n_variants) || (by_stride && d_variant_idx && record_stride >= kMaxSpan))
+        return fail(PGENHIP_ERR_TOO_LARGE, "variant_sums offsets do not fit the kernel's index types");
+    if (n_variants == 0) return PGENHIP_OK;
+    VsumArgs a;
+    rc = select_rows(ctx, a, d_records, record_stride, d_variant_idx, d_record_off, n_variants);
+    if (rc) return rc;
+    a.kept_mask = ctx->d_count_mask;   // NULL with all samples kept or an identity list
+    a.kept_rank = ctx->d_scount_rank;
+    a.values = d_values;
+    a.v_stride = v_stride;
+    a.n_columns = n_columns;
+    a.sums = d_sums;
+    const size_t out_bytes = sizeof(double) * 4u * n_columns * (size_t)n_variants;
+    if (K == 0u) {   // no sample: zeros
+        HIP_TRY(hipMemsetAsync(d_sums, 0, out_bytes, ctx->stream));
+        return PGENHIP_OK;
+    }
+    if (shape == PGENHIP_VSUM_GENERAL) {
+        HIP_TRY(launch_gt_vsum_general(a, ctx->tune.vsum_blocks, ctx->num_cus, ctx->stream));
+    } else {   // AUTO: the matrix-core shape wherever it applies (K >= 1)
+        if (gt_vsum_mfma_atomic(a)) HIP_TRY(hipMemsetAsync(d_sums, 0, out_bytes, ctx->stream));   // tiles of a row meet in atomics: the kernel only adds
+        HIP_TRY(launch_gt_vsum_mfma(a, ctx->tune.vsum_blocks, ctx->num_cus, ctx->stream));
+    }
+    return PGENHIP_OK;
+}
+
+int pgenhip_variant_sums(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                         uint32_t n_variants, const double *d_values, uint64_t v_stride, uint32_t n_columns, double *d_sums,
+                         uint32_t flags)
+{
+    return variant_sums_core(ctx, d_records, record_stride, d_variant_idx, nullptr, n_variants, d_values, v_stride, n_columns, d_sums, flags);
+}
+
+int pgenhip_variant_sums_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
+                            const double *d_values, uint64_t v_stride, uint32_t n_columns, double *d_sums, uint32_t flags)
+{
+    if (const int rc = check_record_off(ctx, d_record_off, n_variants)) return rc;
+    return variant_sums_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, d_values, v_stride, n_columns, d_sums, flags);
+}
+
 static int decode_matrix_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
                               const uint64_t *d_record_off, uint32_t n_variants, void *d_out, uint64_t out_stride, uint32_t elem_bytes,
                               const void *code_values, uint32_t flags)
@@ -972,6 +1034,7 @@ int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)
         case PGENHIP_KNOB_PAIR_BLOCKS: t.pair_blocks = value > 0 ? value : d.pair_blocks; break;
         case PGENHIP_KNOB_PACK_BLOCKS: t.pack_blocks = value > 0 ? value : d.pack_blocks; break;
         case PGENHIP_KNOB_SPAIR_SLICES: t.spair_slices = value > 0 ? value : d.spair_slices; break;
+        case PGENHIP_KNOB_VSUM_BLOCKS: t.vsum_blocks = value > 0 ? value : d.vsum_blocks; break;
         default: return fail(PGENHIP_ERR_BAD_ARG, "unknown knob");
     }
     return PGENHIP_OK;

@@ -58,6 +58,7 @@ struct Tuning {
     int pair_blocks = 0;           // pairwise kernel: grid size in blocks (0 = by shape, capped per CU)
     int pack_blocks = 0;           // pack kernels: grid size in blocks (0 = by shape, capped per CU)
     int spair_slices = 0;          // pairwise sample tables: row ranges per sample tile (0 = by shape: the chip's resident blocks, at least 256 rows each)
+    int vsum_blocks = 0;           // per-variant sums: grid size in blocks (0 = by shape, capped per CU)
 };
 
 // rows are gathered (variant list or byte offsets): the HAS_VIDX instantiations
@@ -151,7 +152,24 @@ struct ScoreArgs : RowSource {
 // slices_per_tile: row ranges per column tile (0 = by shape)
 hipError_t launch_gt_score(const ScoreArgs &a, int slices_per_tile, int num_cus, hipStream_t stream);
 
-// Numeric genotype matrix (gt_matrix.hip): element (j, k) = the pattern of the code of kept sample k in selected row j.
+// Per-variant sums of per-sample values by genotype code (gt_vsum.hip): for every selected row j, column c < n_columns and code x
+// the FP64 sum over the kept samples k with code x in row j of values[k * v_stride + c], at sums[(j * n_columns + c) * 4 + x].
+struct VsumArgs : RowSource {
+    const uint8_t *kept_mask;     // device or nullptr (all samples): the ctx's count mask (CountArgs::kept_mask)
+    const uint32_t *kept_rank;    // device, with kept_mask: kept samples before each 64-sample chunk
+    const double *values;         // device, 8-byte aligned, K x n_columns
+    uint64_t v_stride;            // doubles between the value rows
+    uint32_t n_columns;           // C, 1 .. 16
+    double *sums;                 // device, 8-byte aligned, ordinary device memory (hardware FP64 atomics)
+};
+// blocks: forced grid size (0 = by shape; tests force small grids to walk the grid-stride loops and the multi-tile combine)
+hipError_t launch_gt_vsum_general(const VsumArgs &a, int blocks, int num_cus, hipStream_t stream);
+// the matrix-core shape: any layout, any keep set with K >= 1.  It only ADDS when gt_vsum_mfma_atomic(a) (rows of more than one
+// tile): the caller zeroes the sums first
+bool gt_vsum_mfma_atomic(const VsumArgs &a);
+hipError_t launch_gt_vsum_mfma(const VsumArgs &a, int blocks, int num_cus, hipStream_t stream);
+
+// Numeric genotype matrix (gt_matrix.hip):element (j, k) = the pattern of the code of kept sample k in selected row j.
 struct MatrixArgs : RowSource {
     const uint32_t *kept_idx;     // device or nullptr (all samples, or an identity list)
     uint32_t kept_count;          // K (== N when kept_idx is nullptr)

@@ -461,6 +461,73 @@ class GtEngine:
             raise ValueError("out must be a float64 tensor with >= K * C entries")
         return out.view(-1)
 
+    # -- per-variant sums of per-sample values by genotype code -----------------------------------
+    def variant_sums(
+        self,
+        records: torch.Tensor,
+        values: torch.Tensor,
+        *,
+        record_stride: Optional[int] = None,
+        variant_idx: Optional[torch.Tensor] = None,
+        out: Optional[torch.Tensor] = None,
+        flags: int = 0,
+        n_variants: Optional[int] = None,
+        records_offset: int = 0,
+    ) -> torch.Tensor:
+        """Per-variant sums of per-sample values, split by genotype code: a ``(n_variants, C, 4)`` float64 CUDA tensor,
+        ``S[j, c, x] = sum of values[k, c] over the kept samples k whose code in row j is x`` (0 hom-ref, 1 het, 2 hom-alt,
+        3 missing).  Every addition is FP64, in no fixed order (include/pgen_hip.h).
+
+        ``values``: float64 CUDA tensor of shape (K, C) or (K,), C <= 16, contiguous along the columns; its row stride is taken
+        from the tensor and row k belongs to the k-th kept sample.  Rows are selected as in ``genotype_counts``.  ``out``: optional
+        float64 CUDA tensor of >= n_variants * C * 4 entries (written from its first element; nothing else is touched).
+        ``flags``: a forced shape (``_capi.VSUM_*``)."""
+        v_stride, n_columns = self._vsum_values(values)
+        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
+        out = self._vsum_out(out, n_variants, n_columns)
+        check(
+            lib.pgenhip_variant_sums(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants,
+                                     _ptr(values), v_stride, n_columns, _ptr(out), flags),
+            "pgenhip_variant_sums",
+        )
+        return out[: n_variants * n_columns * 4].view(n_variants, n_columns, 4)
+
+    def variant_sums_at(self, base: torch.Tensor, record_off: torch.Tensor, values: torch.Tensor, *, out: Optional[torch.Tensor] = None,
+                        flags: int = 0, n_variants: Optional[int] = None) -> torch.Tensor:
+        """``variant_sums`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
+        v_stride, n_columns = self._vsum_values(values)
+        n_variants = self._rows_at(base, record_off, n_variants)
+        out = self._vsum_out(out, n_variants, n_columns)
+        check(
+            lib.pgenhip_variant_sums_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, _ptr(values), v_stride, n_columns,
+                                        _ptr(out), flags),
+            "pgenhip_variant_sums_at",
+        )
+        return out[: n_variants * n_columns * 4].view(n_variants, n_columns, 4)
+
+    def _vsum_values(self, values: torch.Tensor) -> tuple[int, int]:
+        """Checks ``values`` and returns ``(v_stride, n_columns)``."""
+        if not values.is_cuda or values.device.index != self.device:
+            raise ValueError(f"values must live on cuda:{self.device}")
+        if values.dtype != torch.float64 or values.dim() not in (1, 2):
+            raise ValueError("values must be a float64 tensor of shape (K, C) or (K,)")
+        n_columns = values.shape[1] if values.dim() == 2 else 1
+        if values.shape[0] < self.kept_count:
+            raise ValueError("values has fewer than K rows")
+        if values.dim() == 2 and n_columns > 1 and values.shape[0] > 0 and values.stride(1) != 1:
+            raise ValueError("values must be contiguous along its columns")
+        v_stride = values.stride(0) if values.shape[0] > 1 else n_columns
+        return int(v_stride), int(n_columns)
+
+    def _vsum_out(self, out: Optional[torch.Tensor], n_variants: int, n_columns: int) -> torch.Tensor:
+        need = n_variants * n_columns * 4
+        if out is None:
+            return torch.empty(max(need, 1), dtype=torch.float64, device=self.torch_device)
+        self._check_dev(out, "out")
+        if out.dtype != torch.float64 or out.numel() < need:
+            raise ValueError("out must be a float64 tensor with >= n_variants * C * 4 entries")
+        return out.view(-1)
+
     # -- numeric genotype matrix ---------------------------------------------------------------
     def decode_matrix(
         self,

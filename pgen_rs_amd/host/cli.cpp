@@ -90,6 +90,7 @@ const char *kUsage =
     "  freq    Per-variant genotype counts of the kept samples, outputting to stdout\n"
     "  sample-counts  Per-sample genotype counts over the kept variants, outputting to stdout\n"
     "  score   Polygenic scores of the kept samples from a weights file, outputting to stdout\n"
+    "  assoc   Linear regression of quantitative phenotypes on every kept variant, outputting to stdout\n"
     "  matrix  Numeric genotype matrix of the kept variants and samples, outputting to a NumPy .npy file\n"
     "  ld      Pairwise r^2 of the kept variants inside a sliding window, outputting to stdout\n"
     "  kinship Pairwise genotype tables and KING-robust kinship of the kept samples, outputting to stdout\n"
@@ -114,6 +115,14 @@ const char *kUsage =
     "       allele or an ID that is not kept skips the row.  A missing call counts as the variant's mean dosage over the kept samples\n"
     "       (--no-mean-imputation: as 0).  One line per kept sample in psam order: IID ALLELE_CT DENOM <NAME>_SUM ... (--avg: <NAME>_AVG =\n"
     "       SUM / DENOM); weights are rounded to f32, sums are FP64; no byte or digit parity with plink2's .sscore is claimed\n"
+    "assoc  <PFILE_PREFIX> --pheno <FILE> [--pheno-name <A,B,...>] [--covar <FILE>] [--include-var <VAR_QUERY>] [--include-sam <SAM_QUERY>] [-o, --out <OUT_FILE>]\n"
+    "       [--gpus <N>] [--shards <S>] [--block-mib <M>] [--read-threads <T>] [--filter-threads <T>] [--stats]\n"
+    "       FILEs: tab-separated with a header line: IID, then one quantitative value per column; NA, nan and empty cells are missing.\n"
+    "       A kept sample stays only with every chosen phenotype and every covariate.  Per variant and phenotype a linear regression on\n"
+    "       the ALT dosage with an intercept and the covariates: CHROM POS ID REF ALT A1 PHENO OBS_CT MISS_CT A1_FREQ BETA SE T_STAT P\n"
+    "       (NA where the fit is degenerate).  A missing call counts as the variant's mean dosage over the called samples (mean\n"
+    "       imputation); plink2 --glm drops the sample for that variant instead, so no digit parity with plink2 is claimed\n"
+    "assoc  --p-of <T_STAT> <DF>   the two-sided Student t P value of one statistic (no fileset, no device)\n"
     "matrix <PFILE_PREFIX> [--include-var <VAR_QUERY>] [--include-sam <SAM_QUERY>] [--dtype i8|f16|f32] [--missing <X>] [--sample-major]\n"
     "       -o, --out <OUT_FILE.npy> [--gpus <N>] [--shards <S>] [--block-mib <M>] [--read-threads <T>] [--filter-threads <T>] [--stats]\n"
     "       NumPy .npy (version 1.0, C order) of shape (variants kept, samples kept), or (samples, variants) with --sample-major:\n"
@@ -436,6 +445,42 @@ int main(int argc, char **argv)
             if (a.has("stats")) {
                 std::fprintf(stderr, "{\"weights_matched\": %llu, \"weights_flipped\": %llu, \"weights_skipped\": %llu}\n",
                              (unsigned long long)st.score_matched, (unsigned long long)st.score_flipped, (unsigned long long)st.score_skipped);
+                print_stats(st, t_main);
+            }
+            return 0;
+        }
+        if (cmd == "assoc") {
+            if (argc >= 3 && std::string(argv[2]) == "--p-of") {
+                char *e1 = nullptr, *e2 = nullptr;
+                const double t = argc == 5 ? std::strtod(argv[3], &e1) : 0.0, df = argc == 5 ? std::strtod(argv[4], &e2) : 0.0;
+                if (argc != 5 || *argv[3] == '\0' || *e1 != '\0' || *argv[4] == '\0' || *e2 != '\0' || !(df > 0)) usage_error("--p-of takes a statistic and its degrees of freedom (> 0)");
+                std::printf("%.17g\n", student_t_two_sided_p(t, df));
+                return 0;
+            }
+            Args a = parse(argc, argv, 2, {{"pheno", 0}, {"pheno-name", 0}, {"covar", 0}, {"include-var", 0}, {"include-sam", 0}, {"out", 'o'}, {"gpus", 0}, {"shards", 0}, {"block-mib", 0}, {"read-threads", 0}, {"filter-threads", 0}},
+                           {{"stats", 0}});
+            if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
+            if (!a.has("pheno") || a.get("pheno")->empty()) usage_error("the following required arguments were not provided: --pheno <FILE>");
+            if (a.has("covar") && a.get("covar")->empty()) usage_error("a value is required for '--covar <FILE>'");
+            AssocOptions ao;
+            ao.pheno_file = *a.get("pheno");
+            ao.covar_file = a.get("covar").value_or("");
+            if (a.has("pheno-name")) {
+                std::string name;
+                for (const char ch : *a.get("pheno-name") + ",") {
+                    if (ch != ',') {
+                        name += ch;
+                        continue;
+                    }
+                    if (name.empty()) usage_error("--pheno-name takes column names separated by commas");
+                    ao.pheno_names.push_back(name);
+                    name.clear();
+                }
+            }
+            const Pfile pfile = Pfile::from_prefix(a.positional[0]);
+            const OutputStats st = pfile.output_assoc(a.get("include-sam"), a.get("include-var"), ao, a.get("out").value_or(""), output_options(a));
+            if (a.has("stats")) {
+                std::fprintf(stderr, "{\"samples_dropped\": %llu}\n", (unsigned long long)st.assoc_dropped);
                 print_stats(st, t_main);
             }
             return 0;

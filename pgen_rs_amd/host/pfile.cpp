@@ -1074,6 +1074,52 @@ struct ScoreCounter {
     }
 };
 
+// assoc's counter: per block the rows' genotype counts and their per-code sums of every value column (Q's columns, then the
+// residualised phenotypes; uploaded once per shard), sixteen columns per launch; both come back block by block.  Group g's sums of
+// a block are bv x cg x 4 doubles behind those of the groups before it.
+struct AssocCounter {
+    uint32_t R;
+    size_t C, bv;                     // value columns, rows of a full block
+    std::vector<uint32_t> &counts;    // 4 per kept variant
+    std::vector<double> &sums;        // per kept variant C x 4
+    const double *d_values;
+    uint32_t *d_gc, *h_gc;
+    double *d_sums, *h_sums;
+    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, size_t, uint32_t nv, uint32_t) const
+    {
+        if (d_off)
+            check(pgenhip_genotype_counts_at(ctx, d_rec, d_off, nv, d_gc, PGENHIP_COUNT_AUTO), "pgenhip_genotype_counts_at");
+        else
+            check(pgenhip_genotype_counts(ctx, d_rec, R, nullptr, nv, d_gc, PGENHIP_COUNT_AUTO), "pgenhip_genotype_counts");
+        for (size_t c0 = 0; c0 < C; c0 += PGENHIP_VSUM_MAX_COLUMNS) {
+            const uint32_t cg = (uint32_t)std::min<size_t>(PGENHIP_VSUM_MAX_COLUMNS, C - c0);
+            double *dst = d_sums + bv * 4 * c0;
+            if (d_off)
+                check(pgenhip_variant_sums_at(ctx, d_rec, d_off, nv, d_values + c0, C, cg, dst, PGENHIP_VSUM_AUTO), "pgenhip_variant_sums_at");
+            else
+                check(pgenhip_variant_sums(ctx, d_rec, R, nullptr, nv, d_values + c0, C, cg, dst, PGENHIP_VSUM_AUTO), "pgenhip_variant_sums");
+        }
+    }
+    void copy(pgenhip_ctx *ctx, size_t nv) const
+    {
+        check(pgenhip_memcpy_d2h(ctx, h_gc, d_gc, nv * 16), "D2H counts");
+        for (size_t c0 = 0; c0 < C; c0 += PGENHIP_VSUM_MAX_COLUMNS) {
+            const size_t cg = std::min<size_t>(PGENHIP_VSUM_MAX_COLUMNS, C - c0);
+            check(pgenhip_memcpy_d2h(ctx, h_sums + bv * 4 * c0, d_sums + bv * 4 * c0, nv * cg * 4 * sizeof(double)), "D2H sums");
+        }
+    }
+    void collect(size_t b0, size_t nv) const
+    {
+        std::memcpy(counts.data() + 4 * b0, h_gc, nv * 16);
+        for (size_t c0 = 0; c0 < C; c0 += PGENHIP_VSUM_MAX_COLUMNS) {
+            const size_t cg = std::min<size_t>(PGENHIP_VSUM_MAX_COLUMNS, C - c0);
+            const double *src = h_sums + bv * 4 * c0;
+            for (size_t j = 0; j < nv; j++) std::memcpy(sums.data() + ((b0 + j) * C + c0) * 4, src + j * cg * 4, cg * 4 * sizeof(double));
+        }
+    }
+    void finish(pgenhip_ctx *) const {}
+};
+
 // matrix's "counter": every block is decoded into one device buffer, copied back and written to its place in the .npy file.
 // Variant-major: a block is nv consecutive rows of the file, one pwrite.  Sample-major: a block is a column band, K pieces of
 // nv elements, written from a few threads.
@@ -1530,6 +1576,282 @@ OutputStats Pfile::output_score(const std::optional<std::string> &sam_query, con
             }
         }
         text += '\n';
+    }
+    st.body_bytes = text.size() - st.header_bytes;
+    st.file_bytes = text.size();
+    write_text(text, filename);
+    st.seconds_body = now_s() - t_body;
+    return st;
+}
+
+ValueTable read_value_table(const std::string &path)
+{
+    const std::string data = read_file(path);
+    ValueTable vt;
+    TsvReader reader(data, !data.empty() && data[0] == '#' ? 1 : 0);
+    const StringRecord &head = reader.headers();
+    if (head.size() < 2) throw PfileError(path + " line 1: a value file has an IID column and at least one value column");
+    vt.names.assign(head.begin() + 1, head.end());
+    const size_t C = vt.names.size();
+    // the line a record starts on: the newlines in front of it, counted as the reader moves on
+    size_t counted = 0, line = 1;
+    auto line_at = [&](size_t pos) {
+        for (; counted < pos; counted++) line += data[counted] == '\n';
+        for (size_t p = pos; p < data.size() && (data[p] == '\n' || data[p] == '\r'); p++) {   // the empty lines the reader skips
+            line += data[p] == '\n';
+            counted = p + 1;
+        }
+        return line;
+    };
+    std::map<std::string, size_t> seen;   // IID -> line
+    StringRecord rec;
+    for (;;) {
+        const size_t at = line_at(reader.position());
+        bool more;
+        try {
+            more = reader.next(rec);
+        } catch (const CsvError &) {
+            throw PfileError(path + " line " + std::to_string(at) + ": expected " + std::to_string(C + 1) + " tab-separated cells like the header's");
+        }
+        if (!more) break;
+        const auto dup = seen.emplace(rec[0], at);
+        if (!dup.second)
+            throw PfileError(path + " line " + std::to_string(at) + ": IID '" + rec[0] + "' occurs twice (first on line " + std::to_string(dup.first->second) + ")");
+        for (size_t c = 0; c < C; c++) {
+            const std::string &cell = rec[1 + c];
+            if (cell.empty() || cell == "NA" || cell == "nan") {
+                vt.x.push_back(std::nan(""));
+                continue;
+            }
+            char *end = nullptr;
+            const double x = std::strtod(cell.c_str(), &end);
+            if (*end != '\0' || !std::isfinite(x))
+                throw PfileError(path + " line " + std::to_string(at) + ": value '" + cell + "' of column " + vt.names[c] + " is not a finite number, NA or nan");
+            vt.x.push_back(x);
+        }
+        vt.iids.push_back(rec[0]);
+    }
+    return vt;
+}
+
+namespace {
+
+// ln Gamma(a + 1/2) - ln Gamma(a): the difference of two lgamma values loses 1e-16 of their size (6e6 at a = 5e5), so from a = 64 on
+// the asymptotic series of the ratio itself
+double lgamma_half_step(double a)
+{
+    if (a < 64.0) return std::lgamma(a + 0.5) - std::lgamma(a);
+    const double i = 1.0 / a, i2 = i * i;
+    return 0.5 * std::log(a) + i * (-1.0 / 8.0 + i2 * (1.0 / 192.0 + i2 * (-1.0 / 640.0 + i2 * (17.0 / 14336.0))));
+}
+
+// the continued fraction of the incomplete beta function by the modified Lentz method
+double beta_cf(double a, double b, double x)
+{
+    const double tiny = 1e-300, eps = 1e-16;
+    const double qab = a + b, qap = a + 1.0, qam = a - 1.0;
+    double c = 1.0, d = 1.0 - qab * x / qap;
+    if (std::fabs(d) < tiny) d = tiny;
+    d = 1.0 / d;
+    double h = d;
+    for (int m = 1; m <= 100000; m++) {
+        const double m2 = 2.0 * m;
+        double aa = m * (b - m) * x / ((qam + m2) * (a + m2));
+        d = 1.0 + aa * d;
+        if (std::fabs(d) < tiny) d = tiny;
+        c = 1.0 + aa / c;
+        if (std::fabs(c) < tiny) c = tiny;
+        d = 1.0 / d;
+        h *= d * c;
+        aa = -(a + m) * (qab + m) * x / ((a + m2) * (qap + m2));
+        d = 1.0 + aa * d;
+        if (std::fabs(d) < tiny) d = tiny;
+        c = 1.0 + aa / c;
+        if (std::fabs(c) < tiny) c = tiny;
+        d = 1.0 / d;
+        const double del = d * c;
+        h *= del;
+        if (std::fabs(del - 1.0) < eps) break;
+    }
+    return h;
+}
+
+}  // namespace
+
+double student_t_two_sided_p(double t, double df)
+{
+    if (std::isnan(t) || std::isnan(df) || df <= 0.0) return std::nan("");
+    if (std::isinf(t)) return 0.0;
+    if (t == 0.0) return 1.0;
+    const double a = 0.5 * df, b = 0.5, t2 = t * t;
+    const double x = df / (df + t2), y = t2 / (df + t2);                 // y = 1 - x without the cancellation
+    // ln of x^a y^b / B(a, b): a ln x = -a log1p(t^2 / df); B(a, 1/2) = Gamma(a) sqrt(pi) / Gamma(a + 1/2)
+    const double front = std::exp(lgamma_half_step(a) - 0.5 * std::log(M_PI) - a * std::log1p(t2 / df) + b * std::log(y));
+    if (x < (a + 1.0) / (a + b + 2.0)) return front * beta_cf(a, b, x) / a;
+    return 1.0 - front * beta_cf(b, a, y) / b;
+}
+
+OutputStats Pfile::output_assoc(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
+                                const AssocOptions &aopt, const std::string &filename, const OutputOptions &opt) const
+{
+    OutputStats st;
+    const double t0 = now_s();
+    const ValueTable ph = read_value_table(aopt.pheno_file);
+    ValueTable cv;
+    if (!aopt.covar_file.empty()) cv = read_value_table(aopt.covar_file);
+    std::vector<size_t> pcol;   // the chosen phenotype columns
+    if (aopt.pheno_names.empty()) {
+        for (size_t c = 0; c < ph.names.size(); c++) pcol.push_back(c);
+    } else {
+        for (const std::string &name : aopt.pheno_names) {
+            const size_t c = std::find(ph.names.begin(), ph.names.end(), name) - ph.names.begin();
+            if (c == ph.names.size()) throw PfileError(aopt.pheno_file + " line 1: no phenotype column named '" + name + "'");
+            pcol.push_back(c);
+        }
+    }
+    const size_t P = pcol.size(), ncov = cv.names.size(), m = 1 + ncov, C = m + P;
+
+    Selection sel = select(sam_query, var_query, opt.filter_threads);
+    size_t iid = sel.sam_header.size();   // vcf_header's rule (:114-126): the first column named IID
+    for (size_t c = 0; c < sel.sam_header.size(); c++) {
+        if (sel.sam_header[c] == "IID") {
+            iid = c;
+            break;
+        }
+    }
+    if (iid == sel.sam_header.size()) throw PfileError("IID not among the headers of " + psam_path());
+    static const char *const kCols[5] = {"CHROM", "POS", "ID", "REF", "ALT"};
+    size_t col[5];
+    for (int c = 0; c < 5; c++) {
+        col[c] = std::find(sel.var_header.begin(), sel.var_header.end(), std::string(kCols[c])) - sel.var_header.begin();
+        if (col[c] == sel.var_header.size()) throw PfileError(std::string(kCols[c]) + " not among the headers of " + pvar_path());
+    }
+
+    // complete cases: a kept sample stays only with every chosen phenotype and every covariate
+    std::map<std::string, size_t> ph_row, cv_row;
+    for (size_t i = 0; i < ph.iids.size(); i++) ph_row.emplace(ph.iids[i], i);
+    for (size_t i = 0; i < cv.iids.size(); i++) cv_row.emplace(cv.iids[i], i);
+    IdxRecords stay;
+    std::vector<double> y, x;   // n x P phenotypes, n x ncov covariates
+    for (auto &sr : sel.sam_idx_rcs) {
+        const auto pi = ph_row.find(sr.second.at(iid));
+        const auto ci = ncov ? cv_row.find(sr.second.at(iid)) : cv_row.end();
+        bool complete = pi != ph_row.end() && (!ncov || ci != cv_row.end());
+        for (size_t p = 0; complete && p < P; p++) complete = !std::isnan(ph.x[pi->second * ph.names.size() + pcol[p]]);
+        for (size_t c = 0; complete && c < ncov; c++) complete = !std::isnan(cv.x[ci->second * ncov + c]);
+        if (!complete) continue;
+        for (size_t p = 0; p < P; p++) y.push_back(ph.x[pi->second * ph.names.size() + pcol[p]]);
+        for (size_t c = 0; c < ncov; c++) x.push_back(cv.x[ci->second * ncov + c]);
+        stay.push_back(std::move(sr));
+    }
+    st.assoc_dropped = sel.sam_idx_rcs.size() - stay.size();
+    sel.sam_idx_rcs = std::move(stay);
+    const size_t n = sel.sam_idx_rcs.size();
+    if (n == 0) throw PfileError("no kept sample has every chosen phenotype of " + aopt.pheno_file + (ncov ? " and every covariate of " + aopt.covar_file : std::string()));
+    if (n < m + 2)
+        throw PfileError("too few samples: " + std::to_string(n) + " complete samples leave " + std::to_string((long long)n - (long long)m - 1) +
+                         " degrees of freedom for an intercept, " + std::to_string(ncov) + " covariates and the genotype");
+    const double df = (double)(n - m - 1);
+
+    // the value columns, n x C: Q's m columns (modified Gram-Schmidt, applied twice), then the residualised phenotypes
+    std::vector<double> values(n * C, 0.0);
+    auto at = [&](size_t k, size_t c) -> double & { return values[k * C + c]; };
+    auto project_out = [&](size_t c, size_t upto) {   // column c minus its parts along columns [0, upto), twice
+        for (int pass = 0; pass < 2; pass++)
+            for (size_t q = 0; q < upto; q++) {
+                double dot = 0.0;
+                for (size_t k = 0; k < n; k++) dot += at(k, q) * at(k, c);
+                for (size_t k = 0; k < n; k++) at(k, c) -= dot * at(k, q);
+            }
+    };
+    auto norm = [&](size_t c) {
+        double ss = 0.0;
+        for (size_t k = 0; k < n; k++) ss += at(k, c) * at(k, c);
+        return std::sqrt(ss);
+    };
+    for (size_t c = 0; c < m; c++) {
+        for (size_t k = 0; k < n; k++) at(k, c) = c == 0 ? 1.0 : x[k * ncov + (c - 1)];
+        const double before = norm(c);
+        project_out(c, c);
+        const double after = norm(c);
+        if (!(after > 1e-10 * before))
+            throw PfileError(aopt.covar_file + ": covariate " + (c ? cv.names[c - 1] : std::string("(intercept)")) + " is collinear with the intercept and the covariates before it");
+        for (size_t k = 0; k < n; k++) at(k, c) /= after;
+    }
+    std::vector<double> rr(P, 0.0);
+    for (size_t p = 0; p < P; p++) {
+        for (size_t k = 0; k < n; k++) at(k, m + p) = y[k * P + p];
+        project_out(m + p, m);
+        for (size_t k = 0; k < n; k++) rr[p] += at(k, m + p) * at(k, m + p);
+    }
+    st.seconds_filter = now_s() - t0;
+
+    const KeptSamples kept = check_selection(*this, sel);
+    const size_t V = sel.var_idx_rcds.size();
+    st.variants = V;
+    st.samples_kept = n;
+
+    std::vector<uint32_t> counts(4 * V, 0u);
+    std::vector<double> sums(V * C * 4, 0.0);
+    const double t_body = now_s();
+    if (V != 0) {   // else the header alone and no device is touched
+        const uint32_t R = variant_record_size();
+        count_blocks(*this, sel.var_idx_rcds, kept, opt, "no HIP device: the assoc path has no CPU fallback", st, [&](DeviceCtx &ctx, uint64_t bv) {
+            const size_t b = (size_t)bv;
+            double *d_values = ctx.device<double>(n * C * sizeof(double), "device values");
+            check(pgenhip_memcpy_h2d(ctx.get(), d_values, values.data(), n * C * sizeof(double)), "H2D values");
+            check(pgenhip_wait(ctx.get()), "pgenhip_wait");
+            return AssocCounter{R, C, b, counts, sums, d_values,
+                                ctx.device<uint32_t>(16 * b, "device variant counts"), ctx.pinned<uint32_t>(16 * b, "pinned variant counts"),
+                                ctx.device<double>(b * C * 4 * sizeof(double), "device sums"), ctx.pinned<double>(b * C * 4 * sizeof(double), "pinned sums")};
+        });
+    }
+
+    std::string text = "#CHROM\tPOS\tID\tREF\tALT\tA1\tPHENO\tOBS_CT\tMISS_CT\tA1_FREQ\tBETA\tSE\tT_STAT\tP\n";
+    st.header_bytes = text.size();
+    char buf[64];
+    auto number = [&](double v) {
+        std::snprintf(buf, sizeof buf, "%.12g", v);
+        text += '\t';
+        text += buf;
+    };
+    for (size_t j = 0; j < V; j++) {
+        const StringRecord &vr = sel.var_idx_rcds[j].second;
+        const double c1 = counts[4 * j + 1], c2 = counts[4 * j + 2], c3 = counts[4 * j + 3], called = (double)counts[4 * j] + c1 + c2;
+        const double mu = called > 0 ? (c1 + 2.0 * c2) / called : 0.0;
+        const double *S = sums.data() + j * C * 4;
+        auto tv = [&](size_t c) { return S[4 * c + 1] + 2.0 * S[4 * c + 2] + mu * S[4 * c + 3]; };
+        const double gg = c1 + 4.0 * c2 + mu * mu * c3;
+        double denom = gg;
+        for (size_t q = 0; q < m; q++) denom -= tv(q) * tv(q);
+        for (size_t p = 0; p < P; p++) {
+            for (int c = 0; c < 5; c++) {
+                if (c) text += '\t';
+                text += vr.at(col[c]);
+            }
+            text += '\t';
+            text += vr.at(col[4]);
+            text += '\t';
+            text += ph.names[pcol[p]];
+            text += '\t';
+            append_u64(text, n);
+            text += '\t';
+            append_u64(text, counts[4 * j + 3]);
+            if (called > 0) number(0.5 * mu);
+            else text += "\tNA";
+            const double b = tv(m + p);
+            const double rss = rr[p] - b * b / denom;
+            if (!(called > 0) || !(denom > 1e-12 * gg) || !(rss > 0)) {
+                text += "\tNA\tNA\tNA\tNA\n";
+                continue;
+            }
+            const double beta = b / denom, se = std::sqrt(rss / df / denom), tstat = beta / se;
+            number(beta);
+            number(se);
+            number(tstat);
+            number(student_t_two_sided_p(tstat, df));
+            text += '\n';
+        }
     }
     st.body_bytes = text.size() - st.header_bytes;
     st.file_bytes = text.size();

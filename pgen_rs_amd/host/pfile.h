@@ -118,6 +118,27 @@ struct ScoreWeights {
 };
 ScoreWeights read_score_weights(const std::string &path);
 
+// `assoc`: the per-sample value files
+struct AssocOptions {
+    std::string pheno_file;                 // --pheno: IID, then one quantitative phenotype per column
+    std::vector<std::string> pheno_names;   // --pheno-name: the columns used (empty: all)
+    std::string covar_file;                 // --covar: IID, then one covariate per column (empty: the intercept alone)
+};
+
+// A `assoc` pheno / covar file: tab-separated, a header line (a leading '#' allowed), then one row per sample: IID, one value per
+// column; NA, nan and empty cells are missing (NaN here).  read_value_table throws a PfileError that names the line for a cell
+// that is not a number, a row with another number of cells than the header, and an IID that occurs twice.
+struct ValueTable {
+    std::vector<std::string> names;          // the value columns' header cells
+    std::vector<std::string> iids;           // per row
+    std::vector<double> x;                   // rows x names.size()
+};
+ValueTable read_value_table(const std::string &path);
+
+// two-sided P of a Student t statistic with df degrees of freedom: I_{df / (df + t^2)}(df / 2, 1 / 2), the regularised incomplete
+// beta function by a Lentz continued fraction (no library)
+double student_t_two_sided_p(double t, double df);
+
 // `kinship`: what is printed and how the kept samples are cut into rank tiles on the device
 struct KinshipOptions {
     bool counts = false;              // --counts: the sixteen cells of the pair's table behind KINSHIP
@@ -132,6 +153,7 @@ struct OutputStats {
     uint64_t file_bytes = 0;                                                     // what the output file holds (BGZF: compressed)
     double seconds_filter = 0, seconds_body = 0, seconds_kernel = 0;
     uint64_t score_matched = 0, score_flipped = 0, score_skipped = 0;            // `score`: weights rows used, of them REF-effect rows, rows not used
+    uint64_t assoc_dropped = 0;                                                  // `assoc`: kept samples dropped for a missing phenotype or covariate
     double seconds_setup = 0;   // inside seconds_body: HIP runtime start, contexts, device and pinned allocations of the slowest shard, before its first block is staged
 };
 
@@ -220,6 +242,22 @@ class Pfile {
     OutputStats output_score(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
                              const std::string &weights_file, const std::string &filename, const ScoreOptions &sopt,
                              const OutputOptions &opt = OutputOptions()) const;
+
+    // `assoc` (not in the reference): a linear regression of every chosen phenotype on every kept variant's ALT dosage with an
+    // intercept and the covariates, over the kept samples that have every chosen phenotype and every covariate (complete cases); a
+    // missing call counts as the variant's mean dosage over the called samples (mean imputation, as in `score`; plink2 --glm drops
+    // the sample for that variant instead, so no digit parity with it is claimed).  The host orthonormalises [1, covariates]
+    // (modified Gram-Schmidt, twice) into Q and residualises every phenotype, r_p = y_p - Q Q' y_p; Q's columns and the r_p go up
+    // once per shard as K x (m + P) doubles.  Per block (freq's block loop and shards) pgenhip_genotype_counts gives c0 .. c3 and
+    // pgenhip_variant_sums, at most PGENHIP_VSUM_MAX_COLUMNS columns per launch, the four per-code sums S[v][x] of every column;
+    // 16 + 32 (m + P) bytes per row come back.  With called = c0 + c1 + c2, mu = (c1 + 2 c2) / called, t_v = S[v][1] + 2 S[v][2]
+    // + mu S[v][3], gg = c1 + 4 c2 + mu^2 c3 and denom = gg - sum over Q's columns of t_q^2: BETA = t_r / denom, rss = r'r -
+    // t_r^2 / denom, SE = sqrt(rss / (n - m - 1) / denom), T_STAT = BETA / SE, P two-sided Student t.  One line per variant and
+    // phenotype: CHROM POS ID REF ALT A1 PHENO OBS_CT MISS_CT A1_FREQ BETA SE T_STAT P (%.12g; NA where called == 0, denom <=
+    // 1e-12 gg or rss <= 0).  Fewer than m + 2 complete samples or collinear covariates: an error before any device is touched.
+    // No kept variant: the header alone.  filename empty: stdout.
+    OutputStats output_assoc(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
+                             const AssocOptions &aopt, const std::string &filename, const OutputOptions &opt = OutputOptions()) const;
 
     // `matrix` (not in the reference): the additive-coded genotype matrix of the kept variants and samples as a NumPy .npy file
     // (version 1.0, C order, data on a multiple of 64 bytes), decoded on the GPU(s) (pgenhip_decode_matrix / _at) block by block and
