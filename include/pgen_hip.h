@@ -508,6 +508,7 @@ typedef enum pgenhip_knob {
     PGENHIP_KNOB_SCORE_SLICES = 21,      /* per-sample scores: row ranges per column tile, each summed by one block (default 0 = by shape: as many as fill the chip's resident blocks, of at least 512 rows each); tests put the row count on either side of every plan edge */
     PGENHIP_KNOB_SPAIR_SLICES = 22,      /* pairwise sample tables: row ranges per sample tile, each summed by one block (default 0 = by shape: as many as fill the chip's resident blocks, of at least 256 rows each); tests put the row count on either side of every slice edge */
     PGENHIP_KNOB_VSUM_BLOCKS = 23,       /* per-variant sums: grid size in blocks (default 0 = by shape: the work, capped at 8 blocks per CU); the MFMA shape also cuts the rows into that many slices, so tests force small grids and the multi-block combine */
+    PGENHIP_KNOB_STORE_POLICY = 24,      /* stream kernel (row items, full lines through it, RUNS): how the text is stored. 0 (default) the measured rule: non-temporal write-through stores (sc1 nt: the line leaves the L2 with the store) on launches of more than 1 GB of text whose rows span several 16-KiB work items, or one and up to 4.5 GB; non-temporal stores elsewhere. 1 non-temporal stores everywhere, 2 write-through stores everywhere (tests force both at small sizes; A/B probes); other values are refused. The other emit kernels store as before whatever the value */
     PGENHIP_KNOB_RUNS_ROWS = 7       /* RUNS kernel: rows per work item (default: as many as one wide load / one span holds) */
 } pgenhip_knob;
 int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value);

@@ -99,6 +99,7 @@ KNOB_PACK_BLOCKS = 20
 KNOB_SCORE_SLICES = 21
 KNOB_SPAIR_SLICES = 22
 KNOB_VSUM_BLOCKS = 23
+KNOB_STORE_POLICY = 24
 
 
 

@@ -1035,6 +1035,10 @@ int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)
         case PGENHIP_KNOB_PACK_BLOCKS: t.pack_blocks = value > 0 ? value : d.pack_blocks; break;
         case PGENHIP_KNOB_SPAIR_SLICES: t.spair_slices = value > 0 ? value : d.spair_slices; break;
         case PGENHIP_KNOB_VSUM_BLOCKS: t.vsum_blocks = value > 0 ? value : d.vsum_blocks; break;
+        case PGENHIP_KNOB_STORE_POLICY:
+            if (value < 0 || value > 2) return fail(PGENHIP_ERR_BAD_ARG, "store policy must be 0 (rule), 1 (nt) or 2 (nt sc1)");
+            t.store_policy = value;
+            break;
         default: return fail(PGENHIP_ERR_BAD_ARG, "unknown knob");
     }
     return PGENHIP_OK;

@@ -146,9 +146,87 @@ __device__ __forceinline__ void lds_flag_write(uint32_t off, uint32_t value)
 // ---- shared by the subset kernels (gt_scan.hip, gt_pick.hip) -------------------------------------
 typedef uint32_t gt_v4u __attribute__((ext_vector_type(4)));
 
+// ---- the 16-byte text / compact-record store of the emit kernels ----------------------------------
+// The policy is a template parameter of the kernel, chosen on the host per launch (Tuning::store_policy), never a branch per store:
+//   kStorePlain  global_store_dwordx4            the line stays in the XCD's L2, dirty
+//   kStoreNt     global_store_dwordx4 nt         (the measured default since round 1) streaming hint; the line still stays dirty in L2
+//   kStoreNtWt   global_store_dwordx4 sc1 nt     write-through: the line leaves L2 with the store, nothing is left for the kernel's end
+// hipcc has no builtin for the third form.  The asm store is not in the compiler's vmcnt bookkeeping (a later compiler wait then only
+// waits for more than it needs: the counter is in order) and ends in s_nop 1, so that the next instruction cannot overwrite the
+// data registers before the store has read them.
+enum : int { kStorePlain = 0, kStoreNt = 1, kStoreNtWt = 2 };
+
+template <int POLICY>
+__device__ __forceinline__ void store_chunk(uint8_t *dst, gt_v4u v)
+{
+    static_assert(POLICY == kStorePlain || POLICY == kStoreNt || POLICY == kStoreNtWt, "store policy");
+    if (POLICY == kStoreNtWt)
+        asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
+    else if (POLICY == kStoreNt)
+        __builtin_nontemporal_store(v, reinterpret_cast<gt_v4u *>(dst));
+    else
+        *reinterpret_cast<gt_v4u *>(dst) = v;
+}
+
+template <int POLICY>
+__device__ __forceinline__ void store_chunk(uint8_t *dst, const u32x4 &v)
+{
+    store_chunk<POLICY>(dst, gt_v4u{v.x, v.y, v.z, v.w});
+}
+
 // The subset kernels' chunk stores: non-temporal like the stream kernel's (the text is not read again on the device; two libraries
 // alternated on one box, profiles/r03_logs/subset_nt_stores_ab.log: level to +3 %)
 __device__ __forceinline__ void subset_store16(uint8_t *dst, gt_v4u v) { __builtin_nontemporal_store(v, reinterpret_cast<gt_v4u *>(dst)); }
+
+// ---- kept-list staging of the subset kernels ---------------------------------------------------
+// tab[i] = entry(src[i]) for i in [0, n); tab[-pad_before .. -1] and tab[n .. n + pad_after) = 0 (pad_before + pad_after <= 64).
+// Written as `for (r ...) tab[r] = entry(src[r])` the loop compiles to load, s_waitcnt vmcnt(0), ds_write per iteration: one load
+// in flight per thread and one full round trip per THREADS entries in front of the block's first record load (20 of them for the
+// 5 008 entries of the compact pass at 1 % of 500 000).  Here a thread issues the loads of a whole batch — kBatch 16-byte loads of
+// four consecutive entries each — before its first LDS write.  `src` is 4-byte aligned (a slice of the 16-byte-aligned kept list
+// that starts at any rank): the up to three entries in front of its first 16-byte boundary and behind its last one travel as
+// single loads, together with the pad entries.  Call from all THREADS threads of the block; the caller's barrier follows.
+template <uint32_t THREADS, typename EntryFn>
+__device__ __forceinline__ void stage_kept_list(uint16_t *tab, uint32_t pad_before, const uint32_t *__restrict__ src, uint32_t n, uint32_t pad_after,
+                                                uint32_t tid, EntryFn entry)
+{
+    constexpr uint32_t kBatch = 4;
+    const uint32_t head = min((0u - (uint32_t)((uintptr_t)src >> 2)) & 3u, n);   // entries in front of the first 16-byte boundary
+    const uint32_t n_quads = (n - head) >> 2;
+    const uint32_t tail0 = head + 4u * n_quads;                                   // first entry behind the last whole quad
+    // the edges travel with the first batch: e counts pad_before | head | tail | pad_after
+    const uint32_t e = tid;
+    const uint32_t n_edge = pad_before + head + (n - tail0) + pad_after;
+    const int32_t er = e < pad_before + head ? (int32_t)e - (int32_t)pad_before : (int32_t)(tail0 + (e - pad_before - head));
+    const bool e_on = e < n_edge, e_real = e_on && er >= 0 && (uint32_t)er < n;
+    const gt_v4u *__restrict__ const src4 = reinterpret_cast<const gt_v4u *>(src + head);
+    // Loads are clamped, not masked (a thread without a quad re-reads the last one; block-uniform branches only): masked loads
+    // come out as one branch each, and the compiler then pairs every load with its LDS write again.
+    uint32_t ev = 0u;
+    if (n != 0u) ev = src[min((uint32_t)max(er, 0), n - 1u)];
+    auto batch = [&](uint32_t q0) {
+        gt_v4u v[kBatch];
+#pragma unroll
+        for (uint32_t b = 0; b < kBatch; b++) v[b] = src4[min(q0 + b * THREADS, n_quads - 1u)];
+#pragma unroll
+        for (uint32_t b = 0; b < kBatch; b++) asm volatile("" : "+v"(v[b]));   // (all issued by here: no load sinks into the branch of its write)
+#pragma unroll
+        for (uint32_t b = 0; b < kBatch; b++) {
+            const uint32_t q = q0 + b * THREADS;
+            if (q < n_quads) {
+                uint16_t *const d = tab + head + 4u * q;
+                d[0] = entry(v[b].x);
+                d[1] = entry(v[b].y);
+                d[2] = entry(v[b].z);
+                d[3] = entry(v[b].w);
+            }
+        }
+    };
+    if (n_quads != 0u) batch(tid);                                                // straight-line: the edge load and the first batch's leave together
+    asm volatile("" : "+v"(ev));   // (entry(ev), and with it the wait for the edge load, stays behind the first batch)
+    if (e_on) tab[er] = e_real ? entry(ev) : (uint16_t)0;
+    for (uint32_t q0 = tid + THREADS * kBatch; q0 < n_quads; q0 += THREADS * kBatch) batch(q0);   // (lists of more than 16 * THREADS entries)
+}
 
 // ---- shared by the count kernels (gt_count.hip, gt_scount.hip) ---------------------------------
 // aligned non-temporal 16-byte record load

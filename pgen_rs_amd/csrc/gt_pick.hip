@@ -129,8 +129,7 @@ __global__ __launch_bounds__(kThreads) void gt_pick_kernel(EmitArgs a, PickParam
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t K = a.kept_count;
     if (!IDENT) {
-        for (uint32_t r = tid; r < kPadBefore + K + kPadAfter; r += (uint32_t)kThreads)
-            s_tab[r] = r >= kPadBefore && r < kPadBefore + K ? pick_entry(a.kept_idx[r - kPadBefore]) : (uint16_t)0;
+        stage_kept_list<kThreads>(s_tab + kPadBefore, kPadBefore, a.kept_idx, K, kPadAfter, tid, [](uint32_t s) { return pick_entry(s); });
     }
     for (uint32_t r = tid; r < (uint32_t)kWaves * (kMaxPackedRows + 1) * 8u; r += (uint32_t)kThreads) (&s_heads[0][0])[r] = 0u;
     __syncthreads();
@@ -391,8 +390,7 @@ __global__ __launch_bounds__(kThreads) void gt_pick_lines_kernel(EmitArgs a, Pic
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t K = a.kept_count;
     if (!IDENT) {
-        for (uint32_t r = tid; r < kPadBefore + K + kPadAfter; r += (uint32_t)kThreads)
-            s_tab[r] = r >= kPadBefore && r < kPadBefore + K ? pick_entry(a.kept_idx[r - kPadBefore]) : (uint16_t)0;
+        stage_kept_list<kThreads>(s_tab + kPadBefore, kPadBefore, a.kept_idx, K, kPadAfter, tid, [](uint32_t s) { return pick_entry(s); });
     }
     __syncthreads();
     const uint16_t *const s_idx = s_tab + kPadBefore;

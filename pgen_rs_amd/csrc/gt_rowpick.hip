@@ -60,9 +60,16 @@ __global__ __launch_bounds__(kThreads) void gt_rowpick_kernel(EmitArgs a, ScanAr
     uint8_t *const stage = s_mem + table_bytes(K) + rank_bytes(n_seg) + wave * (kStageBytes + codes_bytes(K));
     uint8_t *const codes = stage + kStageBytes;
 
-    for (uint32_t r = tid; r < K + 8u; r += (uint32_t)kThreads)
-        s_idx[r] = r < K ? (uint16_t)(a.kept_idx[r] & (kSegSamples - 1u)) : (uint16_t)0;   // offset inside the sample's segment
-    for (uint32_t g = tid; g <= n_seg; g += (uint32_t)kThreads) s_rank[g] = sc.seg_rank[g];
+    // (stage_kept_list, gt_common.hip.h: the loads of a batch in flight together, eight zero entries of slack behind the list)
+    stage_kept_list<kThreads>(s_idx, 0u, a.kept_idx, K, 8u, tid, [](uint32_t s) { return (uint16_t)(s & (kSegSamples - 1u)); });   // offset inside the sample's segment
+    for (uint32_t g0 = tid; g0 <= n_seg; g0 += 4u * (uint32_t)kThreads) {
+        uint32_t rk[4];
+#pragma unroll
+        for (uint32_t b = 0; b < 4u; b++) rk[b] = sc.seg_rank[min(g0 + b * (uint32_t)kThreads, n_seg)];   // (clamped, not masked: four loads back to back)
+#pragma unroll
+        for (uint32_t b = 0; b < 4u; b++)
+            if (g0 + b * (uint32_t)kThreads <= n_seg) s_rank[g0 + b * (uint32_t)kThreads] = rk[b];
+    }
     for (uint32_t i = lane; i < codes_bytes(K); i += 64u) codes[i] = 0;                     // (the slack bytes are read, never stored)
     __syncthreads();
 

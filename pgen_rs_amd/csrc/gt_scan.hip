@@ -113,10 +113,12 @@ __global__ __launch_bounds__(kThreads) void gt_scan_pick_kernel(EmitArgs a, Scan
             for (uint64_t n = lane; n < rows; n += 64ull) row_text(a, j0 + n * row_step)[4ull * K] = (uint8_t)'\n';
         return;
     }
-    for (uint32_t r = tid; r < seg_cnt + 16u; r += (uint32_t)kThreads) {
-        const uint32_t s16 = r < seg_cnt ? a.kept_idx[seg_k0 + r] - seg * kSegSamples : 0u;  // 16 entries of slack for the flush's fifth code / second group
-        s_idx[r] = (uint16_t)(((s16 & 3u) << 13) | (s16 >> 2));
-    }
+    // (stage_kept_list, gt_common.hip.h: the loads of a batch in flight together; 16 zero entries of slack for the flush's fifth code / second group)
+    const uint32_t seg_s0 = seg * kSegSamples;
+    stage_kept_list<kThreads>(s_idx, 0u, a.kept_idx + seg_k0, seg_cnt, 16u, tid, [seg_s0](uint32_t s) {
+        const uint32_t s16 = s - seg_s0;
+        return (uint16_t)(((s16 & 3u) << 13) | (s16 >> 2));
+    });
     __syncthreads();
     if (rows == 0ull) return;
 
@@ -255,8 +257,9 @@ __global__ __launch_bounds__(kThreads) void gt_compact_kernel(EmitArgs a, ScanAr
     const uint32_t n_foreign = min((cb1 << 2) - seg_k1, K - seg_k1);   // 0 .. 3
     uint32_t f_smp = 0u;         // lane i < n_foreign: sample of rank seg_k1 + i
     if (lane < n_foreign) f_smp = a.kept_idx[seg_k1 + lane];
-    for (uint32_t r = tid; r < seg_cnt + 8u; r += (uint32_t)kThreads)
-        s_idx[r] = r < seg_cnt ? (uint16_t)(a.kept_idx[seg_k0 + r] - seg * kSegSamples) : (uint16_t)0;  // slack entries read as sample 0
+    // (stage_kept_list, gt_common.hip.h: the loads of a batch in flight together; the eight slack entries read as sample 0)
+    const uint32_t seg_s0 = seg * kSegSamples;
+    stage_kept_list<kThreads>(s_idx, 0u, a.kept_idx + seg_k0, seg_cnt, 8u, tid, [seg_s0](uint32_t s) { return (uint16_t)(s - seg_s0); });
     __syncthreads();
     if (rows == 0ull) return;
 

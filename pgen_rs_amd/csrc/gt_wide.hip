@@ -57,16 +57,6 @@ __device__ __forceinline__ const uint8_t *row_record(const EmitArgs &a, uint64_t
     return HAS_VIDX ? gathered_record(a, r) : a.records + r * a.record_stride;
 }
 
-template <bool NT>
-__device__ __forceinline__ void store_chunk(uint8_t *dst, const u32x4 &v)
-{
-    v4u t = {v.x, v.y, v.z, v.w};
-    if (NT)
-        __builtin_nontemporal_store(t, reinterpret_cast<v4u *>(dst));
-    else
-        *reinterpret_cast<v4u *>(dst) = t;
-}
-
 // geometry of one work item (all wave-uniform)
 struct Item {
     uint64_t g0;          // first chunk (index into the aligned chunk space of the stream)
@@ -172,7 +162,7 @@ __device__ __forceinline__ Item desc_get_item(const uint8_t *x)
 // j+1 (needed by the chunk that holds row j's '\n') was parked at slab[kSlabBytes] by the loader
 // wave, so this wave never issues a global load (gfx9 has one in-order vmcnt for loads and stores:
 // a wave that waits for a load also drains all its older stores).
-template <bool HAS_VIDX, bool NT, bool NEXT_IN_SLAB, bool LINES = false, int BURST = 1>
+template <bool HAS_VIDX, int SP, bool NEXT_IN_SLAB, bool LINES = false, int BURST = 1>
 __device__ __forceinline__ void emit_item(const EmitArgs &a, const WideParams &p, const Item &it,
                                           const uint8_t *slab, uint32_t lane)
 {
@@ -216,7 +206,7 @@ __device__ __forceinline__ void emit_item(const EmitArgs &a, const WideParams &p
             }
             asm volatile("" ::: "memory");
 #pragma unroll
-            for (int q = 0; q < BURST; q++) store_chunk<NT>(span_ptr + (u + (uint32_t)q) * 1024u, vb[q]);
+            for (int q = 0; q < BURST; q++) store_chunk<SP>(span_ptr + (u + (uint32_t)q) * 1024u, vb[q]);
             u += (uint32_t)BURST - 1u;
             continue;
         }
@@ -232,7 +222,7 @@ __device__ __forceinline__ void emit_item(const EmitArgs &a, const WideParams &p
             v.y = funnel_bytes(t1, t2, psh);
             v.z = funnel_bytes(t2, t3, psh);
             v.w = funnel_bytes(t3, t4, psh);
-            store_chunk<NT>(span_ptr + u * 1024u, v);
+            store_chunk<SP>(span_ptr + u * 1024u, v);
             continue;
         }
         const uint32_t idx = u * 64u + lane;      // position inside the 1-KiB-aligned span
@@ -312,7 +302,7 @@ __device__ __forceinline__ void emit_item(const EmitArgs &a, const WideParams &p
                 }
             }
         }
-        if (whole) store_chunk<NT>(dst, v);
+        if (whole) store_chunk<SP>(dst, v);
     }
     if (LINES) {
         // ---- edge bytes: the row's own bytes of its first chunk (lanes 0-15) and of its last chunk
@@ -400,7 +390,7 @@ __device__ __forceinline__ u32x4 run_text16(const uint8_t *slab, uint32_t rec_of
 //   C. the stage goes out as four 1-KiB stores of whole 128-B lines.
 constexpr uint32_t kStageBytes = 4096;
 
-template <bool NT>
+template <int SP>
 __device__ __forceinline__ void emit_run(const EmitArgs &a, const WideParams &p, const Item &it, const uint8_t *slab, uint8_t *stage, uint32_t lane)
 {
     const uint32_t S = (uint32_t)p.row_bytes;
@@ -490,7 +480,7 @@ __device__ __forceinline__ void emit_run(const EmitArgs &a, const WideParams &p,
             if (u * 64u >= end) break;
             const uint32_t i = u * 64u + lane - it.lead;  // wraps to huge before `lead`
             const v4u v = st[s4 * 64u + lane];
-            if (i < cnt_whole && !(c_first < 0 && i == 0u)) store_chunk<NT>(span_ptr + u * 1024u, u32x4{v.x, v.y, v.z, v.w});
+            if (i < cnt_whole && !(c_first < 0 && i == 0u)) store_chunk<SP>(span_ptr + u * 1024u, u32x4{v.x, v.y, v.z, v.w});
         }
         // the stage is rewritten by the next group: this group's reads must have returned first
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -527,7 +517,7 @@ constexpr int kRingSlots = 3;
 // head word (heads live 128 B apart; ~10 claims/us per word, far below the ~88/us a word takes)
 // and steals from the next range when its own is drained.  Every block therefore runs until the
 // whole launch is out of work and all of them finish within one step of each other.
-template <int NS, bool HAS_VIDX, bool NT, bool LINES = false, int BURST = 2, bool RUNS = false>
+template <int NS, bool HAS_VIDX, int SP, bool LINES = false, int BURST = 2, bool RUNS = false>
 __global__ __launch_bounds__(64 * (NS + 1)) void gt_stream_dyn_kernel(EmitArgs a, WideParams p)
 {
     // RUNS mode trades one slab slot per storer for the storers' 4-KiB text stages (LDS per block: 25 KB -> 45 KB)
@@ -703,9 +693,9 @@ __global__ __launch_bounds__(64 * (NS + 1)) void gt_stream_dyn_kernel(EmitArgs a
             if (t != kNoItem) {                       // kNoItem: this storer has no item in this (last) step of a range
                 const Item it = desc_get_item(desc);
                 if (RUNS)
-                    emit_run<NT>(a, p, it, slab, s_stage[RUNS ? w : 0u], lane);
+                    emit_run<SP>(a, p, it, slab, s_stage[RUNS ? w : 0u], lane);
                 else
-                    emit_item<HAS_VIDX, NT, true, LINES, BURST>(a, p, it, slab, lane);
+                    emit_item<HAS_VIDX, SP, true, LINES, BURST>(a, p, it, slab, lane);
             }
             if (lane == 0u) lds_flag_write(lds_offset(&s_done[w][slot]), step + 1u);
         }
@@ -891,7 +881,7 @@ __device__ __forceinline__ void emit_lines_run(const EmitArgs &a, const WidePara
             const uint32_t i = u * 64u + lane - it.lead;  // wraps to huge before `lead`
             const v4u v = st[s4 * 64u + lane];
             const bool whole = i < it.cnt && !(ragged_head && i == 0u) && !(ragged_tail && i + 1u == it.cnt);
-            if (whole) store_chunk<true>(span_ptr + u * 1024u, u32x4{v.x, v.y, v.z, v.w});
+            if (whole) store_chunk<kStoreNt>(span_ptr + u * 1024u, u32x4{v.x, v.y, v.z, v.w});
             else if (i < it.cnt) {
                 // the stream's first / last chunk: only the bytes inside [0, run_len)
                 const int32_t o = c_first + 16 * (int32_t)i;
@@ -914,8 +904,7 @@ __global__ __launch_bounds__(64 * (NS + 1)) void gt_lineruns_kernel(EmitArgs a, 
     constexpr int RS = 2, DS = RS + 1;
     __shared__ uint16_t s_tab[PICK ? kTabFront + kTabMaxSamples + kTabBack : 1];
     if (PICK) {
-        for (uint32_t r = threadIdx.x; r < kTabFront + a.kept_count + kTabBack; r += 64u * (NS + 1))
-            s_tab[r] = r >= kTabFront && r < kTabFront + a.kept_count ? (uint16_t)a.kept_idx[r - kTabFront] : (uint16_t)0;
+        stage_kept_list<64u * (NS + 1)>(s_tab + kTabFront, kTabFront, a.kept_idx, a.kept_count, kTabBack, threadIdx.x, [](uint32_t s) { return (uint16_t)s; });
     }
     __shared__ __attribute__((aligned(16))) uint8_t slabs[NS][RS][kLrSlab];
     __shared__ __attribute__((aligned(16))) uint8_t s_desc[NS][DS][kDescBytes];
@@ -1106,6 +1095,9 @@ bool gt_wide_lines_applicable(const EmitArgs &a)
            a.work_counters != nullptr;
 }
 
+constexpr uint64_t kShortLaunchBytes = 1000000000ull;     // text per launch up to which a launch counts as short (two blocks per CU, nt stores)
+constexpr uint64_t kWtOneSpanMaxBytes = 4500000000ull;    // rows of one span: text per launch up to which write-through stores are ahead (crossover between 3.8 and 5.6 GB)
+
 hipError_t launch_gt_wide(const EmitArgs &a, const Tuning &t, int num_cus, hipStream_t stream)
 {
     if (a.n_variants == 0) return hipSuccess;
@@ -1133,11 +1125,25 @@ hipError_t launch_gt_wide(const EmitArgs &a, const Tuning &t, int num_cus, hipSt
     // 1 loader + 7 storer waves, nontemporal stores, plain store steps in bursts of 2 (text of both first, then both
     // stores): the measured best of the round-1 A/Bs (3 storers, plain stores, bursts of 1/4/8: profiles/r01_kernel_sweeps.md)
     const uint64_t need = (p.n_items + 6ull) / 7ull;
+    // Store policy (profiles/r04_short_launches.md, both policies interleaved in one process, two boxes).  Write-through (nt sc1)
+    // stores are ahead on LONG launches of rows of several spans — N = 500 000: 12 GB -2.4 / -3.4 %, the 212-GB launch of BASELINE
+    // configs[2] 33.90 -> 32.56 ms (-3.9 %), N = 5 000 / 20 000 / 100 000 at 12 GB -1.4 / -1.9 / -2.2 % — and on rows of one span in the
+    // middle sizes (N = 2 504: 1 GB -1.9 %, 2 GB -2.0 / -2.2 %, 3.8 GB of text -2.1 %); they are BEHIND on rows of one span from 5.6 GB of
+    // text (+1.3 %, 8 GB +1.2 %, the 11.7-GB chr22 block +1.3 % on both boxes) and level on short launches (134 MB +0.9 %, the 0.5-GB
+    // second pass of the two passes +0.3 %: no end-of-kernel flush worth having shows at any size).  The rule takes write-through where
+    // it measured ahead by more than the spread: above the short-launch size of the blocks-per-CU rule below, rows of several
+    // spans at any size, rows of one span up to kWtOneSpanMaxBytes.  (Full lines through this kernel follow the same rule by the
+    // size of their GT text: the same stores behind a prefix each; not measured separately.)
     void (*dk)(EmitArgs, WideParams);
-    if (a.line_off)
-        dk = gathered(a) ? gt_stream_dyn_kernel<7, true, true, true> : gt_stream_dyn_kernel<7, false, true, true>;
-    else
-        dk = gathered(a) ? gt_stream_dyn_kernel<7, true, true> : gt_stream_dyn_kernel<7, false, true>;
+    const bool wt_rule = p.total_bytes > kShortLaunchBytes && (p.spans_per_row > 1u || p.total_bytes <= kWtOneSpanMaxBytes);
+    const bool wt = t.store_policy == 0 ? wt_rule : t.store_policy == 2;
+    if (a.line_off) {
+        if (wt) dk = gathered(a) ? gt_stream_dyn_kernel<7, true, kStoreNtWt, true> : gt_stream_dyn_kernel<7, false, kStoreNtWt, true>;
+        else dk = gathered(a) ? gt_stream_dyn_kernel<7, true, kStoreNt, true> : gt_stream_dyn_kernel<7, false, kStoreNt, true>;
+    } else {
+        if (wt) dk = gathered(a) ? gt_stream_dyn_kernel<7, true, kStoreNtWt> : gt_stream_dyn_kernel<7, false, kStoreNtWt>;
+        else dk = gathered(a) ? gt_stream_dyn_kernel<7, true, kStoreNt> : gt_stream_dyn_kernel<7, false, kStoreNt>;
+    }
     // launch exactly what is resident (62 VGPRs -> 8 waves/SIMD -> four 512-thread blocks per CU; 25 KB of LDS
     // each): blocks beyond that would only start when the queue is already empty.  Interleaved A/B on the chr22
     // block: 2 blocks/CU 2.12 ms, 4 blocks/CU 2.00 ms (profiles/r01_kernel_sweeps.md)
@@ -1148,7 +1154,7 @@ hipError_t launch_gt_wide(const EmitArgs &a, const Tuning &t, int num_cus, hipSt
     // ~4.5 GB (N = 2 504: 134 MB 0.51 against 0.45 of roofline, 2.2 GB 0.77 / 0.71, 6 GB 0.69 / 0.73); on FRESH output regions (one call cut into
     // pieces of that size, tools/split_probe.py) it is small and ends earlier: 134 MB 0.457 / 0.442, 0.5 GB level (K = 4 940: 0.584 / 0.569),
     // 2 GB 0.613 / 0.642 — so the rule takes the size both agree on.
-    if ((uint64_t)a.n_variants * p.row_bytes <= 1000000000ull && per_cu > 2) per_cu = 2;
+    if (p.total_bytes <= kShortLaunchBytes && per_cu > 2) per_cu = 2;
     if (t.wide_blocks_per_cu > 0) per_cu = t.wide_blocks_per_cu;
     const uint64_t cap = (uint64_t)num_cus * (uint64_t)per_cu;
     const uint32_t g = (uint32_t)(need < cap ? need : cap);
@@ -1200,7 +1206,10 @@ hipError_t launch_gt_runs(const EmitArgs &a, const Tuning &t, int num_cus, hipSt
     p.pfx_shift = 0u;
     p.n_items = ((uint64_t)a.n_variants + p.run_rows - 1ull) / p.run_rows;
     const uint64_t need = (p.n_items + 6ull) / 7ull;
-    void (*dk)(EmitArgs, WideParams) = gt_stream_dyn_kernel<7, false, true, false, 2, true>;
+    // store policy: nt; write-through measured level on these launches (N = 300: 134 MB -2.3 % inside a spread of 9 %, 255 MB -0.6 / -1.1 %,
+    // 1 GB level: profiles/r04_short_launches.md), so only the knob selects it
+    void (*dk)(EmitArgs, WideParams) = t.store_policy == 2 ? gt_stream_dyn_kernel<7, false, kStoreNtWt, false, 2, true>
+                                                           : gt_stream_dyn_kernel<7, false, kStoreNt, false, 2, true>;
     // two blocks per CU, not the three the occupancy API allows (45 KB of LDS each): level on 11-GB launches (N = 100 / 300 / 1 000 /
     // 1 900: 0.686 / 0.680 / 0.698 / 0.707 against 0.683 / 0.681 / 0.703 / 0.690) and 8-9 % ahead on the 255-MB launch of the
     // reference's own dataset shape (0.505 against 0.469), whose blocks run only three steps each

@@ -59,6 +59,7 @@ struct Tuning {
     int pack_blocks = 0;           // pack kernels: grid size in blocks (0 = by shape, capped per CU)
     int spair_slices = 0;          // pairwise sample tables: row ranges per sample tile (0 = by shape: the chip's resident blocks, at least 256 rows each)
     int vsum_blocks = 0;           // per-variant sums: grid size in blocks (0 = by shape, capped per CU)
+    int store_policy = 0;          // stream kernel (row items, LINES, RUNS): how text is stored (0 = the measured rule of launch_gt_wide, 1 = nt, 2 = nt sc1, write-through)
 };
 
 // rows are gathered (variant list or byte offsets): the HAS_VIDX instantiations
