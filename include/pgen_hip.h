@@ -448,6 +448,54 @@ int pgenhip_sample_pair_stats_at(pgenhip_ctx *ctx, const void *d_base, const uin
                                  uint32_t a_begin, uint32_t a_count, uint32_t b_begin, uint32_t b_count, uint32_t *d_out,
                                  uint32_t flags);
 
+/* ---- sample Gram matrix (device-resident, asynchronous on the ctx stream) ----
+ * The weighted member of the family whose integer member is pgenhip_sample_pair_stats: Z^T Z in FP64, where every selected row has its
+ * own value for each of the four codes.  Rows are selected exactly as in pgenhip_sample_pair_stats / _at (by stride with
+ * record_stride >= R or n_variants <= 1, through d_variant_idx, or through d_record_off; any byte alignment; a gather that repeats a
+ * row adds it twice).  [a_begin, a_begin + a_count) and [b_begin, b_begin + b_count) are ranges of RANKS in the ctx's kept list (a
+ * rank is the sample index when all samples are kept); they may be equal, overlap, be disjoint or come in either order.  For
+ * a = a_begin + i and b = b_begin + l
+ *     d_out[i * out_stride + l] = sum over the selected rows j of t_j[x_j(a)] * t_j[x_j(b)]
+ * where x_j(s) is the 2-bit code of sample s in row j (0 hom-ref, 1 het, 2 hom-alt, 3 missing) and t_j = d_code_values[4*j .. 4*j+3],
+ * a DEVICE array of FP64 indexed by the row's POSITION IN THE SELECTION (as d_weights of pgenhip_sample_scores is).  The library
+ * does not interpret the table: a standardised GRM ((0-2p)s, (1-2p)s, (2-2p)s, 0), a dominance GRM, a raw dosage cross-product
+ * (0, 1, 2, 0) and the number of rows called in both samples (1, 1, 1, 0) are all "four doubles per row".  out_stride is in doubles,
+ * >= b_count (or a_count <= 1).  The result is mathematically symmetric when the two ranges are equal; the library does not exploit
+ * that, and a host covers K x K with the upper block triangle.  The pad bits of a record's last byte and samples >= N are never read
+ * as samples.
+ *   - Arithmetic.  Every product and every addition is FP64; there are no f32 partial sums.  The order of the additions is not fixed
+ *     (rows are dealt to blocks and accumulator chains, which meet in atomics).  Each entry is within (n_variants + 2) * 2^-53 *
+ *     A(a, b) of the exact sum, A(a, b) = sum over j of |t_j[x_j(a)] * t_j[x_j(b)]|: one rounding per product and n_variants - 1
+ *     additions, to first order, with room to spare.  Sums whose every partial sum is an integer below 2^53 are exact in any order.
+ *     Non-finite table entries give unspecified results.  Bitwise run-to-run reproducibility is not promised.
+ *   - Without PGENHIP_GRAM_ACCUMULATE the call overwrites exactly the a_count x b_count entries (zeros when n_variants == 0).  With
+ *     it the sums are added to what d_out holds, so a host sums blocks of rows in place; n_variants == 0 is then a no-op.  Row
+ *     padding and everything else are not touched; a_count == 0 or b_count == 0 writes nothing and returns PGENHIP_OK.
+ *   - d_out must be ORDINARY device memory (hipMalloc, pgenhip_device_malloc), not fine-grained or host-mapped memory: the
+ *     kernel adds with hardware FP64 atomics, which such memory does not serve.
+ *   - PGENHIP_ERR_BAD_ARG: a range that ends past K; d_code_values NULL with n_variants > 0, or not 8-byte aligned; d_out NULL or not
+ *     8-byte aligned when at least one entry exists; out_stride < b_count with a_count > 1; unknown flag bits or shape ids; a forced
+ *     shape that does not apply (both shapes take every legal call today).  PGENHIP_ERR_TOO_LARGE, before any launch:
+ *     a_count * out_stride * 8 >= 2^52, n_variants * 32 >= 2^52, and the record byte offsets that pgenhip_decode_matrix refuses.
+ *     Nothing is written or launched on a refusal.
+ * Same launch contract as pgenhip_sample_pair_stats: device pointers only, no allocation, no synchronisation, queued on the ctx
+ * stream, graph-capturable (the overwrite is a zeroing memset ahead of the kernel).  The kernels use no work-queue counters, so these
+ * launches do not count against PGENHIP_LAUNCHES_IN_FLIGHT.
+ * flags: a shape (PGENHIP_GRAM_AUTO or a forced one) | PGENHIP_GRAM_ACCUMULATE. */
+#define PGENHIP_GRAM_AUTO 0u
+#define PGENHIP_GRAM_GENERAL 1u       /* a lane per pair, FP64 multiply-add along the rows: the correctness baseline */
+#define PGENHIP_GRAM_MFMA 2u          /* FP64 matrix cores (v_mfma_f64_16x16x4_f64), 64 x 64 ranks per block: what AUTO takes */
+/* 3u is reserved for a matrix-core form with f32 operands (not built; refused with PGENHIP_ERR_BAD_ARG) */
+#define PGENHIP_GRAM_SHAPE_MASK 0xFu
+#define PGENHIP_GRAM_ACCUMULATE 0x10u
+int pgenhip_sample_gram(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                        uint32_t n_variants, const double *d_code_values, uint32_t a_begin, uint32_t a_count, uint32_t b_begin,
+                        uint32_t b_count, double *d_out, uint64_t out_stride, uint32_t flags);
+/* Same, with the record of row j at d_base + d_record_off[j] (DEVICE array of u64 byte offsets). */
+int pgenhip_sample_gram_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
+                           const double *d_code_values, uint32_t a_begin, uint32_t a_count, uint32_t b_begin, uint32_t b_count,
+                           double *d_out, uint64_t out_stride, uint32_t flags);
+
 /* ---- packed records of the kept samples (device-resident, asynchronous on the ctx stream) ----
  * The selection written back as records: row j of the output is the mode-0x02 record of a K-sample file that holds the ctx's kept
  * samples of selected row j, so a host that puts the 12-byte header in front has a .pgen of the subset (src/pfile.rs:172-175 read
@@ -509,6 +557,7 @@ typedef enum pgenhip_knob {
     PGENHIP_KNOB_SPAIR_SLICES = 22,      /* pairwise sample tables: row ranges per sample tile, each summed by one block (default 0 = by shape: as many as fill the chip's resident blocks, of at least 256 rows each); tests put the row count on either side of every slice edge */
     PGENHIP_KNOB_VSUM_BLOCKS = 23,       /* per-variant sums: grid size in blocks (default 0 = by shape: the work, capped at 8 blocks per CU); the MFMA shape also cuts the rows into that many slices, so tests force small grids and the multi-block combine */
     PGENHIP_KNOB_STORE_POLICY = 24,      /* stream kernel (row items, full lines through it, RUNS): how the text is stored. 0 (default) the measured rule: non-temporal write-through stores (sc1 nt: the line leaves the L2 with the store) on launches of more than 1 GB of text whose rows span several 16-KiB work items, or one and up to 4.5 GB; non-temporal stores elsewhere. 1 non-temporal stores everywhere, 2 write-through stores everywhere (tests force both at small sizes; A/B probes); other values are refused. The other emit kernels store as before whatever the value */
+    PGENHIP_KNOB_GRAM_SLICES = 25,       /* sample Gram matrix: row ranges per rank tile, each summed by one block (default 0 = by shape: as many as fill the chip's resident blocks, of at least 256 rows each); tests put the row count on either side of every slice edge */
     PGENHIP_KNOB_RUNS_ROWS = 7       /* RUNS kernel: rows per work item (default: as many as one wide load / one span holds) */
 } pgenhip_knob;
 int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value);

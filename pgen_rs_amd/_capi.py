@@ -63,6 +63,11 @@ SPAIR_GENERAL = 1
 SPAIR_MFMA = 2
 SPAIR_SHAPE_MASK = 0xF
 SPAIR_ACCUMULATE = 0x10
+GRAM_AUTO = 0
+GRAM_GENERAL = 1
+GRAM_MFMA = 2
+GRAM_SHAPE_MASK = 0xF
+GRAM_ACCUMULATE = 0x10
 MATRIX_AUTO = 0
 MATRIX_GENERAL = 1
 MATRIX_STREAM = 2
@@ -100,6 +105,7 @@ KNOB_SCORE_SLICES = 21
 KNOB_SPAIR_SLICES = 22
 KNOB_VSUM_BLOCKS = 23
 KNOB_STORE_POLICY = 24
+KNOB_GRAM_SLICES = 25
 
 
 
@@ -151,6 +157,8 @@ PROTOTYPES = {
     "pgenhip_decode_matrix_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_sample_pair_stats": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_sample_pair_stats_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
+    "pgenhip_sample_gram": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32]),
+    "pgenhip_sample_gram_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32]),
     "pgenhip_pair_stats": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_pair_stats_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_packed_record_size": (C.c_uint32, [ctx_p]),

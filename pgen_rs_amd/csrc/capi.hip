@@ -942,6 +942,74 @@ int pgenhip_sample_pair_stats_at(pgenhip_ctx *ctx, const void *d_base, const uin
     return sample_pair_stats_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, a_begin, a_count, b_begin, b_count, d_out, flags);
 }
 
+static int sample_gram_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                            const uint64_t *d_record_off, uint32_t n_variants, const double *d_code_values, uint32_t a_begin,
+                            uint32_t a_count, uint32_t b_begin, uint32_t b_count, double *d_out, uint64_t out_stride, uint32_t flags)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (flags & ~(PGENHIP_GRAM_SHAPE_MASK | PGENHIP_GRAM_ACCUMULATE)) return fail(PGENHIP_ERR_BAD_ARG, "unknown sample_gram flag");
+    const uint32_t shape = flags & PGENHIP_GRAM_SHAPE_MASK;
+    if (shape > PGENHIP_GRAM_MFMA) return fail(PGENHIP_ERR_BAD_ARG, "sample_gram supports shapes AUTO, GENERAL and MFMA");
+    const bool accumulate = (flags & PGENHIP_GRAM_ACCUMULATE) != 0u;
+    const uint64_t K = ctx->kept_count;
+    if ((uint64_t)a_begin + a_count > K || (uint64_t)b_begin + b_count > K) return fail(PGENHIP_ERR_BAD_ARG, "a sample range ends past the kept count");
+    if (n_variants && !d_code_values) return fail(PGENHIP_ERR_BAD_ARG, "d_code_values is NULL");
+    if ((uintptr_t)d_code_values & 7u) return fail(PGENHIP_ERR_BAD_ARG, "d_code_values is not 8-byte aligned");
+    const uint64_t pairs = (uint64_t)a_count * b_count;
+    if (pairs != 0u && !d_out) return fail(PGENHIP_ERR_BAD_ARG, "d_out is NULL");
+    if (pairs != 0u && ((uintptr_t)d_out & 7u)) return fail(PGENHIP_ERR_BAD_ARG, "d_out is not 8-byte aligned");
+    if (a_count > 1u && out_stride < b_count) return fail(PGENHIP_ERR_BAD_ARG, "out_stride < b_count");
+    // byte offsets of entries, tables and records are 64-bit arithmetic in the kernels; the bounds are decode_matrix's (2^52 bytes)
+    constexpr uint64_t kMaxSpan = 1ull << 52;
+    const bool by_stride = n_variants > 1 && !d_record_off;
+    if ((a_count > 1u && out_stride >= kMaxSpan / 8u / a_count) || (uint64_t)n_variants * 32u >= kMaxSpan ||
+        (by_stride && !d_variant_idx && record_stride >= kMaxSpan / n_variants) || (by_stride && d_variant_idx && record_stride >= kMaxSpan))
+        return fail(PGENHIP_ERR_TOO_LARGE, "sample_gram offsets do not fit the kernels' index types");
+    if (pairs == 0u) return PGENHIP_OK;   // nothing to write
+    GramArgs a;
+    rc = select_rows(ctx, a, d_records, record_stride, d_variant_idx, d_record_off, n_variants);
+    if (rc) return rc;
+    a.kept_idx = (!ctx->subset || ctx->identity) ? nullptr : ctx->d_kept;
+    a.a_begin = a_begin;
+    a.a_count = a_count;
+    a.b_begin = b_begin;
+    a.b_count = b_count;
+    a.code_values = d_code_values;
+    a.out = d_out;
+    a.out_stride = a_count > 1u ? out_stride : b_count;
+    // AUTO: the matrix-core shape
+    const bool mfma = shape != PGENHIP_GRAM_GENERAL;
+    const uint32_t slices = gt_gram_slices(a, mfma, ctx->tune.gram_slices, ctx->num_cus);
+    // one slice that overwrites: every entry has one owner and is stored.  Else the kernels only add, to zeros or to what is there
+    a.store = (!accumulate && n_variants != 0u && slices == 1u) ? 1u : 0u;
+    if (!accumulate && !a.store)
+        HIP_TRY(hipMemset2DAsync(d_out, 8u * (size_t)a.out_stride, 0, 8u * (size_t)b_count, a_count, ctx->stream));
+    if (n_variants == 0) return PGENHIP_OK;
+    if (mfma)
+        HIP_TRY(launch_gt_gram_mfma(a, slices, ctx->stream));
+    else
+        HIP_TRY(launch_gt_gram_general(a, slices, ctx->stream));
+    return PGENHIP_OK;
+}
+
+int pgenhip_sample_gram(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                        uint32_t n_variants, const double *d_code_values, uint32_t a_begin, uint32_t a_count, uint32_t b_begin,
+                        uint32_t b_count, double *d_out, uint64_t out_stride, uint32_t flags)
+{
+    return sample_gram_core(ctx, d_records, record_stride, d_variant_idx, nullptr, n_variants, d_code_values, a_begin, a_count, b_begin,
+                            b_count, d_out, out_stride, flags);
+}
+
+int pgenhip_sample_gram_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
+                           const double *d_code_values, uint32_t a_begin, uint32_t a_count, uint32_t b_begin, uint32_t b_count,
+                           double *d_out, uint64_t out_stride, uint32_t flags)
+{
+    if (const int rc = check_record_off(ctx, d_record_off, n_variants)) return rc;
+    return sample_gram_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, d_code_values, a_begin, a_count, b_begin, b_count, d_out,
+                            out_stride, flags);
+}
+
 static int pack_records_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
                              const uint64_t *d_record_off, uint32_t n_variants, void *d_out, uint64_t out_stride,
                              const uint8_t *code_map, uint32_t flags)
@@ -1035,6 +1103,7 @@ int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)
         case PGENHIP_KNOB_PACK_BLOCKS: t.pack_blocks = value > 0 ? value : d.pack_blocks; break;
         case PGENHIP_KNOB_SPAIR_SLICES: t.spair_slices = value > 0 ? value : d.spair_slices; break;
         case PGENHIP_KNOB_VSUM_BLOCKS: t.vsum_blocks = value > 0 ? value : d.vsum_blocks; break;
+        case PGENHIP_KNOB_GRAM_SLICES: t.gram_slices = value > 0 ? value : d.gram_slices; break;
         case PGENHIP_KNOB_STORE_POLICY:
             if (value < 0 || value > 2) return fail(PGENHIP_ERR_BAD_ARG, "store policy must be 0 (rule), 1 (nt) or 2 (nt sc1)");
             t.store_policy = value;

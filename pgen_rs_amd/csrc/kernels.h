@@ -59,6 +59,7 @@ struct Tuning {
     int pack_blocks = 0;           // pack kernels: grid size in blocks (0 = by shape, capped per CU)
     int spair_slices = 0;          // pairwise sample tables: row ranges per sample tile (0 = by shape: the chip's resident blocks, at least 256 rows each)
     int vsum_blocks = 0;           // per-variant sums: grid size in blocks (0 = by shape, capped per CU)
+    int gram_slices = 0;           // sample Gram matrix: row ranges per rank tile (0 = by shape: the chip's resident blocks, at least 256 rows each)
     int store_policy = 0;          // stream kernel (row items, LINES, RUNS): how text is stored (0 = the measured rule of launch_gt_wide, 1 = nt, 2 = nt sc1, write-through)
 };
 
@@ -211,6 +212,23 @@ struct SpairArgs : RowSource {
 // slices_per_tile: row ranges per sample tile, each summed by one block (0 = by shape)
 hipError_t launch_gt_spair_general(const SpairArgs &a, int slices_per_tile, int num_cus, hipStream_t stream);
 hipError_t launch_gt_spair_mfma(const SpairArgs &a, int slices_per_tile, int num_cus, hipStream_t stream);
+
+// Sample Gram matrix (gt_gram.hip): for a = a_begin + i, b = b_begin + l (ranks in the kept list) the FP64 sum over the selected rows
+// j of t_j[x_j(a)] * t_j[x_j(b)], t_j = code_values[4 j .. 4 j + 3] (indexed by the row's position in the selection), at
+// out[i * out_stride + l]: stored when `store`, else ADDED (FP64 atomics; the caller zeroes the entries first unless it accumulates).
+struct GramArgs : RowSource {
+    const uint32_t *kept_idx;     // device or nullptr (all samples, or an identity list): rank -> sample
+    uint32_t a_begin, a_count;    // a_begin + a_count <= K
+    uint32_t b_begin, b_count;    // b_begin + b_count <= K
+    const double *code_values;    // device, 8-byte aligned, four per selected row
+    double *out;                  // device, 8-byte aligned, ordinary device memory (hardware FP64 atomics)
+    uint64_t out_stride;          // doubles between the output rows
+    uint32_t store;               // 1: every entry has one owner and is overwritten (one slice, no ACCUMULATE): plain stores
+};
+// row ranges per tile of a launch of that shape (slices_per_tile: forced, 0 = by shape); 1 means every entry has one owner
+uint32_t gt_gram_slices(const GramArgs &a, bool mfma, int slices_per_tile, int num_cus);
+hipError_t launch_gt_gram_general(const GramArgs &a, uint32_t slices, hipStream_t stream);
+hipError_t launch_gt_gram_mfma(const GramArgs &a, uint32_t slices, hipStream_t stream);
 
 // Packed records (gt_pack.hip): row j = the mode-0x02 record of the K kept samples of selected row j, ceil(K / 4) bytes at
 // out + j * out_stride, every code sent through a 2-bit -> 2-bit map, pad bits zero.

@@ -742,6 +742,60 @@ class GtEngine:
             raise ValueError(f"out must be an int32 tensor with >= {need} entries")
         return a, b, out.view(-1)
 
+    # -- sample Gram matrix -------------------------------------------------------------------------
+    def sample_gram(self, records: torch.Tensor, record_stride: Optional[int] = None, variant_idx: Optional[torch.Tensor] = None,
+                    n_variants: Optional[int] = None, *, code_values: torch.Tensor, a: Optional[tuple[int, int]] = None,
+                    b: Optional[tuple[int, int]] = None, out: Optional[torch.Tensor] = None, out_stride: Optional[int] = None,
+                    accumulate: bool = False, kernel: int = _capi.GRAM_AUTO, records_offset: int = 0) -> torch.Tensor:
+        """Weighted cross-products of pairs of kept samples over the selected rows: a float64 ``(a_count, b_count)`` CUDA view whose
+        entry ``[i, l]`` is the FP64 sum over the rows j of ``code_values[j, x] * code_values[j, y]``, x and y the codes of the
+        samples of rank ``a_begin + i`` and ``b_begin + l`` in row j.
+
+        ``code_values``: float64 CUDA tensor ``(n_variants, 4)``, contiguous, indexed by the row's position in the selection.
+        ``a``, ``b``: ``(begin, count)`` ranges of ranks in the kept list (default: all K).  Rows are selected as in
+        ``sample_counts``.  ``out``: optional float64 CUDA tensor of >= (a_count - 1) * out_stride + b_count entries (written from
+        its first element; row padding and everything else are untouched); ``out_stride``: doubles between its rows (default
+        b_count).  ``accumulate``: add to what ``out`` holds instead of overwriting it.  ``kernel``: a forced shape
+        (``_capi.GRAM_*``)."""
+        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
+        a, b, out, out_stride = self._gram_out(code_values, n_variants, a, b, out, out_stride, accumulate)
+        check(lib.pgenhip_sample_gram(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants,
+                                      _ptr(code_values), a[0], a[1], b[0], b[1], _ptr(out), out_stride,
+                                      kernel | (_capi.GRAM_ACCUMULATE if accumulate else 0)), "pgenhip_sample_gram")
+        return torch.as_strided(out, (a[1], b[1]), (out_stride, 1))
+
+    def sample_gram_at(self, base: torch.Tensor, record_off: torch.Tensor, code_values: torch.Tensor, n_variants: Optional[int] = None, *,
+                       a: Optional[tuple[int, int]] = None, b: Optional[tuple[int, int]] = None, out: Optional[torch.Tensor] = None,
+                       out_stride: Optional[int] = None, accumulate: bool = False, kernel: int = _capi.GRAM_AUTO) -> torch.Tensor:
+        """``sample_gram`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
+        n_variants = self._rows_at(base, record_off, n_variants)
+        a, b, out, out_stride = self._gram_out(code_values, n_variants, a, b, out, out_stride, accumulate)
+        check(lib.pgenhip_sample_gram_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, _ptr(code_values), a[0], a[1], b[0], b[1],
+                                         _ptr(out), out_stride, kernel | (_capi.GRAM_ACCUMULATE if accumulate else 0)),
+              "pgenhip_sample_gram_at")
+        return torch.as_strided(out, (a[1], b[1]), (out_stride, 1))
+
+    def _gram_out(self, code_values: torch.Tensor, n_variants: int, a, b, out: Optional[torch.Tensor], out_stride: Optional[int],
+                  accumulate: bool):
+        """(the two ranges with their defaults, the flat output: given, or allocated, its row stride in doubles)"""
+        self._check_dev(code_values, "code_values")
+        if code_values.dtype != torch.float64 or code_values.numel() < 4 * n_variants:
+            raise ValueError("code_values must be a float64 tensor of shape (n_variants, 4)")
+        a = (0, self.kept_count) if a is None else (int(a[0]), int(a[1]))
+        b = (0, self.kept_count) if b is None else (int(b[0]), int(b[1]))
+        if min(a + b) < 0:
+            raise ValueError("sample ranges are (begin, count) with begin, count >= 0")
+        if out_stride is None:
+            out_stride = b[1]
+        need = (a[1] - 1) * out_stride + b[1] if a[1] and b[1] else 0
+        if out is None:
+            make = torch.zeros if accumulate else torch.empty
+            return a, b, make(max(need, 1), dtype=torch.float64, device=self.torch_device), out_stride
+        self._check_dev(out, "out")
+        if out.dtype != torch.float64 or out.numel() < need:
+            raise ValueError(f"out must be a float64 tensor with >= {need} entries")
+        return a, b, out.view(-1), out_stride
+
     _MATRIX_DTYPES = {torch.int8: np.int8, torch.uint8: np.uint8, torch.int16: np.int16, torch.int32: np.int32,
                       torch.float16: np.float16, torch.bfloat16: None, torch.float32: np.float32}
 

@@ -20,6 +20,9 @@
 // `pgen-hip kinship <PFILE_PREFIX> [--include-var <EXPR>] [--include-sam <EXPR>] [--min-kinship <X>] [--counts] [-o|--out <FILE>]` (not in
 // the reference): the joint genotype table of every pair of kept samples over the kept variants, counted on the GPU's int8 matrix
 // cores, and the KING-robust kinship estimate from it.
+// `pgen-hip grm <PFILE_PREFIX> [--include-var <EXPR>] [--include-sam <EXPR>] [--format grm-bin|rel] -o|--out <OUT_PREFIX>` (not in the
+// reference): the genetic relationship matrix of the kept samples over the kept variants (GCTA's definition), two FP64 Gram
+// matrices per block of variants on the GPU's FP64 matrix cores.
 // Additions (opt-in, not in the reference): --gpus <N>, --block-mib <M>, --launch-mib <M>, --filter-threads <T>, --stats, --dry-run
 // (filter: write the VCF header only and report the body geometry; needs no GPU); BGZF output (`-o x.vcf.gz` or --bgzf,
 // --bgzf-level <1-9>, --compress-threads <T>) and `pgen-hip bgzf <IN> <OUT>`, the same writer on a file.
@@ -94,6 +97,7 @@ const char *kUsage =
     "  matrix  Numeric genotype matrix of the kept variants and samples, outputting to a NumPy .npy file\n"
     "  ld      Pairwise r^2 of the kept variants inside a sliding window, outputting to stdout\n"
     "  kinship Pairwise genotype tables and KING-robust kinship of the kept samples, outputting to stdout\n"
+    "  grm     Genetic relationship matrix of the kept samples, outputting GCTA-style binary files or a text square\n"
     "  export  Writes the kept variants and samples back as a .pgen (or PLINK 1 .bed) fileset\n"
     "  help    Print this message\n\n"
     "query  <PFILE_PREFIX> -f, --fstring <QUERY_FSTRING> [-i, --include <QUERY>] [-s, --samples]\n"
@@ -147,6 +151,16 @@ const char *kUsage =
     "       the lines below X and the nan lines.  The tables of all pairs (32 bytes x kept samples squared) are held on each device in\n"
     "       square tiles of T ranks (default 1024): out-of-core sample tiling is not built, and a sample set whose tables do not fit\n"
     "       fails with an out-of-memory error.  No byte or digit parity with plink2's .kin0 or KING is claimed\n"
+    "grm    <PFILE_PREFIX> [--include-var <VAR_QUERY>] [--include-sam <SAM_QUERY>] [--format grm-bin|rel] -o, --out <OUT_PREFIX>\n"
+    "       [--gpus <N>] [--shards <S>] [--block-mib <M>] [--block-rows <B>] [--sample-tile <T>] [--read-threads <T>] [--filter-threads <T>] [--stats]\n"
+    "       GRM[a][b] = G[a][b] / N[a][b] over the kept variants called in both samples (GCTA's definition; nan where N is 0):\n"
+    "       G sums (x_a - 2p)(x_b - 2p) / (2p(1-p)) with p the variant's ALT frequency among the kept samples called, N counts the\n"
+    "       variants; a variant with no call or with p of 0 or 1 adds to neither (--stats reports how many).  --format grm-bin (default):\n"
+    "       OUT_PREFIX.grm.bin and .grm.N.bin (little-endian f32, lower triangle with the diagonal, row a then b = 0..a) and .grm.id\n"
+    "       (FID IID with FID = IID); --format rel: OUT_PREFIX.rel (K lines of K tab-separated values, %.17g) and .rel.id.  Both matrices\n"
+    "       (16 bytes x kept samples squared) are held on each device in square tiles of T ranks (default 1024) and on the host:\n"
+    "       out-of-core sample tiling is not built, and a sample set whose matrices do not fit fails with an out-of-memory error.\n"
+    "       Sums are FP64 in no fixed order; no byte or digit parity with plink2 or GCTA is claimed\n"
     "bgzf   <IN_FILE> <OUT_FILE> [--level <1-9>] [--threads <T>] [--chunk-mib <M>]\n";
 
 [[noreturn]] void usage_error(const std::string &msg)
@@ -579,6 +593,39 @@ int main(int argc, char **argv)
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
             const OutputStats st = pfile.output_kinship(a.get("include-sam"), a.get("include-var"), a.get("out").value_or(""), k, output_options(a));
             if (a.has("stats")) print_stats(st, t_main);
+            return 0;
+        }
+        if (cmd == "grm") {
+            Args a = parse(argc, argv, 2, {{"format", 0}, {"sample-tile", 0}, {"block-rows", 0}, {"include-var", 0}, {"include-sam", 0}, {"out", 'o'}, {"gpus", 0}, {"shards", 0}, {"block-mib", 0}, {"read-threads", 0}, {"filter-threads", 0}},
+                           {{"stats", 0}});
+            if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
+            if (!a.has("out") || a.get("out")->empty()) usage_error("the following required arguments were not provided: --out <OUT_PREFIX>");
+            const std::string format = a.get("format").value_or("grm-bin");
+            if (format != "grm-bin" && format != "rel") usage_error("invalid value '" + format + "' for '--format <FORMAT>' [possible values: grm-bin, rel]");
+            GrmOptions g;
+            g.rel = format == "rel";
+            if (auto t = a.get("sample-tile")) {
+                char *end = nullptr;
+                errno = 0;
+                const unsigned long long v = std::strtoull(t->c_str(), &end, 10);
+                if (t->empty() || (*t)[0] == '-' || *end != '\0' || errno != 0 || v < 1 || v > 65536)
+                    usage_error("invalid value '" + *t + "' for '--sample-tile <T>': a number of samples from 1 to 65536");
+                g.tile = (uint32_t)v;
+            }
+            if (auto b = a.get("block-rows")) {
+                char *end = nullptr;
+                errno = 0;
+                const unsigned long long v = std::strtoull(b->c_str(), &end, 10);
+                if (b->empty() || (*b)[0] == '-' || *end != '\0' || errno != 0 || v < 1)
+                    usage_error("invalid value '" + *b + "' for '--block-rows <B>': a number of variants from 1");
+                g.block_rows = v;
+            }
+            const Pfile pfile = Pfile::from_prefix(a.positional[0]);
+            const OutputStats st = pfile.output_grm(a.get("include-sam"), a.get("include-var"), *a.get("out"), g, output_options(a));
+            if (a.has("stats")) {
+                std::fprintf(stderr, "{\"variants_skipped\": %llu}\n", (unsigned long long)st.grm_skipped);
+                print_stats(st, t_main);
+            }
             return 0;
         }
         if (cmd == "bgzf") {

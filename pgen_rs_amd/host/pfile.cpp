@@ -1307,6 +1307,87 @@ struct KinshipCounter {
     }
 };
 
+// grm's counter: per block the variants' counts come back, the host makes the two tables per variant and every pair of rank tiles
+// of the upper block triangle gets two Gram launches (G, then N); the shard's first block overwrites the buffers, the others
+// accumulate; they come back once per shard, filed under the shard's first variant so that the host can add the shards in order
+struct GramCounter {
+    uint32_t R, K, tile, tiles;
+    size_t bv;                                               // rows of a block at most: the N tables lie 4 * bv doubles behind the G tables
+    std::map<size_t, std::vector<std::vector<double>>> &sums;   // shard's first variant -> per pair of tiles, G at 2 p, N at 2 p + 1
+    std::mutex &mu;
+    uint64_t &skipped;
+    std::vector<double *> bufs;                              // device: count(ta) x count(tb) doubles, in the order of `sums`' vectors
+    uint32_t *d_counts, *h_counts;
+    double *d_tab, *h_tab, *h_buf;                           // h_buf: pinned, the largest buffer's size
+    bool first = true;
+    size_t first_b0 = 0;
+    uint32_t count(uint32_t t) const { return std::min(tile, K - t * tile); }
+    void launch(pgenhip_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_off, size_t b0, uint32_t nv, uint32_t)
+    {
+        if (d_off)
+            check(pgenhip_genotype_counts_at(ctx, d_rec, d_off, nv, d_counts, PGENHIP_COUNT_AUTO), "pgenhip_genotype_counts_at");
+        else
+            check(pgenhip_genotype_counts(ctx, d_rec, R, nullptr, nv, d_counts, PGENHIP_COUNT_AUTO), "pgenhip_genotype_counts");
+        check(pgenhip_memcpy_d2h(ctx, h_counts, d_counts, (size_t)nv * 16), "D2H counts");
+        check(pgenhip_wait(ctx), "pgenhip_wait");
+        uint64_t zero_tables = 0;
+        for (size_t j = 0; j < nv; j++) {
+            const uint64_t c0 = h_counts[4 * j], c1 = h_counts[4 * j + 1], c2 = h_counts[4 * j + 2];
+            const uint64_t called = c0 + c1 + c2, alt = c1 + 2 * c2;
+            double *g = h_tab + 4 * j, *n = h_tab + 4 * (bv + j);
+            if (called == 0 || alt == 0 || alt == 2 * called) {   // no call, p == 0 or p == 1: the variant adds nothing
+                for (int x = 0; x < 4; x++) g[x] = n[x] = 0.0;
+                zero_tables++;
+                continue;
+            }
+            const double p = (double)alt / (2.0 * (double)called);
+            const double s = 1.0 / std::sqrt(2.0 * p * (1.0 - p));
+            g[0] = (0.0 - 2.0 * p) * s;
+            g[1] = (1.0 - 2.0 * p) * s;
+            g[2] = (2.0 - 2.0 * p) * s;
+            g[3] = 0.0;
+            n[0] = n[1] = n[2] = 1.0;
+            n[3] = 0.0;
+        }
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            skipped += zero_tables;
+        }
+        check(pgenhip_memcpy_h2d(ctx, d_tab, h_tab, (size_t)(bv + nv) * 32), "H2D code values");
+        const uint32_t flags = PGENHIP_GRAM_AUTO | (first ? 0u : PGENHIP_GRAM_ACCUMULATE);
+        if (first) first_b0 = b0;
+        first = false;
+        size_t p = 0;
+        for (uint32_t ta = 0; ta < tiles; ta++)
+            for (uint32_t tb = ta; tb < tiles; tb++, p++)
+                for (size_t m = 0; m < 2; m++) {
+                    const double *tab = d_tab + m * 4 * bv;
+                    if (d_off)
+                        check(pgenhip_sample_gram_at(ctx, d_rec, d_off, nv, tab, ta * tile, count(ta), tb * tile, count(tb), bufs[2 * p + m], count(tb), flags), "pgenhip_sample_gram_at");
+                    else
+                        check(pgenhip_sample_gram(ctx, d_rec, R, nullptr, nv, tab, ta * tile, count(ta), tb * tile, count(tb), bufs[2 * p + m], count(tb), flags), "pgenhip_sample_gram");
+                }
+    }
+    void copy(pgenhip_ctx *, size_t) const {}
+    void collect(size_t, size_t) const {}
+    void finish(pgenhip_ctx *ctx) const
+    {
+        if (first) return;   // a shard without variants
+        std::vector<std::vector<double>> mine;
+        size_t p = 0;
+        for (uint32_t ta = 0; ta < tiles; ta++)
+            for (uint32_t tb = ta; tb < tiles; tb++, p++)
+                for (size_t m = 0; m < 2; m++) {
+                    const size_t n = (size_t)count(ta) * count(tb);
+                    check(pgenhip_memcpy_d2h(ctx, h_buf, bufs[2 * p + m], n * 8), "D2H Gram matrix");
+                    check(pgenhip_wait(ctx), "pgenhip_wait");
+                    mine.emplace_back(h_buf, h_buf + n);
+                }
+        std::lock_guard<std::mutex> lk(mu);
+        sums.emplace(first_b0, std::move(mine));
+    }
+};
+
 void write_text(const std::string &text, const std::string &filename)
 {
     if (filename.empty()) {
@@ -2003,6 +2084,112 @@ OutputStats Pfile::output_kinship(const std::optional<std::string> &sam_query, c
     st.body_bytes = text.size() - st.header_bytes;
     st.file_bytes = text.size();
     write_text(text, filename);
+    st.seconds_body = now_s() - t_body;
+    return st;
+}
+
+OutputStats Pfile::output_grm(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
+                              const std::string &out_prefix, const GrmOptions &gopt, const OutputOptions &opt) const
+{
+    OutputStats st;
+    const double t0 = now_s();
+    const Selection sel = select(sam_query, var_query, opt.filter_threads);
+    size_t iid = sel.sam_header.size();   // vcf_header's rule (:114-126): the first column named IID
+    for (size_t c = 0; c < sel.sam_header.size(); c++) {
+        if (sel.sam_header[c] == "IID") {
+            iid = c;
+            break;
+        }
+    }
+    if (iid == sel.sam_header.size()) throw PfileError("IID not among the headers of " + psam_path());
+    st.seconds_filter = now_s() - t0;
+
+    const KeptSamples kept = check_selection(*this, sel);
+    const size_t V = sel.var_idx_rcds.size(), K = kept.rows.size();
+    st.variants = V;
+    st.samples_kept = K;
+    const double t_body = now_s();
+
+    const uint32_t tile = std::max<uint32_t>(1u, gopt.tile), tiles = (uint32_t)((K + tile - 1) / tile);
+    auto count = [&](uint32_t t) { return (size_t)std::min<uint64_t>(tile, K - (uint64_t)t * tile); };
+    // per pair of tiles (ta <= tb, row-major), G at 2 p and N at 2 p + 1: the shards' sums, added in shard order
+    std::vector<std::vector<double>> totals;
+    for (uint32_t ta = 0; ta < tiles; ta++)
+        for (uint32_t tb = ta; tb < tiles; tb++)
+            for (int m = 0; m < 2; m++) totals.emplace_back(count(ta) * count(tb), 0.0);
+    if (K != 0 && V != 0) {   // else nothing is summed and no device is touched
+        const uint32_t R = variant_record_size();
+        std::mutex mu;
+        std::map<size_t, std::vector<std::vector<double>>> sums;
+        OutputOptions blocks = opt;
+        if (gopt.block_rows) blocks.block_text_bytes = gopt.block_rows * R;   // count_blocks sizes its blocks by record bytes
+        count_blocks(*this, sel.var_idx_rcds, kept, blocks, "no HIP device: the grm path has no CPU fallback", st, [&](DeviceCtx &ctx, uint64_t bv) {
+            GramCounter gc{R, (uint32_t)K, tile, tiles, (size_t)bv, sums, mu, st.grm_skipped, {}, nullptr, nullptr, nullptr, nullptr, nullptr};
+            for (uint32_t ta = 0; ta < tiles; ta++)
+                for (uint32_t tb = ta; tb < tiles; tb++)
+                    for (int m = 0; m < 2; m++) gc.bufs.push_back(ctx.device<double>(8 * count(ta) * count(tb), "device Gram matrix"));
+            gc.d_counts = ctx.device<uint32_t>((size_t)(16 * bv), "device counts");
+            gc.h_counts = ctx.pinned<uint32_t>((size_t)(16 * bv), "pinned counts");
+            gc.d_tab = ctx.device<double>((size_t)(64 * bv), "device code values");
+            gc.h_tab = ctx.pinned<double>((size_t)(64 * bv), "pinned code values");
+            gc.h_buf = ctx.pinned<double>(8 * count(0) * count(0), "pinned Gram matrix");
+            return gc;
+        });
+        for (const auto &shard : sums)   // ordered by the shard's first variant
+            for (size_t q = 0; q < totals.size(); q++)
+                for (size_t i = 0; i < totals[q].size(); i++) totals[q][i] += shard.second[q][i];
+    }
+    // first buffer pair of each tile row: pair (ta, tb) is at row_first[ta] + tb - ta
+    std::vector<size_t> row_first(tiles);
+    for (size_t ta = 0, p = 0; ta < tiles; p += tiles - ta, ta++) row_first[ta] = p;
+    // entry (a, b) of matrix m, read from the block that holds (min, max): the square written is exactly symmetric
+    auto entry = [&](size_t a, size_t b, size_t m) {
+        const size_t lo = std::min(a, b), hi = std::max(a, b);
+        const size_t ta = lo / tile, tb = hi / tile;
+        return totals[2 * (row_first[ta] + tb - ta) + m][(lo % tile) * count((uint32_t)tb) + hi % tile];
+    };
+    auto grm = [&](size_t a, size_t b) {
+        const double n = entry(a, b, 1);
+        return n == 0.0 ? std::nan("") : entry(a, b, 0) / n;
+    };
+    std::string ids;
+    for (size_t a = 0; a < K; a++) {
+        const std::string &name = sel.sam_idx_rcs[a].second.at(iid);
+        if (!gopt.rel) ids += name + '\t';   // FID = IID: the .psam files here carry no FID
+        ids += name + '\n';
+    }
+    if (gopt.rel) {
+        std::string text;
+        char num[40];
+        for (size_t a = 0; a < K; a++)
+            for (size_t b = 0; b < K; b++) {
+                const double v = grm(a, b);
+                if (std::isnan(v)) {
+                    text += "nan";
+                } else {
+                    std::snprintf(num, sizeof num, "%.17g", v);
+                    text += num;
+                }
+                text += b + 1 < K ? '\t' : '\n';
+            }
+        st.file_bytes = text.size();
+        write_text(text, out_prefix + ".rel");
+        write_text(ids, out_prefix + ".rel.id");
+    } else {
+        std::vector<float> g, n;
+        g.reserve(K * (K + 1) / 2);
+        n.reserve(K * (K + 1) / 2);
+        for (size_t a = 0; a < K; a++)
+            for (size_t b = 0; b <= a; b++) {
+                g.push_back((float)grm(a, b));
+                n.push_back((float)entry(a, b, 1));
+            }
+        st.file_bytes = 8 * g.size();
+        write_text(std::string(reinterpret_cast<const char *>(g.data()), 4 * g.size()), out_prefix + ".grm.bin");
+        write_text(std::string(reinterpret_cast<const char *>(n.data()), 4 * n.size()), out_prefix + ".grm.N.bin");
+        write_text(ids, out_prefix + ".grm.id");
+    }
+    st.body_bytes = st.file_bytes;
     st.seconds_body = now_s() - t_body;
     return st;
 }

@@ -148,12 +148,20 @@ struct KinshipOptions {
     uint64_t block_rows = 0;          // variants per block (0: as many as fill block_text_bytes with their records)
 };
 
+// `grm`: the files written and how the kept samples are cut into rank tiles on the device
+struct GrmOptions {
+    bool rel = false;                 // --format rel: the full square as text instead of GCTA's binary lower triangle
+    uint32_t tile = 1024;             // ranks per square tile: two device buffers of 8 * tile^2 bytes per pair of tiles
+    uint64_t block_rows = 0;          // variants per block (0: as many as fill block_text_bytes with their records)
+};
+
 struct OutputStats {
     uint64_t variants = 0, samples_kept = 0, header_bytes = 0, body_bytes = 0;   // header / body: bytes of VCF text
     uint64_t file_bytes = 0;                                                     // what the output file holds (BGZF: compressed)
     double seconds_filter = 0, seconds_body = 0, seconds_kernel = 0;
     uint64_t score_matched = 0, score_flipped = 0, score_skipped = 0;            // `score`: weights rows used, of them REF-effect rows, rows not used
     uint64_t assoc_dropped = 0;                                                  // `assoc`: kept samples dropped for a missing phenotype or covariate
+    uint64_t grm_skipped = 0;                                                    // `grm`: kept variants that add nothing (no call, or monomorphic among the kept samples)
     double seconds_setup = 0;   // inside seconds_body: HIP runtime start, contexts, device and pinned allocations of the slowest shard, before its first block is staged
 };
 
@@ -305,6 +313,20 @@ class Pfile {
     // the header alone; no kept variant: every table is zero; neither touches a device.  filename empty: stdout.
     OutputStats output_kinship(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
                                const std::string &filename, const KinshipOptions &kopt, const OutputOptions &opt = OutputOptions()) const;
+
+    // `grm` (not in the reference): the genetic relationship matrix of the kept samples over the kept variants, GCTA's definition.
+    // Per block of variants: pgenhip_genotype_counts, then on the host in double called = c0 + c1 + c2, p = (c1 + 2 c2) / (2 called),
+    // s = 1 / sqrt(2p(1-p)) and the two tables G ((0-2p)s, (1-2p)s, (2-2p)s, 0) and N (1, 1, 1, 0), both all zero for a variant
+    // with no call or with p == 0 or p == 1 (counted in grm_skipped); then pgenhip_sample_gram / _at twice for every pair of rank
+    // tiles of the upper block triangle (kinship's tiling, block loop and shards; the shard's first block overwrites, the others
+    // accumulate).  The host adds the shards' doubles in shard order.  GRM[a][b] = G[a][b] / N[a][b], the mean over the variants
+    // called in both samples; nan where N == 0.  Both triangles (16 K^2 bytes) must fit the device and the host: out-of-core sample
+    // tiling is not built.  grm-bin: out_prefix.grm.bin (little-endian f32, lower triangle with the diagonal, row a then b = 0..a),
+    // .grm.N.bin (f32 N in the same order), .grm.id (FID<TAB>IID with FID = IID).  rel: out_prefix.rel (K lines of K tab-separated
+    // %.17g values) and .rel.id (one IID per line).  No kept sample: empty files; no kept variant: every entry nan; neither touches
+    // a device.  No byte or digit parity with plink2 or GCTA is claimed.
+    OutputStats output_grm(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
+                           const std::string &out_prefix, const GrmOptions &gopt, const OutputOptions &opt = OutputOptions()) const;
 
     // the header part of output_vcf (:110-146) on its own: used by output_vcf and by the CPU tests
     std::string vcf_header(const IdxRecords &sam_idx_rcs, const StringRecord &sam_header) const;
