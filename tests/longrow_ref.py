@@ -261,6 +261,73 @@ def sample_pair_tables(recs_rows: Sequence[torch.Tensor], n: int, kept, a_ranks,
     return out.view(ac, bc, 4, 4)
 
 
+def _int_array(x, what: str) -> np.ndarray:
+    """``x`` as int64, after checking that it holds integers only (the exact comparisons rest on that)."""
+    a = np.asarray(x)
+    assert np.array_equal(a, np.rint(a)), f"{what} must be integers: the comparison is exact"
+    return a.astype(np.int64)
+
+
+def gram_ranges(recs_rows: Sequence[torch.Tensor], n: int, kept, tables, a_ranks, b_ranks) -> torch.Tensor:
+    """(a_count, b_count) int64: entry [i, l] = the sum over the rows of ``recs_rows`` of t_j[x] * t_j[y], x and y the codes of rank
+    a_begin + i and of rank b_begin + l in row j, t_j = ``tables[j]`` (the (V, 4) small integers of pgenhip_sample_gram, indexed by the
+    row's position in ``recs_rows``).  ``a_ranks``, ``b_ranks``: (begin, count), small ranges of rows of any length."""
+    dev = recs_rows[0].device
+    kept = as_kept(kept, dev)
+    t = torch.from_numpy(_int_array(tables, "tables").reshape(len(recs_rows), 4).copy()).to(dev)
+    (a0, ac), (b0, bc) = a_ranks, b_ranks
+    out = torch.zeros((ac, bc), dtype=torch.int64, device=dev)
+    for j, rec in enumerate(recs_rows):
+        za = t[j][codes(rec, a0, a0 + ac, kept).to(torch.int64)]
+        zb = t[j][codes(rec, b0, b0 + bc, kept).to(torch.int64)]
+        out += za[:, None] * zb[None, :]
+    return out
+
+
+def check_gram(got: torch.Tensor, want: torch.Tensor):
+    """``got``: the (a_count, b_count) float64 entries pgenhip_sample_gram wrote (any row stride); ``want``: the int64 sums they must
+    equal exactly.  -> None or (i, l, got, want) of the first wrong entry (NaN differs from everything)."""
+    i = _first_diff(got, want.to(torch.float64))
+    if i is None:
+        return None
+    bc = int(want.shape[1])
+    return i // bc, i % bc, float(got[i // bc, i % bc]), int(want[i // bc, i % bc])
+
+
+def check_variant_sums(sums: torch.Tensor, recs_rows: Sequence[torch.Tensor], n: int, kept, values, slab: int = SLAB):
+    """``sums``: the V * C * 4 float64 values pgenhip_variant_sums wrote.  ``values``: (K, C) or (K,) small integers, one row per kept
+    sample: a numpy array, or a tensor on the device of ``sums`` (an int64 tensor is used as it is, rows of any stride).  For every
+    row, column and code the expected sum is formed in int64, slab by slab, as a masked sum of the values, so ``sums`` must equal it
+    exactly as float64.  -> None or (row, column, code, got, want)."""
+    dev = sums.device
+    kept = as_kept(kept, dev)
+    k = kept_count(n, kept)
+    if isinstance(values, torch.Tensor):
+        vals = values if values.dtype == torch.int64 else values.to(torch.int64)
+        assert values.dtype == torch.int64 or bool((vals == values).all()), "values must be integers: the comparison is exact"
+        vals = vals.to(dev)
+    else:
+        vals = torch.from_numpy(_int_array(values, "values").copy()).to(dev)
+    if vals.dim() == 1:
+        vals = vals[:, None]
+    assert vals.shape[0] >= k
+    c = int(vals.shape[1])
+    v = len(recs_rows)
+    want = torch.zeros((v, c, 4), dtype=torch.int64, device=dev)
+    slab = max(1, min(slab, (1 << 26) // c))   # a slab of ranks holds C columns of int64, masked: bound its bytes
+    for a, b in _slabs(k, slab):
+        va = vals[a:b]
+        for j, rec in enumerate(recs_rows):
+            code = codes(rec, a, b, kept)
+            for x in range(4):
+                want[j, :, x] += torch.where((code == x)[:, None], va, 0).sum(dim=0)
+    got = sums.reshape(-1)[: v * c * 4].view(v, c, 4)
+    i = _first_diff(got, want.to(torch.float64))   # (NaN differs from everything, itself included)
+    if i is None:
+        return None
+    return i // (4 * c), (i // 4) % c, i % 4, float(got.reshape(-1)[i]), int(want.reshape(-1)[i])
+
+
 # ---- periodic rows: a closed form for windows too wide to enumerate ------------------------------------------------------------------
 PERIOD = 45   # shares no factor with the pair kernel's 16-row tile: every tile phase meets every row of the period
 

@@ -5,7 +5,8 @@ One shared buffer of 2^32 + 4 099 + 8 * R_max + 64 bytes: random bytes in its fi
 offset lands on when it is cut to 32 bits: a wrong record, read in bounds) and from 64 bytes before FAR to its end (the far rows).
 Each call mixes near and far rows through (i) d_variant_idx with record_stride = FAR, (ii) a small stride with d_variant_idx values
 near FAR / stride, (iii) d_record_off; the packed-record, score, pair-table and sample-pair-table entry points also take (iv) two
-rows by stride alone, FAR bytes apart.  Expected bytes: the CPU oracle and the numpy references on the few records involved.
+rows by stride alone, FAR bytes apart.  Expected bytes: the CPU oracle and the numpy references on the few records involved.  The Gram
+matrix and the per-variant sums take integer tables and values, so their FP64 results are compared exactly.
 test_sample_scores_far_weights does the same for the other pointer a kernel offsets by a row number: d_weights.
 
 The kernels that cannot gather (RUNS, the pick family's packed path, the line-run kernel) get dense records that cross 2^32
@@ -17,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+import gram_ref as GR
 import longrow_ref as LR
 import matrix_ref as MR
 import pack_ref as PK
@@ -26,7 +28,10 @@ import pgen_rs_amd
 import score_ref as SCR
 import spair_ref as SPR
 import subset_plan as SP
+import vsum_ref as VR
 from pgen_rs_amd import _capi
+from test_sample_gram_gpu import int_tables
+from test_variant_sums_gpu import int_values
 
 pytestmark = pytest.mark.gpu
 
@@ -425,6 +430,80 @@ def test_sample_pair_stats_far_records(far, n, k, a, b, kernel):
                 if not (got == exp).all():
                     word = int(np.flatnonzero(got != exp)[0])
                     raise AssertionError(f"{what}: word {word} (pair {word // 16}, cell {word % 16}): got {got[word]}, want {exp[word]}")
+
+
+# ---- Gram matrix and per-variant sums: integer tables and values, exact --------------------------------------------------------------
+GRAM = {"general": _capi.GRAM_GENERAL, "mfma": _capi.GRAM_MFMA, "auto": _capi.GRAM_AUTO}
+VSUM = {"general": _capi.VSUM_GENERAL, "mfma": _capi.VSUM_MFMA, "auto": _capi.VSUM_AUTO}
+
+
+@pytest.mark.parametrize("kernel", ["general", "mfma", "auto"])
+@pytest.mark.parametrize("n,k,a,b", SPAIR_SHAPES, ids=[f"N{n}-{'all' if k is None else k}" for n, k, _, _ in SPAIR_SHAPES])
+def test_sample_gram_far_records(far, n, k, a, b, kernel):
+    """pgenhip_sample_gram and pgenhip_sample_gram_at: GENERAL, MFMA and AUTO over all four row sources (the MFMA kernel has its own row
+    address, compiled per source: its stride, variant_idx and record_off instantiations, with and without a kept list, each read a
+    far row), integer tables by position in the selection, overwrite and ACCUMULATE onto an integer prefill.  Exact.  Needs 5 GiB."""
+    kept = kept_for(n, k)
+    r = MR.rsize(n)
+    prefill = -1000.0
+    nbytes = 8 * a[1] * b[1]
+    with pgen_rs_amd.GtEngine(n, kept_idx=kept, device=0) as eng:
+        for sname, offs, kw, offs_at in sources(n, plain=True):
+            v = len(offs)
+            t = int_tables(v, n + v)
+            codes = GR.unpack(far.records(offs, r), n, kept)
+            want = GR.gram_ref(codes[:, a[0]:a[0] + a[1]], t, codes[:, b[0]:b[0] + b[1]])
+            d_t = torch.from_numpy(t).to(DEV)
+            kw_t, at_t = tensors(kw, offs_at)
+            for accumulate in (False, True):
+                buf, front = framed(nbytes, align=8)
+                out = buf[front: front + nbytes].view(torch.float64)
+                if accumulate:
+                    out.fill_(prefill)
+                if at_t is None:
+                    eng.sample_gram(far.dev, n_variants=v, code_values=d_t, a=a, b=b, out=out, accumulate=accumulate, kernel=GRAM[kernel], **kw_t)
+                else:
+                    eng.sample_gram_at(far.dev, at_t, d_t, v, a=a, b=b, out=out, accumulate=accumulate, kernel=GRAM[kernel])
+                eng.wait()
+                what = f"N={n} {'all' if k is None else k} a={a} b={b} {sname} kernel {kernel} accumulate={accumulate}"
+                got = payload(buf, front, nbytes, what).view(np.float64).reshape(a[1], b[1])
+                exp = want + (prefill if accumulate else 0.0)
+                if not np.array_equal(got, exp):
+                    i, l = np.argwhere(got != exp)[0]
+                    raise AssertionError(f"{what}: entry ({i}, {l}): got {got[i, l]!r}, want {exp[i, l]!r}")
+
+
+@pytest.mark.parametrize("kernel", ["general", "mfma", "auto"])
+@pytest.mark.parametrize("c", [1, 16])
+@pytest.mark.parametrize("n,k", [(n, k) for n, k, _, _ in SPAIR_SHAPES], ids=[f"N{n}-{'all' if k is None else k}" for n, k, _, _ in SPAIR_SHAPES])
+def test_variant_sums_far_records(far, n, k, c, kernel):
+    """pgenhip_variant_sums and pgenhip_variant_sums_at with C = 1 and C = 16: GENERAL, MFMA and AUTO over all four row sources, integer
+    values in [-8, 8].  Exact.  Needs 5 GiB."""
+    kept = kept_for(n, k)
+    kk = n if kept is None else k
+    r = MR.rsize(n)
+    v16 = int_values(np.random.default_rng(n + c), kk)
+    d_v16 = torch.from_numpy(v16).to(DEV)
+    vals = d_v16[:, 0].contiguous() if c == 1 else d_v16
+    with pgen_rs_amd.GtEngine(n, kept_idx=kept, device=0) as eng:
+        for sname, offs, kw, offs_at in sources(n, plain=True):
+            v = len(offs)
+            want, _ = VR.vsum_ref(far.records(offs, r), n, v16[:, :c], kept)
+            kw_t, at_t = tensors(kw, offs_at)
+            nbytes = 8 * v * c * 4
+            buf, front = framed(nbytes, align=8)
+            out = buf[front: front + nbytes].view(torch.float64)
+            if at_t is None:
+                eng.variant_sums(far.dev, vals, out=out, flags=VSUM[kernel], n_variants=v, **kw_t)
+            else:
+                eng.variant_sums_at(far.dev, at_t, vals, out=out, flags=VSUM[kernel], n_variants=v)
+            eng.wait()
+            what = f"N={n} K={kk} C={c} {sname} kernel {kernel}"
+            got = payload(buf, front, nbytes, what).view(np.float64).reshape(v, c, 4)
+            if not np.array_equal(got, want):
+                row, col, code = np.argwhere(got != want)[0]
+                raise AssertionError(f"{what}: row {row} (record at byte {offs[row]:#x}) column {col} code {code}: got {got[row, col, code]!r}, "
+                                     f"want {want[row, col, code]!r}")
 
 
 # ---- dense records that cross 2^32 themselves ---------------------------------------------------------------------------------------

@@ -1,11 +1,13 @@
 """The slab-wise torch reference of the long-row GPU tests (longrow_ref.py) against the CPU oracle's GT text (pgen_oracle.decode_emit),
-the oracle's counts (count_ref.py) and the numpy references (matrix_ref.py, pack_ref.py, score_ref.py, pair_ref.py, spair_ref.py) — on
-the CPU, with a slab of 97 samples so that slab seams fall inside record bytes, on records with dirty pad bits."""
+the oracle's counts (count_ref.py) and the numpy references (matrix_ref.py, pack_ref.py, score_ref.py, pair_ref.py, spair_ref.py,
+gram_ref.py, vsum_ref.py) — on the CPU, with a slab of 97 samples so that slab seams fall inside record bytes, on records with dirty
+pad bits."""
 import numpy as np
 import pytest
 import torch
 
 import count_ref as CR
+import gram_ref as GR
 import longrow_ref as LR
 import matrix_ref as MR
 import pack_ref as PK
@@ -13,6 +15,7 @@ import pair_ref as PR
 import pgen_oracle as oracle
 import score_ref as SCR
 import spair_ref as SPR
+import vsum_ref as VR
 
 SLAB = 97
 N_LIST = [1, 5, 97, 1003, 70_001]
@@ -245,3 +248,76 @@ def test_periodic_closed_form(v, w):
     want = PR.pair_r2(PR.pair_tables(codes, v, w, fill=-1), v, fill=np.float32(0)).view(np.int32)
     got = LR.periodic_expected(r2, 0, v, w, v, 0).numpy()
     assert (got == want).all()
+
+
+# ---- Gram ranges and per-variant sums: against gram_ref and vsum_ref ------------------------------------------------------------------
+SUMS_N = [5, 63, 300, 2504]
+SUMS_KEEPS = ["all", "sparse", "every7"]
+
+
+def sums_kept(n: int, keep: str):
+    if keep == "all":
+        return None
+    if keep == "sparse":
+        return np.unique(np.linspace(0, n - 1, min(n, 9)).astype(np.int64)).astype(np.uint32)   # samples 0 and N - 1 among them
+    return np.arange(0, n, 7, dtype=np.uint32)
+
+
+@pytest.mark.parametrize("keep", SUMS_KEEPS)
+@pytest.mark.parametrize("n", SUMS_N)
+def test_gram_ranges(n, keep):
+    """gram_ranges equals gram_ref.gram_ref on ranges that begin and end inside record bytes, on a gather that repeats a row (the
+    tables go with the position), and check_gram names a single planted wrong entry."""
+    kept = sums_kept(n, keep)
+    recs = records(n)
+    rows = [0, 2, 1, 2, 0]
+    k = LR.kept_count(n, kept)
+    tables = np.random.default_rng(n + len(keep)).integers(-8, 9, size=(len(rows), 4)).astype(np.float64)
+    codes = GR.unpack(recs[rows], n, kept)
+    recs_rows = [torch.from_numpy(recs[j].copy()) for j in rows]
+    for a, b in (((0, min(k, 70)), (max(0, k - 33), min(k, 33))), ((k - 1, 1), (0, min(k, 5))), ((k // 3, min(7, k - k // 3)), (k // 3, min(7, k - k // 3))),
+                 ((min(1, k - 1), min(k - min(1, k - 1), 67)), (0, k))):
+        want = GR.gram_ref(codes[:, a[0]:a[0] + a[1]], tables, codes[:, b[0]:b[0] + b[1]])
+        got = LR.gram_ranges(recs_rows, n, kept, tables, a, b)
+        assert got.dtype == torch.int64 and got.shape == (a[1], b[1]) and np.array_equal(got.numpy().astype(np.float64), want)
+        out = torch.full((a[1], b[1] + 3), -1.5, dtype=torch.float64)[:, :b[1]]   # a padded pitch, as the GPU tests have
+        out.copy_(torch.from_numpy(want))
+        assert LR.check_gram(out, got) is None
+        for i, l in {(0, 0), (a[1] - 1, b[1] - 1), (a[1] // 2, b[1] // 3)}:
+            bad = out.clone()
+            bad[i, l] += 1.0
+            found = LR.check_gram(bad, got)
+            assert found is not None and found[:2] == (i, l) and found[2] == found[3] + 1, found
+        bad = out.clone()
+        bad[0, 0] = float("nan")
+        assert LR.check_gram(bad, got)[:2] == (0, 0)
+
+
+@pytest.mark.parametrize("slab", [7, SLAB])
+@pytest.mark.parametrize("c", [1, 3, 16])
+@pytest.mark.parametrize("keep", SUMS_KEEPS)
+@pytest.mark.parametrize("n", SUMS_N)
+def test_variant_sums_check(n, keep, c, slab):
+    """check_variant_sums accepts vsum_ref.vsum_ref's sums with slabs of 7 and 97 ranks (seams inside record bytes), values given as a
+    numpy array, as an int64 tensor and (C = 3) as a view of 16-wide rows, and names a single planted wrong entry."""
+    kept = sums_kept(n, keep)
+    recs = records(n)
+    rows = [0, 2, 1, 2]   # a gather that repeats a row
+    k = LR.kept_count(n, kept)
+    v16 = np.random.default_rng(n + c).integers(-8, 9, size=(k, 16))
+    vals = v16[:, :c]
+    want, _ = VR.vsum_ref(recs[rows], n, vals.astype(np.float64), kept)
+    recs_rows = [torch.from_numpy(recs[j].copy()) for j in rows]
+    got = torch.from_numpy(want.reshape(-1).copy())
+    assert LR.check_variant_sums(got, recs_rows, n, kept, vals.astype(np.float64), slab=slab) is None
+    t_vals = torch.from_numpy(v16.astype(np.int64))[:, :c]
+    assert t_vals.stride(0) == 16
+    assert LR.check_variant_sums(got.view(len(rows), c, 4), recs_rows, n, kept, t_vals[:, 0] if c == 1 else t_vals, slab=slab) is None
+    for row, col, code in {(0, 0, 0), (len(rows) - 1, c - 1, 3), (1, c // 2, 2)}:
+        bad = got.clone()
+        bad[(row * c + col) * 4 + code] += 1.0
+        found = LR.check_variant_sums(bad, recs_rows, n, kept, t_vals, slab=slab)
+        assert found is not None and found[:3] == (row, col, code) and found[3] == found[4] + 1, found
+    bad = got.clone()
+    bad[0] = float("nan")
+    assert LR.check_variant_sums(bad, recs_rows, n, kept, t_vals, slab=slab)[:3] == (0, 0, 0)

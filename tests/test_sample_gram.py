@@ -64,10 +64,13 @@ def test_kernel_constants_the_gpu_tests_rely_on():
         f"constexpr uint32_t kStepRows = {GP.STEP_ROWS};",
         f"constexpr uint32_t kGroupRows = {GP.GROUP_ROWS};",
         f"constexpr uint32_t kMinSliceRows = {GP.MIN_SLICE_ROWS};",
+        f"constexpr uint32_t kMaxGridTiles = 1u << {GP.MAX_GRID_TILES.bit_length() - 1};",
+        f"constexpr uint32_t kMaxGridBlocks = 1u << {GP.MAX_GRID_BLOCKS.bit_length() - 1};",
         "__builtin_amdgcn_mfma_f64_16x16x4f64(",
     ]:
         assert line in src, line
     assert GP.mfma_slices(1000, 70, 70, forced=7) == 7 and GP.mfma_slices(33, 70, 70, forced=7) == 2 and GP.mfma_slices(5, 70, 70) == 1
+    assert GP.general_slices(1000, 70, 70, forced=7) == 7 and GP.general_slices(5, 70, 70, forced=7) == 5 and GP.general_slices(75, 130, 70) == 1
 
 
 # ---- the reference ----
