@@ -253,6 +253,16 @@ static int select_rows(const pgenhip_ctx *ctx, RowSource &a, const void *d_recor
     return PGENHIP_OK;
 }
 
+// The bound on the bytes the selected records span.  A record's address is plain 64-bit pointer arithmetic in the kernels (row_record,
+// gt_common.hip.h) and the bound is decode_matrix's, 2^52 bytes: by stride, all rows' records lie inside the span; with a variant
+// list the row numbers live on the device (as record_off's offsets do) and only the stride itself is bounded.
+static constexpr uint64_t kMaxSpan = 1ull << 52;
+static bool record_span_too_large(uint64_t record_stride, const uint32_t *d_variant_idx, const uint64_t *d_record_off, uint32_t n_variants)
+{
+    if (n_variants <= 1 || d_record_off) return false;
+    return record_stride >= (d_variant_idx ? kMaxSpan : kMaxSpan / n_variants);
+}
+
 // the *_at entries' own check, in front of their core (which reports a NULL ctx)
 static int check_record_off(const pgenhip_ctx *ctx, const uint64_t *d_record_off, uint32_t n_variants)
 {
@@ -667,12 +677,8 @@ static int sample_scores_core(pgenhip_ctx *ctx, const void *d_records, uint64_t 
     const uint32_t K = ctx->kept_count;
     if (K != 0u && !d_scores) return fail(PGENHIP_ERR_BAD_ARG, "d_scores is NULL");
     if (K != 0u && ((uintptr_t)d_scores & 7u)) return fail(PGENHIP_ERR_BAD_ARG, "d_scores is not 8-byte aligned");
-    // byte offsets are 64-bit arithmetic in the kernel; the bound is decode_matrix's (2^52 bytes).  With a variant list the row
-    // numbers live on the device (as record_off's offsets do) and only the stride itself is bounded
-    constexpr uint64_t kMaxSpan = 1ull << 52;
-    const bool by_stride = n_variants > 1 && !d_record_off;
-    if ((n_variants > 1 && w_stride >= kMaxSpan / 4u / n_variants) || (by_stride && !d_variant_idx && record_stride >= kMaxSpan / n_variants) ||
-        (by_stride && d_variant_idx && record_stride >= kMaxSpan))
+    // byte offsets are 64-bit arithmetic in the kernel; the bound is decode_matrix's (2^52 bytes)
+    if ((n_variants > 1 && w_stride >= kMaxSpan / 4u / n_variants) || record_span_too_large(record_stride, d_variant_idx, d_record_off, n_variants))
         return fail(PGENHIP_ERR_TOO_LARGE, "score offsets do not fit the kernel's index types");
     if (K == 0u) return PGENHIP_OK;   // nothing to write
     ScoreArgs a;
@@ -723,12 +729,9 @@ static int variant_sums_core(pgenhip_ctx *ctx, const void *d_records, uint64_t r
     if (n_variants && !d_sums) return fail(PGENHIP_ERR_BAD_ARG, "d_sums is NULL");
     if ((uintptr_t)d_sums & 7u) return fail(PGENHIP_ERR_BAD_ARG, "d_sums is not 8-byte aligned");
     if (shape == PGENHIP_VSUM_MFMA && K == 0u) return fail(PGENHIP_ERR_BAD_ARG, "the MFMA shape needs at least one kept sample");
-    // byte offsets are 64-bit arithmetic in the kernel; the bound is decode_matrix's (2^52 bytes).  With a variant list the row
-    // numbers live on the device (as record_off's offsets do) and only the stride itself is bounded
-    constexpr uint64_t kMaxSpan = 1ull << 52;
-    const bool by_stride = n_variants > 1 && !d_record_off;
+    // byte offsets are 64-bit arithmetic in the kernel; the bound is decode_matrix's (2^52 bytes)
     if ((K > 1u && v_stride >= kMaxSpan / 8u / K) || (uint64_t)n_variants * n_columns >= kMaxSpan / 32u ||
-        (by_stride && !d_variant_idx && record_stride >= kMaxSpan / n_variants) || (by_stride && d_variant_idx && record_stride >= kMaxSpan))
+        record_span_too_large(record_stride, d_variant_idx, d_record_off, n_variants))
         return fail(PGENHIP_ERR_TOO_LARGE, "variant_sums offsets do not fit the kernel's index types");
     if (n_variants == 0) return PGENHIP_OK;
     VsumArgs a;
@@ -793,13 +796,9 @@ static int decode_matrix_core(pgenhip_ctx *ctx, const void *d_records, uint64_t 
     if (rc) return rc;
     const uint64_t rows = sample_major ? K : n_variants, inner = sample_major ? n_variants : K;
     if (rows > 1 && out_stride < inner * elem_bytes) return fail(PGENHIP_ERR_BAD_ARG, "out_stride < one output row");
-    // the kernels index elements and 16-byte chunks in 64 bits and divide through a double reciprocal: exact below 2^52.  A record's
-    // address is plain 64-bit pointer arithmetic (row_record, gt_common.hip.h): by stride, all rows' records lie inside the span; with
-    // a variant list the row numbers live on the device (as record_off's offsets do) and only the stride itself is bounded
-    constexpr uint64_t kMaxSpan = 1ull << 52;
-    const bool by_stride = n_variants > 1 && !d_record_off;
+    // the kernels index elements and 16-byte chunks in 64 bits and divide through a double reciprocal: exact below 2^52
     if ((uint64_t)n_variants * K >= kMaxSpan / 16u || (rows > 1 && out_stride >= kMaxSpan / rows) ||
-        (by_stride && !d_variant_idx && record_stride >= kMaxSpan / n_variants) || (by_stride && d_variant_idx && record_stride >= kMaxSpan))
+        record_span_too_large(record_stride, d_variant_idx, d_record_off, n_variants))
         return fail(PGENHIP_ERR_TOO_LARGE, "matrix offsets do not fit the kernels' index types");
     a.kept_idx = all_kept ? nullptr : ctx->d_kept;
     a.kept_count = K;
@@ -901,10 +900,7 @@ static int sample_pair_stats_core(pgenhip_ctx *ctx, const void *d_records, uint6
     if (pairs != 0u && !d_out) return fail(PGENHIP_ERR_BAD_ARG, "d_out is NULL");
     if (pairs != 0u && ((uintptr_t)d_out & 15u)) return fail(PGENHIP_ERR_BAD_ARG, "d_out is not 16-byte aligned");
     // byte offsets of table entries and records are 64-bit arithmetic in the kernels; the bounds are decode_matrix's (2^52 bytes)
-    constexpr uint64_t kMaxSpan = 1ull << 52;
-    const bool by_stride = n_variants > 1 && !d_record_off;
-    if (pairs >= kMaxSpan / 64u || (by_stride && !d_variant_idx && record_stride >= kMaxSpan / n_variants) ||
-        (by_stride && d_variant_idx && record_stride >= kMaxSpan))
+    if (pairs >= kMaxSpan / 64u || record_span_too_large(record_stride, d_variant_idx, d_record_off, n_variants))
         return fail(PGENHIP_ERR_TOO_LARGE, "sample_pair_stats offsets do not fit the kernels' index types");
     if (pairs == 0u) return PGENHIP_OK;   // nothing to write
     SpairArgs a;
@@ -961,10 +957,8 @@ static int sample_gram_core(pgenhip_ctx *ctx, const void *d_records, uint64_t re
     if (pairs != 0u && ((uintptr_t)d_out & 7u)) return fail(PGENHIP_ERR_BAD_ARG, "d_out is not 8-byte aligned");
     if (a_count > 1u && out_stride < b_count) return fail(PGENHIP_ERR_BAD_ARG, "out_stride < b_count");
     // byte offsets of entries, tables and records are 64-bit arithmetic in the kernels; the bounds are decode_matrix's (2^52 bytes)
-    constexpr uint64_t kMaxSpan = 1ull << 52;
-    const bool by_stride = n_variants > 1 && !d_record_off;
     if ((a_count > 1u && out_stride >= kMaxSpan / 8u / a_count) || (uint64_t)n_variants * 32u >= kMaxSpan ||
-        (by_stride && !d_variant_idx && record_stride >= kMaxSpan / n_variants) || (by_stride && d_variant_idx && record_stride >= kMaxSpan))
+        record_span_too_large(record_stride, d_variant_idx, d_record_off, n_variants))
         return fail(PGENHIP_ERR_TOO_LARGE, "sample_gram offsets do not fit the kernels' index types");
     if (pairs == 0u) return PGENHIP_OK;   // nothing to write
     GramArgs a;
@@ -1036,12 +1030,8 @@ static int pack_records_core(pgenhip_ctx *ctx, const void *d_records, uint64_t r
     rc = select_rows(ctx, a, d_records, record_stride, d_variant_idx, d_record_off, n_variants);
     if (rc) return rc;
     if (n_variants > 1 && out_stride < RK) return fail(PGENHIP_ERR_BAD_ARG, "out_stride < one packed record");
-    // byte offsets are 64-bit arithmetic in the kernels; the bound is decode_matrix's (2^52 bytes).  With a variant list the row
-    // numbers live on the device (as record_off's offsets do) and only the stride itself is bounded
-    constexpr uint64_t kMaxSpan = 1ull << 52;
-    const bool by_stride = n_variants > 1 && !d_record_off;
-    if ((n_variants > 1 && out_stride >= kMaxSpan / n_variants) || (by_stride && !d_variant_idx && record_stride >= kMaxSpan / n_variants) ||
-        (by_stride && d_variant_idx && record_stride >= kMaxSpan))
+    // byte offsets are 64-bit arithmetic in the kernels; the bound is decode_matrix's (2^52 bytes)
+    if ((n_variants > 1 && out_stride >= kMaxSpan / n_variants) || record_span_too_large(record_stride, d_variant_idx, d_record_off, n_variants))
         return fail(PGENHIP_ERR_TOO_LARGE, "pack offsets do not fit the kernels' index types");
     a.kept_count = K;
     a.out = static_cast<uint8_t *>(d_out);

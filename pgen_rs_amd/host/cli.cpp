@@ -28,6 +28,7 @@
 // --bgzf-level <1-9>, --compress-threads <T>) and `pgen-hip bgzf <IN> <OUT>`, the same writer on a file.
 // Exit codes: 0 ok; 2 usage error (clap's code); 101 where the reference would panic.
 #include <cerrno>
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -363,6 +364,51 @@ void print_stats(const OutputStats &st, std::chrono::steady_clock::time_point t_
                  st.seconds_kernel, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_main).count());
 }
 
+// The arguments of a command that takes filter's selection: the options every such command has and --stats, beside the command's
+// own valued options and flags, and exactly one positional argument, the fileset's prefix
+struct SelectionArgs : Args {
+    SelectionArgs(int argc, char **argv, std::vector<std::pair<std::string, char>> valued, std::vector<std::pair<std::string, char>> flags)
+    {
+        for (const char *name : {"include-var", "include-sam", "gpus", "shards", "block-mib", "read-threads", "filter-threads"}) valued.emplace_back(name, 0);
+        valued.emplace_back("out", 'o');
+        flags.emplace_back("stats", 0);
+        static_cast<Args &>(*this) = parse(argc, argv, 2, valued, flags);
+        if (positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
+    }
+    // the command's last step: the --stats line (behind the lines the command itself has printed)
+    int done(const OutputStats &st, std::chrono::steady_clock::time_point t_main) const
+    {
+        if (has("stats")) print_stats(st, t_main);
+        return 0;
+    }
+};
+
+// `--name <PLACEHOLDER>` as a whole number in [lo, hi]; `what` ends the message for anything else
+unsigned long long unsigned_value(const std::string &s, const char *name, const char *placeholder, unsigned long long lo, unsigned long long hi, const char *what)
+{
+    char *end = nullptr;
+    errno = 0;
+    const unsigned long long v = std::strtoull(s.c_str(), &end, 10);
+    if (s.empty() || s[0] == '-' || *end != '\0' || errno != 0 || v < lo || v > hi)
+        usage_error("invalid value '" + s + "' for '--" + name + " <" + placeholder + ">': " + what);
+    return v;
+}
+
+// the same for a number in [lo, hi] (a NaN is in no range)
+double double_value(const std::string &s, const char *name, const char *placeholder, double lo, double hi, const char *what)
+{
+    char *end = nullptr;
+    errno = 0;
+    const double v = std::strtod(s.c_str(), &end);
+    if (s.empty() || *end != '\0' || errno != 0 || !(v >= lo && v <= hi))
+        usage_error("invalid value '" + s + "' for '--" + name + " <" + placeholder + ">': " + what);
+    return v;
+}
+
+constexpr unsigned long long kNoLimit = ~0ull;
+uint64_t block_rows_value(const std::string &s) { return unsigned_value(s, "block-rows", "B", 1, kNoLimit, "a number of variants from 1"); }
+uint32_t sample_tile_value(const std::string &s) { return (uint32_t)unsigned_value(s, "sample-tile", "T", 1, 65536, "a number of samples from 1 to 65536"); }
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -393,9 +439,7 @@ int main(int argc, char **argv)
             return 0;
         }
         if (cmd == "filter") {  // src/main.rs:114-124
-            Args a = parse(argc, argv, 2, {{"include-var", 0}, {"include-sam", 0}, {"out", 'o'}, {"gpus", 0}, {"shards", 0}, {"block-mib", 0}, {"launch-mib", 0}, {"write-threads", 0}, {"read-threads", 0}, {"filter-threads", 0}, {"bgzf-level", 0}, {"compress-threads", 0}},
-                           {{"stats", 0}, {"dry-run", 0}, {"bgzf", 0}});
-            if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
+            const SelectionArgs a(argc, argv, {{"launch-mib", 0}, {"write-threads", 0}, {"bgzf-level", 0}, {"compress-threads", 0}}, {{"dry-run", 0}, {"bgzf", 0}});
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
             auto ends_with = [](const std::string &x, const char *suffix) { const size_t n = std::strlen(suffix); return x.size() >= n && x.compare(x.size() - n, n, suffix) == 0; };
             const bool bgzf = a.has("bgzf") || (a.get("out") && ends_with(*a.get("out"), ".gz"));
@@ -424,44 +468,30 @@ int main(int argc, char **argv)
             if (auto c = a.get("compress-threads")) opt.compress_threads = std::max(1, std::atoi(c->c_str()));
             if (auto w = a.get("write-threads")) opt.write_threads = std::max(1, std::atoi(w->c_str()));
             if (auto m = a.get("launch-mib")) opt.launch_bytes = (uint64_t)std::max(1, std::atoi(m->c_str())) << 20;
-            const OutputStats st = pfile.output_vcf(a.get("include-sam"), a.get("include-var"), out_file, opt);  // :123
-            if (a.has("stats")) print_stats(st, t_main);
-            return 0;
+            return a.done(pfile.output_vcf(a.get("include-sam"), a.get("include-var"), out_file, opt), t_main);  // :123
         }
         if (cmd == "freq") {
-            Args a = parse(argc, argv, 2, {{"include-var", 0}, {"include-sam", 0}, {"out", 'o'}, {"gpus", 0}, {"shards", 0}, {"block-mib", 0}, {"read-threads", 0}, {"filter-threads", 0}},
-                           {{"stats", 0}});
-            if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
+            const SelectionArgs a(argc, argv, {}, {});
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
-            const OutputStats st = pfile.output_freq(a.get("include-sam"), a.get("include-var"), a.get("out").value_or(""), output_options(a));
-            if (a.has("stats")) print_stats(st, t_main);
-            return 0;
+            return a.done(pfile.output_freq(a.get("include-sam"), a.get("include-var"), a.get("out").value_or(""), output_options(a)), t_main);
         }
         if (cmd == "sample-counts") {
-            Args a = parse(argc, argv, 2, {{"include-var", 0}, {"include-sam", 0}, {"out", 'o'}, {"gpus", 0}, {"shards", 0}, {"block-mib", 0}, {"read-threads", 0}, {"filter-threads", 0}},
-                           {{"stats", 0}});
-            if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
+            const SelectionArgs a(argc, argv, {}, {});
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
-            const OutputStats st = pfile.output_sample_counts(a.get("include-sam"), a.get("include-var"), a.get("out").value_or(""), output_options(a));
-            if (a.has("stats")) print_stats(st, t_main);
-            return 0;
+            return a.done(pfile.output_sample_counts(a.get("include-sam"), a.get("include-var"), a.get("out").value_or(""), output_options(a)), t_main);
         }
         if (cmd == "score") {
-            Args a = parse(argc, argv, 2, {{"weights", 0}, {"include-var", 0}, {"include-sam", 0}, {"out", 'o'}, {"gpus", 0}, {"shards", 0}, {"block-mib", 0}, {"read-threads", 0}, {"filter-threads", 0}},
-                           {{"stats", 0}, {"no-mean-imputation", 0}, {"avg", 0}});
-            if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
+            const SelectionArgs a(argc, argv, {{"weights", 0}}, {{"no-mean-imputation", 0}, {"avg", 0}});
             if (!a.has("weights") || a.get("weights")->empty()) usage_error("the following required arguments were not provided: --weights <FILE>");
             ScoreOptions s;
             s.mean_imputation = !a.has("no-mean-imputation");
             s.average = a.has("avg");
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
             const OutputStats st = pfile.output_score(a.get("include-sam"), a.get("include-var"), *a.get("weights"), a.get("out").value_or(""), s, output_options(a));
-            if (a.has("stats")) {
+            if (a.has("stats"))
                 std::fprintf(stderr, "{\"weights_matched\": %llu, \"weights_flipped\": %llu, \"weights_skipped\": %llu}\n",
                              (unsigned long long)st.score_matched, (unsigned long long)st.score_flipped, (unsigned long long)st.score_skipped);
-                print_stats(st, t_main);
-            }
-            return 0;
+            return a.done(st, t_main);
         }
         if (cmd == "assoc") {
             if (argc >= 3 && std::string(argv[2]) == "--p-of") {
@@ -471,9 +501,7 @@ int main(int argc, char **argv)
                 std::printf("%.17g\n", student_t_two_sided_p(t, df));
                 return 0;
             }
-            Args a = parse(argc, argv, 2, {{"pheno", 0}, {"pheno-name", 0}, {"covar", 0}, {"include-var", 0}, {"include-sam", 0}, {"out", 'o'}, {"gpus", 0}, {"shards", 0}, {"block-mib", 0}, {"read-threads", 0}, {"filter-threads", 0}},
-                           {{"stats", 0}});
-            if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
+            const SelectionArgs a(argc, argv, {{"pheno", 0}, {"pheno-name", 0}, {"covar", 0}}, {});
             if (!a.has("pheno") || a.get("pheno")->empty()) usage_error("the following required arguments were not provided: --pheno <FILE>");
             if (a.has("covar") && a.get("covar")->empty()) usage_error("a value is required for '--covar <FILE>'");
             AssocOptions ao;
@@ -493,140 +521,63 @@ int main(int argc, char **argv)
             }
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
             const OutputStats st = pfile.output_assoc(a.get("include-sam"), a.get("include-var"), ao, a.get("out").value_or(""), output_options(a));
-            if (a.has("stats")) {
-                std::fprintf(stderr, "{\"samples_dropped\": %llu}\n", (unsigned long long)st.assoc_dropped);
-                print_stats(st, t_main);
-            }
-            return 0;
+            if (a.has("stats")) std::fprintf(stderr, "{\"samples_dropped\": %llu}\n", (unsigned long long)st.assoc_dropped);
+            return a.done(st, t_main);
         }
         if (cmd == "matrix") {
-            Args a = parse(argc, argv, 2, {{"include-var", 0}, {"include-sam", 0}, {"out", 'o'}, {"dtype", 0}, {"missing", 0}, {"gpus", 0}, {"shards", 0}, {"block-mib", 0}, {"read-threads", 0}, {"filter-threads", 0}},
-                           {{"stats", 0}, {"sample-major", 0}});
-            if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
+            const SelectionArgs a(argc, argv, {{"dtype", 0}, {"missing", 0}}, {{"sample-major", 0}});
             if (!a.has("out") || a.get("out")->empty()) usage_error("the following required arguments were not provided: --out <OUT_FILE.npy>");
             const MatrixOptions m = matrix_options(a);
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
-            const OutputStats st = pfile.output_matrix(a.get("include-sam"), a.get("include-var"), *a.get("out"), m, output_options(a));
-            if (a.has("stats")) print_stats(st, t_main);
-            return 0;
+            return a.done(pfile.output_matrix(a.get("include-sam"), a.get("include-var"), *a.get("out"), m, output_options(a)), t_main);
         }
         if (cmd == "export") {
-            Args a = parse(argc, argv, 2, {{"include-var", 0}, {"include-sam", 0}, {"out", 'o'}, {"format", 0}, {"gpus", 0}, {"shards", 0}, {"block-mib", 0}, {"read-threads", 0}, {"filter-threads", 0}},
-                           {{"stats", 0}});
-            if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
+            const SelectionArgs a(argc, argv, {{"format", 0}}, {});
             if (!a.has("out") || a.get("out")->empty()) usage_error("the following required arguments were not provided: --out <OUT_PREFIX>");
             const std::string format = a.get("format").value_or("pgen");
             if (format != "pgen" && format != "bed") usage_error("invalid value '" + format + "' for '--format <FORMAT>' [possible values: pgen, bed]");
             ExportOptions e;
             e.bed = format == "bed";
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
-            const OutputStats st = pfile.output_export(a.get("include-sam"), a.get("include-var"), *a.get("out"), e, output_options(a));
-            if (a.has("stats")) print_stats(st, t_main);
-            return 0;
+            return a.done(pfile.output_export(a.get("include-sam"), a.get("include-var"), *a.get("out"), e, output_options(a)), t_main);
         }
         if (cmd == "ld") {
-            Args a = parse(argc, argv, 2, {{"window", 0}, {"min-r2", 0}, {"include-var", 0}, {"include-sam", 0}, {"out", 'o'}, {"gpus", 0}, {"shards", 0}, {"block-mib", 0}, {"block-rows", 0}, {"read-threads", 0}, {"filter-threads", 0}},
-                           {{"stats", 0}, {"counts", 0}});
-            if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
+            const SelectionArgs a(argc, argv, {{"window", 0}, {"min-r2", 0}, {"block-rows", 0}}, {{"counts", 0}});
             if (!a.has("window")) usage_error("the following required arguments were not provided: --window <W>");
             LdOptions ld;
-            {
-                const std::string w = *a.get("window");
-                char *end = nullptr;
-                errno = 0;
-                const unsigned long long v = std::strtoull(w.c_str(), &end, 10);
-                if (w.empty() || w[0] == '-' || *end != '\0' || errno != 0 || v < 1 || v > 0xFFFFFFFFull)
-                    usage_error("invalid value '" + w + "' for '--window <W>': a number of variants from 1 to 4294967295");
-                ld.window = (uint32_t)v;
-            }
-            if (auto m = a.get("min-r2")) {
-                char *end = nullptr;
-                errno = 0;
-                ld.min_r2 = std::strtod(m->c_str(), &end);
-                if (m->empty() || *end != '\0' || errno != 0 || !(ld.min_r2 >= 0.0 && ld.min_r2 <= 1.0))
-                    usage_error("invalid value '" + *m + "' for '--min-r2 <X>': a number from 0 to 1");
-            }
-            if (auto b = a.get("block-rows")) {
-                char *end = nullptr;
-                errno = 0;
-                const unsigned long long v = std::strtoull(b->c_str(), &end, 10);
-                if (b->empty() || (*b)[0] == '-' || *end != '\0' || errno != 0 || v < 1)
-                    usage_error("invalid value '" + *b + "' for '--block-rows <B>': a number of variants from 1");
-                ld.block_rows = v;
-            }
+            ld.window = (uint32_t)unsigned_value(*a.get("window"), "window", "W", 1, 0xFFFFFFFFull, "a number of variants from 1 to 4294967295");
+            if (auto m = a.get("min-r2")) ld.min_r2 = double_value(*m, "min-r2", "X", 0.0, 1.0, "a number from 0 to 1");
+            if (auto b = a.get("block-rows")) ld.block_rows = block_rows_value(*b);
             ld.counts = a.has("counts");
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
-            const OutputStats st = pfile.output_ld(a.get("include-sam"), a.get("include-var"), a.get("out").value_or(""), ld, output_options(a));
-            if (a.has("stats")) print_stats(st, t_main);
-            return 0;
+            return a.done(pfile.output_ld(a.get("include-sam"), a.get("include-var"), a.get("out").value_or(""), ld, output_options(a)), t_main);
         }
         if (cmd == "kinship") {
-            Args a = parse(argc, argv, 2, {{"min-kinship", 0}, {"sample-tile", 0}, {"block-rows", 0}, {"include-var", 0}, {"include-sam", 0}, {"out", 'o'}, {"gpus", 0}, {"shards", 0}, {"block-mib", 0}, {"read-threads", 0}, {"filter-threads", 0}},
-                           {{"stats", 0}, {"counts", 0}});
-            if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
+            const SelectionArgs a(argc, argv, {{"min-kinship", 0}, {"sample-tile", 0}, {"block-rows", 0}}, {{"counts", 0}});
             KinshipOptions k;
             if (auto m = a.get("min-kinship")) {
-                char *end = nullptr;
-                errno = 0;
-                k.min_kinship = std::strtod(m->c_str(), &end);
-                if (m->empty() || *end != '\0' || errno != 0 || !std::isfinite(k.min_kinship))
-                    usage_error("invalid value '" + *m + "' for '--min-kinship <X>': a finite number");
+                k.min_kinship = double_value(*m, "min-kinship", "X", -DBL_MAX, DBL_MAX, "a finite number");
                 k.has_min = true;
             }
-            if (auto t = a.get("sample-tile")) {
-                char *end = nullptr;
-                errno = 0;
-                const unsigned long long v = std::strtoull(t->c_str(), &end, 10);
-                if (t->empty() || (*t)[0] == '-' || *end != '\0' || errno != 0 || v < 1 || v > 65536)
-                    usage_error("invalid value '" + *t + "' for '--sample-tile <T>': a number of samples from 1 to 65536");
-                k.tile = (uint32_t)v;
-            }
-            if (auto b = a.get("block-rows")) {
-                char *end = nullptr;
-                errno = 0;
-                const unsigned long long v = std::strtoull(b->c_str(), &end, 10);
-                if (b->empty() || (*b)[0] == '-' || *end != '\0' || errno != 0 || v < 1)
-                    usage_error("invalid value '" + *b + "' for '--block-rows <B>': a number of variants from 1");
-                k.block_rows = v;
-            }
+            if (auto t = a.get("sample-tile")) k.tile = sample_tile_value(*t);
+            if (auto b = a.get("block-rows")) k.block_rows = block_rows_value(*b);
             k.counts = a.has("counts");
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
-            const OutputStats st = pfile.output_kinship(a.get("include-sam"), a.get("include-var"), a.get("out").value_or(""), k, output_options(a));
-            if (a.has("stats")) print_stats(st, t_main);
-            return 0;
+            return a.done(pfile.output_kinship(a.get("include-sam"), a.get("include-var"), a.get("out").value_or(""), k, output_options(a)), t_main);
         }
         if (cmd == "grm") {
-            Args a = parse(argc, argv, 2, {{"format", 0}, {"sample-tile", 0}, {"block-rows", 0}, {"include-var", 0}, {"include-sam", 0}, {"out", 'o'}, {"gpus", 0}, {"shards", 0}, {"block-mib", 0}, {"read-threads", 0}, {"filter-threads", 0}},
-                           {{"stats", 0}});
-            if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <PFILE_PREFIX>");
+            const SelectionArgs a(argc, argv, {{"format", 0}, {"sample-tile", 0}, {"block-rows", 0}}, {});
             if (!a.has("out") || a.get("out")->empty()) usage_error("the following required arguments were not provided: --out <OUT_PREFIX>");
             const std::string format = a.get("format").value_or("grm-bin");
             if (format != "grm-bin" && format != "rel") usage_error("invalid value '" + format + "' for '--format <FORMAT>' [possible values: grm-bin, rel]");
             GrmOptions g;
             g.rel = format == "rel";
-            if (auto t = a.get("sample-tile")) {
-                char *end = nullptr;
-                errno = 0;
-                const unsigned long long v = std::strtoull(t->c_str(), &end, 10);
-                if (t->empty() || (*t)[0] == '-' || *end != '\0' || errno != 0 || v < 1 || v > 65536)
-                    usage_error("invalid value '" + *t + "' for '--sample-tile <T>': a number of samples from 1 to 65536");
-                g.tile = (uint32_t)v;
-            }
-            if (auto b = a.get("block-rows")) {
-                char *end = nullptr;
-                errno = 0;
-                const unsigned long long v = std::strtoull(b->c_str(), &end, 10);
-                if (b->empty() || (*b)[0] == '-' || *end != '\0' || errno != 0 || v < 1)
-                    usage_error("invalid value '" + *b + "' for '--block-rows <B>': a number of variants from 1");
-                g.block_rows = v;
-            }
+            if (auto t = a.get("sample-tile")) g.tile = sample_tile_value(*t);
+            if (auto b = a.get("block-rows")) g.block_rows = block_rows_value(*b);
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
             const OutputStats st = pfile.output_grm(a.get("include-sam"), a.get("include-var"), *a.get("out"), g, output_options(a));
-            if (a.has("stats")) {
-                std::fprintf(stderr, "{\"variants_skipped\": %llu}\n", (unsigned long long)st.grm_skipped);
-                print_stats(st, t_main);
-            }
-            return 0;
+            if (a.has("stats")) std::fprintf(stderr, "{\"variants_skipped\": %llu}\n", (unsigned long long)st.grm_skipped);
+            return a.done(st, t_main);
         }
         if (cmd == "bgzf") {
             // not in the reference: the BGZF writer of `filter ... -o x.vcf.gz` applied to a file (what `bgzip -c IN > OUT` does)

@@ -6,7 +6,7 @@ Reference: the outer loop of ``Pfile::output_vcf`` (/root/reference/src/pfile.rs
 the kept variants in file order; a shard is a contiguous slice of that iteration space.
 
 There is ONE partitioner, ``pgenhip_shard_range`` in the C ABI: the C++ host's per-device threads
-(``host/pfile.cpp``), ``bench.py``'s ranks and the tests all go through it.
+(``Shards`` in ``host/host_internal.h``), ``bench.py``'s ranks and the tests all go through it.
 """
 from __future__ import annotations
 

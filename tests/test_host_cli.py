@@ -227,3 +227,31 @@ def test_parallel_metadata_filter_matches_serial(tmp_path):
     a, b = dry(1), dry(7)
     assert a.returncode == b.returncode == 0 and a.stdout == b.stdout
     assert json.loads(a.stdout)["variants_kept"] == 50_002
+
+
+BLOCK_ROWS = "invalid value '%s' for '--block-rows <B>': a number of variants from 1"
+SAMPLE_TILE = "invalid value '%s' for '--sample-tile <T>': a number of samples from 1 to 65536"
+WINDOW = "invalid value '%s' for '--window <W>': a number of variants from 1 to 4294967295"
+MIN_R2 = "invalid value '%s' for '--min-r2 <X>': a number from 0 to 1"
+MIN_KINSHIP = "invalid value '%s' for '--min-kinship <X>': a finite number"
+# command and the arguments it needs, option, message, the values the option refuses (0 and -4 are good values of --min-kinship, 0 of --min-r2)
+CHECKED_OPTIONS = [
+    (("ld",), "--window", WINDOW, ("0", "-4", "t", "", "4294967296")),
+    (("ld", "--window", "3"), "--min-r2", MIN_R2, ("-4", "t", "", "1.5", "nan")),
+    (("ld", "--window", "3"), "--block-rows", BLOCK_ROWS, ("0", "-4", "t", "")),
+    (("kinship",), "--min-kinship", MIN_KINSHIP, ("t", "", "inf", "nan")),
+    (("kinship",), "--sample-tile", SAMPLE_TILE, ("0", "-4", "t", "", "70000")),
+    (("kinship",), "--block-rows", BLOCK_ROWS, ("0", "-4", "t", "")),
+    (("grm", "-o", "x"), "--sample-tile", SAMPLE_TILE, ("0", "-4", "t", "", "70000")),
+    (("grm", "-o", "x"), "--block-rows", BLOCK_ROWS, ("0", "-4", "t", "")),
+]
+
+
+@pytest.mark.parametrize("cmd,option,message,value", [(c, o, m, v) for c, o, m, values in CHECKED_OPTIONS for v in values])
+def test_checked_option_messages(cmd, option, message, value):
+    """The checked numeric options name the option, its placeholder and the range, on every command that takes them; the value is
+    refused before the fileset is opened, so the prefix need not exist."""
+    for spelling in ([option, value], [option + "=" + value]):
+        p = run(cmd[0], "no-such-prefix", *cmd[1:], *spelling)
+        assert p.returncode == 2
+        assert p.stderr.split(b"\n")[0].decode() == "error: " + message % value

@@ -108,3 +108,17 @@ def test_tiles_blocks_and_shards_give_the_same_bytes(pfile, flags):
 def test_one_sample_is_the_header_alone(pfile):
     p = run("kinship", str(pfile), "--include-sam", 'IID == "nobody"')
     assert p.returncode == 0 and p.stdout == HEADER, p.stderr
+
+
+def test_variable_width_plain_records_give_the_fixed_width_bytes(tmp_path):
+    """Mode-0x10 records go to the sample-pair kernel through their staged offsets (the `_at` entry): tiles, blocks and a shard
+    seam over 60 plain records give the bytes of the fixed-width file of the same records."""
+    from helpers import plain_record_filesets
+
+    vw, fixed = plain_record_filesets(tmp_path)
+    flags = ["--sample-tile", "16", "--block-rows", "9", "--shards", "2", "--counts", "--include-var", 'RTYPE == "0"']
+    a, b = run("kinship", str(vw), *flags), run("kinship", str(fixed), *flags)
+    assert a.returncode == 0 and b.returncode == 0, a.stderr + b.stderr
+    assert a.stdout == b.stdout and a.stdout.count(b"\n") == 1 + 40 * 39 // 2
+    one = run("kinship", str(fixed), "--counts")
+    assert one.returncode == 0 and one.stdout == b.stdout, one.stderr

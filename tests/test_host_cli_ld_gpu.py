@@ -192,3 +192,17 @@ def test_freq_and_sample_counts_on_the_same_fileset(pfile):
         p = run("sample-counts", str(pfile), *ODD[0], *KEEP3[0], *flags)
         assert p.returncode == 0, p.stderr
         assert p.stdout == want
+
+
+def test_variable_width_plain_records_give_the_fixed_width_bytes(tmp_path):
+    """Mode-0x10 records go to the pair kernel through their staged offsets (the `_at` entry): blocks, halo rows and a shard seam
+    over 60 plain records give the bytes of the fixed-width file of the same records."""
+    from helpers import plain_record_filesets
+
+    vw, fixed = plain_record_filesets(tmp_path)
+    flags = ["--window", "5", "--block-rows", "7", "--shards", "2", "--counts", "--min-r2", "0", "--include-var", 'RTYPE == "0"']
+    a, b = run("ld", str(vw), *flags), run("ld", str(fixed), *flags)
+    assert a.returncode == 0 and b.returncode == 0, a.stderr + b.stderr
+    assert a.stdout == b.stdout and a.stdout.count(b"\n") > 200
+    one = run("ld", str(fixed), "--window", "5", "--counts", "--min-r2", "0")
+    assert one.returncode == 0 and one.stdout == b.stdout, one.stderr

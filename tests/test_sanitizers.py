@@ -13,8 +13,10 @@ import pytest
 import pgen_oracle as oracle
 from helpers import GOLDEN, basic1_known
 
+from pgen_rs_amd import build as host_build
+
 REPO = Path(__file__).resolve().parent.parent
-HOST = REPO / "pgen_rs_amd" / "host"
+HOST_SOURCES = [str(host_build.HOST_DIR / f) for f in host_build.HOST_SOURCES]   # what the pgen-hip binary is built from
 
 
 def test_oracle_selftest_under_asan_ubsan():
@@ -28,7 +30,7 @@ def asan_cli(tmp_path_factory):
     d = tmp_path_factory.mktemp("asan")
     exe = d / "pgen-hip-asan"
     cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-pthread",
-           "-I", str(REPO / "include"), "-o", str(exe), *[str(HOST / f) for f in ("cli.cpp", "pfile.cpp", "csvlite.cpp", "expr.cpp", "bgzf.cpp")],
+           "-I", str(REPO / "include"), "-o", str(exe), *HOST_SOURCES,
            "-L", str(REPO / "pgen_rs_amd"), "-lpgen_hip", "-lz", f"-Wl,-rpath,{REPO / 'pgen_rs_amd'}"]
     p = subprocess.run(cmd, capture_output=True, text=True)
     assert p.returncode == 0, p.stderr
@@ -74,7 +76,7 @@ def test_parallel_metadata_filter_under_asan_and_tsan(asan_cli, tmp_path):
 
     tsan = tmp_path / "pgen-hip-tsan"
     cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=thread", "-pthread", "-I", str(REPO / "include"), "-o", str(tsan),
-           *[str(HOST / f) for f in ("cli.cpp", "pfile.cpp", "csvlite.cpp", "expr.cpp", "bgzf.cpp")],
+           *HOST_SOURCES,
            "-L", str(REPO / "pgen_rs_amd"), "-lpgen_hip", "-lz", f"-Wl,-rpath,{REPO / 'pgen_rs_amd'}"]
     p = subprocess.run(cmd, capture_output=True, text=True)
     assert p.returncode == 0, p.stderr
