@@ -12,6 +12,7 @@
 
 #include "host_pure.h"
 #include "kernels.h"
+#include "launch_plan.h"
 
 using namespace pgenhip;
 
@@ -603,7 +604,7 @@ static int genotype_counts_core(pgenhip_ctx *ctx, const void *d_records, uint64_
     a.kept_mask = ctx->d_count_mask;   // NULL with all samples kept or an identity list
     a.counts = d_counts;
     // AUTO: a wave per row once a row spans more chunks than 32 lanes take in three passes (N > 6 084), else several rows per wave
-    const bool wave_per_row = flags == PGENHIP_COUNT_WAVE_PER_ROW || (flags == PGENHIP_COUNT_AUTO && gt_count_lanes_per_row(ctx->record_size) == 64u);
+    const bool wave_per_row = plan::count::wave_per_row(flags == PGENHIP_COUNT_WAVE_PER_ROW, flags == PGENHIP_COUNT_ROWS_PER_WAVE, ctx->record_size);
     HIP_TRY(launch_gt_count(a, wave_per_row, ctx->num_cus, ctx->stream));
     return PGENHIP_OK;
 }
@@ -751,7 +752,7 @@ static int variant_sums_core(pgenhip_ctx *ctx, const void *d_records, uint64_t r
     if (shape == PGENHIP_VSUM_GENERAL) {
         HIP_TRY(launch_gt_vsum_general(a, ctx->tune.vsum_blocks, ctx->num_cus, ctx->stream));
     } else {   // AUTO: the matrix-core shape wherever it applies (K >= 1)
-        if (gt_vsum_mfma_atomic(a)) HIP_TRY(hipMemsetAsync(d_sums, 0, out_bytes, ctx->stream));   // tiles of a row meet in atomics: the kernel only adds
+        if (plan::vsum::mfma_atomic(a.record_size)) HIP_TRY(hipMemsetAsync(d_sums, 0, out_bytes, ctx->stream));   // tiles of a row meet in atomics: the kernel only adds
         HIP_TRY(launch_gt_vsum_mfma(a, ctx->tune.vsum_blocks, ctx->num_cus, ctx->stream));
     }
     return PGENHIP_OK;
@@ -816,12 +817,18 @@ static int decode_matrix_core(pgenhip_ctx *ctx, const void *d_records, uint64_t 
         }
         a.tab[c] = v;
     }
-    if (shape == PGENHIP_MATRIX_TILE && !gt_matrix_tile_applicable(a))
+    // (the kernels' notion of "all samples kept": no list, K == N)
+    const bool no_list = a.kept_idx == nullptr && a.kept_count == a.sample_count;
+    const uint32_t out_align = (uint32_t)((uintptr_t)a.out & 15u);
+    if (shape == PGENHIP_MATRIX_TILE && !plan::matrix::tile_applicable(no_list, sample_major, out_align, out_stride, K))
         return fail(PGENHIP_ERR_BAD_ARG, "PGENHIP_MATRIX_TILE needs d_out and out_stride to be multiples of 16 bytes");
     const int blocks = ctx->tune.matrix_blocks;
-    if (shape == PGENHIP_MATRIX_STREAM || (shape == PGENHIP_MATRIX_AUTO && gt_matrix_stream_applicable(a)))
+    static_assert(plan::matrix::kGeneral == PGENHIP_MATRIX_GENERAL && plan::matrix::kStream == PGENHIP_MATRIX_STREAM && plan::matrix::kTile == PGENHIP_MATRIX_TILE,
+                  "plan::matrix::Shape carries the ABI's values");
+    const uint32_t run = shape != PGENHIP_MATRIX_AUTO ? shape : plan::matrix::auto_shape(no_list, sample_major, out_align, out_stride, K);
+    if (run == PGENHIP_MATRIX_STREAM)
         HIP_TRY(launch_gt_matrix_stream(a, blocks, ctx->num_cus, ctx->stream));
-    else if (shape == PGENHIP_MATRIX_TILE || (shape == PGENHIP_MATRIX_AUTO && gt_matrix_tile_applicable(a)))
+    else if (run == PGENHIP_MATRIX_TILE)
         HIP_TRY(launch_gt_matrix_tile(a, blocks, ctx->num_cus, ctx->stream));
     else
         HIP_TRY(launch_gt_matrix_general(a, blocks, ctx->num_cus, ctx->stream));
@@ -974,7 +981,9 @@ static int sample_gram_core(pgenhip_ctx *ctx, const void *d_records, uint64_t re
     a.out_stride = a_count > 1u ? out_stride : b_count;
     // AUTO: the matrix-core shape
     const bool mfma = shape != PGENHIP_GRAM_GENERAL;
-    const uint32_t slices = gt_gram_slices(a, mfma, ctx->tune.gram_slices, ctx->num_cus);
+    const uint32_t slices = n_variants == 0u ? 1u   // (nothing is launched)
+                            : mfma ? plan::gram::mfma_slices(n_variants, a_count, b_count, ctx->tune.gram_slices, ctx->num_cus)
+                                   : plan::gram::general_slices(n_variants, a_count, b_count, ctx->tune.gram_slices, ctx->num_cus);
     // one slice that overwrites: every entry has one owner and is stored.  Else the kernels only add, to zeros or to what is there
     a.store = (!accumulate && n_variants != 0u && slices == 1u) ? 1u : 0u;
     if (!accumulate && !a.store)
@@ -1039,9 +1048,9 @@ static int pack_records_core(pgenhip_ctx *ctx, const void *d_records, uint64_t r
     a.map8 = map8;
     const int blocks = ctx->tune.pack_blocks;
     a.kept_idx = all_kept ? nullptr : ctx->d_kept;
-    if (flags == PGENHIP_PACK_DENSE || (flags == PGENHIP_PACK_AUTO && gt_pack_dense_applicable(a))) {
+    if (flags == PGENHIP_PACK_DENSE || (flags == PGENHIP_PACK_AUTO && plan::pack::dense_applicable(a.kept_idx != nullptr, K, a.sample_count))) {
         HIP_TRY(launch_gt_pack_dense(a, blocks, ctx->num_cus, ctx->stream));
-    } else if (flags == PGENHIP_PACK_GATHER || (flags == PGENHIP_PACK_AUTO && gt_pack_gather_applicable(a))) {
+    } else if (flags == PGENHIP_PACK_GATHER || (flags == PGENHIP_PACK_AUTO && plan::pack::gather_applicable(a.kept_idx != nullptr, K))) {
         a.kept_idx = ctx->d_kept;   // forced on an identity list: the list is there
         HIP_TRY(launch_gt_pack_gather(a, blocks, ctx->num_cus, ctx->stream));
     } else {

@@ -78,6 +78,20 @@ __device__ __forceinline__ const uint8_t *row_record(const RowSource &a, uint64_
                                       : a.records + r * a.record_stride;
 }
 
+// Rank of sample s in the kept list (s itself without a mask); kept says whether it is in it.  kept_mask is the ctx's count mask
+// (2 bits per sample, 0b01 = kept, laid out like a record behind 16 zero bytes), kept_rank the kept samples before each 64-sample chunk.
+__device__ __forceinline__ uint32_t kept_rank_of(const uint8_t *kept_mask, const uint32_t *kept_rank, uint32_t s, bool &kept)
+{
+    kept = true;
+    if (kept_mask == nullptr) return s;
+    const uint32_t *mw = reinterpret_cast<const uint32_t *>(kept_mask + 16u + 16u * (s >> 6));
+    const uint32_t j = (s >> 4) & 3u, bit = 2u * (s & 15u);
+    kept = ((mw[j] >> bit) & 1u) != 0u;
+    uint32_t k = kept_rank[s >> 6] + __builtin_popcount(mw[j] & ((1u << bit) - 1u));
+    for (uint32_t i = 0; i < j; i++) k += __builtin_popcount(mw[i]);
+    return k;
+}
+
 // ---- all-samples text from a 16-bit record window ---------------------------------------------
 // 16 bytes of one row's GT text starting at segment offset q (q >= -15) cover samples
 // k0 = floor(q/4) .. k0+4 = 10 bits at bit 2*k0 of the record = record bytes b0 = floor(q/16)

@@ -18,13 +18,13 @@
 // Every row's counts are written by one lane: no atomics, no hand-off between blocks, no scratch.
 #include "gt_common.hip.h"
 #include "kernels.h"
+#include "launch_plan.h"
 
 namespace pgenhip {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr uint32_t kBlocksPerCu = 8;   // 32 waves per CU: up to 128 KiB of record loads in flight per CU on long rows
+using namespace plan::count;   // kThreads, kBlocksPerCu and the launch plan
 
 // bits [0, 2n) of a word, n in [0, 16]
 __device__ __forceinline__ uint32_t low_sample_bits(int32_t n) { return n >= 16 ? 0xFFFFFFFFu : ((1u << (2 * n)) - 1u); }
@@ -59,12 +59,12 @@ template <int G, int RU, int U, bool MASK>
 __global__ __launch_bounds__(kThreads) void gt_count_kernel(CountArgs a)
 {
     constexpr uint32_t kGroups = 64u / G;                 // rows side by side in a wave
-    constexpr uint32_t kRowsPerStep = kGroups * RU;
+    constexpr uint32_t kRowsPerStep = rows_per_step(G, RU);
     const uint32_t lane = threadIdx.x & 63u, gl = lane & (uint32_t)(G - 1), grp = lane / (uint32_t)G;
     const uint64_t wave = ((uint64_t)blockIdx.x * kThreads + threadIdx.x) >> 6;
     const uint64_t n_waves = ((uint64_t)gridDim.x * kThreads) >> 6;
     const uint32_t R = a.record_size;
-    const uint32_t passes = ((R + 30u) / 16u + (uint32_t)(G * U) - 1u) / (uint32_t)(G * U);   // over the most chunks a row can span
+    const uint32_t n_passes = passes(R, G, U);   // over the most chunks a row can span
 
     for (uint64_t r0 = wave * kRowsPerStep; r0 < a.n_variants; r0 += n_waves * kRowsPerStep) {
         const uint8_t *base[RU];
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(kThreads) void gt_count_kernel(CountArgs a)
             base[k] = rec - d[k];   // (pointer arithmetic on the argument keeps the loads global, not flat)
             nch[k] = live && R ? (d[k] + R + 15u) >> 4 : 0u;   // aligned 16-byte chunks the row's bytes touch
         }
-        for (uint32_t t = 0; t < passes; t++) {
+        for (uint32_t t = 0; t < n_passes; t++) {
             gt_v4u w[RU][U], m[RU][U];
 #pragma unroll
             for (int k = 0; k < RU; k++)
@@ -143,10 +143,8 @@ __global__ __launch_bounds__(kThreads) void gt_count_kernel(CountArgs a)
 template <int G, int RU, int U>
 hipError_t launch_shape(const CountArgs &a, int num_cus, hipStream_t stream)
 {
-    const uint64_t rows_per_block = (uint64_t)(kThreads / 64) * (64u / G) * RU;
-    const uint64_t blocks = (a.n_variants + rows_per_block - 1) / rows_per_block;
-    const uint64_t cap = (uint64_t)(num_cus > 0 ? num_cus : 256) * kBlocksPerCu;
-    const uint32_t grid = (uint32_t)(blocks < cap ? blocks : cap);
+    static_assert(shape(0u, G == 64).RU == (uint32_t)RU && shape(0u, G == 64).U == (uint32_t)U, "an instantiation that plan::count::shape names");
+    const uint32_t grid = plan::count::grid(a.n_variants, G, RU, num_cus);
     if (a.kept_mask != nullptr)
         hipLaunchKernelGGL((gt_count_kernel<G, RU, U, true>), dim3(grid), dim3(kThreads), 0, stream, a);
     else
@@ -156,21 +154,15 @@ hipError_t launch_shape(const CountArgs &a, int num_cus, hipStream_t stream)
 
 }  // namespace
 
-uint32_t gt_count_lanes_per_row(uint32_t record_size)
-{
-    const uint32_t chunks = (record_size + 30u) / 16u;   // the most aligned 16-byte chunks a row of R bytes can touch
-    return chunks <= 12u ? 4u : chunks <= 24u ? 8u : chunks <= 48u ? 16u : chunks <= 96u ? 32u : 64u;
-}
-
 hipError_t launch_gt_count(const CountArgs &a, bool wave_per_row, int num_cus, hipStream_t stream)
 {
     if (a.n_variants == 0) return hipSuccess;
-    if (wave_per_row) return launch_shape<64, 1, 4>(a, num_cus, stream);
-    switch (gt_count_lanes_per_row(a.record_size)) {
+    switch (shape(a.record_size, wave_per_row).G) {   // (RU, U) as plan::count::shape says: 1, 4 at a wave per row, else 2, 1
+        case 64u: return launch_shape<64, 1, 4>(a, num_cus, stream);
         case 4u: return launch_shape<4, 2, 1>(a, num_cus, stream);
         case 8u: return launch_shape<8, 2, 1>(a, num_cus, stream);
         case 16u: return launch_shape<16, 2, 1>(a, num_cus, stream);
-        default: return launch_shape<32, 2, 1>(a, num_cus, stream);   // (forced on long rows: more passes per row)
+        default: return launch_shape<32, 2, 1>(a, num_cus, stream);
     }
 }
 

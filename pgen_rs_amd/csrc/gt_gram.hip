@@ -29,20 +29,15 @@
 // ones with global_atomic_add_f64 (the target holds +0.0 or a sum, so a skipped -0.0 cannot matter).
 #include "gt_common.hip.h"
 #include "kernels.h"
+#include "launch_plan.h"
 
 namespace pgenhip {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr uint32_t kTile = 64;             // ranks of a block tile, per operand
-constexpr uint32_t kStepRows = 32;         // rows expanded per step: eight MFMA row groups
-constexpr uint32_t kGroupRows = 4;         // rows of one MFMA (the instruction's k)
+using namespace plan::gram;                // kThreads, kTile, kStepRows, kGroupRows, the grid caps and the launch plan
 constexpr uint32_t kRowStride = 80;        // doubles between rows of the LDS image (64 ranks + 16: the four rows of a ds_read_b64 on different banks)
 constexpr uint32_t kOperandDoubles = kStepRows * kRowStride;
-constexpr uint32_t kMaxGridTiles = 1u << 20;   // tiles (pair blocks) side by side in the grid; a block strides over the rest
-constexpr uint32_t kMaxGridBlocks = 1u << 22;
-constexpr uint32_t kMinSliceRows = 256;    // rows a slice takes at least when the plan is not forced
 
 typedef double gram_v4d __attribute__((ext_vector_type(4)));
 typedef double gram_v2d __attribute__((ext_vector_type(2)));
@@ -65,7 +60,8 @@ __global__ __launch_bounds__(kThreads) void gt_gram_general_kernel(GramArgs a, u
 {
     const uint32_t slice = blockIdx.x / grid_pairs;
     const uint64_t V = a.n_variants;
-    const uint64_t rbeg = V * slice / slices, rend = V * (slice + 1u) / slices;
+    const plan::RowRange rows = plan::slice_rows(V, slice, slices);
+    const uint64_t rbeg = rows.begin, rend = rows.end;
     for (uint64_t pb = blockIdx.x % grid_pairs; pb < pair_blocks; pb += grid_pairs) {
         const uint64_t p = pb * kThreads + threadIdx.x;
         if (p >= pairs) break;
@@ -97,7 +93,8 @@ __global__ __launch_bounds__(kThreads, 2) void gt_gram_mfma_kernel(GramArgs a, u
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t slice = blockIdx.x / grid_tiles;
     const uint64_t V = a.n_variants;
-    const uint64_t rbeg = V * slice / slices, rend = V * (slice + 1u) / slices;   // never empty (launch plan)
+    const plan::RowRange rows = plan::slice_rows(V, slice, slices);   // never empty (launch plan)
+    const uint64_t rbeg = rows.begin, rend = rows.end;
     const uint64_t steps = (rend - rbeg + kStepRows - 1u) / kStepRows;
     // staging role: operand, row of the step, quarter of the tile's ranks
     const uint32_t op = tid >> 7, sr = (tid >> 2) & 31u, q = tid & 3u;
@@ -209,35 +206,6 @@ __global__ __launch_bounds__(kThreads, 2) void gt_gram_mfma_kernel(GramArgs a, u
     }
 }
 
-// row ranges of a launch: forced, or as many as bring the grid to `target` blocks, of at least kMinSliceRows rows each; never
-// more than there are units of `unit_rows` rows, and the grid stays below kMaxGridBlocks
-uint32_t plan_slices(uint32_t n_variants, uint64_t grid_items, int forced, int num_cus, uint32_t blocks_per_cu, uint32_t unit_rows)
-{
-    const uint64_t target = (uint64_t)(num_cus > 0 ? num_cus : 256) * blocks_per_cu;
-    uint64_t s;
-    if (forced > 0) {
-        s = (uint64_t)forced;
-    } else {
-        s = std::max<uint64_t>(1u, target / grid_items);
-        s = std::min<uint64_t>(s, std::max<uint64_t>(1u, n_variants / kMinSliceRows));
-    }
-    s = std::min<uint64_t>(s, ((uint64_t)n_variants + unit_rows - 1u) / unit_rows);
-    s = std::min<uint64_t>(s, kMaxGridBlocks / grid_items);
-    return (uint32_t)std::max<uint64_t>(s, 1u);
-}
-
-uint32_t general_grid_pairs(const GramArgs &a)
-{
-    const uint64_t pairs = (uint64_t)a.a_count * a.b_count;
-    return (uint32_t)std::min<uint64_t>((pairs + kThreads - 1u) / kThreads, kMaxGridTiles);
-}
-
-uint32_t mfma_grid_tiles(const GramArgs &a)
-{
-    const uint64_t tiles = (uint64_t)((a.a_count + kTile - 1u) / kTile) * ((a.b_count + kTile - 1u) / kTile);
-    return (uint32_t)std::min<uint64_t>(tiles, kMaxGridTiles);
-}
-
 template <int MODE>
 void launch_mfma(const GramArgs &a, dim3 grid, uint32_t tiles_b, uint64_t tiles, uint32_t grid_tiles, uint32_t slices, hipStream_t stream)
 {
@@ -249,28 +217,21 @@ void launch_mfma(const GramArgs &a, dim3 grid, uint32_t tiles_b, uint64_t tiles,
 
 }  // namespace
 
-uint32_t gt_gram_slices(const GramArgs &a, bool mfma, int slices_per_tile, int num_cus)
-{
-    if (a.n_variants == 0 || a.a_count == 0 || a.b_count == 0) return 1u;
-    return mfma ? plan_slices(a.n_variants, mfma_grid_tiles(a), slices_per_tile, num_cus, 2u, kStepRows)
-                : plan_slices(a.n_variants, general_grid_pairs(a), slices_per_tile, num_cus, 8u, 1u);
-}
-
 hipError_t launch_gt_gram_general(const GramArgs &a, uint32_t slices, hipStream_t stream)
 {
     if (a.n_variants == 0 || a.a_count == 0 || a.b_count == 0) return hipSuccess;
-    const uint64_t pairs = (uint64_t)a.a_count * a.b_count, pair_blocks = (pairs + kThreads - 1u) / kThreads;
-    const uint32_t grid_pairs = general_grid_pairs(a);
-    hipLaunchKernelGGL(gt_gram_general_kernel, dim3(grid_pairs * slices), dim3(kThreads), 0, stream, a, pairs, pair_blocks, grid_pairs, slices);
+    const uint64_t pairs = (uint64_t)a.a_count * a.b_count;
+    const uint32_t grid_pairs = plan::gram::grid_pairs(a.a_count, a.b_count);
+    hipLaunchKernelGGL(gt_gram_general_kernel, dim3(grid_pairs * slices), dim3(kThreads), 0, stream, a, pairs, pair_blocks(a.a_count, a.b_count), grid_pairs, slices);
     return hipGetLastError();
 }
 
 hipError_t launch_gt_gram_mfma(const GramArgs &a, uint32_t slices, hipStream_t stream)
 {
     if (a.n_variants == 0 || a.a_count == 0 || a.b_count == 0) return hipSuccess;
-    const uint32_t tiles_a = (a.a_count + kTile - 1u) / kTile, tiles_b = (a.b_count + kTile - 1u) / kTile;
-    const uint64_t tiles = (uint64_t)tiles_a * tiles_b;
-    const uint32_t grid_tiles = mfma_grid_tiles(a);
+    const uint32_t tiles_b = range_tiles(a.b_count);
+    const uint64_t tiles = plan::gram::tiles(a.a_count, a.b_count);
+    const uint32_t grid_tiles = plan::gram::grid_tiles(a.a_count, a.b_count);
     const dim3 grid(grid_tiles * slices);
     if (a.record_off != nullptr)
         launch_mfma<2>(a, grid, tiles_b, tiles, grid_tiles, slices, stream);

@@ -33,18 +33,13 @@
 //            band has rows, not on all K rows at once.  Ragged edges (V, N not multiples of the tile) write element by element.
 #include "gt_common.hip.h"
 #include "kernels.h"
+#include "launch_plan.h"
 
 namespace pgenhip {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr uint32_t kBlocksPerCu = 8;         // grid cap of the grid-stride kernels
-constexpr uint32_t kLongRowBytes = 4096;     // STREAM: output rows from this size take the division-free rows kernel
-constexpr uint32_t kTileVariants = 128;      // TILE: rows of a block's tile (16 per lane x 8 lanes)
-constexpr uint32_t kWaveSamples = 128;       // TILE: samples of one wave (16 per lane x 8 lanes)
-constexpr uint32_t kTileSamples = 512;       // TILE: samples of a block's tile = 128 record bytes, one line per row
-constexpr uint32_t kTileBlocksPerCu = 4;     // TILE: grid cap (16 KiB of LDS per block)
+using namespace plan::matrix;   // kThreads, kLongRowBytes, kTileVariants, kWaveSamples, kTileSamples, ... and the launch plans
 
 // the four patterns as the lookup registers of one element size
 template <int E>
@@ -359,30 +354,13 @@ __global__ __launch_bounds__(kThreads) void gt_matrix_tile_kernel(MatrixArgs a, 
     }
 }
 
-uint32_t grid_blocks(uint64_t blocks, uint32_t per_cu, int num_cus, int forced)
-{
-    const uint64_t cap = forced > 0 ? (uint64_t)forced : (uint64_t)(num_cus > 0 ? num_cus : 256) * per_cu;
-    return (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(blocks, cap));
-}
-
 }  // namespace
-
-bool gt_matrix_stream_applicable(const MatrixArgs &a)
-{
-    return a.kept_idx == nullptr && a.kept_count == a.sample_count && !a.sample_major;
-}
-
-bool gt_matrix_tile_applicable(const MatrixArgs &a)
-{
-    return a.kept_idx == nullptr && a.kept_count == a.sample_count && a.sample_major && ((uintptr_t)a.out & 15u) == 0u &&
-           (a.out_stride % 16u == 0u || a.kept_count <= 1u);
-}
 
 hipError_t launch_gt_matrix_general(const MatrixArgs &a, int blocks, int num_cus, hipStream_t stream)
 {
     if (a.n_variants == 0 || a.kept_count == 0) return hipSuccess;
     const uint64_t total = (uint64_t)a.n_variants * a.kept_count;
-    const dim3 grid(grid_blocks((total + kThreads - 1u) / kThreads, kBlocksPerCu, num_cus, blocks)), block(kThreads);
+    const dim3 grid(general_grid(a.n_variants, a.kept_count, num_cus, blocks)), block(kThreads);
     switch (a.elem_bytes) {
         case 1u: hipLaunchKernelGGL(gt_matrix_general_kernel<1>, grid, block, 0, stream, a, total); break;
         case 2u: hipLaunchKernelGGL(gt_matrix_general_kernel<2>, grid, block, 0, stream, a, total); break;
@@ -394,28 +372,21 @@ hipError_t launch_gt_matrix_general(const MatrixArgs &a, int blocks, int num_cus
 hipError_t launch_gt_matrix_stream(const MatrixArgs &a, int blocks, int num_cus, hipStream_t stream)
 {
     if (a.n_variants == 0 || a.kept_count == 0) return hipSuccess;
-    const uint64_t row_bytes = (uint64_t)a.kept_count * a.elem_bytes;
-    const bool dense = a.n_variants == 1u || a.out_stride == row_bytes;
-    const uint64_t per_row = (row_bytes + 15u) / 16u + 1u;   // aligned chunks a row can touch at any phase
-    const uint64_t total = dense ? (((uintptr_t)a.out & 15u) + row_bytes * a.n_variants + 15u) / 16u : per_row * a.n_variants;
-    const double inv = 1.0 / (double)(dense ? (uint64_t)a.kept_count : per_row);
-    const dim3 block(kThreads);
-    if (row_bytes >= kLongRowBytes) {
-        const uint32_t gx = grid_blocks((per_row + kThreads - 1u) / kThreads, kBlocksPerCu, num_cus, blocks > 0 ? 1 : 0);
-        const uint32_t gy = (uint32_t)std::min<uint64_t>(a.n_variants, std::max<uint32_t>(1u, grid_blocks(~0ull, kBlocksPerCu, num_cus, blocks) / gx));
-        const dim3 grid(gx, std::min<uint32_t>(gy, 65535u));
+    const StreamPlan p = stream_plan(a.n_variants, a.kept_count, a.elem_bytes, (uint32_t)((uintptr_t)a.out & 15u), a.out_stride, num_cus, blocks);
+    const dim3 grid(p.grid_x, p.grid_y), block(kThreads);
+    if (p.long_rows) {
         switch (a.elem_bytes) {
-            case 1u: hipLaunchKernelGGL(gt_matrix_stream_rows_kernel<1>, grid, block, 0, stream, a, (uint32_t)per_row); break;
-            case 2u: hipLaunchKernelGGL(gt_matrix_stream_rows_kernel<2>, grid, block, 0, stream, a, (uint32_t)per_row); break;
-            default: hipLaunchKernelGGL(gt_matrix_stream_rows_kernel<4>, grid, block, 0, stream, a, (uint32_t)per_row); break;
+            case 1u: hipLaunchKernelGGL(gt_matrix_stream_rows_kernel<1>, grid, block, 0, stream, a, (uint32_t)p.per_row); break;
+            case 2u: hipLaunchKernelGGL(gt_matrix_stream_rows_kernel<2>, grid, block, 0, stream, a, (uint32_t)p.per_row); break;
+            default: hipLaunchKernelGGL(gt_matrix_stream_rows_kernel<4>, grid, block, 0, stream, a, (uint32_t)p.per_row); break;
         }
         return hipGetLastError();
     }
-    const dim3 grid(grid_blocks((total + kThreads - 1u) / kThreads, kBlocksPerCu, num_cus, blocks));
+    const double inv = 1.0 / (double)(p.dense ? (uint64_t)a.kept_count : p.per_row);   // the kernel divides through a reciprocal
     switch (a.elem_bytes) {
-        case 1u: hipLaunchKernelGGL(gt_matrix_stream_kernel<1>, grid, block, 0, stream, a, dense, per_row, total, inv); break;
-        case 2u: hipLaunchKernelGGL(gt_matrix_stream_kernel<2>, grid, block, 0, stream, a, dense, per_row, total, inv); break;
-        default: hipLaunchKernelGGL(gt_matrix_stream_kernel<4>, grid, block, 0, stream, a, dense, per_row, total, inv); break;
+        case 1u: hipLaunchKernelGGL(gt_matrix_stream_kernel<1>, grid, block, 0, stream, a, p.dense, p.per_row, p.total, inv); break;
+        case 2u: hipLaunchKernelGGL(gt_matrix_stream_kernel<2>, grid, block, 0, stream, a, p.dense, p.per_row, p.total, inv); break;
+        default: hipLaunchKernelGGL(gt_matrix_stream_kernel<4>, grid, block, 0, stream, a, p.dense, p.per_row, p.total, inv); break;
     }
     return hipGetLastError();
 }
@@ -423,14 +394,12 @@ hipError_t launch_gt_matrix_stream(const MatrixArgs &a, int blocks, int num_cus,
 hipError_t launch_gt_matrix_tile(const MatrixArgs &a, int blocks, int num_cus, hipStream_t stream)
 {
     if (a.n_variants == 0 || a.kept_count == 0) return hipSuccess;
-    const uint64_t v_tiles = ((uint64_t)a.n_variants + kTileVariants - 1u) / kTileVariants;
-    const uint64_t bands = ((uint64_t)a.sample_count + kTileSamples - 1u) / kTileSamples;
-    const uint64_t total = v_tiles * bands;
-    const dim3 grid(grid_blocks(total, kTileBlocksPerCu, num_cus, blocks)), block(kThreads);
+    const TilePlan p = tile_plan(a.n_variants, a.sample_count, num_cus, blocks);
+    const dim3 grid(p.grid), block(kThreads);
     switch (a.elem_bytes) {
-        case 1u: hipLaunchKernelGGL(gt_matrix_tile_kernel<1>, grid, block, 0, stream, a, v_tiles, total); break;
-        case 2u: hipLaunchKernelGGL(gt_matrix_tile_kernel<2>, grid, block, 0, stream, a, v_tiles, total); break;
-        default: hipLaunchKernelGGL(gt_matrix_tile_kernel<4>, grid, block, 0, stream, a, v_tiles, total); break;
+        case 1u: hipLaunchKernelGGL(gt_matrix_tile_kernel<1>, grid, block, 0, stream, a, p.v_tiles, p.total); break;
+        case 2u: hipLaunchKernelGGL(gt_matrix_tile_kernel<2>, grid, block, 0, stream, a, p.v_tiles, p.total); break;
+        default: hipLaunchKernelGGL(gt_matrix_tile_kernel<4>, grid, block, 0, stream, a, p.v_tiles, p.total); break;
     }
     return hipGetLastError();
 }

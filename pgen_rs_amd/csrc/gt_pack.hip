@@ -29,16 +29,14 @@
 // Every output byte has one owner: no atomics, no scratch, no work counters.
 #include "gt_common.hip.h"
 #include "kernels.h"
+#include "launch_plan.h"
 
 namespace pgenhip {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr uint32_t kBlocksPerCu = 8;       // grid cap of the grid-stride kernels
+using namespace plan::pack;   // kThreads, kBlocksPerCu, kPartChunks, kStreamRunBytes and the launch plans
 constexpr uint32_t kEven = 0x55555555u;
-constexpr uint32_t kPartChunks = 256u;     // DENSE, wave per row: chunks of one part (4 passes of 64 lanes)
-constexpr uint32_t kStreamRunBytes = 65536u;   // DENSE, dense rows as one stream: bytes of a run of rows (16 parts)
 
 // the map as plane masks: lo[c] / hi[c] = 0x55555555 where map[c] has bit 0 / bit 1
 struct PlaneMap {
@@ -215,51 +213,39 @@ __global__ __launch_bounds__(kThreads) void gt_pack_gather_kernel(PackArgs a, ui
     }
 }
 
-uint32_t grid_blocks(uint64_t blocks, int num_cus, int forced)
-{
-    const uint64_t cap = forced > 0 ? (uint64_t)forced : (uint64_t)(num_cus > 0 ? num_cus : 256) * kBlocksPerCu;
-    return (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(blocks, cap));
-}
-
 template <int G, int P>
-hipError_t launch_dense(const PackArgs &a, int blocks, int num_cus, hipStream_t stream)
+hipError_t launch_dense(const PackArgs &a, const DensePlan &p, hipStream_t stream)
 {
-    const uint32_t chunks = (a.record_size + 30u) / 16u;   // the most aligned chunks a destination row can touch
-    const uint32_t parts = (chunks + (uint32_t)(G * P) - 1u) / (uint32_t)(G * P);
-    const uint64_t row_groups = ((uint64_t)a.n_variants + 64u / G - 1u) / (64u / G);
-    const uint64_t items = row_groups * parts;
-    const dim3 grid(grid_blocks((items + kThreads / 64 - 1u) / (kThreads / 64), num_cus, blocks)), block(kThreads);
+    const dim3 grid(p.grid), block(kThreads);
     if (a.map8 != kPackIdentityMap)
-        hipLaunchKernelGGL((gt_pack_dense_kernel<G, P, true>), grid, block, 0, stream, a, parts, items);
+        hipLaunchKernelGGL((gt_pack_dense_kernel<G, P, true>), grid, block, 0, stream, a, p.parts, p.items);
     else
-        hipLaunchKernelGGL((gt_pack_dense_kernel<G, P, false>), grid, block, 0, stream, a, parts, items);
+        hipLaunchKernelGGL((gt_pack_dense_kernel<G, P, false>), grid, block, 0, stream, a, p.parts, p.items);
     return hipGetLastError();
 }
 
 }  // namespace
 
-bool gt_pack_dense_applicable(const PackArgs &a) { return a.kept_idx == nullptr && a.kept_count == a.sample_count; }
-
-bool gt_pack_gather_applicable(const PackArgs &a) { return a.kept_idx != nullptr && a.kept_count >= 1u; }
-
 hipError_t launch_gt_pack_general(const PackArgs &a, int blocks, int num_cus, hipStream_t stream)
 {
     if (a.n_variants == 0 || a.kept_count == 0) return hipSuccess;
     const uint64_t total = (uint64_t)a.n_variants * ((a.kept_count + 3u) >> 2);
-    const dim3 grid(grid_blocks((total + kThreads - 1u) / kThreads, num_cus, blocks)), block(kThreads);
+    const dim3 grid(general_grid(a.n_variants, a.kept_count, num_cus, blocks)), block(kThreads);
     hipLaunchKernelGGL(gt_pack_general_kernel, grid, block, 0, stream, a, total);
     return hipGetLastError();
 }
 
-// lanes per row: as many as three passes over the row's chunks need; from 97 chunks a wave per row, cut into parts
+// (G, P) as plan::pack::dense_plan says: three passes of 4 .. 32 lanes per row, from 97 chunks a wave per row, cut into parts
 static hipError_t launch_dense_rows(const PackArgs &a, int blocks, int num_cus, hipStream_t stream)
 {
-    const uint32_t chunks = (a.record_size + 30u) / 16u;
-    if (chunks <= 12u) return launch_dense<4, 3>(a, blocks, num_cus, stream);
-    if (chunks <= 24u) return launch_dense<8, 3>(a, blocks, num_cus, stream);
-    if (chunks <= 48u) return launch_dense<16, 3>(a, blocks, num_cus, stream);
-    if (chunks <= 96u) return launch_dense<32, 3>(a, blocks, num_cus, stream);
-    return launch_dense<64, (int)(kPartChunks / 64u)>(a, blocks, num_cus, stream);
+    const DensePlan p = dense_plan(a.record_size, a.n_variants, num_cus, blocks);
+    switch (p.G) {
+        case 4u: return launch_dense<4, 3>(a, p, stream);
+        case 8u: return launch_dense<8, 3>(a, p, stream);
+        case 16u: return launch_dense<16, 3>(a, p, stream);
+        case 32u: return launch_dense<32, 3>(a, p, stream);
+        default: return launch_dense<64, (int)(kPartChunks / 64u)>(a, p, stream);
+    }
 }
 
 hipError_t launch_gt_pack_dense(const PackArgs &a, int blocks, int num_cus, hipStream_t stream)
@@ -268,8 +254,8 @@ hipError_t launch_gt_pack_dense(const PackArgs &a, int blocks, int num_cus, hipS
     // Dense records into dense output with no pad bits (N a multiple of 4) are one byte stream: runs of m rows go as ONE row of
     // m * R bytes (no heads and tails at every record, no idle lanes on 75-byte rows), the rows behind the last whole run row by row
     const uint32_t R = a.record_size;
-    const uint64_t m = kStreamRunBytes / R;
-    if (!gathered(a) && (a.sample_count & 3u) == 0u && a.record_stride == R && a.out_stride == R && m >= 2u && a.n_variants >= 2u * m) {
+    if (merge_runs(gathered(a), a.sample_count, R, a.record_stride, a.out_stride, a.n_variants)) {
+        const uint64_t m = run_rows(R);
         PackArgs run = a, rest = a;
         run.n_variants = (uint32_t)(a.n_variants / m);
         run.record_size = (uint32_t)(m * R);
@@ -290,13 +276,12 @@ hipError_t launch_gt_pack_dense(const PackArgs &a, int blocks, int num_cus, hipS
 hipError_t launch_gt_pack_gather(const PackArgs &a, int blocks, int num_cus, hipStream_t stream)
 {
     if (a.n_variants == 0 || a.kept_count == 0) return hipSuccess;
-    const uint32_t Q = (a.kept_count + 15u) >> 4;   // output dwords of a row
-    const uint64_t total = (uint64_t)a.n_variants * Q;
-    const dim3 grid(grid_blocks((total + kThreads - 1u) / kThreads, num_cus, blocks)), block(kThreads);
+    const GatherPlan p = gather_plan(a.n_variants, a.kept_count, num_cus, blocks);
+    const dim3 grid(p.grid), block(kThreads);
     if (a.map8 != kPackIdentityMap)
-        hipLaunchKernelGGL(gt_pack_gather_kernel<true>, grid, block, 0, stream, a, Q, total);
+        hipLaunchKernelGGL(gt_pack_gather_kernel<true>, grid, block, 0, stream, a, p.Q, p.total);
     else
-        hipLaunchKernelGGL(gt_pack_gather_kernel<false>, grid, block, 0, stream, a, Q, total);
+        hipLaunchKernelGGL(gt_pack_gather_kernel<false>, grid, block, 0, stream, a, p.Q, p.total);
     return hipGetLastError();
 }
 

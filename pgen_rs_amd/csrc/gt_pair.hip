@@ -29,18 +29,16 @@
 
 #include "gt_common.hip.h"
 #include "kernels.h"
+#include "launch_plan.h"
 
 namespace pgenhip {
 
 namespace {
 
-constexpr int kThreads = 64;                            // one wave per tile
-constexpr uint32_t kTile = 16;                          // TL = TR
-constexpr uint32_t kChunkWords = 16;                    // 32-sample words per staged chunk: 512 samples, 128 record bytes per row
+using namespace plan::pair;                             // kThreads (one wave per tile), kTile, kChunkWords, kBlocksPerCu and the launch plan
 constexpr uint32_t kPieces = kChunkWords / 2;           // 16-byte pieces of a row per chunk
 constexpr uint32_t kSlots = 2 * kTile;                  // row slots: 0-15 left, 16-31 right
 constexpr uint32_t kWordStride = 3 * kSlots + 4;        // dwords per staged word; 2 * 100 = 8 (mod 64): see the header comment
-constexpr uint32_t kBlocksPerCu = 16;
 
 static_assert(kThreads == 64 && kPieces == 8 && kSlots == 32, "lane <-> (piece, row slot) and (ty, tx) maps below");
 
@@ -242,14 +240,8 @@ hipError_t launch_gt_pair(const PairArgs &a, int blocks, int num_cus, hipStream_
 {
     const uint64_t V = a.n_variants;
     if (a.n_left == 0 || V <= 1) return hipSuccess;
-    const uint64_t w_eff = a.window < V - 1 ? a.window : V - 1;
-    const uint64_t left_tiles = ((uint64_t)a.n_left + kTile - 1u) / kTile, right_tiles = (V + kTile - 1u) / kTile;
-    uint64_t tiles_per_left = (kTile - 1u + w_eff) / kTile + 1u;   // the right tiles rows i0 .. i0 + 15 reach with d <= W, the diagonal one included
-    if (tiles_per_left > right_tiles) tiles_per_left = right_tiles;
-    const uint64_t n_items = left_tiles * tiles_per_left;
-    const uint64_t cap = (uint64_t)(num_cus > 0 ? num_cus : 256) * kBlocksPerCu;
-    const uint32_t grid = blocks > 0 ? (uint32_t)blocks : (uint32_t)(n_items < cap ? n_items : cap);
-    hipLaunchKernelGGL(gt_pair_kernel, dim3(grid), dim3(kThreads), 0, stream, a, n_items, tiles_per_left);
+    const plan::pair::Plan p = plan::pair::plan(a.n_variants, a.n_left, a.window, num_cus, blocks);
+    hipLaunchKernelGGL(gt_pair_kernel, dim3(p.grid), dim3(kThreads), 0, stream, a, p.n_items, p.tiles_per_left);
     return hipGetLastError();
 }
 

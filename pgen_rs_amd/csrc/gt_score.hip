@@ -22,18 +22,13 @@
 // bytes that other lanes read anyway, add zeros and flush nothing.
 #include "gt_common.hip.h"
 #include "kernels.h"
+#include "launch_plan.h"
 
 namespace pgenhip {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr uint32_t kWaves = kThreads / 64;
-constexpr uint32_t kMaxBlocksPerCu = 4;
-constexpr uint32_t kMinSliceRows = 512;   // rows a slice takes at least when the plan is not forced: a block's flush is worth that many rows
-
-__host__ __device__ constexpr uint32_t lane_bytes(uint32_t columns) { return columns <= 2u ? 4u : columns <= 4u ? 2u : 1u; }
-__host__ __device__ constexpr uint32_t batch_rows(uint32_t columns) { return columns <= 4u ? 4u : 2u; }
+using namespace plan::score;   // kThreads, kWaves, lane_bytes, batch_rows, ... and the launch plan
 
 template <int C>
 struct Row {
@@ -54,14 +49,15 @@ __global__ __launch_bounds__(kThreads) void gt_score_kernel(ScoreArgs a, uint32_
     constexpr int S = 4 * BYTES;               // samples of a lane
     constexpr uint32_t B = batch_rows(C);
     __shared__ double table[64 * S * C];       // [S][C][G] sums of the tile's samples (at most 16 KiB)
-    const uint32_t G = 1u << log_g, groups = 64u >> log_g, slots = kWaves * groups;   // lanes per row, rows per wave, rows side by side in the block
+    const uint32_t G = 1u << log_g, groups = 64u >> log_g, slots = plan::score::slots(log_g);   // lanes per row, rows per wave, rows side by side in the block
     const uint32_t lane = threadIdx.x & 63u, gl = lane & (G - 1u);
     const uint32_t slot = (threadIdx.x >> 6) * groups + (lane >> log_g);
     const uint32_t tile = blockIdx.x % tiles, slice = blockIdx.x / tiles;
     const uint32_t unit = tile * G + gl;       // this lane's row bytes [BYTES unit, BYTES unit + BYTES)
     const uint32_t N = a.sample_count, R = a.record_size;
     const uint64_t V = a.n_variants;
-    const uint64_t rbeg = V * slice / slices, rend = V * (slice + 1u) / slices;
+    const plan::RowRange rows = plan::slice_rows(V, slice, slices);
+    const uint64_t rbeg = rows.begin, rend = rows.end;
 
     for (uint32_t i = threadIdx.x; i < G * (uint32_t)(S * C); i += kThreads) table[i] = 0.0;
     __syncthreads();
@@ -176,7 +172,7 @@ __global__ __launch_bounds__(kThreads) void gt_score_kernel(ScoreArgs a, uint32_
         if (s64 >= N) break;
         const uint32_t s = (uint32_t)s64;
         uint32_t k = s;
-        if (a.kept_mask != nullptr) {
+        if (a.kept_mask != nullptr) {   // kept_rank_of (gt_common.hip.h), written out: an unkept sample leaves before its rank is formed
             const uint32_t *mw = reinterpret_cast<const uint32_t *>(a.kept_mask + 16u + 16u * (s >> 6));
             const uint32_t j = (s >> 4) & 3u, bit = 2u * (s & 15u);
             if (((mw[j] >> bit) & 1u) == 0u) continue;
@@ -186,33 +182,6 @@ __global__ __launch_bounds__(kThreads) void gt_score_kernel(ScoreArgs a, uint32_
         const double v = table[((ts % (uint32_t)S) * (uint32_t)C + c) * G + ts / (uint32_t)S];
         if (v != 0.0) unsafeAtomicAdd(a.scores + (uint64_t)k * (uint32_t)C + c, v);   // global_atomic_add_f64
     }
-}
-
-struct Plan {
-    uint32_t bytes, log_g, tiles, slices;
-};
-
-Plan plan(const ScoreArgs &a, int num_cus, int slices_per_tile)
-{
-    Plan p;
-    p.bytes = lane_bytes(a.n_columns);
-    const uint32_t units = (a.record_size + p.bytes - 1u) / p.bytes;   // units of a row
-    p.log_g = 0u;
-    while (p.log_g < 6u && (1u << p.log_g) < units) p.log_g++;
-    const uint32_t G = 1u << p.log_g;
-    p.tiles = (units + G - 1u) / G;
-    const uint64_t target = (uint64_t)(num_cus > 0 ? num_cus : 256) * kMaxBlocksPerCu;
-    const uint64_t step_rows = (uint64_t)kWaves * (64u / G) * batch_rows(a.n_columns);   // one batch of every slot
-    uint64_t s;
-    if (slices_per_tile > 0) {
-        s = (uint64_t)slices_per_tile;
-    } else {
-        s = std::max<uint64_t>(1u, target / p.tiles);
-        s = std::min<uint64_t>(s, std::max<uint64_t>(1u, a.n_variants / kMinSliceRows));
-    }
-    s = std::min<uint64_t>(s, std::max<uint64_t>(1u, (a.n_variants + step_rows - 1u) / step_rows));
-    p.slices = (uint32_t)std::min<uint64_t>(s, 0x7FFFFFFFull / p.tiles);
-    return p;
 }
 
 template <int BYTES, int C>
@@ -226,7 +195,7 @@ void launch(const ScoreArgs &a, const Plan &p, hipStream_t stream)
 hipError_t launch_gt_score(const ScoreArgs &a, int slices_per_tile, int num_cus, hipStream_t stream)
 {
     if (a.n_variants == 0 || a.sample_count == 0) return hipSuccess;
-    const Plan p = plan(a, num_cus, slices_per_tile);
+    const Plan p = plan::score::plan(a.record_size, a.n_variants, a.n_columns, num_cus, slices_per_tile);
     switch (a.n_columns) {
         case 1u: launch<4, 1>(a, p, stream); break;
         case 2u: launch<4, 2>(a, p, stream); break;

@@ -24,19 +24,13 @@
 // many as fill the chip's resident blocks, so each sample gets at most a few thousand partials.
 #include "gt_common.hip.h"
 #include "kernels.h"
+#include "launch_plan.h"
 
 namespace pgenhip {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr uint32_t kWaves = kThreads / 64;
-constexpr uint32_t kBatch = 8;                           // rows per carry-save batch
-constexpr int kHiBits = 8;                               // batch counter bits
-constexpr uint32_t kWindowBatches = (1u << kHiBits) - 1u;   // batches between flushes (2 040 rows; a counter holds 2 047)
-constexpr uint32_t kColWords = 65;                       // LDS words per 64-sample column chunk and category
-constexpr uint32_t kMaxBlocksPerCu = 4;
-constexpr uint32_t kLdsPerCu = 160u * 1024u;
+using namespace plan::scount;   // kThreads, kBatch, kHiBits, kWindowBatches, kColWords, ... and the launch plan
 
 // 32 samples' counts, bit-sliced: ones + 2 twos + 4 fours + 8 * hi (hi a kHiBits-bit number)
 struct Slice {
@@ -94,14 +88,15 @@ __global__ __launch_bounds__(kThreads) void gt_scount_kernel(ScountArgs a, uint3
 {
     extern __shared__ uint32_t table[];   // [3][cols * kColWords]: het, hom-alt, missing of the tile's samples
     constexpr uint32_t kGroups = 64u / G;
-    constexpr uint32_t kSlots = kWaves * kGroups;   // rows side by side in the block
+    constexpr uint32_t kSlots = slots(G);   // rows side by side in the block
     const uint32_t lane = threadIdx.x & 63u, gl = lane % (uint32_t)G;
     const uint32_t slot = (threadIdx.x >> 6) * kGroups + lane / (uint32_t)G;
     const uint32_t tile = blockIdx.x % tiles, slice = blockIdx.x / tiles;
     const uint32_t col = tile * (uint32_t)G + gl;   // this lane's column chunk: row bytes [16 col, 16 col + 16)
     const uint32_t N = a.sample_count, R = a.record_size;
     const uint64_t V = a.n_variants;
-    const uint64_t rbeg = V * slice / slices, rend = V * (slice + 1u) / slices;
+    const plan::RowRange rows = plan::slice_rows(V, slice, slices);
+    const uint64_t rbeg = rows.begin, rend = rows.end;
     const uint32_t plane = cols * kColWords;
 
     for (uint32_t i = threadIdx.x; i < 3u * plane; i += kThreads) table[i] = 0u;
@@ -146,7 +141,7 @@ __global__ __launch_bounds__(kThreads) void gt_scount_kernel(ScountArgs a, uint3
         }
         // flush the window: batches <= 255, so hi planes past the batch count's bit length are zero
         const uint32_t batches = (uint32_t)((t_end - t0 + kBatch - 1u) / kBatch);
-        const int n_hi = 32 - __builtin_clz(batches | 1u);
+        const int n_hi = hi_planes(batches);
         if (owner) {
             uint32_t *const het = table + gl * kColWords, *const alt = het + plane, *const miss = alt + plane;
 #pragma unroll 1
@@ -172,7 +167,7 @@ __global__ __launch_bounds__(kThreads) void gt_scount_kernel(ScountArgs a, uint3
         const uint32_t s = tile * 64u * (uint32_t)G + ts;
         if (s >= N) break;
         uint32_t k = s;
-        if (a.kept_mask != nullptr) {
+        if (a.kept_mask != nullptr) {   // kept_rank_of (gt_common.hip.h), written out: an unkept sample leaves before its rank is formed
             const uint32_t *mw = reinterpret_cast<const uint32_t *>(a.kept_mask + 16u + 16u * (s >> 6));
             const uint32_t j = (s >> 4) & 3u, bit = 2u * (s & 15u);
             if (((mw[j] >> bit) & 1u) == 0u) continue;
@@ -186,34 +181,12 @@ __global__ __launch_bounds__(kThreads) void gt_scount_kernel(ScountArgs a, uint3
     }
 }
 
-struct Plan {
-    uint32_t G, tiles, cols, slices;
-    size_t lds_bytes;
-};
-
-Plan plan(const ScountArgs &a, int num_cus, int slices_per_tile)
-{
-    Plan p;
-    const uint32_t C = (a.record_size + 15u) / 16u;   // column chunks of a row
-    p.G = C <= 4u ? 4u : C <= 8u ? 8u : C <= 16u ? 16u : C <= 32u ? 32u : 64u;
-    p.tiles = (C + p.G - 1u) / p.G;
-    p.cols = p.tiles == 1u ? C : p.G;
-    p.lds_bytes = (size_t)3u * p.cols * kColWords * sizeof(uint32_t);
-    const uint32_t per_cu = std::max<uint32_t>(1u, std::min<uint32_t>(kMaxBlocksPerCu, kLdsPerCu / (uint32_t)p.lds_bytes));
-    const uint64_t target = (uint64_t)(num_cus > 0 ? num_cus : 256) * per_cu;
-    const uint64_t rows_per_block_step = (uint64_t)kWaves * (64u / p.G) * kBatch;   // one batch of every slot
-    uint64_t s = slices_per_tile > 0 ? (uint64_t)slices_per_tile : std::max<uint64_t>(1u, target / p.tiles);
-    s = std::min<uint64_t>(s, std::max<uint64_t>(1u, (a.n_variants + rows_per_block_step - 1u) / rows_per_block_step));
-    p.slices = (uint32_t)std::min<uint64_t>(s, 0x7FFFFFFFull / p.tiles);
-    return p;
-}
-
 }  // namespace
 
 hipError_t launch_gt_scount(const ScountArgs &a, int slices_per_tile, int num_cus, hipStream_t stream)
 {
     if (a.n_variants == 0 || a.sample_count == 0) return hipSuccess;
-    const Plan p = plan(a, num_cus, slices_per_tile);
+    const Plan p = plan::scount::plan(a.record_size, a.n_variants, num_cus, slices_per_tile);
     const dim3 grid(p.tiles * p.slices), block(kThreads);
     switch (p.G) {
         case 4u: hipLaunchKernelGGL(gt_scount_kernel<4>, grid, block, p.lds_bytes, stream, a, p.tiles, p.slices, p.cols); break;

@@ -30,20 +30,16 @@
 // global_atomic_add_u32.
 #include "gt_common.hip.h"
 #include "kernels.h"
+#include "launch_plan.h"
 
 namespace pgenhip {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr uint32_t kTile = 64;             // ranks of a block tile, per operand
-constexpr uint32_t kStepRows = 64;         // rows of one MFMA step (the instruction's k)
+using namespace plan::spair;               // kThreads, kTile, kStepRows, the grid caps and the launch plan
 constexpr uint32_t kRankStride = 80;       // bytes between ranks in the LDS image (64 rows + 16: ds_read_b128 of 16 ranks spread over the banks)
 constexpr uint32_t kIndBytes = kTile * kRankStride;
 constexpr uint32_t kOperandBytes = 3u * kIndBytes;
-constexpr uint32_t kMaxGridTiles = 1u << 20;   // tiles (pair blocks) side by side in the grid; a block strides over the rest
-constexpr uint32_t kMaxGridBlocks = 1u << 22;
-constexpr uint32_t kMinSliceRows = 256;    // rows a slice takes at least when the plan is not forced
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 
@@ -58,7 +54,8 @@ __global__ __launch_bounds__(kThreads) void gt_spair_general_kernel(SpairArgs a,
 {
     const uint32_t slice = blockIdx.x / grid_pairs;
     const uint64_t V = a.n_variants;
-    const uint64_t rbeg = V * slice / slices, rend = V * (slice + 1u) / slices;
+    const plan::RowRange rows = plan::slice_rows(V, slice, slices);
+    const uint64_t rbeg = rows.begin, rend = rows.end;
     for (uint64_t pb = blockIdx.x % grid_pairs; pb < pair_blocks; pb += grid_pairs) {
         const uint64_t p = pb * kThreads + threadIdx.x;
         if (p >= pairs) break;
@@ -88,7 +85,8 @@ __global__ __launch_bounds__(kThreads, 2) void gt_spair_mfma_kernel(SpairArgs a,
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t slice = blockIdx.x / grid_tiles;
     const uint64_t V = a.n_variants;
-    const uint64_t rbeg = V * slice / slices, rend = V * (slice + 1u) / slices;
+    const plan::RowRange rows = plan::slice_rows(V, slice, slices);
+    const uint64_t rbeg = rows.begin, rend = rows.end;
     const uint32_t n = (uint32_t)(rend - rbeg);                 // < 2^31 (launch plan)
     const uint32_t steps = (n + kStepRows - 1u) / kStepRows;
     // staging role: operand, rank of the tile, half of the step's rows (wave-uniform: waves 0, 1 stage rows 0-31, waves 2, 3 rows 32-63)
@@ -240,43 +238,25 @@ __global__ __launch_bounds__(kThreads, 2) void gt_spair_mfma_kernel(SpairArgs a,
     }
 }
 
-// row ranges of a launch: forced, or as many as bring the grid to `target` blocks, of at least kMinSliceRows rows each; never
-// more than there are units of `unit_rows` rows, never so few that a range reaches 2^31 rows, and the grid stays below kMaxGridBlocks
-uint32_t plan_slices(uint32_t n_variants, uint64_t grid_items, int forced, int num_cus, uint32_t blocks_per_cu, uint32_t unit_rows)
-{
-    const uint64_t target = (uint64_t)(num_cus > 0 ? num_cus : 256) * blocks_per_cu;
-    uint64_t s;
-    if (forced > 0) {
-        s = (uint64_t)forced;
-    } else {
-        s = std::max<uint64_t>(1u, target / grid_items);
-        s = std::min<uint64_t>(s, std::max<uint64_t>(1u, n_variants / kMinSliceRows));
-    }
-    s = std::min<uint64_t>(s, ((uint64_t)n_variants + unit_rows - 1u) / unit_rows);
-    s = std::min<uint64_t>(s, kMaxGridBlocks / grid_items);
-    s = std::max<uint64_t>(s, ((uint64_t)n_variants >> 30) + 1u);
-    return (uint32_t)s;
-}
-
 }  // namespace
 
 hipError_t launch_gt_spair_general(const SpairArgs &a, int slices_per_tile, int num_cus, hipStream_t stream)
 {
     if (a.n_variants == 0 || a.a_count == 0 || a.b_count == 0) return hipSuccess;
-    const uint64_t pairs = (uint64_t)a.a_count * a.b_count, pair_blocks = (pairs + kThreads - 1u) / kThreads;
-    const uint32_t grid_pairs = (uint32_t)std::min<uint64_t>(pair_blocks, kMaxGridTiles);
-    const uint32_t slices = plan_slices(a.n_variants, grid_pairs, slices_per_tile, num_cus, 8u, 1u);
-    hipLaunchKernelGGL(gt_spair_general_kernel, dim3(grid_pairs * slices), dim3(kThreads), 0, stream, a, pairs, pair_blocks, grid_pairs, slices);
+    const uint64_t pairs = (uint64_t)a.a_count * a.b_count;
+    const uint32_t grid_pairs = plan::spair::grid_pairs(a.a_count, a.b_count);
+    const uint32_t slices = general_slices(a.n_variants, a.a_count, a.b_count, slices_per_tile, num_cus);
+    hipLaunchKernelGGL(gt_spair_general_kernel, dim3(grid_pairs * slices), dim3(kThreads), 0, stream, a, pairs, pair_blocks(a.a_count, a.b_count), grid_pairs, slices);
     return hipGetLastError();
 }
 
 hipError_t launch_gt_spair_mfma(const SpairArgs &a, int slices_per_tile, int num_cus, hipStream_t stream)
 {
     if (a.n_variants == 0 || a.a_count == 0 || a.b_count == 0) return hipSuccess;
-    const uint32_t tiles_a = (a.a_count + kTile - 1u) / kTile, tiles_b = (a.b_count + kTile - 1u) / kTile;
-    const uint64_t tiles = (uint64_t)tiles_a * tiles_b;
-    const uint32_t grid_tiles = (uint32_t)std::min<uint64_t>(tiles, kMaxGridTiles);
-    const uint32_t slices = plan_slices(a.n_variants, grid_tiles, slices_per_tile, num_cus, 2u, kStepRows);
+    const uint32_t tiles_b = range_tiles(a.b_count);
+    const uint64_t tiles = plan::spair::tiles(a.a_count, a.b_count);
+    const uint32_t grid_tiles = plan::spair::grid_tiles(a.a_count, a.b_count);
+    const uint32_t slices = mfma_slices(a.n_variants, a.a_count, a.b_count, slices_per_tile, num_cus);
     const dim3 grid(grid_tiles * slices), block(kThreads);
     if (a.record_off != nullptr)
         hipLaunchKernelGGL(gt_spair_mfma_kernel<2>, grid, block, 0, stream, a, tiles_b, tiles, grid_tiles, slices);

@@ -24,32 +24,15 @@
 //   A: m = l & 15, k = l >> 4;   B: k = l >> 4, n = l & 15;   D register i: m = (l >> 4) + 4 i, n = l & 15
 #include "gt_common.hip.h"
 #include "kernels.h"
+#include "launch_plan.h"
 
 namespace pgenhip {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr uint32_t kWaves = kThreads / 64;
-constexpr uint32_t kBlocksPerCu = 8;
-constexpr uint32_t kTileBytes = 32;       // record bytes (MFMA steps) of a tile: 128 samples, 32 A registers (64 VGPRs) per lane
-constexpr uint32_t kGroupRows = 4;        // rows of one MFMA
-constexpr uint32_t kMinSliceRows = 256;   // rows a slice takes at least when the plan is not forced: a block's A load is worth that many rows
+using namespace plan::vsum;   // kThreads, kWaves, kTileBytes, kGroupRows, ... and the launch plan
 
 typedef double vsum_v4d __attribute__((ext_vector_type(4)));
-
-// rank of sample s in the kept list (s itself without a mask); kept says whether it is in it
-__device__ __forceinline__ uint32_t kept_rank_of(const VsumArgs &a, uint32_t s, bool &kept)
-{
-    kept = true;
-    if (a.kept_mask == nullptr) return s;
-    const uint32_t *mw = reinterpret_cast<const uint32_t *>(a.kept_mask + 16u + 16u * (s >> 6));
-    const uint32_t j = (s >> 4) & 3u, bit = 2u * (s & 15u);
-    kept = ((mw[j] >> bit) & 1u) != 0u;
-    uint32_t k = a.kept_rank[s >> 6] + __builtin_popcount(mw[j] & ((1u << bit) - 1u));
-    for (uint32_t i = 0; i < j; i++) k += __builtin_popcount(mw[i]);
-    return k;
-}
 
 __global__ __launch_bounds__(kThreads) void gt_vsum_general_kernel(VsumArgs a)
 {
@@ -70,7 +53,7 @@ __global__ __launch_bounds__(kThreads) void gt_vsum_general_kernel(VsumArgs a)
                 const uint32_t s = 4u * b + i;
                 if (s >= N) break;   // pad bits
                 bool kept;
-                const uint32_t k = kept_rank_of(a, s, kept);
+                const uint32_t k = kept_rank_of(a.kept_mask, a.kept_rank, s, kept);
                 if (!kept) continue;
                 const double v = a.values[(uint64_t)k * a.v_stride + c];
                 const uint32_t code = (byte >> (2u * i)) & 3u;
@@ -107,7 +90,8 @@ __global__ __launch_bounds__(kThreads) void gt_vsum_mfma_kernel(VsumArgs a, uint
 
     for (uint32_t item = blockIdx.x; item < items; item += gridDim.x) {
         const uint32_t tile = item % tiles, slice = item / tiles;
-        const uint64_t gbeg = (V + kGroupRows - 1u) / kGroupRows * slice / slices, gend = (V + kGroupRows - 1u) / kGroupRows * (slice + 1u) / slices;
+        const plan::RowRange slice_groups = plan::slice_rows(groups(V), slice, slices);
+        const uint64_t gbeg = slice_groups.begin, gend = slice_groups.end;
         const uint32_t b0 = tile * kTileBytes;                                   // the tile's own bytes are [b0, b0 + kTileBytes) of the record
         const uint32_t at = R >= kTileBytes ? min(b0, R - kTileBytes) : 0u;      // ... and it reads [at, at + kTileBytes) (block-uniform)
 
@@ -120,7 +104,7 @@ __global__ __launch_bounds__(kThreads) void gt_vsum_mfma_kernel(VsumArgs a, uint
             double v = 0.0;
             if (byte >= b0 && byte < R && s64 < N && m < C) {
                 bool kept;
-                const uint32_t k = kept_rank_of(a, (uint32_t)s64, kept);
+                const uint32_t k = kept_rank_of(a.kept_mask, a.kept_rank, (uint32_t)s64, kept);
                 if (kept) v = a.values[(uint64_t)k * a.v_stride + m];
             }
             av[t] = v;
@@ -173,47 +157,19 @@ __global__ __launch_bounds__(kThreads) void gt_vsum_mfma_kernel(VsumArgs a, uint
     }
 }
 
-struct Plan {
-    uint32_t tiles, slices, grid;
-};
-
-Plan plan(const VsumArgs &a, int num_cus, int blocks)
-{
-    Plan p;
-    p.tiles = (a.record_size + kTileBytes - 1u) / kTileBytes;
-    const uint64_t target = (uint64_t)(num_cus > 0 ? num_cus : 256) * kBlocksPerCu;
-    const uint64_t groups = ((uint64_t)a.n_variants + kGroupRows - 1u) / kGroupRows;
-    uint64_t s;
-    if (blocks > 0) {
-        s = (uint64_t)blocks;
-    } else {
-        s = std::max<uint64_t>(1u, target / p.tiles);
-        s = std::min<uint64_t>(s, std::max<uint64_t>(1u, a.n_variants / kMinSliceRows));
-    }
-    s = std::min<uint64_t>(s, (groups + kWaves - 1u) / kWaves);   // at least one group per wave
-    p.slices = (uint32_t)std::min<uint64_t>(s, 0x7FFFFFFFull / p.tiles);
-    const uint64_t items = (uint64_t)p.tiles * p.slices;
-    p.grid = (uint32_t)std::min<uint64_t>(items, blocks > 0 ? (uint64_t)blocks : target);
-    return p;
-}
-
 }  // namespace
 
 hipError_t launch_gt_vsum_general(const VsumArgs &a, int blocks, int num_cus, hipStream_t stream)
 {
     if (a.n_variants == 0 || a.sample_count == 0) return hipSuccess;
-    const uint64_t need = ((uint64_t)a.n_variants * a.n_columns + kWaves - 1u) / kWaves;   // a wave per (row, column)
-    const uint64_t cap = blocks > 0 ? (uint64_t)blocks : (uint64_t)(num_cus > 0 ? num_cus : 256) * kBlocksPerCu;
-    hipLaunchKernelGGL(gt_vsum_general_kernel, dim3((uint32_t)std::min(need, cap)), dim3(kThreads), 0, stream, a);
+    hipLaunchKernelGGL(gt_vsum_general_kernel, dim3(general_grid(a.n_variants, a.n_columns, num_cus, blocks)), dim3(kThreads), 0, stream, a);
     return hipGetLastError();
 }
-
-bool gt_vsum_mfma_atomic(const VsumArgs &a) { return a.record_size > kTileBytes; }
 
 hipError_t launch_gt_vsum_mfma(const VsumArgs &a, int blocks, int num_cus, hipStream_t stream)
 {
     if (a.n_variants == 0 || a.sample_count == 0) return hipSuccess;
-    const Plan p = plan(a, num_cus, blocks);
+    const MfmaPlan p = mfma_plan(a.record_size, a.n_variants, num_cus, blocks);
     hipLaunchKernelGGL(gt_vsum_mfma_kernel, dim3(p.grid), dim3(kThreads), 0, stream, a, p.tiles, p.slices);
     return hipGetLastError();
 }

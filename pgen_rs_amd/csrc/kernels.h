@@ -124,9 +124,8 @@ struct CountArgs : RowSource {
 };
 // Bytes of the ctx's kept mask buffer for records of R bytes: the mask behind 16 zero bytes, zeros up to the last chunk a row can touch
 inline size_t gt_count_mask_bytes(uint32_t record_size) { return 16u * ((size_t)(record_size + 30u) / 16u + 2u); }
-// lanes per row of the short-row shape for records of R bytes (64: rows this long take the wave-per-row shape under AUTO)
-uint32_t gt_count_lanes_per_row(uint32_t record_size);
-// wave_per_row: one wave per row (long rows); else 4 .. 32 lanes per row, several rows per wave (short rows)
+// wave_per_row: one wave per row (long rows); else 4 .. 32 lanes per row, several rows per wave (short rows); AUTO's choice is
+// plan::count::wave_per_row
 hipError_t launch_gt_count(const CountArgs &a, bool wave_per_row, int num_cus, hipStream_t stream);
 
 // Per-sample genotype counts (gt_scount.hip): the counts of the selected rows added into counts[4 * k + c] for every kept
@@ -166,9 +165,8 @@ struct VsumArgs : RowSource {
 };
 // blocks: forced grid size (0 = by shape; tests force small grids to walk the grid-stride loops and the multi-tile combine)
 hipError_t launch_gt_vsum_general(const VsumArgs &a, int blocks, int num_cus, hipStream_t stream);
-// the matrix-core shape: any layout, any keep set with K >= 1.  It only ADDS when gt_vsum_mfma_atomic(a) (rows of more than one
-// tile): the caller zeroes the sums first
-bool gt_vsum_mfma_atomic(const VsumArgs &a);
+// the matrix-core shape: any layout, any keep set with K >= 1.  It only ADDS when plan::vsum::mfma_atomic(record_size) (rows of
+// more than one tile): the caller zeroes the sums first
 hipError_t launch_gt_vsum_mfma(const VsumArgs &a, int blocks, int num_cus, hipStream_t stream);
 
 // Numeric genotype matrix (gt_matrix.hip):element (j, k) = the pattern of the code of kept sample k in selected row j.
@@ -181,8 +179,8 @@ struct MatrixArgs : RowSource {
     uint32_t sample_major;        // 0: (j, k) at out + j*out_stride + k*elem_bytes; 1: at out + k*out_stride + j*elem_bytes
     uint32_t tab[4];              // the patterns of codes 0-3, zero-extended
 };
-bool gt_matrix_stream_applicable(const MatrixArgs &a);   // variant-major, all samples kept
-bool gt_matrix_tile_applicable(const MatrixArgs &a);     // sample-major, all samples kept, out and out_stride multiples of 16
+// STREAM needs variant-major with all samples kept, TILE sample-major with all samples kept and out, out_stride multiples of 16
+// (plan::matrix::stream_applicable, tile_applicable; AUTO asks plan::matrix::auto_shape)
 // blocks: forced grid size (0 = by shape; tests force small grids to walk the grid-stride loops)
 hipError_t launch_gt_matrix_general(const MatrixArgs &a, int blocks, int num_cus, hipStream_t stream);
 hipError_t launch_gt_matrix_stream(const MatrixArgs &a, int blocks, int num_cus, hipStream_t stream);
@@ -225,8 +223,7 @@ struct GramArgs : RowSource {
     uint64_t out_stride;          // doubles between the output rows
     uint32_t store;               // 1: every entry has one owner and is overwritten (one slice, no ACCUMULATE): plain stores
 };
-// row ranges per tile of a launch of that shape (slices_per_tile: forced, 0 = by shape); 1 means every entry has one owner
-uint32_t gt_gram_slices(const GramArgs &a, bool mfma, int slices_per_tile, int num_cus);
+// slices: row ranges per tile (plan::gram::general_slices / mfma_slices); 1 means every entry has one owner
 hipError_t launch_gt_gram_general(const GramArgs &a, uint32_t slices, hipStream_t stream);
 hipError_t launch_gt_gram_mfma(const GramArgs &a, uint32_t slices, hipStream_t stream);
 
@@ -240,8 +237,7 @@ struct PackArgs : RowSource {
     uint32_t map8;                // the code written for input code c at bits 2c, 2c + 1
 };
 constexpr uint32_t kPackIdentityMap = 0xE4u;
-bool gt_pack_dense_applicable(const PackArgs &a);    // all samples kept
-bool gt_pack_gather_applicable(const PackArgs &a);   // a kept list, K >= 1
+// DENSE needs all samples kept, GATHER a kept list with K >= 1 (plan::pack::dense_applicable, gather_applicable)
 // blocks: forced grid size (0 = by shape; tests force small grids to walk the grid-stride loops)
 hipError_t launch_gt_pack_general(const PackArgs &a, int blocks, int num_cus, hipStream_t stream);
 hipError_t launch_gt_pack_dense(const PackArgs &a, int blocks, int num_cus, hipStream_t stream);

@@ -1,0 +1,463 @@
+// launch_plan.h — the launch plans of the analysis kernels (gt_count, gt_scount, gt_score, gt_vsum, gt_matrix, gt_pair, gt_pack,
+// gt_spair, gt_gram): lanes per row, tiles, row ranges ("slices") and grid caps, as functions of scalars.  The single statement of
+// every plan: the launchers call it, the kernels take their constants and their row ranges from it, and the tests compile this
+// header for the host (tests/plan_probe.cpp) and run it.  Plain C++17 on purpose: no HIP header, no argument struct.
+#pragma once
+#include <stdint.h>
+
+#include <algorithm>
+
+#ifdef __HIPCC__
+#define PGENHIP_PLAN_HD __host__ __device__ __attribute__((always_inline))
+#else
+#define PGENHIP_PLAN_HD
+#endif
+
+namespace pgenhip::plan {
+
+// ---- shared ----------------------------------------------------------------------------------------------------------------------
+// the chip's CUs as a launcher was told them (0: unknown, planned as 256)
+PGENHIP_PLAN_HD inline uint64_t cu_count(int num_cus) { return (uint64_t)(num_cus > 0 ? num_cus : 256); }
+
+// blocks of a grid-stride launch over `work` blocks' worth of items: capped at per_cu blocks per CU, or at the forced size; never 0
+PGENHIP_PLAN_HD inline uint32_t grid_blocks(uint64_t work, uint32_t per_cu, int num_cus, int forced)
+{
+    const uint64_t cap = forced > 0 ? (uint64_t)forced : cu_count(num_cus) * per_cu;
+    return (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(work, cap));
+}
+
+// rows [begin, end) of slice `slice` of `slices`: the slices tile [0, V) in order, and none is empty while slices <= V
+struct RowRange {
+    uint64_t begin, end;
+};
+PGENHIP_PLAN_HD inline RowRange slice_rows(uint64_t V, uint32_t slice, uint32_t slices) { return {V * slice / slices, V * (slice + 1u) / slices}; }
+
+// ---- gt_count: per-variant counts --------------------------------------------------------------------------------------------------
+namespace count {
+
+constexpr int kThreads = 256;
+constexpr uint32_t kBlocksPerCu = 8;   // 32 waves per CU: up to 128 KiB of record loads in flight per CU on long rows
+
+// the most aligned 16-byte chunks a row of R bytes can touch
+PGENHIP_PLAN_HD constexpr uint32_t max_chunks(uint32_t record_size) { return (record_size + 30u) / 16u; }
+
+// lanes per row of the short-row shape: as many as three passes over the row's chunks need (64: rows this long take the
+// wave-per-row shape under AUTO)
+PGENHIP_PLAN_HD constexpr uint32_t lanes_per_row(uint32_t record_size)
+{
+    const uint32_t chunks = max_chunks(record_size);
+    return chunks <= 12u ? 4u : chunks <= 24u ? 8u : chunks <= 48u ? 16u : chunks <= 96u ? 32u : 64u;
+}
+
+// a wave per row: asked for, or AUTO (neither shape asked for) where the ladder says 64 lanes
+PGENHIP_PLAN_HD constexpr bool wave_per_row(bool asked_wave_per_row, bool asked_rows_per_wave, uint32_t record_size)
+{
+    return asked_wave_per_row || (!asked_rows_per_wave && lanes_per_row(record_size) == 64u);
+}
+
+// the instantiation: G lanes per row, RU rows per group in flight, U chunks per lane per pass
+struct Shape {
+    uint32_t G, RU, U;
+};
+PGENHIP_PLAN_HD constexpr Shape shape(uint32_t record_size, bool wave_per_row)
+{
+    if (wave_per_row) return {64u, 1u, 4u};
+    const uint32_t g = lanes_per_row(record_size);
+    return {g < 32u ? g : 32u, 2u, 1u};   // (forced on long rows: G = 32, more passes per row)
+}
+
+PGENHIP_PLAN_HD constexpr uint32_t rows_per_step(uint32_t G, uint32_t RU) { return (64u / G) * RU; }   // rows a wave takes per turn of its loop
+PGENHIP_PLAN_HD constexpr uint32_t rows_per_block(uint32_t G, uint32_t RU) { return (uint32_t)(kThreads / 64) * rows_per_step(G, RU); }
+
+PGENHIP_PLAN_HD inline uint32_t grid(uint32_t n_variants, uint32_t G, uint32_t RU, int num_cus)
+{
+    const uint64_t per_block = rows_per_block(G, RU);
+    return grid_blocks(((uint64_t)n_variants + per_block - 1u) / per_block, kBlocksPerCu, num_cus, 0);
+}
+
+// passes over the most chunks a row can span
+PGENHIP_PLAN_HD constexpr uint32_t passes(uint32_t record_size, uint32_t G, uint32_t U) { return (max_chunks(record_size) + G * U - 1u) / (G * U); }
+
+}  // namespace count
+
+// ---- gt_scount: per-sample counts --------------------------------------------------------------------------------------------------
+namespace scount {
+
+constexpr int kThreads = 256;
+constexpr uint32_t kWaves = kThreads / 64;
+constexpr uint32_t kBatch = 8;                           // rows per carry-save batch
+constexpr int kHiBits = 8;                               // batch counter bits
+constexpr uint32_t kWindowBatches = (1u << kHiBits) - 1u;   // batches between flushes (2 040 rows; a counter holds 2 047)
+constexpr uint32_t kColWords = 65;                       // LDS words per 64-sample column chunk and category
+constexpr uint32_t kMaxBlocksPerCu = 4;
+constexpr uint32_t kLdsPerCu = 160u * 1024u;
+
+// rows side by side in a block of G lanes per row
+PGENHIP_PLAN_HD constexpr uint32_t slots(uint32_t G) { return kWaves * (64u / G); }
+
+// the hi planes a flush reads after `batches` batches (<= kWindowBatches): planes past the batch count's bit length are zero
+PGENHIP_PLAN_HD inline int hi_planes(uint32_t batches) { return 32 - __builtin_clz(batches | 1u); }
+
+struct Plan {
+    uint32_t G, tiles, cols, slices;
+    size_t lds_bytes;
+};
+
+// slices_per_tile: forced (0 = as many as fill the chip's resident blocks); never more than one batch of every slot leaves rows for
+PGENHIP_PLAN_HD inline Plan plan(uint32_t record_size, uint32_t n_variants, int num_cus, int slices_per_tile)
+{
+    Plan p{};
+    const uint32_t C = (record_size + 15u) / 16u;   // column chunks of a row
+    p.G = C <= 4u ? 4u : C <= 8u ? 8u : C <= 16u ? 16u : C <= 32u ? 32u : 64u;
+    p.tiles = (C + p.G - 1u) / p.G;
+    p.cols = p.tiles == 1u ? C : p.G;
+    p.lds_bytes = (size_t)3u * p.cols * kColWords * sizeof(uint32_t);
+    const uint32_t per_cu = std::max<uint32_t>(1u, std::min<uint32_t>(kMaxBlocksPerCu, kLdsPerCu / (uint32_t)p.lds_bytes));
+    const uint64_t target = cu_count(num_cus) * per_cu;
+    const uint64_t rows_per_block_step = (uint64_t)slots(p.G) * kBatch;   // one batch of every slot
+    uint64_t s = slices_per_tile > 0 ? (uint64_t)slices_per_tile : std::max<uint64_t>(1u, target / p.tiles);
+    s = std::min<uint64_t>(s, std::max<uint64_t>(1u, (n_variants + rows_per_block_step - 1u) / rows_per_block_step));
+    p.slices = (uint32_t)std::min<uint64_t>(s, 0x7FFFFFFFull / p.tiles);
+    return p;
+}
+
+}  // namespace scount
+
+// ---- gt_score: per-sample weighted sums --------------------------------------------------------------------------------------------
+namespace score {
+
+constexpr int kThreads = 256;
+constexpr uint32_t kWaves = kThreads / 64;
+constexpr uint32_t kMaxBlocksPerCu = 4;
+constexpr uint32_t kMinSliceRows = 512;   // rows a slice takes at least when the plan is not forced: a block's flush is worth that many rows
+
+PGENHIP_PLAN_HD constexpr uint32_t lane_bytes(uint32_t columns) { return columns <= 2u ? 4u : columns <= 4u ? 2u : 1u; }
+PGENHIP_PLAN_HD constexpr uint32_t batch_rows(uint32_t columns) { return columns <= 4u ? 4u : 2u; }
+
+// rows side by side in a block of 2^log_g lanes per row
+PGENHIP_PLAN_HD constexpr uint32_t slots(uint32_t log_g) { return kWaves * (64u >> log_g); }
+
+struct Plan {
+    uint32_t bytes, log_g, tiles, slices;
+};
+
+PGENHIP_PLAN_HD inline Plan plan(uint32_t record_size, uint32_t n_variants, uint32_t n_columns, int num_cus, int slices_per_tile)
+{
+    Plan p{};
+    p.bytes = lane_bytes(n_columns);
+    const uint32_t units = (record_size + p.bytes - 1u) / p.bytes;   // units of a row
+    p.log_g = 0u;
+    while (p.log_g < 6u && (1u << p.log_g) < units) p.log_g++;
+    const uint32_t G = 1u << p.log_g;
+    p.tiles = (units + G - 1u) / G;
+    const uint64_t target = cu_count(num_cus) * kMaxBlocksPerCu;
+    const uint64_t step_rows = (uint64_t)slots(p.log_g) * batch_rows(n_columns);   // one batch of every slot
+    uint64_t s;
+    if (slices_per_tile > 0) {
+        s = (uint64_t)slices_per_tile;
+    } else {
+        s = std::max<uint64_t>(1u, target / p.tiles);
+        s = std::min<uint64_t>(s, std::max<uint64_t>(1u, n_variants / kMinSliceRows));
+    }
+    s = std::min<uint64_t>(s, std::max<uint64_t>(1u, (n_variants + step_rows - 1u) / step_rows));
+    p.slices = (uint32_t)std::min<uint64_t>(s, 0x7FFFFFFFull / p.tiles);
+    return p;
+}
+
+}  // namespace score
+
+// ---- gt_vsum: per-variant sums -----------------------------------------------------------------------------------------------------
+namespace vsum {
+
+constexpr int kThreads = 256;
+constexpr uint32_t kWaves = kThreads / 64;
+constexpr uint32_t kBlocksPerCu = 8;
+constexpr uint32_t kTileBytes = 32;       // record bytes (MFMA steps) of a tile: 128 samples, 32 A registers (64 VGPRs) per lane
+constexpr uint32_t kGroupRows = 4;        // rows of one MFMA
+constexpr uint32_t kMinSliceRows = 256;   // rows a slice takes at least when the plan is not forced: a block's A load is worth that many rows
+
+// groups of kGroupRows rows; a slice is a range of groups (slice_rows over the groups)
+PGENHIP_PLAN_HD constexpr uint64_t groups(uint64_t n_variants) { return (n_variants + kGroupRows - 1u) / kGroupRows; }
+
+// MFMA: tiles of one row meet in atomics (the caller zeroes the sums first) when a row has more than one
+PGENHIP_PLAN_HD constexpr bool mfma_atomic(uint32_t record_size) { return record_size > kTileBytes; }
+
+struct MfmaPlan {
+    uint32_t tiles, slices, grid;
+};
+
+// blocks: forced grid size, which also forces the slices (0 = by shape)
+PGENHIP_PLAN_HD inline MfmaPlan mfma_plan(uint32_t record_size, uint32_t n_variants, int num_cus, int blocks)
+{
+    MfmaPlan p{};
+    p.tiles = (record_size + kTileBytes - 1u) / kTileBytes;
+    const uint64_t target = cu_count(num_cus) * kBlocksPerCu;
+    uint64_t s;
+    if (blocks > 0) {
+        s = (uint64_t)blocks;
+    } else {
+        s = std::max<uint64_t>(1u, target / p.tiles);
+        s = std::min<uint64_t>(s, std::max<uint64_t>(1u, n_variants / kMinSliceRows));
+    }
+    s = std::min<uint64_t>(s, (groups(n_variants) + kWaves - 1u) / kWaves);   // at least one group per wave
+    p.slices = (uint32_t)std::min<uint64_t>(s, 0x7FFFFFFFull / p.tiles);
+    const uint64_t items = (uint64_t)p.tiles * p.slices;
+    p.grid = (uint32_t)std::min<uint64_t>(items, blocks > 0 ? (uint64_t)blocks : target);
+    return p;
+}
+
+// GENERAL: a wave per (row, column), the rest by grid stride
+PGENHIP_PLAN_HD inline uint32_t general_grid(uint32_t n_variants, uint32_t n_columns, int num_cus, int blocks)
+{
+    return grid_blocks(((uint64_t)n_variants * n_columns + kWaves - 1u) / kWaves, kBlocksPerCu, num_cus, blocks);
+}
+
+}  // namespace vsum
+
+// ---- gt_matrix: numeric genotype matrix --------------------------------------------------------------------------------------------
+namespace matrix {
+
+constexpr int kThreads = 256;
+constexpr uint32_t kBlocksPerCu = 8;         // grid cap of the grid-stride kernels
+constexpr uint32_t kLongRowBytes = 4096;     // STREAM: output rows from this size take the division-free rows kernel
+constexpr uint32_t kTileVariants = 128;      // TILE: rows of a block's tile (16 per lane x 8 lanes)
+constexpr uint32_t kWaveSamples = 128;       // TILE: samples of one wave (16 per lane x 8 lanes)
+constexpr uint32_t kTileSamples = 512;       // TILE: samples of a block's tile = 128 record bytes, one line per row
+constexpr uint32_t kTileBlocksPerCu = 4;     // TILE: grid cap (16 KiB of LDS per block)
+
+enum Shape : uint32_t { kGeneral = 1u, kStream = 2u, kTile = 3u };   // the values of PGENHIP_MATRIX_GENERAL / _STREAM / _TILE
+
+// STREAM: variant-major, all samples kept
+PGENHIP_PLAN_HD constexpr bool stream_applicable(bool all_kept, bool sample_major) { return all_kept && !sample_major; }
+
+// TILE: sample-major, all samples kept, out and out_stride multiples of 16 (one output row: the stride is not used)
+PGENHIP_PLAN_HD constexpr bool tile_applicable(bool all_kept, bool sample_major, uint32_t out_align, uint64_t out_stride, uint32_t kept_count)
+{
+    return all_kept && sample_major && out_align == 0u && (out_stride % 16u == 0u || kept_count <= 1u);
+}
+
+// what AUTO launches; out_align = out & 15
+PGENHIP_PLAN_HD constexpr Shape auto_shape(bool all_kept, bool sample_major, uint32_t out_align, uint64_t out_stride, uint32_t kept_count)
+{
+    return stream_applicable(all_kept, sample_major)                                   ? kStream
+           : tile_applicable(all_kept, sample_major, out_align, out_stride, kept_count) ? kTile
+                                                                                        : kGeneral;
+}
+
+PGENHIP_PLAN_HD inline uint32_t general_grid(uint32_t n_variants, uint32_t kept_count, int num_cus, int blocks)
+{
+    return grid_blocks(((uint64_t)n_variants * kept_count + kThreads - 1u) / kThreads, kBlocksPerCu, num_cus, blocks);
+}
+
+struct StreamPlan {
+    bool dense;         // the whole matrix is one span of bytes (else every row is a span of its own)
+    bool long_rows;     // the rows kernel: grid_x blocks along a row's chunks, grid_y along the rows
+    uint64_t per_row;   // aligned chunks a row can touch at any phase
+    uint64_t total;     // chunks (lanes' work items) of the launch
+    uint32_t grid_x, grid_y;
+};
+
+PGENHIP_PLAN_HD inline StreamPlan stream_plan(uint32_t n_variants, uint32_t kept_count, uint32_t elem_bytes, uint32_t out_align, uint64_t out_stride,
+                                              int num_cus, int blocks)
+{
+    StreamPlan p{};
+    const uint64_t row_bytes = (uint64_t)kept_count * elem_bytes;
+    p.dense = n_variants == 1u || out_stride == row_bytes;
+    p.per_row = (row_bytes + 15u) / 16u + 1u;
+    p.total = p.dense ? (out_align + row_bytes * n_variants + 15u) / 16u : p.per_row * n_variants;
+    p.long_rows = row_bytes >= kLongRowBytes;
+    if (p.long_rows) {
+        p.grid_x = grid_blocks((p.per_row + kThreads - 1u) / kThreads, kBlocksPerCu, num_cus, blocks > 0 ? 1 : 0);
+        const uint32_t gy = (uint32_t)std::min<uint64_t>(n_variants, std::max<uint32_t>(1u, grid_blocks(~0ull, kBlocksPerCu, num_cus, blocks) / p.grid_x));
+        p.grid_y = std::min<uint32_t>(gy, 65535u);
+    } else {
+        p.grid_x = grid_blocks((p.total + kThreads - 1u) / kThreads, kBlocksPerCu, num_cus, blocks);
+        p.grid_y = 1u;
+    }
+    return p;
+}
+
+struct TilePlan {
+    uint64_t v_tiles, bands, total;   // a launch walks bands x variant tiles, variant tile fastest
+    uint32_t grid;
+};
+
+PGENHIP_PLAN_HD inline TilePlan tile_plan(uint32_t n_variants, uint32_t sample_count, int num_cus, int blocks)
+{
+    TilePlan p{};
+    p.v_tiles = ((uint64_t)n_variants + kTileVariants - 1u) / kTileVariants;
+    p.bands = ((uint64_t)sample_count + kTileSamples - 1u) / kTileSamples;
+    p.total = p.v_tiles * p.bands;
+    p.grid = grid_blocks(p.total, kTileBlocksPerCu, num_cus, blocks);
+    return p;
+}
+
+}  // namespace matrix
+
+// ---- gt_pair: windowed pairwise tables ---------------------------------------------------------------------------------------------
+namespace pair {
+
+constexpr int kThreads = 64;                            // one wave per tile
+constexpr uint32_t kTile = 16;                          // TL = TR
+constexpr uint32_t kChunkWords = 16;                    // 32-sample words per staged chunk: 512 samples, 128 record bytes per row
+constexpr uint32_t kBlocksPerCu = 16;
+
+struct Plan {
+    uint64_t w_eff, tiles_per_left, n_items;
+    uint32_t grid;
+};
+
+// n_left >= 1, n_variants >= 2; blocks: forced grid size (0 = by shape)
+PGENHIP_PLAN_HD inline Plan plan(uint32_t n_variants, uint32_t n_left, uint32_t window, int num_cus, int blocks)
+{
+    Plan p{};
+    const uint64_t V = n_variants;
+    p.w_eff = window < V - 1 ? window : V - 1;
+    const uint64_t left_tiles = ((uint64_t)n_left + kTile - 1u) / kTile, right_tiles = (V + kTile - 1u) / kTile;
+    p.tiles_per_left = (kTile - 1u + p.w_eff) / kTile + 1u;   // the right tiles rows i0 .. i0 + 15 reach with d <= W, the diagonal one included
+    if (p.tiles_per_left > right_tiles) p.tiles_per_left = right_tiles;
+    p.n_items = left_tiles * p.tiles_per_left;
+    p.grid = blocks > 0 ? (uint32_t)blocks : grid_blocks(p.n_items, kBlocksPerCu, num_cus, 0);
+    return p;
+}
+
+}  // namespace pair
+
+// ---- gt_pack: packed records -------------------------------------------------------------------------------------------------------
+namespace pack {
+
+constexpr int kThreads = 256;
+constexpr uint32_t kBlocksPerCu = 8;       // grid cap of the grid-stride kernels
+constexpr uint32_t kPartChunks = 256u;     // DENSE, wave per row: chunks of one part (4 passes of 64 lanes)
+constexpr uint32_t kStreamRunBytes = 65536u;   // DENSE, dense rows as one stream: bytes of a run of rows (16 parts)
+
+PGENHIP_PLAN_HD constexpr bool dense_applicable(bool has_kept_list, uint32_t kept_count, uint32_t sample_count) { return !has_kept_list && kept_count == sample_count; }
+PGENHIP_PLAN_HD constexpr bool gather_applicable(bool has_kept_list, uint32_t kept_count) { return has_kept_list && kept_count >= 1u; }
+
+PGENHIP_PLAN_HD inline uint32_t general_grid(uint32_t n_variants, uint32_t kept_count, int num_cus, int blocks)
+{
+    return grid_blocks(((uint64_t)n_variants * ((kept_count + 3u) >> 2) + kThreads - 1u) / kThreads, kBlocksPerCu, num_cus, blocks);
+}
+
+struct GatherPlan {
+    uint32_t Q;       // output dwords of a row
+    uint64_t total;   // lanes' work items
+    uint32_t grid;
+};
+PGENHIP_PLAN_HD inline GatherPlan gather_plan(uint32_t n_variants, uint32_t kept_count, int num_cus, int blocks)
+{
+    GatherPlan p{};
+    p.Q = (kept_count + 15u) >> 4;
+    p.total = (uint64_t)n_variants * p.Q;
+    p.grid = grid_blocks((p.total + kThreads - 1u) / kThreads, kBlocksPerCu, num_cus, blocks);
+    return p;
+}
+
+struct DensePlan {
+    uint32_t G, P;    // lanes per row, passes per work item
+    uint32_t parts;   // work items of a row
+    uint64_t items;
+    uint32_t grid;
+};
+// lanes per row: as many as three passes over the row's chunks need; from 97 chunks a wave per row, cut into parts
+PGENHIP_PLAN_HD inline DensePlan dense_plan(uint32_t record_size, uint32_t n_variants, int num_cus, int blocks)
+{
+    DensePlan p{};
+    const uint32_t chunks = (record_size + 30u) / 16u;   // the most aligned chunks a destination row can touch
+    p.G = chunks <= 12u ? 4u : chunks <= 24u ? 8u : chunks <= 48u ? 16u : chunks <= 96u ? 32u : 64u;
+    p.P = p.G == 64u ? kPartChunks / 64u : 3u;
+    p.parts = (chunks + p.G * p.P - 1u) / (p.G * p.P);
+    const uint64_t row_groups = ((uint64_t)n_variants + 64u / p.G - 1u) / (64u / p.G);
+    p.items = row_groups * p.parts;
+    p.grid = grid_blocks((p.items + kThreads / 64 - 1u) / (kThreads / 64), kBlocksPerCu, num_cus, blocks);
+    return p;
+}
+
+// Dense records into dense output with no pad bits (N a multiple of 4) are one byte stream: runs of run_rows rows go as ONE row
+PGENHIP_PLAN_HD inline uint64_t run_rows(uint32_t record_size) { return kStreamRunBytes / record_size; }
+PGENHIP_PLAN_HD inline bool merge_runs(bool gathered, uint32_t sample_count, uint32_t record_size, uint64_t record_stride, uint64_t out_stride, uint32_t n_variants)
+{
+    const uint64_t m = run_rows(record_size);
+    return !gathered && (sample_count & 3u) == 0u && record_stride == record_size && out_stride == record_size && m >= 2u && n_variants >= 2u * m;
+}
+
+}  // namespace pack
+
+// ---- gt_spair, gt_gram: pairs of samples summed over rows --------------------------------------------------------------------------
+namespace sample_pairs {
+
+constexpr int kThreads = 256;              // lanes of a block; GENERAL owns one pair per lane
+constexpr uint32_t kTile = 64;             // ranks of a block tile, per operand
+constexpr uint32_t kMaxGridTiles = 1u << 20;   // tiles (pair blocks) side by side in the grid; a block strides over the rest
+constexpr uint32_t kMaxGridBlocks = 1u << 22;
+constexpr uint32_t kMinSliceRows = 256;    // rows a slice takes at least when the plan is not forced
+constexpr uint32_t kGeneralBlocksPerCu = 8;
+constexpr uint32_t kMfmaBlocksPerCu = 2;   // what the MFMA kernels are compiled for
+
+// row ranges of a launch: forced, or as many as bring the grid to the chip's resident blocks, of at least kMinSliceRows rows each;
+// never more than there are units of `unit_rows` rows (so no slice is empty), the grid stays below kMaxGridBlocks, and never fewer
+// than min_slices
+PGENHIP_PLAN_HD inline uint32_t pair_slices(uint32_t n_variants, uint64_t grid_items, int forced, int num_cus, uint32_t blocks_per_cu, uint32_t unit_rows,
+                                            uint64_t min_slices)
+{
+    const uint64_t target = cu_count(num_cus) * blocks_per_cu;
+    uint64_t s;
+    if (forced > 0) {
+        s = (uint64_t)forced;
+    } else {
+        s = std::max<uint64_t>(1u, target / grid_items);
+        s = std::min<uint64_t>(s, std::max<uint64_t>(1u, n_variants / kMinSliceRows));
+    }
+    s = std::min<uint64_t>(s, ((uint64_t)n_variants + unit_rows - 1u) / unit_rows);
+    s = std::min<uint64_t>(s, kMaxGridBlocks / grid_items);
+    return (uint32_t)std::max<uint64_t>(s, min_slices);
+}
+
+// MFMA: tiles of kTile x kTile ranks
+PGENHIP_PLAN_HD constexpr uint32_t range_tiles(uint32_t count) { return (count + kTile - 1u) / kTile; }
+PGENHIP_PLAN_HD constexpr uint64_t tiles(uint32_t a_count, uint32_t b_count) { return (uint64_t)range_tiles(a_count) * range_tiles(b_count); }
+PGENHIP_PLAN_HD inline uint32_t grid_tiles(uint32_t a_count, uint32_t b_count) { return (uint32_t)std::min<uint64_t>(tiles(a_count, b_count), kMaxGridTiles); }
+
+// GENERAL: blocks of kThreads pairs
+PGENHIP_PLAN_HD constexpr uint64_t pair_blocks(uint32_t a_count, uint32_t b_count) { return ((uint64_t)a_count * b_count + kThreads - 1u) / kThreads; }
+PGENHIP_PLAN_HD inline uint32_t grid_pairs(uint32_t a_count, uint32_t b_count) { return (uint32_t)std::min<uint64_t>(pair_blocks(a_count, b_count), kMaxGridTiles); }
+
+}  // namespace sample_pairs
+
+namespace spair {
+
+using namespace sample_pairs;
+constexpr uint32_t kStepRows = 64;         // rows of one MFMA step (the instruction's k)
+
+// a slice stays below 2^31 rows, so an i32 accumulator stays below its sign bit
+PGENHIP_PLAN_HD constexpr uint64_t min_slices(uint32_t n_variants) { return ((uint64_t)n_variants >> 30) + 1u; }
+
+PGENHIP_PLAN_HD inline uint32_t general_slices(uint32_t n_variants, uint32_t a_count, uint32_t b_count, int forced, int num_cus)
+{
+    return pair_slices(n_variants, grid_pairs(a_count, b_count), forced, num_cus, kGeneralBlocksPerCu, 1u, min_slices(n_variants));
+}
+PGENHIP_PLAN_HD inline uint32_t mfma_slices(uint32_t n_variants, uint32_t a_count, uint32_t b_count, int forced, int num_cus)
+{
+    return pair_slices(n_variants, grid_tiles(a_count, b_count), forced, num_cus, kMfmaBlocksPerCu, kStepRows, min_slices(n_variants));
+}
+
+}  // namespace spair
+
+namespace gram {
+
+using namespace sample_pairs;
+constexpr uint32_t kStepRows = 32;         // rows expanded per step: eight MFMA row groups
+constexpr uint32_t kGroupRows = 4;         // rows of one MFMA (the instruction's k)
+
+PGENHIP_PLAN_HD inline uint32_t general_slices(uint32_t n_variants, uint32_t a_count, uint32_t b_count, int forced, int num_cus)
+{
+    return pair_slices(n_variants, grid_pairs(a_count, b_count), forced, num_cus, kGeneralBlocksPerCu, 1u, 1u);
+}
+PGENHIP_PLAN_HD inline uint32_t mfma_slices(uint32_t n_variants, uint32_t a_count, uint32_t b_count, int forced, int num_cus)
+{
+    return pair_slices(n_variants, grid_tiles(a_count, b_count), forced, num_cus, kMfmaBlocksPerCu, kStepRows, 1u);
+}
+
+}  // namespace gram
+
+}  // namespace pgenhip::plan

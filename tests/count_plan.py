@@ -1,24 +1,17 @@
-"""The launch plan of the genotype-count kernel, restated from csrc/gt_count.hip so that the count tests can place their cells
-on both sides of every shape class and of every grid-stride boundary (the rows one grid covers, past which
-``gt_count_kernel`` runs its ``r0 += n_waves * kRowsPerStep`` loop again).
-
-Mirrors (keep in step; test_count_plan.py checks them against the source):
-  * ``kThreads``, ``kBlocksPerCu``;
-  * the chunk bound ``(R + 30) / 16`` and the lanes-per-row ladder of ``gt_count_lanes_per_row``;
-  * the ``<G, RU, U>`` instantiations ``launch_gt_count`` picks, forced kernels included;
-  * ``rows_per_block`` and the grid cap of ``launch_shape``.
+"""The launch plan of the genotype-count kernel, RUN from csrc/launch_plan.h (namespace plan::count) through tests/launch_plan.py
+rather than restated, so that the count tests can place their cells on both sides of every shape class and of every grid-stride
+boundary (the rows one grid covers, past which ``gt_count_kernel`` runs its ``r0 += n_waves * kRowsPerStep`` loop again).
+Only the helpers that lay out test sizes (``rows_per_grid``, ``CLASS_EDGES``) are Python, on top of probed values.
 """
 from __future__ import annotations
 
-THREADS = 256          # kThreads
-BLOCKS_PER_CU = 8      # kBlocksPerCu
+import launch_plan as L
+
+THREADS = L.CONST["count.kThreads"]
+BLOCKS_PER_CU = L.CONST["count.kBlocksPerCu"]
 WAVE = 64
 
 AUTO, WAVE_PER_ROW, ROWS_PER_WAVE = 0, 1, 2   # PGENHIP_COUNT_* (include/pgen_hip.h)
-
-# lanes per row -> (G, RU, U) of launch_gt_count's switch; 64 is the wave-per-row instantiation
-SHAPES = {4: (4, 2, 1), 8: (8, 2, 1), 16: (16, 2, 1), 32: (32, 2, 1), 64: (64, 1, 4)}
-LADDER = [(12, 4), (24, 8), (48, 16), (96, 32)]   # chunks <= bound -> lanes per row; above the last: 64
 
 
 def record_size(n: int) -> int:
@@ -27,46 +20,38 @@ def record_size(n: int) -> int:
 
 def max_chunks(r: int) -> int:
     """The most aligned 16-byte chunks a row of R bytes can touch."""
-    return (r + 30) // 16
+    return L.call("count_lanes_per_row", 2, r)[1]
 
 
 def lanes_per_row(r: int) -> int:
-    c = max_chunks(r)
-    for bound, g in LADDER:
-        if c <= bound:
-            return g
-    return 64
+    return L.call("count_lanes_per_row", 2, r)[0]
 
 
 def shape(n: int, kernel: int = AUTO):
     """(G, RU, U) that launch_gt_count runs for N samples under ``kernel``."""
-    g = lanes_per_row(record_size(n))
-    if kernel == WAVE_PER_ROW or (kernel == AUTO and g == 64):
-        return SHAPES[64]
-    return SHAPES[min(g, 32)]   # forced ROWS_PER_WAVE on long rows: G = 32, more passes per row
+    return L.call("count_shape", 4, record_size(n), kernel == WAVE_PER_ROW, kernel == ROWS_PER_WAVE)[1:]
 
 
 def rows_per_step(g: int, ru: int) -> int:
     """Rows one wave takes per iteration of the row loop (kRowsPerStep)."""
-    return (WAVE // g) * ru
+    return L.call("count_grid", 3, 1, g, ru, 0)[0]
 
 
 def rows_per_block(g: int, ru: int) -> int:
-    return (THREADS // WAVE) * rows_per_step(g, ru)
+    return L.call("count_grid", 3, 1, g, ru, 0)[1]
 
 
 def grid(n_variants: int, g: int, ru: int, num_cus: int) -> int:
-    blocks = -(-n_variants // rows_per_block(g, ru))
-    return min(blocks, (num_cus if num_cus > 0 else 256) * BLOCKS_PER_CU)
+    return L.call("count_grid", 3, n_variants, g, ru, num_cus)[2]
 
 
 def rows_per_grid(g: int, ru: int, num_cus: int) -> int:
     """Rows one full grid covers (S): rows past S are reached only through the grid-stride loop."""
-    return (num_cus if num_cus > 0 else 256) * BLOCKS_PER_CU * rows_per_block(g, ru)
+    return L.cu_count(num_cus) * BLOCKS_PER_CU * rows_per_block(g, ru)
 
 
 def passes(r: int, g: int, u: int) -> int:
-    return (max_chunks(r) + g * u - 1) // (g * u)
+    return L.call("count_passes", 1, r, g, u)[0]
 
 
 def _last_n_of_class():
@@ -81,3 +66,5 @@ def _last_n_of_class():
 
 
 CLASS_EDGES = _last_n_of_class()   # the last N of the 4 / 8 / 16 / 32 lanes-per-row classes: [708, 1476, 3012, 6084]
+# lanes per row -> the (G, RU, U) instantiation of that class under AUTO; 64 is the wave-per-row one
+SHAPES = {lanes_per_row(record_size(n)): shape(n) for n in CLASS_EDGES + [CLASS_EDGES[-1] + 1]}

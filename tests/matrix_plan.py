@@ -1,26 +1,24 @@
-"""The launch plan of the genotype-matrix kernels, restated from csrc/gt_matrix.hip and the dispatch in csrc/capi.hip so that the
-tests can place their cells on both sides of every edge: the 16-byte chunk of the STREAM shape (16 / 8 / 4 elements), its dense and
-per-row forms, the 128-variant x 512-sample block tile and 128-sample wave tile of the TILE shape, the grids one launch covers and
-the shape AUTO takes.
-
-Mirrors (keep in step; test_decode_matrix.py checks them against the source):
-  * ``kThreads``, ``kBlocksPerCu``, ``kTileVariants``, ``kWaveSamples``, ``kTileSamples``, ``kTileBlocksPerCu``;
-  * ``launch_gt_matrix_stream``: ``dense``, ``per_row``, ``total``, ``kLongRowBytes`` and the rows kernel's grid;
-  * ``launch_gt_matrix_tile``: ``v_tiles``, ``bands``;
-  * ``gt_matrix_stream_applicable`` / ``gt_matrix_tile_applicable`` and the order AUTO asks them in.
+"""The launch plan of the genotype-matrix kernels, RUN from csrc/launch_plan.h (namespace plan::matrix, which csrc/gt_matrix.hip and
+the dispatch in csrc/capi.hip call) through tests/launch_plan.py rather than restated, so that the tests can place their cells on
+both sides of every edge: the 16-byte chunk of the STREAM shape (16 / 8 / 4 elements), its dense and per-row forms, the 128-variant x
+512-sample block tile and 128-sample wave tile of the TILE shape, the grids one launch covers and the shape AUTO takes.  Only
+``N_EDGES`` and ``V_EDGES``, which lay out test sizes, are Python, on top of probed values.
 """
 from __future__ import annotations
 
-THREADS = 256
-BLOCKS_PER_CU = 8
-TILE_VARIANTS = 128
-WAVE_SAMPLES = 128
-TILE_SAMPLES = 512
-TILE_BLOCKS_PER_CU = 4
-CHUNK = 16
-LONG_ROW_BYTES = 4096    # kLongRowBytes: STREAM rows from this many output bytes take the rows kernel
+import launch_plan as L
 
-AUTO, GENERAL, STREAM, TILE = 0, 1, 2, 3     # PGENHIP_MATRIX_* (include/pgen_hip.h)
+THREADS = L.CONST["matrix.kThreads"]
+BLOCKS_PER_CU = L.CONST["matrix.kBlocksPerCu"]
+TILE_VARIANTS = L.CONST["matrix.kTileVariants"]
+WAVE_SAMPLES = L.CONST["matrix.kWaveSamples"]
+TILE_SAMPLES = L.CONST["matrix.kTileSamples"]
+TILE_BLOCKS_PER_CU = L.CONST["matrix.kTileBlocksPerCu"]
+CHUNK = 16
+LONG_ROW_BYTES = L.CONST["matrix.kLongRowBytes"]    # STREAM rows from this many output bytes take the rows kernel
+
+AUTO = 0                                            # PGENHIP_MATRIX_* (include/pgen_hip.h)
+GENERAL, STREAM, TILE = L.CONST["matrix.kGeneral"], L.CONST["matrix.kStream"], L.CONST["matrix.kTile"]
 SHAPE_MASK = 0xF
 SAMPLE_MAJOR = 0x10
 KNOB_MATRIX_BLOCKS = 18
@@ -32,58 +30,49 @@ def record_size(n: int) -> int:
 
 def auto_shape(all_kept: bool, sample_major: bool, out_addr: int, out_stride: int, k: int) -> int:
     """What PGENHIP_MATRIX_AUTO launches."""
-    if all_kept and not sample_major:
-        return STREAM
-    if all_kept and sample_major and out_addr % 16 == 0 and (out_stride % 16 == 0 or k <= 1):
-        return TILE
-    return GENERAL
+    return L.call("matrix_auto_shape", 3, all_kept, sample_major, out_addr % 16, out_stride, k)[0]
+
+
+def stream_plan(v, k, elem, out_addr, out_stride, cus=256, forced=0):
+    """(dense, long_rows, per_row, total, grid_x, grid_y) of a STREAM launch."""
+    return L.call("matrix_stream_plan", 6, v, k, elem, out_addr % 16, out_stride, cus, forced)
 
 
 def stream_dense(v: int, k: int, elem: int, out_stride: int) -> bool:
-    return v == 1 or out_stride == k * elem
+    return bool(stream_plan(v, k, elem, 0, out_stride)[0])
 
 
 def stream_chunks(v: int, k: int, elem: int, out_addr: int, out_stride: int) -> int:
     """Work items (one lane each) of a STREAM launch."""
-    row_bytes = k * elem
-    if stream_dense(v, k, elem, out_stride):
-        return (out_addr % 16 + row_bytes * v + 15) // 16
-    return ((row_bytes + 15) // 16 + 1) * v
+    return stream_plan(v, k, elem, out_addr, out_stride)[3]
 
 
 def stream_long_rows(k: int, elem: int) -> bool:
-    return k * elem >= LONG_ROW_BYTES
+    return bool(stream_plan(1, k, elem, 0, k * elem)[1])
 
 
 def stream_rows_grid(v: int, k: int, elem: int, cus: int = 256, forced: int = 0) -> tuple[int, int]:
     """(blocks along a row's chunks, blocks along the rows) of the long-row STREAM kernel."""
-    per_row = (k * elem + 15) // 16 + 1
-    gx = grid((per_row + THREADS - 1) // THREADS, BLOCKS_PER_CU, cus, 1 if forced > 0 else 0)
-    cap = forced if forced > 0 else cus * BLOCKS_PER_CU
-    return gx, min(v, max(1, cap // gx), 65535)
-
-
-def grid(work_blocks: int, per_cu: int, cus: int = 256, forced: int = 0) -> int:
-    cap = forced if forced > 0 else cus * per_cu
-    return max(1, min(work_blocks, cap))
+    assert stream_long_rows(k, elem)
+    return stream_plan(v, k, elem, 0, k * elem, cus, forced)[4:]
 
 
 def stream_grid(v, k, elem, out_addr, out_stride, cus=256, forced=0) -> int:
-    return grid((stream_chunks(v, k, elem, out_addr, out_stride) + THREADS - 1) // THREADS, BLOCKS_PER_CU, cus, forced)
+    """Blocks of the short-row STREAM kernel over the launch's chunks (rows below LONG_ROW_BYTES launch exactly this)."""
+    return L.grid_blocks((stream_chunks(v, k, elem, out_addr, out_stride) + THREADS - 1) // THREADS, BLOCKS_PER_CU, cus, forced)
 
 
 def general_grid(v, k, cus=256, forced=0) -> int:
-    return grid((v * k + THREADS - 1) // THREADS, BLOCKS_PER_CU, cus, forced)
+    return L.call("matrix_general_grid", 1, v, k, cus, forced)[0]
 
 
 def tile_counts(v: int, n: int) -> tuple[int, int]:
     """(variant tiles, sample bands); a launch walks bands x variant tiles, variant tile fastest."""
-    return (v + TILE_VARIANTS - 1) // TILE_VARIANTS, (n + TILE_SAMPLES - 1) // TILE_SAMPLES
+    return L.call("matrix_tile_plan", 4, v, n, 256, 0)[:2]
 
 
 def tile_grid(v, n, cus=256, forced=0) -> int:
-    vt, bands = tile_counts(v, n)
-    return grid(vt * bands, TILE_BLOCKS_PER_CU, cus, forced)
+    return L.call("matrix_tile_plan", 4, v, n, cus, forced)[3]
 
 
 # sample counts at the edges of the plan: the 16-sample lane piece and the 128-sample wave piece of TILE, its 512-sample band

@@ -1,18 +1,16 @@
-"""The launch plan of the per-sample score kernel, restated from csrc/gt_score.hip so that the tests can place their row counts on
-both sides of every edge it has: the bytes a lane owns (by the number of columns), the lanes-per-row ladder and the column tiles
-past 64 lanes, the rows a block has side by side, the batch of rows whose loads are issued together, and the row ranges (slices)
-a tile is cut into.
-
-Mirrors (keep in step; test_sample_scores.py checks them against the source):
-  * ``lane_bytes`` and ``batch_rows``;
-  * ``plan``: units, ``log_g``, tiles, the cap of the slices at one batch of every slot;
-  * the rows of a block, ``rbeg = V * slice / slices``.
+"""The launch plan of the per-sample score kernel, RUN from csrc/launch_plan.h (namespace plan::score) through tests/launch_plan.py
+rather than restated, so that the tests can place their row counts on both sides of every edge it has: the bytes a lane owns (by
+the number of columns), the lanes-per-row ladder and the column tiles past 64 lanes, the rows a block has side by side, the batch
+of rows whose loads are issued together, and the row ranges (slices) a tile is cut into.  Only ``edge_rows``, which lays out test
+sizes, is Python, on top of probed values.
 """
 from __future__ import annotations
 
-THREADS = 256
-WAVES = THREADS // 64
-MIN_SLICE_ROWS = 512    # kMinSliceRows (only when the slices are not forced)
+import launch_plan as L
+
+THREADS = L.CONST["score.kThreads"]
+WAVES = L.CONST["score.kWaves"]
+MIN_SLICE_ROWS = L.CONST["score.kMinSliceRows"]    # only when the slices are not forced
 
 AUTO, ROWS = 0, 1       # PGENHIP_SCORE_* (include/pgen_hip.h)
 ACCUMULATE = 0x10
@@ -23,34 +21,30 @@ def record_size(n: int) -> int:
     return (2 * n + 7) // 8
 
 
+def plan(n: int, c: int, v: int = 1, forced: int = 0, num_cus: int = 256):
+    """(lane_bytes, batch_rows, log_g, tiles, slices, slots) of a launch over V rows of N samples with C columns."""
+    return L.call("score_plan", 6, record_size(n), v, c, num_cus, forced)
+
+
 def lane_bytes(c: int) -> int:
-    return 4 if c <= 2 else 2 if c <= 4 else 1
+    return plan(1, c)[0]
 
 
 def batch_rows(c: int) -> int:
-    return 4 if c <= 4 else 2
-
-
-def units(n: int, c: int) -> int:
-    b = lane_bytes(c)
-    return (record_size(n) + b - 1) // b
+    return plan(1, c)[1]
 
 
 def lanes_per_row(n: int, c: int) -> int:
-    g = 1
-    while g < 64 and g < units(n, c):
-        g *= 2
-    return g
+    return 1 << plan(n, c)[2]
 
 
 def tiles(n: int, c: int) -> int:
-    g = lanes_per_row(n, c)
-    return (units(n, c) + g - 1) // g
+    return plan(n, c)[3]
 
 
 def slots(n: int, c: int) -> int:
     """Rows a block has side by side (4 waves x 64 / G groups)."""
-    return WAVES * (64 // lanes_per_row(n, c))
+    return plan(n, c)[5]
 
 
 def step_rows(n: int, c: int) -> int:
@@ -58,8 +52,8 @@ def step_rows(n: int, c: int) -> int:
     return slots(n, c) * batch_rows(c)
 
 
-def slices(n: int, c: int, v: int, forced: int) -> int:
-    return max(1, min(forced, (v + step_rows(n, c) - 1) // step_rows(n, c)))
+def slices(n: int, c: int, v: int, forced: int = 0, num_cus: int = 256) -> int:
+    return plan(n, c, v, forced, num_cus)[4]
 
 
 def edge_rows(n: int, c: int, forced: int) -> list[int]:

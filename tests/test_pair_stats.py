@@ -10,12 +10,12 @@ import numpy as np
 import pytest
 import torch
 
+import launch_plan as LP
 import pair_ref as PR
 import pgen_oracle as oracle
 from pgen_rs_amd import _capi
 
 REPO = Path(__file__).resolve().parent.parent
-SRC = REPO / "pgen_rs_amd" / "csrc" / "gt_pair.hip"
 
 
 def random_case(seed):
@@ -116,14 +116,8 @@ def test_header_documents_the_contract():
 
 
 def test_kernel_constants_the_gpu_tests_rely_on():
-    """tests/test_pair_stats_gpu.py places its N, V and W around these."""
-    src = SRC.read_text()
-    for line in [
-        "constexpr int kThreads = 64;",
-        "constexpr uint32_t kTile = 16;",
-        "constexpr uint32_t kChunkWords = 16;",
-    ]:
-        assert line in src, line
+    """tests/test_pair_stats_gpu.py places its N, V and W around these (csrc/launch_plan.h, run through tests/launch_plan.py)."""
+    assert (LP.CONST["pair.kThreads"], LP.CONST["pair.kTile"], LP.CONST["pair.kChunkWords"]) == (64, 16, 16)
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="only meaningful on a box without a GPU")

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import launch_plan as LP
 import pair_ref as PR
 import pgen_rs_amd
 from pgen_rs_amd import _capi
@@ -14,8 +15,8 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 SENT = -0x5A5A5A5B                      # 0xA5A5A5A5 as int32
 SENT_U = 0xA5A5A5A5
-TILE = 16                               # gt_pair.hip: kTile (pinned by tests/test_pair_stats.py)
-CHUNK = 32 * 16                         # samples per staged chunk: 32 * kChunkWords
+TILE = LP.CONST["pair.kTile"]            # gt_pair.hip's tile of rows, from csrc/launch_plan.h (16: pinned by tests/test_pair_stats.py)
+CHUNK = 32 * LP.CONST["pair.kChunkWords"]   # samples per staged chunk
 
 
 def keep_set(name, n):

@@ -56,19 +56,10 @@ def test_constants_and_header():
 
 
 def test_kernel_constants_the_gpu_tests_rely_on():
-    """tests/test_sample_gram_gpu.py places its N and V around these (tests/gram_plan.py mirrors them)."""
-    src = SRC.read_text()
-    for line in [
-        f"constexpr int kThreads = {GP.THREADS};",
-        f"constexpr uint32_t kTile = {GP.TILE};",
-        f"constexpr uint32_t kStepRows = {GP.STEP_ROWS};",
-        f"constexpr uint32_t kGroupRows = {GP.GROUP_ROWS};",
-        f"constexpr uint32_t kMinSliceRows = {GP.MIN_SLICE_ROWS};",
-        f"constexpr uint32_t kMaxGridTiles = 1u << {GP.MAX_GRID_TILES.bit_length() - 1};",
-        f"constexpr uint32_t kMaxGridBlocks = 1u << {GP.MAX_GRID_BLOCKS.bit_length() - 1};",
-        "__builtin_amdgcn_mfma_f64_16x16x4f64(",
-    ]:
-        assert line in src, line
+    """tests/test_sample_gram_gpu.py places its N and V around these (tests/gram_plan.py runs csrc/launch_plan.h for them)."""
+    assert (GP.THREADS, GP.TILE, GP.STEP_ROWS, GP.GROUP_ROWS, GP.MIN_SLICE_ROWS) == (256, 64, 32, 4, 256)
+    assert (GP.MAX_GRID_TILES, GP.MAX_GRID_BLOCKS) == (1 << 20, 1 << 22)
+    assert "__builtin_amdgcn_mfma_f64_16x16x4f64(" in SRC.read_text()
     assert GP.mfma_slices(1000, 70, 70, forced=7) == 7 and GP.mfma_slices(33, 70, 70, forced=7) == 2 and GP.mfma_slices(5, 70, 70) == 1
     assert GP.general_slices(1000, 70, 70, forced=7) == 7 and GP.general_slices(5, 70, 70, forced=7) == 5 and GP.general_slices(75, 130, 70) == 1
 

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import launch_plan as LP
 import pgen_oracle as oracle
 import spair_ref as XR
 from helpers import GOLDEN
@@ -108,15 +109,9 @@ def test_constants_and_header():
 
 
 def test_kernel_constants_the_gpu_tests_rely_on():
-    """tests/test_sample_pair_stats_gpu.py places its N and V around these."""
-    src = SRC.read_text()
-    for line in [
-        "constexpr int kThreads = 256;",
-        "constexpr uint32_t kTile = 64;",
-        "constexpr uint32_t kStepRows = 64;",
-        "__builtin_amdgcn_mfma_i32_16x16x64_i8(",
-    ]:
-        assert line in src, line
+    """tests/test_sample_pair_stats_gpu.py places its N and V around these (csrc/launch_plan.h, run through tests/launch_plan.py)."""
+    assert (LP.CONST["spair.kThreads"], LP.CONST["spair.kTile"], LP.CONST["spair.kStepRows"]) == (256, 64, 64)
+    assert "__builtin_amdgcn_mfma_i32_16x16x64_i8(" in SRC.read_text()
 
 
 # ---- `pgen-hip kinship` without a device ----

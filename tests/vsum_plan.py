@@ -1,21 +1,19 @@
-"""The launch plan of the matrix-core shape of the per-variant sums kernel, restated from csrc/gt_vsum.hip so that the tests can
-place their row and sample counts on both sides of every edge it has: the record bytes of a tile (one tile: every sum has one
-owner and is stored; more: tiles meet in FP64 atomics), the rows of one MFMA, the groups the waves of a block take in turn, and the
-row ranges (slices) a tile is cut into, which the grid-size knob forces.
-
-Mirrors (keep in step; test_variant_sums.py checks them against the source):
-  * ``kTileBytes``, ``kGroupRows``, ``kMinSliceRows``;
-  * ``plan``: tiles, the cap of the slices at one group per wave, the grid;
-  * the groups of a slice, ``gbeg = groups * slice / slices``.
+"""The launch plan of the matrix-core shape of the per-variant sums kernel, RUN from csrc/launch_plan.h (namespace plan::vsum) through
+tests/launch_plan.py rather than restated, so that the tests can place their row and sample counts on both sides of every edge it
+has: the record bytes of a tile (one tile: every sum has one owner and is stored; more: tiles meet in FP64 atomics), the rows of one
+MFMA, the groups the waves of a block take in turn, and the row ranges (slices) a tile is cut into, which the grid-size knob forces.
+Only ``edge_rows`` and ``edge_samples``, which lay out test sizes, are Python, on top of probed values.
 """
 from __future__ import annotations
 
-THREADS = 256
-WAVES = THREADS // 64
-TILE_BYTES = 32         # kTileBytes
+import launch_plan as L
+
+THREADS = L.CONST["vsum.kThreads"]
+WAVES = L.CONST["vsum.kWaves"]
+TILE_BYTES = L.CONST["vsum.kTileBytes"]
 TILE_SAMPLES = 4 * TILE_BYTES
-GROUP_ROWS = 4          # kGroupRows
-MIN_SLICE_ROWS = 256    # kMinSliceRows (only when the grid is not forced)
+GROUP_ROWS = L.CONST["vsum.kGroupRows"]
+MIN_SLICE_ROWS = L.CONST["vsum.kMinSliceRows"]    # only when the grid is not forced
 
 AUTO, GENERAL, MFMA = 0, 1, 2   # PGENHIP_VSUM_* (include/pgen_hip.h)
 MAX_COLUMNS = 16
@@ -25,21 +23,26 @@ def record_size(n: int) -> int:
     return (2 * n + 7) // 8
 
 
+def plan(n: int, v: int = 1, forced: int = 0, num_cus: int = 256):
+    """(tiles, slices, grid, atomic, groups) of an MFMA launch over V rows of N samples."""
+    return L.call("vsum_mfma_plan", 5, record_size(n), v, num_cus, forced)
+
+
 def tiles(n: int) -> int:
-    return (record_size(n) + TILE_BYTES - 1) // TILE_BYTES
+    return plan(n)[0]
 
 
 def groups(v: int) -> int:
-    return (v + GROUP_ROWS - 1) // GROUP_ROWS
+    return plan(1, v)[4]
 
 
-def slices(v: int, forced: int) -> int:
-    """Row ranges per tile with the grid forced to ``forced`` blocks: at most one per WAVES groups."""
-    return max(1, min(forced, (groups(v) + WAVES - 1) // WAVES))
+def slices(v: int, forced: int = 0, n: int = 1, num_cus: int = 256) -> int:
+    """Row ranges per tile (``forced``: the grid forced to that many blocks; at most one slice per WAVES groups)."""
+    return plan(n, v, forced, num_cus)[1]
 
 
-def grid(n: int, v: int, forced: int) -> int:
-    return min(tiles(n) * slices(v, forced), forced)
+def grid(n: int, v: int, forced: int = 0, num_cus: int = 256) -> int:
+    return plan(n, v, forced, num_cus)[2]
 
 
 def edge_rows(forced: int) -> list[int]:
