@@ -496,6 +496,54 @@ int pgenhip_sample_gram_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t 
                            const double *d_code_values, uint32_t a_begin, uint32_t a_count, uint32_t b_begin, uint32_t b_count,
                            double *d_out, uint64_t out_stride, uint32_t flags);
 
+/* ---- Gram product (device-resident, asynchronous on the ctx stream) ----
+ * (Z^T Z) Q without Z^T Z: what an eigen-solver iterates (principal components) when the K x K matrix of pgenhip_sample_gram does not
+ * fit.  Rows are selected exactly as in pgenhip_sample_gram / _at (by stride with record_stride >= R or n_variants <= 1, through
+ * d_variant_idx, or through d_record_off; any byte alignment; a gather that repeats a row adds it twice).  With
+ *     Z[j][k] = t_j[x_j(k)]
+ * where x_j(k) is the 2-bit code, in selected row j, of the sample of rank k in the ctx's kept list (0 hom-ref, 1 het, 2 hom-alt,
+ * 3 missing) and t_j = d_code_values[4*j .. 4*j+3] (the table argument of pgenhip_sample_gram: a DEVICE array of FP64 indexed by the
+ * row's POSITION IN THE SELECTION, not interpreted by the library), the call computes over ALL K kept samples
+ *     d_proj[j * n_columns + c] = P[j][c] = sum over k of Z[j][k] * d_q[k * q_stride + c]        (always overwritten)
+ *     d_out[k * out_stride + c] = Y[k][c] = sum over j of Z[j][k] * P[j][c]
+ * for c < n_columns <= PGENHIP_GAPPLY_MAX_COLUMNS.  q_stride and out_stride are in doubles, >= n_columns (or K <= 1).  d_proj, the
+ * variants' projections, is a documented output: rows are the unit a host blocks over, as in pgenhip_variant_sums, and it is the only
+ * intermediate, so no hidden scratch exists.  The pad bits of a record's last byte and samples >= N are never read as samples.
+ *   - Arithmetic.  Every product and every addition is FP64; there are no f32 partial sums.  The order of the additions is not fixed
+ *     (samples and rows are dealt to lanes, blocks and accumulator chains, which meet in atomics).  To first order, with room to
+ *     spare: P[j][c] is within (K + 1) * 2^-53 * sum over k of |Z[j][k] * q[k][c]| of the exact sum, and Y[k][c] is within
+ *     (n_variants + K + 4) * 2^-53 * B(k, c) of it, B(k, c) = sum over j of |Z[j][k]| * sum over k' of |Z[j][k'] * q[k'][c]|.  Sums
+ *     whose every partial sum is an integer below 2^53 are exact in any order.  Non-finite input gives unspecified results.  Bitwise
+ *     run-to-run reproducibility is not promised.
+ *   - Without PGENHIP_GAPPLY_ACCUMULATE the call overwrites exactly the K x n_columns entries of d_out (zeros when n_variants == 0).
+ *     With it Y is added to what d_out holds, so a host sums blocks of rows in place; n_variants == 0 is then a no-op.  Row padding
+ *     and everything else are not touched.  K == 0 writes zeros to d_proj and nothing to d_out.
+ *   - d_out and d_proj must be ORDINARY device memory (hipMalloc, pgenhip_device_malloc), not fine-grained or host-mapped memory:
+ *     the kernels add with hardware FP64 atomics, which such memory does not serve.  d_q, d_proj and d_out must not overlap.
+ *   - PGENHIP_ERR_BAD_ARG: n_columns 0 or above 16; q_stride < n_columns or out_stride < n_columns with K > 1; d_code_values, d_q,
+ *     d_proj or d_out NULL or not 8-byte aligned where at least one element would be read or written; unknown flag bits or shape
+ *     ids.  PGENHIP_ERR_TOO_LARGE, before any launch: K * q_stride * 8, K * out_stride * 8 or n_variants * n_columns * 8 of 2^52 or
+ *     more, and the record byte offsets that pgenhip_decode_matrix refuses.  Nothing is written or launched on a refusal.  (With a
+ *     32-bit n_variants and at most 16 columns n_variants * n_columns * 8 stays below 2^40: that refusal cannot be reached through
+ *     this ABI version and no test can provoke it; it is stated, and checked, for the day either type widens.)
+ * Same launch contract as pgenhip_sample_gram: device pointers only, no allocation, no synchronisation, queued on the ctx stream,
+ * graph-capturable (zeroing memsets ahead of two kernels).  The kernels use no work-queue counters, so these launches do not count
+ * against PGENHIP_LAUNCHES_IN_FLIGHT.
+ * flags: a shape (PGENHIP_GAPPLY_AUTO or a forced one; both take every legal call) | PGENHIP_GAPPLY_ACCUMULATE. */
+#define PGENHIP_GAPPLY_MAX_COLUMNS 16u
+#define PGENHIP_GAPPLY_AUTO 0u
+#define PGENHIP_GAPPLY_GENERAL 1u     /* correctness baseline, any shape */
+#define PGENHIP_GAPPLY_MFMA 2u        /* v_mfma_f64_16x16x4_f64 in both passes */
+#define PGENHIP_GAPPLY_SHAPE_MASK 0xFu
+#define PGENHIP_GAPPLY_ACCUMULATE 0x10u
+int pgenhip_gram_apply(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                       uint32_t n_variants, const double *d_code_values, const double *d_q, uint64_t q_stride,
+                       uint32_t n_columns, double *d_proj, double *d_out, uint64_t out_stride, uint32_t flags);
+/* Same, with the record of row j at d_base + d_record_off[j] (DEVICE array of u64 byte offsets). */
+int pgenhip_gram_apply_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
+                          const double *d_code_values, const double *d_q, uint64_t q_stride, uint32_t n_columns,
+                          double *d_proj, double *d_out, uint64_t out_stride, uint32_t flags);
+
 /* ---- packed records of the kept samples (device-resident, asynchronous on the ctx stream) ----
  * The selection written back as records: row j of the output is the mode-0x02 record of a K-sample file that holds the ctx's kept
  * samples of selected row j, so a host that puts the 12-byte header in front has a .pgen of the subset (src/pfile.rs:172-175 read
@@ -558,6 +606,8 @@ typedef enum pgenhip_knob {
     PGENHIP_KNOB_VSUM_BLOCKS = 23,       /* per-variant sums: grid size in blocks (default 0 = by shape: the work, capped at 8 blocks per CU); the MFMA shape also cuts the rows into that many slices, so tests force small grids and the multi-block combine */
     PGENHIP_KNOB_STORE_POLICY = 24,      /* stream kernel (row items, full lines through it, RUNS): how the text is stored. 0 (default) the measured rule: non-temporal write-through stores (sc1 nt: the line leaves the L2 with the store) on launches of more than 1 GB of text whose rows span several 16-KiB work items, or one and up to 4.5 GB; non-temporal stores elsewhere. 1 non-temporal stores everywhere, 2 write-through stores everywhere (tests force both at small sizes; A/B probes); other values are refused. The other emit kernels store as before whatever the value */
     PGENHIP_KNOB_GRAM_SLICES = 25,       /* sample Gram matrix: row ranges per rank tile, each summed by one block (default 0 = by shape: as many as fill the chip's resident blocks, of at least 256 rows each); tests put the row count on either side of every slice edge */
+    PGENHIP_KNOB_GAPPLY_SAMPLE_SLICES = 26, /* Gram product, P pass: sample ranges per row tile, each summed by one block (default 0 = by shape: as many as fill the chip's resident blocks, of at least 4096 samples each); tests put the sample count on either side of every slice edge */
+    PGENHIP_KNOB_GAPPLY_ROW_SLICES = 27, /* Gram product, Y pass: row ranges per sample tile, each summed by one block (default 0 = by shape: as many as fill the chip's resident blocks, of at least 256 rows each); tests put the row count on either side of every slice edge */
     PGENHIP_KNOB_RUNS_ROWS = 7       /* RUNS kernel: rows per work item (default: as many as one wide load / one span holds) */
 } pgenhip_knob;
 int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value);

@@ -68,6 +68,12 @@ GRAM_GENERAL = 1
 GRAM_MFMA = 2
 GRAM_SHAPE_MASK = 0xF
 GRAM_ACCUMULATE = 0x10
+GAPPLY_MAX_COLUMNS = 16
+GAPPLY_AUTO = 0
+GAPPLY_GENERAL = 1
+GAPPLY_MFMA = 2
+GAPPLY_SHAPE_MASK = 0xF
+GAPPLY_ACCUMULATE = 0x10
 MATRIX_AUTO = 0
 MATRIX_GENERAL = 1
 MATRIX_STREAM = 2
@@ -106,6 +112,8 @@ KNOB_SPAIR_SLICES = 22
 KNOB_VSUM_BLOCKS = 23
 KNOB_STORE_POLICY = 24
 KNOB_GRAM_SLICES = 25
+KNOB_GAPPLY_SAMPLE_SLICES = 26
+KNOB_GAPPLY_ROW_SLICES = 27
 
 
 
@@ -159,6 +167,8 @@ PROTOTYPES = {
     "pgenhip_sample_pair_stats_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_sample_gram": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32]),
     "pgenhip_sample_gram_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32]),
+    "pgenhip_gram_apply": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]),
+    "pgenhip_gram_apply_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]),
     "pgenhip_pair_stats": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_pair_stats_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_packed_record_size": (C.c_uint32, [ctx_p]),

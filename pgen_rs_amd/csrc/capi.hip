@@ -1013,6 +1013,80 @@ int pgenhip_sample_gram_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t 
                             out_stride, flags);
 }
 
+static int gram_apply_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                           const uint64_t *d_record_off, uint32_t n_variants, const double *d_code_values, const double *d_q,
+                           uint64_t q_stride, uint32_t n_columns, double *d_proj, double *d_out, uint64_t out_stride, uint32_t flags)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (flags & ~(PGENHIP_GAPPLY_SHAPE_MASK | PGENHIP_GAPPLY_ACCUMULATE)) return fail(PGENHIP_ERR_BAD_ARG, "unknown gram_apply flag");
+    const uint32_t shape = flags & PGENHIP_GAPPLY_SHAPE_MASK;
+    if (shape > PGENHIP_GAPPLY_MFMA) return fail(PGENHIP_ERR_BAD_ARG, "gram_apply supports shapes AUTO, GENERAL and MFMA");
+    const bool accumulate = (flags & PGENHIP_GAPPLY_ACCUMULATE) != 0u;
+    if (n_columns == 0u || n_columns > PGENHIP_GAPPLY_MAX_COLUMNS) return fail(PGENHIP_ERR_BAD_ARG, "n_columns must be 1 .. 16");
+    const uint64_t K = ctx->kept_count, C = n_columns;
+    if (K > 1u && q_stride < C) return fail(PGENHIP_ERR_BAD_ARG, "q_stride < n_columns");
+    if (K > 1u && out_stride < C) return fail(PGENHIP_ERR_BAD_ARG, "out_stride < n_columns");
+    // what is read or written: tables and q with rows and samples, proj with rows, out with samples
+    const bool rows = n_variants != 0u, samples = K != 0u;
+    if (rows && samples && (!d_code_values || ((uintptr_t)d_code_values & 7u))) return fail(PGENHIP_ERR_BAD_ARG, "d_code_values is NULL or not 8-byte aligned");
+    if (rows && samples && (!d_q || ((uintptr_t)d_q & 7u))) return fail(PGENHIP_ERR_BAD_ARG, "d_q is NULL or not 8-byte aligned");
+    if (rows && (!d_proj || ((uintptr_t)d_proj & 7u))) return fail(PGENHIP_ERR_BAD_ARG, "d_proj is NULL or not 8-byte aligned");
+    if (samples && !(accumulate && !rows) && (!d_out || ((uintptr_t)d_out & 7u))) return fail(PGENHIP_ERR_BAD_ARG, "d_out is NULL or not 8-byte aligned");
+    // byte offsets of entries, tables and records are 64-bit arithmetic in the kernels; the bounds are decode_matrix's (2^52 bytes)
+    if ((K > 1u && (q_stride >= kMaxSpan / 8u / K || out_stride >= kMaxSpan / 8u / K)) || (uint64_t)n_variants * C * 8u >= kMaxSpan ||
+        record_span_too_large(record_stride, d_variant_idx, d_record_off, n_variants))
+        return fail(PGENHIP_ERR_TOO_LARGE, "gram_apply offsets do not fit the kernels' index types");
+    GapplyArgs a;
+    rc = select_rows(ctx, a, d_records, record_stride, d_variant_idx, d_record_off, n_variants);
+    if (rc) return rc;
+    if (!samples) {   // no sample: every projection is an empty sum, and there is no Y
+        if (rows) HIP_TRY(hipMemsetAsync(d_proj, 0, 8u * (size_t)n_variants * C, ctx->stream));
+        return PGENHIP_OK;
+    }
+    a.kept_idx = (!ctx->subset || ctx->identity) ? nullptr : ctx->d_kept;
+    a.kept_count = (uint32_t)K;
+    a.code_values = d_code_values;
+    a.q = d_q;
+    a.q_stride = K > 1u ? q_stride : C;
+    a.n_columns = n_columns;
+    a.proj = d_proj;
+    a.out = d_out;
+    a.out_stride = K > 1u ? out_stride : C;
+    // AUTO: the matrix-core shape
+    const bool mfma = shape != PGENHIP_GAPPLY_GENERAL;
+    if (!rows) {
+        if (!accumulate) HIP_TRY(hipMemset2DAsync(d_out, 8u * (size_t)a.out_stride, 0, 8u * (size_t)C, K, ctx->stream));
+        return PGENHIP_OK;
+    }
+    const plan::gapply::Plan p = plan::gapply::plan(n_variants, (uint32_t)K, n_columns, mfma, ctx->tune.gapply_sample_slices, ctx->tune.gapply_row_slices, ctx->num_cus);
+    // a pass with one slice that overwrites: every entry has one owner and is stored.  Else the kernels only add, to zeros or to what is there
+    a.p_store = p.sample_slices == 1u ? 1u : 0u;
+    a.y_store = (!accumulate && p.row_slices == 1u) ? 1u : 0u;
+    if (!a.p_store) HIP_TRY(hipMemsetAsync(d_proj, 0, 8u * (size_t)n_variants * C, ctx->stream));
+    if (!accumulate && !a.y_store) HIP_TRY(hipMemset2DAsync(d_out, 8u * (size_t)a.out_stride, 0, 8u * (size_t)C, K, ctx->stream));
+    HIP_TRY(launch_gt_gapply_p(a, mfma, p.p_tiles, p.p_grid, p.sample_slices, ctx->stream));
+    HIP_TRY(launch_gt_gapply_y(a, mfma, p.y_tiles, p.y_grid, p.row_slices, ctx->stream));
+    return PGENHIP_OK;
+}
+
+int pgenhip_gram_apply(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                       uint32_t n_variants, const double *d_code_values, const double *d_q, uint64_t q_stride,
+                       uint32_t n_columns, double *d_proj, double *d_out, uint64_t out_stride, uint32_t flags)
+{
+    return gram_apply_core(ctx, d_records, record_stride, d_variant_idx, nullptr, n_variants, d_code_values, d_q, q_stride, n_columns,
+                           d_proj, d_out, out_stride, flags);
+}
+
+int pgenhip_gram_apply_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
+                          const double *d_code_values, const double *d_q, uint64_t q_stride, uint32_t n_columns,
+                          double *d_proj, double *d_out, uint64_t out_stride, uint32_t flags)
+{
+    if (const int rc = check_record_off(ctx, d_record_off, n_variants)) return rc;
+    return gram_apply_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, d_code_values, d_q, q_stride, n_columns, d_proj, d_out,
+                           out_stride, flags);
+}
+
 static int pack_records_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
                              const uint64_t *d_record_off, uint32_t n_variants, void *d_out, uint64_t out_stride,
                              const uint8_t *code_map, uint32_t flags)
@@ -1103,6 +1177,8 @@ int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)
         case PGENHIP_KNOB_SPAIR_SLICES: t.spair_slices = value > 0 ? value : d.spair_slices; break;
         case PGENHIP_KNOB_VSUM_BLOCKS: t.vsum_blocks = value > 0 ? value : d.vsum_blocks; break;
         case PGENHIP_KNOB_GRAM_SLICES: t.gram_slices = value > 0 ? value : d.gram_slices; break;
+        case PGENHIP_KNOB_GAPPLY_SAMPLE_SLICES: t.gapply_sample_slices = value > 0 ? value : d.gapply_sample_slices; break;
+        case PGENHIP_KNOB_GAPPLY_ROW_SLICES: t.gapply_row_slices = value > 0 ? value : d.gapply_row_slices; break;
         case PGENHIP_KNOB_STORE_POLICY:
             if (value < 0 || value > 2) return fail(PGENHIP_ERR_BAD_ARG, "store policy must be 0 (rule), 1 (nt) or 2 (nt sc1)");
             t.store_policy = value;

@@ -60,6 +60,8 @@ struct Tuning {
     int spair_slices = 0;          // pairwise sample tables: row ranges per sample tile (0 = by shape: the chip's resident blocks, at least 256 rows each)
     int vsum_blocks = 0;           // per-variant sums: grid size in blocks (0 = by shape, capped per CU)
     int gram_slices = 0;           // sample Gram matrix: row ranges per rank tile (0 = by shape: the chip's resident blocks, at least 256 rows each)
+    int gapply_sample_slices = 0;  // Gram product, P pass: sample ranges per row tile (0 = by shape: the chip's resident blocks, at least 4096 samples each)
+    int gapply_row_slices = 0;     // Gram product, Y pass: row ranges per sample tile (0 = by shape: the chip's resident blocks, at least 256 rows each)
     int store_policy = 0;          // stream kernel (row items, LINES, RUNS): how text is stored (0 = the measured rule of launch_gt_wide, 1 = nt, 2 = nt sc1, write-through)
 };
 
@@ -226,6 +228,26 @@ struct GramArgs : RowSource {
 // slices: row ranges per tile (plan::gram::general_slices / mfma_slices); 1 means every entry has one owner
 hipError_t launch_gt_gram_general(const GramArgs &a, uint32_t slices, hipStream_t stream);
 hipError_t launch_gt_gram_mfma(const GramArgs &a, uint32_t slices, hipStream_t stream);
+
+// Gram product (gt_gapply.hip): with Z[j][k] = t_j[x_j(k)] over the selected rows j and ALL kept samples k (ranks), the P pass gives
+// proj[j * n_columns + c] = sum over k of Z[j][k] * q[k * q_stride + c] and the Y pass out[k * out_stride + c] = sum over j of
+// Z[j][k] * proj[j * n_columns + c].  A pass with one slice that overwrites stores; everything else ADDS with FP64 atomics (the caller
+// zeroes first unless it accumulates).
+struct GapplyArgs : RowSource {
+    const uint32_t *kept_idx;     // device or nullptr (all samples, or an identity list): rank -> sample
+    uint32_t kept_count;          // K >= 1
+    const double *code_values;    // device, 8-byte aligned, four per selected row
+    const double *q;              // device, 8-byte aligned, K rows of n_columns
+    uint64_t q_stride;            // doubles between the rows of q
+    uint32_t n_columns;           // C, 1 .. 16
+    double *proj;                 // device, 8-byte aligned, n_variants x n_columns, ordinary device memory (hardware FP64 atomics)
+    double *out;                  // device, 8-byte aligned, ordinary device memory
+    uint64_t out_stride;          // doubles between the rows of out
+    uint32_t p_store, y_store;    // 1: the pass has one slice (and out is overwritten): every entry has one owner and is stored
+};
+// tiles / grid / slices of each pass: plan::gapply::plan of the same shape
+hipError_t launch_gt_gapply_p(const GapplyArgs &a, bool mfma, uint64_t tiles, uint32_t grid_tiles, uint32_t slices, hipStream_t stream);
+hipError_t launch_gt_gapply_y(const GapplyArgs &a, bool mfma, uint64_t tiles, uint32_t grid_tiles, uint32_t slices, hipStream_t stream);
 
 // Packed records (gt_pack.hip): row j = the mode-0x02 record of the K kept samples of selected row j, ceil(K / 4) bytes at
 // out + j * out_stride, every code sent through a 2-bit -> 2-bit map, pad bits zero.

@@ -1,7 +1,7 @@
 // launch_plan.h — the launch plans of the analysis kernels (gt_count, gt_scount, gt_score, gt_vsum, gt_matrix, gt_pair, gt_pack,
-// gt_spair, gt_gram): lanes per row, tiles, row ranges ("slices") and grid caps, as functions of scalars.  The single statement of
-// every plan: the launchers call it, the kernels take their constants and their row ranges from it, and the tests compile this
-// header for the host (tests/plan_probe.cpp) and run it.  Plain C++17 on purpose: no HIP header, no argument struct.
+// gt_spair, gt_gram, gt_gapply): lanes per row, tiles, row ranges ("slices") and grid caps, as functions of scalars.  The single statement
+// of every plan: the launchers call it, the kernels take their constants and their row ranges from it, and the tests compile this
+// header for the host (tests/plan_probe.cpp, tests/gapply_plan_probe.cpp) and run it.  Plain C++17 on purpose: no HIP header, no argument struct.
 #pragma once
 #include <stdint.h>
 
@@ -459,5 +459,70 @@ PGENHIP_PLAN_HD inline uint32_t mfma_slices(uint32_t n_variants, uint32_t a_coun
 }
 
 }  // namespace gram
+
+// ---- gt_gapply: Z^T (Z Q) in two passes ----------------------------------------------------------------------------------------------
+namespace gapply {
+
+constexpr int kThreads = 256;
+constexpr uint32_t kWaves = kThreads / 64;
+constexpr uint32_t kGroup = 4;               // the k of one v_mfma_f64_16x16x4_f64: samples in the P pass, rows in the Y pass
+constexpr uint32_t kRowTile = 64;            // P pass, MFMA: rows of a block (16 per wave), which share every staged tile of Q
+constexpr uint32_t kStepSamples = 64;        // P pass: samples of one staged tile of Q; also the unit sample slices are cut in
+constexpr uint32_t kSampleTile = 256;        // Y pass, MFMA: samples of a block (64 per wave)
+constexpr uint32_t kStepRows = 64;           // Y pass, MFMA: rows of one staged tile of P (and of their tables)
+constexpr uint32_t kMinSliceSamples = 4096;  // samples a P-pass slice takes at least when the plan is not forced
+constexpr uint32_t kMinSliceRows = 256;      // rows a Y-pass slice takes at least when the plan is not forced
+constexpr uint32_t kMaxGridTiles = 1u << 20;   // tiles side by side in the grid; a block strides over the rest
+constexpr uint32_t kMaxGridBlocks = 1u << 22;
+constexpr uint32_t kGeneralBlocksPerCu = 8;
+constexpr uint32_t kMfmaBlocksPerCu = 2;
+
+// ranges the reduction dimension of a pass is cut into: forced, or as many as bring the grid to the chip's resident blocks, of at
+// least min_slice each; never more than there are units (so no range is empty), and the grid stays below kMaxGridBlocks
+PGENHIP_PLAN_HD inline uint32_t cut(uint64_t extent, uint32_t unit, uint32_t min_slice, uint64_t grid_tiles, int forced, int num_cus, uint32_t per_cu)
+{
+    const uint64_t target = cu_count(num_cus) * per_cu;
+    uint64_t s;
+    if (forced > 0) {
+        s = (uint64_t)forced;
+    } else {
+        s = std::max<uint64_t>(1u, target / grid_tiles);
+        s = std::min<uint64_t>(s, std::max<uint64_t>(1u, extent / min_slice));
+    }
+    s = std::min<uint64_t>(s, (extent + unit - 1u) / unit);
+    s = std::min<uint64_t>(s, kMaxGridBlocks / grid_tiles);
+    return (uint32_t)std::max<uint64_t>(s, 1u);
+}
+
+// samples [begin, end) of slice `slice` of the P pass: whole units of kStepSamples, the last one ends at K
+PGENHIP_PLAN_HD inline RowRange slice_samples(uint64_t K, uint32_t slice, uint32_t slices)
+{
+    const RowRange u = slice_rows((K + kStepSamples - 1u) / kStepSamples, slice, slices);
+    return {u.begin * kStepSamples, std::min<uint64_t>(u.end * kStepSamples, K)};
+}
+
+struct Plan {
+    uint64_t p_tiles, y_tiles;         // P pass: row tiles (MFMA) or blocks of (row, column) waves (GENERAL); Y pass: sample tiles or entry blocks
+    uint32_t p_grid, y_grid;           // tiles side by side in the grid
+    uint32_t sample_slices, row_slices;   // the grids are p_grid * sample_slices and y_grid * row_slices blocks
+};
+
+// n_variants, kept_count, n_columns >= 1
+PGENHIP_PLAN_HD inline Plan plan(uint32_t n_variants, uint32_t kept_count, uint32_t n_columns, bool mfma, int forced_sample_slices, int forced_row_slices,
+                                 int num_cus)
+{
+    Plan p{};
+    const uint64_t V = n_variants, K = kept_count, C = n_columns;
+    p.p_tiles = mfma ? (V + kRowTile - 1u) / kRowTile : (V * C + kWaves - 1u) / kWaves;
+    p.y_tiles = mfma ? (K + kSampleTile - 1u) / kSampleTile : (K * C + kThreads - 1u) / kThreads;
+    p.p_grid = (uint32_t)std::min<uint64_t>(p.p_tiles, kMaxGridTiles);
+    p.y_grid = (uint32_t)std::min<uint64_t>(p.y_tiles, kMaxGridTiles);
+    const uint32_t per_cu = mfma ? kMfmaBlocksPerCu : kGeneralBlocksPerCu;
+    p.sample_slices = cut(K, kStepSamples, kMinSliceSamples, p.p_grid, forced_sample_slices, num_cus, per_cu);
+    p.row_slices = cut(V, mfma ? kStepRows : 1u, kMinSliceRows, p.y_grid, forced_row_slices, num_cus, per_cu);
+    return p;
+}
+
+}  // namespace gapply
 
 }  // namespace pgenhip::plan

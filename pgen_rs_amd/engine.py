@@ -796,6 +796,73 @@ class GtEngine:
             raise ValueError(f"out must be a float64 tensor with >= {need} entries")
         return a, b, out.view(-1), out_stride
 
+    # -- Gram product -------------------------------------------------------------------------------
+    def gram_apply(self, records: torch.Tensor, code_values: torch.Tensor, q: torch.Tensor, *, record_stride: Optional[int] = None,
+                   variant_idx: Optional[torch.Tensor] = None, n_variants: Optional[int] = None, proj: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None, out_stride: Optional[int] = None, accumulate: bool = False,
+                   kernel: int = _capi.GAPPLY_AUTO, records_offset: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+        """``(Z^T Z) q`` without ``Z^T Z``: with ``Z[j, k] = code_values[j, code of the sample of rank k in row j]`` over the selected
+        rows and all K kept samples, returns ``(proj, out)``: ``proj = Z q`` as a float64 ``(n_variants, C)`` CUDA view (always
+        overwritten) and ``out = Z^T proj`` as a float64 ``(K, C)`` CUDA view.
+
+        ``code_values``: float64 CUDA tensor ``(n_variants, 4)``, contiguous, indexed by the row's position in the selection.
+        ``q``: float64 CUDA tensor ``(K, C)`` with unit column stride, C <= 16 (its row stride is passed on).  Rows are selected as in
+        ``sample_counts``.  ``proj``: optional float64 CUDA tensor of >= n_variants * C entries.  ``out``: optional float64 CUDA
+        tensor of >= (K - 1) * out_stride + C entries (written from its first element; row padding and everything else are
+        untouched); ``out_stride``: doubles between its rows (default C).  ``accumulate``: add to what ``out`` holds instead of
+        overwriting it.  ``kernel``: a forced shape (``_capi.GAPPLY_*``)."""
+        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
+        q_stride, c, proj, out, out_stride = self._gapply_out(code_values, q, n_variants, proj, out, out_stride, accumulate)
+        check(lib.pgenhip_gram_apply(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants,
+                                     _ptr(code_values), _ptr(q), q_stride, c, _ptr(proj), _ptr(out), out_stride,
+                                     kernel | (_capi.GAPPLY_ACCUMULATE if accumulate else 0)), "pgenhip_gram_apply")
+        return proj[: n_variants * c].view(n_variants, c), torch.as_strided(out, (self.kept_count, c), (out_stride, 1))
+
+    def gram_apply_at(self, base: torch.Tensor, record_off: torch.Tensor, code_values: torch.Tensor, q: torch.Tensor, *,
+                      n_variants: Optional[int] = None, proj: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                      out_stride: Optional[int] = None, accumulate: bool = False,
+                      kernel: int = _capi.GAPPLY_AUTO) -> tuple[torch.Tensor, torch.Tensor]:
+        """``gram_apply`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
+        n_variants = self._rows_at(base, record_off, n_variants)
+        q_stride, c, proj, out, out_stride = self._gapply_out(code_values, q, n_variants, proj, out, out_stride, accumulate)
+        check(lib.pgenhip_gram_apply_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, _ptr(code_values), _ptr(q), q_stride, c,
+                                        _ptr(proj), _ptr(out), out_stride, kernel | (_capi.GAPPLY_ACCUMULATE if accumulate else 0)),
+              "pgenhip_gram_apply_at")
+        return proj[: n_variants * c].view(n_variants, c), torch.as_strided(out, (self.kept_count, c), (out_stride, 1))
+
+    def _gapply_out(self, code_values: torch.Tensor, q: torch.Tensor, n_variants: int, proj: Optional[torch.Tensor],
+                    out: Optional[torch.Tensor], out_stride: Optional[int], accumulate: bool):
+        """(q's row stride, C, the flat proj and out: given, or allocated, out's row stride in doubles)"""
+        k = self.kept_count
+        self._check_dev(code_values, "code_values")
+        if code_values.dtype != torch.float64 or code_values.numel() < 4 * n_variants:
+            raise ValueError("code_values must be a float64 tensor of shape (n_variants, 4)")
+        if not q.is_cuda or q.device.index != self.device:   # (not _check_dev: q may be a view with padded rows)
+            raise ValueError(f"q must live on cuda:{self.device}")
+        if q.dtype != torch.float64 or q.dim() != 2 or q.shape[0] != k or not 1 <= q.shape[1] <= _capi.GAPPLY_MAX_COLUMNS:
+            raise ValueError(f"q must be a float64 tensor of shape (K = {k}, 1 .. {_capi.GAPPLY_MAX_COLUMNS})")
+        c = q.shape[1]
+        if k and q.stride(1) != 1 or k > 1 and q.stride(0) < c:
+            raise ValueError("q must have unit column stride and a row stride >= its column count")
+        q_stride = q.stride(0) if k > 1 else c
+        if out_stride is None:
+            out_stride = c
+        if proj is None:
+            proj = torch.empty(max(n_variants * c, 1), dtype=torch.float64, device=self.torch_device)
+        else:
+            self._check_dev(proj, "proj")
+            if proj.dtype != torch.float64 or proj.numel() < n_variants * c:
+                raise ValueError(f"proj must be a float64 tensor with >= {n_variants * c} entries")
+            proj = proj.view(-1)
+        need = (k - 1) * out_stride + c if k else 0
+        if out is None:
+            make = torch.zeros if accumulate else torch.empty
+            return q_stride, c, proj, make(max(need, 1), dtype=torch.float64, device=self.torch_device), out_stride
+        self._check_dev(out, "out")
+        if out.dtype != torch.float64 or out.numel() < need:
+            raise ValueError(f"out must be a float64 tensor with >= {need} entries")
+        return q_stride, c, proj, out.view(-1), out_stride
+
     _MATRIX_DTYPES = {torch.int8: np.int8, torch.uint8: np.uint8, torch.int16: np.int16, torch.int32: np.int32,
                       torch.float16: np.float16, torch.bfloat16: None, torch.float32: np.float32}
 

@@ -23,6 +23,9 @@
 // `pgen-hip grm <PFILE_PREFIX> [--include-var <EXPR>] [--include-sam <EXPR>] [--format grm-bin|rel] -o|--out <OUT_PREFIX>` (not in the
 // reference): the genetic relationship matrix of the kept samples over the kept variants (GCTA's definition), two FP64 Gram
 // matrices per block of variants on the GPU's FP64 matrix cores.
+// `pgen-hip pca <PFILE_PREFIX> [--include-var <EXPR>] [--include-sam <EXPR>] [--pcs <P>] [--tol <X>] [--max-passes <I>] [--seed <S>]
+// -o|--out <OUT_PREFIX>` (not in the reference): the leading principal components of the kept samples by randomised subspace iteration,
+// every pass one matrix-free Gram product (pgenhip_gram_apply) over the kept variants; the K x K matrix is never formed.
 // Additions (opt-in, not in the reference): --gpus <N>, --block-mib <M>, --launch-mib <M>, --filter-threads <T>, --stats, --dry-run
 // (filter: write the VCF header only and report the body geometry; needs no GPU); BGZF output (`-o x.vcf.gz` or --bgzf,
 // --bgzf-level <1-9>, --compress-threads <T>) and `pgen-hip bgzf <IN> <OUT>`, the same writer on a file.
@@ -99,6 +102,7 @@ const char *kUsage =
     "  ld      Pairwise r^2 of the kept variants inside a sliding window, outputting to stdout\n"
     "  kinship Pairwise genotype tables and KING-robust kinship of the kept samples, outputting to stdout\n"
     "  grm     Genetic relationship matrix of the kept samples, outputting GCTA-style binary files or a text square\n"
+    "  pca     Leading principal components of the kept samples, outputting .eigenval and .eigenvec files\n"
     "  export  Writes the kept variants and samples back as a .pgen (or PLINK 1 .bed) fileset\n"
     "  help    Print this message\n\n"
     "query  <PFILE_PREFIX> -f, --fstring <QUERY_FSTRING> [-i, --include <QUERY>] [-s, --samples]\n"
@@ -162,6 +166,15 @@ const char *kUsage =
     "       (16 bytes x kept samples squared) are held on each device in square tiles of T ranks (default 1024) and on the host:\n"
     "       out-of-core sample tiling is not built, and a sample set whose matrices do not fit fails with an out-of-memory error.\n"
     "       Sums are FP64 in no fixed order; no byte or digit parity with plink2 or GCTA is claimed\n"
+    "pca    <PFILE_PREFIX> [--include-sam <SAM_QUERY>] [--include-var <VAR_QUERY>] [--pcs <P>] [--tol <X>] [--max-passes <I>] [--seed <S>] -o, --out <OUT_PREFIX>\n"
+    "       [--gpus <N>] [--shards <S>] [--block-mib <M>] [--block-rows <B>] [--read-threads <T>] [--filter-threads <T>] [--stats]\n"
+    "       the P (default 10, 1 .. 32) leading principal components of M = Z^T Z / V_used, Z the kept variants' standardised genotypes\n"
+    "       (x - 2p) / sqrt(2p(1-p)) with a missing call at the variant's mean (plink2 --pca's convention; grm's G / N is pairwise-complete\n"
+    "       and differs wherever calls are missing); a variant with no call or with p of 0 or 1 is skipped (--stats reports how many).\n"
+    "       The K x K matrix is never formed: randomised subspace iteration on min(K, P + 10) columns with Rayleigh-Ritz in every pass,\n"
+    "       each pass one Gram product over all records, until the residuals of the P pairs are <= X * lambda_1 (default 1e-6) or after I\n"
+    "       passes (default 100: a warning, exit 0, \"converged\": false under --stats beside passes and residual).  OUT_PREFIX.eigenval: P\n"
+    "       lines; OUT_PREFIX.eigenvec: #IID PC1 .. PCP, one line per kept sample, unit-norm vectors, %.17g.  No digit parity with plink2 is claimed\n"
     "bgzf   <IN_FILE> <OUT_FILE> [--level <1-9>] [--threads <T>] [--chunk-mib <M>]\n";
 
 [[noreturn]] void usage_error(const std::string &msg)
@@ -577,6 +590,22 @@ int main(int argc, char **argv)
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
             const OutputStats st = pfile.output_grm(a.get("include-sam"), a.get("include-var"), *a.get("out"), g, output_options(a));
             if (a.has("stats")) std::fprintf(stderr, "{\"variants_skipped\": %llu}\n", (unsigned long long)st.grm_skipped);
+            return a.done(st, t_main);
+        }
+        if (cmd == "pca") {
+            const SelectionArgs a(argc, argv, {{"pcs", 0}, {"tol", 0}, {"max-passes", 0}, {"seed", 0}, {"block-rows", 0}}, {});
+            if (!a.has("out") || a.get("out")->empty()) usage_error("the following required arguments were not provided: --out <OUT_PREFIX>");
+            PcaOptions p;
+            if (auto v = a.get("pcs")) p.pcs = (uint32_t)unsigned_value(*v, "pcs", "P", 1, 32, "a number of components from 1 to 32");
+            if (auto v = a.get("tol")) p.tol = double_value(*v, "tol", "X", 0.0, 1.0, "a number from 0 to 1");
+            if (auto v = a.get("max-passes")) p.max_passes = (uint32_t)unsigned_value(*v, "max-passes", "I", 1, 1000000, "a number of passes from 1 to 1000000");
+            if (auto v = a.get("seed")) p.seed = unsigned_value(*v, "seed", "S", 0, kNoLimit, "a whole number");
+            if (auto b = a.get("block-rows")) p.block_rows = block_rows_value(*b);
+            const Pfile pfile = Pfile::from_prefix(a.positional[0]);
+            const OutputStats st = pfile.output_pca(a.get("include-sam"), a.get("include-var"), *a.get("out"), p, output_options(a));
+            if (a.has("stats"))
+                std::fprintf(stderr, "{\"variants_skipped\": %llu, \"passes\": %llu, \"residual\": %.6g, \"converged\": %s}\n", (unsigned long long)st.pca_skipped,
+                             (unsigned long long)st.pca_passes, st.pca_residual, st.pca_converged ? "true" : "false");
             return a.done(st, t_main);
         }
         if (cmd == "bgzf") {

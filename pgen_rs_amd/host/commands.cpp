@@ -1,5 +1,5 @@
 // commands.cpp — the commands of pfile.h that the reference does not have: freq, sample-counts, score, assoc, matrix, ld, export,
-// kinship and grm, with the block loop they share.  Line references are to the reference's src/pfile.rs.
+// kinship, grm and pca, with the block loop they share.  Line references are to the reference's src/pfile.rs.
 #include <fcntl.h>
 
 #include <algorithm>
@@ -11,6 +11,7 @@
 #include <mutex>
 
 #include "host_internal.h"
+#include "linalg.h"
 
 namespace pgenhost {
 
@@ -538,6 +539,45 @@ struct GramCounter : Counter {
         sums.emplace(first_b0, std::move(mine));
     }
 };
+
+// pca's counter of one pass: Q (K x L) goes up once per shard; per block the rows' tables go up and every group of at most sixteen
+// columns gets one Gram product into the shard's K x L doubles (the first block overwrites, the others accumulate); they come back
+// once per shard, filed under the shard's first variant so that the host can add the shards in order
+struct PcaCounter : Counter {
+    size_t K, L;
+    const std::vector<double> &tables;                 // 4 per kept variant
+    std::map<size_t, std::vector<double>> &sums;       // shard's first variant -> K x L
+    std::mutex &mu;
+    double *d_q, *d_y, *d_proj, *d_tab, *h_y;
+    size_t first_b0 = 0;
+    void launch(const BlockRows &b, size_t b0, uint32_t nv, uint32_t, bool first)
+    {
+        check(pgenhip_memcpy_h2d(b.ctx, d_tab, tables.data() + 4 * b0, (size_t)nv * 32), "H2D code values");
+        const uint32_t flags = PGENHIP_GAPPLY_AUTO | (first ? 0u : PGENHIP_GAPPLY_ACCUMULATE);
+        if (first) first_b0 = b0;
+        for (size_t c0 = 0; c0 < L; c0 += PGENHIP_GAPPLY_MAX_COLUMNS) {
+            const uint32_t cg = (uint32_t)std::min<size_t>(PGENHIP_GAPPLY_MAX_COLUMNS, L - c0);
+            launch_rows(b, NAMED(pgenhip_gram_apply), NAMED(pgenhip_gram_apply_at), nv, (const double *)d_tab, (const double *)(d_q + c0), (uint64_t)L, cg,
+                        d_proj, d_y + c0, (uint64_t)L, flags);
+        }
+    }
+    void finish(pgenhip_ctx *ctx) const   // (count_blocks has launched at least one block)
+    {
+        check(pgenhip_memcpy_d2h(ctx, h_y, d_y, K * L * 8), "D2H Gram product");
+        check(pgenhip_wait(ctx), "pgenhip_wait");
+        std::lock_guard<std::mutex> lk(mu);
+        sums.emplace(first_b0, std::vector<double>(h_y, h_y + K * L));
+    }
+};
+
+// splitmix64: the next state's output
+uint64_t splitmix64(uint64_t &state)
+{
+    uint64_t z = (state += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
 
 }  // namespace
 
@@ -1245,6 +1285,153 @@ OutputStats Pfile::output_grm(const std::optional<std::string> &sam_query, const
     st.body_bytes = st.file_bytes;
     st.seconds_body = now_s() - t_body;
     return st;
+}
+
+OutputStats Pfile::output_pca(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
+                              const std::string &out_prefix, const PcaOptions &popt, const OutputOptions &opt) const
+{
+    OutputStats st;
+    const double t0 = now_s();
+    const Selection sel = select(sam_query, var_query, opt.filter_threads);
+    const size_t iid = iid_column(*this, sel.sam_header);
+    st.seconds_filter = now_s() - t0;
+
+    const KeptSamples kept = check_selection(*this, sel);
+    const size_t V = sel.var_idx_rcds.size(), K = kept.rows.size(), P = popt.pcs;
+    st.variants = V;
+    st.samples_kept = K;
+    const double t_body = now_s();
+    std::string header = "#IID";
+    for (size_t i = 0; i < P; i++) header += "\tPC" + std::to_string(i + 1);
+    header += '\n';
+    st.header_bytes = header.size();
+    auto write_out = [&](const std::string &vals, const std::string &vecs) {
+        st.file_bytes = header.size() + vecs.size();
+        st.body_bytes = vecs.size();
+        write_text(vals, out_prefix + ".eigenval");
+        write_text(header + vecs, out_prefix + ".eigenvec");
+        st.seconds_body = now_s() - t_body;
+        return st;
+    };
+    if (K == 0 || V == 0) return write_out("", "");   // nothing to decompose and no device touched
+    if (P > K) throw PfileError("--pcs " + std::to_string(P) + " asks for more components than the " + std::to_string(K) + " kept samples");
+    static const char *const kNoDevice = "no HIP device: the pca path has no CPU fallback";
+
+    // the tables: grm's table G per variant, from a first pass of genotype counts
+    std::vector<uint32_t> counts(4 * V, 0u);
+    count_blocks(*this, sel.var_idx_rcds, kept, opt, kNoDevice, st, [&](DeviceCtx &ctx, uint64_t bv) {
+        return VariantCounter{{}, counts, ctx.device<uint32_t>((size_t)(16 * bv), "device counts"), ctx.pinned<uint32_t>((size_t)(16 * bv), "pinned counts")};
+    }, popt.block_rows);
+    std::vector<double> tables(4 * V, 0.0);
+    for (size_t j = 0; j < V; j++) {
+        const uint64_t c0 = counts[4 * j], c1 = counts[4 * j + 1], c2 = counts[4 * j + 2];
+        const uint64_t called = c0 + c1 + c2, alt = c1 + 2 * c2;
+        if (called == 0 || alt == 0 || alt == 2 * called) {   // no call, p == 0 or p == 1: the variant adds nothing
+            st.pca_skipped++;
+            continue;
+        }
+        const double p = (double)alt / (2.0 * (double)called);
+        const double s = 1.0 / std::sqrt(2.0 * p * (1.0 - p));
+        double *g = tables.data() + 4 * j;
+        g[0] = (0.0 - 2.0 * p) * s;
+        g[1] = (1.0 - 2.0 * p) * s;
+        g[2] = (2.0 - 2.0 * p) * s;
+    }
+    const size_t V_used = V - (size_t)st.pca_skipped;
+    if (V_used == 0) return write_out("", "");
+
+    // the start: a seeded Gaussian K x L matrix, orthonormalised
+    const size_t L = std::min(K, P + 10);
+    std::vector<double> Q(K * L), Y(K * L), U(K * L), T(L * L), W, lambda;
+    uint64_t state = popt.seed;
+    for (double &x : Q) {
+        const double u1 = (double)((splitmix64(state) >> 11) + 1) * 0x1p-53, u2 = (double)(splitmix64(state) >> 11) * 0x1p-53;
+        x = std::sqrt(-2.0 * std::log(u1)) * std::cos(2.0 * M_PI * u2);
+    }
+    linalg::qr_thin(Q, K, L);
+
+    double kernel_s = 0, setup_s = 0;
+    for (;;) {
+        // Y = M Q
+        std::mutex mu;
+        std::map<size_t, std::vector<double>> sums;
+        count_blocks(*this, sel.var_idx_rcds, kept, opt, kNoDevice, st, [&](DeviceCtx &ctx, uint64_t bv) {
+            PcaCounter pc{{}, K, L, tables, sums, mu, ctx.device<double>(K * L * 8, "device Q"), ctx.device<double>(K * L * 8, "device Gram product"),
+                          ctx.device<double>((size_t)(bv * PGENHIP_GAPPLY_MAX_COLUMNS * 8), "device projections"),
+                          ctx.device<double>((size_t)(bv * 32), "device code values"), ctx.pinned<double>(K * L * 8, "pinned Gram product")};
+            check(pgenhip_memcpy_h2d(ctx.get(), pc.d_q, Q.data(), K * L * 8), "H2D Q");
+            return pc;
+        }, popt.block_rows);
+        kernel_s += st.seconds_kernel;
+        setup_s += st.seconds_setup;
+        std::fill(Y.begin(), Y.end(), 0.0);
+        for (const auto &shard : sums)   // ordered by the shard's first variant
+            for (size_t i = 0; i < K * L; i++) Y[i] += shard.second[i];
+        for (double &y : Y) y /= (double)V_used;
+        st.pca_passes++;
+
+        // Rayleigh-Ritz: T = Q^T Y symmetrised = W Lambda W^T, U = Q W, residuals of the first P pairs
+        for (size_t a = 0; a < L; a++)
+            for (size_t b = 0; b < L; b++) {
+                double dot = 0.0;
+                for (size_t k = 0; k < K; k++) dot += Q[k * L + a] * Y[k * L + b];
+                T[a * L + b] = dot;
+            }
+        for (size_t a = 0; a < L; a++)
+            for (size_t b = a + 1; b < L; b++) T[a * L + b] = T[b * L + a] = 0.5 * (T[a * L + b] + T[b * L + a]);
+        linalg::jacobi_eigh(T, L, lambda, W);
+        double worst = 0.0;
+        for (size_t i = 0; i < L; i++) {
+            double rr = 0.0;
+            for (size_t k = 0; k < K; k++) {
+                double u = 0.0, yw = 0.0;
+                for (size_t a = 0; a < L; a++) {
+                    u += Q[k * L + a] * W[a * L + i];
+                    yw += Y[k * L + a] * W[a * L + i];
+                }
+                U[k * L + i] = u;
+                const double r = yw - lambda[i] * u;
+                rr += r * r;
+            }
+            if (i < P) worst = std::max(worst, std::sqrt(rr));
+        }
+        st.pca_residual = lambda[0] > 0.0 ? worst / lambda[0] : 0.0;
+        st.pca_converged = worst <= popt.tol * lambda[0];
+        if (st.pca_converged || st.pca_passes >= popt.max_passes) break;
+        Q = Y;
+        linalg::qr_thin(Q, K, L);
+    }
+    st.seconds_kernel = kernel_s;
+    st.seconds_setup = setup_s;
+    if (!st.pca_converged)
+        std::fprintf(stderr, "pgen-hip: warning: pca did not reach --tol within %llu passes (residual %.3g of lambda_1); the outputs are written all the same\n",
+                     (unsigned long long)st.pca_passes, st.pca_residual);
+
+    std::string vals, vecs;
+    char num[40];
+    for (size_t i = 0; i < P; i++) {
+        std::snprintf(num, sizeof num, "%.17g\n", lambda[i]);
+        vals += num;
+    }
+    // unit norm, the largest-magnitude entry positive
+    std::vector<double> scale(P, 1.0);
+    for (size_t i = 0; i < P; i++) {
+        double ss = 0.0, big = 0.0;
+        for (size_t k = 0; k < K; k++) {
+            ss += U[k * L + i] * U[k * L + i];
+            if (std::fabs(U[k * L + i]) > std::fabs(big)) big = U[k * L + i];
+        }
+        scale[i] = (big < 0.0 ? -1.0 : 1.0) / (ss > 0.0 ? std::sqrt(ss) : 1.0);
+    }
+    for (size_t k = 0; k < K; k++) {
+        vecs += sel.sam_idx_rcs[k].second.at(iid);
+        for (size_t i = 0; i < P; i++) {
+            std::snprintf(num, sizeof num, "\t%.17g", U[k * L + i] * scale[i]);
+            vecs += num;
+        }
+        vecs += '\n';
+    }
+    return write_out(vals, vecs);
 }
 
 OutputStats Pfile::output_matrix(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,

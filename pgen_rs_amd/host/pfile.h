@@ -155,6 +155,15 @@ struct GrmOptions {
     uint64_t block_rows = 0;          // variants per block (0: as many as fill block_text_bytes with their records)
 };
 
+// `pca`: how many components, when the iteration stops, where it starts
+struct PcaOptions {
+    uint32_t pcs = 10;                // --pcs: principal components written, 1 .. 32 and <= kept samples
+    double tol = 1e-6;                // --tol: stop when the largest residual norm of the first pcs Ritz pairs is <= tol * lambda_1
+    uint32_t max_passes = 100;        // --max-passes: passes over the records at most (each is one product M Q)
+    uint64_t seed = 1;                // --seed: of the Gaussian start matrix
+    uint64_t block_rows = 0;          // variants per block (0: as many as fill block_text_bytes with their records)
+};
+
 struct OutputStats {
     uint64_t variants = 0, samples_kept = 0, header_bytes = 0, body_bytes = 0;   // header / body: bytes of VCF text
     uint64_t file_bytes = 0;                                                     // what the output file holds (BGZF: compressed)
@@ -162,6 +171,9 @@ struct OutputStats {
     uint64_t score_matched = 0, score_flipped = 0, score_skipped = 0;            // `score`: weights rows used, of them REF-effect rows, rows not used
     uint64_t assoc_dropped = 0;                                                  // `assoc`: kept samples dropped for a missing phenotype or covariate
     uint64_t grm_skipped = 0;                                                    // `grm`: kept variants that add nothing (no call, or monomorphic among the kept samples)
+    uint64_t pca_skipped = 0, pca_passes = 0;                                    // `pca`: kept variants that add nothing; passes over the records
+    double pca_residual = 0;                                                     // `pca`: max over the written components of |M u - lambda u| / lambda_1 at the last pass
+    bool pca_converged = true;                                                   // `pca`: the residual reached --tol within --max-passes
     double seconds_setup = 0;   // inside seconds_body: HIP runtime start, contexts, device and pinned allocations of the slowest shard, before its first block is staged
 };
 
@@ -327,6 +339,23 @@ class Pfile {
     // a device.  No byte or digit parity with plink2 or GCTA is claimed.
     OutputStats output_grm(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
                            const std::string &out_prefix, const GrmOptions &gopt, const OutputOptions &opt = OutputOptions()) const;
+
+    // `pca` (not in the reference): the leading principal components of the kept samples over the kept variants, without the K x K
+    // matrix.  M = Z^T Z / V_used with Z[j][k] = grm's table G of variant j at the code of sample k: ((0-2p)s, (1-2p)s, (2-2p)s, 0), p
+    // from a first pass of pgenhip_genotype_counts, so a missing call sits at the variant's mean (plink2 --pca's convention; grm's
+    // G / N is pairwise-complete and differs wherever calls are missing).  A variant with no call or p of 0 or 1 is skipped
+    // (pca_skipped); V_used counts the others.  Randomised subspace iteration with Rayleigh-Ritz in every pass: L = min(K, pcs + 10)
+    // columns; Q starts as a seeded Gaussian K x L matrix (splitmix64 from the seed; per entry two draws u1 in (0, 1], u2 in [0, 1)
+    // and the Box-Muller cosine sqrt(-2 ln u1) cos(2 pi u2), row-major), orthonormalised (linalg.h).  One pass: Y = M Q by
+    // pgenhip_gram_apply / _at over freq's block loop and shards, 16 columns per call; the shard's first block overwrites, the
+    // others accumulate; the host adds the shards in the order of their first variants; records are re-staged every pass.  Then
+    // T = Q^T Y (symmetrised) = W Lambda W^T, U = Q W, r_i = Y w_i - lambda_i u_i; stop when max over i < pcs of |r_i| <= tol * lambda_1
+    // or after max_passes passes (pca_converged false: the outputs are written all the same), else Q = orth(Y).
+    // out_prefix.eigenval: pcs lines, %.17g.  out_prefix.eigenvec: "#IID<TAB>PC1 .. PCpcs", one line per kept sample, unit-norm
+    // vectors, each with its largest-magnitude entry positive, %.17g.  No kept sample, no kept variant or no usable variant: the
+    // header alone and an empty .eigenval (the first two touch no device).  No digit parity with plink2 is claimed.
+    OutputStats output_pca(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
+                           const std::string &out_prefix, const PcaOptions &popt, const OutputOptions &opt = OutputOptions()) const;
 
     // the header part of output_vcf (:110-146) on its own: used by output_vcf and by the CPU tests
     std::string vcf_header(const IdxRecords &sam_idx_rcs, const StringRecord &sam_header) const;
