@@ -1,7 +1,7 @@
 """A slab-wise reference for rows too long to decode on the host: plain torch integer ops on the record bytes (src/pfile.rs:172-175:
 sample s in byte s >> 2, bits 2 * (s & 3)), on whatever device the tensors live on, a slab of samples (or of kept ranks) at a time.
 Nothing here calls a product kernel; test_longrow_ref.py holds every function against the CPU oracle and the numpy references with
-a slab of 97 samples, so that slab seams fall inside bytes.
+a slab of 97 samples (the Gram product's two functions with slabs of 1, 7 and 64 ranks), so that slab seams fall inside bytes.
 
 Conventions: ``rec`` is a 1-D uint8 tensor whose first byte is the record's first byte (>= ceil(n / 4) bytes); ``kept`` is None (all
 samples) or the ascending kept list as a numpy uint32 array or an int32 / int64 tensor (``as_kept`` moves it to a device once);
@@ -326,6 +326,71 @@ def check_variant_sums(sums: torch.Tensor, recs_rows: Sequence[torch.Tensor], n:
     if i is None:
         return None
     return i // (4 * c), (i // 4) % c, i % 4, float(got.reshape(-1)[i]), int(want.reshape(-1)[i])
+
+
+def _int_tensor(x, what: str, device) -> torch.Tensor:
+    """``x`` (a numpy array, or a tensor with rows of any stride) as an int64 tensor on ``device``, after checking that it holds
+    integers only."""
+    if not isinstance(x, torch.Tensor):
+        return torch.from_numpy(_int_array(x, what).copy()).to(device)
+    xi = x if x.dtype == torch.int64 else x.to(torch.int64)
+    assert x.dtype == torch.int64 or bool((xi == x).all()), f"{what} must be integers: the comparison is exact"
+    return xi.to(device)
+
+
+def apply_proj(recs_rows: Sequence[torch.Tensor], n: int, kept, tables, q, slab: int = SLAB) -> torch.Tensor:
+    """(V, C) int64: P[j, c] = the sum over the kept ranks k of t_j[code of rank k in row j] * q[k, c], the P pass of
+    pgenhip_gram_apply.  ``tables``: (V, 4) small integers by the row's position in ``recs_rows``; ``q``: (K, C) small integers, a
+    numpy array or a tensor on the records' device with rows of any stride (the padded Q the call reads).  Summed over slabs of
+    ranks; every partial sum is an integer below 2^52 (asserted from K and the largest |t| and |q|)."""
+    dev = recs_rows[0].device
+    kept = as_kept(kept, dev)
+    k = kept_count(n, kept)
+    v = len(recs_rows)
+    t = _int_tensor(tables, "tables", dev).reshape(v, 4)
+    if not isinstance(q, torch.Tensor):
+        q = torch.from_numpy(np.asarray(q).copy()).to(dev)
+    assert q.dim() == 2 and q.shape[0] == k
+    c = int(q.shape[1])
+    out = torch.zeros((v, c), dtype=torch.int64, device=dev)
+    slab = max(1, min(slab, (1 << 26) // c))   # a slab of ranks holds C columns of int64: bound its bytes
+    t_max, q_max = int(t.abs().max()) if v else 0, 0
+    for a, b in _slabs(k, slab):
+        qi = _int_tensor(q[a:b], "q", dev)
+        q_max = max(q_max, int(qi.abs().max()))
+        for j, rec in enumerate(recs_rows):
+            z = t[j][codes(rec, a, b, kept).to(torch.int64)]
+            out[j] += (z[:, None] * qi).sum(dim=0)
+    assert k * t_max * q_max < 2 ** 52, "a partial sum of P may not be exact in float64"
+    return out
+
+
+def check_apply_out(out: torch.Tensor, recs_rows: Sequence[torch.Tensor], n: int, kept, tables, proj, slab: int = SLAB):
+    """``out``: the (K, C) float64 view (rows of any stride) of what the Y pass of pgenhip_gram_apply wrote; ``proj``: the (V, C)
+    integers it summed (apply_proj; twice them after an ACCUMULATE call on top: the sums are linear in proj).  want[k, c] = the sum
+    over the rows j of t_j[code of rank k in row j] * proj[j, c] is formed in int64 slab by slab, so ``out`` must equal it exactly
+    as float64.  -> None or (rank, column, got, want) of the first wrong entry (NaN differs from everything)."""
+    dev = out.device
+    kept = as_kept(kept, dev)
+    k = kept_count(n, kept)
+    v = len(recs_rows)
+    t = _int_tensor(tables, "tables", dev).reshape(v, 4)
+    p = _int_tensor(proj, "proj", dev)
+    assert p.shape[0] == v and tuple(out.shape) == (k, p.shape[1])
+    c = int(p.shape[1])
+    if v:
+        assert v * int(t.abs().max()) * int(p.abs().max()) < 2 ** 52, "a partial sum of Y may not be exact in float64"
+    slab = max(1, min(slab, (1 << 26) // c))   # a slab of ranks holds C columns of int64 and of float64: bound its bytes
+    for a, b in _slabs(k, slab):
+        want = torch.zeros((b - a, c), dtype=torch.int64, device=dev)
+        for j, rec in enumerate(recs_rows):
+            z = t[j][codes(rec, a, b, kept).to(torch.int64)]
+            want += z[:, None] * p[j][None, :]
+        got = out[a:b]
+        i = _first_diff(got, want.to(torch.float64))
+        if i is not None:
+            return a + i // c, i % c, float(got[i // c, i % c]), int(want[i // c, i % c])
+    return None
 
 
 # ---- periodic rows: a closed form for windows too wide to enumerate ------------------------------------------------------------------

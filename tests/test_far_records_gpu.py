@@ -6,7 +6,7 @@ offset lands on when it is cut to 32 bits: a wrong record, read in bounds) and f
 Each call mixes near and far rows through (i) d_variant_idx with record_stride = FAR, (ii) a small stride with d_variant_idx values
 near FAR / stride, (iii) d_record_off; the packed-record, score, pair-table and sample-pair-table entry points also take (iv) two
 rows by stride alone, FAR bytes apart.  Expected bytes: the CPU oracle and the numpy references on the few records involved.  The Gram
-matrix and the per-variant sums take integer tables and values, so their FP64 results are compared exactly.
+matrix, the per-variant sums and the Gram product take integer tables, values and Q, so their FP64 results are compared exactly.
 test_sample_scores_far_weights does the same for the other pointer a kernel offsets by a row number: d_weights.
 
 The kernels that cannot gather (RUNS, the pick family's packed path, the line-run kernel) get dense records that cross 2^32
@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+import gapply_ref as AR
 import gram_ref as GR
 import longrow_ref as LR
 import matrix_ref as MR
@@ -30,6 +31,7 @@ import spair_ref as SPR
 import subset_plan as SP
 import vsum_ref as VR
 from pgen_rs_amd import _capi
+from test_gram_apply_gpu import int_q
 from test_sample_gram_gpu import int_tables
 from test_variant_sums_gpu import int_values
 
@@ -504,6 +506,48 @@ def test_variant_sums_far_records(far, n, k, c, kernel):
                 row, col, code = np.argwhere(got != want)[0]
                 raise AssertionError(f"{what}: row {row} (record at byte {offs[row]:#x}) column {col} code {code}: got {got[row, col, code]!r}, "
                                      f"want {want[row, col, code]!r}")
+
+
+GAPPLY = {"general": _capi.GAPPLY_GENERAL, "mfma": _capi.GAPPLY_MFMA, "auto": _capi.GAPPLY_AUTO}
+
+
+@pytest.mark.parametrize("kernel", ["general", "mfma", "auto"])
+@pytest.mark.parametrize("keep", ["all", "every7"])
+def test_gram_apply_far_records(far, keep, kernel):
+    """pgenhip_gram_apply and pgenhip_gram_apply_at with N = 299 and C = 13, all samples and every 7th: GENERAL, MFMA and AUTO over
+    all four row sources (both passes of the MFMA shape have their own row address, compiled per source: the stride, variant_idx and
+    record_off instantiations, with and without a kept list, each read a far row), integer tables by position in the selection and
+    an integer Q, P and Y into sentinel frames.  Exact.  Needs 5 GiB."""
+    n, c = 299, 13
+    kept = None if keep == "all" else np.arange(0, n, 7, dtype=np.uint32)
+    r = MR.rsize(n)
+    with pgen_rs_amd.GtEngine(n, kept_idx=kept, device=0) as eng:
+        kk = eng.kept_count
+        q = int_q(kk, c, n)
+        d_q = torch.from_numpy(q).to(DEV)
+        for sname, offs, kw, offs_at in sources(n, plain=True):
+            v = len(offs)
+            t = int_tables(v, n + v)
+            wp, wy = AR.apply_int(GR.unpack(far.records(offs, r), n, kept), t, q)
+            d_t = torch.from_numpy(t).to(DEV)
+            kw_t, at_t = tensors(kw, offs_at)
+            pbuf, pfront = framed(8 * v * c, align=8)
+            obuf, ofront = framed(8 * kk * c, align=8)
+            proj = pbuf[pfront: pfront + 8 * v * c].view(torch.float64)
+            out = obuf[ofront: ofront + 8 * kk * c].view(torch.float64)
+            if at_t is None:
+                eng.gram_apply(far.dev, d_t, d_q, n_variants=v, proj=proj, out=out, kernel=GAPPLY[kernel], **kw_t)
+            else:
+                eng.gram_apply_at(far.dev, at_t, d_t, d_q, n_variants=v, proj=proj, out=out, kernel=GAPPLY[kernel])
+            eng.wait()
+            what = f"N={n} {keep} C={c} {sname} kernel {kernel}"
+            for name, got, want, offs_of in (("P", payload(pbuf, pfront, 8 * v * c, what + " P").view(np.float64).reshape(v, c), wp, offs),
+                                            ("Y", payload(obuf, ofront, 8 * kk * c, what + " Y").view(np.float64).reshape(kk, c), wy, None)):
+                exp = want.astype(np.float64)
+                if not np.array_equal(got, exp):
+                    i, l = np.argwhere(got != exp)[0]
+                    at = f" (row {i}: record at byte {offs_of[i]:#x})" if offs_of else ""
+                    raise AssertionError(f"{what}: {name} entry ({i}, {l}){at}: got {float(got[i, l])!r}, want {float(exp[i, l])!r}")
 
 
 # ---- dense records that cross 2^32 themselves ---------------------------------------------------------------------------------------

@@ -1,12 +1,13 @@
 """The slab-wise torch reference of the long-row GPU tests (longrow_ref.py) against the CPU oracle's GT text (pgen_oracle.decode_emit),
 the oracle's counts (count_ref.py) and the numpy references (matrix_ref.py, pack_ref.py, score_ref.py, pair_ref.py, spair_ref.py,
-gram_ref.py, vsum_ref.py) — on the CPU, with a slab of 97 samples so that slab seams fall inside record bytes, on records with dirty
+gram_ref.py, vsum_ref.py, gapply_ref.py) — on the CPU, with a slab of 97 samples so that slab seams fall inside record bytes, on records with dirty
 pad bits."""
 import numpy as np
 import pytest
 import torch
 
 import count_ref as CR
+import gapply_ref as AR
 import gram_ref as GR
 import longrow_ref as LR
 import matrix_ref as MR
@@ -321,3 +322,44 @@ def test_variant_sums_check(n, keep, c, slab):
     bad = got.clone()
     bad[0] = float("nan")
     assert LR.check_variant_sums(bad, recs_rows, n, kept, t_vals, slab=slab)[:3] == (0, 0, 0)
+
+
+# ---- the Gram product's two passes: against gapply_ref ----------------------------------------------------------------------------------
+APPLY_N = [5, 63, 128, 301]   # 128: slabs of 64 ranks end on the data's last rank; the others are no multiple of 4
+
+
+@pytest.mark.parametrize("slab", [1, 7, 64])
+@pytest.mark.parametrize("c", [1, 3, 16])
+@pytest.mark.parametrize("keep", SUMS_KEEPS)
+@pytest.mark.parametrize("n", APPLY_N)
+def test_apply_proj_and_check_apply_out(n, keep, c, slab):
+    """apply_proj equals gapply_ref.apply_int's P, and check_apply_out accepts its Y, with slabs of 1, 7 and 64 ranks (seams inside
+    record bytes, between them and on the last rank), on a gather that repeats a row (the tables go with the position), with Q and
+    the output as views of wider rows; twice proj goes with twice Y; a single planted wrong entry is named."""
+    kept = sums_kept(n, keep)
+    recs = records(n)
+    rows = [0, 2, 1, 2, 0]
+    k = LR.kept_count(n, kept)
+    rng = np.random.default_rng(n + c + len(keep))
+    tables = rng.integers(-8, 9, size=(len(rows), 4)).astype(np.float64)
+    q = rng.integers(-4, 5, size=(k, c)).astype(np.float64)
+    wp, wy = AR.apply_int(AR.unpack(recs[rows], n, kept), tables, q)
+    recs_rows = [torch.from_numpy(recs[j].copy()) for j in rows]
+    q_wide = torch.full((k, c + 3), -1.5, dtype=torch.float64)
+    q_wide[:, :c] = torch.from_numpy(q)
+    for q_arg in (q, q_wide[:, :c]):
+        proj = LR.apply_proj(recs_rows, n, kept, tables, q_arg, slab=slab)
+        assert proj.dtype == torch.int64 and proj.shape == (len(rows), c) and np.array_equal(proj.numpy(), wp)
+    out = torch.full((k, c + 3), -1.5, dtype=torch.float64)[:, :c]   # a padded pitch, as the GPU tests have
+    out.copy_(torch.from_numpy(wy.astype(np.float64)))
+    assert LR.check_apply_out(out, recs_rows, n, kept, tables, proj, slab=slab) is None
+    assert LR.check_apply_out(out, recs_rows, n, kept, tables, wp.astype(np.float64), slab=slab) is None
+    assert LR.check_apply_out(2.0 * out, recs_rows, n, kept, tables, 2 * proj, slab=slab) is None
+    for rank, col in {(0, 0), (k - 1, c - 1), (k // 2, c // 2)}:
+        bad = out.clone()
+        bad[rank, col] += 1.0
+        found = LR.check_apply_out(bad, recs_rows, n, kept, tables, proj, slab=slab)
+        assert found is not None and found[:2] == (rank, col) and found[2] == found[3] + 1 == wy[rank, col] + 1, found
+    bad = out.clone()
+    bad[0, 0] = float("nan")
+    assert LR.check_apply_out(bad, recs_rows, n, kept, tables, proj, slab=slab)[:2] == (0, 0)
