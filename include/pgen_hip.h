@@ -583,8 +583,8 @@ int pgenhip_pack_records_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t
 /* Launch-shape knobs of one ctx (tests force small grids to exercise ring re-use; A/B probes).
  * value 0 restores the built-in default of a knob unless noted. */
 typedef enum pgenhip_knob {
-    PGENHIP_KNOB_WIDE_BLOCKS_PER_CU = 1, /* stream kernel: resident blocks per CU (default: occupancy API) */
-    PGENHIP_KNOB_WIDE_RANGES = 2,        /* stream kernel: work-queue ranges (write fronts of a launch), a power of two up to 64; default 0 = by shape (8 for rows of more than 16 KiB of text, else 2) */
+    PGENHIP_KNOB_WIDE_BLOCKS_PER_CU = 1, /* stream kernel: resident blocks per CU (default: occupancy API; two on launches of up to 1 GB of text, and on launches of short rows, N < 1 916, of up to 3 GB) */
+    PGENHIP_KNOB_WIDE_RANGES = 2,        /* stream kernel: work-queue ranges (write fronts of a launch), a power of two up to 64; default 0 = by shape (8 for rows of more than 16 KiB of text and for launches of more than 3 GB of short rows, N < 1 916, else 2) */
     PGENHIP_KNOB_FLAT_BLOCKS_PER_CU = 3, /* flat kernel: grid cap per CU (default 64) */
     PGENHIP_KNOB_SCAN_BLOCKS_PER_CU = 4, /* segment kernel: resident blocks per CU (default: 2 from ~0.6 % kept, else the occupancy API's 3) */
     /* 5 was the band override of round 1's three-segment gather kernel (removed) */
@@ -608,6 +608,7 @@ typedef enum pgenhip_knob {
     PGENHIP_KNOB_GRAM_SLICES = 25,       /* sample Gram matrix: row ranges per rank tile, each summed by one block (default 0 = by shape: as many as fill the chip's resident blocks, of at least 256 rows each); tests put the row count on either side of every slice edge */
     PGENHIP_KNOB_GAPPLY_SAMPLE_SLICES = 26, /* Gram product, P pass: sample ranges per row tile, each summed by one block (default 0 = by shape: as many as fill the chip's resident blocks, of at least 4096 samples each); tests put the sample count on either side of every slice edge */
     PGENHIP_KNOB_GAPPLY_ROW_SLICES = 27, /* Gram product, Y pass: row ranges per sample tile, each summed by one block (default 0 = by shape: as many as fill the chip's resident blocks, of at least 256 rows each); tests put the row count on either side of every slice edge */
+    PGENHIP_KNOB_WIDE_BURST = 28,        /* stream kernel (GT segments and full lines of long rows): plain store steps issued back to back, 1 or 2; default 0 = by shape (1 on launches of 9 GB of text and more in rows of more than 16 KiB, else 2) */
     PGENHIP_KNOB_RUNS_ROWS = 7       /* RUNS kernel: rows per work item (default: as many as one wide load / one span holds) */
 } pgenhip_knob;
 int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value);

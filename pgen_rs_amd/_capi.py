@@ -114,6 +114,7 @@ KNOB_STORE_POLICY = 24
 KNOB_GRAM_SLICES = 25
 KNOB_GAPPLY_SAMPLE_SLICES = 26
 KNOB_GAPPLY_ROW_SLICES = 27
+KNOB_WIDE_BURST = 28
 
 
 

@@ -1183,6 +1183,10 @@ int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)
             if (value < 0 || value > 2) return fail(PGENHIP_ERR_BAD_ARG, "store policy must be 0 (rule), 1 (nt) or 2 (nt sc1)");
             t.store_policy = value;
             break;
+        case PGENHIP_KNOB_WIDE_BURST:
+            if (value < 0 || value > 2) return fail(PGENHIP_ERR_BAD_ARG, "burst must be 0 (rule), 1 or 2");
+            t.wide_burst = value;
+            break;
         default: return fail(PGENHIP_ERR_BAD_ARG, "unknown knob");
     }
     return PGENHIP_OK;

@@ -21,12 +21,13 @@
 
 #include "gt_common.hip.h"
 #include "kernels.h"
+#include "launch_plan.h"
 
 namespace pgenhip {
 
 namespace {
 
-constexpr uint32_t kSpanChunks = 1024;  // chunks per work item: 16 stores x 64 lanes
+constexpr uint32_t kSpanChunks = plan::wide::kSpanChunks;  // chunks per work item: 16 stores x 64 lanes
 constexpr uint32_t kSlabBytes = 1088;   // 66 lanes x 16 B staged at most, rounded to 64
 constexpr uint32_t kSlabExtra = 16;     // stream kernels: +0 u8 = first record byte of row j+1 (for the chunk holding row j's '\n')
 // Item descriptors travel in their own LDS ring (ring slots + 1 per storer, 64 B each), so the
@@ -1095,9 +1096,17 @@ bool gt_wide_lines_applicable(const EmitArgs &a)
            a.work_counters != nullptr;
 }
 
-constexpr uint64_t kShortLaunchBytes = 1000000000ull;     // text per launch up to which a launch counts as short (two blocks per CU, nt stores)
-constexpr uint64_t kWtOneSpanMaxBytes = 4500000000ull;    // rows of one span: text per launch up to which write-through stores are ahead (crossover between 3.8 and 5.6 GB)
+// the instantiation of the row-item kernel for a rule's store policy and burst
+template <bool HAS_VIDX, bool LINES>
+static auto stream_kernel_for(const plan::wide::Rule &r) -> void (*)(EmitArgs, WideParams)
+{
+    const bool wt = r.policy == plan::wide::kStoreWt;
+    if (r.burst == 1u) return wt ? gt_stream_dyn_kernel<7, HAS_VIDX, kStoreNtWt, LINES, 1> : gt_stream_dyn_kernel<7, HAS_VIDX, kStoreNt, LINES, 1>;
+    return wt ? gt_stream_dyn_kernel<7, HAS_VIDX, kStoreNtWt, LINES, 2> : gt_stream_dyn_kernel<7, HAS_VIDX, kStoreNt, LINES, 2>;
+}
 
+// 1 loader + 7 storer waves; store policy, burst, blocks per CU, write fronts and grid by plan::wide::rule (launch_plan.h), where
+// every measured threshold is stated
 hipError_t launch_gt_wide(const EmitArgs &a, const Tuning &t, int num_cus, hipStream_t stream)
 {
     if (a.n_variants == 0) return hipSuccess;
@@ -1106,62 +1115,23 @@ hipError_t launch_gt_wide(const EmitArgs &a, const Tuning &t, int num_cus, hipSt
     p.row_bytes = 4ull * a.kept_count + 1ull;
     p.total_bytes = (uint64_t)a.n_variants * p.row_bytes;
     p.head = (uint32_t)(((uint64_t)(uintptr_t)a.out) & 127ull);
-    // interleaved in one process (profiles/r01_kernel_sweeps.md, chr22 block): 8 ranges 2.058 ms, 4: 2.045, 2: 2.038, 1: 2.039
     p.run_rows = 0u;
     p.run_rec = 0u;
     p.magic = 0u;
-    p.pfx_shift = 0u;
-    // a row owns floor(S/16) or ceil(S/16) chunks (one more for row 0 with an unaligned pointer), and
-    // its first span starts up to 63 chunks before them (1-KiB-aligned span grid)
-    const uint64_t max_row_chunks = (p.row_bytes + 15ull) / 16ull + 1ull + 63ull;
-    p.spans_per_row = (uint32_t)((max_row_chunks + kSpanChunks - 1ull) / kSpanChunks);
+    p.spans_per_row = plan::wide::spans_per_row(p.row_bytes);
     p.n_items = (uint64_t)a.n_variants * p.spans_per_row;
-    // Write fronts of the launch (set below, once the grid is known).  Rows of several spans on a launch of >= 64 steps per block: 8 ranges — on the 212-GB launch of BASELINE configs[2] two fronts ran at 0.73
-    // or 0.78 of roofline depending on where the driver had put the buffer (stable per allocation, 5-7 % apart), eight at 0.784 on
-    // every box; 0.765 -> 0.784 on the 266-GB shard of configs[3]; +0.4-2.4 % on 12-GB launches of N = 5 000 .. 100 000.  Rows of one
-    // span (the chr22 shape): 2 — four or eight were level on one box and 1.6-2.4 % behind on another; short launches (the 0.8-GB second
-    // pass of the two-pass path: 15 steps per block): 2 — eight cost 9 % there (profiles/r02_kernel_sweeps.md).
-
-    // 1 loader + 7 storer waves, nontemporal stores, plain store steps in bursts of 2 (text of both first, then both
-    // stores): the measured best of the round-1 A/Bs (3 storers, plain stores, bursts of 1/4/8: profiles/r01_kernel_sweeps.md)
-    const uint64_t need = (p.n_items + 6ull) / 7ull;
-    // Store policy (profiles/r04_short_launches.md, both policies interleaved in one process, two boxes).  Write-through (nt sc1)
-    // stores are ahead on LONG launches of rows of several spans — N = 500 000: 12 GB -2.4 / -3.4 %, the 212-GB launch of BASELINE
-    // configs[2] 33.90 -> 32.56 ms (-3.9 %), N = 5 000 / 20 000 / 100 000 at 12 GB -1.4 / -1.9 / -2.2 % — and on rows of one span in the
-    // middle sizes (N = 2 504: 1 GB -1.9 %, 2 GB -2.0 / -2.2 %, 3.8 GB of text -2.1 %); they are BEHIND on rows of one span from 5.6 GB of
-    // text (+1.3 %, 8 GB +1.2 %, the 11.7-GB chr22 block +1.3 % on both boxes) and level on short launches (134 MB +0.9 %, the 0.5-GB
-    // second pass of the two passes +0.3 %: no end-of-kernel flush worth having shows at any size).  The rule takes write-through where
-    // it measured ahead by more than the spread: above the short-launch size of the blocks-per-CU rule below, rows of several
-    // spans at any size, rows of one span up to kWtOneSpanMaxBytes.  (Full lines through this kernel follow the same rule by the
-    // size of their GT text: the same stores behind a prefix each; not measured separately.)
+    const uint64_t need = plan::wide::steps(p.n_items);
+    plan::wide::Rule r = plan::wide::kernel_choice(p.total_bytes, p.spans_per_row, false, t.store_policy, t.wide_burst);
     void (*dk)(EmitArgs, WideParams);
-    const bool wt_rule = p.total_bytes > kShortLaunchBytes && (p.spans_per_row > 1u || p.total_bytes <= kWtOneSpanMaxBytes);
-    const bool wt = t.store_policy == 0 ? wt_rule : t.store_policy == 2;
-    if (a.line_off) {
-        if (wt) dk = gathered(a) ? gt_stream_dyn_kernel<7, true, kStoreNtWt, true> : gt_stream_dyn_kernel<7, false, kStoreNtWt, true>;
-        else dk = gathered(a) ? gt_stream_dyn_kernel<7, true, kStoreNt, true> : gt_stream_dyn_kernel<7, false, kStoreNt, true>;
-    } else {
-        if (wt) dk = gathered(a) ? gt_stream_dyn_kernel<7, true, kStoreNtWt> : gt_stream_dyn_kernel<7, false, kStoreNtWt>;
-        else dk = gathered(a) ? gt_stream_dyn_kernel<7, true, kStoreNt> : gt_stream_dyn_kernel<7, false, kStoreNt>;
-    }
-    // launch exactly what is resident (62 VGPRs -> 8 waves/SIMD -> four 512-thread blocks per CU; 25 KB of LDS
-    // each): blocks beyond that would only start when the queue is already empty.  Interleaved A/B on the chr22
-    // block: 2 blocks/CU 2.12 ms, 4 blocks/CU 2.00 ms (profiles/r01_kernel_sweeps.md)
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dk, 512, 0) != hipSuccess || per_cu < 1) per_cu = 2;
-    // ... on long launches.  SHORT launches (up to ~1 GB of text: a CLI block, a chunk of the two passes) run faster with two blocks per
-    // CU (round 3, profiles/r03_kernel_sweeps.md §6).  On a re-used output buffer (what the CLI does) the advantage is large and holds up to
-    // ~4.5 GB (N = 2 504: 134 MB 0.51 against 0.45 of roofline, 2.2 GB 0.77 / 0.71, 6 GB 0.69 / 0.73); on FRESH output regions (one call cut into
-    // pieces of that size, tools/split_probe.py) it is small and ends earlier: 134 MB 0.457 / 0.442, 0.5 GB level (K = 4 940: 0.584 / 0.569),
-    // 2 GB 0.613 / 0.642 — so the rule takes the size both agree on.
-    if (p.total_bytes <= kShortLaunchBytes && per_cu > 2) per_cu = 2;
-    if (t.wide_blocks_per_cu > 0) per_cu = t.wide_blocks_per_cu;
-    const uint64_t cap = (uint64_t)num_cus * (uint64_t)per_cu;
-    const uint32_t g = (uint32_t)(need < cap ? need : cap);
-    p.n_ranges = t.wide_ranges > 0 ? (uint32_t)t.wide_ranges : (p.spans_per_row > 1u && need >= 64ull * g ? 8u : 2u);
+    if (a.line_off) dk = gathered(a) ? stream_kernel_for<true, true>(r) : stream_kernel_for<false, true>(r);
+    else dk = gathered(a) ? stream_kernel_for<true, false>(r) : stream_kernel_for<false, false>(r);
+    int occupancy = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occupancy, dk, plan::wide::kThreads, 0) != hipSuccess || occupancy < 1) occupancy = 2;
+    r = plan::wide::rule(p.total_bytes, p.spans_per_row, false, need, occupancy, num_cus, t.store_policy, t.wide_blocks_per_cu, t.wide_ranges, t.wide_burst);
+    p.n_ranges = r.fronts;
     // LINES: the storer waves copy the prefixes themselves before their first item (lanes per line by the longest prefix: prefix_copy_shift)
     p.pfx_shift = prefix_copy_shift(a);
-    hipLaunchKernelGGL(dk, dim3(g), dim3(512), 0, stream, a, p);
+    hipLaunchKernelGGL(dk, dim3(r.grid), dim3(plan::wide::kThreads), 0, stream, a, p);
     return hipGetLastError();
 }
 
@@ -1198,27 +1168,19 @@ hipError_t launch_gt_runs(const EmitArgs &a, const Tuning &t, int num_cus, hipSt
     p.row_bytes = 4ull * a.kept_count + 1ull;
     p.total_bytes = (uint64_t)a.n_variants * p.row_bytes;
     p.head = (uint32_t)(((uint64_t)(uintptr_t)a.out) & 127ull);
-    p.n_ranges = t.wide_ranges > 0 ? (uint32_t)t.wide_ranges : 2u;   // (1 .. 64 measured level in this mode)
     p.spans_per_row = 1u;
     p.run_rows = t.runs_rows > 0 && (uint32_t)t.runs_rows < run_rows_for(a) ? (uint32_t)t.runs_rows : run_rows_for(a);
     p.run_rec = a.record_size;
     p.magic = (uint32_t)(0x100000000ull / p.row_bytes) + 1u;
     p.pfx_shift = 0u;
     p.n_items = ((uint64_t)a.n_variants + p.run_rows - 1ull) / p.run_rows;
-    const uint64_t need = (p.n_items + 6ull) / 7ull;
-    // store policy: nt; write-through measured level on these launches (N = 300: 134 MB -2.3 % inside a spread of 9 %, 255 MB -0.6 / -1.1 %,
-    // 1 GB level: profiles/r04_short_launches.md), so only the knob selects it
-    void (*dk)(EmitArgs, WideParams) = t.store_policy == 2 ? gt_stream_dyn_kernel<7, false, kStoreNtWt, false, 2, true>
-                                                           : gt_stream_dyn_kernel<7, false, kStoreNt, false, 2, true>;
-    // two blocks per CU, not the three the occupancy API allows (45 KB of LDS each): level on 11-GB launches (N = 100 / 300 / 1 000 /
-    // 1 900: 0.686 / 0.680 / 0.698 / 0.707 against 0.683 / 0.681 / 0.703 / 0.690) and 8-9 % ahead on the 255-MB launch of the
-    // reference's own dataset shape (0.505 against 0.469), whose blocks run only three steps each
-    // (round 3: on one box three were ahead again from ~5.5 GB of re-used output — 6.4 M rows of N = 300: 0.73 against 0.69 — which round 2's
-    // boxes did not show; left at two)
-    int per_cu = 2;
-    if (t.wide_blocks_per_cu > 0) per_cu = t.wide_blocks_per_cu;
-    const uint64_t cap = (uint64_t)num_cus * (uint64_t)per_cu;
-    hipLaunchKernelGGL(dk, dim3((uint32_t)(need < cap ? need : cap)), dim3(512), 0, stream, a, p);
+    const bool wt = plan::wide::kernel_choice(p.total_bytes, 1u, true, t.store_policy, 0).policy == plan::wide::kStoreWt;
+    void (*dk)(EmitArgs, WideParams) = wt ? gt_stream_dyn_kernel<7, false, kStoreNtWt, false, 2, true> : gt_stream_dyn_kernel<7, false, kStoreNt, false, 2, true>;
+    int occupancy = 0;   // (three blocks per CU, 45 KB of LDS each)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occupancy, dk, plan::wide::kThreads, 0) != hipSuccess || occupancy < 1) occupancy = 2;
+    const plan::wide::Rule r = plan::wide::rule(p.total_bytes, 1u, true, plan::wide::steps(p.n_items), occupancy, num_cus, t.store_policy, t.wide_blocks_per_cu, t.wide_ranges, 0);
+    p.n_ranges = r.fronts;
+    hipLaunchKernelGGL(dk, dim3(r.grid), dim3(plan::wide::kThreads), 0, stream, a, p);
     return hipGetLastError();
 }
 

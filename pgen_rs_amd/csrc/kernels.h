@@ -39,8 +39,8 @@ constexpr uint32_t kMaxQueueRanges = 64;
 // pgenhip_tune overrides one (tests force small grids to exercise ring reuse; A/B probes).  Nothing on the
 // launch path reads the process environment.
 struct Tuning {
-    int wide_blocks_per_cu = 0;    // stream kernel: 0 = what the occupancy API says is resident
-    int wide_ranges = 0;           // stream kernel: work-queue ranges = write fronts of a launch (power of two <= 64); 0 = by shape (8 for rows of several spans, else 2)
+    int wide_blocks_per_cu = 0;    // stream kernel: 0 = by shape (plan::wide::rule: what the occupancy API says is resident, two on short launches)
+    int wide_ranges = 0;           // stream kernel: work-queue ranges = write fronts of a launch (power of two <= 64); 0 = by shape (plan::wide::rule: 8 for rows of several spans and long RUNS launches, else 2)
     int flat_blocks_per_cu = 64;   // flat kernel: grid cap
     int scan_blocks_per_cu = 0;    // segment kernel: 0 = the measured rule (2 from ~0.6 % kept, else what the occupancy API says)
     int pick_batch_bytes = 32768;  // short-record pick kernel: text per batch (one store drain per batch)
@@ -62,7 +62,8 @@ struct Tuning {
     int gram_slices = 0;           // sample Gram matrix: row ranges per rank tile (0 = by shape: the chip's resident blocks, at least 256 rows each)
     int gapply_sample_slices = 0;  // Gram product, P pass: sample ranges per row tile (0 = by shape: the chip's resident blocks, at least 4096 samples each)
     int gapply_row_slices = 0;     // Gram product, Y pass: row ranges per sample tile (0 = by shape: the chip's resident blocks, at least 256 rows each)
-    int store_policy = 0;          // stream kernel (row items, LINES, RUNS): how text is stored (0 = the measured rule of launch_gt_wide, 1 = nt, 2 = nt sc1, write-through)
+    int store_policy = 0;          // stream kernel (row items, LINES, RUNS): how text is stored (0 = the measured rule, plan::wide::rule, 1 = nt, 2 = nt sc1, write-through)
+    int wide_burst = 0;            // stream kernel (row items, LINES): plain store steps issued back to back (0 = the measured rule: 1 on long launches of rows of several spans, else 2)
 };
 
 // rows are gathered (variant list or byte offsets): the HAS_VIDX instantiations

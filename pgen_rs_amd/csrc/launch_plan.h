@@ -1,7 +1,8 @@
 // launch_plan.h — the launch plans of the analysis kernels (gt_count, gt_scount, gt_score, gt_vsum, gt_matrix, gt_pair, gt_pack,
-// gt_spair, gt_gram, gt_gapply): lanes per row, tiles, row ranges ("slices") and grid caps, as functions of scalars.  The single statement
+// gt_spair, gt_gram, gt_gapply) and the launch rule of the stream kernel (gt_wide): lanes per row, tiles, row ranges ("slices"), grid
+// caps, store policy and write fronts, as functions of scalars.  The single statement
 // of every plan: the launchers call it, the kernels take their constants and their row ranges from it, and the tests compile this
-// header for the host (tests/plan_probe.cpp, tests/gapply_plan_probe.cpp) and run it.  Plain C++17 on purpose: no HIP header, no argument struct.
+// header for the host (tests/plan_probe.cpp, tests/gapply_plan_probe.cpp, tests/wide_plan_probe.cpp) and run it.  Plain C++17 on purpose: no HIP header, no argument struct.
 #pragma once
 #include <stdint.h>
 
@@ -524,5 +525,111 @@ PGENHIP_PLAN_HD inline Plan plan(uint32_t n_variants, uint32_t kept_count, uint3
 }
 
 }  // namespace gapply
+
+// ---- gt_wide: the work-queue stream kernel (row items, LINES, RUNS) -------------------------------------------------------------------
+namespace wide {
+
+constexpr int kThreads = 512;              // 1 loader wave + kStorers storer waves
+constexpr uint32_t kStorers = 7;           // items of one step of a block
+constexpr uint32_t kSpanChunks = 1024;     // 16-byte chunks of one work item: 16 stores x 64 lanes
+constexpr uint64_t kShortLaunchBytes = 1000000000ull;     // text per launch up to which a launch counts as short (two blocks per CU, nt stores)
+constexpr uint64_t kWtOneSpanMaxBytes = 4500000000ull;    // rows of one span: text per launch up to which write-through stores are ahead (crossover between 3.8 and 5.6 GB)
+constexpr uint64_t kBurstOneMinBytes = 9000000000ull;     // rows of several spans: text per launch from which single store steps are ahead of bursts of two (crossover between 6 and 12 GB)
+constexpr uint64_t kRunsLongBytes = 3000000000ull;        // RUNS: text per launch above which the launch takes every resident block and eight write fronts (ahead from 1.9 GB, behind at 0.9 GB)
+constexpr uint32_t kFrontSteps = 64;       // rows of several spans take eight write fronts from this many steps per block
+constexpr uint32_t kStoreNt = 1, kStoreWt = 2;   // the values of PGENHIP_KNOB_STORE_POLICY: nt, nt sc1 (write-through)
+
+// spans (work items) of a row of row_bytes of text: a row owns floor(S/16) or ceil(S/16) chunks (one more for row 0 with an unaligned
+// pointer), and its first span starts up to 63 chunks before them (1-KiB-aligned span grid)
+PGENHIP_PLAN_HD constexpr uint32_t spans_per_row(uint64_t row_bytes) { return (uint32_t)(((row_bytes + 15u) / 16u + 1u + 63u + kSpanChunks - 1u) / kSpanChunks); }
+
+// steps a launch of n_items items needs: every step of a block takes kStorers items
+PGENHIP_PLAN_HD constexpr uint64_t steps(uint64_t n_items) { return (n_items + kStorers - 1u) / kStorers; }
+
+struct Rule {
+    uint32_t policy;          // kStoreNt or kStoreWt
+    uint32_t burst;           // plain store steps issued back to back
+    uint32_t blocks_per_cu;
+    uint32_t fronts;          // work-queue ranges = write fronts of the launch
+    uint32_t grid;            // blocks
+};
+
+// The kernel a launch runs (store policy, burst): the part of the rule that does not need that kernel's occupancy figure.
+// text_bytes: GT text of the launch (full lines: without their prefixes); runs: the RUNS mode (short rows, several rows per item).
+//
+// Store policy (profiles/r04_short_launches.md, both policies interleaved in one process, two boxes).  Write-through (nt sc1)
+// stores are ahead on LONG launches of rows of several spans — N = 500 000: 12 GB -2.4 / -3.4 %, the 212-GB launch of BASELINE
+// configs[2] 33.90 -> 32.56 ms (-3.9 %), N = 5 000 / 20 000 / 100 000 at 12 GB -1.4 / -1.9 / -2.2 % — and on rows of one span in the
+// middle sizes (N = 2 504: 1 GB -1.9 %, 2 GB -2.0 / -2.2 %, 3.8 GB of text -2.1 %); they are BEHIND on rows of one span from 5.6 GB of
+// text (+1.3 %, 8 GB +1.2 %, the 11.7-GB chr22 block +1.3 % on both boxes) and level on short launches (134 MB +0.9 %, the 0.5-GB
+// second pass of the two passes +0.3 %: no end-of-kernel flush worth having shows at any size).  The rule takes write-through where
+// it measured ahead by more than the spread: above the short-launch size of the blocks-per-CU rule below, rows of several
+// spans at any size, rows of one span up to kWtOneSpanMaxBytes.  (Full lines through this kernel follow the same rule by the
+// size of their GT text: the same stores behind a prefix each; not measured separately.)
+// RUNS: nt; write-through measured level on these launches (N = 300: 134 MB -2.3 % inside a spread of 9 %, 255 MB -0.6 / -1.1 %,
+// 1 GB level), so only the knob selects it.
+// The joint grid of profiles/r05_stream_rule.md (policy x fronts x blocks per CU x burst in one process) confirms every branch above
+// on its own axis: no other policy is ahead of the rule's beyond the spread on any of its ten shapes.
+//
+// Burst: 2 (text of both steps first, then both stores); 1 / 4 / 8 lost under nt on the chr22 block (profiles/r01_kernel_sweeps.md).
+// Rows of several spans from kBurstOneMinBytes: 1 (profiles/r05_stream_rule.md, all bursts interleaved under the rule's other choices) —
+// the 212-GB launch of BASELINE configs[2] 32 754 -> 32 389 us (-1.1 %, spread 0.3 %), 12 GB of N = 20 000 / 100 000 / 500 000
+// -0.8 / -0.8 / -0.4 % (spreads 0.1-0.2 %), and under forced nt stores by more (-2.8 % at 212 GB); BEHIND below that: 6 / 3 / 1.5 GB
+// of N = 20 000 +0.8 / +2.0 / +1.5 %, 2 GB of N = 4 940 +1.8 %, the 0.5-GB second pass of the two passes +4.8 %, and on rows of one
+// span at every size (N = 2 504: 2 / 4 GB +2.0 / +2.2 %, the chr22 block +1.4 %).  Bursts of 4 were within 0.6 % of 2 everywhere,
+// on either side (-0.5 % at 6 and 12 GB of long rows, +0.6 % at 2 GB of N = 4 940): not taken, and not instantiated.
+PGENHIP_PLAN_HD inline Rule kernel_choice(uint64_t text_bytes, uint32_t spans, bool runs, int forced_policy, int forced_burst)
+{
+    Rule r{};
+    const bool wt_rule = !runs && text_bytes > kShortLaunchBytes && (spans > 1u || text_bytes <= kWtOneSpanMaxBytes);
+    r.policy = forced_policy == 0 ? (wt_rule ? kStoreWt : kStoreNt) : (forced_policy == (int)kStoreWt ? kStoreWt : kStoreNt);
+    r.burst = forced_burst > 0 ? (uint32_t)forced_burst : (!runs && spans > 1u && text_bytes >= kBurstOneMinBytes ? 1u : 2u);   // (RUNS has no burst: 2 by convention)
+    return r;
+}
+
+// The whole launch decision.  steps_needed: steps(n_items); occupancy: resident blocks per CU of kernel_choice's kernel, as the
+// occupancy API says (>= 1; RUNS: 3); forced_*: the knobs (0 = by rule).
+//
+// Blocks per CU.  Long launches run exactly what is resident (62 VGPRs -> 8 waves/SIMD -> four 512-thread blocks per CU; 25 KB of
+// LDS each): blocks beyond that would only start when the queue is already empty.  Interleaved A/B on the chr22 block: 2 blocks/CU
+// 2.12 ms, 4 blocks/CU 2.00 ms (profiles/r01_kernel_sweeps.md).  SHORT launches (up to ~1 GB of text: a CLI block, a chunk of the two
+// passes) run faster with two blocks per CU (round 3, profiles/r03_kernel_sweeps.md §6).  On a re-used output buffer (what the CLI
+// does) the advantage is large and holds up to ~4.5 GB (N = 2 504: 134 MB 0.51 against 0.45 of roofline, 2.2 GB 0.77 / 0.71, 6 GB
+// 0.69 / 0.73); on FRESH output regions (one call cut into pieces of that size, tools/split_probe.py) it is small and ends earlier:
+// 134 MB 0.457 / 0.442, 0.5 GB level (K = 4 940: 0.584 / 0.569), 2 GB 0.613 / 0.642 — so the rule takes the size both agree on.
+// RUNS: two, not the three the occupancy API allows (45 KB of LDS each): level on 11-GB launches (N = 100 / 300 / 1 000 / 1 900:
+// 0.686 / 0.680 / 0.698 / 0.707 against 0.683 / 0.681 / 0.703 / 0.690) and 8-9 % ahead on the 255-MB launch of the reference's own
+// dataset shape (0.505 against 0.469), whose blocks run only three steps each (round 3: on one box three were ahead again from
+// ~5.5 GB of re-used output — 6.4 M rows of N = 300: 0.73 against 0.69 — which round 2's boxes did not show).  With EIGHT write fronts
+// the three are ahead on every long launch (profiles/r05_stream_rule.md, N = 300: 1.9 / 3.8 / 6.6 / 10.4 GB of text -4.9 / -7.2 / -5.8 / -5.6 %,
+// N = 100 / 1 000 at 11 GB -5.4 / -5.0 %; with two fronts only -0.7 .. -3.5 % at 7-11 GB) and behind on short ones (0.9 GB +5.1 %, 0.5 GB
+// +6.4 %, 255 MB +3.7 %): the occupancy figure above kRunsLongBytes, on the far side of the one size (1.9 GB, re-used output) that
+// the fresh-region effect above could still reach.
+//
+// Write fronts.  Rows of several spans on a launch of >= kFrontSteps steps per block: 8 — on the 212-GB launch of BASELINE
+// configs[2] two fronts ran at 0.73 or 0.78 of roofline depending on where the driver had put the buffer (stable per allocation,
+// 5-7 % apart), eight at 0.784 on every box; 0.765 -> 0.784 on the 266-GB shard of configs[3]; +0.4-2.4 % on 12-GB launches of
+// N = 5 000 .. 100 000.  Rows of one span (the chr22 shape): 2 — four or eight were level on one box and 1.6-2.4 % behind on another
+// (interleaved in one process, chr22 block: 8 ranges 2.058 ms, 4: 2.045, 2: 2.038, 1: 2.039); short launches (the 0.8-GB second pass
+// of the two-pass path: 15 steps per block): 2 — eight cost 9 % there (profiles/r02_kernel_sweeps.md).  RUNS: 2 (1 .. 64 measured level
+// with two blocks per CU); 8 above kRunsLongBytes, where they are what makes the third block per CU pay (above).
+// The joint grid of profiles/r05_stream_rule.md leaves the rest as it was: on the chr22 block four or eight fronts are 2.2-2.6 % AHEAD
+// on one output allocation and 0.4-1.9 % BEHIND on three others of the same process, under either policy and any burst (no arm closes
+// that placement spread); rows of several spans keep 8 fronts and the occupancy figure (4 / 16 fronts, 3 blocks: within 0.4 %).
+PGENHIP_PLAN_HD inline Rule rule(uint64_t text_bytes, uint32_t spans, bool runs, uint64_t steps_needed, int occupancy, int num_cus, int forced_policy,
+                                 int forced_blocks_per_cu, int forced_fronts, int forced_burst)
+{
+    Rule r = kernel_choice(text_bytes, spans, runs, forced_policy, forced_burst);
+    const bool runs_long = runs && text_bytes > kRunsLongBytes;
+    int per_cu = runs && !runs_long ? 2 : std::max(occupancy, 1);   // (short RUNS launches: two whatever the occupancy figure, as ever)
+    if (!runs && text_bytes <= kShortLaunchBytes && per_cu > 2) per_cu = 2;
+    if (forced_blocks_per_cu > 0) per_cu = forced_blocks_per_cu;
+    r.blocks_per_cu = (uint32_t)per_cu;
+    r.grid = grid_blocks(steps_needed, r.blocks_per_cu, num_cus, 0);
+    r.fronts = forced_fronts > 0 ? (uint32_t)forced_fronts : (runs ? runs_long : spans > 1u && steps_needed >= (uint64_t)kFrontSteps * r.grid) ? 8u : 2u;
+    return r;
+}
+
+}  // namespace wide
 
 }  // namespace pgenhip::plan
