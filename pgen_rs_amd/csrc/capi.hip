@@ -66,26 +66,13 @@ int bind(const pgenhip_ctx *ctx)
     return PGENHIP_OK;
 }
 
-// Sparse keeps on long records (BASELINE config 5: 1 % of 500 000 samples) go through TWO passes: the segment kernel writes each
-// row's COMPACT record (the K kept codes packed like a mode-0x02 record of K samples: 41-byte pieces instead of 656-byte pieces of
-// text per row and segment) and the all-samples kernels turn those into text with whole-line stores.  Worth it while the text is
-// small against the records.  Measured band (N = 500 000, profiles/r02_kernel_sweeps.md): 0.5 % kept -2 %, 0.65 % +4 %, 1 % +15 %,
-// 2 % +11 %, 4 % +7 %, 5 % level, 10 % -4 %  ->  0.6 % .. 4.5 % kept.
-// (Short records, N <= 4 096, were tried through the same two passes with a COMPACT instantiation of the short-record pick
-// kernel: 0.42-0.50 of roofline against the single pass's 0.52-0.63 at every density — the compaction costs more than the text
-// it saves there; profiles/r02_kernel_sweeps.md.)
-bool two_pass_shape(uint32_t sample_count, uint32_t kept_count)
-{
-    return sample_count > 4096u && kept_count >= 8u && (uint64_t)kept_count * 170ull >= (uint64_t)sample_count &&
-           (uint64_t)kept_count * 22ull <= (uint64_t)sample_count;
-}
+// What the emit entry points run is decided in plan::emit (launch_plan.h): the shapes each kernel takes, AUTO's chains and their
+// measured thresholds, the forced kernel ids, the chunks of the two passes
+namespace E = plan::emit;
+using E::Emit;
 
 constexpr size_t kWorkBlockBytes = (kMaxQueueRanges + 1u) * 128u;  // the heads 128 B apart + the exit counter
 constexpr size_t kWorkBlockWords = kWorkBlockBytes / sizeof(uint64_t);
-// Two-pass path: every launch in flight has its own slice of compact-record scratch, like its own counter block (launches of one
-// ctx on different streams may overlap: include/pgen_hip.h, "Streams").  A slice holds one chunk of rows between the two passes;
-// a chunk stays in the 256-MiB Infinity Cache, so a smaller one costs only its two extra kernel launches.
-constexpr size_t kCompactSliceBytes = 32u << 20;
 // pgenhip_emit_lines: a bound on the line length (max_prefix_bytes + 4K + 1) below which every kernel can plan its tiles, batches and
 // seams; larger bounds are PGENHIP_ERR_TOO_LARGE before any launch
 constexpr uint64_t kMaxLineBytes = 1ull << 31;
@@ -184,8 +171,8 @@ int pgenhip_create(pgenhip_ctx **out, int device_ordinal, uint32_t sample_count,
             // two-pass path (sparse keeps on long records): scratch for the compact records of one chunk of rows per launch in flight
             // (config 5's per-GPU shard, 125 000 rows x 1 250 bytes, is five chunks; a chunk stays in the 256-MiB Infinity Cache
             // between the two passes); allocated here so that no launch ever allocates
-            if (two_pass_shape(sample_count, kept_count)) {
-                ctx->compact_bytes = kCompactSliceBytes;
+            if (E::two_pass_shape(sample_count, kept_count)) {
+                ctx->compact_bytes = E::kCompactSliceBytes;
                 if ((e = hipMalloc(reinterpret_cast<void **>(&ctx->d_compact), PGENHIP_LAUNCHES_IN_FLIGHT * ctx->compact_bytes)) != hipSuccess) { rc = fail_hip(e, "hipMalloc(compact records)"); break; }
             }
         }
@@ -312,163 +299,49 @@ static int claim_counters(pgenhip_ctx *ctx, EmitArgs &a)
         }                                          \
     } while (0)
 
-// measured crossover (profiles/r01_kernel_sweeps.md: N = 500 000, 0.2 % kept list gather 1.13 ms vs 1.49 ms,
-// 0.4 % kept 1.51 vs 1.47; round 2, with the faster segment kernel: 0.25 % 1.33 vs 1.51, 0.33 % 1.48 vs 1.52, 0.4 % 1.60 vs 1.57): below ~1/280 kept on long records the list gather touches only the kept
-// samples' lines and wins; everywhere else the segment kernels do (they read each record once, wide)
-static bool very_sparse(const pgenhip_ctx *ctx)
-{
-    return ctx->sample_count >= 65536u && (uint64_t)ctx->kept_count * 280ull <= ctx->sample_count;
-}
-
-// Kept subsets on long records through the row-owner kernel WRITING TEXT (gt_rowpick.hip, one pass): the whole kept list fits its LDS
-// table (K <= 16 384) and the launch has enough rows for every resident wave.  Where it is ahead of the segment kernel / the two passes
-// (profiles/r03_kernel_sweeps.md §7, fraction of roofline against the previous dispatch):
-//   * records of one full segment and a thin second one (16 384 < N < 24 576): the segment kernel's blocks are unbalanced there —
-//     N = 16 385 with 10 / 50 % kept 0.57 / 0.55 against 0.39 / 0.38, N = 20 000 with 10 / 30 / 80 % 0.60 / 0.57 / 0.51 against 0.50 / 0.43 / 0.43;
-//   * 2 % .. 20 % kept on longer records: N = 30 000 5 % 0.62 / 0.53, N = 60 000 10 % 0.60 / 0.58, N = 100 000 2 / 5 % 0.65 / 0.62 against 0.62 / 0.56,
-//     N = 500 000 3.2 % 0.62 / 0.58 (level from ~20 %: N = 60 000 25 % 0.565 / 0.571; behind at 50 %).
-// Below 2 % the two passes keep the sparse band (BASELINE configs[4], 1 % of 500 000: one pass reads 86 % and writes 14 % of its bytes
-// everywhere at once and runs at the copy ceiling, 3-6 % behind; N = 200 000 1 %: 0.635 against 0.658).
-// PGENHIP_KNOB_SCAN_ROWPICK = -1 takes it nowhere.
-static bool rowpick_shape(const pgenhip_ctx *ctx, const EmitArgs &a)
-{
-    if (ctx->tune.scan_rowpick == 0 || ctx->sample_count <= kScanSegmentSamples || very_sparse(ctx) || !gt_rowpick_applicable(a, ctx->num_cus)) return false;
-    const uint64_t N = ctx->sample_count, K = ctx->kept_count;
-    if (N < 24576ull) return true;
-    return K * 50ull >= N && K * 5ull <= N;
-}
-
-// What an emit call runs: one of the launchers of kernels.h (run() below), or the two passes (dispatch_two_pass)
-enum class Emit { Rows, Flat, Wide, Runs, LineRuns, Pick, Scan, RowPick, TwoPass };
-
-// AUTO for all samples kept: GT segments at a.out + j * a.out_stride, or full lines (a.line_off / a.prefix_off set).  Two chains:
-// their sample thresholds were measured per mode.
-static Emit choose_all_samples(const EmitArgs &a)
-{
-    if (a.line_off != nullptr) {
-        // long rows: the work-queue stream kernel writes the GT segments in place behind their prefixes (+ a small prefix copy).
-        // From N = 1 400: at N = 1 024 / 1 200 it runs at 0.45 / 0.49 of roofline against 0.48-0.51 for the two kernels below, at
-        // N = 1 500 / 1 900 at 0.56 / 0.60 against 0.49-0.55 (profiles/r02_kernel_sweeps.md)
-        if (gt_wide_lines_applicable(a) && a.sample_count >= 1400u) return Emit::Wide;
-        // short rows, dense records: runs of whole lines (prefix + GT + '\n') assembled in LDS and stored as whole 128-B lines.
-        // Ahead of the pick family's full-line kernel while a run holds seven lines or more (prefixes up to ~90 bytes) and N < 1 000:
-        // 30-byte prefixes, N = 100 / 300 / 500: 0.41 / 0.51 / 0.53 of roofline against 0.36 / 0.44 / 0.49; with 166-byte prefixes a run
-        // is three or four lines and the pick family is ahead at every N (0.37-0.52 against 0.14-0.50); from N = 1 000 it is level or
-        // ahead with short prefixes too (profiles/r03_logs/lines_sweep_after.log)
-        if (gt_lineruns_applicable(a) && gt_lineruns_rows(a) >= 7u && a.sample_count < 1000u) return Emit::LineRuns;
-        // the pick family (identity for a table): rows' interiors + batched seams (gt_pick_lines_kernel); gathered / padded records:
-        // row by row (it writes the prefixes too)
-        if (gt_pick_applicable(a)) return Emit::Pick;
-        return Emit::Rows;
-    }
-    // short rows, dense records (8 <= N <= 1915): runs of rows as one work item, text staged through LDS in 4-KiB groups
-    // so that every 128-B line leaves whole: 0.68-0.71 of roofline from N = 100 to 1500 where the flat kernel had
-    // 0.42-0.56, the pick kernel 0.31-0.62 and the row-item stream kernel 0.51-0.65 (profiles/r02_kernel_sweeps.md)
-    if (gt_runs_preferred(a)) return Emit::Runs;
-    // short rows that are gathered or padded (no contiguous runs): batches of rows through gt_pick.hip with the identity for a
-    // table, several rows per load instruction.  Gathered rows, fraction of roofline, pick / flat / row-item stream kernel:
-    // N = 64 0.46 / 0.28 / -, 300 0.49 / 0.31 / -, 1 399 0.58 / 0.40 / 0.52, 1 500 0.58 / 0.40 / 0.54, 2 504 0.59 / 0.41 / 0.68
-    if (gt_pick_applicable(a) && a.sample_count < 2000u) return Emit::Pick;
-    if (gt_wide_applicable(a)) return Emit::Wide;
-    if (gt_flat_applicable(a)) return Emit::Flat;
-    return Emit::Rows;
-}
-
-// Two passes for sparse keeps on long records, chunk by chunk of as many rows as the compact scratch holds: (1) the row-owner kernel
-// (chunks of many rows; else the segment kernel) compacts each row's kept codes into a K-sample record, (2) what
-// choose_all_samples above picks for those records turns them into text.
-static bool two_pass(const pgenhip_ctx *ctx, const EmitArgs &a)
-{
-    // (full lines: only where the second pass is the stream kernel's LINES mode, K >= 1 024 — below that it would flush row by row)
-    return ctx->tune.scan_two_pass != 0 && ctx->d_compact != nullptr && a.kept_idx != nullptr && a.record_size >= 16u &&
-           ctx->max_seg_count <= kCompactMaxSegCodes &&
-           (a.line_off != nullptr ? a.kept_count >= 1024u : (a.n_variants <= 1u || a.out_stride == 4ull * a.kept_count + 1ull));
-}
-
-// AUTO for a kept subset that is not the identity: one chain for GT segments and full lines (where a kernel writes full lines it
-// writes the prefixes too)
-static Emit choose_subset(const pgenhip_ctx *ctx, const EmitArgs &a)
-{
-    if (rowpick_shape(ctx, a)) return Emit::RowPick;
-    if (two_pass(ctx, a) && !very_sparse(ctx)) return Emit::TwoPass;
-    // full lines only (the line-run kernel needs a.line_off): kept subset on VERY short dense records: runs of whole lines, picks through
-    // its LDS kept table (N = 100, 30-byte prefixes, 50 / 10 % kept: 0.28 / 0.13 of roofline against 0.23 / 0.10 for the pick family's
-    // full-line kernel; from N = 300 that kernel is level or ahead — N = 500: 0.48 / 0.27 against 0.39 / 0.15 — and with long prefixes
-    // always: profiles/r03_logs/lines_sweep_after.log)
-    if (gt_lineruns_applicable(a) && gt_lineruns_rows(a) >= 7u && a.sample_count < 300u) return Emit::LineRuns;
-    // short records (the 1000 Genomes shape with a sample filter): output-driven pick, any density (full lines: interiors + batched
-    // seams; gathered / padded records: row by row)
-    if (gt_pick_applicable(a)) return Emit::Pick;
-    if (very_sparse(ctx) || ctx->record_size < 16u) return Emit::Rows;
-    // the segment kernel (full lines: each GT segment behind its prefix, the prefix kernel the rest)
-    return Emit::Scan;
-}
-
 // The one place a kernel id (the flags of the emit entry points) becomes what runs: AUTO by shape, a forced id where its kernel takes
 // the shape.  Only AUTO treats an identity list (`--include-sam` that keeps everybody: same bytes) as all samples: forced kernels see the list.
 static int choose(const pgenhip_ctx *ctx, EmitArgs &a, uint32_t kernel, Emit &out)
 {
-    const bool lines = a.line_off != nullptr;
-    const char *needs = nullptr;   // a forced kernel's refusal
-    switch (kernel) {
-        case PGENHIP_KERNEL_AUTO:
-            if (ctx->identity) a.kept_idx = nullptr;
-            out = a.kept_idx == nullptr ? choose_all_samples(a) : choose_subset(ctx, a);
-            break;
-        case PGENHIP_KERNEL_ROWS: out = Emit::Rows; break;
-        case PGENHIP_KERNEL_FLAT:
-            out = Emit::Flat;
-            if (!gt_flat_applicable(a)) needs = "PGENHIP_KERNEL_FLAT needs GT segments, all samples kept, N >= 8 and out_stride == 4N+1";
-            break;
-        case PGENHIP_KERNEL_SCAN:
-            out = Emit::Scan;
-            if (!ctx->subset || ctx->record_size < 16u) needs = "PGENHIP_KERNEL_SCAN needs a kept-sample list and N >= 61 (records of >= 16 bytes)";
-            break;
-        case PGENHIP_KERNEL_WIDE:
-            out = Emit::Wide;
-            if (!(lines ? gt_wide_lines_applicable(a) : gt_wide_applicable(a)))
-                needs = "PGENHIP_KERNEL_WIDE needs all samples kept, N >= 1024 and (GT segments) out_stride == 4N+1";
-            break;
-        case PGENHIP_KERNEL_PICK:
-            out = Emit::Pick;
-            if (!gt_pick_applicable(a)) needs = "PGENHIP_KERNEL_PICK needs K >= 1, 61 <= N <= 4096 and (GT segments) out_stride == 4K+1";
-            break;
-        case PGENHIP_KERNEL_RUNS:
-            out = lines ? Emit::LineRuns : Emit::Runs;
-            if (!(lines ? gt_lineruns_applicable(a) : gt_runs_applicable(a)))
-                needs = lines ? "PGENHIP_KERNEL_RUNS (lines) needs dense records, >= 8 kept samples (of <= 4096 with a keep list) and two lines per item"
-                              : "PGENHIP_KERNEL_RUNS needs all samples kept, 8 <= N <= 3831, dense records and text, no variant gather";
-            break;
-        case PGENHIP_KERNEL_ROWPICK:
-            out = Emit::RowPick;   // (the launcher refuses more than 4 096 segments: PGENHIP_ERR_HIP)
-            if (!ctx->subset || ctx->record_size < 16u || ctx->kept_count < 1u || ctx->kept_count > kRowPickMaxKept)
-                needs = "PGENHIP_KERNEL_ROWPICK needs a kept-sample list of 1 .. 16384 samples and N >= 61";
-            break;
-        default:
-            needs = "not a kernel id: the emit entry points take PGENHIP_KERNEL_AUTO, _ROWS, _FLAT, _SCAN, _WIDE, _PICK, _RUNS or _ROWPICK";
+    if (kernel == PGENHIP_KERNEL_AUTO) {
+        if (ctx->identity) a.kept_idx = nullptr;
+        const E::Shape s = emit_shape(a);
+        out = a.kept_idx == nullptr ? E::choose_all_samples(s)
+                                    : E::choose_subset(s, ctx->tune.scan_rowpick != 0, ctx->tune.scan_two_pass != 0, ctx->max_seg_count, ctx->num_cus);
+        return PGENHIP_OK;
     }
-    return needs ? fail(PGENHIP_ERR_BAD_ARG, needs) : PGENHIP_OK;
+    const E::Shape s = emit_shape(a);
+    out = E::forced(kernel, s.lines);
+    if (E::accepts(kernel, s)) return PGENHIP_OK;
+    const char *needs = "not a kernel id: the emit entry points take PGENHIP_KERNEL_AUTO, _ROWS, _FLAT, _SCAN, _WIDE, _PICK, _RUNS or _ROWPICK";
+    switch (kernel) {   // a forced kernel's refusal
+        case PGENHIP_KERNEL_FLAT: needs = "PGENHIP_KERNEL_FLAT needs GT segments, all samples kept, N >= 8 and out_stride == 4N+1"; break;
+        case PGENHIP_KERNEL_SCAN: needs = "PGENHIP_KERNEL_SCAN needs a kept-sample list and N >= 61 (records of >= 16 bytes)"; break;
+        case PGENHIP_KERNEL_WIDE: needs = "PGENHIP_KERNEL_WIDE needs all samples kept, N >= 1024 and (GT segments) out_stride == 4N+1"; break;
+        case PGENHIP_KERNEL_PICK: needs = "PGENHIP_KERNEL_PICK needs K >= 1, 61 <= N <= 4096 and (GT segments) out_stride == 4K+1"; break;
+        case PGENHIP_KERNEL_RUNS:
+            needs = s.lines ? "PGENHIP_KERNEL_RUNS (lines) needs dense records, >= 8 kept samples (of <= 4096 with a keep list) and two lines per item"
+                            : "PGENHIP_KERNEL_RUNS needs all samples kept, 8 <= N <= 3831, dense records and text, no variant gather";
+            break;
+        case PGENHIP_KERNEL_ROWPICK:   // (its launcher refuses more than 4 096 segments: PGENHIP_ERR_HIP)
+            needs = "PGENHIP_KERNEL_ROWPICK needs a kept-sample list of 1 .. 16384 samples and N >= 61";
+            break;
+    }
+    return fail(PGENHIP_ERR_BAD_ARG, needs);
 }
 
 static int run(pgenhip_ctx *ctx, const EmitArgs &a, const ScanArgs &sc, Emit choice);
 
+// The two passes (plan::emit::two_pass), chunk by chunk of plan::emit::chunks: pointer arithmetic and launches only
 static int dispatch_two_pass(pgenhip_ctx *ctx, const EmitArgs &a, const ScanArgs &sc)
 {
     const uint32_t rc_bytes = (a.kept_count + 3u) / 4u;
     uint8_t *const scratch = ctx->d_compact + (size_t)ctx->launch_slot * ctx->compact_bytes;  // this launch's own slice
-    uint64_t chunk_rows = std::max<uint64_t>(1ull, ctx->compact_bytes / rc_bytes);
-    if (ctx->tune.scan_chunk_rows > 0) chunk_rows = std::min<uint64_t>(chunk_rows, (uint64_t)ctx->tune.scan_chunk_rows);
-    // the row-owner compact pass deals rows to its resident waves round-robin: whole rounds per chunk
-    bool row_owner = false;
-    if (ctx->tune.scan_rowpick != 0) {
-        EmitArgs probe = a;
-        probe.n_variants = (uint32_t)std::min<uint64_t>(chunk_rows, a.n_variants);
-        row_owner = gt_rowpick_applicable(probe, ctx->num_cus);
-        const uint64_t round = gt_rowpick_resident_waves(probe, ctx->tune, ctx->num_cus, true);
-        if (row_owner && round && chunk_rows > round && ctx->tune.scan_chunk_rows <= 0) chunk_rows -= chunk_rows % round;
-    }
-    for (uint64_t row0 = 0; row0 < a.n_variants; row0 += chunk_rows) {
-        const uint32_t n = (uint32_t)std::min<uint64_t>(chunk_rows, (uint64_t)a.n_variants - row0);
+    const bool rowpick_on = ctx->tune.scan_rowpick != 0;
+    const uint64_t round_rows = rowpick_on ? gt_rowpick_resident_waves(a, ctx->tune, ctx->num_cus, true) : 0ull;
+    const E::Chunks chunks = E::chunks(emit_shape(a), ctx->compact_bytes, ctx->tune.scan_chunk_rows, rowpick_on, round_rows, ctx->num_cus);
+    for (uint64_t row0 = 0; row0 < a.n_variants; row0 += chunks.rows) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(chunks.rows, (uint64_t)a.n_variants - row0);
         EmitArgs c = a;  // pass 1: this chunk's rows -> compact records
         if (a.record_off) c.record_off = a.record_off + row0;
         else if (a.variant_idx) c.variant_idx = a.variant_idx + row0;
@@ -479,7 +352,7 @@ static int dispatch_two_pass(pgenhip_ctx *ctx, const EmitArgs &a, const ScanArgs
         c.prefix_blob = nullptr;
         c.prefix_off = nullptr;
         c.line_off = nullptr;
-        if (row_owner && (uint64_t)n * 2ull >= chunk_rows)   // (a short last chunk: the segment kernel cuts it finer)
+        if (E::chunk_by_row_owner(chunks, n))
             LAUNCH_TRY(launch_gt_rowpick(c, sc, ctx->tune, ctx->num_cus, ctx->stream, true));   // a wave per row: whole compact records, wide stores
         else
             LAUNCH_TRY(launch_gt_scan(c, sc, ctx->tune, ctx->num_cus, ctx->stream, true));
@@ -498,7 +371,7 @@ static int dispatch_two_pass(pgenhip_ctx *ctx, const EmitArgs &a, const ScanArgs
         } else {
             d.out = a.out + row0 * a.out_stride;
         }
-        const int rc = run(ctx, d, sc, choose_all_samples(d));
+        const int rc = run(ctx, d, sc, E::choose_all_samples(emit_shape(d)));
         if (rc) return rc;
     }
     return PGENHIP_OK;
@@ -530,7 +403,7 @@ struct LineInputs {
 };
 
 // The three emit entry points: GT segments at d_out + j * out_stride (lines == nullptr), or full lines at d_out + line_off[j].
-// A refused forced kernel has claimed its counter block already (the applicability predicates look at a.work_counters).
+// Every launch claims its counter block before the choice (a refused forced kernel has claimed one too).
 static int emit_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
                      const uint64_t *d_record_off, uint32_t n_variants, void *d_out, uint64_t out_stride, const LineInputs *lines, uint32_t flags)
 {

@@ -504,12 +504,11 @@ __device__ __forceinline__ void copy_prefix_rows(const EmitArgs &a, uint32_t shi
 }
 
 
-// lanes per line of copy_prefix_rows as log2, by the launch's longest prefix (ms for 1 M lines of 2 504 samples with 30 / 100 / 166-byte
-// prefixes: 8 lanes 0.055 / 0.123 / 0.217, 16 lanes 0.076 / 0.117 / 0.162, 32 lanes - / 0.136 / 0.171); 0 = the launch has no prefix bytes
+// lanes per line of copy_prefix_rows as log2, by the launch's longest prefix (plan::emit::prefix_copy_shift); 0 = the launch has no prefix bytes
 __host__ __device__ inline uint32_t prefix_copy_shift(const EmitArgs &a)
 {
     if (a.line_off == nullptr || a.prefix_blob == nullptr) return 0u;
-    return a.max_line_bytes - (4ull * a.kept_count + 1ull) <= 48ull ? 3u : 4u;
+    return plan::emit::prefix_copy_shift(a.max_line_bytes - (4ull * a.kept_count + 1ull));
 }
 
 }  // namespace pgenhip

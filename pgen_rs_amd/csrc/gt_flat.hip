@@ -216,13 +216,7 @@ __global__ __launch_bounds__(kThreads) void gt_flat_kernel(EmitArgs a, FlatParam
 
 }  // namespace
 
-bool gt_flat_applicable(const EmitArgs &a)
-{
-    // N >= 8: a row is >= 33 bytes, so a 16-byte chunk meets at most one '\n', and R >= 2
-    return a.kept_idx == nullptr && a.line_off == nullptr && a.sample_count >= 8u &&
-           (a.n_variants <= 1 || a.out_stride == 4ull * a.kept_count + 1ull);
-}
-
+// (the shapes it takes: plan::emit::flat)
 hipError_t launch_gt_flat(const EmitArgs &a, const Tuning &t, int num_cus, hipStream_t stream)
 {
     if (a.n_variants == 0) return hipSuccess;

@@ -32,10 +32,7 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr uint32_t kMaxSamples = 4096;          // R <= 1024: one 16-B piece per lane covers a record
-constexpr uint32_t kStageBytes = 8192;          // per wave: B rows at the padded pitch (PACKED: the batch's contiguous record bytes)
-constexpr int kMaxBatchRows = 12;               // load instructions per batch (one per row; PACKED: one per KiB of the batch's records)
-constexpr uint32_t kMaxPackedRows = 64;         // PACKED batches: rows (their heads are prepared by lane <-> row)
+using namespace plan::emit::pick_family;               // kMaxSamples, kStageBytes, kMaxBatchRows, kMaxPackedRows, kPfxBytes (launch_plan.h)
 
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 
@@ -370,7 +367,6 @@ __global__ __launch_bounds__(kThreads) void gt_pick_kernel(EmitArgs a, PickParam
 // A batch owns the seams BEHIND its rows, so it stages one record more than it has rows (the row behind it), and the launch's first
 // batch also owns the piece in front of row 0.  Offsets are fetched two batches ahead (lane <-> row), so that the prefix bytes of
 // the next batch can be requested together with its records.
-constexpr uint32_t kPfxBytes = 2048;                         // prefix bytes of a batch (+ the row behind it) that the stage holds
 constexpr uint32_t kPfxStage = 16 + 16 + kPfxBytes + 16;     // 16 of slack in front, 15 of misalignment, 16 of slack behind
 
 struct PickLinesParams {
@@ -561,70 +557,36 @@ __global__ __launch_bounds__(kThreads) void gt_pick_lines_kernel(EmitArgs a, Pic
 
 }  // namespace
 
-bool gt_pick_applicable(const EmitArgs &a)
-{
-    // kept subset, record of one tile (16 <= R <= 1024), at least one kept sample (rows of >= 17 bytes: a 16-B chunk touches at
-    // most two rows; K = 1, 2, 3: up to four, built byte by byte), dense output pitch or full-line mode (rows then go out one
-    // by one behind their prefixes)
-    // (kept_idx == NULL: all samples kept — the same kernel with the identity in place of the table)
-    return a.sample_count <= kMaxSamples && a.record_size >= 16u && a.kept_count >= 1u &&
-           (a.line_off != nullptr || a.n_variants <= 1u || a.out_stride == 4ull * a.kept_count + 1ull);
-}
-
+// (the shapes it takes, the batches and the full-line plan: plan::emit::pick, pick_plan, pick_lines_plan)
 hipError_t launch_gt_pick(const EmitArgs &a, const Tuning &t, int num_cus, hipStream_t stream)
 {
     if (a.n_variants == 0) return hipSuccess;
+    const plan::emit::Shape s = emit_shape(a);
+    const plan::emit::PickPlan pp = plan::emit::pick_plan(s, t.pick_batch_bytes);
     PickParams p;
     p.pieces = (a.record_size + 15u) / 16u;
-    p.pitch = p.pieces * 16u;
+    p.pitch = pp.pitch;
     p.row_bytes = 4u * a.kept_count + 1u;
     p.pfx_shift = prefix_copy_shift(a);
     p.align_stores = t.align_stores != 0 ? 1u : 0u;
-    // rows per batch: ~32 KiB of text per batch (8 / 16 / 32 / 64 KiB at 50 % kept on the chr22 shape: 1.44 / 1.41 / 1.37 / 1.36 ms),
-    // what the stage holds, what the register buffer holds
-    const uint32_t batch_bytes = t.pick_batch_bytes > 0 ? (uint32_t)t.pick_batch_bytes : 32768u;
-    uint32_t b = (batch_bytes + p.row_bytes - 1u) / p.row_bytes;
-    b = b < 1u ? 1u : b;
-    // dense records and no gather: the batch's records are one contiguous run (rows at pitch R, up to 64 of them)
-    p.packed = !gathered(a) && (a.n_variants <= 1u || a.record_stride == a.record_size) ? 1u : 0u;
-    if (p.packed) {
-        p.pitch = a.record_size;
-        if (b > kMaxPackedRows) b = kMaxPackedRows;
-        if (b > (kStageBytes - 16u) / p.pitch) b = (kStageBytes - 16u) / p.pitch;  // 15 bytes of misalignment + B * R <= 8 192: >= 7 rows, <= 8 loads
-    } else {
-        // row-by-row loads, G rows per instruction: lanes per row = the record's pieces rounded up to a power of two
-        uint32_t lpr = 1u;
-        while (lpr < p.pieces) lpr <<= 1;
-        p.pitch = lpr * 16u;
-        const uint32_t rows_per_load = 64u / lpr;
-        if (b > (uint32_t)kMaxBatchRows * rows_per_load) b = (uint32_t)kMaxBatchRows * rows_per_load;
-        if (b > kMaxPackedRows) b = kMaxPackedRows;
-        if (b > kStageBytes / p.pitch) b = kStageBytes / p.pitch;  // >= 8 (pitch <= 1024)
-    }
-    p.batch_rows = b;
+    p.packed = pp.packed ? 1u : 0u;
+    p.batch_rows = pp.batch_rows;
     p.magic = (uint32_t)(0x100000000ull / p.row_bytes) + 1u;    // exact up to one compare for run offsets < 2^20 (<= 12 rows of <= 16 385 bytes, or <= 64 rows within 32 KiB + one row)
-    p.n_batches = (uint32_t)(((uint64_t)a.n_variants + b - 1u) / b);
+    p.n_batches = (uint32_t)(((uint64_t)a.n_variants + pp.batch_rows - 1u) / pp.batch_rows);
     // full lines of dense records: interiors + seams, every byte written once as part of a whole chunk (gt_pick_lines_kernel)
-    if (a.line_off != nullptr && p.packed && a.kept_count >= 4u && a.prefix_blob != nullptr) {
-        const uint64_t max_prefix = a.max_line_bytes - (uint64_t)p.row_bytes;
+    const plan::emit::PickLinesPlan pl = plan::emit::pick_lines_plan(s, pp);
+    if (pl.taken) {
         PickLinesParams lp;
-        uint32_t bl = b;
-        if (bl > 62u) bl = 62u;
-        if (15u + (bl + 1u) * a.record_size > kStageBytes) bl = (kStageBytes - 15u) / a.record_size - 1u;           // the row behind the batch comes along
-        if (max_prefix != 0ull && (uint64_t)(bl + 1u) * max_prefix > kPfxBytes - 16u) bl = (uint32_t)((kPfxBytes - 16u) / max_prefix) - 1u;   // and its prefix (two 1-KiB loads from the 16-B boundary below)
-        const uint32_t seam_chunks = (uint32_t)((max_prefix + 31ull) / 16ull);                                         // a seam is at most P + 31 bytes
-        lp.cps_shift = seam_chunks <= 4u ? 2u : (seam_chunks <= 8u ? 3u : (seam_chunks <= 16u ? 4u : (seam_chunks <= 32u ? 5u : 6u)));
-        if (max_prefix <= 993ull && (int32_t)bl >= 2 && bl <= 62u) {
-            lp.batch_rows = bl;
-            lp.n_batches = (uint32_t)(((uint64_t)a.n_variants + bl - 1u) / bl);
-            void (*lk)(EmitArgs, PickLinesParams) = a.kept_idx == nullptr ? gt_pick_lines_kernel<true> : gt_pick_lines_kernel<false>;
-            int lper_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&lper_cu, lk, kThreads, 0) != hipSuccess || lper_cu < 1) lper_cu = 1;
-            const uint64_t lneed = ((uint64_t)lp.n_batches + kWaves - 1ull) / kWaves;
-            const uint64_t lcap = (uint64_t)lper_cu * (uint64_t)num_cus;
-            hipLaunchKernelGGL(lk, dim3((uint32_t)(lneed < lcap ? lneed : lcap)), dim3(kThreads), 0, stream, a, lp);
-            return hipGetLastError();
-        }
+        lp.cps_shift = pl.cps_shift;
+        lp.batch_rows = (uint32_t)pl.batch_rows;
+        lp.n_batches = (uint32_t)(((uint64_t)a.n_variants + lp.batch_rows - 1u) / lp.batch_rows);
+        void (*lk)(EmitArgs, PickLinesParams) = a.kept_idx == nullptr ? gt_pick_lines_kernel<true> : gt_pick_lines_kernel<false>;
+        int lper_cu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&lper_cu, lk, kThreads, 0) != hipSuccess || lper_cu < 1) lper_cu = 1;
+        const uint64_t lneed = ((uint64_t)lp.n_batches + kWaves - 1ull) / kWaves;
+        const uint64_t lcap = (uint64_t)lper_cu * (uint64_t)num_cus;
+        hipLaunchKernelGGL(lk, dim3((uint32_t)(lneed < lcap ? lneed : lcap)), dim3(kThreads), 0, stream, a, lp);
+        return hipGetLastError();
     }
     void (*kern)(EmitArgs, PickParams);
     if (a.kept_idx == nullptr) {

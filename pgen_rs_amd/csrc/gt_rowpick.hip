@@ -39,10 +39,10 @@ __device__ __forceinline__ uint64_t sgpr64_(uint64_t v)   // a wave-uniform valu
     return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v);
 }
 
-// bytes of dynamic LDS: table (K + 8 u16, 16-B rounded) | kept-before-segment (n_seg + 1 u32, 16-B rounded) | per wave: stage + compact record
-__host__ __device__ inline uint32_t table_bytes(uint32_t K) { return (2u * (K + 8u) + 15u) & ~15u; }
-__host__ __device__ inline uint32_t rank_bytes(uint32_t n_seg) { return (4u * (n_seg + 1u) + 15u) & ~15u; }
-__host__ __device__ inline uint32_t codes_bytes(uint32_t K) { return ((K + 3u) / 4u + 16u + 15u) & ~15u; }   // + slack behind the record for the flush's fifth code
+// dynamic LDS: table | kept-before-segment | per wave: stage + compact record (launch_plan.h; plan::emit::rowpick_lds_bytes is their sum)
+using plan::emit::rowpick_codes_bytes;
+using plan::emit::rowpick_rank_bytes;
+using plan::emit::rowpick_table_bytes;
 
 // COMPACT instantiation: instead of text the wave writes the row's compact record itself — ceil(K / 4) bytes at a.out + row *
 // a.out_stride, whole 16-byte chunks — the first pass of the two-pass path (capi.hip): an almost pure record reader, the text is
@@ -53,11 +53,11 @@ __global__ __launch_bounds__(kThreads) void gt_rowpick_kernel(EmitArgs a, ScanAr
     extern __shared__ __attribute__((aligned(16))) uint8_t s_mem[];
     const uint32_t K = a.kept_count;
     uint16_t *const s_idx = reinterpret_cast<uint16_t *>(s_mem);
-    uint32_t *const s_rank = reinterpret_cast<uint32_t *>(s_mem + table_bytes(K));
+    uint32_t *const s_rank = reinterpret_cast<uint32_t *>(s_mem + rowpick_table_bytes(K));
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    uint8_t *const stage = s_mem + table_bytes(K) + rank_bytes(n_seg) + wave * (kStageBytes + codes_bytes(K));
+    uint8_t *const stage = s_mem + rowpick_table_bytes(K) + rowpick_rank_bytes(n_seg) + wave * (kStageBytes + rowpick_codes_bytes(K));
     uint8_t *const codes = stage + kStageBytes;
 
     // (stage_kept_list, gt_common.hip.h: the loads of a batch in flight together, eight zero entries of slack behind the list)
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(kThreads) void gt_rowpick_kernel(EmitArgs a, ScanAr
         for (uint32_t b = 0; b < 4u; b++)
             if (g0 + b * (uint32_t)kThreads <= n_seg) s_rank[g0 + b * (uint32_t)kThreads] = rk[b];
     }
-    for (uint32_t i = lane; i < codes_bytes(K); i += 64u) codes[i] = 0;                     // (the slack bytes are read, never stored)
+    for (uint32_t i = lane; i < rowpick_codes_bytes(K); i += 64u) codes[i] = 0;                     // (the slack bytes are read, never stored)
     __syncthreads();
 
     const uint32_t R = a.record_size;
@@ -267,39 +267,26 @@ __global__ __launch_bounds__(kThreads) void gt_rowpick_kernel(EmitArgs a, ScanAr
 
 }  // namespace
 
-// K <= 16 384 kept samples (the table + a compact record per wave fit the LDS with several blocks per CU), records of at least one
-// 16-byte piece, at most 4 096 segments (N <= 64 M), and enough rows that every resident wave owns some
-bool gt_rowpick_applicable(const EmitArgs &a, int num_cus)
-{
-    const uint32_t n_seg = (a.sample_count + kSegSamples - 1u) / kSegSamples;
-    return a.kept_idx != nullptr && a.kept_count >= 1u && a.kept_count <= kRowPickMaxKept && a.record_size >= 16u && n_seg >= 1u && n_seg <= 4096u &&
-           (uint64_t)a.n_variants >= 8ull * (uint64_t)num_cus * kWaves;
-}
-
 namespace {
 
 struct RowPickLaunch {
     void (*kern)(EmitArgs, ScanArgs, uint32_t);
-    uint32_t n_seg, lds, max_blocks;   // max_blocks: one resident round
+    uint32_t n_seg, lds;
+    plan::emit::RowPickPlan plan;
 };
 
-bool plan(const EmitArgs &a, const Tuning &t, int num_cus, bool compact, RowPickLaunch &L)
+// the kernel, its LDS and plan::emit::rowpick_plan with that kernel's occupancy figure; false: plan::emit::rowpick_takes refuses the shape
+bool plan_launch(const EmitArgs &a, const Tuning &t, int num_cus, bool compact, RowPickLaunch &L)
 {
-    if (a.kept_idx == nullptr || a.kept_count > kRowPickMaxKept) return false;
-    L.n_seg = (a.sample_count + kSegSamples - 1u) / kSegSamples;
-    if (L.n_seg < 1u || L.n_seg > 4096u || a.record_size < 16u) return false;
-    L.lds = table_bytes(a.kept_count) + rank_bytes(L.n_seg) + (uint32_t)kWaves * (kStageBytes + codes_bytes(a.kept_count));
+    if (!plan::emit::rowpick_takes(emit_shape(a))) return false;
+    L.n_seg = plan::emit::n_segments(a.sample_count);
+    L.lds = plan::emit::rowpick_lds_bytes(a.sample_count, a.kept_count);
     const bool g = gathered(a);
     if (compact) L.kern = g ? gt_rowpick_kernel<true, true> : gt_rowpick_kernel<false, true>;
     else L.kern = g ? gt_rowpick_kernel<true, false> : gt_rowpick_kernel<false, false>;
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, L.kern, kThreads, L.lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    // two blocks per CU measure best on long records (the loads of 8 waves per CU already saturate the read path: tools/readbench.hip; 3:
-    // level, 5: -3 %); on records of barely more than one segment, where a row is mostly text to write, all that fit (N = 16 385 with
-    // 10 % kept: 0.51 / 0.57 / 0.56 of roofline at 2 / 3 / 4 per CU; N = 20 000 with 30 %: 0.52 / 0.56 / 0.57)
-    const int want = t.rowpick_blocks_per_cu > 0 ? t.rowpick_blocks_per_cu : (!compact && a.sample_count < 24576u ? 4 : 2);
-    if (want < per_cu) per_cu = want;
-    L.max_blocks = (uint32_t)per_cu * (uint32_t)num_cus;
+    L.plan = plan::emit::rowpick_plan(a.sample_count, a.n_variants, compact, per_cu, t.rowpick_blocks_per_cu, num_cus);
     return true;
 }
 
@@ -310,16 +297,15 @@ bool plan(const EmitArgs &a, const Tuning &t, int num_cus, bool compact, RowPick
 uint32_t gt_rowpick_resident_waves(const EmitArgs &a, const Tuning &t, int num_cus, bool compact)
 {
     RowPickLaunch L;
-    return plan(a, t, num_cus, compact, L) ? L.max_blocks * (uint32_t)kWaves : 0u;
+    return plan_launch(a, t, num_cus, compact, L) ? L.plan.max_blocks * (uint32_t)kWaves : 0u;
 }
 
 hipError_t launch_gt_rowpick(const EmitArgs &a, const ScanArgs &sc, const Tuning &t, int num_cus, hipStream_t stream, bool compact)
 {
     if (a.n_variants == 0) return hipSuccess;
     RowPickLaunch L;
-    if (!plan(a, t, num_cus, compact, L)) return hipErrorInvalidValue;
-    const uint64_t need = ((uint64_t)a.n_variants + kWaves - 1ull) / kWaves;
-    hipLaunchKernelGGL(L.kern, dim3((uint32_t)(need < L.max_blocks ? need : L.max_blocks)), dim3(kThreads), L.lds, stream, a, sc, L.n_seg);
+    if (!plan_launch(a, t, num_cus, compact, L)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(L.kern, dim3(L.plan.grid), dim3(kThreads), L.lds, stream, a, sc, L.n_seg);
     return hipGetLastError();
 }
 

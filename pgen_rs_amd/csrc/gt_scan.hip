@@ -348,54 +348,31 @@ __global__ __launch_bounds__(kThreads) void gt_compact_kernel(EmitArgs a, ScanAr
 
 }  // namespace
 
-// Every block walks the same number of rows, so the launch must be exactly ONE resident round: a grid
-// that exceeds residency by a few blocks runs those in a second round that takes as long as the first.
+// plan::emit::scan_plan (launch_plan.h) with the kernel's occupancy figure: blocks per CU, row groups, block map, bands, grid
 template <typename Kern>
-static uint32_t resident_blocks(Kern kern, int threads, int num_cus, const Tuning &t, int preferred)
+static plan::emit::ScanPlan scan_plan_for(Kern kern, const EmitArgs &a, const Tuning &t, int num_cus, bool compact)
 {
     int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-    if (preferred > 0 && preferred < per_cu) per_cu = preferred;
-    if (t.scan_blocks_per_cu > 0) per_cu = t.scan_blocks_per_cu;
-    return (uint32_t)per_cu * (uint32_t)num_cus;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kThreads, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+    return plan::emit::scan_plan(a.sample_count, a.kept_count, a.n_variants, compact, per_cu, t.scan_blocks_per_cu, t.scan_xcd_map != 0, num_cus);
 }
 
 hipError_t launch_gt_scan(const EmitArgs &a, const ScanArgs &sc, const Tuning &t, int num_cus, hipStream_t stream, bool compact)
 {
     if (a.n_variants == 0) return hipSuccess;
     if (a.kept_idx == nullptr) return hipErrorInvalidValue;
-    const uint32_t n_seg = (a.sample_count + kSegSamples - 1u) / kSegSamples;
-    const uint32_t n_seg_eff = n_seg ? n_seg : 1u;
-    const uint64_t groups_needed = ((uint64_t)a.n_variants + kWaves - 1ull) / kWaves;
-    // One kernel for every density (round 1's three-segment gather kernel kept a 0.8-2 % band; with the XCD-aware block map and
-    // two blocks per CU the pick kernel is ahead there too: 1.5 % kept 1.85 vs 1.99 ms, profiles/r02_kernel_sweeps.md).
-    // Blocks per CU: the occupancy API says 3 (32 KiB table + 16 KiB of stages); from ~0.6 % kept upwards 2 measure the same or
-    // better (+5-9 % at 1-3 % kept, level from 30 %), below that 3 do (the kernel is then a pure record reader).
     if (compact) {
-        // first pass of the two-pass path: a.out / a.out_stride address the compact records (ceil(K / 4) bytes per row)
-        if (sc.max_seg_count > kCompactMaxSegCodes) return hipErrorInvalidValue;  // (capi.hip takes the single pass then)
-        void (*ckern)(EmitArgs, ScanArgs, uint32_t, uint32_t, uint32_t) = gathered(a) ? gt_compact_kernel<true> : gt_compact_kernel<false>;
-        uint64_t groups = (uint64_t)resident_blocks(ckern, kThreads, num_cus, t, 2) / n_seg_eff;  // floor: never a partial second round; two blocks per CU (3: -1 %, 5: -6 %)
-        if (groups < 1ull) groups = 1ull;
-        if (groups > groups_needed) groups = groups_needed;
+        // first pass of the two-pass path: a.out / a.out_stride address the compact records (ceil(K / 4) bytes per row);
         // one narrow window of rows (a record reader: banded -3 %, profiles/r02_kernel_sweeps.md)
-        const uint32_t xcd_groups = t.scan_xcd_map != 0 ? (uint32_t)(groups & ~7ull) : 0u;
-        hipLaunchKernelGGL(ckern, dim3((uint32_t)(groups * n_seg_eff)), dim3(kThreads), 0, stream, a, sc, n_seg_eff, (uint32_t)groups, xcd_groups);
+        if (sc.max_seg_count > kCompactMaxSegCodes) return hipErrorInvalidValue;  // (plan::emit::two_pass takes the single pass then)
+        void (*ckern)(EmitArgs, ScanArgs, uint32_t, uint32_t, uint32_t) = gathered(a) ? gt_compact_kernel<true> : gt_compact_kernel<false>;
+        const plan::emit::ScanPlan p = scan_plan_for(ckern, a, t, num_cus, true);
+        hipLaunchKernelGGL(ckern, dim3(p.grid), dim3(kThreads), 0, stream, a, sc, p.n_seg, p.groups, p.xcd_groups);
         return hipGetLastError();
     }
     void (*kern)(EmitArgs, ScanArgs, uint32_t, uint32_t, uint32_t, uint32_t) = gathered(a) ? gt_scan_pick_kernel<true> : gt_scan_pick_kernel<false>;
-    const int preferred = (uint64_t)a.kept_count * 170ull >= (uint64_t)a.sample_count ? 2 : 0;
-    uint64_t groups = (uint64_t)resident_blocks(kern, kThreads, num_cus, t, preferred) / n_seg_eff;  // floor: never a partial second round
-    if (groups < 1ull) groups = 1ull;  // more segments than resident blocks (N > ~16 M samples): rounds are unavoidable
-    if (groups > groups_needed) groups = groups_needed;
-    const uint32_t xcd_groups = t.scan_xcd_map != 0 ? (uint32_t)(groups & ~7ull) : 0u;
-    const uint32_t grid = (uint32_t)(groups * n_seg_eff);
-    // Eight bands where the text dominates the traffic (>= 10 % kept: N = 500 000, 10 % kept 0.599 -> 0.626 of roofline, 50 % 0.589 ->
-    // 0.593); one front where the launch is mostly a record reader (1 % kept, compact pass: 0.634 vs 0.614 banded; 0.3 % single pass:
-    // 0.741 vs 0.693) — reads like the one narrow window, writes like several fronts (profiles/r02_kernel_sweeps.md)
-    const bool banded = (uint64_t)a.kept_count * 10ull >= (uint64_t)a.sample_count && groups % 8ull == 0ull && groups_needed >= 64ull * groups;
-    const uint32_t bands = banded ? 8u : 1u;   // (every band holds the same number of row groups)
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), 0, stream, a, sc, n_seg_eff, (uint32_t)groups, xcd_groups, bands);
+    const plan::emit::ScanPlan p = scan_plan_for(kern, a, t, num_cus, false);
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(kThreads), 0, stream, a, sc, p.n_seg, p.groups, p.xcd_groups, p.bands);
     return hipGetLastError();
 }
 

@@ -718,9 +718,9 @@ __global__ __launch_bounds__(64 * (NS + 1)) void gt_stream_dyn_kernel(EmitArgs a
 //   C. four 1-KiB stores of whole 128-B lines.
 // Against flushing row by row behind a separate prefix copy (gt_pick.hip LINES: 0.24 of roofline at N = 300) every 128-B line
 // leaves whole, once.
-constexpr uint32_t kLrMaxRows = 30;                       // lines per item (+ the line behind the run)
+using plan::emit::kLrMaxRows;                             // lines per item (+ the line behind the run)
 constexpr uint32_t kLrRecBytes = kSlabBytes;              // slab: [records | prefix bytes | lrel[32] | prel[32]]
-constexpr uint32_t kLrPfxBytes = 768;
+using plan::emit::kLrPfxBytes;
 constexpr uint32_t kLrSlab = kLrRecBytes + kLrPfxBytes + 2u * 32u * 4u;
 
 // one text byte of GT-segment offset x of the record at slab offset rec_off (src/pfile.rs:171-187)
@@ -733,7 +733,7 @@ __device__ __forceinline__ uint32_t run_text_byte(const uint8_t *slab, uint32_t 
 // kept-subset form (PICK): the 2-bit code of kept rank `rank` of the record at `rec` — `tab` is the block's LDS copy of the ascending
 // kept list as u16 (what filter_metadata src/pfile.rs:319-333 yields), with kTabFront / kTabBack entries of slack around it (ranks
 // -4 .. K + 4 occur next to a line's ends; their bytes are never stored)
-constexpr uint32_t kTabFront = 4, kTabBack = 12, kTabMaxSamples = 4096;
+constexpr uint32_t kTabFront = 4, kTabBack = 12, kTabMaxSamples = plan::emit::kLrTabMaxSamples;
 __device__ __forceinline__ uint32_t tab_code(const uint8_t *rec, const uint16_t *tab, int32_t rank)
 {
     const uint32_t s = (uint32_t)tab[rank];
@@ -749,6 +749,15 @@ __device__ __forceinline__ u32x4 tab_text16(const uint8_t *rec, const uint16_t *
     const uint32_t t3 = gt_text(tab_code(rec, tab, g + 3)), t4 = gt_text(tab_code(rec, tab, g + 4));
     return u32x4{funnel_bytes(t0, t1, sh), funnel_bytes(t1, t2, sh), funnel_bytes(t2, t3, sh), funnel_bytes(t3, t4, sh)};
 }
+
+// plan::emit::lineruns_seam_shift, spelled in place: a call into the plan header moves this kernel's registers and schedule, so the
+// kernel keeps the expression and the compiler holds it to the header on both sides of every step
+#define PGENHIP_LR_SEAM_SHIFT(b) ((b) <= 16u ? 2u : ((b) <= 32u ? 3u : ((b) <= 64u ? 4u : ((b) <= 128u ? 5u : 6u))))
+static_assert(PGENHIP_LR_SEAM_SHIFT(1u) == plan::emit::lineruns_seam_shift(1u) && PGENHIP_LR_SEAM_SHIFT(16u) == plan::emit::lineruns_seam_shift(16u) &&
+              PGENHIP_LR_SEAM_SHIFT(17u) == plan::emit::lineruns_seam_shift(17u) && PGENHIP_LR_SEAM_SHIFT(32u) == plan::emit::lineruns_seam_shift(32u) &&
+              PGENHIP_LR_SEAM_SHIFT(33u) == plan::emit::lineruns_seam_shift(33u) && PGENHIP_LR_SEAM_SHIFT(64u) == plan::emit::lineruns_seam_shift(64u) &&
+              PGENHIP_LR_SEAM_SHIFT(65u) == plan::emit::lineruns_seam_shift(65u) && PGENHIP_LR_SEAM_SHIFT(128u) == plan::emit::lineruns_seam_shift(128u) &&
+              PGENHIP_LR_SEAM_SHIFT(129u) == plan::emit::lineruns_seam_shift(129u));
 
 template <bool PICK>
 __device__ __forceinline__ void emit_lines_run(const EmitArgs &a, const WideParams &p, const Item &it, const uint8_t *slab, uint8_t *stage,
@@ -784,7 +793,7 @@ __device__ __forceinline__ void emit_lines_run(const EmitArgs &a, const WidePara
     const float inv_mean = (float)nrows / (float)max(run_len, 1);   // lines per byte of the run (phase A's first guess of a chunk's line)
     // phase B: lanes per seam (log2) by the launch's longest prefix (+ the '\n' in front of it), four bytes per lane
     const uint32_t seam_bytes = (uint32_t)(a.max_line_bytes - (uint64_t)(4u * a.kept_count + 1u)) + 1u;
-    const uint32_t seam_shift = seam_bytes <= 16u ? 2u : (seam_bytes <= 32u ? 3u : (seam_bytes <= 64u ? 4u : (seam_bytes <= 128u ? 5u : 6u)));
+    const uint32_t seam_shift = PGENHIP_LR_SEAM_SHIFT(seam_bytes);
     // (only a prefix shorter than 15 bytes can leave a line's first GT bytes in a chunk that starts back in the previous line)
     const uint32_t plen_v = (uint32_t)__shfl_down((int)pr_v, 1, 64) - pr_v;   // lane l: prefix length of line l (every lane takes part in the shuffle)
     const bool short_prefix = __ballot(lane < nrows + (has_next ? 1u : 0u) && plen_v < 15u) != 0ull;
@@ -1082,20 +1091,6 @@ __global__ __launch_bounds__(64 * (NS + 1)) void gt_lineruns_kernel(EmitArgs a, 
 
 }  // namespace
 
-bool gt_wide_applicable(const EmitArgs &a)
-{
-    // rows of >= 4 KiB keep a wave's span reasonably full; R >= 16 for the clamped window reads
-    return a.kept_idx == nullptr && a.line_off == nullptr && a.sample_count >= 1024u &&
-           (a.n_variants <= 1 || a.out_stride == 4ull * a.kept_count + 1ull);
-}
-
-bool gt_wide_lines_applicable(const EmitArgs &a)
-{
-    // full lines through the work-queue stream kernel: all samples kept, rows of >= 4 KiB, queue heads present
-    return a.kept_idx == nullptr && a.line_off != nullptr && a.prefix_off != nullptr && a.sample_count >= 1024u &&
-           a.work_counters != nullptr;
-}
-
 // the instantiation of the row-item kernel for a rule's store policy and burst
 template <bool HAS_VIDX, bool LINES>
 static auto stream_kernel_for(const plan::wide::Rule &r) -> void (*)(EmitArgs, WideParams)
@@ -1106,7 +1101,7 @@ static auto stream_kernel_for(const plan::wide::Rule &r) -> void (*)(EmitArgs, W
 }
 
 // 1 loader + 7 storer waves; store policy, burst, blocks per CU, write fronts and grid by plan::wide::rule (launch_plan.h), where
-// every measured threshold is stated
+// every measured threshold is stated (the shapes it takes: plan::emit::wide, wide_lines)
 hipError_t launch_gt_wide(const EmitArgs &a, const Tuning &t, int num_cus, hipStream_t stream)
 {
     if (a.n_variants == 0) return hipSuccess;
@@ -1136,40 +1131,19 @@ hipError_t launch_gt_wide(const EmitArgs &a, const Tuning &t, int num_cus, hipSt
 }
 
 // ---- RUNS mode: short rows, B rows per work item ---------------------------------------------------------
-static uint32_t run_rows_for(const EmitArgs &a)
-{
-    if (a.record_size == 0u) return 0u;
-    const uint32_t S = 4u * a.kept_count + 1u;
-    // one 16-B-per-lane load (+ the two shared extra pieces) covers the run's record bytes at any alignment + 1 byte:
-    // 15 + B*R + 1 <= 66 * 16; the run's chunks (+ up to 63 of lead) fit one 1 024-chunk span: B*S/16 + 2 + 63 <= 1 024
-    const uint32_t by_load = 1040u / a.record_size;
-    const uint32_t by_span = 15328u / S;
-    return by_load < by_span ? by_load : by_span;
-}
-
-bool gt_runs_applicable(const EmitArgs &a)
-{
-    // all samples kept, dense records AND dense text (both are then contiguous over a run of rows), rows of >= 33 bytes
-    // (a 16-byte chunk meets at most one '\n') and at least one whole row per item (N <= 3 831)
-    return a.kept_idx == nullptr && a.line_off == nullptr && !gathered(a) && a.sample_count >= 8u &&
-           (a.n_variants <= 1 || (a.out_stride == 4ull * a.kept_count + 1ull && a.record_stride == a.record_size)) &&
-           a.work_counters != nullptr && run_rows_for(a) >= 1u;
-}
-
-// AUTO takes the RUNS mode where an item holds at least two rows (N <= 1 915); with one row per item it is the row-item
-// kernel's work item with LDS-staged text, measured against it in profiles/r02_kernel_sweeps.md
-bool gt_runs_preferred(const EmitArgs &a) { return gt_runs_applicable(a) && run_rows_for(a) >= 2u; }
-
+// (the shapes it takes and the rows of a run: plan::emit::runs, run_rows)
 hipError_t launch_gt_runs(const EmitArgs &a, const Tuning &t, int num_cus, hipStream_t stream)
 {
     if (a.n_variants == 0) return hipSuccess;
-    if (!gt_runs_applicable(a)) return hipErrorInvalidValue;
+    const plan::emit::Shape s = emit_shape(a);
+    if (a.work_counters == nullptr || !plan::emit::runs(s)) return hipErrorInvalidValue;
+    const uint32_t b_max = plan::emit::run_rows(s);
     WideParams p;
     p.row_bytes = 4ull * a.kept_count + 1ull;
     p.total_bytes = (uint64_t)a.n_variants * p.row_bytes;
     p.head = (uint32_t)(((uint64_t)(uintptr_t)a.out) & 127ull);
     p.spans_per_row = 1u;
-    p.run_rows = t.runs_rows > 0 && (uint32_t)t.runs_rows < run_rows_for(a) ? (uint32_t)t.runs_rows : run_rows_for(a);
+    p.run_rows = t.runs_rows > 0 && (uint32_t)t.runs_rows < b_max ? (uint32_t)t.runs_rows : b_max;
     p.run_rec = a.record_size;
     p.magic = (uint32_t)(0x100000000ull / p.row_bytes) + 1u;
     p.pfx_shift = 0u;
@@ -1185,41 +1159,19 @@ hipError_t launch_gt_runs(const EmitArgs &a, const Tuning &t, int num_cus, hipSt
 }
 
 // ---- runs of full LINES: short rows, all samples kept, dense records ---------------------------------------------------------
-static uint32_t lineruns_rows_for(const EmitArgs &a)
-{
-    if (a.record_size == 0u || a.max_line_bytes == 0ull || a.max_line_bytes > 15328ull) return 0u;
-    const uint32_t row_text = 4u * a.kept_count + 1u;
-    const uint32_t max_prefix = (uint32_t)a.max_line_bytes - row_text;
-    uint32_t b = 1040u / a.record_size;                                        // one wide load of the run's records (+ 1 byte)
-    if (a.kept_idx && b) b--;                                                   // kept list: + the whole record behind the run
-    b = std::min<uint32_t>(b, 15328u / (uint32_t)a.max_line_bytes);            // the run's chunks (+ lead) fit one span
-    b = std::min<uint32_t>(b, kLrMaxRows);
-    if (max_prefix) b = std::min<uint32_t>(b, (kLrPfxBytes - 16u) / max_prefix - (((kLrPfxBytes - 16u) / max_prefix) ? 1u : 0u));  // prefixes of B + 1 lines
-    return b;
-}
-
-uint32_t gt_lineruns_rows(const EmitArgs &a) { return lineruns_rows_for(a); }
-
-bool gt_lineruns_applicable(const EmitArgs &a)
-{
-    // all samples, or a kept list of >= 8 samples out of <= 4 096 (its u16 copy lives in LDS); lines of >= 33 bytes of GT text (a
-    // 16-byte chunk meets at most one '\n'); dense records; at least two lines per item
-    const bool samples_ok = a.kept_idx == nullptr ? a.sample_count >= 8u : (a.sample_count <= kTabMaxSamples && a.kept_count >= 8u);
-    return samples_ok && a.line_off != nullptr && a.prefix_off != nullptr && !gathered(a) &&
-           (a.n_variants <= 1 || a.record_stride == a.record_size) && a.work_counters != nullptr && lineruns_rows_for(a) >= 2u;
-}
-
+// (the shapes it takes and the lines of a run: plan::emit::lineruns, lineruns_rows)
 hipError_t launch_gt_lineruns(const EmitArgs &a, const Tuning &t, int num_cus, hipStream_t stream)
 {
     if (a.n_variants == 0) return hipSuccess;
-    if (!gt_lineruns_applicable(a)) return hipErrorInvalidValue;
+    const plan::emit::Shape s = emit_shape(a);
+    if (a.work_counters == nullptr || a.prefix_off == nullptr || !plan::emit::lineruns(s)) return hipErrorInvalidValue;
     WideParams p;
     p.row_bytes = 4ull * a.kept_count + 1ull;
     p.total_bytes = 0ull;
     p.head = (uint32_t)(((uint64_t)(uintptr_t)a.out) & 127ull);
     p.n_ranges = t.wide_ranges > 0 ? (uint32_t)t.wide_ranges : 2u;   // (1 .. 64 measured level in this mode)
     p.spans_per_row = 1u;
-    const uint32_t b_max = lineruns_rows_for(a);
+    const uint32_t b_max = plan::emit::lineruns_rows(s);
     p.run_rows = t.runs_rows > 0 && (uint32_t)t.runs_rows < b_max ? (uint32_t)t.runs_rows : b_max;
     p.run_rec = a.record_size;
     p.magic = 0u;

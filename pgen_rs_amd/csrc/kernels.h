@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launch_plan.h"
+
 namespace pgenhip {
 
 // Which records a launch reads: the selected rows of every kernel family (each argument struct below starts with these fields).
@@ -69,54 +71,61 @@ struct Tuning {
 // rows are gathered (variant list or byte offsets): the HAS_VIDX instantiations
 __host__ __device__ inline bool gathered(const RowSource &a) { return a.variant_idx != nullptr || a.record_off != nullptr; }
 
+// The scalars the emit path decides from (plan::emit of launch_plan.h: applicability, AUTO, launch plans)
+__host__ __device__ inline plan::emit::Shape emit_shape(const EmitArgs &a)
+{
+    plan::emit::Shape s{};
+    s.N = a.sample_count, s.K = a.kept_count, s.R = a.record_size, s.V = a.n_variants;
+    s.kept_list = a.kept_idx != nullptr;
+    s.lines = a.line_off != nullptr;   // (the entry point refuses full lines without prefix_off)
+    s.gathered = gathered(a);
+    s.records_dense = a.n_variants <= 1u || a.record_stride == a.record_size;
+    s.out_dense = a.n_variants <= 1u || a.out_stride == 4ull * a.kept_count + 1ull;
+    s.max_line_bytes = a.max_line_bytes;
+    s.prefix_blob = a.prefix_blob != nullptr;
+    return s;
+}
+
+// The emit launchers.  Which shapes each takes is plan::emit's (flat, wide, wide_lines, runs, lineruns, pick, rowpick_takes); the
+// work-queue kernels (wide, runs, lineruns) also refuse a null a.work_counters.
 // General row-tiled kernel: any alignment, any strides, list gather for kept subsets.
 hipError_t launch_gt_rows(const EmitArgs &a, int num_cus, hipStream_t stream);
 
 // Dense all-samples stream kernel (K = N, out_stride == 4N+1): every lane owns one aligned
 // 16-byte chunk of the whole launch's output stream.
-bool gt_flat_applicable(const EmitArgs &a);
 hipError_t launch_gt_flat(const EmitArgs &a, const Tuning &t, int num_cus, hipStream_t stream);
 
 // Same contract as the flat kernel, but records are staged with wide (16 B/lane) loads through LDS by a loader
-// wave and storer waves issue 16 coalesced 1-KiB stores per work item (rows >= 4 KiB of text; needs work_counters).
-bool gt_wide_applicable(const EmitArgs &a);
-bool gt_wide_lines_applicable(const EmitArgs &a);  // full-line mode (line_off/prefix_off set) through the stream kernel
+// wave and storer waves issue 16 coalesced 1-KiB stores per work item (rows >= 4 KiB of text); also full lines
+// (line_off / prefix_off set).
 hipError_t launch_gt_wide(const EmitArgs &a, const Tuning &t, int num_cus, hipStream_t stream);
 // RUNS mode of the same kernel for SHORT rows (8 <= N <= ~2000, dense records and dense text, no gather): a work item
 // is a run of consecutive rows — one wide load of their contiguous record bytes, their text as one contiguous run.
-bool gt_runs_applicable(const EmitArgs &a);
-bool gt_runs_preferred(const EmitArgs &a);  // what AUTO uses
 hipError_t launch_gt_runs(const EmitArgs &a, const Tuning &t, int num_cus, hipStream_t stream);
 // Runs of FULL LINES (line_off / prefix_off set) on short rows, all samples kept, dense records: prefixes, GT text and '\n' of a
 // run of lines assembled in the storers' LDS stages and stored as whole 128-B lines (gt_wide.hip, gt_lineruns_kernel).
-bool gt_lineruns_applicable(const EmitArgs &a);
-uint32_t gt_lineruns_rows(const EmitArgs &a);  // lines per work item for this shape (records of one wide load, prefix bytes of the slab, one span of text)
 hipError_t launch_gt_lineruns(const EmitArgs &a, const Tuning &t, int num_cus, hipStream_t stream);
 
 // Kept-subset segment kernels: number of kept samples before each segment of kScanSegmentSamples samples.
-constexpr uint32_t kScanSegmentSamples = 16384u;
+using plan::emit::kScanSegmentSamples;
 struct ScanArgs {
     const uint32_t *seg_rank;    // device; n_segments + 1 entries
     uint32_t max_seg_count;      // most kept samples in any one segment
     uint32_t align_stores;       // Tuning::align_stores
 };
-// The compact pass takes segments with at most this many kept samples (a quarter of a segment; the two-pass band is <= 4.5 %
-// kept overall, so only a very clustered list has more in one segment: capi.hip then stays with the single-pass kernel)
-constexpr uint32_t kCompactMaxSegCodes = 4096u;
+using plan::emit::kCompactMaxSegCodes;   // the compact pass takes segments with at most this many kept samples
 // compact = true: write each row's COMPACT record (the K kept codes packed like a mode-0x02 record of K samples) to a.out + j * a.out_stride
 // instead of text: the first pass of the two-pass path for sparse keeps (capi.hip)
 hipError_t launch_gt_scan(const EmitArgs &a, const ScanArgs &sc, const Tuning &t, int num_cus, hipStream_t stream, bool compact = false);
 
 // Sparse kept subsets on long records, one wave per ROW (gt_rowpick.hip): the whole kept list as the LDS table, the row's compact
 // record assembled in LDS segment by segment, its text written in one go.  Any strides / gathers / full lines.
-constexpr uint32_t kRowPickMaxKept = 16384u;
-bool gt_rowpick_applicable(const EmitArgs &a, int num_cus);   // what AUTO requires (incl. enough rows for every resident wave)
+using plan::emit::kRowPickMaxKept;
 // compact = true: the row's COMPACT record (ceil(K / 4) bytes at a.out + row * a.out_stride) instead of its text: first pass of the two-pass path
 uint32_t gt_rowpick_resident_waves(const EmitArgs &a, const Tuning &t, int num_cus, bool compact);   // rows of one round (0: not applicable)
 hipError_t launch_gt_rowpick(const EmitArgs &a, const ScanArgs &sc, const Tuning &t, int num_cus, hipStream_t stream, bool compact = false);
 
 // kept subsets on short records (N <= 4096): output-driven pick through the kept list, no compaction (gt_pick.hip)
-bool gt_pick_applicable(const EmitArgs &a);
 hipError_t launch_gt_pick(const EmitArgs &a, const Tuning &t, int num_cus, hipStream_t stream);
 
 // Per-variant genotype counts (gt_count.hip): four u32 per selected row at counts + 4 * j (hom-ref, het, hom-alt, missing).

@@ -1,12 +1,17 @@
 // launch_plan.h — the launch plans of the analysis kernels (gt_count, gt_scount, gt_score, gt_vsum, gt_matrix, gt_pair, gt_pack,
 // gt_spair, gt_gram, gt_gapply) and the launch rule of the stream kernel (gt_wide): lanes per row, tiles, row ranges ("slices"), grid
-// caps, store policy and write fronts, as functions of scalars.  The single statement
-// of every plan: the launchers call it, the kernels take their constants and their row ranges from it, and the tests compile this
-// header for the host (tests/plan_probe.cpp, tests/gapply_plan_probe.cpp, tests/wide_plan_probe.cpp) and run it.  Plain C++17 on purpose: no HIP header, no argument struct.
+// caps, store policy and write fronts, as functions of scalars; and the emit path (namespace emit): the shapes each emit kernel takes,
+// AUTO's chains and the forced kernel ids, the chunks of the two passes, and the launch plans of the segment, row-owner and pick
+// kernels.  The single statement
+// of every plan: capi.hip and the launchers call it, the kernels take their constants and their row ranges from it, and the tests compile this
+// header for the host (tests/plan_probe.cpp, tests/gapply_plan_probe.cpp, tests/wide_plan_probe.cpp, tests/emit_plan_probe.cpp) and run it.
+// Plain C++17 on purpose: no HIP header, no kernel argument struct (emit::Shape is a struct of scalars).
 #pragma once
 #include <stdint.h>
 
 #include <algorithm>
+
+#include "../../include/pgen_hip.h"   // the kernel ids (plain C)
 
 #ifdef __HIPCC__
 #define PGENHIP_PLAN_HD __host__ __device__ __attribute__((always_inline))
@@ -631,5 +636,429 @@ PGENHIP_PLAN_HD inline Rule rule(uint64_t text_bytes, uint32_t spans, bool runs,
 }
 
 }  // namespace wide
+
+// ---- the emit path: what pgenhip_decode_emit / _at / pgenhip_emit_lines run, and the launch plans of its kernels ----------------------
+namespace emit {
+
+// ---- constants (kernels.h and the .hip files take them from here)
+constexpr uint32_t kWaves = 4;                        // waves of a block of the segment, row-owner and pick kernels (256 threads)
+// Kept-subset segment kernels: the kept list is sliced by segments of this many samples (4 KiB of every record)
+constexpr uint32_t kScanSegmentSamples = 16384u;
+// The compact pass takes segments with at most this many kept samples (a quarter of a segment; the two-pass band is <= 4.5 %
+// kept overall, so only a very clustered list has more in one segment: two_pass() then stays with the single-pass kernel)
+constexpr uint32_t kCompactMaxSegCodes = 4096u;
+// Two-pass path: every launch in flight has its own slice of compact-record scratch, like its own counter block (launches of one
+// ctx on different streams may overlap: include/pgen_hip.h, "Streams").  A slice holds one chunk of rows between the two passes;
+// a chunk stays in the 256-MiB Infinity Cache, so a smaller one costs only its two extra kernel launches.
+constexpr size_t kCompactSliceBytes = 32u << 20;
+// row-owner kernel (gt_rowpick.hip): the whole kept list is its LDS table; segments of a row; rows every resident wave must own under AUTO
+constexpr uint32_t kRowPickMaxKept = 16384u;
+constexpr uint32_t kRowPickMaxSegments = 4096u;       // N <= 64 Mi samples
+constexpr uint32_t kRowPickRowsPerWave = 8u;
+// RUNS and line-run modes of the stream kernel (gt_wide.hip): one 16-B-per-lane load (+ the two shared extra pieces) covers a run's
+// record bytes at any alignment + 1 byte: 15 + B*R + 1 <= 66 * 16; the run's chunks (+ up to 63 of lead) fit one 1 024-chunk span:
+// B*S/16 + 2 + 63 <= 1 024
+constexpr uint32_t kRunLoadBytes = 1040u;
+constexpr uint32_t kRunSpanBytes = 15328u;
+constexpr uint32_t kLrMaxRows = 30;                   // line runs: lines per item (+ the line behind the run)
+constexpr uint32_t kLrPfxBytes = 768;                 // line runs: LDS area of the prefixes of B + 1 lines
+constexpr uint32_t kLrTabMaxSamples = 4096;           // line runs with a kept list: its u16 copy lives in LDS
+
+// the pick family (gt_pick.hip)
+namespace pick_family {
+constexpr uint32_t kMaxSamples = 4096;          // R <= 1024: one 16-B piece per lane covers a record
+constexpr uint32_t kStageBytes = 8192;          // per wave: B rows at the padded pitch (PACKED: the batch's contiguous record bytes)
+constexpr int kMaxBatchRows = 12;               // load instructions per batch (one per row; PACKED: one per KiB of the batch's records)
+constexpr uint32_t kMaxPackedRows = 64;         // PACKED batches: rows (their heads are prepared by lane <-> row)
+constexpr uint32_t kPfxBytes = 2048;            // full lines: prefix bytes of a batch (+ the row behind it) that the stage holds
+constexpr uint32_t kMaxLinesRows = 62;          // full lines: rows of a batch of gt_pick_lines_kernel
+constexpr uint64_t kMaxLinesPrefix = 993;       // full lines: the longest prefix gt_pick_lines_kernel's seams take
+}  // namespace pick_family
+
+// ---- the shape of a call: everything the emit path decides from (kernels.h fills it from an EmitArgs: emit_shape)
+struct Shape {
+    uint32_t N, K, R, V;       // samples, kept samples, record bytes, rows
+    bool kept_list;            // a kept list is present (AUTO has dropped an identity list by then)
+    bool lines;                // full lines (else GT segments at a pitch)
+    bool gathered;             // rows by variant list or record byte offsets
+    bool records_dense;        // record_stride == record_size, or V <= 1
+    bool out_dense;            // GT segments: out_stride == 4K + 1, or V <= 1
+    uint64_t max_line_bytes;   // full lines: bound on prefix + 4K + 1
+    bool prefix_blob;          // full lines: prefix bytes are present
+};
+
+PGENHIP_PLAN_HD constexpr uint32_t row_text_bytes(uint32_t K) { return 4u * K + 1u; }
+// full lines: the bound on a prefix's length
+PGENHIP_PLAN_HD constexpr uint64_t max_prefix(const Shape &s) { return s.max_line_bytes - (4ull * s.K + 1ull); }
+PGENHIP_PLAN_HD constexpr uint32_t n_segments(uint32_t N) { return (N + kScanSegmentSamples - 1u) / kScanSegmentSamples; }
+
+// ---- applicability: the shapes each kernel takes (the launchers that need work-queue counters refuse a null pointer themselves)
+// flat: N >= 8: a row is >= 33 bytes, so a 16-byte chunk meets at most one '\n', and R >= 2
+PGENHIP_PLAN_HD constexpr bool flat(const Shape &s) { return !s.kept_list && !s.lines && s.N >= 8u && s.out_dense; }
+// stream kernel, row items: rows of >= 4 KiB keep a wave's span reasonably full; R >= 16 for the clamped window reads
+PGENHIP_PLAN_HD constexpr bool wide(const Shape &s) { return !s.kept_list && !s.lines && s.N >= 1024u && s.out_dense; }
+// full lines through the stream kernel: all samples kept, rows of >= 4 KiB
+PGENHIP_PLAN_HD constexpr bool wide_lines(const Shape &s) { return !s.kept_list && s.lines && s.N >= 1024u; }
+
+// RUNS: rows per work item (what one wide load and one span hold; 0 from N = 3 832)
+PGENHIP_PLAN_HD constexpr uint32_t run_rows(const Shape &s)
+{
+    if (s.R == 0u) return 0u;
+    const uint32_t by_load = kRunLoadBytes / s.R, by_span = kRunSpanBytes / row_text_bytes(s.K);
+    return by_load < by_span ? by_load : by_span;
+}
+// all samples kept, dense records AND dense text (both are then contiguous over a run of rows), rows of >= 33 bytes
+// (a 16-byte chunk meets at most one '\n') and at least one whole row per item (N <= 3 831)
+PGENHIP_PLAN_HD constexpr bool runs(const Shape &s)
+{
+    return !s.kept_list && !s.lines && !s.gathered && s.N >= 8u && s.out_dense && s.records_dense && run_rows(s) >= 1u;
+}
+// AUTO takes the RUNS mode where an item holds at least two rows (N <= 1 915); with one row per item it is the row-item
+// kernel's work item with LDS-staged text, measured against it in profiles/r02_kernel_sweeps.md
+PGENHIP_PLAN_HD constexpr bool runs_preferred(const Shape &s) { return runs(s) && run_rows(s) >= 2u; }
+
+// line runs: lines per work item (records of one wide load, prefix bytes of the slab, one span of text)
+PGENHIP_PLAN_HD inline uint32_t lineruns_rows(const Shape &s)
+{
+    if (s.R == 0u || s.max_line_bytes == 0ull || s.max_line_bytes > kRunSpanBytes) return 0u;
+    const uint32_t prefix = (uint32_t)s.max_line_bytes - row_text_bytes(s.K);
+    uint32_t b = kRunLoadBytes / s.R;                                          // one wide load of the run's records (+ 1 byte)
+    if (s.kept_list && b) b--;                                                 // kept list: + the whole record behind the run
+    b = std::min<uint32_t>(b, kRunSpanBytes / (uint32_t)s.max_line_bytes);     // the run's chunks (+ lead) fit one span
+    b = std::min<uint32_t>(b, kLrMaxRows);
+    if (prefix) b = std::min<uint32_t>(b, (kLrPfxBytes - 16u) / prefix - (((kLrPfxBytes - 16u) / prefix) ? 1u : 0u));  // prefixes of B + 1 lines
+    return b;
+}
+// all samples, or a kept list of >= 8 samples out of <= 4 096; lines of >= 33 bytes of GT text (a 16-byte chunk meets at most one
+// '\n'); dense records; at least two lines per item
+PGENHIP_PLAN_HD inline bool lineruns(const Shape &s)
+{
+    const bool samples_ok = !s.kept_list ? s.N >= 8u : (s.N <= kLrTabMaxSamples && s.K >= 8u);
+    return samples_ok && s.lines && !s.gathered && s.records_dense && lineruns_rows(s) >= 2u;
+}
+// line runs, phase B: lanes per seam (log2) by the launch's longest prefix + the '\n' in front of it, four bytes per lane
+PGENHIP_PLAN_HD constexpr uint32_t lineruns_seam_shift(uint32_t seam_bytes)
+{
+    return seam_bytes <= 16u ? 2u : (seam_bytes <= 32u ? 3u : (seam_bytes <= 64u ? 4u : (seam_bytes <= 128u ? 5u : 6u)));
+}
+
+// pick family: record of one tile (16 <= R <= 1024), at least one kept sample (rows of >= 17 bytes: a 16-B chunk touches at most
+// two rows; K = 1, 2, 3: up to four, built byte by byte), dense output pitch or full lines (rows then go out one by one behind
+// their prefixes).  No kept list: all samples kept — the same kernel with the identity in place of the table
+PGENHIP_PLAN_HD constexpr bool pick(const Shape &s) { return s.N <= pick_family::kMaxSamples && s.R >= 16u && s.K >= 1u && (s.lines || s.out_dense); }
+
+// row owner, what its launcher takes: K <= 16 384 kept samples (the table + a compact record per wave fit the LDS with several
+// blocks per CU), records of at least one 16-byte piece, at most 4 096 segments
+PGENHIP_PLAN_HD constexpr bool rowpick_takes(const Shape &s)
+{
+    return s.kept_list && s.K <= kRowPickMaxKept && n_segments(s.N) >= 1u && n_segments(s.N) <= kRowPickMaxSegments && s.R >= 16u;
+}
+// ... and what AUTO requires: at least one kept sample and enough rows that every resident wave owns some
+PGENHIP_PLAN_HD constexpr bool rowpick(const Shape &s, int num_cus)
+{
+    return rowpick_takes(s) && s.K >= 1u && (uint64_t)s.V >= (uint64_t)kRowPickRowsPerWave * (uint64_t)num_cus * kWaves;
+}
+
+// lanes per line of the prefix copy (copy_prefix_rows, gt_common.hip.h) as log2, by the launch's longest prefix (ms for 1 M lines of
+// 2 504 samples with 30 / 100 / 166-byte prefixes: 8 lanes 0.055 / 0.123 / 0.217, 16 lanes 0.076 / 0.117 / 0.162, 32 lanes - / 0.136 / 0.171)
+PGENHIP_PLAN_HD constexpr uint32_t prefix_copy_shift(uint64_t max_prefix_bytes) { return max_prefix_bytes <= 48ull ? 3u : 4u; }
+
+// ---- AUTO
+// What an emit call runs: one of the launchers of kernels.h, or the two passes
+enum class Emit { Rows, Flat, Wide, Runs, LineRuns, Pick, Scan, RowPick, TwoPass };
+
+// Sparse keeps on long records (BASELINE config 5: 1 % of 500 000 samples) go through TWO passes: the segment kernel writes each
+// row's COMPACT record (the K kept codes packed like a mode-0x02 record of K samples: 41-byte pieces instead of 656-byte pieces of
+// text per row and segment) and the all-samples kernels turn those into text with whole-line stores.  Worth it while the text is
+// small against the records.  Measured band (N = 500 000, profiles/r02_kernel_sweeps.md): 0.5 % kept -2 %, 0.65 % +4 %, 1 % +15 %,
+// 2 % +11 %, 4 % +7 %, 5 % level, 10 % -4 %  ->  0.6 % .. 4.5 % kept.
+// (Short records, N <= 4 096, were tried through the same two passes with a COMPACT instantiation of the short-record pick
+// kernel: 0.42-0.50 of roofline against the single pass's 0.52-0.63 at every density — the compaction costs more than the text
+// it saves there; profiles/r02_kernel_sweeps.md.)
+// pgenhip_create allocates the compact scratch for exactly these contexts.
+PGENHIP_PLAN_HD constexpr bool two_pass_shape(uint32_t N, uint32_t K)
+{
+    return N > 4096u && K >= 8u && (uint64_t)K * 170ull >= (uint64_t)N && (uint64_t)K * 22ull <= (uint64_t)N;
+}
+
+// measured crossover (profiles/r01_kernel_sweeps.md: N = 500 000, 0.2 % kept list gather 1.13 ms vs 1.49 ms,
+// 0.4 % kept 1.51 vs 1.47; round 2, with the faster segment kernel: 0.25 % 1.33 vs 1.51, 0.33 % 1.48 vs 1.52, 0.4 % 1.60 vs 1.57): below ~1/280 kept on long records the list gather touches only the kept
+// samples' lines and wins; everywhere else the segment kernels do (they read each record once, wide)
+PGENHIP_PLAN_HD constexpr bool very_sparse(uint32_t N, uint32_t K) { return N >= 65536u && (uint64_t)K * 280ull <= N; }
+
+// Kept subsets on long records through the row-owner kernel WRITING TEXT (gt_rowpick.hip, one pass): the whole kept list fits its LDS
+// table (K <= 16 384) and the launch has enough rows for every resident wave.  Where it is ahead of the segment kernel / the two passes
+// (profiles/r03_kernel_sweeps.md §7, fraction of roofline against the previous dispatch):
+//   * records of one full segment and a thin second one (16 384 < N < 24 576): the segment kernel's blocks are unbalanced there —
+//     N = 16 385 with 10 / 50 % kept 0.57 / 0.55 against 0.39 / 0.38, N = 20 000 with 10 / 30 / 80 % 0.60 / 0.57 / 0.51 against 0.50 / 0.43 / 0.43;
+//   * 2 % .. 20 % kept on longer records: N = 30 000 5 % 0.62 / 0.53, N = 60 000 10 % 0.60 / 0.58, N = 100 000 2 / 5 % 0.65 / 0.62 against 0.62 / 0.56,
+//     N = 500 000 3.2 % 0.62 / 0.58 (level from ~20 %: N = 60 000 25 % 0.565 / 0.571; behind at 50 %).
+// Below 2 % the two passes keep the sparse band (BASELINE configs[4], 1 % of 500 000: one pass reads 86 % and writes 14 % of its bytes
+// everywhere at once and runs at the copy ceiling, 3-6 % behind; N = 200 000 1 %: 0.635 against 0.658).
+// rowpick_on: PGENHIP_KNOB_SCAN_ROWPICK (-1 takes it nowhere).
+PGENHIP_PLAN_HD constexpr bool rowpick_shape(const Shape &s, bool rowpick_on, int num_cus)
+{
+    if (!rowpick_on || s.N <= kScanSegmentSamples || very_sparse(s.N, s.K) || !rowpick(s, num_cus)) return false;
+    if (s.N < 24576u) return true;
+    return (uint64_t)s.K * 50ull >= s.N && (uint64_t)s.K * 5ull <= s.N;
+}
+
+// AUTO for all samples kept: GT segments at a pitch, or full lines.  Two chains: their sample thresholds were measured per mode.
+PGENHIP_PLAN_HD inline Emit choose_all_samples(const Shape &s)
+{
+    if (s.lines) {
+        // long rows: the work-queue stream kernel writes the GT segments in place behind their prefixes (+ a small prefix copy).
+        // From N = 1 400: at N = 1 024 / 1 200 it runs at 0.45 / 0.49 of roofline against 0.48-0.51 for the two kernels below, at
+        // N = 1 500 / 1 900 at 0.56 / 0.60 against 0.49-0.55 (profiles/r02_kernel_sweeps.md)
+        if (wide_lines(s) && s.N >= 1400u) return Emit::Wide;
+        // short rows, dense records: runs of whole lines (prefix + GT + '\n') assembled in LDS and stored as whole 128-B lines.
+        // Ahead of the pick family's full-line kernel while a run holds seven lines or more (prefixes up to ~90 bytes) and N < 1 000:
+        // 30-byte prefixes, N = 100 / 300 / 500: 0.41 / 0.51 / 0.53 of roofline against 0.36 / 0.44 / 0.49; with 166-byte prefixes a run
+        // is three or four lines and the pick family is ahead at every N (0.37-0.52 against 0.14-0.50); from N = 1 000 it is level or
+        // ahead with short prefixes too (profiles/r03_logs/lines_sweep_after.log)
+        if (lineruns(s) && lineruns_rows(s) >= 7u && s.N < 1000u) return Emit::LineRuns;
+        // the pick family (identity for a table): rows' interiors + batched seams (gt_pick_lines_kernel); gathered / padded records:
+        // row by row (it writes the prefixes too)
+        if (pick(s)) return Emit::Pick;
+        return Emit::Rows;
+    }
+    // short rows, dense records (8 <= N <= 1915): runs of rows as one work item, text staged through LDS in 4-KiB groups
+    // so that every 128-B line leaves whole: 0.68-0.71 of roofline from N = 100 to 1500 where the flat kernel had
+    // 0.42-0.56, the pick kernel 0.31-0.62 and the row-item stream kernel 0.51-0.65 (profiles/r02_kernel_sweeps.md)
+    if (runs_preferred(s)) return Emit::Runs;
+    // short rows that are gathered or padded (no contiguous runs): batches of rows through gt_pick.hip with the identity for a
+    // table, several rows per load instruction.  Gathered rows, fraction of roofline, pick / flat / row-item stream kernel:
+    // N = 64 0.46 / 0.28 / -, 300 0.49 / 0.31 / -, 1 399 0.58 / 0.40 / 0.52, 1 500 0.58 / 0.40 / 0.54, 2 504 0.59 / 0.41 / 0.68
+    if (pick(s) && s.N < 2000u) return Emit::Pick;
+    if (wide(s)) return Emit::Wide;
+    if (flat(s)) return Emit::Flat;
+    return Emit::Rows;
+}
+
+// Two passes for sparse keeps on long records, chunk by chunk of as many rows as the compact scratch holds: (1) the row-owner kernel
+// (chunks of many rows; else the segment kernel) compacts each row's kept codes into a K-sample record, (2) what
+// choose_all_samples picks for those records turns them into text.  two_pass_on: PGENHIP_KNOB_SCAN_TWO_PASS; max_seg_count: the
+// most kept samples in one segment.
+// (full lines: only where the second pass is the stream kernel's LINES mode, K >= 1 024 — below that it would flush row by row)
+PGENHIP_PLAN_HD constexpr bool two_pass(const Shape &s, bool two_pass_on, uint32_t max_seg_count)
+{
+    return two_pass_on && two_pass_shape(s.N, s.K) && s.kept_list && s.R >= 16u && max_seg_count <= kCompactMaxSegCodes &&
+           (s.lines ? s.K >= 1024u : s.out_dense);
+}
+
+// AUTO for a kept subset that is not the identity: one chain for GT segments and full lines (where a kernel writes full lines it
+// writes the prefixes too)
+PGENHIP_PLAN_HD inline Emit choose_subset(const Shape &s, bool rowpick_on, bool two_pass_on, uint32_t max_seg_count, int num_cus)
+{
+    if (rowpick_shape(s, rowpick_on, num_cus)) return Emit::RowPick;
+    if (two_pass(s, two_pass_on, max_seg_count) && !very_sparse(s.N, s.K)) return Emit::TwoPass;
+    // full lines only (the line-run kernel takes nothing else): kept subset on VERY short dense records: runs of whole lines, picks through
+    // its LDS kept table (N = 100, 30-byte prefixes, 50 / 10 % kept: 0.28 / 0.13 of roofline against 0.23 / 0.10 for the pick family's
+    // full-line kernel; from N = 300 that kernel is level or ahead — N = 500: 0.48 / 0.27 against 0.39 / 0.15 — and with long prefixes
+    // always: profiles/r03_logs/lines_sweep_after.log)
+    if (lineruns(s) && lineruns_rows(s) >= 7u && s.N < 300u) return Emit::LineRuns;
+    // short records (the 1000 Genomes shape with a sample filter): output-driven pick, any density (full lines: interiors + batched
+    // seams; gathered / padded records: row by row)
+    if (pick(s)) return Emit::Pick;
+    if (very_sparse(s.N, s.K) || s.R < 16u) return Emit::Rows;
+    // the segment kernel (full lines: each GT segment behind its prefix, the prefix kernel the rest)
+    return Emit::Scan;
+}
+
+// ---- forced kernel ids (PGENHIP_KERNEL_* of include/pgen_hip.h, AUTO excepted)
+// is it a kernel id of the emit entry points?
+PGENHIP_PLAN_HD constexpr bool is_kernel_id(uint32_t kernel)
+{
+    return kernel == PGENHIP_KERNEL_AUTO || kernel == PGENHIP_KERNEL_ROWS || kernel == PGENHIP_KERNEL_FLAT || kernel == PGENHIP_KERNEL_SCAN ||
+           kernel == PGENHIP_KERNEL_WIDE || kernel == PGENHIP_KERNEL_PICK || kernel == PGENHIP_KERNEL_RUNS || kernel == PGENHIP_KERNEL_ROWPICK;
+}
+// what a forced id runs (RUNS: the line-run kernel for full lines)
+PGENHIP_PLAN_HD constexpr Emit forced(uint32_t kernel, bool lines)
+{
+    return kernel == PGENHIP_KERNEL_FLAT      ? Emit::Flat
+           : kernel == PGENHIP_KERNEL_SCAN    ? Emit::Scan
+           : kernel == PGENHIP_KERNEL_WIDE    ? Emit::Wide
+           : kernel == PGENHIP_KERNEL_PICK    ? Emit::Pick
+           : kernel == PGENHIP_KERNEL_RUNS    ? (lines ? Emit::LineRuns : Emit::Runs)
+           : kernel == PGENHIP_KERNEL_ROWPICK ? Emit::RowPick
+                                              : Emit::Rows;
+}
+// does a call of shape s take this id?  A forced kernel sees the ctx's kept list, an identity list included.  (ROWPICK: its launcher
+// still refuses more than kRowPickMaxSegments segments)
+PGENHIP_PLAN_HD inline bool accepts(uint32_t kernel, const Shape &s)
+{
+    switch (kernel) {
+        case PGENHIP_KERNEL_AUTO:
+        case PGENHIP_KERNEL_ROWS: return true;
+        case PGENHIP_KERNEL_FLAT: return flat(s);
+        case PGENHIP_KERNEL_SCAN: return s.kept_list && s.R >= 16u;
+        case PGENHIP_KERNEL_WIDE: return s.lines ? wide_lines(s) : wide(s);
+        case PGENHIP_KERNEL_PICK: return pick(s);
+        case PGENHIP_KERNEL_RUNS: return s.lines ? lineruns(s) : runs(s);
+        case PGENHIP_KERNEL_ROWPICK: return s.kept_list && s.R >= 16u && s.K >= 1u && s.K <= kRowPickMaxKept;
+        default: return false;
+    }
+}
+
+// ---- the two passes, chunk by chunk
+struct Chunks {
+    uint64_t rows;    // rows of a chunk (the last one may be shorter)
+    bool row_owner;   // pass 1 of a full chunk is the row-owner kernel (else the segment kernel)
+};
+// slice_bytes: the launch's compact scratch; forced_rows: PGENHIP_KNOB_SCAN_CHUNK_ROWS (0 = as many as the slice holds); round_rows:
+// rows of one resident round of the row owner's compact pass (0: it does not take the shape).  The row-owner compact pass deals
+// rows to its resident waves round-robin: whole rounds per chunk
+PGENHIP_PLAN_HD inline Chunks chunks(const Shape &s, uint64_t slice_bytes, int forced_rows, bool rowpick_on, uint64_t round_rows, int num_cus)
+{
+    Chunks c{std::max<uint64_t>(1ull, slice_bytes / ((s.K + 3u) / 4u)), false};
+    if (forced_rows > 0) c.rows = std::min<uint64_t>(c.rows, (uint64_t)forced_rows);
+    if (rowpick_on) {
+        Shape probe = s;
+        probe.V = (uint32_t)std::min<uint64_t>(c.rows, s.V);
+        c.row_owner = rowpick(probe, num_cus);
+        if (c.row_owner && round_rows && c.rows > round_rows && forced_rows <= 0) c.rows -= c.rows % round_rows;
+    }
+    return c;
+}
+// pass 1 of a chunk of n rows through the row owner?  (a short last chunk: the segment kernel cuts it finer)
+PGENHIP_PLAN_HD constexpr bool chunk_by_row_owner(const Chunks &c, uint32_t n) { return c.row_owner && (uint64_t)n * 2ull >= c.rows; }
+
+// ---- launch plan of the segment kernels (gt_scan.hip): text, or the compact pass
+struct ScanPlan {
+    uint32_t n_seg;        // segments of a row (at least 1)
+    uint32_t per_cu;       // blocks per CU planned for
+    uint32_t groups;       // row groups: blocks per segment
+    uint32_t xcd_groups;   // row groups under the XCD-aware block map (0: plain map)
+    uint32_t bands;
+    uint32_t grid;
+};
+// occupancy: resident blocks per CU of the kernel as the occupancy API says (>= 1); forced_per_cu: PGENHIP_KNOB_SCAN_BLOCKS_PER_CU.
+// Every block walks the same number of rows, so the launch must be exactly ONE resident round: a grid that exceeds residency by a few
+// blocks runs those in a second round that takes as long as the first.
+// One kernel for every density (round 1's three-segment gather kernel kept a 0.8-2 % band; with the XCD-aware block map and
+// two blocks per CU the pick kernel is ahead there too: 1.5 % kept 1.85 vs 1.99 ms, profiles/r02_kernel_sweeps.md).
+// Blocks per CU: the occupancy API says 3 (32 KiB table + 16 KiB of stages); from ~0.6 % kept upwards 2 measure the same or
+// better (+5-9 % at 1-3 % kept, level from 30 %), below that 3 do (the kernel is then a pure record reader).  Compact pass: two
+// blocks per CU (3: -1 %, 5: -6 %).
+PGENHIP_PLAN_HD inline ScanPlan scan_plan(uint32_t N, uint32_t K, uint32_t V, bool compact, int occupancy, int forced_per_cu, bool xcd_map, int num_cus)
+{
+    ScanPlan p{};
+    p.n_seg = n_segments(N) ? n_segments(N) : 1u;
+    const uint64_t groups_needed = ((uint64_t)V + kWaves - 1ull) / kWaves;
+    const int preferred = compact || (uint64_t)K * 170ull >= (uint64_t)N ? 2 : 0;
+    int per_cu = std::max(occupancy, 1);
+    if (preferred > 0 && preferred < per_cu) per_cu = preferred;
+    if (forced_per_cu > 0) per_cu = forced_per_cu;
+    p.per_cu = (uint32_t)per_cu;
+    uint64_t groups = (uint64_t)(p.per_cu * (uint32_t)num_cus) / p.n_seg;   // floor: never a partial second round
+    if (groups < 1ull) groups = 1ull;   // more segments than resident blocks (N > ~16 M samples): rounds are unavoidable
+    if (groups > groups_needed) groups = groups_needed;
+    p.groups = (uint32_t)groups;
+    p.xcd_groups = xcd_map ? (uint32_t)(groups & ~7ull) : 0u;
+    p.grid = (uint32_t)(groups * p.n_seg);
+    // Eight bands where the text dominates the traffic (>= 10 % kept: N = 500 000, 10 % kept 0.599 -> 0.626 of roofline, 50 % 0.589 ->
+    // 0.593); one front where the launch is mostly a record reader (1 % kept, compact pass: 0.634 vs 0.614 banded; 0.3 % single pass:
+    // 0.741 vs 0.693) — reads like the one narrow window, writes like several fronts (profiles/r02_kernel_sweeps.md)
+    const bool banded = !compact && (uint64_t)K * 10ull >= (uint64_t)N && groups % 8ull == 0ull && groups_needed >= 64ull * groups;
+    p.bands = banded ? 8u : 1u;   // (every band holds the same number of row groups)
+    return p;
+}
+
+// ---- launch plan of the row-owner kernel (gt_rowpick.hip)
+// bytes of dynamic LDS: table (K + 8 u16, 16-B rounded) | kept-before-segment (n_seg + 1 u32, 16-B rounded) | per wave: stage + compact record
+PGENHIP_PLAN_HD constexpr uint32_t rowpick_table_bytes(uint32_t K) { return (2u * (K + 8u) + 15u) & ~15u; }
+PGENHIP_PLAN_HD constexpr uint32_t rowpick_rank_bytes(uint32_t n_seg) { return (4u * (n_seg + 1u) + 15u) & ~15u; }
+PGENHIP_PLAN_HD constexpr uint32_t rowpick_codes_bytes(uint32_t K) { return ((K + 3u) / 4u + 16u + 15u) & ~15u; }   // + slack behind the record for the flush's fifth code
+PGENHIP_PLAN_HD constexpr uint32_t rowpick_lds_bytes(uint32_t N, uint32_t K)
+{
+    return rowpick_table_bytes(K) + rowpick_rank_bytes(n_segments(N)) + kWaves * (kScanSegmentSamples / 4u + rowpick_codes_bytes(K));
+}
+struct RowPickPlan {
+    uint32_t per_cu;
+    uint32_t max_blocks;   // one resident round
+    uint32_t grid;
+};
+// a shape that rowpick_takes; occupancy: resident blocks per CU with rowpick_lds_bytes of LDS, as the occupancy API says (>= 1);
+// forced_per_cu: PGENHIP_KNOB_ROWPICK_BLOCKS_PER_CU (a cap).
+// Two blocks per CU measure best on long records (the loads of 8 waves per CU already saturate the read path: tools/readbench.hip; 3:
+// level, 5: -3 %); on records of barely more than one segment, where a row is mostly text to write, all that fit (N = 16 385 with
+// 10 % kept: 0.51 / 0.57 / 0.56 of roofline at 2 / 3 / 4 per CU; N = 20 000 with 30 %: 0.52 / 0.56 / 0.57)
+PGENHIP_PLAN_HD inline RowPickPlan rowpick_plan(uint32_t N, uint32_t V, bool compact, int occupancy, int forced_per_cu, int num_cus)
+{
+    RowPickPlan p{};
+    int per_cu = std::max(occupancy, 1);
+    const int want = forced_per_cu > 0 ? forced_per_cu : (!compact && N < 24576u ? 4 : 2);
+    if (want < per_cu) per_cu = want;
+    p.per_cu = (uint32_t)per_cu;
+    p.max_blocks = p.per_cu * (uint32_t)num_cus;
+    const uint64_t need = ((uint64_t)V + kWaves - 1ull) / kWaves;
+    p.grid = (uint32_t)(need < p.max_blocks ? need : p.max_blocks);
+    return p;
+}
+
+// ---- launch plans of the pick family (gt_pick.hip)
+struct PickPlan {
+    bool packed;           // dense records and no gather: the batch's records are one contiguous run (rows at pitch R, up to 64 of them)
+    uint32_t pitch;        // bytes between the rows of a batch in the stage
+    uint32_t batch_rows;
+};
+// rows per batch: ~32 KiB of text per batch (8 / 16 / 32 / 64 KiB at 50 % kept on the chr22 shape: 1.44 / 1.41 / 1.37 / 1.36 ms),
+// what the stage holds, what the register buffer holds.  batch_bytes: PGENHIP_KNOB_PICK_BATCH_BYTES (<= 0: 32 768)
+PGENHIP_PLAN_HD inline PickPlan pick_plan(const Shape &s, int batch_bytes)
+{
+    PickPlan p{};
+    const uint32_t pieces = (s.R + 15u) / 16u;
+    const uint32_t text = batch_bytes > 0 ? (uint32_t)batch_bytes : 32768u;
+    uint32_t b = (text + row_text_bytes(s.K) - 1u) / row_text_bytes(s.K);
+    b = b < 1u ? 1u : b;
+    p.packed = !s.gathered && s.records_dense;
+    if (p.packed) {
+        p.pitch = s.R;
+        if (b > pick_family::kMaxPackedRows) b = pick_family::kMaxPackedRows;
+        if (b > (pick_family::kStageBytes - 16u) / p.pitch) b = (pick_family::kStageBytes - 16u) / p.pitch;  // 15 bytes of misalignment + B * R <= 8 192: >= 7 rows, <= 8 loads
+    } else {
+        // row-by-row loads, G rows per instruction: lanes per row = the record's pieces rounded up to a power of two
+        uint32_t lpr = 1u;
+        while (lpr < pieces) lpr <<= 1;
+        p.pitch = lpr * 16u;
+        const uint32_t rows_per_load = 64u / lpr;
+        if (b > (uint32_t)pick_family::kMaxBatchRows * rows_per_load) b = (uint32_t)pick_family::kMaxBatchRows * rows_per_load;
+        if (b > pick_family::kMaxPackedRows) b = pick_family::kMaxPackedRows;
+        if (b > pick_family::kStageBytes / p.pitch) b = pick_family::kStageBytes / p.pitch;  // >= 8 (pitch <= 1024)
+    }
+    p.batch_rows = b;
+    return p;
+}
+struct PickLinesPlan {
+    bool taken;            // gt_pick_lines_kernel runs (else the row-by-row kernel)
+    int32_t batch_rows;    // (below 2: not taken)
+    uint32_t cps_shift;    // log2 of the chunk slots (lanes) per seam
+};
+// full lines of dense records: interiors + seams, every byte written once as part of a whole chunk (gt_pick_lines_kernel); row by
+// row where a batch would hold fewer than two rows, or prefixes are longer than kMaxLinesPrefix bytes
+PGENHIP_PLAN_HD inline int32_t pick_lines_rows(uint32_t R, uint64_t prefix, uint32_t batch_rows)
+{
+    uint32_t bl = batch_rows;
+    if (bl > pick_family::kMaxLinesRows) bl = pick_family::kMaxLinesRows;
+    if (15u + (bl + 1u) * R > pick_family::kStageBytes) bl = (pick_family::kStageBytes - 15u) / R - 1u;           // the row behind the batch comes along
+    if (prefix != 0ull && (uint64_t)(bl + 1u) * prefix > pick_family::kPfxBytes - 16u) bl = (uint32_t)((pick_family::kPfxBytes - 16u) / prefix) - 1u;   // and its prefix (two 1-KiB loads from the 16-B boundary below)
+    return (int32_t)bl;
+}
+PGENHIP_PLAN_HD constexpr uint32_t pick_cps_shift(uint64_t prefix)
+{
+    const uint32_t seam_chunks = (uint32_t)((prefix + 31ull) / 16ull);   // a seam is at most P + 31 bytes
+    return seam_chunks <= 4u ? 2u : (seam_chunks <= 8u ? 3u : (seam_chunks <= 16u ? 4u : (seam_chunks <= 32u ? 5u : 6u)));
+}
+PGENHIP_PLAN_HD inline PickLinesPlan pick_lines_plan(const Shape &s, const PickPlan &pp)
+{
+    PickLinesPlan p{};
+    if (!(s.lines && pp.packed && s.K >= 4u && s.prefix_blob)) return p;
+    p.batch_rows = pick_lines_rows(s.R, max_prefix(s), pp.batch_rows);
+    p.cps_shift = pick_cps_shift(max_prefix(s));
+    p.taken = max_prefix(s) <= pick_family::kMaxLinesPrefix && p.batch_rows >= 2 && p.batch_rows <= (int32_t)pick_family::kMaxLinesRows;
+    return p;
+}
+
+}  // namespace emit
 
 }  // namespace pgenhip::plan

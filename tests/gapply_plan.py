@@ -1,48 +1,14 @@
 """The launch plan of gt_gapply.hip, RUN from csrc/launch_plan.h (namespace plan::gapply) rather than restated, for the tests that
-are placed around its constants and its slices.  Like tests/launch_plan.py: tests/gapply_plan_probe.cpp is compiled with g++ into a
-directory under the system temp dir, named by a hash of the two sources, and loaded with ctypes; nothing is written into the
-repository, and a failed compile is an error."""
+are placed around its constants and its slices.  tests/gapply_plan_probe.cpp is built and loaded by tests/launch_plan.py (``load``),
+as every probe is."""
 from __future__ import annotations
 
-import ctypes
-import hashlib
-import os
-import subprocess
-import tempfile
+import functools
 from collections import namedtuple
-from pathlib import Path
 
-TESTS = Path(__file__).resolve().parent
-PROBE = TESTS / "gapply_plan_probe.cpp"
-HEADER = TESTS.parent / "pgen_rs_amd" / "csrc" / "launch_plan.h"
+import launch_plan
 
-
-def _build() -> Path:
-    digest = hashlib.sha256(PROBE.read_bytes() + HEADER.read_bytes()).hexdigest()[:16]
-    out_dir = Path(tempfile.gettempdir()) / f"pgen_gapply_plan_probe_{os.getuid()}_{digest}"
-    lib = out_dir / "gapply_plan_probe.so"
-    if not lib.exists():
-        out_dir.mkdir(parents=True, exist_ok=True)
-        tmp = out_dir / f"gapply_plan_probe.{os.getpid()}.so"
-        cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-shared", "-fPIC", "-o", str(tmp), str(PROBE)]
-        proc = subprocess.run(cmd, capture_output=True, text=True)
-        if proc.returncode != 0:
-            raise RuntimeError(f"gapply plan probe did not compile ({' '.join(cmd)}):\n{proc.stdout}{proc.stderr}")
-        os.replace(tmp, lib)   # atomic: parallel test processes never load a half-written file
-    return lib
-
-
-_lib = ctypes.CDLL(str(_build()))
-
-
-def _call(name: str, n_out: int, *args: int) -> tuple[int, ...]:
-    fn = getattr(_lib, name)
-    fn.restype = None
-    fn.argtypes = [ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_uint64)]
-    a = (ctypes.c_int64 * max(len(args), 1))(*[int(x) for x in args])
-    out = (ctypes.c_uint64 * n_out)()
-    fn(a, out)
-    return tuple(out)
+_call = functools.partial(launch_plan.call_into, launch_plan.load("gapply_plan_probe"))
 
 
 (THREADS, WAVES, GROUP, ROW_TILE, STEP_SAMPLES, SAMPLE_TILE, STEP_ROWS, MIN_SLICE_SAMPLES, MIN_SLICE_ROWS, MAX_GRID_TILES,

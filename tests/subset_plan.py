@@ -1,24 +1,21 @@
-"""The kept-subset GT path's dispatch and launch plans, restated from csrc/ so that the subset tests can place their cells on both
-sides of every edge AUTO and the kernels' launch plans derive from N, K, V and the CU count.  numpy only (no torch): the CPU
-coverage test imports the cell table from here.
+"""The kept-subset GT path's dispatch and launch plans, RUN from csrc/launch_plan.h (namespace plan::emit, through
+tests/emit_plan_probe.cpp and tests/launch_plan.py) so that the subset tests can place their cells on both sides of every edge AUTO
+and the kernels' launch plans derive from N, K, V and the CU count.  numpy only (no torch): the CPU coverage test imports the cell
+table from here.
 
-Mirrors (keep in step; test_subset_plan.py checks the constants and literals against the sources):
-  * AUTO's kept-subset dispatch in capi.hip: ``two_pass_shape``, ``very_sparse``, ``rowpick_shape``, ``two_pass``, the one chain of
-    ``choose_subset`` (GT segments and full lines), ``kCompactSliceBytes`` and the chunking of ``dispatch_two_pass`` (chunk rows,
-    rounding to whole row-owner rounds, the short last chunk that goes to the segment kernel);
-  * the forced kernel ids' checks in ``choose`` (capi.hip) and the ``gt_*_applicable`` predicates behind them: ``accepts``;
-  * the segment kernel's launch plan, ``launch_gt_scan`` (gt_scan.hip): ``n_seg``, ``groups`` (clamped to 1 when one resident round
-    cannot hold a block per segment: the grid then runs in rounds), ``xcd_groups``, ``bands``; the compact pass's plan;
-  * the row-owner kernel's ``plan`` / ``gt_rowpick_applicable`` (gt_rowpick.hip): LDS bytes, blocks per CU, ``max_blocks``;
-  * ``kScanSegmentSamples``, ``kCompactMaxSegCodes``, ``kRowPickMaxKept`` (kernels.h).
+What the header decides and this module only asks for: AUTO's kept-subset chain (``two_pass_shape``, ``very_sparse``,
+``rowpick_shape``, ``two_pass``, ``choose_subset``), the forced kernel ids (``accepts``), the chunks of the two passes, the launch
+plans of the segment and row-owner kernels, and every constant.  What lives here: the cell table, ``kept_list``, the arm and edge
+bookkeeping, and the occupancy figures.
 
-Occupancy-API results cannot be computed on a CPU; they are restated below as constants with their derivation and are UNMEASURED
-(gfx950: 160 KiB of LDS per CU, at most 32 waves = 8 four-wave blocks per CU).  Every GPU cell whose arm depends on one of them
-also runs with the blocks-per-CU knob set explicitly.
+Occupancy-API results cannot be computed on a CPU; they are stated below as constants with their derivation, are UNMEASURED
+(gfx950: 160 KiB of LDS per CU, at most 32 waves = 8 four-wave blocks per CU) and go into the header's plans as arguments, where the
+launchers pass what the occupancy API says.  Every GPU cell whose arm depends on one of them also runs with the blocks-per-CU knob
+set explicitly.
 
 Unreachable edges (listed, not tested): ``two_pass_shape``'s K >= 8 (K * 170 >= N > 4 096 already means K >= 25); ``two_pass``'s
-record_size >= 16 (N > 4 096 means R >= 1 024); the compact pass's own max_seg_count > 4 096 refusal (capi.hip's ``two_pass``
-checks it first); the row owner's n_seg >= 1 (R >= 16 means N >= 61).
+record_size >= 16 (N > 4 096 means R >= 1 024); the compact pass's own max_seg_count > 4 096 refusal (``two_pass`` checks it
+first); the row owner's n_seg >= 1 (R >= 16 means N >= 61).
 """
 from __future__ import annotations
 
@@ -28,16 +25,18 @@ from typing import Optional
 
 import numpy as np
 
-# kernels.h
-SEG_SAMPLES = 16384          # kScanSegmentSamples
-COMPACT_MAX_SEG_CODES = 4096  # kCompactMaxSegCodes
-ROWPICK_MAX_KEPT = 16384     # kRowPickMaxKept
-# capi.hip
-COMPACT_SLICE_BYTES = 32 << 20   # kCompactSliceBytes: one slice per launch in flight
-# gt_rowpick.hip
-ROWPICK_MAX_SEGS = 4096      # plan / gt_rowpick_applicable: n_seg <= 4096 (N <= 64 Mi samples)
-ROWPICK_ROWS_PER_WAVE = 8    # gt_rowpick_applicable: V >= 8 * num_cus * kWaves
-WAVES = 4                    # kWaves of the segment and row-owner kernels (256 threads)
+import launch_plan
+
+_call = functools.partial(launch_plan.call_into, launch_plan.load("emit_plan_probe"))
+
+# plan::emit's constants (test_subset_plan.py and test_line_plan.py pin their values)
+(WAVES, SEG_SAMPLES, COMPACT_MAX_SEG_CODES, COMPACT_SLICE_BYTES, ROWPICK_MAX_KEPT, ROWPICK_MAX_SEGS, ROWPICK_ROWS_PER_WAVE, RUN_LOAD_BYTES,
+ RUN_SPAN_BYTES, LR_MAX_ROWS, LR_PFX_BYTES, LR_TAB_MAX_SAMPLES, PICK_MAX_SAMPLES, PICK_STAGE_BYTES, PICK_MAX_BATCH_ROWS, PICK_MAX_PACKED_ROWS,
+ PICK_PFX_BYTES, PICK_MAX_LINES_ROWS, PICK_MAX_LINES_PREFIX) = _call("emit_constants", 19)
+
+# plan::emit::Emit, by value
+CHOICES = ("rows", "flat", "wide", "runs", "lineruns", "pick", "scan", "rowpick", "two_pass")
+assert _call("emit_choices", len(CHOICES)) == tuple(range(len(CHOICES)))
 
 # ---- occupancy (UNMEASURED: what the occupancy API is expected to say, from the LDS each block holds) ---------------------------
 LDS_PER_CU = 160 * 1024
@@ -52,20 +51,25 @@ NUM_CUS = 256                # MI355X; the GPU tests use the device's own count
 
 
 def record_size(n: int) -> int:
+    """pgenhip_variant_record_size: bytes of a record of n samples."""
     return (2 * n + 7) // 8
 
 
+def shape(n: int, k: int, v: int = 2, *, kept_list: bool, lines: bool = False, gathered: bool = False, records_dense: bool = True,
+          out_dense: bool = True, bound: int = 0, prefix_blob: bool = True) -> tuple:
+    """The scalars of a plan::emit::Shape, in the order of its fields (what kernels.h's emit_shape fills from a call): V rows of N
+    samples, K kept; `bound`: max_prefix_bytes of a full-line call; one row is dense whatever its strides."""
+    return (n, k, record_size(n), v, kept_list, lines, gathered, records_dense or v <= 1, out_dense or v <= 1, bound + 4 * k + 1 if lines else 0,
+            prefix_blob)
+
+
 def n_segments(n: int) -> int:
-    return (n + SEG_SAMPLES - 1) // SEG_SAMPLES
-
-
-def _r16(x: int) -> int:
-    return (x + 15) & ~15
+    return _call("emit_n_segments", 1, n)[0]
 
 
 def rowpick_lds_bytes(n: int, k: int) -> int:
     """Dynamic LDS of one row-owner block: table | kept-before-segment | four waves x (stage + compact record)."""
-    return _r16(2 * (k + 8)) + _r16(4 * (n_segments(n) + 1)) + WAVES * (SEG_SAMPLES // 4 + _r16((k + 3) // 4 + 16))
+    return _call("emit_rowpick_lds_bytes", 1, n, k)[0]
 
 
 def rowpick_occupancy(n: int, k: int) -> int:
@@ -146,80 +150,56 @@ class Tune:
         return {name: value for name, value in self.__dict__.items() if value}
 
 
-def scan_plan(n: int, k: int, v: int, tune: Tune = Tune(), num_cus: int = NUM_CUS, compact: bool = False) -> ScanPlan:
-    """launch_gt_scan (gt_scan.hip)."""
-    n_seg = max(1, n_segments(n))
-    groups_needed = (v + WAVES - 1) // WAVES
-    occ = COMPACT_OCCUPANCY if compact else SCAN_OCCUPANCY
-    preferred = 2 if compact or k * 170 >= n else 0
-    per_cu = min(occ, preferred) if preferred > 0 else occ
-    if tune.scan_blocks_per_cu > 0:
-        per_cu = tune.scan_blocks_per_cu
-    resident = per_cu * num_cus
-    groups = max(1, resident // n_seg)
-    groups = min(groups, groups_needed)
-    xcd_groups = groups & ~7 if tune.scan_xcd_map >= 0 else 0
-    banded = not compact and k * 10 >= n and groups % 8 == 0 and groups_needed >= 64 * groups
-    grid = groups * n_seg
-    return ScanPlan(n_seg, per_cu, groups, xcd_groups, 8 if banded else 1, grid, grid > resident)
+def scan_plan(n: int, k: int, v: int, tune: Tune = Tune(), num_cus: int = NUM_CUS, compact: bool = False, occupancy: Optional[int] = None) -> ScanPlan:
+    """plan::emit::scan_plan, what launch_gt_scan (gt_scan.hip) launches, with the unmeasured occupancy figure (or `occupancy`)."""
+    occ = occupancy if occupancy is not None else COMPACT_OCCUPANCY if compact else SCAN_OCCUPANCY
+    n_seg, per_cu, groups, xcd_groups, bands, grid = _call("emit_scan_plan", 6, n, k, v, compact, occ, tune.scan_blocks_per_cu, tune.scan_xcd_map >= 0, num_cus)
+    return ScanPlan(n_seg, per_cu, groups, xcd_groups, bands, grid, grid > per_cu * num_cus)
 
 
-def rowpick_plan(n: int, k: int, v: int, tune: Tune = Tune(), num_cus: int = NUM_CUS, compact: bool = False) -> Optional[RowPickPlan]:
-    """plan + launch_gt_rowpick (gt_rowpick.hip); None where plan() refuses."""
-    if k > ROWPICK_MAX_KEPT or not 1 <= n_segments(n) <= ROWPICK_MAX_SEGS or record_size(n) < 16:
+def rowpick_plan(n: int, k: int, v: int, tune: Tune = Tune(), num_cus: int = NUM_CUS, compact: bool = False, occupancy: Optional[int] = None) -> Optional[RowPickPlan]:
+    """plan::emit::rowpick_plan, what launch_gt_rowpick (gt_rowpick.hip) launches, with the unmeasured occupancy figure (or
+    `occupancy`); None where it refuses (rowpick_takes)."""
+    if not _call("emit_applicable", 11, *shape(n, k, v, kept_list=True), num_cus)[7]:
         return None
     lds = rowpick_lds_bytes(n, k)
-    want = tune.rowpick_blocks_per_cu if tune.rowpick_blocks_per_cu > 0 else (4 if not compact and n < 24576 else 2)
-    per_cu = min(rowpick_occupancy(n, k), want)
-    max_blocks = per_cu * num_cus
-    return RowPickPlan(lds, per_cu, max_blocks, min((v + WAVES - 1) // WAVES, max_blocks), lds > LDS_64K)
+    occ = occupancy if occupancy is not None else rowpick_occupancy(n, k)
+    per_cu, max_blocks, grid = _call("emit_rowpick_plan", 3, n, v, compact, occ, tune.rowpick_blocks_per_cu, num_cus)
+    return RowPickPlan(lds, per_cu, max_blocks, grid, lds > LDS_64K)
 
 
 def rowpick_applicable(n: int, k: int, v: int, num_cus: int = NUM_CUS) -> bool:
-    return (1 <= k <= ROWPICK_MAX_KEPT and record_size(n) >= 16 and 1 <= n_segments(n) <= ROWPICK_MAX_SEGS
-            and v >= ROWPICK_ROWS_PER_WAVE * num_cus * WAVES)
+    return bool(_call("emit_applicable", 11, *shape(n, k, v, kept_list=True), num_cus)[8])
 
 
 def two_pass_shape(n: int, k: int) -> bool:
-    return n > 4096 and k >= 8 and k * 170 >= n and k * 22 <= n
+    return bool(_call("emit_two_pass_shape", 1, n, k)[0])
 
 
 def very_sparse(n: int, k: int) -> bool:
-    return n >= 65536 and k * 280 <= n
+    return bool(_call("emit_very_sparse", 1, n, k)[0])
 
 
 def rowpick_shape(n: int, k: int, v: int, tune: Tune, num_cus: int) -> bool:
-    if tune.rowpick_mode() == 0 or n <= SEG_SAMPLES or very_sparse(n, k) or not rowpick_applicable(n, k, v, num_cus):
-        return False
-    if n < 24576:
-        return True
-    return k * 50 >= n and k * 5 <= n
+    return bool(_call("emit_rowpick_shape", 1, *shape(n, k, v, kept_list=True), tune.rowpick_mode() != 0, num_cus)[0])
 
 
 def two_pass(n: int, k: int, msc: int, lines: bool, tune: Tune) -> bool:
-    """capi.hip two_pass for a kept list that is not the identity, dense output pitch (the cells' only pitch)."""
-    return tune.scan_two_pass >= 0 and two_pass_shape(n, k) and record_size(n) >= 16 and msc <= COMPACT_MAX_SEG_CODES and (
-        k >= 1024 if lines else True)
+    """plan::emit::two_pass for a kept list that is not the identity, dense output pitch (the cells' only pitch)."""
+    return bool(_call("emit_two_pass", 1, *shape(n, k, kept_list=True, lines=lines), tune.scan_two_pass >= 0, msc)[0])
 
 
 def two_pass_chunks(n: int, k: int, v: int, tune: Tune, num_cus: int):
-    """dispatch_two_pass: (chunk rows, ((rows, pass-1 kernel, pass-1 plan), ...))."""
-    rc = (k + 3) // 4
-    chunk = max(1, COMPACT_SLICE_BYTES // rc)
-    if tune.scan_chunk_rows > 0:
-        chunk = min(chunk, tune.scan_chunk_rows)
-    row_owner = False
-    if tune.rowpick_mode() != 0:
-        probe_v = min(chunk, v)
-        row_owner = rowpick_applicable(n, k, probe_v, num_cus)
-        rp = rowpick_plan(n, k, probe_v, tune, num_cus, compact=True)
-        rnd = rp.max_blocks * WAVES if rp else 0
-        if row_owner and rnd and chunk > rnd and tune.scan_chunk_rows <= 0:
-            chunk -= chunk % rnd
+    """The chunks dispatch_two_pass (capi.hip) walks: (chunk rows, ((rows, pass-1 kernel, pass-1 plan), ...)), by plan::emit::chunks
+    and chunk_by_row_owner."""
+    rp = rowpick_plan(n, k, v, tune, num_cus, compact=True) if tune.rowpick_mode() != 0 else None
+    round_rows = rp.max_blocks * WAVES if rp else 0   # gt_rowpick_resident_waves
+    chunk, row_owner = _call("emit_chunks", 2, *shape(n, k, v, kept_list=True), COMPACT_SLICE_BYTES, tune.scan_chunk_rows, tune.rowpick_mode() != 0,
+                             round_rows, num_cus)
     out = []
     for row0 in range(0, v, chunk):
         rows = min(chunk, v - row0)
-        if row_owner and rows * 2 >= chunk:
+        if _call("emit_chunk_by_row_owner", 1, chunk, row_owner, rows)[0]:
             out.append((rows, "rowpick", rowpick_plan(n, k, rows, tune, num_cus, compact=True)))
         else:
             out.append((rows, "scan", scan_plan(n, k, rows, tune, num_cus, compact=True)))
@@ -231,43 +211,31 @@ KERNEL_IDS = {"auto": 0, "rows": 1, "flat": 2, "scan": 3, "wide": 4, "pick": 6, 
 
 
 def runs_rows(n: int) -> int:
-    """Rows per work item of the RUNS mode, all samples kept (gt_wide.hip run_rows_for): one wide load of the run's records and one
+    """Rows per work item of the RUNS mode, all samples kept (plan::emit::run_rows): one wide load of the run's records and one
     span of its text; 0 from N = 3 832 (no whole row of 4N + 1 bytes in a span)."""
-    import line_plan as LP
-
-    r = record_size(n)
-    return min(LP.LR_LOAD_BYTES // r, LP.SPAN_BYTES // (4 * n + 1)) if r else 0
+    return _call("emit_applicable", 11, *shape(n, n, kept_list=False), NUM_CUS)[9]
 
 
 def accepts(kernel: int, n: int, k: int, subset: bool, bound: int = 0, gather: bool = False, mode: str = "lines",
             dense_pitch: bool = True) -> bool:
     """Does a call of more than one row take this kernel id: pgenhip_emit_lines (mode "lines", `bound` = max_prefix_bytes) or
-    pgenhip_decode_emit / _at (mode "segments", `dense_pitch`: out_stride == 4K + 1)?  capi.hip's ``choose`` and the kernels'
-    applicability, for dense records.  `subset`: the ctx has a kept list (an identity list is one: forced kernels see it);
-    `gather`: a variant list or record byte offsets.  False for AUTO's neighbours that are no kernel id (5, 9 .. 15, bits above
-    the mask)."""
-    import line_plan as LP   # (it imports this module's constants: not at the top)
+    pgenhip_decode_emit / _at (mode "segments", `dense_pitch`: out_stride == 4K + 1)?  plan::emit::accepts, for dense records.
+    `subset`: the ctx has a kept list (an identity list is one: forced kernels see it); `gather`: a variant list or record byte
+    offsets.  False for AUTO's neighbours that are no kernel id (5, 9 .. 15, bits above the mask)."""
+    s = shape(n, k, kept_list=subset, lines=mode == "lines", gathered=gather, out_dense=dense_pitch, bound=bound)
+    taken, is_id, _ = _call("emit_accepts", 3, *s, kernel)
+    return bool(taken and is_id)
 
-    lines = mode == "lines"
-    name = {v: key for key, v in KERNEL_IDS.items()}.get(kernel)
-    if name is None:
-        return False
-    if name in ("auto", "rows"):
-        return True
-    if name == "scan":
-        return subset and record_size(n) >= 16
-    if name == "rowpick":
-        return subset and record_size(n) >= 16 and 1 <= k <= ROWPICK_MAX_KEPT
-    if name == "pick":
-        return record_size(n) >= 16 and n <= LP.PICK_MAX_SAMPLES and k >= 1 and (lines or dense_pitch)
-    if name == "wide":
-        return not subset and n >= 1024 and (lines or dense_pitch)
-    if name == "flat":
-        return not lines and not subset and n >= 8 and dense_pitch
-    assert name == "runs"
-    if lines:
-        return not gather and LP.lineruns_accepts(n, k, subset, bound)
-    return not subset and not gather and n >= 8 and runs_rows(n) >= 1 and dense_pitch
+
+def choose_all_samples(n: int, v: int = 2, **kw) -> str:
+    """AUTO for all samples kept (plan::emit::choose_all_samples); kw: the fields of `shape`."""
+    return CHOICES[_call("emit_choose_all_samples", 1, *shape(n, n, v, kept_list=False, **kw))[0]]
+
+
+def choose_subset(n: int, k: int, v: int, *, msc: Optional[int] = None, tune: Tune = Tune(), num_cus: int = NUM_CUS, **kw) -> str:
+    """AUTO for a kept list that is not the identity (plan::emit::choose_subset); kw: the fields of `shape`."""
+    msc = min(k, SEG_SAMPLES) if msc is None else msc
+    return CHOICES[_call("emit_choose_subset", 1, *shape(n, k, v, kept_list=True, **kw), tune.rowpick_mode() != 0, tune.scan_two_pass >= 0, msc, num_cus)[0]]
 
 
 KERNELS = ("auto", "rows", "scan", "rowpick")
@@ -276,33 +244,27 @@ KERNELS = ("auto", "rows", "scan", "rowpick")
 def arm(n: int, k: int, v: int, *, mode: str = "segments", kernel: str = "auto", msc: Optional[int] = None, tune: Tune = Tune(),
         num_cus: int = NUM_CUS) -> Plan:
     """What pgenhip_decode_emit / _at / pgenhip_emit_lines run for a kept list of K of N samples (`msc`: its most kept samples in one
-    segment), V rows at the dense pitch, under `kernel` (AUTO or a forced ROWS / SCAN / ROWPICK).  A gathered or offset-addressed
-    launch plans the same (only the kernels' HAS_VIDX instantiation differs)."""
+    segment), V rows at the dense pitch, under `kernel` (AUTO: plan::emit::choose_subset; or a forced ROWS / SCAN / ROWPICK).  A
+    gathered or offset-addressed launch plans the same (only the kernels' HAS_VIDX instantiation differs).  Full lines are planned
+    for empty prefixes (tests/line_plan.py has the prefix-driven limits)."""
     lines = mode == "lines"
     if msc is None:
         msc = min(k, SEG_SAMPLES)
     if kernel != "auto" and not accepts(KERNEL_IDS[kernel], n, k, True, mode=mode):
         return Plan(kernel, status="bad_arg")
-    if kernel == "rows":
-        return Plan("rows")
+    if kernel == "auto":
+        if k == n:
+            return Plan("all_samples")   # an identity list: AUTO drops it (capi.hip) and takes the all-samples kernels
+        kernel = choose_subset(n, k, v, msc=msc, tune=tune, num_cus=num_cus, lines=lines)
     if kernel == "scan":
         return Plan("scan", scan=scan_plan(n, k, v, tune, num_cus))
     if kernel == "rowpick":
         rp = rowpick_plan(n, k, v, tune, num_cus)
         return Plan("rowpick", status="ok" if rp else "hip", rowpick=rp)
-    assert kernel == "auto"
-    if k == n:
-        return Plan("all_samples")   # an identity list: the all-samples kernels
-    if rowpick_shape(n, k, v, tune, num_cus):
-        return Plan("rowpick", rowpick=rowpick_plan(n, k, v, tune, num_cus))
-    if two_pass(n, k, msc, lines, tune) and not very_sparse(n, k):
+    if kernel == "two_pass":
         chunk, chunks = two_pass_chunks(n, k, v, tune, num_cus)
         return Plan("two_pass", chunk_rows=chunk, chunks=chunks)
-    if n <= 4096 and record_size(n) >= 16 and k >= 1:
-        return Plan("pick")          # (lines: the line-run kernel first for N < 300; tests/line_plan.py)
-    if very_sparse(n, k) or record_size(n) < 16:
-        return Plan("rows")
-    return Plan("scan", scan=scan_plan(n, k, v, tune, num_cus))
+    return Plan(kernel)   # "rows" | "pick" | "lineruns"
 
 
 # ---- the GPU cell table --------------------------------------------------------------------------------------------------------

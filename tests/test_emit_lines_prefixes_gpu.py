@@ -3,7 +3,7 @@
 The prefix length bound (``max_prefix_bytes``) is the one input of the full-line path that the kernels plan with: rows per item and
 seam lanes of the line-run kernel, batch rows and seam-chunk lanes of the pick family's full-line kernel (and its row-by-row
 fallback), lanes per line of the prefix copy in the stream / segment / row-owner / pick kernels, tiles per row of the general kernel,
-and AUTO's choice between them.  tests/line_plan.py restates that arithmetic; every edge it derives gets a cell on each side, run
+and AUTO's choice between them.  tests/line_plan.py runs that arithmetic from csrc/launch_plan.h; every edge it derives gets a cell on each side, run
 through AUTO and through every forced kernel that accepts the shape (a forced kernel that refuses must be one the plan says refuses).
 Each output buffer is framed by sentinel bytes that must stay untouched; lines start behind output byte 0 at an unaligned pointer
 and the blob does not start at a prefix.  Prefix lengths per cell: all at the bound, uniform in 0 .. bound with 20 % empty, and one

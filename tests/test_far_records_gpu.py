@@ -128,7 +128,7 @@ def first_diff(got: np.ndarray, want: np.ndarray, what: str):
                          f"want {int(want.reshape(-1)[bad[0]])}")
 
 
-# (N, kept samples or None, the kernels the shape must reach: capi.hip's `choose`, tests/subset_plan.py `accepts`)
+# (N, kept samples or None, the kernels the shape must reach: plan::emit::accepts of csrc/launch_plan.h, through tests/subset_plan.py `accepts`)
 EMIT_SHAPES = [(40, None, ("rows", "flat")), (300, None, ("pick", "flat", "rows")), (300, 30, ("pick", "rows")),
                (2504, None, ("wide", "pick", "rows")), (2504, 1252, ("pick", "scan", "rows")), (20_000, 2000, ("scan", "rowpick", "rows"))]
 

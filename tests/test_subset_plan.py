@@ -1,22 +1,18 @@
-"""CPU guard of tests/subset_plan.py: what it restates must still read the same in csrc/, and its GPU cell table must reach every
-arm and both sides of every edge of the kept-subset dispatch and launch plans.  A changed constant, literal or condition fails here
-instead of silently moving an edge away from the cells of test_subset_plan_gpu.py that test it."""
+"""CPU tests of the kept-subset dispatch and launch plans (plan::emit of csrc/launch_plan.h, run through tests/subset_plan.py): the
+values on both sides of every condition AUTO, the forced kernel ids, the two-pass chunks and the launch plans contain, the
+constants, the shape of capi.hip's emit path, and that the GPU cell table of test_subset_plan_gpu.py reaches every arm and both
+sides of every edge.  A changed threshold fails here instead of silently moving an edge away from the cells that test it."""
 import re
 from pathlib import Path
 
 import subset_plan as SP
 
 CSRC = Path(__file__).resolve().parent.parent / "pgen_rs_amd" / "csrc"
+T = SP.Tune
 
 
 def _src(file):
     return (CSRC / file).read_text()
-
-
-def _const(file, name):
-    m = re.findall(rf"constexpr\s+(?:uint32_t|int|size_t)\s+{name}\s*=\s*([^;]+);", _src(file))
-    assert len(m) == 1, f"{name} in {file}: {m}"
-    return m[0].strip()
 
 
 def _body(file, signature):
@@ -25,18 +21,10 @@ def _body(file, signature):
     return b[: b.index("\n}\n")]
 
 
-def _conditions(body):
-    """The branch points of a body: `if`s, `&&`, `||` and `?`."""
-    return len(re.findall(r"\bif \(|&&|\|\||\?", body))
-
-
-def test_mirrored_constants_match_the_sources():
-    assert _const("kernels.h", "kScanSegmentSamples") == f"{SP.SEG_SAMPLES}u"
-    assert _const("kernels.h", "kCompactMaxSegCodes") == f"{SP.COMPACT_MAX_SEG_CODES}u"
-    assert _const("kernels.h", "kRowPickMaxKept") == f"{SP.ROWPICK_MAX_KEPT}u"
-    assert _const("capi.hip", "kCompactSliceBytes") == "32u << 20" and SP.COMPACT_SLICE_BYTES == 32 << 20
-    for f in ("gt_scan.hip", "gt_rowpick.hip"):
-        assert _const(f, "kThreads") == "256" and _const(f, "kWaves") == "kThreads / 64" and SP.WAVES == 4
+def test_constants_are_pinned():
+    assert (SP.SEG_SAMPLES, SP.COMPACT_MAX_SEG_CODES, SP.ROWPICK_MAX_KEPT, SP.COMPACT_SLICE_BYTES) == (16384, 4096, 16384, 32 << 20)
+    assert (SP.WAVES, SP.ROWPICK_MAX_SEGS, SP.ROWPICK_ROWS_PER_WAVE) == (4, 4096, 8)
+    assert SP.CHOICES == ("rows", "flat", "wide", "runs", "lineruns", "pick", "scan", "rowpick", "two_pass")
     # the static LDS the unmeasured occupancy constants are derived from
     scan = _src("gt_scan.hip")
     assert "__shared__ __attribute__((aligned(16))) uint16_t s_idx[kPickMaxSegCodes + 16];" in scan
@@ -47,66 +35,132 @@ def test_mirrored_constants_match_the_sources():
     assert (SP.SCAN_OCCUPANCY, SP.COMPACT_OCCUPANCY) == (3, 5)
 
 
-def test_mirrored_dispatch_matches_capi():
-    """capi.hip: the literals of two_pass_shape, very_sparse, rowpick_shape and two_pass, the chunk rounding of dispatch_two_pass,
-    the AUTO arms (choose_subset: one chain for GT segments and full lines; choose_all_samples: one per mode) and the one place
-    that maps a kernel id (choose) for the three entry points; a new condition in any of them changes its branch count and fails
-    here until subset_plan.py, line_plan.py and the cells follow."""
-    b = _body("capi.hip", "bool two_pass_shape(uint32_t sample_count, uint32_t kept_count)")
-    assert ("sample_count > 4096u && kept_count >= 8u && (uint64_t)kept_count * 170ull >= (uint64_t)sample_count &&\n"
-            "           (uint64_t)kept_count * 22ull <= (uint64_t)sample_count;") in b
-    assert _conditions(b) == 3
-    b = _body("capi.hip", "static bool very_sparse(const pgenhip_ctx *ctx)")
-    assert "ctx->sample_count >= 65536u && (uint64_t)ctx->kept_count * 280ull <= ctx->sample_count;" in b and _conditions(b) == 1
-    b = _body("capi.hip", "static bool rowpick_shape(const pgenhip_ctx *ctx, const EmitArgs &a)")
-    assert ("if (ctx->tune.scan_rowpick == 0 || ctx->sample_count <= kScanSegmentSamples || very_sparse(ctx) || "
-            "!gt_rowpick_applicable(a, ctx->num_cus)) return false;") in b
-    assert "if (N < 24576ull) return true;" in b and "return K * 50ull >= N && K * 5ull <= N;" in b
-    assert _conditions(b) == 6
-    b = _body("capi.hip", "static bool two_pass(const pgenhip_ctx *ctx, const EmitArgs &a)")
-    assert ("ctx->tune.scan_two_pass != 0 && ctx->d_compact != nullptr && a.kept_idx != nullptr && a.record_size >= 16u &&\n"
-            "           ctx->max_seg_count <= kCompactMaxSegCodes &&\n"
-            "           (a.line_off != nullptr ? a.kept_count >= 1024u : (a.n_variants <= 1u || a.out_stride == 4ull * a.kept_count + 1ull));") in b
-    assert _conditions(b) == 7
-    assert "if (two_pass_shape(sample_count, kept_count)) {\n                ctx->compact_bytes = kCompactSliceBytes;" in _src("capi.hip")
-    b = _body("capi.hip", "static int dispatch_two_pass(pgenhip_ctx *ctx, const EmitArgs &a, const ScanArgs &sc)")
-    assert "const uint32_t rc_bytes = (a.kept_count + 3u) / 4u;" in b
-    assert "uint64_t chunk_rows = std::max<uint64_t>(1ull, ctx->compact_bytes / rc_bytes);" in b
-    assert "if (ctx->tune.scan_chunk_rows > 0) chunk_rows = std::min<uint64_t>(chunk_rows, (uint64_t)ctx->tune.scan_chunk_rows);" in b
-    assert "probe.n_variants = (uint32_t)std::min<uint64_t>(chunk_rows, a.n_variants);" in b
-    assert "const uint64_t round = gt_rowpick_resident_waves(probe, ctx->tune, ctx->num_cus, true);" in b
-    assert "if (row_owner && round && chunk_rows > round && ctx->tune.scan_chunk_rows <= 0) chunk_rows -= chunk_rows % round;" in b
-    assert "if (row_owner && (uint64_t)n * 2ull >= chunk_rows)" in b
-    assert "if (a.record_off) c.record_off = a.record_off + row0;" in b and "else if (a.variant_idx) c.variant_idx = a.variant_idx + row0;" in b
-    assert _conditions(b) == 12
-    # the AUTO arms for kept subsets: one chain for GT segments and full lines, in this order
-    b = _body("capi.hip", "static Emit choose_subset(const pgenhip_ctx *ctx, const EmitArgs &a)")
-    order = ["if (rowpick_shape(ctx, a)) return Emit::RowPick;", "if (two_pass(ctx, a) && !very_sparse(ctx)) return Emit::TwoPass;",
-             "if (gt_lineruns_applicable(a) && gt_lineruns_rows(a) >= 7u && a.sample_count < 300u) return Emit::LineRuns;",
-             "if (gt_pick_applicable(a)) return Emit::Pick;", "if (very_sparse(ctx) || ctx->record_size < 16u) return Emit::Rows;",
-             "return Emit::Scan;"]
-    assert [b.index(s) for s in order] == sorted(b.index(s) for s in order) and _conditions(b) == 9
-    # the AUTO arms for all samples kept (tests/line_plan.py): the full-line chain, then the GT-segment chain
-    b = _body("capi.hip", "static Emit choose_all_samples(const EmitArgs &a)")
-    order = ["if (a.line_off != nullptr) {", "if (gt_wide_lines_applicable(a) && a.sample_count >= 1400u) return Emit::Wide;",
-             "if (gt_lineruns_applicable(a) && gt_lineruns_rows(a) >= 7u && a.sample_count < 1000u) return Emit::LineRuns;",
-             "if (gt_pick_applicable(a)) return Emit::Pick;", "return Emit::Rows;\n    }", "if (gt_runs_preferred(a)) return Emit::Runs;",
-             "if (gt_pick_applicable(a) && a.sample_count < 2000u) return Emit::Pick;", "if (gt_wide_applicable(a)) return Emit::Wide;",
-             "if (gt_flat_applicable(a)) return Emit::Flat;", "return Emit::Rows;"]
-    at = []
-    for s in order:
-        at.append(b.index(s, at[-1] + 1 if at else 0))   # each behind the one before it
-    assert _conditions(b) == 12
-    # AUTO: an identity list goes with all samples, a kept list through the chain above; forced kernels see the list
-    b = _body("capi.hip", "static int choose(const pgenhip_ctx *ctx, EmitArgs &a, uint32_t kernel, Emit &out)")
-    auto = b[b.index("case PGENHIP_KERNEL_AUTO:"): b.index("case PGENHIP_KERNEL_ROWS:")]
-    assert "if (ctx->identity) a.kept_idx = nullptr;\n            out = a.kept_idx == nullptr ? choose_all_samples(a) : choose_subset(ctx, a);" in auto
-    assert b.count("a.kept_idx = nullptr") == 1 and _conditions(b) == 17
-    # forced ROWPICK: capi.hip's own checks (the launcher refuses more than 4 096 segments: PGENHIP_ERR_HIP), once for every entry point
+def _around(f, edge):
+    return [bool(f(edge + d)) for d in (-1, 0, 1)]
+
+
+def test_auto_predicates_on_both_sides_of_every_condition():
+    """two_pass_shape, very_sparse, rowpick_shape and two_pass at -1, 0, +1 of each of their conditions."""
+    # two_pass_shape: N > 4 096, K * 170 >= N, K * 22 <= N (K >= 8 cannot be reached: K * 170 >= N > 4 096 means K >= 25)
+    assert _around(lambda n: SP.two_pass_shape(n, 100), 4096) == [False, False, True]
+    assert _around(lambda k: SP.two_pass_shape(170_000, k), 1000) == [False, True, True]
+    assert _around(lambda k: SP.two_pass_shape(44_000, k), 2000) == [True, True, False]
+    assert not any(SP.two_pass_shape(n, 7) for n in (1, 1190, 4097, 100_000))
+    # very_sparse: N >= 65 536, K * 280 <= N
+    assert _around(lambda n: SP.very_sparse(n, 234), 65536) == [False, True, True]
+    assert _around(lambda k: SP.very_sparse(280_000, k), 1000) == [True, True, False]
+    # rowpick_shape: the knob, N > 16 384, N < 24 576, else K * 50 >= N and K * 5 <= N; applicability: K in 1 .. 16 384, rows for every wave
+    rs = lambda n, k, v=8192, tune=T(), cus=256: SP.rowpick_shape(n, k, v, tune, cus)   # noqa: E731
+    assert rs(20_000, 2_000) and not rs(20_000, 2_000, tune=T(scan_rowpick=-1))
+    assert _around(lambda n: rs(n, 1_638), 16384) == [False, False, True]
+    assert _around(lambda n: rs(n, 10_000), 24576) == [True, False, False]
+    assert _around(lambda k: rs(100_000, k), 2000) == [False, True, True]
+    assert _around(lambda k: rs(50_000, k), 10_000) == [True, True, False]
+    assert _around(lambda k: rs(20_000, k), 16384) == [True, True, False] and _around(lambda k: SP.rowpick_applicable(20_000, k, 8192), 1) == [False, True, True]
+    for cus in (80, 256, 304):
+        assert _around(lambda v: rs(20_000, 2_000, v, cus=cus), 32 * cus) == [False, True, True]
+    assert _around(lambda n: SP.rowpick_applicable(n, 1_000, 8192), 4096 * 16384 + 1) == [True, False, False]   # 4 096 segments
+    assert _around(lambda n: SP.rowpick_applicable(n, 5, 8192), 61) == [False, True, True]                        # records of 16 bytes
+    # two_pass: the knob, the shape, max_seg_count <= 4 096, full lines from K = 1 024
+    assert SP.two_pass(100_000, 1_999, 1_999, False, T()) and not SP.two_pass(100_000, 1_999, 1_999, False, T(scan_two_pass=-1))
+    assert not SP.two_pass(100_000, 20_000, 4_000, False, T())
+    assert _around(lambda m: SP.two_pass(100_000, 4_500, m, False, T()), 4096) == [True, True, False]
+    assert _around(lambda k: SP.two_pass(100_000, k, k, True, T()), 1024) == [False, True, True]
+    s = SP.shape(100_000, 1_999, kept_list=True)
+    assert SP._call("emit_two_pass", 1, *s, 1, 1_999)[0] == 1
+    assert SP._call("emit_two_pass", 1, *SP.shape(100_000, 1_999, kept_list=True, out_dense=False), 1, 1_999)[0] == 0   # padded output
+    assert SP._call("emit_two_pass", 1, *SP.shape(100_000, 1_999, kept_list=False), 1, 1_999)[0] == 0                  # no kept list
+
+
+def test_choose_subset_takes_its_arms_in_order():
+    """One chain for GT segments and full lines: row owner, two passes, line runs (full lines, N < 300), pick, rows, segment kernel."""
+    cs = SP.choose_subset
+    # both the row owner's and the two passes' shape: the row owner first; one row fewer than every wave needs: the two passes
+    assert SP.two_pass(100_000, 3_000, 3_000, False, T()) and cs(100_000, 3_000, 8192) == "rowpick" and cs(100_000, 3_000, 8191) == "two_pass"
+    assert cs(100_000, 3_000, 8192, tune=T(scan_rowpick=-1)) == "two_pass" and cs(100_000, 3_000, 8191, tune=T(scan_two_pass=-1)) == "scan"
+    assert cs(100_000, 4_500, 33, msc=4096) == "two_pass" and cs(100_000, 4_500, 33, msc=4097) == "scan"
+    for mode in (False, True):
+        assert [cs(n, 409, 33, lines=mode) for n in (4095, 4096, 4097)] == ["pick", "pick", "scan"]
+        assert [cs(280_000, k, 33, lines=mode) for k in (999, 1000, 1001)] == ["rows", "rows", "scan"]
+        assert [cs(65_536 + d, 234, 33, lines=mode) for d in (-1, 0, 1)] == ["scan", "rows", "rows"]
+    assert [cs(n, 5, 33) for n in (59, 60, 61, 62)] == ["rows", "rows", "pick", "pick"]
+    # full lines: runs of lines below N = 300 while a run holds seven (30-byte prefixes); the pick family from there, and for GT segments
+    assert [cs(n, 50, 33, lines=True, bound=30) for n in (100, 298, 299, 300, 301)] == ["lineruns", "lineruns", "lineruns", "pick", "pick"]
+    assert [cs(100, 50, 33, lines=True, bound=p) for p in (93, 94, 95)] == ["lineruns", "lineruns", "pick"]
+    assert cs(100, 50, 33, bound=30) == "pick" and cs(100, 50, 33, lines=True, bound=30, gathered=True) == "pick"
+    assert cs(100, 50, 33, lines=True, bound=30, records_dense=False) == "pick" and [cs(100, k, 33, lines=True, bound=30) for k in (7, 8, 9)] == ["pick", "lineruns", "lineruns"]
+    # full lines through the two passes from K = 1 024
+    assert [cs(100_000, k, 33, lines=True) for k in (1023, 1024, 1025)] == ["scan", "two_pass", "two_pass"]
+
+
+def test_two_pass_chunks_on_both_sides_of_every_condition():
+    rc = (1_999 + 3) // 4
+    full = (32 << 20) // rc                                    # 67 108 rows of 500 bytes
+    chunks = lambda v, tune=T(), cus=256, n=100_000, k=1_999: SP.two_pass_chunks(n, k, v, tune, cus)   # noqa: E731
+    # the rows a slice holds, rounded down to whole row-owner rounds (2 blocks per CU x 4 waves) where the row owner takes the chunk
+    assert chunks(200_000)[0] == full - full % 2048 == 65_536 and chunks(200_000, cus=304)[0] == full - full % 2432
+    assert chunks(200_000, T(scan_rowpick=-1))[0] == full and chunks(200_000, T(scan_rowpick=-1))[1][0][1] == "scan"
+    assert chunks(8191)[0] == full and chunks(8191)[1] == ((8191, "scan", SP.scan_plan(100_000, 1_999, 8191, compact=True)),)   # too few rows for the row owner
+    assert chunks(8192)[0] == 65_536 and chunks(8192)[1][0][:2] == (8192, "scan")                              # (a short only chunk)
+    # the knob caps the chunk and is not rounded
+    assert chunks(200_000, T(scan_chunk_rows=10_000))[0] == 10_000 and chunks(200_000, T(scan_chunk_rows=100_000))[0] == full
+    assert chunks(200_000, T(rowpick_blocks_per_cu=1))[0] == full - full % 1024
+    # at least one row however long the compact record
+    assert SP._call("emit_chunks", 2, *SP.shape(4096 * 16384, 3_000_000, 10, kept_list=True), 1000, 0, 1, 0, 256) == (1, 0)
+    # the short last chunk: the row owner while it has at least half a chunk of rows
+    assert [SP._call("emit_chunk_by_row_owner", 1, 100, 1, n)[0] for n in (49, 50, 51)] == [0, 1, 1]
+    assert SP._call("emit_chunk_by_row_owner", 1, 100, 0, 100)[0] == 0
+    assert [k for _, k, _ in chunks(65_536 + 32_767)[1]] == ["rowpick", "scan"] and [k for _, k, _ in chunks(65_536 + 32_768)[1]] == ["rowpick", "rowpick"]
+
+
+def test_segment_plan_on_both_sides_of_every_condition():
+    sp = SP.scan_plan
+    # blocks per CU: the occupancy figure, two from K * 170 >= N and in the compact pass, the knob over both
+    assert [sp(170_000, k, 1000).per_cu for k in (999, 1000, 1001)] == [3, 2, 2]
+    assert [sp(170_000, 1000, 1000, occupancy=o).per_cu for o in (0, 1, 2, 3)] == [1, 1, 2, 2] and sp(170_000, 999, 1000, occupancy=5).per_cu == 5
+    assert sp(170_000, 999, 1000, compact=True).per_cu == 2 and sp(170_000, 999, 1000, compact=True, occupancy=1).per_cu == 1
+    assert sp(170_000, 1000, 1000, T(scan_blocks_per_cu=4)).per_cu == 4 and sp(170_000, 999, 1000, T(scan_blocks_per_cu=1), compact=True).per_cu == 1
+    # row groups: resident blocks / segments, floored; at least one; no more than the rows need
+    p = sp(147_456, 20_000, 14_336)
+    assert (p.n_seg, p.groups, p.grid) == (9, 56, 504) and sp(147_457, 20_000, 14_336).groups == 51
+    assert [sp(n, n // 20, 16).groups for n in (2 * 256 * 16384, 2 * 256 * 16384 + 1)] == [1, 1]
+    assert [sp(10_000, 1_000, v).groups for v in (4, 5, 2044, 2045, 2048, 2049)] == [1, 2, 511, 512, 512, 512]
+    assert sp(1, 1, 1).n_seg == 1
+    # the XCD-aware map takes whole eights of row groups; the plain map none
+    assert [sp(10_000, 1_000, v).xcd_groups for v in (28, 29, 32, 33, 60, 61)] == [0, 8, 8, 8, 8, 16]
+    assert sp(10_000, 1_000, 131_072, T(scan_xcd_map=-1)).xcd_groups == 0
+    # eight bands: K * 10 >= N, a multiple of eight groups, 64 steps of every group; never in the compact pass
+    assert [sp(10_000, k, 131_072).bands for k in (999, 1000, 1001)] == [1, 8, 8]
+    assert [sp(10_000, 1_000, v).bands for v in (131_068, 131_069, 131_072)] == [1, 8, 8]
+    assert [sp(n, 20_000, 14_336).bands for n in (147_456, 147_457)] == [8, 1] and sp(10_000, 1_000, 131_072, compact=True).bands == 1
+
+
+def test_row_owner_plan_on_both_sides_of_every_condition():
+    rp = SP.rowpick_plan
+    # what the launcher refuses: more than 16 384 kept samples, more than 4 096 segments, records below 16 bytes
+    assert [rp(20_000, k, 100) is None for k in (16_383, 16_384, 16_385)] == [False, False, True]
+    assert [rp(n, 1_000, 100) is None for n in (4096 * 16384 - 1, 4096 * 16384, 4096 * 16384 + 1)] == [False, False, True]
+    assert [rp(n, 5, 100) is None for n in (60, 61, 62)] == [True, False, False]
+    # the LDS of a block
+    # (table of K + 8 u16 | ranks of 3 u32 | four waves x (4 096 + ceil(K / 4) + 16), each part rounded up to 16)
+    assert [SP.rowpick_lds_bytes(20_000, k) for k in (1, 8, 9, 16_336, 16_337)] == [32 + 16 + 4 * (4096 + 32)] * 2 + [48 + 16 + 4 * (4096 + 32), 65_536, 65_552]
+    assert SP.rowpick_lds_bytes(16_384 * 3, 1) - SP.rowpick_lds_bytes(16_384 * 3 + 1, 1) == -16   # the rank table grows every four segments
+    # blocks per CU: four (text, N < 24 576) or two, never more than fit; the knob caps
+    assert [rp(n, 2_000, 8192).per_cu for n in (24_575, 24_576, 24_577)] == [4, 2, 2]
+    assert rp(24_575, 2_000, 8192, compact=True).per_cu == 2
+    assert [rp(20_000, 2_000, 8192, occupancy=o).per_cu for o in (0, 1, 3, 4, 5)] == [1, 1, 3, 4, 4]
+    assert rp(20_000, 16_384, 8192).per_cu == 2 == SP.rowpick_occupancy(20_000, 16_384)
+    assert [rp(20_000, 2_000, 8192, T(rowpick_blocks_per_cu=b)).per_cu for b in (1, 3, 6)] == [1, 3, 6] and rp(20_000, 2_000, 8192, T(rowpick_blocks_per_cu=8), occupancy=5).per_cu == 5
+    # one resident round; a block per four rows up to it
+    for cus in (80, 256, 304):
+        p = rp(100_000, 2_000, 10 ** 6, num_cus=cus)
+        assert (p.max_blocks, p.grid) == (2 * cus, 2 * cus)
+        assert [rp(100_000, 2_000, v, num_cus=cus).grid for v in (1, 4, 5, 8 * cus - 4, 8 * cus - 3, 8 * cus, 8 * cus + 1)] == [1, 1, 2, 2 * cus - 1, 2 * cus, 2 * cus, 2 * cus]
+
+
+def test_emit_path_of_capi_has_one_choice_and_one_switch():
+    """capi.hip: three entry points -> one emit_core -> one choice (plan::emit) -> one `run` switch; no predicate of its own."""
     src = _src("capi.hip")
-    assert src.count("if (!ctx->subset || ctx->record_size < 16u || ctx->kept_count < 1u || ctx->kept_count > kRowPickMaxKept)") == 1
-    assert all(src.count(f"case PGENHIP_KERNEL_{k.upper()}:") == 1 for k in SP.KERNEL_IDS)
-    # the three entry points reach the one core, which chooses once and launches through the one switch
     for sig in ("int pgenhip_decode_emit(", "int pgenhip_decode_emit_at(", "int pgenhip_emit_lines("):
         b = _body("capi.hip", sig)
         assert b.count("return emit_core(ctx, ") == 1 and "launch_gt_" not in b and "choose" not in b and "PGENHIP_KERNEL_" not in b, sig
@@ -114,53 +168,19 @@ def test_mirrored_dispatch_matches_capi():
     steps = ["bind(ctx)", "fill_args(ctx, a, ", "claim_counters(ctx, a)", "choose(ctx, a, flags, choice)", "return run(ctx, a, sc, choice);"]
     assert [core.index(s) for s in steps] == sorted(core.index(s) for s in steps) and all(core.count(s) == 1 for s in steps)
     assert src.count("const ScanArgs sc{") == 1 and "launch_gt_" not in core
+    # the one place a kernel id becomes what runs: AUTO by the header's chains (an identity list dropped first), a forced id by the header's table
+    b = _body("capi.hip", "static int choose(const pgenhip_ctx *ctx, EmitArgs &a, uint32_t kernel, Emit &out)")
+    assert b.count("a.kept_idx = nullptr") == 1 and b.index("if (ctx->identity) a.kept_idx = nullptr;") < b.index("emit_shape(a)")
+    assert b.count("E::choose_all_samples(") == 1 and b.count("E::choose_subset(") == 1 and b.count("E::accepts(kernel, s)") == 1 and b.count("E::forced(kernel, s.lines)") == 1
+    assert src.count("E::choose_subset(") == 1 and src.count("E::choose_all_samples(") == 2 and src.count("E::accepts(") == 1
+    assert not re.search(r"gt_\w+_(applicable|preferred|rows)\b", src)
     run = _body("capi.hip", "static int run(pgenhip_ctx *ctx, const EmitArgs &a, const ScanArgs &sc, Emit choice)\n{")
     emit_launches = re.findall(r"LAUNCH_TRY\(launch_gt_(\w+)\(", src)
     assert sorted(re.findall(r"LAUNCH_TRY\(launch_gt_(\w+)\(", run)) == sorted(["rows", "flat", "wide", "runs", "lineruns", "pick", "scan", "rowpick"])
     assert len(emit_launches) == 10   # + the two compact passes of dispatch_two_pass
-    assert "const int rc = run(ctx, d, sc, choose_all_samples(d));" in _body("capi.hip", "static int dispatch_two_pass(")
-
-
-def test_mirrored_segment_plan_and_knobs_match_the_source():
-    b = _body("gt_scan.hip", "hipError_t launch_gt_scan(")
-    assert "const uint32_t n_seg = (a.sample_count + kSegSamples - 1u) / kSegSamples;" in b
-    assert "const uint64_t groups_needed = ((uint64_t)a.n_variants + kWaves - 1ull) / kWaves;" in b
-    assert "uint64_t groups = (uint64_t)resident_blocks(ckern, kThreads, num_cus, t, 2) / n_seg_eff;" in b
-    assert "const int preferred = (uint64_t)a.kept_count * 170ull >= (uint64_t)a.sample_count ? 2 : 0;" in b
-    assert "uint64_t groups = (uint64_t)resident_blocks(kern, kThreads, num_cus, t, preferred) / n_seg_eff;" in b
-    assert b.count("if (groups < 1ull) groups = 1ull;") == 2 and b.count("if (groups > groups_needed) groups = groups_needed;") == 2
-    assert b.count("const uint32_t xcd_groups = t.scan_xcd_map != 0 ? (uint32_t)(groups & ~7ull) : 0u;") == 2
-    assert ("const bool banded = (uint64_t)a.kept_count * 10ull >= (uint64_t)a.sample_count && groups % 8ull == 0ull && "
-            "groups_needed >= 64ull * groups;") in b
-    assert "const uint32_t bands = banded ? 8u : 1u;" in b and "const uint32_t grid = (uint32_t)(groups * n_seg_eff);" in b
-    r = _body("gt_scan.hip", "static uint32_t resident_blocks(")
-    assert "if (preferred > 0 && preferred < per_cu) per_cu = preferred;" in r and "if (t.scan_blocks_per_cu > 0) per_cu = t.scan_blocks_per_cu;" in r
-    k = _src("gt_scan.hip")
-    assert "const uint32_t band = row_group % bands, group_in_band = row_group / bands;" in k
-    assert "const uint64_t row_step = (uint64_t)(row_groups / bands) * kWaves;" in k
-    tune = _src("capi.hip")
-    assert "case PGENHIP_KNOB_SCAN_XCD_MAP: t.scan_xcd_map = value < 0 ? 0 : 1; break;" in tune
-    assert "case PGENHIP_KNOB_SCAN_TWO_PASS: t.scan_two_pass = value < 0 ? 0 : 1; break;" in tune
-    assert "case PGENHIP_KNOB_SCAN_ROWPICK: t.scan_rowpick = value < 0 ? 0 : 1; break;" in tune
-
-
-def test_mirrored_row_owner_plan_matches_the_source():
-    s = _src("gt_rowpick.hip")
-    assert "inline uint32_t table_bytes(uint32_t K) { return (2u * (K + 8u) + 15u) & ~15u; }" in s
-    assert "inline uint32_t rank_bytes(uint32_t n_seg) { return (4u * (n_seg + 1u) + 15u) & ~15u; }" in s
-    assert "inline uint32_t codes_bytes(uint32_t K) { return ((K + 3u) / 4u + 16u + 15u) & ~15u; }" in s
-    assert "constexpr uint32_t kStageBytes = kSegSamples / 4u;" in s
-    p = _body("gt_rowpick.hip", "bool plan(const EmitArgs &a, const Tuning &t, int num_cus, bool compact, RowPickLaunch &L)")
-    assert "L.lds = table_bytes(a.kept_count) + rank_bytes(L.n_seg) + (uint32_t)kWaves * (kStageBytes + codes_bytes(a.kept_count));" in p
-    assert "if (L.n_seg < 1u || L.n_seg > 4096u || a.record_size < 16u) return false;" in p
-    assert "const int want = t.rowpick_blocks_per_cu > 0 ? t.rowpick_blocks_per_cu : (!compact && a.sample_count < 24576u ? 4 : 2);" in p
-    assert "if (want < per_cu) per_cu = want;" in p and "L.max_blocks = (uint32_t)per_cu * (uint32_t)num_cus;" in p
-    a = _body("gt_rowpick.hip", "bool gt_rowpick_applicable(const EmitArgs &a, int num_cus)")
-    assert ("a.kept_idx != nullptr && a.kept_count >= 1u && a.kept_count <= kRowPickMaxKept && a.record_size >= 16u && n_seg >= 1u && "
-            "n_seg <= 4096u &&\n           (uint64_t)a.n_variants >= 8ull * (uint64_t)num_cus * kWaves;") in a
-    assert (SP.ROWPICK_MAX_SEGS, SP.ROWPICK_ROWS_PER_WAVE) == (4096, 8)
-    l = _body("gt_rowpick.hip", "hipError_t launch_gt_rowpick(")
-    assert "dim3((uint32_t)(need < L.max_blocks ? need : L.max_blocks))" in l
+    two = _body("capi.hip", "static int dispatch_two_pass(")
+    assert "const int rc = run(ctx, d, sc, E::choose_all_samples(emit_shape(d)));" in two
+    assert sorted(re.findall(r"LAUNCH_TRY\(launch_gt_(\w+)\(", two)) == ["rowpick", "scan"] and two.count("E::chunks(") == 1 and two.count("E::chunk_by_row_owner(") == 1
 
 
 def test_forced_kernel_acceptance_table():
@@ -183,6 +203,30 @@ def test_forced_kernel_acceptance_table():
             assert not SP.accepts(SP.KERNEL_IDS["flat"], n, k, subset, 10, False)   # full lines: never FLAT
     assert not any(SP.accepts(i, 300, 300, False, mode=m) for i in (5, 9, 10, 11, 12, 13, 14, 15, 0x10, 0x13) for m in ("segments", "lines"))
     assert (SP.runs_rows(3831), SP.runs_rows(3832)) == (1, 0) and SP.accepts(7, 3831, 3831, False, mode="segments") and not SP.accepts(7, 3832, 3832, False, mode="segments")
+
+
+def test_forced_kernel_ids_on_both_sides_of_every_condition():
+    ids = SP.KERNEL_IDS
+    acc = lambda name, n, k=None, subset=False, **kw: SP.accepts(ids[name], n, n if k is None else k, subset, **kw)   # noqa: E731
+    for mode in ("segments", "lines"):
+        assert [acc("scan", n, 5, True, mode=mode) for n in (60, 61, 62)] == [False, True, True] and not acc("scan", 300, mode=mode)
+        assert [acc("rowpick", n, 5, True, mode=mode) for n in (60, 61, 62)] == [False, True, True] and not acc("rowpick", 20_000, mode=mode)
+        assert [acc("rowpick", 20_000, k, True, mode=mode) for k in (0, 1, 2, 16_383, 16_384, 16_385)] == [False, True, True, True, True, False]
+        assert [acc("wide", n, mode=mode) for n in (1023, 1024, 1025)] == [False, True, True] and not acc("wide", 1024, 1024, True, mode=mode)
+        assert [acc("pick", n, mode=mode) for n in (60, 61, 62, 4095, 4096, 4097)] == [False, True, True, True, True, False]
+        assert [acc("pick", 300, k, True, mode=mode) for k in (0, 1, 2)] == [False, True, True]
+    assert [acc("flat", n, mode="segments") for n in (7, 8, 9)] == [False, True, True] and not acc("flat", 300, 30, True, mode="segments")
+    assert [acc("runs", n, mode="segments") for n in (7, 8, 9, 3830, 3831, 3832)] == [False, True, True, True, True, False]
+    assert acc("wide", 1024, mode="lines", dense_pitch=False) and acc("pick", 300, mode="lines", dense_pitch=False)
+    # RUNS for full lines: the line-run kernel (tests/test_line_plan.py has its prefix-driven limits)
+    assert [acc("runs", n, mode="lines", bound=30) for n in (7, 8, 9)] == [False, True, True]
+    assert [acc("runs", n, 50, True, mode="lines", bound=30) for n in (1384, 1385, 4096, 4097)] == [True, False, False, False]
+    assert [acc("runs", 300, k, True, mode="lines", bound=30) for k in (7, 8, 9)] == [False, True, True]
+    assert not acc("runs", 300, mode="lines", bound=30, gather=True)
+    # what a forced id runs
+    forced = lambda name, lines: SP.CHOICES[SP._call("emit_accepts", 3, *SP.shape(300, 300, kept_list=False, lines=lines), ids[name])[2]]   # noqa: E731
+    assert [forced(k, False) for k in ("rows", "flat", "scan", "wide", "pick", "runs", "rowpick")] == ["rows", "flat", "scan", "wide", "pick", "runs", "rowpick"]
+    assert forced("runs", True) == "lineruns" and forced("pick", True) == "pick"
 
 
 def test_derived_edges():

@@ -1,6 +1,6 @@
 """The kept-subset GT path at every edge of its dispatch and launch plans, byte for byte against the oracle.
 
-tests/subset_plan.py restates AUTO's subset dispatch (row owner, two passes, segment kernel, general kernel), the segment kernel's
+tests/subset_plan.py runs, from csrc/launch_plan.h, AUTO's subset dispatch (row owner, two passes, segment kernel, general kernel), the segment kernel's
 launch plan (groups, XCD map, bands, rounds), the chunking of the two passes and the row owner's plan (LDS bytes, blocks per CU,
 its segment limit); its cell table places cells on both sides of every edge those derive from N, K, V and the CU count (the
 device's own: the table is computed from it).  Each cell runs AUTO and every forced kernel that accepts the shape (forced kernels

@@ -1,47 +1,13 @@
-"""The launch rule of the stream kernel (gt_wide.hip), RUN from csrc/launch_plan.h (namespace plan::wide) rather than restated.  Like
-tests/launch_plan.py: tests/wide_plan_probe.cpp is compiled with g++ into a directory under the system temp dir, named by a hash of
-the two sources, and loaded with ctypes; nothing is written into the repository, and a failed compile is an error."""
+"""The launch rule of the stream kernel (gt_wide.hip), RUN from csrc/launch_plan.h (namespace plan::wide) rather than restated.
+tests/wide_plan_probe.cpp is built and loaded by tests/launch_plan.py (``load``), as every probe is."""
 from __future__ import annotations
 
-import ctypes
-import hashlib
-import os
-import subprocess
-import tempfile
+import functools
 from collections import namedtuple
-from pathlib import Path
 
-TESTS = Path(__file__).resolve().parent
-PROBE = TESTS / "wide_plan_probe.cpp"
-HEADER = TESTS.parent / "pgen_rs_amd" / "csrc" / "launch_plan.h"
+import launch_plan
 
-
-def _build() -> Path:
-    digest = hashlib.sha256(PROBE.read_bytes() + HEADER.read_bytes()).hexdigest()[:16]
-    out_dir = Path(tempfile.gettempdir()) / f"pgen_wide_plan_probe_{os.getuid()}_{digest}"
-    lib = out_dir / "wide_plan_probe.so"
-    if not lib.exists():
-        out_dir.mkdir(parents=True, exist_ok=True)
-        tmp = out_dir / f"wide_plan_probe.{os.getpid()}.so"
-        cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-shared", "-fPIC", "-o", str(tmp), str(PROBE)]
-        proc = subprocess.run(cmd, capture_output=True, text=True)
-        if proc.returncode != 0:
-            raise RuntimeError(f"wide plan probe did not compile ({' '.join(cmd)}):\n{proc.stdout}{proc.stderr}")
-        os.replace(tmp, lib)   # atomic: parallel test processes never load a half-written file
-    return lib
-
-
-_lib = ctypes.CDLL(str(_build()))
-
-
-def _call(name: str, n_out: int, *args: int) -> tuple[int, ...]:
-    fn = getattr(_lib, name)
-    fn.restype = None
-    fn.argtypes = [ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_uint64)]
-    a = (ctypes.c_int64 * max(len(args), 1))(*[int(x) for x in args])
-    out = (ctypes.c_uint64 * n_out)()
-    fn(a, out)
-    return tuple(out)
+_call = functools.partial(launch_plan.call_into, launch_plan.load("wide_plan_probe"))
 
 
 THREADS, STORERS, SPAN_CHUNKS, SHORT_LAUNCH_BYTES, WT_ONE_SPAN_MAX_BYTES, FRONT_STEPS, NT, WT, BURST_ONE_MIN_BYTES, RUNS_LONG_BYTES = _call("wide_constants", 10)
