@@ -580,6 +580,67 @@ int pgenhip_pack_records(pgenhip_ctx *ctx, const void *d_records, uint64_t recor
 int pgenhip_pack_records_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
                             void *d_out, uint64_t out_stride, const uint8_t *code_map, uint32_t flags);
 
+/* ---- GT text to records (device-resident, asynchronous on the ctx stream) ----
+ * The inverse of pgenhip_decode_emit: for every line j of a text buffer the sample fields become the line's mode-0x02 record of the
+ * ctx's N samples (sample s in byte s/4, bits 2*(s%4), LSB first; pad bits zero), so a host that puts the 12-byte header in front
+ * of the rows has a .pgen of a VCF's GT calls.  The ctx must keep all samples (no list, or the identity list); a proper subset is
+ * PGENHIP_ERR_BAD_ARG with a detail string: subsetting is pgenhip_pack_records' job.
+ *
+ * Grammar.  The sample region of line j is text[d_field_off[j], d_line_end[j]): a sequence of fields, each introduced by a '\t';
+ * the tab at d_field_off[j] introduces sample 0.  A field's GT is its bytes up to the first ':', or the whole field.  An allele is
+ * one or more bytes of 0-9, or the single byte '.'.  A GT is `A` (haploid) or `A S B` (diploid) with S one of '/' and '|'.
+ *   - A GT of neither form (empty, three alleles, other bytes) sets BAD_CALL; otherwise a digit token other than exactly "0" and
+ *     "1" ("2", "10", "01") sets ALLELE_RANGE.  In both cases the sample's code is 3 and the field sets no other flag.
+ *   - Otherwise: diploid, both called: a + b; diploid with a '.': 3, and HALF_CALL if only one is; haploid: "0" 0, "1" 2, "." 3, and
+ *     HAPLOID; a '|' sets PHASED (the phase is dropped).
+ *   - Fields with ordinal >= N are ignored and set FIELD_COUNT; samples without a field get code 3 and set FIELD_COUNT.  A region
+ *     that is empty or does not begin with a tab has no fields.
+ * Shapes (flags & PGENHIP_PARSE_SHAPE_MASK; other bits and values are PGENHIP_ERR_BAD_ARG).  GENERAL takes fields of any width; a
+ * block per line, so a call with few very long lines uses few CUs.  FIXED takes the lines this library's own emit path writes — a
+ * region of exactly 4N bytes, every field `\t[01.][/|][01.]` — flat over the launch's bytes; any other line is declined as a whole:
+ * PGENHIP_PARSE_DECLINED is its only flag and its record bytes are not touched.  AUTO
+ * runs FIXED and then GENERAL on the declined lines: its records and flags equal GENERAL's bit for bit on every input.
+ *   - Row j is the R = ceil(N / 4) bytes at d_out + j*out_stride, out_stride >= R or n_lines <= 1; d_out may have any alignment.
+ *     d_line_flags[j] is always overwritten.  Nothing outside the n_lines x R record bytes and the n_lines flag words is written.
+ *   - Nothing outside [d_text, d_text + text_len) is read: offsets past text_len are clamped to it, d_field_off[j] > d_line_end[j]
+ *     is an empty region.  d_text may have any alignment.
+ *   - n_lines == 0 is a no-op.  Refused before any launch, everything untouched: PGENHIP_ERR_BAD_ARG for a NULL pointer where an
+ *     element would be touched, d_line_flags not 4-byte aligned, offset arrays not 8-byte aligned, a stride below R, unknown flag
+ *     bits or shapes; PGENHIP_ERR_TOO_LARGE for out_stride * n_lines >= 2^52.  Malformed text is data, reported in the flags.
+ * Same launch contract as pgenhip_pack_records: device pointers only, no allocation, no synchronisation, queued on the ctx stream
+ * (a memset of the flag words and up to two kernels), graph-capturable, no work counters: not counted against
+ * PGENHIP_LAUNCHES_IN_FLIGHT. */
+#define PGENHIP_PARSE_AUTO 0u
+#define PGENHIP_PARSE_GENERAL 1u
+#define PGENHIP_PARSE_FIXED 2u
+#define PGENHIP_PARSE_SHAPE_MASK 0xFu
+/* per-line flag bits */
+#define PGENHIP_PARSE_FIELD_COUNT  0x01u
+#define PGENHIP_PARSE_BAD_CALL     0x02u
+#define PGENHIP_PARSE_ALLELE_RANGE 0x04u
+#define PGENHIP_PARSE_HALF_CALL    0x08u   /* informational */
+#define PGENHIP_PARSE_HAPLOID      0x10u   /* informational */
+#define PGENHIP_PARSE_PHASED       0x20u   /* informational */
+#define PGENHIP_PARSE_DECLINED     0x40u   /* forced FIXED only: line not taken, its record bytes not touched */
+int pgenhip_parse_gt(pgenhip_ctx *ctx, const void *d_text, uint64_t text_len,
+                     const uint64_t *d_field_off, const uint64_t *d_line_end, uint32_t n_lines,
+                     void *d_out, uint64_t out_stride, uint32_t *d_line_flags, uint32_t flags);
+
+/* Pure host function: the lines of a block of VCF body text, for pgenhip_parse_gt.  Per complete line i < *n_lines (a line ends
+ * with '\n'; with PGENHIP_VCF_LAST_BLOCK a non-empty remainder without one counts as a line that ends at text_len):
+ *   line_start[i]  the line's first byte
+ *   format_off[i]  the first byte of column format_col (columns are separated by '\t', column 0 starts the line)
+ *   field_off[i]   the tab that ends that column; line_end[i] when the line has exactly format_col + 1 columns; UINT64_MAX (as
+ *                  format_off[i] is then) when it has fewer, which the caller turns into an error
+ *   line_end[i]    the offset of the '\n', or of a '\r' directly before it
+ * Stops after max_lines lines (the arrays' length).  *consumed is the offset just past the last line reported, so the caller can
+ * carry the remainder into its next block.  PGENHIP_ERR_BAD_ARG for a NULL array or counter, a NULL text with text_len != 0, or
+ * unknown flags. */
+#define PGENHIP_VCF_LAST_BLOCK 1u   /* a final line without '\n' counts */
+int pgenhip_vcf_index_lines(const uint8_t *text, uint64_t text_len, uint32_t format_col, uint64_t max_lines, uint32_t flags,
+                            uint64_t *line_start, uint64_t *format_off, uint64_t *field_off, uint64_t *line_end,
+                            uint64_t *n_lines, uint64_t *consumed);
+
 /* Launch-shape knobs of one ctx (tests force small grids to exercise ring re-use; A/B probes).
  * value 0 restores the built-in default of a knob unless noted. */
 typedef enum pgenhip_knob {
@@ -609,6 +670,7 @@ typedef enum pgenhip_knob {
     PGENHIP_KNOB_GAPPLY_SAMPLE_SLICES = 26, /* Gram product, P pass: sample ranges per row tile, each summed by one block (default 0 = by shape: as many as fill the chip's resident blocks, of at least 4096 samples each); tests put the sample count on either side of every slice edge */
     PGENHIP_KNOB_GAPPLY_ROW_SLICES = 27, /* Gram product, Y pass: row ranges per sample tile, each summed by one block (default 0 = by shape: as many as fill the chip's resident blocks, of at least 256 rows each); tests put the row count on either side of every slice edge */
     PGENHIP_KNOB_WIDE_BURST = 28,        /* stream kernel (GT segments and full lines of long rows): plain store steps issued back to back, 1 or 2; default 0 = by shape (1 on launches of 9 GB of text and more in rows of more than 16 KiB, else 2) */
+    PGENHIP_KNOB_PARSE_BLOCKS = 29,      /* GT text parse kernels: grid size in blocks (default 0 = by shape: the work, capped at 8 blocks per CU); tests force small grids */
     PGENHIP_KNOB_RUNS_ROWS = 7       /* RUNS kernel: rows per work item (default: as many as one wide load / one span holds) */
 } pgenhip_knob;
 int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value);

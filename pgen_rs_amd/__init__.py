@@ -21,6 +21,7 @@ from .engine import (  # noqa: F401
     parse_header,
     record_offset,
     variant_record_size,
+    vcf_index_lines,
     vw_parse_header,
     vw_select_uncompressed,
     vw_walk_index,
@@ -33,6 +34,7 @@ __all__ = [
     "parse_header",
     "record_offset",
     "variant_record_size",
+    "vcf_index_lines",
     "vw_parse_header",
     "vw_walk_index",
     "vw_select_uncompressed",

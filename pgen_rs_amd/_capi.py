@@ -84,6 +84,18 @@ PACK_AUTO = 0
 PACK_GENERAL = 1
 PACK_DENSE = 2
 PACK_GATHER = 3
+PARSE_AUTO = 0
+PARSE_GENERAL = 1
+PARSE_FIXED = 2
+PARSE_SHAPE_MASK = 0xF
+PARSE_FIELD_COUNT = 0x01
+PARSE_BAD_CALL = 0x02
+PARSE_ALLELE_RANGE = 0x04
+PARSE_HALF_CALL = 0x08
+PARSE_HAPLOID = 0x10
+PARSE_PHASED = 0x20
+PARSE_DECLINED = 0x40
+VCF_LAST_BLOCK = 1
 PAIR_TABLE = 0
 PAIR_R2 = 1
 SYNTH_DIRTY_PAD = 1
@@ -115,6 +127,7 @@ KNOB_GRAM_SLICES = 25
 KNOB_GAPPLY_SAMPLE_SLICES = 26
 KNOB_GAPPLY_ROW_SLICES = 27
 KNOB_WIDE_BURST = 28
+KNOB_PARSE_BLOCKS = 29
 
 
 
@@ -175,6 +188,8 @@ PROTOTYPES = {
     "pgenhip_packed_record_size": (C.c_uint32, [ctx_p]),
     "pgenhip_pack_records": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]),
     "pgenhip_pack_records_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]),
+    "pgenhip_parse_gt": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]),
+    "pgenhip_vcf_index_lines": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u64p, u64p]),
     "pgenhip_tune": (C.c_int, [ctx_p, C.c_uint32, C.c_int32]),
     "pgenhip_wait": (C.c_int, [ctx_p]),
     "pgenhip_timer_start": (C.c_int, [ctx_p]),

@@ -1021,6 +1021,53 @@ int pgenhip_pack_records_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t
     return pack_records_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, d_out, out_stride, code_map, flags);
 }
 
+int pgenhip_parse_gt(pgenhip_ctx *ctx, const void *d_text, uint64_t text_len, const uint64_t *d_field_off, const uint64_t *d_line_end,
+                     uint32_t n_lines, void *d_out, uint64_t out_stride, uint32_t *d_line_flags, uint32_t flags)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    const uint32_t shape = flags & PGENHIP_PARSE_SHAPE_MASK;
+    if ((flags & ~PGENHIP_PARSE_SHAPE_MASK) || shape > PGENHIP_PARSE_FIXED) return fail(PGENHIP_ERR_BAD_ARG, "unknown parse_gt flag");
+    if (ctx->subset && !ctx->identity) return fail(PGENHIP_ERR_BAD_ARG, "parse_gt needs all samples kept (subsets are pack_records' job)");
+    if (n_lines == 0) return PGENHIP_OK;   // nothing to write
+    const uint32_t R = ctx->record_size;
+    if (!d_field_off || !d_line_end || !d_line_flags) return fail(PGENHIP_ERR_BAD_ARG, "d_field_off, d_line_end or d_line_flags is NULL");
+    if (!d_text && text_len) return fail(PGENHIP_ERR_BAD_ARG, "d_text is NULL");
+    if (!d_out && R) return fail(PGENHIP_ERR_BAD_ARG, "d_out is NULL");
+    if ((uintptr_t)d_line_flags & 3u) return fail(PGENHIP_ERR_BAD_ARG, "d_line_flags is not 4-byte aligned");
+    if (((uintptr_t)d_field_off | (uintptr_t)d_line_end) & 7u) return fail(PGENHIP_ERR_BAD_ARG, "d_field_off or d_line_end is not 8-byte aligned");
+    if (n_lines > 1 && out_stride < R) return fail(PGENHIP_ERR_BAD_ARG, "out_stride < one record");
+    // byte offsets are 64-bit arithmetic in the kernels; the bound is decode_matrix's (2^52 bytes)
+    if (n_lines > 1 && out_stride >= kMaxSpan / n_lines) return fail(PGENHIP_ERR_TOO_LARGE, "parse offsets do not fit the kernels' index types");
+    ParseArgs a;
+    a.text = static_cast<const uint8_t *>(d_text);
+    a.text_len = text_len;
+    a.field_off = d_field_off;
+    a.line_end = d_line_end;
+    a.n_lines = n_lines;
+    a.sample_count = ctx->sample_count;
+    a.record_size = R;
+    a.out = static_cast<uint8_t *>(d_out);
+    a.out_stride = out_stride;
+    a.line_flags = d_line_flags;
+    const int blocks = ctx->tune.parse_blocks;
+    if (shape == PGENHIP_PARSE_GENERAL || (shape == PGENHIP_PARSE_AUTO && !plan::parse::kAutoFixedFirst)) {
+        HIP_TRY(launch_gt_parse_general(a, false, blocks, ctx->num_cus, ctx->stream));
+        return PGENHIP_OK;
+    }
+    HIP_TRY(hipMemsetAsync(d_line_flags, 0, 4u * (size_t)n_lines, ctx->stream));   // FIXED ORs into the flag words
+    if (shape == PGENHIP_PARSE_FIXED) {
+        // a declined line's record bytes stay untouched: decide every line first, then write the lines that were taken
+        HIP_TRY(launch_gt_parse_fixed(a, true, false, blocks, ctx->num_cus, ctx->stream));
+        HIP_TRY(launch_gt_parse_fixed(a, false, true, blocks, ctx->num_cus, ctx->stream));
+    } else {
+        // AUTO: one FIXED pass that writes as it decides, then GENERAL rewrites the declined lines, flag words included
+        HIP_TRY(launch_gt_parse_fixed(a, true, true, blocks, ctx->num_cus, ctx->stream));
+        HIP_TRY(launch_gt_parse_general(a, true, blocks, ctx->num_cus, ctx->stream));
+    }
+    return PGENHIP_OK;
+}
+
 int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)
 {
     if (!ctx) return fail(PGENHIP_ERR_BAD_ARG, "ctx is NULL");
@@ -1047,6 +1094,7 @@ int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)
         case PGENHIP_KNOB_MATRIX_BLOCKS: t.matrix_blocks = value > 0 ? value : d.matrix_blocks; break;
         case PGENHIP_KNOB_PAIR_BLOCKS: t.pair_blocks = value > 0 ? value : d.pair_blocks; break;
         case PGENHIP_KNOB_PACK_BLOCKS: t.pack_blocks = value > 0 ? value : d.pack_blocks; break;
+        case PGENHIP_KNOB_PARSE_BLOCKS: t.parse_blocks = value > 0 ? value : d.parse_blocks; break;
         case PGENHIP_KNOB_SPAIR_SLICES: t.spair_slices = value > 0 ? value : d.spair_slices; break;
         case PGENHIP_KNOB_VSUM_BLOCKS: t.vsum_blocks = value > 0 ? value : d.vsum_blocks; break;
         case PGENHIP_KNOB_GRAM_SLICES: t.gram_slices = value > 0 ? value : d.gram_slices; break;

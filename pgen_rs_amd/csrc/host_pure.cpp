@@ -4,6 +4,8 @@
 // (tests/test_sanitizers.py fuzzes the table walk with it — these functions parse bytes that come straight from a file).
 #include "../../include/pgen_hip.h"
 
+#include <string.h>
+
 #include <algorithm>
 #include <string>
 
@@ -196,6 +198,48 @@ int pgenhip_vw_select_uncompressed(const uint8_t *record_type, const uint32_t *r
         }
         sel_off[j] = record_off[v];
     }
+    return PGENHIP_OK;
+}
+
+// the lines of a block of VCF body text: where each starts and ends, and where its column `format_col` starts and ends
+int pgenhip_vcf_index_lines(const uint8_t *text, uint64_t text_len, uint32_t format_col, uint64_t max_lines, uint32_t flags,
+                            uint64_t *line_start, uint64_t *format_off, uint64_t *field_off, uint64_t *line_end,
+                            uint64_t *n_lines, uint64_t *consumed)
+{
+    if (!n_lines || !consumed || (!text && text_len) || (max_lines && (!line_start || !format_off || !field_off || !line_end)))
+        return fail(PGENHIP_ERR_BAD_ARG, "NULL argument");
+    if (flags & ~PGENHIP_VCF_LAST_BLOCK) return fail(PGENHIP_ERR_BAD_ARG, "unknown vcf_index_lines flag");
+    uint64_t n = 0, pos = 0;
+    while (n < max_lines && pos < text_len) {
+        const uint8_t *nl = static_cast<const uint8_t *>(memchr(text + pos, '\n', (size_t)(text_len - pos)));
+        if (!nl && !(flags & PGENHIP_VCF_LAST_BLOCK)) break;   // an incomplete line: the caller's next block starts with it
+        const uint64_t stop = nl ? (uint64_t)(nl - text) : text_len;   // the '\n', or the end of the last block
+        const uint64_t end = nl && stop > pos && text[stop - 1] == '\r' ? stop - 1 : stop;
+        // column c starts behind the c-th tab of the line
+        uint64_t col = pos;
+        bool has_col = true;
+        for (uint32_t c = 0; c < format_col; c++) {
+            const uint8_t *t = static_cast<const uint8_t *>(memchr(text + col, '\t', (size_t)(end - col)));
+            if (!t) {
+                has_col = false;
+                break;
+            }
+            col = (uint64_t)(t - text) + 1u;
+        }
+        line_start[n] = pos;
+        line_end[n] = end;
+        if (has_col) {
+            const uint8_t *t = static_cast<const uint8_t *>(memchr(text + col, '\t', (size_t)(end - col)));
+            format_off[n] = col;
+            field_off[n] = t ? (uint64_t)(t - text) : end;
+        } else {
+            format_off[n] = field_off[n] = UINT64_MAX;
+        }
+        n++;
+        pos = nl ? stop + 1u : text_len;
+    }
+    *n_lines = n;
+    *consumed = pos;
     return PGENHIP_OK;
 }
 

@@ -59,6 +59,7 @@ struct Tuning {
     int matrix_blocks = 0;         // genotype matrix kernels: grid size in blocks (0 = by shape, capped per CU)
     int pair_blocks = 0;           // pairwise kernel: grid size in blocks (0 = by shape, capped per CU)
     int pack_blocks = 0;           // pack kernels: grid size in blocks (0 = by shape, capped per CU)
+    int parse_blocks = 0;          // GT text parse kernels: grid size in blocks (0 = by shape, capped per CU)
     int spair_slices = 0;          // pairwise sample tables: row ranges per sample tile (0 = by shape: the chip's resident blocks, at least 256 rows each)
     int vsum_blocks = 0;           // per-variant sums: grid size in blocks (0 = by shape, capped per CU)
     int gram_slices = 0;           // sample Gram matrix: row ranges per rank tile (0 = by shape: the chip's resident blocks, at least 256 rows each)
@@ -274,6 +275,28 @@ constexpr uint32_t kPackIdentityMap = 0xE4u;
 hipError_t launch_gt_pack_general(const PackArgs &a, int blocks, int num_cus, hipStream_t stream);
 hipError_t launch_gt_pack_dense(const PackArgs &a, int blocks, int num_cus, hipStream_t stream);
 hipError_t launch_gt_pack_gather(const PackArgs &a, int blocks, int num_cus, hipStream_t stream);
+
+// GT text -> records (gt_parse.hip): for line j the sample fields of text[field_off[j], line_end[j]) become the mode-0x02 record of
+// N samples at out + j * out_stride (pad bits zero) and the line's PGENHIP_PARSE_* flag word.  Offsets past text_len are clamped.
+struct ParseArgs {
+    const uint8_t *text;          // device, any alignment
+    uint64_t text_len;
+    const uint64_t *field_off;    // device: the tab in front of sample 0's field
+    const uint64_t *line_end;     // device: one past the last field's last byte
+    uint32_t n_lines;
+    uint32_t sample_count;        // N
+    uint32_t record_size;         // R = ceil(N/4)
+    uint8_t *out;                 // device, any alignment
+    uint64_t out_stride;
+    uint32_t *line_flags;         // device, one word per line
+};
+// GENERAL: any field width; overwrites a line's R record bytes and its flag word.  declined_only: takes the lines whose flag word
+// has PGENHIP_PARSE_DECLINED (AUTO's second pass) and leaves the others alone.
+hipError_t launch_gt_parse_general(const ParseArgs &a, bool declined_only, int blocks, int num_cus, hipStream_t stream);
+// FIXED: regions of exactly 4N bytes of `\t[01.][/|][01.]`.  validate: ORs PHASED / HALF_CALL / DECLINED into the flag words (zero
+// before the launch); write: stores the record bytes — with validate, of every 4N-byte line (AUTO: GENERAL rewrites the declined
+// ones), without, of the lines a validate launch before it did not decline (forced FIXED).
+hipError_t launch_gt_parse_fixed(const ParseArgs &a, bool validate, bool write, int blocks, int num_cus, hipStream_t stream);
 
 // Deterministic synthetic records (SURVEY.md §8d counter-based generator).
 hipError_t launch_synth_records(uint8_t *dst, uint64_t record_stride, uint32_t sample_count,

@@ -1,10 +1,11 @@
 // launch_plan.h — the launch plans of the analysis kernels (gt_count, gt_scount, gt_score, gt_vsum, gt_matrix, gt_pair, gt_pack,
-// gt_spair, gt_gram, gt_gapply) and the launch rule of the stream kernel (gt_wide): lanes per row, tiles, row ranges ("slices"), grid
+// gt_spair, gt_gram, gt_gapply, gt_parse) and the launch rule of the stream kernel (gt_wide): lanes per row, tiles, row ranges ("slices"), grid
 // caps, store policy and write fronts, as functions of scalars; and the emit path (namespace emit): the shapes each emit kernel takes,
 // AUTO's chains and the forced kernel ids, the chunks of the two passes, and the launch plans of the segment, row-owner and pick
 // kernels.  The single statement
 // of every plan: capi.hip and the launchers call it, the kernels take their constants and their row ranges from it, and the tests compile this
-// header for the host (tests/plan_probe.cpp, tests/gapply_plan_probe.cpp, tests/wide_plan_probe.cpp, tests/emit_plan_probe.cpp) and run it.
+// header for the host (tests/plan_probe.cpp, tests/gapply_plan_probe.cpp, tests/wide_plan_probe.cpp, tests/emit_plan_probe.cpp,
+// tests/parse_plan_probe.cpp) and run it.
 // Plain C++17 on purpose: no HIP header, no kernel argument struct (emit::Shape is a struct of scalars).
 #pragma once
 #include <stdint.h>
@@ -1060,5 +1061,63 @@ PGENHIP_PLAN_HD inline PickLinesPlan pick_lines_plan(const Shape &s, const PickP
 }
 
 }  // namespace emit
+
+// ---- gt_parse: GT text -> mode-0x02 records (the inverse of the emit path) ------------------------------------------------------------
+namespace parse {
+
+constexpr int kThreads = 256;
+constexpr uint32_t kWaves = kThreads / 64;
+constexpr uint32_t kBlocksPerCu = 8;          // grid cap of both grid-stride kernels
+// FIXED: a piece is one work item — kPieceBytes record bytes = kPieceSamples fields = kPieceText text bytes (one 16-byte load at
+// any alignment; byte loads on a line's last, partial piece).  A lane takes kLanePieces of them per turn, kThreads items apart.
+constexpr uint32_t kPieceBytes = 1;
+constexpr uint32_t kPieceSamples = 4u * kPieceBytes;
+constexpr uint32_t kPieceText = 4u * kPieceSamples;
+constexpr uint32_t kLanePieces = 4;
+constexpr uint32_t kBlockPieces = (uint32_t)kThreads * kLanePieces;   // items of a block per turn
+// GENERAL: text bytes of one chunk of a line (kChunkLaneBytes per lane); the tab count runs on from chunk to chunk
+constexpr uint32_t kChunkLaneBytes = 4;
+constexpr uint32_t kChunkBytes = (uint32_t)kThreads * kChunkLaneBytes;
+
+// FIXED: pieces of a line.  A line of no samples still has one, which only checks that the region is empty.
+PGENHIP_PLAN_HD constexpr uint32_t pieces_per_line(uint32_t record_size) { return record_size == 0u ? 1u : (record_size + kPieceBytes - 1u) / kPieceBytes; }
+// record bytes [begin, end) of piece p of a line of R bytes: the pieces tile [0, R) in order
+PGENHIP_PLAN_HD constexpr RowRange piece_bytes(uint32_t record_size, uint32_t piece)
+{
+    return {std::min<uint64_t>((uint64_t)piece * kPieceBytes, record_size), std::min<uint64_t>(((uint64_t)piece + 1u) * kPieceBytes, record_size)};
+}
+// FIXED: the launch is flat over (line, piece): item i is piece i % P of line i / P, kBlockPieces consecutive items per block and
+// turn, so a block holds kBlockPieces / P lines of short rows (rows_per_block; at least part of two when P does not divide
+// kBlockPieces) and a long row spreads over ceil(P / kBlockPieces) blocks.
+PGENHIP_PLAN_HD constexpr uint32_t rows_per_block(uint32_t record_size) { return std::max<uint32_t>(1u, kBlockPieces / pieces_per_line(record_size)); }
+PGENHIP_PLAN_HD constexpr uint32_t blocks_per_row(uint32_t record_size) { return (pieces_per_line(record_size) + kBlockPieces - 1u) / kBlockPieces; }
+
+struct FixedPlan {
+    uint32_t pieces;   // per line
+    uint64_t total;    // items of the launch
+    uint32_t grid;
+};
+// blocks: forced grid size (0 = by shape)
+PGENHIP_PLAN_HD inline FixedPlan fixed_plan(uint32_t record_size, uint32_t n_lines, int num_cus, int blocks)
+{
+    FixedPlan p{};
+    p.pieces = pieces_per_line(record_size);
+    p.total = (uint64_t)n_lines * p.pieces;
+    p.grid = grid_blocks((p.total + kBlockPieces - 1u) / kBlockPieces, kBlocksPerCu, num_cus, blocks);
+    return p;
+}
+
+// GENERAL: a block per line, the lines by grid stride.  One line is not split over blocks: a call with few very long lines uses
+// few CUs (as pair_stats' tiles do with few rows).
+PGENHIP_PLAN_HD inline uint32_t general_grid(uint32_t n_lines, int num_cus, int blocks) { return grid_blocks(n_lines, kBlocksPerCu, num_cus, blocks); }
+// chunks a region of `bytes` text bytes takes when it starts `lead` bytes (0 .. 3) behind a 4-byte boundary
+PGENHIP_PLAN_HD constexpr uint64_t general_chunks(uint64_t bytes, uint32_t lead) { return (bytes + lead + kChunkBytes - 1u) / kChunkBytes; }
+
+// AUTO: the FIXED pass over every line, then a GENERAL pass that takes the declined lines only.  GENERAL alone, the other
+// candidate, measured 6.9-14 x behind the two passes on fixed-width text (chr22 29.3 against 3.9 ms, basic2 55.9 against 3.9 ms, a
+// block of configs[2] 10.2 against 1.5 ms: profiles/r14_parse/parse_bench.jsonl).
+constexpr bool kAutoFixedFirst = true;
+
+}  // namespace parse
 
 }  // namespace pgenhip::plan

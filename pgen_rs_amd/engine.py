@@ -82,6 +82,21 @@ def vw_select_uncompressed(types: np.ndarray, lens: np.ndarray, offs: np.ndarray
     return sel[:n]
 
 
+def vcf_index_lines(data: bytes, format_col: int, last_block: bool = True, max_lines: Optional[int] = None):
+    """The lines of a block of VCF body text (``pgenhip_vcf_index_lines``): ``(line_start, format_off, field_off, line_end,
+    consumed)``, four uint64 arrays with one entry per line and the offset just past the last line reported.  ``field_off`` is
+    the tab behind column ``format_col`` (``line_end`` for a line whose last column that is, 2**64 - 1 for a line with fewer
+    columns); ``last_block``: a final line without a newline counts."""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    cap = buf.size + 1 if max_lines is None else int(max_lines)   # a line takes at least one byte
+    arrs = [np.zeros(max(cap, 1), dtype=np.uint64) for _ in range(4)]
+    n, consumed = C.c_uint64(), C.c_uint64()
+    check(lib.pgenhip_vcf_index_lines(buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size, format_col, cap,
+                                      _capi.VCF_LAST_BLOCK if last_block else 0, *[a.ctypes.data_as(C.c_void_p) for a in arrs],
+                                      C.byref(n), C.byref(consumed)), "pgenhip_vcf_index_lines")
+    return (*[a[:n.value] for a in arrs], int(consumed.value))
+
+
 # pack_records' code_map for PLINK 1 .bed with ALT as A1: 00 hom A1, 01 missing, 10 het, 11 hom A2
 BED_CODE_MAP = (3, 2, 0, 1)
 
@@ -629,6 +644,53 @@ class GtEngine:
 
     def _pack_view(self, out: torch.Tensor, n_variants: int, stride: int, out_offset: int) -> torch.Tensor:
         return torch.as_strided(out, (n_variants, self.packed_record_size), (stride, 1), out_offset)
+
+    # -- GT text to records ---------------------------------------------------------------------
+    def parse_gt(self, text: torch.Tensor, field_off: torch.Tensor, line_end: torch.Tensor, *, out: Optional[torch.Tensor] = None,
+                 out_stride: Optional[int] = None, out_offset: int = 0, shape: int = _capi.PARSE_AUTO, text_offset: int = 0,
+                 text_len: Optional[int] = None, line_flags: Optional[torch.Tensor] = None,
+                 n_lines: Optional[int] = None) -> tuple[torch.Tensor, torch.Tensor]:
+        """The inverse of ``decode_emit``: ``(records, line_flags)``, a ``(n_lines, R)`` uint8 view whose row j is the mode-0x02
+        record of the N samples of line j's fields (pad bits zero), and an int32 tensor of the lines' ``_capi.PARSE_*`` flag bits.
+
+        ``text``: a flat uint8 CUDA tensor; the library reads bytes ``[text_offset, text_offset + text_len)`` of it and nothing
+        else (default: to its end), and ``field_off`` / ``line_end`` (int64 CUDA tensors: the tab in front of sample 0's field, and
+        one past the last field) count from ``text_offset``.  ``out``: a flat uint8 CUDA tensor; row j goes to byte
+        ``out_offset + j*out_stride`` (default stride R) and nothing else is touched.  ``line_flags``: an int32 CUDA tensor of
+        ``n_lines`` words to write into.  The context must keep all samples."""
+        for t, name in ((text, "text"), (field_off, "field_off"), (line_end, "line_end")):
+            self._check_dev(t, name)
+        if text.dtype != torch.uint8:
+            raise ValueError("text must be a uint8 tensor")
+        if field_off.dtype not in (torch.int64, torch.uint64) or line_end.dtype not in (torch.int64, torch.uint64):
+            raise ValueError("field_off and line_end must be 64-bit integer tensors")
+        if n_lines is None:
+            n_lines = field_off.numel()
+        if field_off.numel() < n_lines or line_end.numel() < n_lines:
+            raise ValueError("field_off or line_end has fewer than n_lines entries")
+        if text_len is None:
+            text_len = text.numel() - text_offset
+        if text_offset < 0 or text_len < 0 or text_offset + text_len > text.numel():
+            raise ValueError("text_offset / text_len lie outside text")
+        r = self.record_size
+        if out_stride is None:
+            out_stride = r
+        if out is None:
+            out = torch.empty(out_offset + max(n_lines * out_stride, r, 1), dtype=torch.uint8, device=self.torch_device)
+        self._check_dev(out, "out")
+        if out.dtype != torch.uint8:
+            raise ValueError("out must be a uint8 tensor")
+        if n_lines and out.numel() < out_offset + (n_lines - 1) * out_stride + r:
+            raise ValueError("out too small")
+        if line_flags is None:
+            line_flags = torch.empty(max(n_lines, 1), dtype=torch.int32, device=self.torch_device)
+        self._check_dev(line_flags, "line_flags")
+        if line_flags.dtype not in (torch.int32, torch.uint32) or line_flags.numel() < n_lines:
+            raise ValueError("line_flags must be a 32-bit integer tensor of n_lines entries")
+        out = out.view(-1)
+        check(lib.pgenhip_parse_gt(self._ctx, _ptr(text, text_offset), text_len, _ptr(field_off), _ptr(line_end), n_lines,
+                                   _ptr(out, out_offset), out_stride, _ptr(line_flags), shape), "pgenhip_parse_gt")
+        return torch.as_strided(out, (n_lines, r), (out_stride, 1), out_offset), line_flags[:n_lines]
 
     # -- windowed pairwise tables / r^2 ---------------------------------------------------------
     def pair_tables(self, records: torch.Tensor, record_stride: Optional[int] = None, variant_idx: Optional[torch.Tensor] = None,

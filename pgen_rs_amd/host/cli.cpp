@@ -104,6 +104,7 @@ const char *kUsage =
     "  grm     Genetic relationship matrix of the kept samples, outputting GCTA-style binary files or a text square\n"
     "  pca     Leading principal components of the kept samples, outputting .eigenval and .eigenvec files\n"
     "  export  Writes the kept variants and samples back as a .pgen (or PLINK 1 .bed) fileset\n"
+    "  import  Reads a VCF's GT calls into a .pgen / .pvar / .psam fileset\n"
     "  help    Print this message\n\n"
     "query  <PFILE_PREFIX> -f, --fstring <QUERY_FSTRING> [-i, --include <QUERY>] [-s, --samples]\n"
     "filter <PFILE_PREFIX> [--include-var <VAR_QUERY>] [--include-sam <SAM_QUERY>] [-o, --out <OUT_FILE>]\n"
@@ -148,6 +149,16 @@ const char *kUsage =
     "       the kept variants and samples as OUT_PREFIX.pgen (fixed-width, storage mode 0x02), .pvar (the header lines and the kept\n"
     "       rows) and .psam; --format bed: PLINK 1 OUT_PREFIX.bed (variant-major, ALT as A1), .bim (CHROM ID 0 POS ALT REF) and .fam\n"
     "       (FID IID PAT MAT SEX -9; 0 for a missing column).  OUT_PREFIX must not name the input; no byte parity with plink2 is claimed\n"
+    "import <IN.vcf[.gz]> -o, --out <OUT_PREFIX> [--skip-multiallelic] [--block-mib <M>] [--stats]\n"
+    "       the VCF's biallelic GT hard calls as OUT_PREFIX.pgen (fixed-width, storage mode 0x02), .pvar (the ## lines but ##fileformat= and\n"
+    "       `##source=pgen-rs`, which filter adds itself, and the columns in front of FORMAT, verbatim) and .psam (#IID SEX, with NA), so that\n"
+    "       `filter` on OUT_PREFIX gives back a VCF that `filter` wrote.  GT must be the first FORMAT key; calls are 0, 1 and '.' with '/' or\n"
+    "       '|' (the phase is dropped; a half call and a haploid '.' are missing, haploid 0 / 1 are 0/0 / 1/1; the lines with any of the three\n"
+    "       are counted and warned about once each).  Any other call, another allele (what a multiallelic line holds: --skip-multiallelic\n"
+    "       drops the lines whose ALT has a ',' and counts them), or a line with too few columns or fields is an error that names the input's line and leaves no\n"
+    "       output file.  A gzip or BGZF input is inflated by one sequential zlib stream over its members (parallel inflate of BGZF members is\n"
+    "       not built); one device is used whatever --gpus says: the reader, not the parse kernel, bounds this command.  Compressed .pgen\n"
+    "       records and BCF are not read\n"
     "kinship <PFILE_PREFIX> [--include-var <VAR_QUERY>] [--include-sam <SAM_QUERY>] [--min-kinship <X>] [--counts] [-o, --out <OUT_FILE>]\n"
     "       [--gpus <N>] [--shards <S>] [--block-mib <M>] [--block-rows <B>] [--sample-tile <T>] [--read-threads <T>] [--filter-threads <T>] [--stats]\n"
     "       one line per pair of kept samples in psam order: IID1 IID2 N HETHET IBS0 HET1 HET2 KINSHIP over the kept variants called in\n"
@@ -553,6 +564,26 @@ int main(int argc, char **argv)
             e.bed = format == "bed";
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
             return a.done(pfile.output_export(a.get("include-sam"), a.get("include-var"), *a.get("out"), e, output_options(a)), t_main);
+        }
+        if (cmd == "import") {
+            Args a = parse(argc, argv, 2, {{"out", 'o'}, {"block-mib", 0}}, {{"skip-multiallelic", 0}, {"stats", 0}});
+            if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <IN.vcf[.gz]>");
+            if (!a.has("out") || a.get("out")->empty()) usage_error("the following required arguments were not provided: --out <OUT_PREFIX>");
+            ImportOptions io;
+            io.skip_multiallelic = a.has("skip-multiallelic");
+            OutputOptions opt;
+            if (auto m = a.get("block-mib")) opt.block_text_bytes = unsigned_value(*m, "block-mib", "M", 1, 65536, "a number of MiB from 1 to 65536") << 20;
+            const OutputStats st = import_vcf(a.positional[0], *a.get("out"), io, opt);
+            if (a.has("stats"))
+                std::fprintf(stderr,
+                             "{\"variants\": %llu, \"samples\": %llu, \"skipped_multiallelic\": %llu, \"half_call_lines\": %llu, \"haploid_lines\": %llu, "
+                             "\"phased_lines\": %llu, \"file_bytes\": %llu, \"seconds_filter\": %.6f, \"seconds_body\": %.6f, \"seconds_setup\": %.6f, "
+                             "\"seconds_kernel\": %.6f, \"seconds_main\": %.6f}\n",
+                             (unsigned long long)st.variants, (unsigned long long)st.samples_kept, (unsigned long long)st.import_skipped,
+                             (unsigned long long)st.import_half_call, (unsigned long long)st.import_haploid, (unsigned long long)st.import_phased,
+                             (unsigned long long)st.file_bytes, st.seconds_filter, st.seconds_body, st.seconds_setup, st.seconds_kernel,
+                             std::chrono::duration<double>(std::chrono::steady_clock::now() - t_main).count());
+            return 0;
         }
         if (cmd == "ld") {
             const SelectionArgs a(argc, argv, {{"window", 0}, {"min-r2", 0}, {"block-rows", 0}}, {{"counts", 0}});

@@ -174,6 +174,7 @@ struct OutputStats {
     uint64_t pca_skipped = 0, pca_passes = 0;                                    // `pca`: kept variants that add nothing; passes over the records
     double pca_residual = 0;                                                     // `pca`: max over the written components of |M u - lambda u| / lambda_1 at the last pass
     bool pca_converged = true;                                                   // `pca`: the residual reached --tol within --max-passes
+    uint64_t import_skipped = 0, import_half_call = 0, import_haploid = 0, import_phased = 0;   // `import`: multiallelic lines dropped; lines with a half call, a haploid call, a phased call
     double seconds_setup = 0;   // inside seconds_body: HIP runtime start, contexts, device and pinned allocations of the slowest shard, before its first block is staged
 };
 
@@ -364,6 +365,21 @@ class Pfile {
 // Synthetic PREFIX.{pgen,pvar,psam}: pvar rows "22\t{16050000+7i}\tsnp{i}\tA\tG\t100\tPASS\t.",
 // psam "#IID\tSEX\tKEEP" with "S{i:06d}\tNA\t{keep}", records from pgenhip_synth_records on device 0.
 void synth_pfile(const std::string &prefix, uint32_t variants, uint32_t samples, uint32_t keep_modulus, uint64_t seed);
+
+// `import`: what becomes of lines that a biallelic hard-call file cannot hold
+struct ImportOptions {
+    bool skip_multiallelic = false;   // --skip-multiallelic: drop the lines whose ALT holds a ',' (and count them); without it their alleles >= 2 are an error
+};
+
+// VCF (plain text, or gzip / BGZF: one sequential zlib stream over concatenated members) to OUT_PREFIX.pgen (fixed-width, storage
+// mode 0x02), .pvar (the ## lines but ##fileformat= and `##source=pgen-rs`, which `filter` adds itself; the columns in front of FORMAT,
+// verbatim) and .psam (#IID SEX, NA).  Blocks of whole lines go through read -> pinned -> H2D -> pgenhip_parse_gt -> D2H -> pwrite at
+// 12 + j*R; a reader thread fills and indexes block k + 1 (pgenhip_vcf_index_lines) while block k is on the device.  One device: the
+// reader bounds the command.  A FORMAT other than GT / GT:..., a line with too few columns or fields, a call of another form than
+// the grammar's or an allele other than 0, 1 and '.' is an error that names the input's line (1-based) and leaves no output file;
+// half calls, haploid calls and phased calls are counted per line and warned about once each.  More than 2^32 - 1 variants is an
+// error.  Uses block_text_bytes of `opt` (text bytes per block).
+OutputStats import_vcf(const std::string &in_path, const std::string &out_prefix, const ImportOptions &iopt, const OutputOptions &opt = OutputOptions());
 
 // whole-file read helper (metadata files are read once; the reference streams them through BufReader)
 std::string read_file(const std::string &path);
