@@ -48,6 +48,7 @@
 #include "bgzf.h"
 #include "expr.h"
 #include "pfile.h"
+#include "stats.h"
 
 using namespace pgenhost;
 
@@ -522,7 +523,7 @@ int main(int argc, char **argv)
                 char *e1 = nullptr, *e2 = nullptr;
                 const double t = argc == 5 ? std::strtod(argv[3], &e1) : 0.0, df = argc == 5 ? std::strtod(argv[4], &e2) : 0.0;
                 if (argc != 5 || *argv[3] == '\0' || *e1 != '\0' || *argv[4] == '\0' || *e2 != '\0' || !(df > 0)) usage_error("--p-of takes a statistic and its degrees of freedom (> 0)");
-                std::printf("%.17g\n", student_t_two_sided_p(t, df));
+                std::printf("%.17g\n", stats::student_t_two_sided_p(t, df));
                 return 0;
             }
             const SelectionArgs a(argc, argv, {{"pheno", 0}, {"pheno-name", 0}, {"covar", 0}}, {});

@@ -1,5 +1,5 @@
-// host_internal.h — what pfile.cpp (the restatement of src/pfile.rs) and commands.cpp (the commands the reference does not have)
-// share below the public surface of pfile.h: status checks, file spans, the checked selection, a ctx with its buffers, the shards.
+// host_internal.h — what pfile.cpp (the restatement of src/pfile.rs) and commands.cpp / import.cpp (the commands the reference does
+// not have) share below the public surface of pfile.h: status checks, file spans, the checked selection, a ctx with its buffers, the shards.
 #pragma once
 #include <algorithm>
 #include <mutex>

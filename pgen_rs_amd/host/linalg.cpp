@@ -1,5 +1,5 @@
-// linalg.cpp — Householder QR and cyclic Jacobi for `pgen-hip pca` (linalg.h).  Pure C++; tests/linalg_check.cpp runs it under
-// AddressSanitizer and UBSan as a stand-alone program.
+// linalg.cpp — Householder QR, cyclic Jacobi and the steps of the subspace iteration for `pgen-hip pca` (linalg.h).  Pure C++;
+// tests/linalg_check.cpp and tests/stats_check.cpp run it under AddressSanitizer and UBSan as stand-alone programs.
 #include "linalg.h"
 
 #include <algorithm>
@@ -103,6 +103,74 @@ void jacobi_eigh(const std::vector<double> &t, size_t L, std::vector<double> &la
             if (std::fabs(v[k * L + src]) > std::fabs(v[big * L + src])) big = k;
         const double sign = v[big * L + src] < 0.0 ? -1.0 : 1.0;
         for (size_t k = 0; k < L; k++) w[k * L + i] = sign * v[k * L + src];
+    }
+}
+
+namespace {
+
+// splitmix64: the next state's output
+uint64_t splitmix64(uint64_t &state)
+{
+    uint64_t z = (state += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+}  // namespace
+
+void gaussian_start(uint64_t seed, size_t K, size_t L, std::vector<double> &q)
+{
+    q.resize(K * L);
+    uint64_t state = seed;
+    for (double &x : q) {
+        const double u1 = (double)((splitmix64(state) >> 11) + 1) * 0x1p-53, u2 = (double)(splitmix64(state) >> 11) * 0x1p-53;
+        x = std::sqrt(-2.0 * std::log(u1)) * std::cos(2.0 * M_PI * u2);
+    }
+}
+
+double rayleigh_ritz(const std::vector<double> &q, const std::vector<double> &y, size_t K, size_t L, size_t P, std::vector<double> &lambda,
+                     std::vector<double> &u)
+{
+    std::vector<double> t(L * L), w;
+    for (size_t a = 0; a < L; a++)
+        for (size_t b = 0; b < L; b++) {
+            double dot = 0.0;
+            for (size_t k = 0; k < K; k++) dot += q[k * L + a] * y[k * L + b];
+            t[a * L + b] = dot;
+        }
+    for (size_t a = 0; a < L; a++)
+        for (size_t b = a + 1; b < L; b++) t[a * L + b] = t[b * L + a] = 0.5 * (t[a * L + b] + t[b * L + a]);
+    jacobi_eigh(t, L, lambda, w);
+    u.resize(K * L);
+    double worst = 0.0;
+    for (size_t i = 0; i < L; i++) {
+        double rr = 0.0;
+        for (size_t k = 0; k < K; k++) {
+            double uk = 0.0, yw = 0.0;
+            for (size_t a = 0; a < L; a++) {
+                uk += q[k * L + a] * w[a * L + i];
+                yw += y[k * L + a] * w[a * L + i];
+            }
+            u[k * L + i] = uk;
+            const double r = yw - lambda[i] * uk;
+            rr += r * r;
+        }
+        if (i < P) worst = std::max(worst, std::sqrt(rr));
+    }
+    return worst;
+}
+
+void unit_columns_largest_positive(std::vector<double> &u, size_t K, size_t L, size_t P)
+{
+    for (size_t i = 0; i < P; i++) {
+        double ss = 0.0, big = 0.0;
+        for (size_t k = 0; k < K; k++) {
+            ss += u[k * L + i] * u[k * L + i];
+            if (std::fabs(u[k * L + i]) > std::fabs(big)) big = u[k * L + i];
+        }
+        const double scale = (big < 0.0 ? -1.0 : 1.0) / (ss > 0.0 ? std::sqrt(ss) : 1.0);
+        for (size_t k = 0; k < K; k++) u[k * L + i] *= scale;
     }
 }
 

@@ -135,10 +135,6 @@ struct ValueTable {
 };
 ValueTable read_value_table(const std::string &path);
 
-// two-sided P of a Student t statistic with df degrees of freedom: I_{df / (df + t^2)}(df / 2, 1 / 2), the regularised incomplete
-// beta function by a Lentz continued fraction (no library)
-double student_t_two_sided_p(double t, double df);
-
 // `kinship`: what is printed and how the kept samples are cut into rank tiles on the device
 struct KinshipOptions {
     bool counts = false;              // --counts: the sixteen cells of the pair's table behind KINSHIP
@@ -268,7 +264,7 @@ class Pfile {
     // intercept and the covariates, over the kept samples that have every chosen phenotype and every covariate (complete cases); a
     // missing call counts as the variant's mean dosage over the called samples (mean imputation, as in `score`; plink2 --glm drops
     // the sample for that variant instead, so no digit parity with it is claimed).  The host orthonormalises [1, covariates]
-    // (modified Gram-Schmidt, twice) into Q and residualises every phenotype, r_p = y_p - Q Q' y_p; Q's columns and the r_p go up
+    // (modified Gram-Schmidt, twice; stats.h holds this arithmetic) into Q and residualises every phenotype, r_p = y_p - Q Q' y_p; Q's columns and the r_p go up
     // once per shard as K x (m + P) doubles.  Per block (freq's block loop and shards) pgenhip_genotype_counts gives c0 .. c3 and
     // pgenhip_variant_sums, at most PGENHIP_VSUM_MAX_COLUMNS columns per launch, the four per-code sums S[v][x] of every column;
     // 16 + 32 (m + P) bytes per row come back.  With called = c0 + c1 + c2, mu = (c1 + 2 c2) / called, t_v = S[v][1] + 2 S[v][2]
