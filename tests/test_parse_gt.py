@@ -244,6 +244,52 @@ def test_fixed_items_tile_every_line_once():
     assert parse_plan.edge_sample_counts() == sorted(set(parse_plan.edge_sample_counts())) and len(parse_plan.edge_sample_counts()) >= 3
 
 
+def test_plans_at_the_far_end_of_the_item_range():
+    """The launches of tests/test_long_rows_parse_gpu.py on both sides of 2^32 items, and the most lines of the longest rows: ``total``
+    is not truncated and the grids equal their caps."""
+    cap = 256 * parse_plan.BLOCKS_PER_CU
+    for r, n_lines, total in ((1025, 4_190_208, 4_294_963_200), (1025, 4_190_211, 2**32 - 1021), (1025, 4_190_213, 4_294_968_325),
+                              (2**29, 2**32 - 1, 2**61 - 2**29)):
+        for blocks in (0, 7):
+            want = (r, total, blocks or cap)
+            assert parse_plan.fixed_plan(r, n_lines, 256, blocks) == want
+            assert parse_plan.probe("parse_fixed_plan", 3, r, n_lines, 256, blocks) == want
+    for num_cus, blocks in ((256, 0), (0, 0), (304, 0), (256, 3)):
+        want = blocks or (num_cus or 256) * parse_plan.BLOCKS_PER_CU
+        assert parse_plan.general_grid(2**32 - 1, num_cus, blocks) == want
+        assert parse_plan.probe("parse_general", 2, 2**32 - 1, num_cus, blocks, 0, 0)[0] == want
+
+
+def test_fixed_items_tile_every_line_once_around_2_32():
+    """The tiling property on a window of items around 2^32: item i is piece i % P of line i // P.  A host loop as the FIXED kernel's
+    (blocks of BLOCK_PIECES items by grid stride, LANE_PIECES items per lane, THREADS apart) over the last two turns of the launch
+    only: every item of the window is taken once, none at or past ``total``, and the items of the lines that lie wholly inside the
+    window are every piece of that line once, with the piece's record bytes from the header."""
+    r = 1025
+    for n_lines in (4_190_208, 4_190_211, 4_190_213):
+        pieces, total, grid = parse_plan.fixed_plan(r, n_lines)
+        bp, threads = parse_plan.BLOCK_PIECES, parse_plan.THREADS
+        turn = grid * bp
+        first_turn = max(0, -(-total // turn) - 2)
+        lane_items = (np.arange(parse_plan.LANE_PIECES, dtype=np.int64)[:, None] * threads + np.arange(threads, dtype=np.int64)[None, :]).reshape(-1)
+        taken, masked_off = [], 0
+        for block in range(grid):
+            for i0 in range(block * bp + first_turn * turn, total, turn):
+                at = i0 + lane_items
+                taken.append(at[at < total])
+                masked_off += int((at >= total).sum())
+        taken = np.sort(np.concatenate(taken))
+        lo = first_turn * turn
+        assert lo < 2**32 - bp and np.array_equal(taken, np.arange(lo, total, dtype=np.int64))   # every item once, none at or past total
+        assert masked_off == -total % bp and (int(taken[-1]) >= 2**32) == (n_lines == 4_190_213)
+        j0 = -(-lo // pieces)   # the lines wholly inside the window: every piece once, in order
+        inside = taken[taken >= j0 * pieces]
+        assert np.array_equal(inside // pieces, np.repeat(np.arange(j0, n_lines, dtype=np.int64), pieces))
+        assert np.array_equal(inside % pieces, np.tile(np.arange(pieces, dtype=np.int64), n_lines - j0))
+        j = n_lines - 1
+        assert [parse_plan.probe("parse_piece_bytes", 2, r, i % pieces) for i in (j * pieces, (j + 1) * pieces - 1)] == [(0, 1), (r - 1, r)]
+
+
 # ---- the import command, up to the device -----------------------------------------------------------------------------------------------
 def run(*args):
     return subprocess.run([str(CLI), *args], capture_output=True)
