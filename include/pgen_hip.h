@@ -626,6 +626,52 @@ int pgenhip_parse_gt(pgenhip_ctx *ctx, const void *d_text, uint64_t text_len,
                      const uint64_t *d_field_off, const uint64_t *d_line_end, uint32_t n_lines,
                      void *d_out, uint64_t out_stride, uint32_t *d_line_flags, uint32_t flags);
 
+/* ---- sample-wise join of records (device-resident, asynchronous on the ctx stream) ----
+ * The inverse of pgenhip_pack_records' sample selection: row j of the output is the mode-0x02 record of N_out = sum of the parts'
+ * sample_count samples, the samples of part 0 first, then part 1, and so on: output sample start_p + s (s < n_p) is sample s of part
+ * p's record for row j, the record at d_base + d_record_off[j] (ceil(n_p / 4) bytes, any alignment).  So a host that puts the 12-byte
+ * header in front of the rows has a .pgen of several filesets' samples side by side.
+ *   - A part whose d_record_off[j] is PGENHIP_JOIN_ABSENT has no record for row j: its n_p samples get code 3 and nothing of the
+ *     part is read for that row.  Two rows may name the same record.
+ *   - A part with a d_flip array has codes 0 and 2 exchanged in the rows with d_flip[j] != 0 (REF and ALT the other way round in
+ *     that part); codes 1 and 3 stay.
+ *   - The pad bits of the output's last byte are always written as zero.  The pad bits of a part's last record byte are never
+ *     read as samples, whatever they hold.
+ *   - The ctx must keep all samples (no list, or the identity list), as for pgenhip_parse_gt, and its sample count must equal the
+ *     sum of the parts' sample_count (summed in 64 bits).  A part with sample_count 0 is legal: it adds nothing and its pointers are
+ *     not touched.
+ *   - Row j is the R = ceil(N_out / 4) bytes at d_out + j*out_stride, out_stride >= R or n_variants <= 1; d_out and the records
+ *     may have any alignment.  Nothing outside the n_variants x R record bytes is written: row padding is untouched.
+ *   - Of a part, only aligned 16-byte chunks that hold a byte of a present row's ceil(n_p / 4)-byte record may be loaded (the
+ *     kernels as built load record bytes only), and its n_variants offsets and flip bytes.
+ *   - n_variants == 0 or N_out == 0 writes nothing and is PGENHIP_OK.
+ *   - Shapes (flags; other bits and values are PGENHIP_ERR_BAD_ARG).  GENERAL: a lane per output byte, the correctness baseline.
+ *     STREAM: a lane per aligned 16-byte chunk of an output row, its source bytes read at the part's own bit phase.  Both take any
+ *     part sizes; their bytes are equal.  AUTO takes STREAM.
+ *   - Refused before any launch, d_out untouched.  PGENHIP_ERR_BAD_ARG, with a detail string: parts NULL; n_parts 0 or above
+ *     PGENHIP_JOIN_MAX_PARTS; a part's reserved != 0; a sample sum other than the ctx's N; a ctx with a proper subset; a part with
+ *     sample_count > 0 and a NULL d_base or d_record_off while n_variants > 0; a d_record_off not 8-byte aligned; d_out NULL where a
+ *     byte would be written; out_stride < R with n_variants > 1; unknown flags.  PGENHIP_ERR_TOO_LARGE for out_stride * n_variants
+ *     >= 2^52.
+ * `parts` is a HOST array, read during the call and passed as kernel arguments (no device copy, no allocation; a captured graph
+ * keeps the table it was captured with).  Same launch contract as pgenhip_pack_records: device pointers only, no allocation, no
+ * synchronisation, queued on the ctx stream (one kernel), graph-capturable.  Every output byte has one owner: no atomics and no
+ * work counters, so these launches do not count against PGENHIP_LAUNCHES_IN_FLIGHT. */
+#define PGENHIP_JOIN_MAX_PARTS 8u
+#define PGENHIP_JOIN_ABSENT UINT64_MAX
+typedef struct pgenhip_join_part {
+    const void *d_base;            /* DEVICE */
+    const uint64_t *d_record_off;  /* DEVICE, n_variants byte offsets from d_base; PGENHIP_JOIN_ABSENT = no such row in this part */
+    const uint8_t *d_flip;         /* DEVICE, n_variants bytes, or NULL (no row flipped) */
+    uint32_t sample_count;         /* n_p; 0 is legal: the part adds nothing and its pointers are not touched */
+    uint32_t reserved;             /* must be 0 */
+} pgenhip_join_part;
+#define PGENHIP_JOIN_AUTO 0u
+#define PGENHIP_JOIN_GENERAL 1u   /* one lane per output byte: the correctness baseline */
+#define PGENHIP_JOIN_STREAM 2u    /* output-driven: one aligned 16-byte chunk of an output row per lane */
+int pgenhip_join_records(pgenhip_ctx *ctx, const pgenhip_join_part *parts, uint32_t n_parts, uint32_t n_variants,
+                         void *d_out, uint64_t out_stride, uint32_t flags);
+
 /* Pure host function: the lines of a block of VCF body text, for pgenhip_parse_gt.  Per complete line i < *n_lines (a line ends
  * with '\n'; with PGENHIP_VCF_LAST_BLOCK a non-empty remainder without one counts as a line that ends at text_len):
  *   line_start[i]  the line's first byte
@@ -671,6 +717,7 @@ typedef enum pgenhip_knob {
     PGENHIP_KNOB_GAPPLY_ROW_SLICES = 27, /* Gram product, Y pass: row ranges per sample tile, each summed by one block (default 0 = by shape: as many as fill the chip's resident blocks, of at least 256 rows each); tests put the row count on either side of every slice edge */
     PGENHIP_KNOB_WIDE_BURST = 28,        /* stream kernel (GT segments and full lines of long rows): plain store steps issued back to back, 1 or 2; default 0 = by shape (1 on launches of 9 GB of text and more in rows of more than 16 KiB, else 2) */
     PGENHIP_KNOB_PARSE_BLOCKS = 29,      /* GT text parse kernels: grid size in blocks (default 0 = by shape: the work, capped at 8 blocks per CU); tests force small grids */
+    PGENHIP_KNOB_JOIN_BLOCKS = 30,       /* join kernels: grid size in blocks (default 0 = by shape: the work, capped at 8 blocks per CU); tests force small grids */
     PGENHIP_KNOB_RUNS_ROWS = 7       /* RUNS kernel: rows per work item (default: as many as one wide load / one span holds) */
 } pgenhip_knob;
 int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value);

@@ -95,6 +95,11 @@ PARSE_HALF_CALL = 0x08
 PARSE_HAPLOID = 0x10
 PARSE_PHASED = 0x20
 PARSE_DECLINED = 0x40
+JOIN_AUTO = 0
+JOIN_GENERAL = 1
+JOIN_STREAM = 2
+JOIN_MAX_PARTS = 8
+JOIN_ABSENT = 0xFFFFFFFFFFFFFFFF
 VCF_LAST_BLOCK = 1
 PAIR_TABLE = 0
 PAIR_R2 = 1
@@ -128,6 +133,7 @@ KNOB_GAPPLY_SAMPLE_SLICES = 26
 KNOB_GAPPLY_ROW_SLICES = 27
 KNOB_WIDE_BURST = 28
 KNOB_PARSE_BLOCKS = 29
+KNOB_JOIN_BLOCKS = 30
 
 
 
@@ -137,6 +143,12 @@ class VwHeader(C.Structure):
                 ("record_type_bits", C.c_uint8), ("record_length_bytes", C.c_uint8), ("allele_count_bytes", C.c_uint8),
                 ("provisional_ref_storage", C.c_uint8), ("reserved", C.c_uint8 * 3), ("block_count", C.c_uint64),
                 ("main_header_body_offset", C.c_uint64), ("variant_records_offset", C.c_uint64)]
+
+
+class JoinPart(C.Structure):
+    """``pgenhip_join_part`` (include/pgen_hip.h): one input of ``pgenhip_join_records``."""
+    _fields_ = [("d_base", C.c_void_p), ("d_record_off", C.c_void_p), ("d_flip", C.c_void_p), ("sample_count", C.c_uint32),
+                ("reserved", C.c_uint32)]
 
 
 u8p = C.POINTER(C.c_uint8)
@@ -189,6 +201,7 @@ PROTOTYPES = {
     "pgenhip_pack_records": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]),
     "pgenhip_pack_records_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]),
     "pgenhip_parse_gt": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]),
+    "pgenhip_join_records": (C.c_int, [ctx_p, C.POINTER(JoinPart), C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32]),
     "pgenhip_vcf_index_lines": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u64p, u64p]),
     "pgenhip_tune": (C.c_int, [ctx_p, C.c_uint32, C.c_int32]),
     "pgenhip_wait": (C.c_int, [ctx_p]),

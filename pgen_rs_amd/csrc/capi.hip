@@ -1068,6 +1068,55 @@ int pgenhip_parse_gt(pgenhip_ctx *ctx, const void *d_text, uint64_t text_len, co
     return PGENHIP_OK;
 }
 
+int pgenhip_join_records(pgenhip_ctx *ctx, const pgenhip_join_part *parts, uint32_t n_parts, uint32_t n_variants, void *d_out,
+                         uint64_t out_stride, uint32_t flags)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (flags > PGENHIP_JOIN_STREAM) return fail(PGENHIP_ERR_BAD_ARG, "unknown join_records flag");
+    if (!parts) return fail(PGENHIP_ERR_BAD_ARG, "parts is NULL");
+    if (n_parts == 0u || n_parts > PGENHIP_JOIN_MAX_PARTS) return fail(PGENHIP_ERR_BAD_ARG, "n_parts must be 1 .. PGENHIP_JOIN_MAX_PARTS");
+    if (ctx->subset && !ctx->identity) return fail(PGENHIP_ERR_BAD_ARG, "join_records needs all samples kept (subsets are pack_records' job)");
+    uint64_t sum = 0u;
+    for (uint32_t p = 0; p < n_parts; p++) {
+        if (parts[p].reserved != 0u) return fail(PGENHIP_ERR_BAD_ARG, "a part's reserved field is not 0");
+        sum += parts[p].sample_count;
+    }
+    if (sum != ctx->sample_count) return fail(PGENHIP_ERR_BAD_ARG, "the parts' sample counts do not add up to the ctx's sample count");
+    if (n_variants == 0 || sum == 0u) return PGENHIP_OK;   // nothing to write
+    const uint32_t R = ctx->record_size;
+    JoinArgs a{};
+    for (uint32_t p = 0; p < n_parts; p++) {   // the table holds the parts that have samples
+        const pgenhip_join_part &s = parts[p];
+        if (s.sample_count == 0u) continue;
+        if (!s.d_base || !s.d_record_off) return fail(PGENHIP_ERR_BAD_ARG, "a part with samples has a NULL d_base or d_record_off");
+        if ((uintptr_t)s.d_record_off & 7u) return fail(PGENHIP_ERR_BAD_ARG, "a part's d_record_off is not 8-byte aligned");
+        JoinPart &t = a.part[a.n_parts];
+        t.base = static_cast<const uint8_t *>(s.d_base);
+        t.record_off = s.d_record_off;
+        t.flip = s.d_flip;
+        t.start = a.n_parts ? a.part[a.n_parts - 1u].start + a.part[a.n_parts - 1u].count : 0u;
+        t.count = s.sample_count;
+        a.n_parts++;
+    }
+    if (!d_out) return fail(PGENHIP_ERR_BAD_ARG, "d_out is NULL");
+    if (n_variants > 1 && out_stride < R) return fail(PGENHIP_ERR_BAD_ARG, "out_stride < one record");
+    // byte offsets are 64-bit arithmetic in the kernels; the bound is decode_matrix's (2^52 bytes)
+    if (n_variants > 1 && out_stride >= kMaxSpan / n_variants) return fail(PGENHIP_ERR_TOO_LARGE, "join offsets do not fit the kernels' index types");
+    a.n_variants = n_variants;
+    a.sample_count = ctx->sample_count;
+    a.record_size = R;
+    a.out = static_cast<uint8_t *>(d_out);
+    a.out_stride = out_stride;
+    const int blocks = ctx->tune.join_blocks;
+    if (flags == PGENHIP_JOIN_STREAM || (flags == PGENHIP_JOIN_AUTO && plan::join::auto_stream(R, n_variants, a.n_parts))) {
+        HIP_TRY(launch_gt_join_stream(a, blocks, ctx->num_cus, ctx->stream));
+    } else {
+        HIP_TRY(launch_gt_join_general(a, blocks, ctx->num_cus, ctx->stream));
+    }
+    return PGENHIP_OK;
+}
+
 int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)
 {
     if (!ctx) return fail(PGENHIP_ERR_BAD_ARG, "ctx is NULL");
@@ -1095,6 +1144,7 @@ int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)
         case PGENHIP_KNOB_PAIR_BLOCKS: t.pair_blocks = value > 0 ? value : d.pair_blocks; break;
         case PGENHIP_KNOB_PACK_BLOCKS: t.pack_blocks = value > 0 ? value : d.pack_blocks; break;
         case PGENHIP_KNOB_PARSE_BLOCKS: t.parse_blocks = value > 0 ? value : d.parse_blocks; break;
+        case PGENHIP_KNOB_JOIN_BLOCKS: t.join_blocks = value > 0 ? value : d.join_blocks; break;
         case PGENHIP_KNOB_SPAIR_SLICES: t.spair_slices = value > 0 ? value : d.spair_slices; break;
         case PGENHIP_KNOB_VSUM_BLOCKS: t.vsum_blocks = value > 0 ? value : d.vsum_blocks; break;
         case PGENHIP_KNOB_GRAM_SLICES: t.gram_slices = value > 0 ? value : d.gram_slices; break;

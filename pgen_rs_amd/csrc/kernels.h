@@ -60,6 +60,7 @@ struct Tuning {
     int pair_blocks = 0;           // pairwise kernel: grid size in blocks (0 = by shape, capped per CU)
     int pack_blocks = 0;           // pack kernels: grid size in blocks (0 = by shape, capped per CU)
     int parse_blocks = 0;          // GT text parse kernels: grid size in blocks (0 = by shape, capped per CU)
+    int join_blocks = 0;           // join kernels: grid size in blocks (0 = by shape, capped per CU)
     int spair_slices = 0;          // pairwise sample tables: row ranges per sample tile (0 = by shape: the chip's resident blocks, at least 256 rows each)
     int vsum_blocks = 0;           // per-variant sums: grid size in blocks (0 = by shape, capped per CU)
     int gram_slices = 0;           // sample Gram matrix: row ranges per rank tile (0 = by shape: the chip's resident blocks, at least 256 rows each)
@@ -297,6 +298,27 @@ hipError_t launch_gt_parse_general(const ParseArgs &a, bool declined_only, int b
 // before the launch); write: stores the record bytes — with validate, of every 4N-byte line (AUTO: GENERAL rewrites the declined
 // ones), without, of the lines a validate launch before it did not decline (forced FIXED).
 hipError_t launch_gt_parse_fixed(const ParseArgs &a, bool validate, bool write, int blocks, int num_cus, hipStream_t stream);
+
+// Sample-wise join (gt_join.hip): row j = the mode-0x02 record of N = sum count samples at out + j * out_stride, part p's samples at
+// start .. start + count - 1, pad bits zero.  The table holds the parts that have samples, in order, their ranges tiling [0, N).
+struct JoinPart {
+    const uint8_t *base;          // device, any alignment
+    const uint64_t *record_off;   // device: byte offset of row j's record from base, or PGENHIP_JOIN_ABSENT (code 3, nothing read)
+    const uint8_t *flip;          // device or nullptr: flip[j] != 0 exchanges codes 0 and 2
+    uint32_t start, count;        // first output sample, samples (count >= 1)
+};
+struct JoinArgs {
+    JoinPart part[PGENHIP_JOIN_MAX_PARTS];
+    uint32_t n_parts;
+    uint32_t n_variants;
+    uint32_t sample_count;        // N
+    uint32_t record_size;         // R = ceil(N/4)
+    uint8_t *out;                 // device, any alignment
+    uint64_t out_stride;
+};
+// blocks: forced grid size (0 = by shape; tests force small grids to walk the grid-stride loops)
+hipError_t launch_gt_join_general(const JoinArgs &a, int blocks, int num_cus, hipStream_t stream);
+hipError_t launch_gt_join_stream(const JoinArgs &a, int blocks, int num_cus, hipStream_t stream);
 
 // Deterministic synthetic records (SURVEY.md §8d counter-based generator).
 hipError_t launch_synth_records(uint8_t *dst, uint64_t record_stride, uint32_t sample_count,

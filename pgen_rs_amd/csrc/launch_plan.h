@@ -1,11 +1,11 @@
 // launch_plan.h — the launch plans of the analysis kernels (gt_count, gt_scount, gt_score, gt_vsum, gt_matrix, gt_pair, gt_pack,
-// gt_spair, gt_gram, gt_gapply, gt_parse) and the launch rule of the stream kernel (gt_wide): lanes per row, tiles, row ranges ("slices"), grid
+// gt_spair, gt_gram, gt_gapply, gt_parse, gt_join) and the launch rule of the stream kernel (gt_wide): lanes per row, tiles, row ranges ("slices"), grid
 // caps, store policy and write fronts, as functions of scalars; and the emit path (namespace emit): the shapes each emit kernel takes,
 // AUTO's chains and the forced kernel ids, the chunks of the two passes, and the launch plans of the segment, row-owner and pick
 // kernels.  The single statement
 // of every plan: capi.hip and the launchers call it, the kernels take their constants and their row ranges from it, and the tests compile this
 // header for the host (tests/plan_probe.cpp, tests/gapply_plan_probe.cpp, tests/wide_plan_probe.cpp, tests/emit_plan_probe.cpp,
-// tests/parse_plan_probe.cpp) and run it.
+// tests/parse_plan_probe.cpp, tests/join_plan_probe.cpp) and run it.
 // Plain C++17 on purpose: no HIP header, no kernel argument struct (emit::Shape is a struct of scalars).
 #pragma once
 #include <stdint.h>
@@ -1119,5 +1119,54 @@ PGENHIP_PLAN_HD constexpr uint64_t general_chunks(uint64_t bytes, uint32_t lead)
 constexpr bool kAutoFixedFirst = true;
 
 }  // namespace parse
+
+// ---- gt_join: sample-wise join of records ----------------------------------------------------------------------------------------
+namespace join {
+
+constexpr int kThreads = 256;
+constexpr uint32_t kBlocksPerCu = 8;     // grid cap of both grid-stride kernels
+constexpr uint32_t kChunkBytes = 16u;    // STREAM: a lane's piece of an output row, aligned in memory (64 samples)
+
+// GENERAL: a lane per output byte
+PGENHIP_PLAN_HD inline uint32_t general_grid(uint32_t n_variants, uint32_t record_size, int num_cus, int blocks)
+{
+    return grid_blocks(((uint64_t)n_variants * record_size + kThreads - 1u) / kThreads, kBlocksPerCu, num_cus, blocks);
+}
+
+// STREAM: the most aligned chunks a row of R bytes can touch, whatever its address (R = 1 at byte 15 of a chunk: one)
+PGENHIP_PLAN_HD constexpr uint32_t chunks_per_row(uint32_t record_size) { return (record_size + 2u * kChunkBytes - 2u) / kChunkBytes; }
+// row bytes [begin, end) under chunk c of a row whose first byte lies `mis` bytes (0 .. 15) behind a chunk boundary: the chunks
+// tile [0, R) in order; the last one is empty when the row's address leaves it nothing
+PGENHIP_PLAN_HD inline RowRange chunk_bytes(uint32_t record_size, uint32_t mis, uint32_t chunk)
+{
+    const int64_t b0 = (int64_t)kChunkBytes * chunk - mis;
+    const int64_t lo = std::min<int64_t>(std::max<int64_t>(b0, 0), record_size), hi = std::max<int64_t>(lo, std::min<int64_t>(b0 + kChunkBytes, record_size));
+    return {(uint64_t)lo, (uint64_t)hi};
+}
+// The launch is flat over (row, chunk): item i is chunk i % C of row i / C, kThreads consecutive items per block and turn, so a
+// block holds kThreads / C rows of short records and a long row spreads over ceil(C / kThreads) blocks.
+PGENHIP_PLAN_HD constexpr uint32_t rows_per_block(uint32_t record_size) { return std::max<uint32_t>(1u, (uint32_t)kThreads / chunks_per_row(record_size)); }
+PGENHIP_PLAN_HD constexpr uint32_t blocks_per_row(uint32_t record_size) { return (chunks_per_row(record_size) + kThreads - 1u) / kThreads; }
+
+struct StreamPlan {
+    uint32_t chunks;   // per row
+    uint64_t total;    // items of the launch
+    uint32_t grid;
+};
+// blocks: forced grid size (0 = by shape)
+PGENHIP_PLAN_HD inline StreamPlan stream_plan(uint32_t record_size, uint32_t n_variants, int num_cus, int blocks)
+{
+    StreamPlan p{};
+    p.chunks = chunks_per_row(record_size);
+    p.total = (uint64_t)n_variants * p.chunks;
+    p.grid = grid_blocks((p.total + kThreads - 1u) / kThreads, kBlocksPerCu, num_cus, blocks);
+    return p;
+}
+
+// AUTO: STREAM on every shape.  It measured ahead of GENERAL in every case run (two and eight parts, flipped or not: chr22 1.9-3.0 x,
+// basic2 2.3-3.8 x, a block of configs[2] 20-24 x: profiles/r15_join/join_bench.jsonl), so the rule has no edge.
+PGENHIP_PLAN_HD constexpr bool auto_stream(uint32_t /*record_size*/, uint32_t /*n_variants*/, uint32_t /*n_parts*/) { return true; }
+
+}  // namespace join
 
 }  // namespace pgenhip::plan

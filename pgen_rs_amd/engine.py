@@ -645,6 +645,46 @@ class GtEngine:
     def _pack_view(self, out: torch.Tensor, n_variants: int, stride: int, out_offset: int) -> torch.Tensor:
         return torch.as_strided(out, (n_variants, self.packed_record_size), (stride, 1), out_offset)
 
+    # -- sample-wise join of records --------------------------------------------------------------
+    def join_records(self, parts, n_variants: Optional[int] = None, *, out: Optional[torch.Tensor] = None,
+                     out_stride: Optional[int] = None, out_offset: int = 0, shape: int = _capi.JOIN_AUTO) -> torch.Tensor:
+        """Several filesets' samples side by side: a ``(n_variants, R)`` uint8 view whose row j is the mode-0x02 record of the
+        context's N samples, the samples of part 0 first, then part 1, and so on; pad bits zero.
+
+        ``parts``: a sequence of ``(base, record_off, sample_count, flip_or_None)``, at most ``_capi.JOIN_MAX_PARTS`` of them, whose
+        sample counts add up to N.  ``base``: a uint8 CUDA tensor; ``record_off``: an int64 CUDA tensor of ``n_variants`` byte offsets
+        into it, ``-1`` where the part has no record for the row (its samples get code 3); ``flip``: a uint8 CUDA tensor of
+        ``n_variants`` bytes, nonzero where the part's codes 0 and 2 are exchanged.  A part of 0 samples adds nothing.
+        ``n_variants`` defaults to the shortest ``record_off``.  ``out``: a flat uint8 CUDA tensor; row j goes to byte
+        ``out_offset + j*out_stride`` (default stride R) and nothing else is touched.  The context must keep all samples."""
+        parts = list(parts)
+        if n_variants is None:
+            n_variants = min((p[1].numel() for p in parts), default=0)
+        table = (_capi.JoinPart * max(len(parts), 1))()
+        for i, (base, record_off, count, flip) in enumerate(parts):
+            self._rows_at(base, record_off, n_variants)
+            if base.dtype != torch.uint8:
+                raise ValueError("base must be a uint8 tensor")
+            if flip is not None:
+                self._check_dev(flip, "flip")
+                if flip.dtype != torch.uint8 or flip.numel() < n_variants:
+                    raise ValueError("flip must be a uint8 tensor of n_variants entries")
+            table[i] = _capi.JoinPart(_ptr(base), _ptr(record_off), _ptr(flip), int(count), 0)
+        r = self.record_size
+        if out_stride is None:
+            out_stride = r
+        if out is None:
+            out = torch.empty(out_offset + max(n_variants * out_stride, r, 1), dtype=torch.uint8, device=self.torch_device)
+        self._check_dev(out, "out")
+        if out.dtype != torch.uint8:
+            raise ValueError("out must be a uint8 tensor")
+        if n_variants and out.numel() < out_offset + (n_variants - 1) * out_stride + r:
+            raise ValueError("out too small")
+        out = out.view(-1)
+        check(lib.pgenhip_join_records(self._ctx, table, len(parts), n_variants, _ptr(out, out_offset), out_stride, shape),
+              "pgenhip_join_records")
+        return torch.as_strided(out, (n_variants, r), (out_stride, 1), out_offset)
+
     # -- GT text to records ---------------------------------------------------------------------
     def parse_gt(self, text: torch.Tensor, field_off: torch.Tensor, line_end: torch.Tensor, *, out: Optional[torch.Tensor] = None,
                  out_stride: Optional[int] = None, out_offset: int = 0, shape: int = _capi.PARSE_AUTO, text_offset: int = 0,

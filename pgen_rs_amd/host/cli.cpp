@@ -26,6 +26,9 @@
 // `pgen-hip pca <PFILE_PREFIX> [--include-var <EXPR>] [--include-sam <EXPR>] [--pcs <P>] [--tol <X>] [--max-passes <I>] [--seed <S>]
 // -o|--out <OUT_PREFIX>` (not in the reference): the leading principal components of the kept samples by randomised subspace iteration,
 // every pass one matrix-free Gram product (pgenhip_gram_apply) over the kept variants; the K x K matrix is never formed.
+// `pgen-hip merge <PFILE_PREFIX> <PFILE_PREFIX> [...] -o|--out <OUT_PREFIX> [--union]` (not in the reference): two to eight filesets'
+// samples side by side in one fileset, variants matched by (CHROM, POS, {REF, ALT}) with REF/ALT swaps flipped; the records are
+// joined on the GPU (pgenhip_join_records).
 // Additions (opt-in, not in the reference): --gpus <N>, --block-mib <M>, --launch-mib <M>, --filter-threads <T>, --stats, --dry-run
 // (filter: write the VCF header only and report the body geometry; needs no GPU); BGZF output (`-o x.vcf.gz` or --bgzf,
 // --bgzf-level <1-9>, --compress-threads <T>) and `pgen-hip bgzf <IN> <OUT>`, the same writer on a file.
@@ -47,7 +50,9 @@
 
 #include "bgzf.h"
 #include "expr.h"
+#include "merge.h"
 #include "pfile.h"
+#include "../../include/pgen_hip.h"
 #include "stats.h"
 
 using namespace pgenhost;
@@ -160,6 +165,14 @@ const char *kUsage =
     "       output file.  A gzip or BGZF input is inflated by one sequential zlib stream over its members (parallel inflate of BGZF members is\n"
     "       not built); one device is used whatever --gpus says: the reader, not the parse kernel, bounds this command.  Compressed .pgen\n"
     "       records and BCF are not read\n"
+    "merge  <PFILE_PREFIX> <PFILE_PREFIX> [<PFILE_PREFIX> ...] -o, --out <OUT_PREFIX> [--union] [--block-mib <M>] [--read-threads <T>] [--stats] [--dry-run]\n"
+    "       two to eight filesets' samples side by side (more: merge in stages) as OUT_PREFIX.pgen (fixed-width, storage mode 0x02), .pvar\n"
+    "       and .psam: the inputs' samples in argument order (column lines byte-identical, no IID twice).  A variant is (CHROM, POS, {REF,\n"
+    "       ALT}), strings compared verbatim; an input that has REF and ALT exchanged against the first input that holds the variant is\n"
+    "       flipped (0/0 <-> 1/1), and that first input's .pvar row is written (a differing ID in a later input is counted, not an error).\n"
+    "       Default: the variants every input holds, in the first input's order; --union: every variant, sorted by (CHROM by first\n"
+    "       appearance, POS, first seen), an input that lacks one is ./. there.  Strand flips (A/G against T/C) are not detected; differing\n"
+    "       columns are not harmonised; one device is used.  --dry-run matches and prints the counts as one JSON line, without a device or a file\n"
     "kinship <PFILE_PREFIX> [--include-var <VAR_QUERY>] [--include-sam <SAM_QUERY>] [--min-kinship <X>] [--counts] [-o, --out <OUT_FILE>]\n"
     "       [--gpus <N>] [--shards <S>] [--block-mib <M>] [--block-rows <B>] [--sample-tile <T>] [--read-threads <T>] [--filter-threads <T>] [--stats]\n"
     "       one line per pair of kept samples in psam order: IID1 IID2 N HETHET IBS0 HET1 HET2 KINSHIP over the kept variants called in\n"
@@ -584,6 +597,27 @@ int main(int argc, char **argv)
                              (unsigned long long)st.import_half_call, (unsigned long long)st.import_haploid, (unsigned long long)st.import_phased,
                              (unsigned long long)st.file_bytes, st.seconds_filter, st.seconds_body, st.seconds_setup, st.seconds_kernel,
                              std::chrono::duration<double>(std::chrono::steady_clock::now() - t_main).count());
+            return 0;
+        }
+        if (cmd == "merge") {
+            Args a = parse(argc, argv, 2, {{"out", 'o'}, {"block-mib", 0}, {"read-threads", 0}}, {{"union", 0}, {"stats", 0}, {"dry-run", 0}});
+            if (a.positional.size() < 2) usage_error("merge takes at least two <PFILE_PREFIX> arguments");
+            if (a.positional.size() > PGENHIP_JOIN_MAX_PARTS) usage_error("merge takes at most eight <PFILE_PREFIX> arguments: merge in stages");
+            if (!a.has("out") || a.get("out")->empty()) usage_error("the following required arguments were not provided: --out <OUT_PREFIX>");
+            MergeOptions mo;
+            mo.with_union = a.has("union");
+            mo.dry_run = a.has("dry-run");
+            OutputOptions opt;
+            if (auto m = a.get("block-mib")) opt.block_text_bytes = unsigned_value(*m, "block-mib", "M", 1, 65536, "a number of MiB from 1 to 65536") << 20;
+            if (auto t = a.get("read-threads")) opt.read_threads = (int)unsigned_value(*t, "read-threads", "T", 1, 256, "a number of threads from 1 to 256");
+            const MergeStats st = merge_pfiles(a.positional, *a.get("out"), mo, opt);
+            if (mo.dry_run) {
+                std::printf("{%s}\n", st.json_counts().c_str());
+            } else if (a.has("stats")) {
+                std::fprintf(stderr, "{%s, \"file_bytes\": %llu, \"seconds_filter\": %.6f, \"seconds_body\": %.6f, \"seconds_setup\": %.6f, \"seconds_kernel\": %.6f, \"seconds_main\": %.6f}\n",
+                             st.json_counts().c_str(), (unsigned long long)st.file_bytes, st.seconds_filter, st.seconds_body, st.seconds_setup, st.seconds_kernel,
+                             std::chrono::duration<double>(std::chrono::steady_clock::now() - t_main).count());
+            }
             return 0;
         }
         if (cmd == "ld") {
