@@ -412,6 +412,57 @@ int pgenhip_pair_stats(pgenhip_ctx *ctx, const void *d_records, uint64_t record_
 int pgenhip_pair_stats_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
                           uint32_t n_left, uint32_t window, void *d_out, uint32_t flags);
 
+/* ---- LD pruning: one bit per pair, and the greedy independent set of the graph they form (device-resident, asynchronous) ----
+ * pgenhip_pair_mask: rows, pairs, n_left, window = W and the kept samples are exactly those of pgenhip_pair_stats / _at; the pair
+ * (i, j = i + d) exists for i < n_left, 1 <= d <= W, j < n_variants.  An existing pair is an EDGE iff
+ *   - the f32 value PGENHIP_PAIR_R2 defines for it compares > min_r2 (the same formula: exact u64 terms, doubles, one rounding;
+ *     NaN is never an edge), and
+ *   - d_key == NULL, or (d_key[j] - d_key[i]) mod 2^64 <= max_span.  d_key is a DEVICE array of u64 indexed by the row's position in
+ *     the selection; the library does not interpret it.  A host passes (chromosome rank << 32) | POS: a pair across chromosomes, or
+ *     out of order, is then never an edge, and with POS left 0 and max_span = 0 a window in variants still stops at chromosome ends.
+ * With b = d - 1, an edge sets bit b & 31 of d_fwd[i * mask_stride + b / 32] and, when d_bwd != NULL, the same bit of
+ * d_bwd[j * mask_stride + b / 32].  mask_stride is in u32 words, >= ceil(W / 32).  The call only ever SETS bits (integer OR, so any
+ * order gives the same words), clears nothing, and writes nothing outside the words that hold an edge's bit: row padding and the
+ * words of rows without an edge are untouched.  The caller zeroes the masks once and calls per block with d_fwd / d_bwd advanced by
+ * block_row0 * mask_stride, so the halo rows of a block land on the next block's rows of d_bwd.  flags must be 0.
+ *   - PGENHIP_ERR_BAD_ARG: window == 0, n_left > n_variants, min_r2 NaN, d_key not 8-byte aligned, unknown flags, and — when a pair
+ *     exists — d_fwd NULL, a mask not 4-byte aligned, mask_stride < ceil(W / 32) when more than one mask row is addressed.
+ *   - PGENHIP_ERR_TOO_LARGE before any launch when n_variants * mask_stride * 4 >= 2^52.
+ * Launch contract as for pgenhip_pair_stats: device pointers only, no allocation, no synchronisation, one kernel on the ctx stream,
+ * graph-capturable, masks in ordinary device memory; PGENHIP_KNOB_PAIR_BLOCKS forces its grid too.
+ *
+ * pgenhip_prune_resolve: the neighbours of row v are v + d for the bits d - 1 set in d_fwd's row v and v - d for the bits set in
+ * d_bwd's row v (rows of mask_stride words each); only 1 <= d <= window and neighbours in [0, n_rows) count, bits that point outside
+ * are ignored, never followed.  Row u BEATS v iff d_priority[u] > d_priority[v], or the two are equal and u < v (d_priority == NULL:
+ * the lower index wins).  The answer S: take the rows in beating order; a row whose d_state byte the caller pre-set to KEPT or REMOVED
+ * has that state; any other row is KEPT iff none of its neighbours that beat it is KEPT, else REMOVED.  S is unique.  One call
+ *   (a) never changes a non-zero state and never writes a state that differs from S;
+ *   (b) decides at least one row if any is undecided when it starts (a host loop ends after at most n_rows calls);
+ *   (c) overwrites *d_undecided (DEVICE u64) with the exact number of rows still undecided when it ends.
+ * The host loops call -> D2H of the counter -> repeat until the counter is 0.  n_rows == 0 writes 0 to the counter and nothing else
+ * (a NULL d_undecided is accepted then, and nothing at all is written).
+ * State bytes other than 0, 1, 2 give an unspecified result without any out-of-bounds access; so does a d_bwd that is not the
+ * transpose of d_fwd (some consistent-looking result).  flags: a shape; every shape takes every legal call and ends at the same S.
+ *   - PGENHIP_ERR_BAD_ARG: window == 0; with n_rows > 0 a NULL d_fwd / d_bwd / d_state / d_undecided; masks or d_priority not 4-byte
+ *     aligned, d_undecided not 8-byte aligned; mask_stride < ceil(window / 32) with n_rows > 1; unknown flags or shapes.
+ *   - PGENHIP_ERR_TOO_LARGE: n_rows * mask_stride * 4 >= 2^52.
+ * Device pointers only, no allocation, no synchronisation; one 8-byte memset and one kernel on the ctx stream; graph-capturable. */
+int pgenhip_pair_mask(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                      uint32_t n_variants, uint32_t n_left, uint32_t window, float min_r2, const uint64_t *d_key, uint64_t max_span,
+                      uint32_t *d_fwd, uint32_t *d_bwd, uint64_t mask_stride, uint32_t flags);
+/* Same, with the record of row j at d_base + d_record_off[j] (DEVICE array of u64 byte offsets). */
+int pgenhip_pair_mask_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants, uint32_t n_left,
+                         uint32_t window, float min_r2, const uint64_t *d_key, uint64_t max_span, uint32_t *d_fwd, uint32_t *d_bwd,
+                         uint64_t mask_stride, uint32_t flags);
+#define PGENHIP_PRUNE_UNDECIDED 0u
+#define PGENHIP_PRUNE_KEPT 1u
+#define PGENHIP_PRUNE_REMOVED 2u
+#define PGENHIP_PRUNE_AUTO 0u
+#define PGENHIP_PRUNE_GENERAL 1u   /* a lane per row, one sweep per call: the correctness baseline */
+#define PGENHIP_PRUNE_BLOCK 2u     /* a workgroup per range of rows, swept to a local fixed point in LDS */
+int pgenhip_prune_resolve(pgenhip_ctx *ctx, const uint32_t *d_fwd, const uint32_t *d_bwd, uint64_t mask_stride, uint32_t window,
+                          uint64_t n_rows, const uint32_t *d_priority, uint8_t *d_state, uint64_t *d_undecided, uint32_t flags);
+
 /* ---- pairwise sample tables (device-resident, asynchronous on the ctx stream) ----
  * The transpose of pgenhip_pair_stats: pairs of kept SAMPLES, summed over the selected rows.  Rows are selected exactly as in
  * pgenhip_sample_counts / pgenhip_sample_counts_at (by stride with record_stride >= R or n_variants <= 1, through d_variant_idx, or
@@ -718,6 +769,7 @@ typedef enum pgenhip_knob {
     PGENHIP_KNOB_WIDE_BURST = 28,        /* stream kernel (GT segments and full lines of long rows): plain store steps issued back to back, 1 or 2; default 0 = by shape (1 on launches of 9 GB of text and more in rows of more than 16 KiB, else 2) */
     PGENHIP_KNOB_PARSE_BLOCKS = 29,      /* GT text parse kernels: grid size in blocks (default 0 = by shape: the work, capped at 8 blocks per CU); tests force small grids */
     PGENHIP_KNOB_JOIN_BLOCKS = 30,       /* join kernels: grid size in blocks (default 0 = by shape: the work, capped at 8 blocks per CU); tests force small grids */
+    PGENHIP_KNOB_PRUNE_BLOCKS = 31,      /* prune resolve kernels: grid size in blocks (default 0 = by shape); for the BLOCK shape thereby the rows of a workgroup's range; tests force small grids */
     PGENHIP_KNOB_RUNS_ROWS = 7       /* RUNS kernel: rows per work item (default: as many as one wide load / one span holds) */
 } pgenhip_knob;
 int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value);
@@ -741,6 +793,9 @@ int pgenhip_host_free_pinned(pgenhip_ctx *ctx, void *h_ptr);
 /* asynchronous on the ctx stream (truly async only from/to pinned host memory) */
 int pgenhip_memcpy_h2d(pgenhip_ctx *ctx, void *d_dst, const void *h_src, size_t bytes);
 int pgenhip_memcpy_d2h(pgenhip_ctx *ctx, void *h_dst, const void *d_src, size_t bytes);
+/* bytes of the ctx's device that are free right now, and that it has (either pointer may be NULL, not both): what a host sizes
+ * buffers that stay resident by, before it allocates them */
+int pgenhip_device_memory(pgenhip_ctx *ctx, uint64_t *free_bytes, uint64_t *total_bytes);
 
 /* ---- synthetic records generated on the device --------- */
 #define PGENHIP_SYNTH_DIRTY_PAD 1u

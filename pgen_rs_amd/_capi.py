@@ -103,6 +103,12 @@ JOIN_ABSENT = 0xFFFFFFFFFFFFFFFF
 VCF_LAST_BLOCK = 1
 PAIR_TABLE = 0
 PAIR_R2 = 1
+PRUNE_UNDECIDED = 0
+PRUNE_KEPT = 1
+PRUNE_REMOVED = 2
+PRUNE_AUTO = 0
+PRUNE_GENERAL = 1
+PRUNE_BLOCK = 2
 SYNTH_DIRTY_PAD = 1
 SYNTH_HWE = 2
 CREATE_KEEP_LIST = 1
@@ -134,6 +140,7 @@ KNOB_GAPPLY_ROW_SLICES = 27
 KNOB_WIDE_BURST = 28
 KNOB_PARSE_BLOCKS = 29
 KNOB_JOIN_BLOCKS = 30
+KNOB_PRUNE_BLOCKS = 31
 
 
 
@@ -197,6 +204,9 @@ PROTOTYPES = {
     "pgenhip_gram_apply_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]),
     "pgenhip_pair_stats": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_pair_stats_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
+    "pgenhip_pair_mask": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]),
+    "pgenhip_pair_mask_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]),
+    "pgenhip_prune_resolve": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "pgenhip_packed_record_size": (C.c_uint32, [ctx_p]),
     "pgenhip_pack_records": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]),
     "pgenhip_pack_records_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]),
@@ -215,6 +225,7 @@ PROTOTYPES = {
     "pgenhip_host_free_pinned": (C.c_int, [ctx_p, C.c_void_p]),
     "pgenhip_memcpy_h2d": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "pgenhip_memcpy_d2h": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "pgenhip_device_memory": (C.c_int, [ctx_p, u64p, u64p]),
     "pgenhip_synth_records": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32]),
 }
 

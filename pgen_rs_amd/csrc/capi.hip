@@ -764,6 +764,96 @@ int pgenhip_pair_stats_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *
     return pair_stats_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, n_left, window, d_out, flags);
 }
 
+static int pair_mask_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                          const uint64_t *d_record_off, uint32_t n_variants, uint32_t n_left, uint32_t window, float min_r2,
+                          const uint64_t *d_key, uint64_t max_span, uint32_t *d_fwd, uint32_t *d_bwd, uint64_t mask_stride, uint32_t flags)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (flags != 0u) return fail(PGENHIP_ERR_BAD_ARG, "unknown pair_mask flag");
+    if (window == 0u) return fail(PGENHIP_ERR_BAD_ARG, "window is 0");
+    if (n_left > n_variants) return fail(PGENHIP_ERR_BAD_ARG, "n_left > n_variants");
+    if (min_r2 != min_r2) return fail(PGENHIP_ERR_BAD_ARG, "min_r2 is NaN");
+    if ((uintptr_t)d_key & 7u) return fail(PGENHIP_ERR_BAD_ARG, "d_key is not 8-byte aligned");
+    if (n_left == 0u || n_variants <= 1u) return PGENHIP_OK;   // no pair exists
+    if (!d_fwd) return fail(PGENHIP_ERR_BAD_ARG, "d_fwd is NULL");
+    if (((uintptr_t)d_fwd | (uintptr_t)d_bwd) & 3u) return fail(PGENHIP_ERR_BAD_ARG, "a mask is not 4-byte aligned");
+    // rows the masks address: the left rows of d_fwd, every row of d_bwd
+    if ((d_bwd ? n_variants : n_left) > 1u && mask_stride < plan::prune::mask_words(window))
+        return fail(PGENHIP_ERR_BAD_ARG, "mask_stride < ceil(window / 32)");
+    // a mask word's byte offset is 64-bit arithmetic in the kernel; the bound is the other kernels' (2^52 bytes)
+    if (mask_stride >= kMaxSpan / 4u / n_variants) return fail(PGENHIP_ERR_TOO_LARGE, "n_variants * mask_stride * 4 >= 2^52");
+    PairMaskArgs a;
+    rc = select_rows(ctx, a, d_records, record_stride, d_variant_idx, d_record_off, n_variants);
+    if (rc) return rc;
+    a.kept_count = ctx->kept_count;
+    a.kept_mask = ctx->d_count_mask;   // NULL with all samples kept or an identity list
+    a.n_left = n_left;
+    a.window = window;
+    a.out = nullptr;
+    a.r2 = 1u;
+    a.min_r2 = min_r2;
+    a.key = d_key;
+    a.max_span = max_span;
+    a.fwd = d_fwd;
+    a.bwd = d_bwd;
+    a.mask_stride = mask_stride;
+    HIP_TRY(launch_gt_pair_mask(a, ctx->tune.pair_blocks, ctx->num_cus, ctx->stream));
+    return PGENHIP_OK;
+}
+
+int pgenhip_pair_mask(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                      uint32_t n_variants, uint32_t n_left, uint32_t window, float min_r2, const uint64_t *d_key, uint64_t max_span,
+                      uint32_t *d_fwd, uint32_t *d_bwd, uint64_t mask_stride, uint32_t flags)
+{
+    return pair_mask_core(ctx, d_records, record_stride, d_variant_idx, nullptr, n_variants, n_left, window, min_r2, d_key, max_span, d_fwd,
+                          d_bwd, mask_stride, flags);
+}
+
+int pgenhip_pair_mask_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants, uint32_t n_left,
+                         uint32_t window, float min_r2, const uint64_t *d_key, uint64_t max_span, uint32_t *d_fwd, uint32_t *d_bwd,
+                         uint64_t mask_stride, uint32_t flags)
+{
+    if (const int rc = check_record_off(ctx, d_record_off, n_variants)) return rc;
+    return pair_mask_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, n_left, window, min_r2, d_key, max_span, d_fwd, d_bwd,
+                          mask_stride, flags);
+}
+
+int pgenhip_prune_resolve(pgenhip_ctx *ctx, const uint32_t *d_fwd, const uint32_t *d_bwd, uint64_t mask_stride, uint32_t window,
+                          uint64_t n_rows, const uint32_t *d_priority, uint8_t *d_state, uint64_t *d_undecided, uint32_t flags)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (flags > PGENHIP_PRUNE_BLOCK) return fail(PGENHIP_ERR_BAD_ARG, "prune_resolve supports shapes AUTO, GENERAL and BLOCK");
+    if (window == 0u) return fail(PGENHIP_ERR_BAD_ARG, "window is 0");
+    if (n_rows != 0u && (!d_fwd || !d_bwd || !d_state)) return fail(PGENHIP_ERR_BAD_ARG, "d_fwd, d_bwd or d_state is NULL");
+    if (n_rows != 0u && !d_undecided) return fail(PGENHIP_ERR_BAD_ARG, "d_undecided is NULL");
+    if (((uintptr_t)d_fwd | (uintptr_t)d_bwd) & 3u) return fail(PGENHIP_ERR_BAD_ARG, "a mask is not 4-byte aligned");
+    if ((uintptr_t)d_priority & 3u) return fail(PGENHIP_ERR_BAD_ARG, "d_priority is not 4-byte aligned");
+    if ((uintptr_t)d_undecided & 7u) return fail(PGENHIP_ERR_BAD_ARG, "d_undecided is not 8-byte aligned");
+    if (n_rows > 1u && mask_stride < plan::prune::mask_words(window)) return fail(PGENHIP_ERR_BAD_ARG, "mask_stride < ceil(window / 32)");
+    if (n_rows > 1u && (n_rows >= kMaxSpan / 4u || mask_stride >= kMaxSpan / 4u / n_rows))
+        return fail(PGENHIP_ERR_TOO_LARGE, "n_rows * mask_stride * 4 >= 2^52");
+    if (d_undecided) HIP_TRY(hipMemsetAsync(d_undecided, 0, sizeof(uint64_t), ctx->stream));   // the kernels add the rows they leave undecided
+    if (n_rows == 0u) return PGENHIP_OK;
+    PruneArgs a;
+    a.fwd = d_fwd;
+    a.bwd = d_bwd;
+    a.mask_stride = n_rows > 1u ? mask_stride : 0u;   // (one row: its words are at the masks' start whatever the stride)
+    a.window = (uint32_t)std::min<uint64_t>(window, n_rows - 1u);   // no farther neighbour is a row: its bit is never read
+    a.n_rows = n_rows;
+    a.priority = d_priority;
+    a.state = d_state;
+    a.undecided = reinterpret_cast<unsigned long long *>(d_undecided);
+    static_assert(PGENHIP_PRUNE_UNDECIDED == 0u && PGENHIP_PRUNE_KEPT == 1u && PGENHIP_PRUNE_REMOVED == 2u, "gt_prune.hip's state bytes");
+    const bool block = flags == PGENHIP_PRUNE_BLOCK || (flags == PGENHIP_PRUNE_AUTO && plan::prune::auto_block(n_rows, window));
+    if (block)
+        HIP_TRY(launch_gt_prune_block(a, ctx->tune.prune_blocks, ctx->num_cus, ctx->stream));
+    else
+        HIP_TRY(launch_gt_prune_general(a, ctx->tune.prune_blocks, ctx->num_cus, ctx->stream));
+    return PGENHIP_OK;
+}
+
 static int sample_pair_stats_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
                                   const uint64_t *d_record_off, uint32_t n_variants, uint32_t a_begin, uint32_t a_count,
                                   uint32_t b_begin, uint32_t b_count, uint32_t *d_out, uint32_t flags)
@@ -1145,6 +1235,7 @@ int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)
         case PGENHIP_KNOB_PACK_BLOCKS: t.pack_blocks = value > 0 ? value : d.pack_blocks; break;
         case PGENHIP_KNOB_PARSE_BLOCKS: t.parse_blocks = value > 0 ? value : d.parse_blocks; break;
         case PGENHIP_KNOB_JOIN_BLOCKS: t.join_blocks = value > 0 ? value : d.join_blocks; break;
+        case PGENHIP_KNOB_PRUNE_BLOCKS: t.prune_blocks = value > 0 ? value : d.prune_blocks; break;
         case PGENHIP_KNOB_SPAIR_SLICES: t.spair_slices = value > 0 ? value : d.spair_slices; break;
         case PGENHIP_KNOB_VSUM_BLOCKS: t.vsum_blocks = value > 0 ? value : d.vsum_blocks; break;
         case PGENHIP_KNOB_GRAM_SLICES: t.gram_slices = value > 0 ? value : d.gram_slices; break;
@@ -1258,6 +1349,18 @@ int pgenhip_memcpy_d2h(pgenhip_ctx *ctx, void *h_dst, const void *d_src, size_t 
     if (rc) return rc;
     if (bytes && (!h_dst || !d_src)) return fail(PGENHIP_ERR_BAD_ARG, "NULL pointer");
     if (bytes) HIP_TRY(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return PGENHIP_OK;
+}
+
+int pgenhip_device_memory(pgenhip_ctx *ctx, uint64_t *free_bytes, uint64_t *total_bytes)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!free_bytes && !total_bytes) return fail(PGENHIP_ERR_BAD_ARG, "free_bytes and total_bytes are both NULL");
+    size_t f = 0, t = 0;
+    HIP_TRY(hipMemGetInfo(&f, &t));
+    if (free_bytes) *free_bytes = f;
+    if (total_bytes) *total_bytes = t;
     return PGENHIP_OK;
 }
 

@@ -23,9 +23,16 @@
 // Tiles are numbered (left tile) * tiles_per_left + k, right tile = left tile + k, and the grid strides over the numbers; the few
 // numbers at the ragged end whose tile lies outside the band or past the last row leave at once without touching memory.  Every
 // pair has exactly one owner lane: no atomics, no counters, no scratch, nothing allocated, graph-capturable.
+//
+// The third epilogue (pgenhip_pair_mask) keeps one bit per pair instead: the pair's r^2 above a threshold and, with
+// keys, the rows' keys inside a span (which is how a window in base pairs is expressed).  A row's bits of one tile are neighbours
+// in one or two mask words; the lanes that hold them combine them with shuffles and one lane per row ORs them in with an atomic
+// (rows of a mask are shared between tiles), a tile without an edge writes nothing.
 // Not built: splitting one pair's samples over several blocks (few rows of very long records leave CUs idle), explicit pair
-// lists, windows in base pairs.
+// lists.
 #include <math.h>
+
+#include <type_traits>
 
 #include "gt_common.hip.h"
 #include "kernels.h"
@@ -74,8 +81,32 @@ __device__ __forceinline__ float table_r2(const uint32_t (&t)[4][4])
     return (float)((c * c) / ((double)vx * (double)vy));
 }
 
-__global__ __launch_bounds__(kThreads) void gt_pair_kernel(PairArgs a, uint64_t n_items, uint64_t tiles_per_left)
+// 16 edge bits of one row and tile, bit t = the partner at b0 + t (b0 >= -16; bits below mask bit 0 are clear by construction):
+// OR into the one or two mask words that hold a set bit, nothing else is touched
+__device__ __forceinline__ void or_mask_bits(uint32_t *row_words, int64_t b0, uint32_t bits16)
 {
+    if (bits16 == 0u) return;
+    uint64_t bits = bits16;
+    uint64_t bit0 = 0u;
+    if (b0 < 0) {
+        bits >>= (uint32_t)(-b0);
+    } else {
+        bit0 = (uint64_t)b0;
+        bits <<= (uint32_t)(bit0 & 31u);
+    }
+    uint32_t *w = row_words + (bit0 >> 5);
+    const uint32_t lo = (uint32_t)bits, hi = (uint32_t)(bits >> 32);
+    if (lo) atomicOr(w, lo);
+    if (hi) atomicOr(w + 1, hi);
+}
+
+// Args = PairArgs: tables or r^2 (a.r2), one owner lane per entry.  Args = PairMaskArgs: the same tile, staging and accumulation, and
+// an epilogue that keeps one bit per pair (the r^2 above a threshold, the keys inside a span): a row's 16 partner bits of the tile are
+// ORed together across the eight lanes that hold them (three shuffles), then one lane per row ORs them into the mask.
+template <class Args>
+__global__ __launch_bounds__(kThreads) void gt_pair_kernel(Args a, uint64_t n_items, uint64_t tiles_per_left)
+{
+    constexpr bool kMask = std::is_same<Args, PairMaskArgs>::value;
     __shared__ __attribute__((aligned(16))) uint32_t vec[kChunkWords * kWordStride];
     __shared__ uint32_t marg[kSlots * 3];
     const uint32_t lane = threadIdx.x;
@@ -195,12 +226,13 @@ __global__ __launch_bounds__(kThreads) void gt_pair_kernel(PairArgs a, uint64_t 
         __syncthreads();
 
         // ---- epilogue: 2 x 2 pairs per lane
+        [[maybe_unused]] uint32_t fwd_bits = 0u, bwd_bits = 0u;   // mask mode: this lane's edges, two 16-bit halves each
 #pragma unroll
         for (uint32_t x = 0; x < 2u; x++)
 #pragma unroll
             for (uint32_t y = 0; y < 2u; y++) {
                 const uint64_t i = i0 + 2u * ty + x, j = j0 + 2u * tx + y;
-                if (i >= a.n_left || j <= i || j - i > W || j >= V) continue;
+                if (i >= a.n_left || j <= i || j - i > W || j >= V) continue;   // (no lane leaves the wave: the mask epilogue shuffles below)
                 const uint32_t *mi = marg + (2u * ty + x) * 3u, *mj = marg + (rbase + 2u * tx + y) * 3u;
                 uint32_t t[4][4];
                 uint32_t rows_called = 0u, top = 0u;
@@ -221,28 +253,64 @@ __global__ __launch_bounds__(kThreads) void gt_pair_kernel(PairArgs a, uint64_t 
                     top += t[0][v];
                 }
                 t[0][0] = a.kept_count - rows_called - top;
-                const uint64_t p = i * W + (j - i - 1u);
-                if (a.r2) {
-                    static_cast<float *>(a.out)[p] = table_r2(t);
+                if constexpr (kMask) {
+                    // NaN compares false; the key difference is taken mod 2^64, so a partner with a smaller key is far away
+                    if (table_r2(t) > a.min_r2 && (a.key == nullptr || a.key[j] - a.key[i] <= a.max_span)) {
+                        fwd_bits |= 1u << (16u * x + 2u * tx + y);             // row i's partner at j0 + (2 tx + y)
+                        bwd_bits |= 1u << (16u * y + 15u - (2u * ty + x));     // row j's partner at i0 + 15 - (bit)
+                    }
                 } else {
-                    gt_v4u *dst = reinterpret_cast<gt_v4u *>(static_cast<uint32_t *>(a.out) + 16ull * p);
+                    const uint64_t p = i * W + (j - i - 1u);
+                    if (a.r2) {
+                        static_cast<float *>(a.out)[p] = table_r2(t);
+                    } else {
+                        gt_v4u *dst = reinterpret_cast<gt_v4u *>(static_cast<uint32_t *>(a.out) + 16ull * p);
 #pragma unroll
-                    for (uint32_t u = 0; u < 4u; u++) dst[u] = gt_v4u{t[u][0], t[u][1], t[u][2], t[u][3]};
+                        for (uint32_t u = 0; u < 4u; u++) dst[u] = gt_v4u{t[u][0], t[u][1], t[u][2], t[u][3]};
+                    }
                 }
             }
+        if constexpr (kMask) if (__ballot(fwd_bits != 0u) != 0ull) {   // (wave-uniform; most tiles of real data hold no edge at all)
+            // forward: the lanes tx = 0 .. 7 of one ty hold the 16 partners of rows i0 + 2 ty + {0, 1}; bit t of a half = j0 + t
+            fwd_bits |= __shfl_xor(fwd_bits, 1, 8);
+            fwd_bits |= __shfl_xor(fwd_bits, 2, 8);
+            fwd_bits |= __shfl_xor(fwd_bits, 4, 8);
+            // backward: the lanes ty = 0 .. 7 of one tx hold the 16 partners of rows j0 + 2 tx + {0, 1}; bit t of a half = i0 + 15 - t
+            bwd_bits |= __shfl_xor(bwd_bits, 8);
+            bwd_bits |= __shfl_xor(bwd_bits, 16);
+            bwd_bits |= __shfl_xor(bwd_bits, 32);
+            if (tx == 0u) {
+#pragma unroll
+                for (uint32_t x = 0; x < 2u; x++) {
+                    const uint64_t i = i0 + 2u * ty + x;   // bit b = j - i - 1 of row i: j = j0 + t
+                    or_mask_bits(a.fwd + i * a.mask_stride, (int64_t)(j0 - i) - 1, (fwd_bits >> (16u * x)) & 0xFFFFu);
+                }
+            }
+            if (ty == 0u && a.bwd != nullptr) {
+#pragma unroll
+                for (uint32_t y = 0; y < 2u; y++) {
+                    const uint64_t j = j0 + 2u * tx + y;   // bit b = j - i - 1 of row j: i = i0 + 15 - t
+                    or_mask_bits(a.bwd + j * a.mask_stride, (int64_t)(j - i0) - 16, (bwd_bits >> (16u * y)) & 0xFFFFu);
+                }
+            }
+        }
         __syncthreads();   // marg and vec are rewritten by the next item
     }
 }
 
 }  // namespace
 
-hipError_t launch_gt_pair(const PairArgs &a, int blocks, int num_cus, hipStream_t stream)
+template <class Args>
+static hipError_t launch(const Args &a, int blocks, int num_cus, hipStream_t stream)
 {
     const uint64_t V = a.n_variants;
     if (a.n_left == 0 || V <= 1) return hipSuccess;
     const plan::pair::Plan p = plan::pair::plan(a.n_variants, a.n_left, a.window, num_cus, blocks);
-    hipLaunchKernelGGL(gt_pair_kernel, dim3(p.grid), dim3(kThreads), 0, stream, a, p.n_items, p.tiles_per_left);
+    hipLaunchKernelGGL(gt_pair_kernel<Args>, dim3(p.grid), dim3(kThreads), 0, stream, a, p.n_items, p.tiles_per_left);
     return hipGetLastError();
 }
+
+hipError_t launch_gt_pair(const PairArgs &a, int blocks, int num_cus, hipStream_t stream) { return launch(a, blocks, num_cus, stream); }
+hipError_t launch_gt_pair_mask(const PairMaskArgs &a, int blocks, int num_cus, hipStream_t stream) { return launch(a, blocks, num_cus, stream); }
 
 }  // namespace pgenhip

@@ -61,6 +61,7 @@ struct Tuning {
     int pack_blocks = 0;           // pack kernels: grid size in blocks (0 = by shape, capped per CU)
     int parse_blocks = 0;          // GT text parse kernels: grid size in blocks (0 = by shape, capped per CU)
     int join_blocks = 0;           // join kernels: grid size in blocks (0 = by shape, capped per CU)
+    int prune_blocks = 0;          // prune resolve kernels: grid size in blocks (0 = by shape); for BLOCK thereby the rows of a range
     int spair_slices = 0;          // pairwise sample tables: row ranges per sample tile (0 = by shape: the chip's resident blocks, at least 256 rows each)
     int vsum_blocks = 0;           // per-variant sums: grid size in blocks (0 = by shape, capped per CU)
     int gram_slices = 0;           // sample Gram matrix: row ranges per rank tile (0 = by shape: the chip's resident blocks, at least 256 rows each)
@@ -212,6 +213,35 @@ struct PairArgs : RowSource {
 };
 // blocks: forced grid size (0 = by shape; tests force small grids to walk the grid-stride loop)
 hipError_t launch_gt_pair(const PairArgs &a, int blocks, int num_cus, hipStream_t stream);
+// One bit per pair instead (same kernel, third epilogue; out and r2 are not used): the pair is an edge iff its r^2 (PairArgs' r2
+// value) > min_r2 and key[j] - key[i] (mod 2^64) <= max_span; bit (d - 1) & 31 of fwd[i * mask_stride + (d - 1) / 32] and of
+// bwd[j * mask_stride + (d - 1) / 32] is then ORed in (atomics).  Nothing else is written.
+struct PairMaskArgs : PairArgs {
+    float min_r2;                 // not NaN
+    const uint64_t *key;          // device or nullptr (every pair is inside the span), one per selected row
+    uint64_t max_span;
+    uint32_t *fwd;                // device, 4-byte aligned
+    uint32_t *bwd;                // device or nullptr (forward mask only)
+    uint64_t mask_stride;         // u32 words per mask row, >= ceil(window / 32)
+};
+hipError_t launch_gt_pair_mask(const PairMaskArgs &a, int blocks, int num_cus, hipStream_t stream);
+
+// Greedy independent set of the graph two such masks hold (gt_prune.hip): state[v] 0 undecided, 1 kept, 2 removed.  Row u beats v
+// iff priority[u] > priority[v], or they are equal (or priority is nullptr) and u < v.  A sweep decides every undecided row whose
+// beating neighbours are all decided: kept iff none of them is kept.  States only go from 0 to their final value.
+struct PruneArgs {
+    const uint32_t *fwd, *bwd;    // device; bit d - 1 of row v: neighbour v + d / v - d
+    uint64_t mask_stride;         // u32 words per mask row
+    uint32_t window;              // bits d - 1 >= window are ignored
+    uint64_t n_rows;
+    const uint32_t *priority;     // device or nullptr
+    uint8_t *state;               // device
+    unsigned long long *undecided;   // device, zero at launch: every block adds the rows it leaves undecided
+};
+// blocks: forced grid size (0 = by shape).  GENERAL: a lane per row, one sweep.  BLOCK: a workgroup per contiguous range of rows
+// (plan::prune::block_plan), swept to a local fixed point in LDS.
+hipError_t launch_gt_prune_general(const PruneArgs &a, int blocks, int num_cus, hipStream_t stream);
+hipError_t launch_gt_prune_block(const PruneArgs &a, int blocks, int num_cus, hipStream_t stream);
 
 // Pairwise sample tables (gt_spair.hip): for a = a_begin + i, b = b_begin + l (ranks in the kept list) the number of selected rows
 // in which a has code x and b has code y, ADDED to out[16 * (i * b_count + l) + 4 * x + y] (u32, modular).

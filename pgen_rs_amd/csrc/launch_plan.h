@@ -1,11 +1,11 @@
 // launch_plan.h — the launch plans of the analysis kernels (gt_count, gt_scount, gt_score, gt_vsum, gt_matrix, gt_pair, gt_pack,
-// gt_spair, gt_gram, gt_gapply, gt_parse, gt_join) and the launch rule of the stream kernel (gt_wide): lanes per row, tiles, row ranges ("slices"), grid
+// gt_spair, gt_gram, gt_gapply, gt_parse, gt_join, gt_prune) and the launch rule of the stream kernel (gt_wide): lanes per row, tiles, row ranges ("slices"), grid
 // caps, store policy and write fronts, as functions of scalars; and the emit path (namespace emit): the shapes each emit kernel takes,
 // AUTO's chains and the forced kernel ids, the chunks of the two passes, and the launch plans of the segment, row-owner and pick
 // kernels.  The single statement
 // of every plan: capi.hip and the launchers call it, the kernels take their constants and their row ranges from it, and the tests compile this
 // header for the host (tests/plan_probe.cpp, tests/gapply_plan_probe.cpp, tests/wide_plan_probe.cpp, tests/emit_plan_probe.cpp,
-// tests/parse_plan_probe.cpp, tests/join_plan_probe.cpp) and run it.
+// tests/parse_plan_probe.cpp, tests/join_plan_probe.cpp, tests/prune_plan_probe.cpp) and run it.
 // Plain C++17 on purpose: no HIP header, no kernel argument struct (emit::Shape is a struct of scalars).
 #pragma once
 #include <stdint.h>
@@ -1168,5 +1168,48 @@ PGENHIP_PLAN_HD inline StreamPlan stream_plan(uint32_t record_size, uint32_t n_v
 PGENHIP_PLAN_HD constexpr bool auto_stream(uint32_t /*record_size*/, uint32_t /*n_variants*/, uint32_t /*n_parts*/) { return true; }
 
 }  // namespace join
+
+// ---- gt_prune: greedy independent set of a windowed pair mask --------------------------------------------------------------------
+namespace prune {
+
+constexpr int kThreads = 256;
+constexpr uint32_t kBlocksPerCu = 8;      // grid cap of both kernels
+constexpr uint32_t kChunkRows = 1024u;    // BLOCK: rows a workgroup sweeps to a fixed point at a time (one turn of its range)
+constexpr uint32_t kHaloRows = 512u;      // BLOCK: rows on either side of a turn whose states are in LDS too; farther neighbours are read from memory
+constexpr uint32_t kLdsRows = kChunkRows + 2u * kHaloRows;   // one state byte each
+
+// u32 words that hold a row's `window` bits
+PGENHIP_PLAN_HD constexpr uint64_t mask_words(uint32_t window) { return ((uint64_t)window + 31u) / 32u; }
+// BLOCK: the rows before / behind a turn that are staged (the whole window where it fits)
+PGENHIP_PLAN_HD constexpr uint32_t halo_rows(uint32_t window) { return window < kHaloRows ? window : kHaloRows; }
+
+// GENERAL: a lane per row, grid-stride
+PGENHIP_PLAN_HD inline uint32_t general_grid(uint64_t n_rows, int num_cus, int blocks)
+{
+    return grid_blocks((n_rows + kThreads - 1u) / kThreads, kBlocksPerCu, num_cus, blocks);
+}
+
+// BLOCK: block b owns rows [b * range_rows, min((b + 1) * range_rows, n_rows)) and walks them in turns of kChunkRows; no block is
+// empty.  blocks: forced grid size (0 = by shape: a turn per block, capped per CU); a forced grid larger than the rows shrinks to them.
+struct BlockPlan {
+    uint64_t range_rows;
+    uint32_t grid;
+};
+PGENHIP_PLAN_HD inline BlockPlan block_plan(uint64_t n_rows, int num_cus, int blocks)
+{
+    BlockPlan p{};
+    const uint64_t rows = std::max<uint64_t>(n_rows, 1u);
+    const uint64_t want = blocks > 0 ? std::min<uint64_t>((uint64_t)blocks, rows) : grid_blocks((rows + kChunkRows - 1u) / kChunkRows, kBlocksPerCu, num_cus, 0);
+    p.range_rows = (rows + want - 1u) / want;
+    p.grid = (uint32_t)((rows + p.range_rows - 1u) / p.range_rows);
+    return p;
+}
+
+// AUTO: BLOCK on every shape.  On masks of synthetic rows with LD (tools/prune_bench.py: about 7 edges per row, 4 096 to 1 048 576
+// rows, W = 32 and 128) it ended in 2-3 calls against GENERAL's 10-14 and in 0.60-0.72 x its time in every case run
+// (profiles/r16_prune/prune_bench_resolve.jsonl), so the rule has no edge.  Edge densities of real data are unmeasured.
+PGENHIP_PLAN_HD constexpr bool auto_block(uint64_t /*n_rows*/, uint32_t /*window*/) { return true; }
+
+}  // namespace prune
 
 }  // namespace pgenhip::plan

@@ -797,6 +797,104 @@ class GtEngine:
             raise ValueError(f"out must be a {dtype} tensor with >= {need} entries")
         return n_left, out.view(-1)
 
+    # -- LD pruning: one bit per pair, the greedy independent set -------------------------------------
+    def pair_mask(self, records: torch.Tensor, record_stride: Optional[int] = None, variant_idx: Optional[torch.Tensor] = None,
+                  n_variants: Optional[int] = None, *, n_left: Optional[int] = None, window: int, min_r2: float,
+                  key: Optional[torch.Tensor] = None, max_span: int = 0, fwd: Optional[torch.Tensor] = None,
+                  bwd: Optional[torch.Tensor] = None, want_bwd: bool = True, mask_stride: Optional[int] = None,
+                  records_offset: int = 0) -> tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """One bit per pair of ``pair_r2``'s pairs: ``(fwd, bwd)``, int32 ``(n_variants, mask_stride)`` CUDA tensors.  Pair
+        (i, j = i + d) is an edge iff its r^2 (``pair_r2``'s float32) is ``> min_r2`` and, with ``key`` (int64 CUDA tensor, one u64
+        per row), ``(key[j] - key[i]) mod 2^64 <= max_span``; bit ``(d - 1) % 32`` of word ``(d - 1) // 32`` of ``fwd``'s row i and
+        of ``bwd``'s row j is then set.  The call only ORs bits in: masks that are given (int32, ``mask_stride`` words per row,
+        default ``ceil(window / 32)``) keep what they hold, masks allocated here start as zeros.  ``want_bwd=False`` without
+        ``bwd`` leaves the backward mask out (``None``)."""
+        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
+        n_left, mask_stride, fwd, bwd, key_p = self._mask_out(n_variants, n_left, window, key, fwd, bwd, want_bwd, mask_stride)
+        check(lib.pgenhip_pair_mask(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants, n_left,
+                                    window, min_r2, key_p, max_span, _ptr(fwd), _ptr(bwd), mask_stride, 0), "pgenhip_pair_mask")
+        return fwd, bwd
+
+    def pair_mask_at(self, base: torch.Tensor, record_off: torch.Tensor, n_variants: Optional[int] = None, *,
+                     n_left: Optional[int] = None, window: int, min_r2: float, key: Optional[torch.Tensor] = None, max_span: int = 0,
+                     fwd: Optional[torch.Tensor] = None, bwd: Optional[torch.Tensor] = None, want_bwd: bool = True,
+                     mask_stride: Optional[int] = None) -> tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """``pair_mask`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
+        n_variants = self._rows_at(base, record_off, n_variants)
+        n_left, mask_stride, fwd, bwd, key_p = self._mask_out(n_variants, n_left, window, key, fwd, bwd, want_bwd, mask_stride)
+        check(lib.pgenhip_pair_mask_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, n_left, window, min_r2, key_p, max_span,
+                                       _ptr(fwd), _ptr(bwd), mask_stride, 0), "pgenhip_pair_mask_at")
+        return fwd, bwd
+
+    def _mask_out(self, n_variants: int, n_left: Optional[int], window: int, key, fwd, bwd, want_bwd: bool, mask_stride: Optional[int]):
+        """(n_left and mask_stride with their defaults, the masks: given, or zeros, and the key's pointer)"""
+        if n_left is None:
+            n_left = n_variants
+        if window < 1 or not 0 <= n_left <= n_variants:
+            raise ValueError("need window >= 1 and 0 <= n_left <= n_variants")
+        words = (window + 31) // 32
+        if mask_stride is None:
+            mask_stride = words
+        if mask_stride < words:
+            raise ValueError(f"mask_stride must be >= ceil(window / 32) = {words}")
+        if key is not None:
+            self._check_dev(key, "key")
+            if key.dtype != torch.int64 or key.numel() < n_variants:
+                raise ValueError("key must be an int64 tensor (u64 keys) with >= n_variants entries")
+        masks = []
+        for name, m, want in (("fwd", fwd, True), ("bwd", bwd, want_bwd)):
+            if m is None:
+                m = torch.zeros((n_variants, mask_stride), dtype=torch.int32, device=self.torch_device) if want else None
+            else:
+                self._check_dev(m, name)
+                if m.dtype != torch.int32 or m.numel() < n_variants * mask_stride:
+                    raise ValueError(f"{name} must be an int32 tensor with >= n_variants * mask_stride = {n_variants * mask_stride} entries")
+            masks.append(m)
+        return n_left, mask_stride, masks[0], masks[1], _ptr(key)
+
+    def prune_resolve(self, fwd: torch.Tensor, bwd: torch.Tensor, window: int, priority: Optional[torch.Tensor] = None,
+                      state: Optional[torch.Tensor] = None, shape: int = _capi.PRUNE_AUTO, max_calls: Optional[int] = None,
+                      *, n_rows: Optional[int] = None, mask_stride: Optional[int] = None, on_call=None) -> tuple[torch.Tensor, int]:
+        """The priority-greedy independent set of the graph two ``pair_mask`` masks hold: ``(state, calls)``, ``state`` a uint8
+        CUDA tensor of ``n_rows`` bytes (1 kept, 2 removed).  Row u beats v iff ``priority[u] > priority[v]`` (int32 tensor holding
+        u32 values; ``None``: all equal) or they are equal and u < v; a row is kept iff none of its neighbours that beat it is kept.
+        Rows whose byte in a given ``state`` is already 1 or 2 keep it.  Runs ``pgenhip_prune_resolve`` and reads its counter back
+        until no row is undecided; ``max_calls`` (default ``n_rows``) bounds the loop, and a loop that reaches it raises.
+        ``on_call(calls, undecided)`` is called after every call (tests watch the intermediate states through it)."""
+        for name, m in (("fwd", fwd), ("bwd", bwd)):
+            self._check_dev(m, name)
+            if m.dtype != torch.int32:
+                raise ValueError(f"{name} must be an int32 tensor")
+        if n_rows is None:
+            n_rows = fwd.shape[0] if fwd.dim() == 2 else (state.numel() if state is not None else 0)
+        if mask_stride is None:
+            mask_stride = fwd.shape[1] if fwd.dim() == 2 else (window + 31) // 32
+        if priority is not None:
+            self._check_dev(priority, "priority")
+            if priority.dtype not in (torch.int32, torch.uint32) or priority.numel() < n_rows:
+                raise ValueError("priority must be a 32-bit integer tensor with >= n_rows entries")
+        if state is None:
+            state = torch.zeros(max(n_rows, 1), dtype=torch.uint8, device=self.torch_device)[:n_rows]
+        else:
+            self._check_dev(state, "state")
+            if state.dtype != torch.uint8 or state.numel() < n_rows:
+                raise ValueError("state must be a uint8 tensor with >= n_rows entries")
+        counter = torch.zeros(1, dtype=torch.int64, device=self.torch_device)
+        limit = max(n_rows, 1) if max_calls is None else max_calls
+        calls = 0
+        while True:
+            check(lib.pgenhip_prune_resolve(self._ctx, _ptr(fwd), _ptr(bwd), mask_stride, window, n_rows, _ptr(priority), _ptr(state),
+                                            _ptr(counter), shape), "pgenhip_prune_resolve")
+            calls += 1
+            self.wait()                  # the ctx stream, whichever it is
+            left = int(counter.item())
+            if on_call is not None:
+                on_call(calls, left)
+            if left == 0:
+                return state, calls
+            if calls >= limit:
+                raise RuntimeError(f"prune_resolve: {left} rows undecided after {calls} calls")
+
     # -- pairwise sample tables ------------------------------------------------------------------
     def sample_pair_tables(self, records: torch.Tensor, record_stride: Optional[int] = None, variant_idx: Optional[torch.Tensor] = None,
                            n_variants: Optional[int] = None, *, a: Optional[tuple[int, int]] = None, b: Optional[tuple[int, int]] = None,

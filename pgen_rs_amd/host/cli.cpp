@@ -106,6 +106,7 @@ const char *kUsage =
     "  assoc   Linear regression of quantitative phenotypes on every kept variant, outputting to stdout\n"
     "  matrix  Numeric genotype matrix of the kept variants and samples, outputting to a NumPy .npy file\n"
     "  ld      Pairwise r^2 of the kept variants inside a sliding window, outputting to stdout\n"
+    "  prune   LD pruning of the kept variants: writes OUT.prune.in / OUT.prune.out, and with --export the pruned fileset\n"
     "  kinship Pairwise genotype tables and KING-robust kinship of the kept samples, outputting to stdout\n"
     "  grm     Genetic relationship matrix of the kept samples, outputting GCTA-style binary files or a text square\n"
     "  pca     Leading principal components of the kept samples, outputting .eigenval and .eigenvec files\n"
@@ -173,6 +174,18 @@ const char *kUsage =
     "       Default: the variants every input holds, in the first input's order; --union: every variant, sorted by (CHROM by first\n"
     "       appearance, POS, first seen), an input that lacks one is ./. there.  Strand flips (A/G against T/C) are not detected; differing\n"
     "       columns are not harmonised; one device is used.  --dry-run matches and prints the counts as one JSON line, without a device or a file\n"
+    "prune  <PFILE_PREFIX> (--window <W> | --window-kb <KB> [--window <W>]) --r2 <X> -o, --out <OUT_PREFIX> [--export]\n"
+    "       [--include-var <VAR_QUERY>] [--include-sam <SAM_QUERY>] [--block-mib <M>] [--block-rows <B>] [--read-threads <T>] [--filter-threads <T>] [--stats]\n"
+    "       OUT_PREFIX.prune.in: the IDs of the kept variants that stay, one per line in file order; OUT_PREFIX.prune.out: the removed ones'.\n"
+    "       Two kept variants on one chromosome, at most W variants apart (with --window-kb: at most KB x 1000 base pairs apart, and W\n"
+    "       is then the most variants such a span holds, capped by --window), are linked when their unphased genotype r^2 over the kept\n"
+    "       samples (ld's R2, as float32) is above X.  Variants are taken by minor-allele frequency among called alleles, the more common\n"
+    "       first, ties to the earlier one; each stays unless a linked variant before it in that order stayed.  So no two variants that\n"
+    "       stay inside a window have r^2 above X, and every removed variant has a kept, more common (or equally common, earlier) variant\n"
+    "       inside its window with r^2 above X.  A monomorphic or uncalled variant has no r^2, hence no link, and stays; MAF filters are\n"
+    "       not part of this.  --export also writes OUT_PREFIX.pgen / .pvar / .psam with the variants that stay and the kept samples, as\n"
+    "       `export` would.  One device is used; the result does not depend on --block-rows.  No parity with plink2 --indep-pairwise is\n"
+    "       claimed: its result depends on its window stepping.  Prints one JSON line: kept, removed, edges, window, resolve_calls, mask_bytes\n"
     "kinship <PFILE_PREFIX> [--include-var <VAR_QUERY>] [--include-sam <SAM_QUERY>] [--min-kinship <X>] [--counts] [-o, --out <OUT_FILE>]\n"
     "       [--gpus <N>] [--shards <S>] [--block-mib <M>] [--block-rows <B>] [--sample-tile <T>] [--read-threads <T>] [--filter-threads <T>] [--stats]\n"
     "       one line per pair of kept samples in psam order: IID1 IID2 N HETHET IBS0 HET1 HET2 KINSHIP over the kept variants called in\n"
@@ -630,6 +643,28 @@ int main(int argc, char **argv)
             ld.counts = a.has("counts");
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
             return a.done(pfile.output_ld(a.get("include-sam"), a.get("include-var"), a.get("out").value_or(""), ld, output_options(a)), t_main);
+        }
+        if (cmd == "prune") {
+            const SelectionArgs a(argc, argv, {{"window", 0}, {"window-kb", 0}, {"r2", 0}, {"block-rows", 0}}, {{"export", 0}});
+            if (!a.has("window") && !a.has("window-kb")) usage_error("the following required arguments were not provided: --window <W> or --window-kb <KB>");
+            if (!a.has("r2")) usage_error("the following required arguments were not provided: --r2 <X>");
+            if (!a.has("out") || a.get("out")->empty()) usage_error("the following required arguments were not provided: --out <OUT_PREFIX>");
+            PruneOptions po;
+            if (auto w = a.get("window")) po.window = (uint32_t)unsigned_value(*w, "window", "W", 1, 0xFFFFFFFFull, "a number of variants from 1 to 4294967295");
+            if (auto k = a.get("window-kb")) {
+                po.window_kb = unsigned_value(*k, "window-kb", "KB", 0, 4294967ull, "a number of kilobases from 0 to 4294967");
+                po.has_window_kb = true;
+            }
+            po.min_r2 = double_value(*a.get("r2"), "r2", "X", 0.0, 1.0, "a number from 0 to 1");
+            if (auto b = a.get("block-rows")) po.block_rows = block_rows_value(*b);
+            po.with_export = a.has("export");
+            const Pfile pfile = Pfile::from_prefix(a.positional[0]);
+            const OutputStats st = pfile.output_prune(a.get("include-sam"), a.get("include-var"), *a.get("out"), po, output_options(a));
+            std::printf("{\"kept\": %llu, \"removed\": %llu, \"edges\": %llu, \"window\": %llu, \"resolve_calls\": %llu, \"mask_bytes\": %llu}\n",
+                        (unsigned long long)st.prune_kept, (unsigned long long)st.prune_removed, (unsigned long long)st.prune_edges,
+                        (unsigned long long)st.prune_window, (unsigned long long)st.prune_calls, (unsigned long long)st.prune_mask_bytes);
+            std::fflush(stdout);
+            return a.done(st, t_main);
         }
         if (cmd == "kinship") {
             const SelectionArgs a(argc, argv, {{"min-kinship", 0}, {"sample-tile", 0}, {"block-rows", 0}}, {{"counts", 0}});

@@ -12,6 +12,7 @@
 #include <mutex>
 
 #include "block_loop.h"
+#include "prune.h"
 #include "linalg.h"
 #include "stats.h"
 
@@ -1104,22 +1105,13 @@ OutputStats Pfile::output_matrix(const std::optional<std::string> &sam_query, co
     return st;
 }
 
-OutputStats Pfile::output_export(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
-                                 const std::string &out_prefix, const ExportOptions &eopt, const OutputOptions &opt) const
+// export's two halves, which `prune --export` also runs on the variants it kept (prune.h): the two metadata texts of a selection ...
+void export_texts(const Pfile &pf, const Pfile::Selection &sel, const ExportOptions &eopt, std::string &var_text, std::string &sam_text)
 {
-    OutputStats st;
-    const std::string out_main = out_prefix + (eopt.bed ? ".bed" : ".pgen");
-    const std::string out_var = out_prefix + (eopt.bed ? ".bim" : ".pvar"), out_sam = out_prefix + (eopt.bed ? ".fam" : ".psam");
-    if (!eopt.bed) {   // the same file by another spelling or through a link is still the input
-        std::error_code ec1, ec2;
-        const auto in = std::filesystem::weakly_canonical(pgen_path(), ec1), out = std::filesystem::weakly_canonical(out_main, ec2);
-        if (out_main == pgen_path() || (!ec1 && !ec2 && in == out))
-            throw PfileError("export would overwrite its input: " + out_main + " is " + pgen_path());
-    }
     auto optional_column = [](const StringRecord &header, const char *name) {   // header.size(): the file has none
         return (size_t)(std::find(header.begin(), header.end(), std::string(name)) - header.begin());
     };
-    auto join_rows = [](std::string &text, const IdxRecords &rows) {
+    auto join_rows = [](std::string &text, const Pfile::IdxRecords &rows) {
         for (const auto &ir : rows) {
             for (size_t c = 0; c < ir.second.size(); c++) {
                 if (c) text += '\t';
@@ -1128,41 +1120,44 @@ OutputStats Pfile::output_export(const std::optional<std::string> &sam_query, co
             text += '\n';
         }
     };
-    std::string var_text, sam_text;
-    const Opening o = open_selection(*this, sam_query, var_query, opt, st, false, [&](const Selection &sel) {
-        if (eopt.bed) {
-            const StringRecord &vh = sel.var_header, &sh = sel.sam_header;
-            const size_t chrom = column(vh, "CHROM", pvar_path()), id = column(vh, "ID", pvar_path()), pos = column(vh, "POS", pvar_path()),
-                         ref = column(vh, "REF", pvar_path()), alt = column(vh, "ALT", pvar_path());
-            for (const auto &vr : sel.var_idx_rcds) {
-                const StringRecord &r = vr.second;
-                if (r.at(alt).find(',') != std::string::npos)
-                    throw PfileError("variant " + r.at(id) + " (row " + std::to_string(vr.first) + " of " + pvar_path() + ") has more than one ALT allele (" +
-                                     r.at(alt) + "): a .bed holds biallelic variants only");
-                var_text += r.at(chrom) + '\t' + r.at(id) + "\t0\t" + r.at(pos) + '\t' + r.at(alt) + '\t' + r.at(ref) + '\n';
-            }
-            const size_t iid = iid_column(*this, sh), fid = optional_column(sh, "FID"), pat = optional_column(sh, "PAT"), mat = optional_column(sh, "MAT"),
-                         sex = optional_column(sh, "SEX");
-            for (const auto &sr : sel.sam_idx_rcs) {
-                const StringRecord &r = sr.second;
-                auto or_zero = [&](size_t c) { return c == sh.size() ? std::string("0") : r.at(c); };
-                const std::string sx = sex == sh.size() ? std::string("0") : r.at(sex);
-                sam_text += or_zero(fid) + '\t' + r.at(iid) + '\t' + or_zero(pat) + '\t' + or_zero(mat) + '\t' + (sx == "1" || sx == "2" ? sx : std::string("0")) + "\t-9\n";
-            }
-        } else {
-            const auto [pvar_header, pvar_column_names] = read_pvar_header();
-            var_text = pvar_header + pvar_column_names;
-            if (!var_text.empty() && var_text.back() != '\n') var_text += '\n';
-            join_rows(var_text, sel.var_idx_rcds);
-            const std::string psam = read_file(psam_path());
-            const size_t eol = psam.find('\n', (size_t)find_metadata_file_header_start(psam));
-            sam_text = eol == std::string::npos ? psam + "\n" : psam.substr(0, eol + 1);
-            join_rows(sam_text, sel.sam_idx_rcs);
+    if (eopt.bed) {
+        const StringRecord &vh = sel.var_header, &sh = sel.sam_header;
+        const size_t chrom = column(vh, "CHROM", pf.pvar_path()), id = column(vh, "ID", pf.pvar_path()), pos = column(vh, "POS", pf.pvar_path()),
+                     ref = column(vh, "REF", pf.pvar_path()), alt = column(vh, "ALT", pf.pvar_path());
+        for (const auto &vr : sel.var_idx_rcds) {
+            const StringRecord &r = vr.second;
+            if (r.at(alt).find(',') != std::string::npos)
+                throw PfileError("variant " + r.at(id) + " (row " + std::to_string(vr.first) + " of " + pf.pvar_path() + ") has more than one ALT allele (" +
+                                 r.at(alt) + "): a .bed holds biallelic variants only");
+            var_text += r.at(chrom) + '\t' + r.at(id) + "\t0\t" + r.at(pos) + '\t' + r.at(alt) + '\t' + r.at(ref) + '\n';
         }
-    });
-    const Selection &sel = o.sel;
-    const KeptSamples &kept = o.kept;
-    const size_t V = o.V, K = o.K, RK = (K + 3) / 4;
+        const size_t iid = iid_column(pf, sh), fid = optional_column(sh, "FID"), pat = optional_column(sh, "PAT"), mat = optional_column(sh, "MAT"),
+                     sex = optional_column(sh, "SEX");
+        for (const auto &sr : sel.sam_idx_rcs) {
+            const StringRecord &r = sr.second;
+            auto or_zero = [&](size_t c) { return c == sh.size() ? std::string("0") : r.at(c); };
+            const std::string sx = sex == sh.size() ? std::string("0") : r.at(sex);
+            sam_text += or_zero(fid) + '\t' + r.at(iid) + '\t' + or_zero(pat) + '\t' + or_zero(mat) + '\t' + (sx == "1" || sx == "2" ? sx : std::string("0")) + "\t-9\n";
+        }
+    } else {
+        const auto [pvar_header, pvar_column_names] = pf.read_pvar_header();
+        var_text = pvar_header + pvar_column_names;
+        if (!var_text.empty() && var_text.back() != '\n') var_text += '\n';
+        join_rows(var_text, sel.var_idx_rcds);
+        const std::string psam = read_file(pf.psam_path());
+        const size_t eol = psam.find('\n', (size_t)Pfile::find_metadata_file_header_start(psam));
+        sam_text = eol == std::string::npos ? psam + "\n" : psam.substr(0, eol + 1);
+        join_rows(sam_text, sel.sam_idx_rcs);
+    }
+}
+
+// ... and the records of its variants packed on the device(s) and written with the texts (st.variants: the variants written)
+void export_records(const Pfile &pf, const Pfile::IdxRecords &vars, const KeptSamples &kept, const std::string &out_prefix, const ExportOptions &eopt,
+                    const OutputOptions &opt, OutputStats &st, const std::string &var_text, const std::string &sam_text)
+{
+    const std::string out_main = out_prefix + (eopt.bed ? ".bed" : ".pgen");
+    const std::string out_var = out_prefix + (eopt.bed ? ".bim" : ".pvar"), out_sam = out_prefix + (eopt.bed ? ".fam" : ".psam");
+    const size_t V = vars.size(), K = kept.rows.size(), RK = (K + 3) / 4;
     std::string header;
     if (eopt.bed) {
         header.assign("\x6C\x1B\x01", 3);   // variant-major
@@ -1183,7 +1178,7 @@ OutputStats Pfile::output_export(const std::optional<std::string> &sam_query, co
     pwrite_exact(out.get(), header.data(), header.size(), 0, out_main);
     if (V != 0 && K != 0) {   // else a zero dimension: the header alone, no device touched
         static const uint8_t kBedMap[4] = {3, 2, 0, 1};   // ALT as A1: 00 hom A1, 01 missing, 10 het, 11 hom A2
-        count_blocks(*this, sel.var_idx_rcds, kept, opt, kNoDevice, st, [&](DeviceCtx &ctx, uint64_t bv) {
+        count_blocks(pf, vars, kept, opt, kNoDevice, st, [&](DeviceCtx &ctx, uint64_t bv) {
             const size_t bytes = (size_t)(bv * RK);
             return PackWriter{{}, RK, eopt.bed ? kBedMap : nullptr, ctx.device<uint8_t>(bytes, "device packed records"),
                               ctx.pinned<uint8_t>(bytes, "pinned packed records"), out.get(), out_main, (uint64_t)header.size()};
@@ -1193,6 +1188,25 @@ OutputStats Pfile::output_export(const std::optional<std::string> &sam_query, co
     write_text(var_text, out_var);
     write_text(sam_text, out_sam);
     st.seconds_body = now_s() - t_body;
+}
+
+void refuse_export_over_input(const Pfile &pf, const std::string &out_main)
+{
+    // the same file by another spelling or through a link is still the input
+    std::error_code ec1, ec2;
+    const auto in = std::filesystem::weakly_canonical(pf.pgen_path(), ec1), out = std::filesystem::weakly_canonical(out_main, ec2);
+    if (out_main == pf.pgen_path() || (!ec1 && !ec2 && in == out))
+        throw PfileError("export would overwrite its input: " + out_main + " is " + pf.pgen_path());
+}
+
+OutputStats Pfile::output_export(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
+                                 const std::string &out_prefix, const ExportOptions &eopt, const OutputOptions &opt) const
+{
+    OutputStats st;
+    if (!eopt.bed) refuse_export_over_input(*this, out_prefix + ".pgen");
+    std::string var_text, sam_text;
+    const Opening o = open_selection(*this, sam_query, var_query, opt, st, false, [&](const Selection &sel) { export_texts(*this, sel, eopt, var_text, sam_text); });
+    export_records(*this, o.sel.var_idx_rcds, o.kept, out_prefix, eopt, opt, st, var_text, sam_text);
     return st;
 }
 

@@ -101,6 +101,16 @@ struct ExportOptions {
     bool bed = false;                 // PLINK 1 .bed / .bim / .fam instead of .pgen / .pvar / .psam
 };
 
+// `prune`: the window in kept variants and / or in base pairs, the r^2 above which two variants do not both stay
+struct PruneOptions {
+    uint32_t window = 0;              // --window W (0: not given; then --window-kb sets W from the positions)
+    uint64_t window_kb = 0;           // --window-kb KB (0: not given): pairs further apart than KB x 1000 base pairs are no edges
+    bool has_window_kb = false;
+    double min_r2 = 0.2;              // --r2: an edge is r^2 > min_r2 (as float32)
+    bool with_export = false;         // --export: OUT.pgen / .pvar / .psam of the kept variants and samples beside the two lists
+    uint64_t block_rows = 0;          // rows per block (0: as many as fill block_text_bytes with their records)
+};
+
 // `score`: how missing calls count and what is printed
 struct ScoreOptions {
     bool mean_imputation = true;      // a missing call counts as the variant's mean dosage over the kept samples called (else as 0)
@@ -171,6 +181,7 @@ struct OutputStats {
     double pca_residual = 0;                                                     // `pca`: max over the written components of |M u - lambda u| / lambda_1 at the last pass
     bool pca_converged = true;                                                   // `pca`: the residual reached --tol within --max-passes
     uint64_t import_skipped = 0, import_half_call = 0, import_haploid = 0, import_phased = 0;   // `import`: multiallelic lines dropped; lines with a half call, a haploid call, a phased call
+    uint64_t prune_kept = 0, prune_removed = 0, prune_edges = 0, prune_window = 0, prune_calls = 0, prune_mask_bytes = 0;   // `prune`: its JSON line
     double seconds_setup = 0;   // inside seconds_body: HIP runtime start, contexts, device and pinned allocations of the slowest shard, before its first block is staged
 };
 
@@ -307,6 +318,18 @@ class Pfile {
     // Uses n_gpus, n_shards, block_text_bytes (bytes of records per block), read_threads and filter_threads of `opt`.
     OutputStats output_export(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
                               const std::string &out_prefix, const ExportOptions &eopt, const OutputOptions &opt = OutputOptions()) const;
+
+    // `prune` (not in the reference): LD pruning of the kept variants.  One pass over the blocks (each with the W rows behind it) counts
+    // every row (pgenhip_genotype_counts) and ORs its pairs' edges into two masks that stay on the device (pgenhip_pair_mask with keys
+    // (CHROM rank by first appearance << 32) | POS; without --window-kb POS is left out and max_span is 0, so a window in variants
+    // still stops at chromosome ends); then the priorities (minor-allele frequency among called alleles, host/prune_plan.h) go up,
+    // pgenhip_prune_resolve runs until nothing is undecided, and one state byte per row comes back.  The more common variant of a
+    // correlated pair stays, ties go to the earlier one; a monomorphic or uncalled variant has no r^2, hence no edge, and is kept.
+    // Writes OUT.prune.in (the kept variants' IDs, one per line, in file order) and OUT.prune.out (the removed ones'), with --export
+    // also OUT.pgen / .pvar / .psam of the kept variants and samples through `export`'s own path.  One device.  Fewer than two kept
+    // variants or no kept sample: every variant is kept and no device is touched.  No parity with plink2 --indep-pairwise is claimed.
+    OutputStats output_prune(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
+                             const std::string &out_prefix, const PruneOptions &popt, const OutputOptions &opt = OutputOptions()) const;
 
     // `kinship` (not in the reference): the joint genotype tables of every pair of kept samples over the kept variants
     // (pgenhip_sample_pair_stats / _at) and the KING-robust between-family kinship estimate from them.  The kept samples are cut into
