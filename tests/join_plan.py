@@ -35,6 +35,37 @@ def chunk_bytes(record_size: int, mis: int, chunk: int) -> tuple[int, int]:
     return lo, max(lo, min(b0 + CHUNK_BYTES, record_size))
 
 
+def stream_paths(sizes, dmis: int) -> list[tuple]:
+    """The class of every chunk of one output row of parts ``sizes`` (all present) that starts ``dmis`` bytes behind a chunk boundary,
+    as gt_join_stream_kernel sorts them (gt_join.hip; the conditions are the kernel's, in its order):
+      ("edge", None, None, None)      `b0 >= 0 && last >= 15` fails: the row's head or tail, bytes through join_dword
+      ("dword", p, phase, depth)      a whole chunk built by four join_dword calls; p, phase and depth are None where the 64 samples
+                                      span parts (`s0 >= pt.start && s0 - pt.start + 64u <= pt.count` holds for no part), else the
+                                      part's index, `ls & 3` and `rp - sb` (< 20: `sb + 20u <= rp` fails)
+      ("fast", p, phase, depth)       the 16 + 4-byte load, funnel-shifted by ph = 2 * (ls & 3): phase = `ls & 3`, depth = `rp - sb`
+    Chunks with no byte of the row (`b0 >= R || b0 + kChunkBytes <= 0`) are left out."""
+    starts = [sum(sizes[:p]) for p in range(len(sizes))]
+    r = (sum(sizes) + 3) // 4
+    out = []
+    for c in range(chunks_per_row(r)):
+        b0 = CHUNK_BYTES * c - dmis
+        if b0 >= r or b0 + CHUNK_BYTES <= 0:
+            continue
+        last = r - 1 - b0
+        if not (b0 >= 0 and last >= CHUNK_BYTES - 1):
+            out.append(("edge", None, None, None))
+            continue
+        s0 = 4 * b0
+        kind = ("dword", None, None, None)
+        for p, (start, count) in enumerate(zip(starts, sizes)):
+            if s0 >= start and s0 - start + 64 <= count:
+                ls = s0 - start
+                sb, rp = ls >> 2, (count + 3) >> 2
+                kind = ("fast" if sb + 20 <= rp else "dword", p, ls & 3, rp - sb)
+        out.append(kind)
+    return out
+
+
 def rows_per_block(record_size: int) -> int:
     """STREAM: whole rows of short records that share a block."""
     return max(1, THREADS // chunks_per_row(record_size))

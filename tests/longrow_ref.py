@@ -179,6 +179,34 @@ def check_packed(out_row: torch.Tensor, rec: torch.Tensor, n: int, kept=None, ma
     return None
 
 
+def check_joined(out_row: torch.Tensor, parts_rows: Sequence[Optional[torch.Tensor]], starts: Sequence[int], counts: Sequence[int],
+                 flips: Sequence[bool], absent: Sequence[bool], n: int, slab: int = SLAB):
+    """``out_row``: the ceil(n / 4) bytes of one joined row (pgenhip_join_records).  Part p's record ``parts_rows[p]`` (not read where
+    ``absent[p]``) holds ``counts[p]`` samples that must appear as output samples ``starts[p]`` onwards: as they are, with codes 0 and
+    2 exchanged where ``flips[p]``, all 3 where ``absent[p]``.  Compared sample by sample, so slab seams and part seams fall inside
+    bytes of both sides.  -> None, or (output sample, got code, want code) of the first wrong code in sample order; set pad bits in the
+    last byte are reported as (n, pad bits, 0)."""
+    flip = torch.tensor([2, 1, 0, 3], dtype=torch.uint8, device=out_row.device)
+    assert sum(counts) == n and all(s == sum(counts[:p]) for p, s in enumerate(starts))
+    for p, (start, count) in enumerate(zip(starts, counts)):
+        for a, b in _slabs(count, slab):
+            got = codes(out_row, start + a, start + b)
+            if absent[p]:
+                want = torch.full_like(got, 3)
+            else:
+                want = codes(parts_rows[p], a, b)
+                if flips[p]:
+                    want = flip[want.to(torch.int64)]
+            i = _first_diff(got, want)
+            if i is not None:
+                return start + a + i, int(got[i]), int(want[i])
+    if n % 4:
+        pad = int(out_row[(n - 1) >> 2]) >> (2 * (n % 4))
+        if pad:
+            return n, pad, 0
+    return None
+
+
 def check_scores(scores: torch.Tensor, recs_rows: Sequence[torch.Tensor], n: int, kept, weights, miss=None, prefill: int = 0,
                  slab: int = SLAB):
     """``scores``: the K * C float64 values pgenhip_sample_scores wrote.  ``weights``: (V, C) small integers, ``miss``: V small integers
@@ -432,6 +460,14 @@ def framed(nbytes: int, device, align: int = 1):
     buf = torch.full((front + nbytes + BACK,), SENT, dtype=torch.uint8, device=device)
     assert buf.data_ptr() % 16 == 0
     return buf, front
+
+
+def fill_periodic(dst: torch.Tensor, pattern: torch.Tensor):
+    """dst[i] = pattern[i % len(pattern)] for a 1-D ``dst`` of any length, without a temporary of its size"""
+    p = pattern.numel()
+    whole = dst.numel() // p
+    dst[: whole * p].view(whole, p).copy_(pattern[None, :].expand(whole, p))
+    dst[whole * p:].copy_(pattern[: dst.numel() - whole * p])
 
 
 def frame_ok(buf: torch.Tensor, front: int, nbytes: int) -> bool:

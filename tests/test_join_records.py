@@ -82,6 +82,42 @@ def test_plan_twin_matches_header():
                 assert bool(join_plan.probe("join_auto", 1, r, v, n_parts)[0]) == join_plan.auto_stream(r, v, n_parts)
 
 
+def test_stream_paths_classifier_by_hand():
+    # R = 101 bytes at phase 0: chunks 0..5 whole, chunk 6 the tail.  Part 1 (100 bytes) starts at sample 1: ls & 3 == 3 in all its chunks
+    got = join_plan.stream_paths((1, 400), 0)
+    assert got[0] == ("dword", None, None, None) and got[-1] == ("edge", None, None, None) and len(got) == 7
+    assert got[1] == ("fast", 1, 3, 100 - 15) and got[5] == ("fast", 1, 3, 100 - 79)
+    assert join_plan.stream_paths((1, 400), 1)[:2] == [("edge", None, None, None), ("fast", 1, 3, 100 - 14)]
+    assert join_plan.stream_paths((3,), 5) == [("edge", None, None, None)]
+    # one part, 80 samples = 20 bytes: the only whole chunk is byte 0's, exactly 20 bytes deep; one byte less and it is not
+    assert join_plan.stream_paths((80,), 0) == [("fast", 0, 0, 20), ("edge", None, None, None)]
+    assert join_plan.stream_paths((76,), 0) == [("dword", 0, 0, 19), ("edge", None, None, None)]
+
+
+def test_gpu_size_lists_reach_every_stream_path():
+    """The size lists of tests/test_join_records_gpu.py, at all 16 address phases of an output row, reach: the fast path at every bit
+    phase; a whole chunk inside one part 19, 20 and 21 bytes from the record's end (the last that misses the fast path and the first
+    two that take it) at every bit phase; the fast path in the first, a middle and the last part of an eight-part table."""
+    import test_join_records_gpu as G
+
+    fast, depth, eight = set(), set(), set()
+    for sizes in G.SIZES + [G.PHASE_SIZES]:
+        for dmis in range(16):
+            for kind, p, phase, deep in join_plan.stream_paths(sizes, dmis):
+                if p is None:
+                    continue
+                assert kind == ("fast" if deep >= 20 else "dword")
+                if kind == "fast":
+                    fast.add(phase)
+                    if len(sizes) == 8:
+                        eight.add(p)
+                if deep in (19, 20, 21):
+                    depth.add((phase, deep))
+    assert fast == {0, 1, 2, 3}, f"fast path only at ls & 3 in {sorted(fast)}"
+    assert depth == {(ph, d) for ph in range(4) for d in (19, 20, 21)}, f"rp - sb reached: {sorted(depth)}"
+    assert 0 in eight and 7 in eight and eight & set(range(1, 7)), f"fast path in parts {sorted(eight)} of eight"
+
+
 def test_stream_chunks_tile_every_row_once():
     """Whatever the row's address, the chunks of the plan cover each of its bytes once, in order, 16 at the most each."""
     for r in sorted(set(list(range(1, 50)) + join_plan.edge_record_sizes() + [17501])):

@@ -18,6 +18,10 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 SENT = 0xA5
 SIZES = [(1,), (3, 5), (1, 1, 1, 1, 1, 1, 1, 1), (16, 16), (17, 1, 2, 44), (63, 64, 65), (5, 0, 6), (300, 2504), (70001, 3)]
+# STREAM's fast path at every bit phase ls & 3, 19, 20 and 21 bytes from the record's end, in the first, a middle and the last of eight
+# parts (starts of every residue mod 4): tests/test_join_records.py holds these lists against the kernel's branch conditions
+SIZES += [(1, 400), (2, 401, 3), (3, 90, 333), (84, 85, 86, 87, 84, 90, 99, 101)]
+PHASE_SIZES = (17, 1, 2, 44, 70, 9)   # test_every_output_address_phase
 SHAPES = [_capi.JOIN_GENERAL, _capi.JOIN_STREAM, _capi.JOIN_AUTO]
 MODES = ["plain", "flip", "absent", "repeat"]
 
@@ -111,7 +115,7 @@ def test_join_against_numpy(sizes):
 
 def test_every_output_address_phase():
     """One seam-rich case at each of the 16 byte phases of the output, dense pitch and padded: the head and tail bytes of every row."""
-    sizes, v = (17, 1, 2, 44, 70, 9), 5
+    sizes, v = PHASE_SIZES, 5
     parts = case(sizes, v, "flip", 77)
     want = JR.join(parts, v)
     dparts = to_dev(parts)

@@ -153,6 +153,62 @@ def test_packed_check(n, keep, map4):
             assert LR.check_packed(bad, rec, n, kept, map4, slab=SLAB) == (k, 0x80 >> (2 * (k % 4)), 0)
 
 
+def test_fill_periodic():
+    pattern = torch.arange(7, dtype=torch.int32) + 100
+    for n in (0, 3, 7, 8, 20, 21, 1000):
+        dst = torch.full((n,), -1, dtype=torch.int32)
+        LR.fill_periodic(dst, pattern)
+        assert dst.tolist() == [100 + i % 7 for i in range(n)]
+
+
+JOINS = [(3, 5), (97, 1, 96), (1, 400), (63, 64, 65, 2), (84, 85, 0, 87, 84, 90, 99, 101)]
+
+
+@pytest.mark.parametrize("sizes", JOINS, ids=lambda s: "x".join(map(str, s)))
+def test_joined_check(sizes):
+    """check_joined against join_ref.join (sources with dirty pad bits at odd addresses): plain, flipped and absent parts agree;
+    a wrong sample on either side of every seam, a set pad bit and a wrong last byte are each reported where they were planted."""
+    import join_ref as JR
+
+    n = sum(sizes)
+    starts = [sum(sizes[:p]) for p in range(len(sizes))]
+    rng = np.random.default_rng(n)
+    v = 3
+    parts = []
+    for cnt in sizes:
+        r = (cnt + 3) // 4
+        base = rng.integers(0, 256, size=1 + v * (r + 2), dtype=np.uint8)   # random bytes: the pad bits are dirty
+        parts.append([base, np.array([1 + j * (r + 2) for j in range(v)], dtype=np.int64), cnt,
+                      np.array([0, 1, 0], dtype=np.uint8) if len(parts) % 2 else np.array([0, 0, 1], dtype=np.uint8)])
+    parts[len(sizes) // 2][1][2] = JR.ABSENT
+    want = JR.join([tuple(p) for p in parts], v)
+    for j in range(v):
+        row = torch.from_numpy(want[j].copy())
+        rows = [torch.from_numpy(b[int(o[j]):].copy()) if o[j] != JR.ABSENT else None for b, o, _, _ in parts]
+        flips = [bool(f[j]) for _, _, _, f in parts]
+        absent = [r is None for r in rows]
+        assert any(flips) or j == 0
+        assert absent == [j == 2 and p == len(sizes) // 2 for p in range(len(sizes))]
+        args = (rows, starts, list(sizes), flips, absent, n)
+        assert LR.check_joined(row, *args, slab=SLAB) is None
+        if any(f and c >= 60 and not a for f, c, a in zip(flips, sizes, absent)):   # 60 random codes hold a 0 or a 2
+            assert LR.check_joined(row, rows, starts, list(sizes), [False] * len(sizes), absent, n, slab=SLAB) is not None
+        seams = {s for p, s in enumerate(starts) if sizes[p]} | {s - 1 for s in starts if s} | {0, n - 1, SLAB - 1, SLAB}
+        for sample in sorted(s for s in seams if 0 <= s < n):
+            bad = row.clone()
+            bad[sample >> 2] ^= 1 << (2 * (sample & 3))
+            found = LR.check_joined(bad, *args, slab=SLAB)
+            assert found is not None and found[0] == sample and found[1] == found[2] ^ 1, (sample, found)
+        bad = row.clone()
+        bad[-1] ^= 0x02                                                  # the last byte's first sample: always a real one
+        found = LR.check_joined(bad, *args, slab=SLAB)
+        assert found is not None and found[0] >> 2 == (n - 1) >> 2
+        if n % 4:
+            bad = row.clone()
+            bad[-1] |= 0x80
+            assert LR.check_joined(bad, *args, slab=SLAB) == (n, 0x80 >> (2 * (n % 4)), 0)
+
+
 @pytest.mark.parametrize("n,keep", CASES)
 @pytest.mark.parametrize("c", [1, 3, 8])
 def test_scores_check(n, keep, c):

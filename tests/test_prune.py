@@ -154,6 +154,32 @@ def test_gpu_cases_keep_clear_of_the_threshold():
         R.edges(c[60 * i: 60 * i + 60], 60, 32, G.MIN_R2)
 
 
+def test_far_range_cases_are_what_prune_ref_gives_row_by_row():
+    """The builders of tests/test_long_rows_prune_gpu.py, at sizes small enough to go through prune_ref row by row: the periodic rows
+    never trip the guard and their tiled masks are prune_ref.masks of prune_ref.edges of all rows; the S of a graph of disjoint
+    segments (strays and truncated last segment included) is the S of one segment, tiled."""
+    import test_long_rows_prune_gpu as G
+
+    _, fwd, bwd, codes = G.periodic_mask_case()
+    assert fwd.shape == bwd.shape == (G.V_FAR, 2) and fwd[:, 1].any() and bwd[:, 1].any()
+    for v in (50, 200):
+        _, f, b, _ = G.periodic_mask_case(v)
+        rf, rb = R.masks(R.edges(codes[np.arange(v) % G.P], v, G.W_FAR, G.MIN_R2))
+        assert (f == rf).all() and (b == rb).all(), v
+        assert (f == fwd[:v]).sum() > f.size // 2 and (b == bwd[:v]).all()    # the long case's first rows, but for the clipping
+    v = 2 * G.SEGMENT_TURNS + 517
+    f, b, p, s_whole, s_tail = G.many_turns_case(v)
+    assert len(s_tail) == 517 and set(p.tolist()) == {0, 1, 2}
+    assert (R.resolve(f, b, G.W_TURNS, p) == np.concatenate([s_whole, s_whole, s_tail])).all()
+    for prio_values in (0, 1 << 32):
+        v = 3 * 90 + 63
+        f90, b90, p90, s_whole, s_tail = G.segment_graph(90, 90, 32, 0.1, v, prio_values)
+        rows = np.arange(v) % 90
+        got = R.resolve(f90[rows], b90[rows], 32, None if p90 is None else p90[rows])
+        assert (got == np.concatenate([s_whole] * 3 + [s_tail])).all()
+        assert any(R.neighbours(f90[:63], b90[:63], 32, r) != R.neighbours(f90, b90, 32, r) for r in range(63))   # strays exist
+
+
 # ---- the plan ---------------------------------------------------------------------------------------------------------------------------
 def test_plan_twin_matches_header():
     assert (PP.THREADS, PP.CHUNK_ROWS, PP.HALO_ROWS, PP.LDS_ROWS) == (256, 1024, 512, 2048) and PP.LDS_ROWS == PP.CHUNK_ROWS + 2 * PP.HALO_ROWS
