@@ -341,6 +341,64 @@ int pgenhip_variant_sums(pgenhip_ctx *ctx, const void *d_records, uint64_t recor
 int pgenhip_variant_sums_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
                             const double *d_values, uint64_t v_stride, uint32_t n_columns, double *d_sums, uint32_t flags);
 
+/* ---- per-variant logistic regression (device-resident, asynchronous on the ctx stream) ----
+ * What pgenhip_variant_sums cannot give: a fit whose weights depend on the row's own coefficients.  For every selected row j a
+ * logistic regression of d_y on X = [design, g] over the ctx's kept samples, g_k = t_j[x_j(k)] with x_j(k) the code of kept sample k
+ * in row j (0 hom-ref, 1 het, 2 hom-alt, 3 missing) and t_j = d_code_values[4*j .. 4*j+3] (the table argument of pgenhip_sample_gram:
+ * a DEVICE array of FP64 indexed by the row's position in the selection).  A NaN table entry leaves the samples with that code out of
+ * row j's fit, so one kernel serves both policies for a missing call: a host passes the row's mean dosage for code 3 (mean
+ * imputation) or NaN (the sample is dropped for that row).  The library does not interpret the table.
+ * Rows are selected exactly as in pgenhip_variant_sums / pgenhip_variant_sums_at: by stride (record_stride >= R, or n_variants <= 1),
+ * through d_variant_idx, or through d_record_off; records may start at any byte alignment; a gather that repeats a row writes it
+ * twice.  The pad bits of a record's last byte and samples >= N are never read as samples.  d_design is a DEVICE array of FP64,
+ * K x n_cov, indexed by the sample's rank in the kept list like d_values of pgenhip_variant_sums (x_stride in doubles, >= n_cov or
+ * K <= 1; a host puts the intercept there as a column); d_y holds K values in [0, 1]; d_start the n_cov coefficients of the null
+ * model (the fit without the genotype), from which every row starts.
+ *   - The algorithm is fixed, so that a reference can restate it.  beta = (d_start, 0).  For it = 1 .. max_iter: over the included
+ *     samples evaluate mu = 1 / (1 + e^-(X beta)), grad = X^T (y - mu) and H = X^T diag(mu (1 - mu)) X; take the Cholesky factor of
+ *     H, where a pivot that is <= 0 or not finite ends the row as SINGULAR (the coefficients keep this beta, the SE is NaN);
+ *     delta = H^-1 grad; if max |delta_i| <= tol the row is CONVERGED and reports THIS beta (not beta + delta), SE =
+ *     sqrt((H^-1)[g][g]) from this H and it evaluations; else, if it == max_iter, the row is NOT_CONVERGED (the coefficients hold
+ *     this beta, the SE is NaN); else beta += delta.  So max_iter evaluations take at most max_iter - 1 steps.  There is no step
+ *     halving and no Firth penalty: a separated row ends as NOT_CONVERGED or SINGULAR.  A row with no included sample is SINGULAR.
+ *   - Arithmetic: every product and every addition is FP64.  The ORDER of the additions is not fixed (samples are dealt to lanes);
+ *     bitwise run-to-run and shape-to-shape reproducibility is NOT promised.  e^-eta overflowing to inf gives mu = 0, not NaN.
+ *   - Outputs, per row j: d_coef[j * c_stride .. + n_cov] (c_stride in doubles, >= n_cov + 1 or n_variants <= 1): the covariates'
+ *     coefficients, then the genotype's; d_se[j]: the genotype's standard error or NaN; d_status[j]: the evaluations done in the low
+ *     8 bits and one of PGENHIP_LOGIT_CONVERGED / NOT_CONVERGED / SINGULAR.  d_coef rows may be used as working storage during the
+ *     call; nothing outside the three outputs is written.  K == 0 writes SINGULAR for every row (d_design and d_y are not read).
+ *     n_variants == 0 is a no-op.
+ *   - PGENHIP_ERR_BAD_ARG, before any launch and with nothing written: n_cov == 0 or > PGENHIP_LOGIT_MAX_COVARIATES; max_iter == 0 or
+ *     > PGENHIP_LOGIT_MAX_ITER; tol NaN or negative; x_stride < n_cov with K > 1; c_stride < n_cov + 1 with n_variants > 1; with
+ *     n_variants > 0 a NULL d_code_values, d_start, d_coef, d_se or d_status, and with K > 0 as well a NULL d_design or d_y; a
+ *     pointer to doubles that is not 8-byte aligned, d_status not 4-byte aligned; unknown flag bits or shape ids.
+ *     PGENHIP_ERR_TOO_LARGE, before any launch: byte offsets of 2^52 or more (x_stride * K * 8, c_stride * n_variants * 8,
+ *     record_stride * n_variants as in pgenhip_decode_matrix).
+ * Same launch contract as pgenhip_variant_sums: device pointers only, no allocation, no synchronisation, one kernel queued on the
+ * ctx stream, graph-capturable, no work counters (these launches do not count against PGENHIP_LAUNCHES_IN_FLIGHT), outputs in
+ * ordinary device memory.  One row's samples are not split over blocks (the iteration needs no meeting across blocks): a call with
+ * few rows of very long records uses few CUs.  PGENHIP_KNOB_LOGIT_BLOCKS forces the grid.
+ * flags: a shape (PGENHIP_LOGIT_AUTO or a forced one). */
+#define PGENHIP_LOGIT_MAX_COVARIATES 15u   /* design columns incl. the intercept; the genotype is the 16th */
+#define PGENHIP_LOGIT_MAX_ITER 64u
+#define PGENHIP_LOGIT_AUTO 0u
+#define PGENHIP_LOGIT_GENERAL 1u   /* a block per row, one pass over the samples per row of H: the correctness baseline, any shape */
+#define PGENHIP_LOGIT_FAST 2u      /* H's lower half in each lane's registers, one pass per evaluation, rows in groups: what AUTO takes */
+#define PGENHIP_LOGIT_SHAPE_MASK 0xFu
+/* d_status[j]: low 8 bits = evaluations done; then */
+#define PGENHIP_LOGIT_CONVERGED     0x100u
+#define PGENHIP_LOGIT_NOT_CONVERGED 0x200u
+#define PGENHIP_LOGIT_SINGULAR      0x400u
+int pgenhip_variant_logistic(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                             uint32_t n_variants, const double *d_code_values, const double *d_design, uint64_t x_stride,
+                             uint32_t n_cov, const double *d_y, const double *d_start, uint32_t max_iter, double tol,
+                             double *d_coef, uint64_t c_stride, double *d_se, uint32_t *d_status, uint32_t flags);
+/* Same, with the record of row j at d_base + d_record_off[j] (DEVICE array of u64 byte offsets). */
+int pgenhip_variant_logistic_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
+                                const double *d_code_values, const double *d_design, uint64_t x_stride, uint32_t n_cov,
+                                const double *d_y, const double *d_start, uint32_t max_iter, double tol, double *d_coef,
+                                uint64_t c_stride, double *d_se, uint32_t *d_status, uint32_t flags);
+
 /* ---- numeric genotype matrix (device-resident, asynchronous on the ctx stream) ----
  * The GT text with the fixed bytes removed: element (j, k) is the code pgenhip_decode_emit prints as the k-th field of row j,
  * mapped through a four-entry table.  Rows are selected exactly as in pgenhip_decode_emit / pgenhip_decode_emit_at; a gather that
@@ -770,6 +828,7 @@ typedef enum pgenhip_knob {
     PGENHIP_KNOB_PARSE_BLOCKS = 29,      /* GT text parse kernels: grid size in blocks (default 0 = by shape: the work, capped at 8 blocks per CU); tests force small grids */
     PGENHIP_KNOB_JOIN_BLOCKS = 30,       /* join kernels: grid size in blocks (default 0 = by shape: the work, capped at 8 blocks per CU); tests force small grids */
     PGENHIP_KNOB_PRUNE_BLOCKS = 31,      /* prune resolve kernels: grid size in blocks (default 0 = by shape); for the BLOCK shape thereby the rows of a workgroup's range; tests force small grids */
+    PGENHIP_KNOB_LOGIT_BLOCKS = 32,      /* per-variant logistic regression: grid size in blocks (default 0 = by shape: a block per group of rows (FAST) or per row (GENERAL), capped at 8 blocks per CU); tests force small grids */
     PGENHIP_KNOB_RUNS_ROWS = 7       /* RUNS kernel: rows per work item (default: as many as one wide load / one span holds) */
 } pgenhip_knob;
 int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value);

@@ -58,6 +58,15 @@ VSUM_AUTO = 0
 VSUM_GENERAL = 1
 VSUM_MFMA = 2
 VSUM_SHAPE_MASK = 0xF
+LOGIT_MAX_COVARIATES = 15
+LOGIT_MAX_ITER = 64
+LOGIT_AUTO = 0
+LOGIT_GENERAL = 1
+LOGIT_FAST = 2
+LOGIT_SHAPE_MASK = 0xF
+LOGIT_CONVERGED = 0x100
+LOGIT_NOT_CONVERGED = 0x200
+LOGIT_SINGULAR = 0x400
 SPAIR_AUTO = 0
 SPAIR_GENERAL = 1
 SPAIR_MFMA = 2
@@ -141,6 +150,7 @@ KNOB_WIDE_BURST = 28
 KNOB_PARSE_BLOCKS = 29
 KNOB_JOIN_BLOCKS = 30
 KNOB_PRUNE_BLOCKS = 31
+KNOB_LOGIT_BLOCKS = 32
 
 
 
@@ -194,6 +204,8 @@ PROTOTYPES = {
     "pgenhip_sample_scores_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]),
     "pgenhip_variant_sums": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_variant_sums_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
+    "pgenhip_variant_logistic": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "pgenhip_variant_logistic_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
     "pgenhip_decode_matrix": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_decode_matrix_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
     "pgenhip_sample_pair_stats": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),

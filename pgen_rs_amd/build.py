@@ -21,7 +21,7 @@ REPO_ROOT = PKG_DIR.parent
 CSRC = PKG_DIR / "csrc"
 HIP_LIB = PKG_DIR / "libpgen_hip.so"
 
-HIP_SOURCES = ["capi.hip", "host_pure.cpp", "gt_rows.hip", "gt_flat.hip", "gt_wide.hip", "gt_scan.hip", "gt_pick.hip", "gt_rowpick.hip", "gt_count.hip", "gt_scount.hip", "gt_score.hip", "gt_vsum.hip", "gt_matrix.hip", "gt_pair.hip", "gt_spair.hip", "gt_gram.hip", "gt_gapply.hip", "gt_pack.hip", "gt_parse.hip", "gt_join.hip", "gt_prune.hip"]
+HIP_SOURCES = ["capi.hip", "host_pure.cpp", "gt_rows.hip", "gt_flat.hip", "gt_wide.hip", "gt_scan.hip", "gt_pick.hip", "gt_rowpick.hip", "gt_count.hip", "gt_scount.hip", "gt_score.hip", "gt_vsum.hip", "gt_logit.hip", "gt_matrix.hip", "gt_pair.hip", "gt_spair.hip", "gt_gram.hip", "gt_gapply.hip", "gt_pack.hip", "gt_parse.hip", "gt_join.hip", "gt_prune.hip"]
 HIPCC_FLAGS = [
     "-O3",
     "-std=c++17",

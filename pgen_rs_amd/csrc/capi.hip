@@ -645,6 +645,75 @@ int pgenhip_variant_sums_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t
     return variant_sums_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, d_values, v_stride, n_columns, d_sums, flags);
 }
 
+static int variant_logistic_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                                 const uint64_t *d_record_off, uint32_t n_variants, const double *d_code_values, const double *d_design,
+                                 uint64_t x_stride, uint32_t n_cov, const double *d_y, const double *d_start, uint32_t max_iter, double tol,
+                                 double *d_coef, uint64_t c_stride, double *d_se, uint32_t *d_status, uint32_t flags)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (flags & ~PGENHIP_LOGIT_SHAPE_MASK) return fail(PGENHIP_ERR_BAD_ARG, "unknown variant_logistic flag");
+    const uint32_t shape = flags & PGENHIP_LOGIT_SHAPE_MASK;
+    if (shape > PGENHIP_LOGIT_FAST) return fail(PGENHIP_ERR_BAD_ARG, "variant_logistic supports shapes AUTO, GENERAL and FAST");
+    if (n_cov == 0u || n_cov > PGENHIP_LOGIT_MAX_COVARIATES) return fail(PGENHIP_ERR_BAD_ARG, "n_cov must be 1 .. PGENHIP_LOGIT_MAX_COVARIATES");
+    if (max_iter == 0u || max_iter > PGENHIP_LOGIT_MAX_ITER) return fail(PGENHIP_ERR_BAD_ARG, "max_iter must be 1 .. PGENHIP_LOGIT_MAX_ITER");
+    if (!(tol >= 0.0)) return fail(PGENHIP_ERR_BAD_ARG, "tol is NaN or negative");
+    const uint32_t K = ctx->kept_count;
+    if (K > 1u && x_stride < n_cov) return fail(PGENHIP_ERR_BAD_ARG, "x_stride < n_cov");
+    if (n_variants > 1u && c_stride < n_cov + 1u) return fail(PGENHIP_ERR_BAD_ARG, "c_stride < n_cov + 1");
+    if (n_variants && (!d_code_values || !d_start || !d_coef || !d_se || !d_status))
+        return fail(PGENHIP_ERR_BAD_ARG, "d_code_values, d_start, d_coef, d_se or d_status is NULL");
+    if (n_variants && K != 0u && (!d_design || !d_y)) return fail(PGENHIP_ERR_BAD_ARG, "d_design or d_y is NULL");
+    if (((uintptr_t)d_code_values | (uintptr_t)d_design | (uintptr_t)d_y | (uintptr_t)d_start | (uintptr_t)d_coef | (uintptr_t)d_se) & 7u)
+        return fail(PGENHIP_ERR_BAD_ARG, "d_code_values, d_design, d_y, d_start, d_coef or d_se is not 8-byte aligned");
+    if ((uintptr_t)d_status & 3u) return fail(PGENHIP_ERR_BAD_ARG, "d_status is not 4-byte aligned");
+    // byte offsets are 64-bit arithmetic in the kernel; the bound is decode_matrix's (2^52 bytes)
+    if ((K > 1u && x_stride >= kMaxSpan / 8u / K) || (n_variants > 1u && c_stride >= kMaxSpan / 8u / n_variants) ||
+        record_span_too_large(record_stride, d_variant_idx, d_record_off, n_variants))
+        return fail(PGENHIP_ERR_TOO_LARGE, "variant_logistic offsets do not fit the kernel's index types");
+    if (n_variants == 0) return PGENHIP_OK;
+    LogitArgs a;
+    rc = select_rows(ctx, a, d_records, record_stride, d_variant_idx, d_record_off, n_variants);
+    if (rc) return rc;
+    if (K == 0u) a.sample_count = 0u;   // no sample is included: every row ends SINGULAR at its first evaluation, nothing per sample is read
+    a.kept_mask = ctx->d_count_mask;    // NULL with all samples kept or an identity list
+    a.kept_rank = ctx->d_scount_rank;
+    a.code_values = d_code_values;
+    a.design = d_design;
+    a.x_stride = x_stride;
+    a.n_cov = n_cov;
+    a.y = d_y;
+    a.start = d_start;
+    a.max_iter = max_iter;
+    a.tol = tol;
+    a.coef = d_coef;
+    a.c_stride = c_stride;
+    a.se = d_se;
+    a.status = d_status;
+    if (shape == PGENHIP_LOGIT_GENERAL) HIP_TRY(launch_gt_logit_general(a, ctx->tune.logit_blocks, ctx->num_cus, ctx->stream));
+    else HIP_TRY(launch_gt_logit_fast(a, ctx->tune.logit_blocks, ctx->num_cus, ctx->stream));   // AUTO: FAST applies to every shape
+    return PGENHIP_OK;
+}
+
+int pgenhip_variant_logistic(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
+                             uint32_t n_variants, const double *d_code_values, const double *d_design, uint64_t x_stride,
+                             uint32_t n_cov, const double *d_y, const double *d_start, uint32_t max_iter, double tol,
+                             double *d_coef, uint64_t c_stride, double *d_se, uint32_t *d_status, uint32_t flags)
+{
+    return variant_logistic_core(ctx, d_records, record_stride, d_variant_idx, nullptr, n_variants, d_code_values, d_design, x_stride, n_cov,
+                                 d_y, d_start, max_iter, tol, d_coef, c_stride, d_se, d_status, flags);
+}
+
+int pgenhip_variant_logistic_at(pgenhip_ctx *ctx, const void *d_base, const uint64_t *d_record_off, uint32_t n_variants,
+                                const double *d_code_values, const double *d_design, uint64_t x_stride, uint32_t n_cov,
+                                const double *d_y, const double *d_start, uint32_t max_iter, double tol, double *d_coef,
+                                uint64_t c_stride, double *d_se, uint32_t *d_status, uint32_t flags)
+{
+    if (const int rc = check_record_off(ctx, d_record_off, n_variants)) return rc;
+    return variant_logistic_core(ctx, d_base, 0, nullptr, d_record_off, n_variants, d_code_values, d_design, x_stride, n_cov, d_y, d_start,
+                                 max_iter, tol, d_coef, c_stride, d_se, d_status, flags);
+}
+
 static int decode_matrix_core(pgenhip_ctx *ctx, const void *d_records, uint64_t record_stride, const uint32_t *d_variant_idx,
                               const uint64_t *d_record_off, uint32_t n_variants, void *d_out, uint64_t out_stride, uint32_t elem_bytes,
                               const void *code_values, uint32_t flags)
@@ -1238,6 +1307,7 @@ int pgenhip_tune(pgenhip_ctx *ctx, uint32_t knob, int32_t value)
         case PGENHIP_KNOB_PRUNE_BLOCKS: t.prune_blocks = value > 0 ? value : d.prune_blocks; break;
         case PGENHIP_KNOB_SPAIR_SLICES: t.spair_slices = value > 0 ? value : d.spair_slices; break;
         case PGENHIP_KNOB_VSUM_BLOCKS: t.vsum_blocks = value > 0 ? value : d.vsum_blocks; break;
+        case PGENHIP_KNOB_LOGIT_BLOCKS: t.logit_blocks = value > 0 ? value : d.logit_blocks; break;
         case PGENHIP_KNOB_GRAM_SLICES: t.gram_slices = value > 0 ? value : d.gram_slices; break;
         case PGENHIP_KNOB_GAPPLY_SAMPLE_SLICES: t.gapply_sample_slices = value > 0 ? value : d.gapply_sample_slices; break;
         case PGENHIP_KNOB_GAPPLY_ROW_SLICES: t.gapply_row_slices = value > 0 ? value : d.gapply_row_slices; break;

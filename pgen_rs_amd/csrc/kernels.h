@@ -64,6 +64,7 @@ struct Tuning {
     int prune_blocks = 0;          // prune resolve kernels: grid size in blocks (0 = by shape); for BLOCK thereby the rows of a range
     int spair_slices = 0;          // pairwise sample tables: row ranges per sample tile (0 = by shape: the chip's resident blocks, at least 256 rows each)
     int vsum_blocks = 0;           // per-variant sums: grid size in blocks (0 = by shape, capped per CU)
+    int logit_blocks = 0;          // per-variant logistic regression: grid size in blocks (0 = by shape, capped per CU)
     int gram_slices = 0;           // sample Gram matrix: row ranges per rank tile (0 = by shape: the chip's resident blocks, at least 256 rows each)
     int gapply_sample_slices = 0;  // Gram product, P pass: sample ranges per row tile (0 = by shape: the chip's resident blocks, at least 4096 samples each)
     int gapply_row_slices = 0;     // Gram product, Y pass: row ranges per sample tile (0 = by shape: the chip's resident blocks, at least 256 rows each)
@@ -290,6 +291,30 @@ struct GapplyArgs : RowSource {
 // tiles / grid / slices of each pass: plan::gapply::plan of the same shape
 hipError_t launch_gt_gapply_p(const GapplyArgs &a, bool mfma, uint64_t tiles, uint32_t grid_tiles, uint32_t slices, hipStream_t stream);
 hipError_t launch_gt_gapply_y(const GapplyArgs &a, bool mfma, uint64_t tiles, uint32_t grid_tiles, uint32_t slices, hipStream_t stream);
+
+// Per-variant logistic regression (gt_logit.hip): for every selected row j the Newton iteration of include/pgen_hip.h on
+// X = [design, t_j[code]] over the kept samples whose table entry is not NaN; coefficients, the genotype's standard error and a
+// status word per row.
+struct LogitArgs : RowSource {
+    const uint8_t *kept_mask;     // device or nullptr (all samples): the ctx's count mask (CountArgs::kept_mask)
+    const uint32_t *kept_rank;    // device, with kept_mask: kept samples before each 64-sample chunk
+    const double *code_values;    // device, 8-byte aligned, four per selected row
+    const double *design;         // device, 8-byte aligned, K x n_cov
+    uint64_t x_stride;            // doubles between the design rows
+    uint32_t n_cov;               // 1 .. 15
+    const double *y;              // device, K values
+    const double *start;          // device, n_cov values
+    uint32_t max_iter;            // 1 .. 64
+    double tol;
+    double *coef;                 // device, n_variants x (n_cov + 1)
+    uint64_t c_stride;            // doubles between the coefficient rows
+    double *se;                   // device, n_variants
+    uint32_t *status;             // device, n_variants
+};
+// sample_count == 0 in the arguments means "no sample is included" (K == 0): every row ends SINGULAR at its first evaluation.
+// blocks: forced grid size (0 = by shape; tests force small grids to walk the grid-stride loops)
+hipError_t launch_gt_logit_general(const LogitArgs &a, int blocks, int num_cus, hipStream_t stream);
+hipError_t launch_gt_logit_fast(const LogitArgs &a, int blocks, int num_cus, hipStream_t stream);
 
 // Packed records (gt_pack.hip): row j = the mode-0x02 record of the K kept samples of selected row j, ceil(K / 4) bytes at
 // out + j * out_stride, every code sent through a 2-bit -> 2-bit map, pad bits zero.

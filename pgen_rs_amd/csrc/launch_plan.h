@@ -1,11 +1,11 @@
 // launch_plan.h — the launch plans of the analysis kernels (gt_count, gt_scount, gt_score, gt_vsum, gt_matrix, gt_pair, gt_pack,
-// gt_spair, gt_gram, gt_gapply, gt_parse, gt_join, gt_prune) and the launch rule of the stream kernel (gt_wide): lanes per row, tiles, row ranges ("slices"), grid
+// gt_spair, gt_gram, gt_gapply, gt_parse, gt_join, gt_prune, gt_logit) and the launch rule of the stream kernel (gt_wide): lanes per row, tiles, row ranges ("slices"), grid
 // caps, store policy and write fronts, as functions of scalars; and the emit path (namespace emit): the shapes each emit kernel takes,
 // AUTO's chains and the forced kernel ids, the chunks of the two passes, and the launch plans of the segment, row-owner and pick
 // kernels.  The single statement
 // of every plan: capi.hip and the launchers call it, the kernels take their constants and their row ranges from it, and the tests compile this
 // header for the host (tests/plan_probe.cpp, tests/gapply_plan_probe.cpp, tests/wide_plan_probe.cpp, tests/emit_plan_probe.cpp,
-// tests/parse_plan_probe.cpp, tests/join_plan_probe.cpp, tests/prune_plan_probe.cpp) and run it.
+// tests/parse_plan_probe.cpp, tests/join_plan_probe.cpp, tests/prune_plan_probe.cpp, tests/logit_plan_probe.cpp) and run it.
 // Plain C++17 on purpose: no HIP header, no kernel argument struct (emit::Shape is a struct of scalars).
 #pragma once
 #include <stdint.h>
@@ -1211,5 +1211,38 @@ PGENHIP_PLAN_HD inline BlockPlan block_plan(uint64_t n_rows, int num_cus, int bl
 PGENHIP_PLAN_HD constexpr bool auto_block(uint64_t /*n_rows*/, uint32_t /*window*/) { return true; }
 
 }  // namespace prune
+
+// ---- gt_logit: per-variant logistic regression -------------------------------------------------------------------------------------
+namespace logit {
+
+constexpr int kThreads = 256;
+constexpr uint32_t kWaves = kThreads / 64;
+constexpr uint32_t kMaxP = 16;            // design columns with the genotype: PGENHIP_LOGIT_MAX_COVARIATES + 1
+constexpr uint32_t kSums = kMaxP * (kMaxP + 1u) / 2u + kMaxP;   // the lower half of H, then the gradient
+constexpr uint32_t kBlocksPerCu = 8;      // grid cap; the FAST kernel's registers leave fewer resident, the rest queue
+
+// FAST is compiled for p = n_cov + 1 rounded up to a bucket: the accumulators of a lane are bucket * (bucket + 1) / 2 + bucket
+// FP64 registers.  At 16 they do not fit one wave's 256 VGPRs at all, and at 12 the compiler fits them only with copies through
+// AGPRs and one wave per SIMD, so above 8 the rows of H are dealt to two waves
+PGENHIP_PLAN_HD constexpr uint32_t bucket(uint32_t p) { return p <= 4u ? 4u : p <= 8u ? 8u : p <= 12u ? 12u : 16u; }
+PGENHIP_PLAN_HD constexpr uint32_t waves_per_row(uint32_t bucket) { return bucket > 8u ? 2u : 1u; }
+// rows a block carries through the iterations together (they share every design value through the CU's L1)
+PGENHIP_PLAN_HD constexpr uint32_t group_rows(uint32_t bucket) { return kWaves / waves_per_row(bucket); }
+PGENHIP_PLAN_HD constexpr uint64_t groups(uint64_t n_variants, uint32_t bucket) { return (n_variants + group_rows(bucket) - 1u) / group_rows(bucket); }
+// which of a row's waves owns row a of H (and entry a of the gradient): rows 0, 3, 4, 7, ... and 1, 2, 5, 6, ... hold the same number
+// of entries of the lower half
+PGENHIP_PLAN_HD constexpr uint32_t row_part(uint32_t a, uint32_t waves) { return waves == 1u ? 0u : (((a & 3u) == 0u || (a & 3u) == 3u) ? 0u : 1u); }
+// FP64 FMAs per included sample that the sums themselves take (the issue bound: 4 cycles each per 64 samples)
+PGENHIP_PLAN_HD constexpr uint32_t sum_fmas(uint32_t p) { return p * (p + 1u) / 2u + p; }
+
+// blocks: forced grid size (0 = by shape)
+PGENHIP_PLAN_HD inline uint32_t fast_grid(uint32_t n_variants, uint32_t p, int num_cus, int blocks)
+{
+    return grid_blocks(groups(n_variants, bucket(p)), kBlocksPerCu, num_cus, blocks);
+}
+// GENERAL: a block per row, the rest by grid stride
+PGENHIP_PLAN_HD inline uint32_t general_grid(uint32_t n_variants, int num_cus, int blocks) { return grid_blocks(n_variants, kBlocksPerCu, num_cus, blocks); }
+
+}  // namespace logit
 
 }  // namespace pgenhip::plan

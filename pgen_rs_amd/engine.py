@@ -543,6 +543,103 @@ class GtEngine:
             raise ValueError("out must be a float64 tensor with >= n_variants * C * 4 entries")
         return out.view(-1)
 
+    # -- per-variant logistic regression ----------------------------------------------------------
+    def variant_logistic(
+        self,
+        records: torch.Tensor,
+        code_values: torch.Tensor,
+        design: torch.Tensor,
+        y: torch.Tensor,
+        start: torch.Tensor,
+        *,
+        max_iter: int = 25,
+        tol: float = 1e-9,
+        record_stride: Optional[int] = None,
+        variant_idx: Optional[torch.Tensor] = None,
+        coef: Optional[torch.Tensor] = None,
+        se: Optional[torch.Tensor] = None,
+        status: Optional[torch.Tensor] = None,
+        flags: int = 0,
+        n_variants: Optional[int] = None,
+        records_offset: int = 0,
+    ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Per-variant logistic regression of ``y`` on ``[design, g]``, ``g = code_values[j, code]``: the Newton iteration that
+        include/pgen_hip.h fixes (``pgenhip_variant_logistic``).  Returns ``(coef, se, status)``: a ``(n_variants, n_cov + 1)``
+        float64 tensor (the covariates' coefficients, then the genotype's), the genotype's standard errors ``(n_variants,)``
+        float64 (NaN unless converged) and the status words ``(n_variants,)`` int32 (evaluations in the low 8 bits and one of
+        ``_capi.LOGIT_CONVERGED`` / ``NOT_CONVERGED`` / ``SINGULAR``).
+
+        ``code_values``: float64 CUDA tensor ``(n_variants, 4)``, contiguous; a NaN entry leaves the samples with that code out of
+        the row's fit.  ``design``: float64 CUDA tensor ``(K, n_cov)`` or ``(K,)``, n_cov <= 15, contiguous along the columns (its
+        row stride is taken from the tensor; the intercept is a column of it).  ``y``: float64, K values in [0, 1].  ``start``:
+        float64, n_cov coefficients of the null model.  Rows are selected as in ``variant_sums``.  ``coef`` / ``se`` / ``status``:
+        optional outputs (written from their first element, ``coef`` with rows of n_cov + 1).  ``flags``: a forced shape
+        (``_capi.LOGIT_*``)."""
+        x_stride, n_cov = self._logit_inputs(design, y, start)
+        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
+        coef, se, status = self._logit_out(code_values, n_variants, n_cov, coef, se, status)
+        check(
+            lib.pgenhip_variant_logistic(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants,
+                                         _ptr(code_values), _ptr(design), x_stride, n_cov, _ptr(y), _ptr(start), max_iter, tol,
+                                         _ptr(coef), n_cov + 1, _ptr(se), _ptr(status), flags),
+            "pgenhip_variant_logistic",
+        )
+        return coef[: n_variants * (n_cov + 1)].view(n_variants, n_cov + 1), se[:n_variants], status[:n_variants]
+
+    def variant_logistic_at(self, base: torch.Tensor, record_off: torch.Tensor, code_values: torch.Tensor, design: torch.Tensor,
+                            y: torch.Tensor, start: torch.Tensor, *, max_iter: int = 25, tol: float = 1e-9,
+                            coef: Optional[torch.Tensor] = None, se: Optional[torch.Tensor] = None,
+                            status: Optional[torch.Tensor] = None, flags: int = 0,
+                            n_variants: Optional[int] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``variant_logistic`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
+        x_stride, n_cov = self._logit_inputs(design, y, start)
+        n_variants = self._rows_at(base, record_off, n_variants)
+        coef, se, status = self._logit_out(code_values, n_variants, n_cov, coef, se, status)
+        check(
+            lib.pgenhip_variant_logistic_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, _ptr(code_values), _ptr(design),
+                                            x_stride, n_cov, _ptr(y), _ptr(start), max_iter, tol, _ptr(coef), n_cov + 1, _ptr(se),
+                                            _ptr(status), flags),
+            "pgenhip_variant_logistic_at",
+        )
+        return coef[: n_variants * (n_cov + 1)].view(n_variants, n_cov + 1), se[:n_variants], status[:n_variants]
+
+    def _logit_inputs(self, design: torch.Tensor, y: torch.Tensor, start: torch.Tensor) -> tuple[int, int]:
+        """Checks ``design``, ``y`` and ``start`` and returns ``(x_stride, n_cov)``."""
+        for t, name in ((design, "design"), (y, "y"), (start, "start")):
+            if not t.is_cuda or t.device.index != self.device:
+                raise ValueError(f"{name} must live on cuda:{self.device}")
+            if t.dtype != torch.float64:
+                raise ValueError(f"{name} must be a float64 tensor")
+        if design.dim() not in (1, 2):
+            raise ValueError("design must be a float64 tensor of shape (K, n_cov) or (K,)")
+        n_cov = design.shape[1] if design.dim() == 2 else 1
+        if design.shape[0] < self.kept_count or y.numel() < self.kept_count:
+            raise ValueError("design or y has fewer than K rows")
+        if design.dim() == 2 and n_cov > 1 and design.shape[0] > 0 and design.stride(1) != 1:
+            raise ValueError("design must be contiguous along its columns")
+        if not y.is_contiguous() or not start.is_contiguous() or start.numel() < n_cov:
+            raise ValueError("y and start must be contiguous, start with >= n_cov entries")
+        x_stride = design.stride(0) if design.shape[0] > 1 else n_cov
+        return int(x_stride), int(n_cov)
+
+    def _logit_out(self, code_values: torch.Tensor, n_variants: int, n_cov: int, coef: Optional[torch.Tensor],
+                   se: Optional[torch.Tensor], status: Optional[torch.Tensor]) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        self._check_dev(code_values, "code_values")
+        if code_values.dtype != torch.float64 or code_values.numel() < 4 * n_variants or not code_values.is_contiguous():
+            raise ValueError("code_values must be a contiguous float64 tensor of shape (n_variants, 4)")
+        outs = []
+        for t, name, dtype, need in ((coef, "coef", torch.float64, n_variants * (n_cov + 1)), (se, "se", torch.float64, n_variants),
+                                     (status, "status", torch.int32, n_variants)):
+            if t is None:
+                t = torch.empty(max(need, 1), dtype=dtype, device=self.torch_device)
+            else:
+                self._check_dev(t, name)
+                if t.dtype != dtype or t.numel() < need or not t.is_contiguous():
+                    raise ValueError(f"{name} must be a contiguous {dtype} tensor with >= {need} entries")
+                t = t.view(-1)
+            outs.append(t)
+        return outs[0], outs[1], outs[2]
+
     # -- numeric genotype matrix ---------------------------------------------------------------
     def decode_matrix(
         self,

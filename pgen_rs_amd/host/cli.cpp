@@ -103,7 +103,7 @@ const char *kUsage =
     "  freq    Per-variant genotype counts of the kept samples, outputting to stdout\n"
     "  sample-counts  Per-sample genotype counts over the kept variants, outputting to stdout\n"
     "  score   Polygenic scores of the kept samples from a weights file, outputting to stdout\n"
-    "  assoc   Linear regression of quantitative phenotypes on every kept variant, outputting to stdout\n"
+    "  assoc   Linear regression of quantitative phenotypes (--logistic: logistic regression of case/control phenotypes) on every kept variant, outputting to stdout\n"
     "  matrix  Numeric genotype matrix of the kept variants and samples, outputting to a NumPy .npy file\n"
     "  ld      Pairwise r^2 of the kept variants inside a sliding window, outputting to stdout\n"
     "  prune   LD pruning of the kept variants: writes OUT.prune.in / OUT.prune.out, and with --export the pruned fileset\n"
@@ -140,6 +140,17 @@ const char *kUsage =
     "       (NA where the fit is degenerate).  A missing call counts as the variant's mean dosage over the called samples (mean\n"
     "       imputation); plink2 --glm drops the sample for that variant instead, so no digit parity with plink2 is claimed\n"
     "assoc  --p-of <T_STAT> <DF>   the two-sided Student t P value of one statistic (no fileset, no device)\n"
+    "assoc --logistic <PFILE_PREFIX> --pheno <FILE> [--pheno-name <A,B,...>] [--covar <FILE>] [--no-mean-imputation] [--max-iter <I>] [--tol <X>] [...as assoc]\n"
+    "       case/control phenotypes: every value of a column 1 or 2 with a 2 present (control / case), or every value 0 or 1 (0 control).  Per\n"
+    "       variant and phenotype a logistic regression on the ALT dosage with an intercept and up to 14 covariates, fitted on the device by\n"
+    "       Newton's iteration from the null model, at most I evaluations (default 25, 1 .. 64), converged when no coefficient moves by more\n"
+    "       than X (default 1e-9): CHROM POS ID REF ALT A1 PHENO OBS_CT MISS_CT A1_FREQ BETA SE Z_STAT P ITER STATUS.  BETA is the log-odds per\n"
+    "       ALT allele, P = erfc(|Z| / sqrt 2) the Wald test; STATUS is . / NOT_CONVERGED / SINGULAR and BETA SE Z_STAT P are NA unless the fit\n"
+    "       converged.  A missing call counts as the variant's mean dosage (--no-mean-imputation: the sample is dropped for that variant, as\n"
+    "       plink2 does, and OBS_CT excludes it).  Not built: a Firth fallback, step halving (a separated variant ends NOT_CONVERGED or\n"
+    "       SINGULAR), likelihood-ratio tests, per-genotype case/control counts, interaction terms, more than 14 covariates; no digit parity\n"
+    "       with plink2 --glm is claimed\n"
+    "assoc  --p-of-z <Z_STAT>      the two-sided normal (Wald) P value of one statistic (no fileset, no device)\n"
     "matrix <PFILE_PREFIX> [--include-var <VAR_QUERY>] [--include-sam <SAM_QUERY>] [--dtype i8|f16|f32] [--missing <X>] [--sample-major]\n"
     "       -o, --out <OUT_FILE.npy> [--gpus <N>] [--shards <S>] [--block-mib <M>] [--read-threads <T>] [--filter-threads <T>] [--stats]\n"
     "       NumPy .npy (version 1.0, C order) of shape (variants kept, samples kept), or (samples, variants) with --sample-major:\n"
@@ -552,7 +563,17 @@ int main(int argc, char **argv)
                 std::printf("%.17g\n", stats::student_t_two_sided_p(t, df));
                 return 0;
             }
-            const SelectionArgs a(argc, argv, {{"pheno", 0}, {"pheno-name", 0}, {"covar", 0}}, {});
+            if (argc >= 3 && std::string(argv[2]) == "--p-of-z") {
+                char *e1 = nullptr;
+                const double z = argc == 4 ? std::strtod(argv[3], &e1) : 0.0;
+                if (argc != 4 || *argv[3] == '\0' || *e1 != '\0') usage_error("--p-of-z takes one statistic");
+                std::printf("%.17g\n", stats::wald_p(z));
+                return 0;
+            }
+            const SelectionArgs a(argc, argv, {{"pheno", 0}, {"pheno-name", 0}, {"covar", 0}, {"max-iter", 0}, {"tol", 0}}, {{"logistic", 0}, {"no-mean-imputation", 0}});
+            if (!a.has("logistic"))   // the options of the logistic fit do not exist without it
+                for (const char *name : {"no-mean-imputation", "max-iter", "tol"})
+                    if (a.has(name)) usage_error(std::string("unexpected argument '--") + name + "' found");
             if (!a.has("pheno") || a.get("pheno")->empty()) usage_error("the following required arguments were not provided: --pheno <FILE>");
             if (a.has("covar") && a.get("covar")->empty()) usage_error("a value is required for '--covar <FILE>'");
             AssocOptions ao;
@@ -570,9 +591,22 @@ int main(int argc, char **argv)
                     name.clear();
                 }
             }
+            if (a.has("logistic")) {
+                ao.logistic = true;
+                ao.mean_imputation = !a.has("no-mean-imputation");
+                if (a.has("max-iter")) ao.max_iter = (uint32_t)unsigned_value(*a.get("max-iter"), "max-iter", "I", 1, PGENHIP_LOGIT_MAX_ITER, "a number of evaluations from 1 to 64");
+                if (a.has("tol")) {
+                    char *end = nullptr;
+                    ao.tol = std::strtod(a.get("tol")->c_str(), &end);
+                    if (a.get("tol")->empty() || *end != '\0' || !(ao.tol >= 0.0) || std::isinf(ao.tol)) usage_error("invalid value '" + *a.get("tol") + "' for '--tol <X>': not a finite number >= 0");
+                }
+            }
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
             const OutputStats st = pfile.output_assoc(a.get("include-sam"), a.get("include-var"), ao, a.get("out").value_or(""), output_options(a));
-            if (a.has("stats")) std::fprintf(stderr, "{\"samples_dropped\": %llu}\n", (unsigned long long)st.assoc_dropped);
+            if (a.has("stats") && ao.logistic)
+                std::fprintf(stderr, "{\"samples_dropped\": %llu, \"converged\": %llu, \"not_converged\": %llu, \"singular\": %llu}\n", (unsigned long long)st.assoc_dropped,
+                             (unsigned long long)st.logit_converged, (unsigned long long)st.logit_not_converged, (unsigned long long)st.logit_singular);
+            else if (a.has("stats")) std::fprintf(stderr, "{\"samples_dropped\": %llu}\n", (unsigned long long)st.assoc_dropped);
             return a.done(st, t_main);
         }
         if (cmd == "matrix") {

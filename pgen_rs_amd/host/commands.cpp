@@ -132,6 +132,59 @@ struct AssocCounter : Counter {
     }
 };
 
+// assoc --logistic's counter: per block the rows' genotype counts come back at once (a row's code table holds its mean dosage), the
+// tables go up, and one pgenhip_variant_logistic per phenotype follows; the genotype's coefficient and standard error and the status
+// word of every (phenotype, row) come back block by block.  The design (n x m), the 0 / 1 phenotypes (P x n) and the null models'
+// coefficients (P x m) are uploaded once per shard.
+struct LogitCounter : Counter {
+    size_t P, m, n, bv;
+    const AssocOptions &ao;
+    std::vector<uint32_t> &counts;    // 4 per kept variant
+    std::vector<double> &beta, &se;   // P per kept variant
+    std::vector<uint32_t> &status;    // P per kept variant
+    const double *d_design, *d_y, *d_start;
+    uint32_t *d_gc, *h_gc;
+    double *d_tab, *h_tab;            // 4 per row
+    double *d_coef, *h_coef;          // P x bv x (m + 1)
+    double *d_se, *h_se;              // P x bv
+    uint32_t *d_status, *h_status;    // P x bv
+    void launch(const BlockRows &b, size_t, uint32_t nv, uint32_t, bool) const
+    {
+        pgenhip_ctx *ctx = b.ctx;
+        genotype_counts(b, nv, d_gc);
+        check(pgenhip_memcpy_d2h(ctx, h_gc, d_gc, (size_t)nv * 16), "D2H counts");
+        check(pgenhip_wait(ctx), "pgenhip_wait");
+        for (uint32_t j = 0; j < nv; j++) {
+            double *t = h_tab + 4 * (size_t)j;
+            t[0] = 0.0, t[1] = 1.0, t[2] = 2.0;
+            t[3] = ao.mean_imputation ? stats::mean_dosage(h_gc + 4 * j) : std::nan("");
+        }
+        check(pgenhip_memcpy_h2d(ctx, d_tab, h_tab, (size_t)nv * 4 * sizeof(double)), "H2D code tables");
+        for (size_t p = 0; p < P; p++)
+            launch_rows(b, NAMED(pgenhip_variant_logistic), NAMED(pgenhip_variant_logistic_at), nv, d_tab, d_design, (uint64_t)m, (uint32_t)m,
+                        d_y + p * n, d_start + p * m, ao.max_iter, ao.tol, d_coef + p * bv * (m + 1), (uint64_t)(m + 1), d_se + p * bv,
+                        d_status + p * bv, PGENHIP_LOGIT_AUTO);
+    }
+    void copy(pgenhip_ctx *ctx, size_t nv) const
+    {
+        for (size_t p = 0; p < P; p++) {
+            check(pgenhip_memcpy_d2h(ctx, h_coef + p * bv * (m + 1), d_coef + p * bv * (m + 1), nv * (m + 1) * sizeof(double)), "D2H coefficients");
+            check(pgenhip_memcpy_d2h(ctx, h_se + p * bv, d_se + p * bv, nv * sizeof(double)), "D2H standard errors");
+            check(pgenhip_memcpy_d2h(ctx, h_status + p * bv, d_status + p * bv, nv * sizeof(uint32_t)), "D2H status words");
+        }
+    }
+    void collect(size_t b0, size_t nv) const
+    {
+        std::memcpy(counts.data() + 4 * b0, h_gc, nv * 16);
+        for (size_t p = 0; p < P; p++)
+            for (size_t j = 0; j < nv; j++) {
+                beta[(b0 + j) * P + p] = h_coef[(p * bv + j) * (m + 1) + m];
+                se[(b0 + j) * P + p] = h_se[p * bv + j];
+                status[(b0 + j) * P + p] = h_status[p * bv + j];
+            }
+    }
+};
+
 // matrix's "counter": every block is decoded into one device buffer, copied back and written to its place in the .npy file.
 // Variant-major: a block is nv consecutive rows of the file, one pwrite.  Sample-major: a block is a column band, K pieces of
 // nv elements, written from a few threads.
@@ -663,6 +716,16 @@ OutputStats Pfile::output_assoc(const std::optional<std::string> &sam_query, con
         }
     }
     const size_t P = pcol.size(), ncov = cv.names.size(), m = 1 + ncov, C = m + P;
+    std::vector<stats::BinaryCoding> coding(P, stats::BinaryCoding::kNone);
+    if (aopt.logistic) {
+        if (m > PGENHIP_LOGIT_MAX_COVARIATES)
+            throw PfileError(aopt.covar_file + ": " + std::to_string(ncov) + " covariates; assoc --logistic takes " + std::to_string(PGENHIP_LOGIT_MAX_COVARIATES - 1) + " at most");
+        for (size_t p = 0; p < P; p++) {
+            coding[p] = stats::binary_coding(ph.x.data() + pcol[p], ph.iids.size(), ph.names.size());
+            if (coding[p] == stats::BinaryCoding::kNone)
+                throw PfileError(aopt.pheno_file + ": phenotype " + ph.names[pcol[p]] + " is not a case/control column (every value 1 or 2 with a 2 present, or every value 0 or 1)");
+        }
+    }
 
     Selection sel = select(sam_query, var_query, opt.filter_threads);
     const size_t iid = iid_column(*this, sel.sam_header);
@@ -694,6 +757,98 @@ OutputStats Pfile::output_assoc(const std::optional<std::string> &sam_query, con
     if (n < m + 2)
         throw PfileError("too few samples: " + std::to_string(n) + " complete samples leave " + std::to_string((long long)n - (long long)m - 1) +
                          " degrees of freedom for an intercept, " + std::to_string(ncov) + " covariates and the genotype");
+
+    if (aopt.logistic) {
+        // the design, n x m: Q's columns scaled by sqrt(n); the phenotypes as 0 / 1, P x n; the null models, P x m
+        std::vector<double> xq, y01(P * n), start(P * m);
+        if (const size_t c = stats::logistic_design(x, n, ncov, xq); c != stats::kNoColumn)
+            throw PfileError(aopt.covar_file + ": covariate " + (c ? cv.names[c - 1] : std::string("(intercept)")) + " is collinear with the intercept and the covariates before it");
+        for (size_t p = 0; p < P; p++) {
+            size_t cases = 0;
+            for (size_t k = 0; k < n; k++) cases += (y01[p * n + k] = stats::binary_value(y[k * P + p], coding[p])) != 0.0;
+            if (cases == 0 || cases == n)
+                throw PfileError(aopt.pheno_file + ": phenotype " + ph.names[pcol[p]] + " has no " + (cases ? "control" : "case") + " among the " + std::to_string(n) + " complete samples");
+            const stats::LogisticNull fit = stats::logistic_null(xq, n, m, y01.data() + p * n, (int)PGENHIP_LOGIT_MAX_ITER, 1e-12);
+            if (!fit.converged)
+                throw PfileError(aopt.pheno_file + ": the null model of phenotype " + ph.names[pcol[p]] + " (intercept and covariates alone) did not converge: the covariates separate it");
+            std::copy(fit.beta.begin(), fit.beta.end(), start.begin() + p * m);
+        }
+        st.seconds_filter = now_s() - t0;
+
+        const KeptSamples kept = check_selection(*this, sel);
+        const size_t V = sel.var_idx_rcds.size();
+        st.variants = V;
+        st.samples_kept = n;
+        std::vector<uint32_t> counts(4 * V, 0u), status(V * P, 0u);
+        std::vector<double> beta(V * P, 0.0), se(V * P, 0.0);
+        const double t_body = now_s();
+        if (V != 0) {   // else the header alone and no device is touched
+            count_blocks(*this, sel.var_idx_rcds, kept, opt, "no HIP device: the assoc path has no CPU fallback", st, [&](DeviceCtx &ctx, uint64_t bv) {
+                const size_t b = (size_t)bv;
+                double *d_design = ctx.device<double>(n * m * sizeof(double), "device design");
+                double *d_y = ctx.device<double>(P * n * sizeof(double), "device phenotypes");
+                double *d_start = ctx.device<double>(P * m * sizeof(double), "device null models");
+                check(pgenhip_memcpy_h2d(ctx.get(), d_design, xq.data(), n * m * sizeof(double)), "H2D design");
+                check(pgenhip_memcpy_h2d(ctx.get(), d_y, y01.data(), P * n * sizeof(double)), "H2D phenotypes");
+                check(pgenhip_memcpy_h2d(ctx.get(), d_start, start.data(), P * m * sizeof(double)), "H2D null models");
+                check(pgenhip_wait(ctx.get()), "pgenhip_wait");
+                return LogitCounter{{}, P, m, n, b, aopt, counts, beta, se, status, d_design, d_y, d_start,
+                                    ctx.device<uint32_t>(16 * b, "device variant counts"), ctx.pinned<uint32_t>(16 * b, "pinned variant counts"),
+                                    ctx.device<double>(b * 4 * sizeof(double), "device code tables"), ctx.pinned<double>(b * 4 * sizeof(double), "pinned code tables"),
+                                    ctx.device<double>(P * b * (m + 1) * sizeof(double), "device coefficients"), ctx.pinned<double>(P * b * (m + 1) * sizeof(double), "pinned coefficients"),
+                                    ctx.device<double>(P * b * sizeof(double), "device standard errors"), ctx.pinned<double>(P * b * sizeof(double), "pinned standard errors"),
+                                    ctx.device<uint32_t>(P * b * sizeof(uint32_t), "device status words"), ctx.pinned<uint32_t>(P * b * sizeof(uint32_t), "pinned status words")};
+            });
+        }
+
+        std::string text = "#CHROM\tPOS\tID\tREF\tALT\tA1\tPHENO\tOBS_CT\tMISS_CT\tA1_FREQ\tBETA\tSE\tZ_STAT\tP\tITER\tSTATUS\n";
+        st.header_bytes = text.size();
+        char buf[64];
+        auto number = [&](double v) {
+            std::snprintf(buf, sizeof buf, "%.12g", v);
+            text += '\t';
+            text += buf;
+        };
+        for (size_t j = 0; j < V; j++) {
+            const StringRecord &vr = sel.var_idx_rcds[j].second;
+            const uint32_t *ct = counts.data() + 4 * j;
+            const bool called = (uint64_t)ct[0] + ct[1] + ct[2] != 0;
+            for (size_t p = 0; p < P; p++) {
+                for (int c = 0; c < 5; c++) {
+                    if (c) text += '\t';
+                    text += vr.at(col[c]);
+                }
+                text += '\t';
+                text += vr.at(col[4]);
+                text += '\t';
+                text += ph.names[pcol[p]];
+                text += '\t';
+                append_u64(text, aopt.mean_imputation ? n : n - ct[3]);
+                text += '\t';
+                append_u64(text, ct[3]);
+                if (called) number(0.5 * stats::mean_dosage(ct));
+                else text += "\tNA";
+                const uint32_t word = status[j * P + p];
+                const bool converged = (word & PGENHIP_LOGIT_CONVERGED) != 0u;
+                if (converged) {
+                    const double b = beta[j * P + p], s = se[j * P + p], z = b / s;
+                    number(b);
+                    number(s);
+                    number(z);
+                    number(stats::wald_p(z));
+                    st.logit_converged++;
+                } else {
+                    text += "\tNA\tNA\tNA\tNA";
+                    ++((word & PGENHIP_LOGIT_SINGULAR) ? st.logit_singular : st.logit_not_converged);
+                }
+                text += '\t';
+                append_u64(text, word & 0xFFu);
+                text += converged ? "\t.\n" : (word & PGENHIP_LOGIT_SINGULAR) ? "\tSINGULAR\n" : "\tNOT_CONVERGED\n";
+            }
+        }
+        finish_text(st, text, filename, t_body);
+        return st;
+    }
 
     // the value columns, n x C: Q's m columns, then the residualised phenotypes
     stats::AssocDesign design;

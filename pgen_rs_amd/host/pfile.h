@@ -133,6 +133,10 @@ struct AssocOptions {
     std::string pheno_file;                 // --pheno: IID, then one quantitative phenotype per column
     std::vector<std::string> pheno_names;   // --pheno-name: the columns used (empty: all)
     std::string covar_file;                 // --covar: IID, then one covariate per column (empty: the intercept alone)
+    bool logistic = false;                  // --logistic: case/control phenotypes, a logistic regression per variant on the device
+    bool mean_imputation = true;            // --logistic: a missing call counts as the variant's mean dosage (else the sample is dropped for that variant)
+    uint32_t max_iter = 25;                 // --logistic: evaluations per variant at most (1 .. PGENHIP_LOGIT_MAX_ITER)
+    double tol = 1e-9;                      // --logistic: a fit has converged when no coefficient moves by more
 };
 
 // A `assoc` pheno / covar file: tab-separated, a header line (a leading '#' allowed), then one row per sample: IID, one value per
@@ -176,6 +180,7 @@ struct OutputStats {
     double seconds_filter = 0, seconds_body = 0, seconds_kernel = 0;
     uint64_t score_matched = 0, score_flipped = 0, score_skipped = 0;            // `score`: weights rows used, of them REF-effect rows, rows not used
     uint64_t assoc_dropped = 0;                                                  // `assoc`: kept samples dropped for a missing phenotype or covariate
+    uint64_t logit_converged = 0, logit_not_converged = 0, logit_singular = 0;   // `assoc --logistic`: output lines per status
     uint64_t grm_skipped = 0;                                                    // `grm`: kept variants that add nothing (no call, or monomorphic among the kept samples)
     uint64_t pca_skipped = 0, pca_passes = 0;                                    // `pca`: kept variants that add nothing; passes over the records
     double pca_residual = 0;                                                     // `pca`: max over the written components of |M u - lambda u| / lambda_1 at the last pass
@@ -284,6 +289,13 @@ class Pfile {
     // phenotype: CHROM POS ID REF ALT A1 PHENO OBS_CT MISS_CT A1_FREQ BETA SE T_STAT P (%.12g; NA where called == 0, denom <=
     // 1e-12 gg or rss <= 0).  Fewer than m + 2 complete samples or collinear covariates: an error before any device is touched.
     // No kept variant: the header alone.  filename empty: stdout.
+    // With aopt.logistic the phenotypes are case/control columns (1 / 2 with a 2 present, or 0 / 1; another column, or one without a
+    // case or without a control among the complete cases, is an error that names it) and every line is a logistic fit: the host
+    // scales Q by sqrt(n) into the design, fits every phenotype's null model (stats.h), and per block pgenhip_genotype_counts gives
+    // the code table (0, 1, 2 and the mean dosage, or NaN without mean imputation: the sample is dropped for that variant) and
+    // pgenhip_variant_logistic, once per phenotype, the genotype's coefficient (log-odds per ALT allele), its standard error and a
+    // status: CHROM POS ID REF ALT A1 PHENO OBS_CT MISS_CT A1_FREQ BETA SE Z_STAT P ITER STATUS, P = erfc(|Z| / sqrt 2) (Wald),
+    // STATUS "." / NOT_CONVERGED / SINGULAR and NA in BETA .. P unless converged.  No Firth fallback, no step halving.
     OutputStats output_assoc(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
                              const AssocOptions &aopt, const std::string &filename, const OutputOptions &opt = OutputOptions()) const;
 

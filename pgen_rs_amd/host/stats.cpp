@@ -160,4 +160,83 @@ AssocTest assoc_test(const AssocDesign &d, const uint32_t counts[4], const doubl
     return r;
 }
 
+BinaryCoding binary_coding(const double *v, size_t n, size_t stride)
+{
+    bool zero_one = true, one_two = true, two = false;
+    for (size_t k = 0; k < n; k++) {
+        const double x = v[k * stride];
+        if (std::isnan(x)) continue;
+        zero_one = zero_one && (x == 0.0 || x == 1.0);
+        one_two = one_two && (x == 1.0 || x == 2.0);
+        two = two || x == 2.0;
+    }
+    if (one_two && two) return BinaryCoding::kOneTwo;
+    return zero_one ? BinaryCoding::kZeroOne : BinaryCoding::kNone;
+}
+
+size_t logistic_design(const std::vector<double> &x, size_t n, size_t ncov, std::vector<double> &design)
+{
+    AssocDesign d;
+    const size_t bad = assoc_design(x, std::vector<double>(), n, ncov, 0, d);
+    if (bad != kNoColumn) return bad;
+    const double scale = std::sqrt((double)n);
+    design = std::move(d.values);
+    for (double &v : design) v *= scale;
+    return kNoColumn;
+}
+
+LogisticNull logistic_null(const std::vector<double> &design, size_t n, size_t m, const double *y, int max_iter, double tol)
+{
+    LogisticNull r{false, 0, std::vector<double>(m, 0.0)};
+    std::vector<double> H(m * m), g(m);
+    for (int it = 1; it <= max_iter; it++) {
+        r.evaluations = it;
+        std::fill(H.begin(), H.end(), 0.0);
+        std::fill(g.begin(), g.end(), 0.0);
+        for (size_t k = 0; k < n; k++) {
+            const double *xr = design.data() + k * m;
+            double eta = 0.0;
+            for (size_t c = 0; c < m; c++) eta += xr[c] * r.beta[c];
+            const double mu = 1.0 / (1.0 + std::exp(-eta)), w = mu * (1.0 - mu), res = y[k] - mu;
+            for (size_t a = 0; a < m; a++) {
+                g[a] += xr[a] * res;
+                const double wx = w * xr[a];
+                for (size_t b = 0; b <= a; b++) H[a * m + b] += wx * xr[b];
+            }
+        }
+        for (size_t j = 0; j < m; j++) {   // Cholesky in place, lower
+            double piv = H[j * m + j];
+            for (size_t k = 0; k < j; k++) piv -= H[j * m + k] * H[j * m + k];
+            if (!(piv > 0.0) || std::isinf(piv)) return r;
+            const double l = std::sqrt(piv);
+            H[j * m + j] = l;
+            for (size_t i = j + 1; i < m; i++) {
+                double v = H[i * m + j];
+                for (size_t k = 0; k < j; k++) v -= H[i * m + k] * H[j * m + k];
+                H[i * m + j] = v / l;
+            }
+        }
+        for (size_t i = 0; i < m; i++) {
+            double v = g[i];
+            for (size_t k = 0; k < i; k++) v -= H[i * m + k] * g[k];
+            g[i] = v / H[i * m + i];
+        }
+        for (size_t i = m; i-- > 0;) {
+            double v = g[i];
+            for (size_t k = i + 1; k < m; k++) v -= H[k * m + i] * g[k];
+            g[i] = v / H[i * m + i];
+        }
+        bool converged = true;
+        for (size_t i = 0; i < m; i++) converged = converged && std::fabs(g[i]) <= tol;
+        if (converged) {
+            r.converged = true;
+            return r;
+        }
+        for (size_t i = 0; i < m; i++) r.beta[i] += g[i];
+    }
+    return r;
+}
+
+double wald_p(double z) { return std::erfc(std::fabs(z) / std::sqrt(2.0)); }
+
 }  // namespace pgenhost::stats

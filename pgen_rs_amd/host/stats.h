@@ -55,4 +55,30 @@ struct AssocTest {
 };
 AssocTest assoc_test(const AssocDesign &d, const uint32_t counts[4], const double *S, size_t p);
 
+// ---- `assoc --logistic` ----
+// How a case/control column is coded, from its n values v[0], v[stride], ... (NaN: missing, skipped): every value 1 or 2 with a 2
+// present (control / case), else every value 0 or 1 (0 control), else neither
+enum class BinaryCoding { kNone, kZeroOne, kOneTwo };
+BinaryCoding binary_coding(const double *v, size_t n, size_t stride);
+// 0 / 1 from a value of a column coded so
+inline double binary_value(double v, BinaryCoding c) { return c == BinaryCoding::kOneTwo ? v - 1.0 : v; }
+
+// The design the device iterates on: the n x m orthonormal columns of assoc_design scaled by sqrt(n), so that the first column is
+// the constant 1 and coefficients are O(1); the genotype's coefficient and its standard error do not depend on the basis of the
+// covariates' span.  Returns assoc_design's column report; x as there.
+size_t logistic_design(const std::vector<double> &x, size_t n, size_t ncov, std::vector<double> &design);
+
+// The null model: Newton's iteration on the design alone (n x m, row-major) from zero, the algorithm of the device's fit without the
+// genotype: Cholesky of H = X^T diag(mu (1 - mu)) X, stop when max |delta| <= tol.  converged is false after max_iter evaluations
+// or at a pivot that is <= 0 or not finite (a phenotype the covariates separate); beta then holds the last coefficients.
+struct LogisticNull {
+    bool converged;
+    int evaluations;
+    std::vector<double> beta;   // m
+};
+LogisticNull logistic_null(const std::vector<double> &design, size_t n, size_t m, const double *y, int max_iter, double tol);
+
+// two-sided P of a Wald statistic: erfc(|z| / sqrt 2)
+double wald_p(double z);
+
 }  // namespace pgenhost::stats
