@@ -76,7 +76,7 @@ def build_hip(force: bool = False, verbose: bool = False) -> Path:
 
 HOST_DIR = PKG_DIR / "host"
 HOST_BIN = PKG_DIR / "pgen-hip"
-HOST_SOURCES = ["cli.cpp", "pfile.cpp", "commands.cpp", "import.cpp", "merge.cpp", "merge_match.cpp", "prune.cpp", "prune_plan.cpp", "stats.cpp", "linalg.cpp", "csvlite.cpp", "expr.cpp", "bgzf.cpp"]
+HOST_SOURCES = ["cli.cpp", "pfile.cpp", "commands.cpp", "assoc.cpp", "import.cpp", "merge.cpp", "merge_match.cpp", "prune.cpp", "prune_plan.cpp", "stats.cpp", "linalg.cpp", "csvlite.cpp", "expr.cpp", "bgzf.cpp"]
 
 
 def build_host(force: bool = False, verbose: bool = False) -> Path:

@@ -1,10 +1,12 @@
-// block_loop.h — what the commands of commands.cpp (and import.cpp) are built from below their own counters: the block loop over a
-// shard's records with the counter it drives, the ABI pairs it launches, the shards' sums in order, the tile triangle of the
-// sample-pair commands, a command's opening, and the text a command ends with.
+// block_loop.h — what the commands of commands.cpp, assoc.cpp and prune.cpp (and import.cpp) are built from below their own
+// counters: the block loop over a shard's records with the counter it drives, the ABI pairs it launches, the column groups of a wide
+// launch, the shards' sums in order, the tile triangle of the sample-pair commands, a command's opening, the cells its lines are
+// made of, and the text a command ends with.
 #pragma once
 #include <fcntl.h>
 
 #include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -23,6 +25,49 @@ inline void append_u64(std::string &s, uint64_t v)
         v /= 10;
     } while (v);
     while (n) s += buf[--n];
+}
+
+// one floating-point cell, %.<precision>g; nan_word: a NaN is written as "nan" whatever its sign (else as printf writes it)
+inline void append_double(std::string &s, double v, int precision, bool nan_word = false)
+{
+    if (nan_word && std::isnan(v)) {
+        s += "nan";
+        return;
+    }
+    char buf[40];
+    std::snprintf(buf, sizeof buf, "%.*g", precision, v);
+    s += buf;
+}
+
+// the sixteen cells of a 4 x 4 genotype table behind ld's and kinship's own columns: their header cells, and a line's
+inline void append_table_header(std::string &s)
+{
+    for (int a = 0; a < 4; a++)
+        for (int b = 0; b < 4; b++) s += std::string("\tT") + (char)('0' + a) + (char)('0' + b);
+}
+inline void append_table_cells(std::string &s, const uint32_t *t)
+{
+    for (int c = 0; c < 16; c++) {
+        s += '\t';
+        append_u64(s, t[c]);
+    }
+}
+
+// the .pvar columns of these names, in this order
+template <size_t N>
+void pvar_columns(const Pfile &pf, const StringRecord &header, const char *const (&names)[N], size_t (&col)[N])
+{
+    for (size_t c = 0; c < N; c++) col[c] = column(header, names[c], pf.pvar_path());
+}
+
+// the five leading columns of a per-variant line, copied verbatim from the .pvar columns of these names, a tab behind each
+constexpr const char *kVariantColumns[5] = {"CHROM", "POS", "ID", "REF", "ALT"};
+inline void append_variant_columns(std::string &s, const StringRecord &r, const size_t (&col)[5])
+{
+    for (int c = 0; c < 5; c++) {
+        s += r.at(col[c]);
+        s += '\t';
+    }
 }
 
 inline void write_text(const std::string &text, const std::string &filename)
@@ -47,8 +92,10 @@ inline void finish_text(OutputStats &st, const std::string &text, const std::str
     st.seconds_body = now_s() - t_body;
 }
 
-// The opening of a command: the selection, what the command looks up in or builds from it (columns(sel)), the .psam's IID column
-// when the command prints it, all inside st.seconds_filter; then the checked kept samples and the two sizes into st
+// The opening of a command: the selection, what the command looks up in or builds from it (columns(sel), which may also replace
+// the selection's rows by the ones the command goes on with), the .psam's IID column when the command prints it, all inside
+// st.seconds_filter, which starts at t0 (a command that reads files of its own first takes t0 before them); then the checked kept
+// samples and the two sizes into st
 struct Opening {
     Pfile::Selection sel;
     size_t iid = 0;
@@ -57,9 +104,8 @@ struct Opening {
 };
 template <class Columns>
 Opening open_selection(const Pfile &pf, const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
-                       const OutputOptions &opt, OutputStats &st, bool with_iid, const Columns &columns)
+                       const OutputOptions &opt, OutputStats &st, bool with_iid, const Columns &columns, double t0 = now_s())
 {
-    const double t0 = now_s();
     Opening o;
     o.sel = pf.select(sam_query, var_query, opt.filter_threads);
     columns(o.sel);
@@ -99,6 +145,21 @@ void launch_rows(const BlockRows &b, Plain plain, const char *plain_name, At at,
 inline void genotype_counts(const BlockRows &b, uint32_t nv, uint32_t *d_counts)
 {
     launch_rows(b, NAMED(pgenhip_genotype_counts), NAMED(pgenhip_genotype_counts_at), nv, d_counts, PGENHIP_COUNT_AUTO);
+}
+
+// the same counts on the host now: the launch, the copy and a wait, for a counter whose launches need the block's counts
+inline void genotype_counts_now(const BlockRows &b, uint32_t nv, uint32_t *d_counts, uint32_t *h_counts)
+{
+    genotype_counts(b, nv, d_counts);
+    check(pgenhip_memcpy_d2h(b.ctx, h_counts, d_counts, (size_t)nv * 16), "D2H counts");
+    check(pgenhip_wait(b.ctx), "pgenhip_wait");
+}
+
+// fn(c0, cg) over C columns in groups of at most max_columns, the most one launch of a wide entry takes: group c0 .. c0 + cg
+template <class Fn>
+void column_groups(size_t C, size_t max_columns, const Fn &fn)
+{
+    for (size_t c0 = 0; c0 < C; c0 += max_columns) fn(c0, std::min(max_columns, C - c0));
 }
 
 inline void sample_counts(const BlockRows &b, uint32_t nv, uint32_t *d_counts, bool accumulate)

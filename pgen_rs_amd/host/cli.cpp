@@ -248,6 +248,19 @@ struct Args {
             if (o.first == n) v = o.second;
         return v;
     }
+    // the value of an option the command cannot do without (shown: the option as the usage text words it); an empty one is none
+    std::string required(const std::string &n, const char *shown) const
+    {
+        if (!has(n) || get(n)->empty()) usage_error(std::string("the following required arguments were not provided: ") + shown);
+        return *get(n);
+    }
+    // --format: one of the command's two, the first when the option is absent
+    std::string format(const std::string &first, const std::string &second) const
+    {
+        const std::string f = get("format").value_or(first);
+        if (f != first && f != second) usage_error("invalid value '" + f + "' for '--format <FORMAT>' [possible values: " + first + ", " + second + "]");
+        return f;
+    }
 };
 
 // clap-style: long `--name value` / `--name=value`, short `-f value` / `-fvalue`, flags without values
@@ -415,15 +428,22 @@ MatrixOptions matrix_options(const Args &a)
     return m;
 }
 
+// the times that end every --stats line (OutputStats or MergeStats): the "seconds_*" members, seconds_main up to now
+template <class Stats>
+std::string seconds_json(const Stats &st, std::chrono::steady_clock::time_point t_main)
+{
+    char buf[200];
+    std::snprintf(buf, sizeof buf, "\"seconds_filter\": %.6f, \"seconds_body\": %.6f, \"seconds_setup\": %.6f, \"seconds_kernel\": %.6f, \"seconds_main\": %.6f",
+                  st.seconds_filter, st.seconds_body, st.seconds_setup, st.seconds_kernel, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_main).count());
+    return buf;
+}
+
 // --stats: one JSON line on stderr
 void print_stats(const OutputStats &st, std::chrono::steady_clock::time_point t_main)
 {
-    std::fprintf(stderr,
-                 "{\"variants_kept\": %llu, \"samples_kept\": %llu, \"header_bytes\": %llu, \"body_bytes\": %llu, \"file_bytes\": %llu, "
-                 "\"seconds_filter\": %.6f, \"seconds_body\": %.6f, \"seconds_setup\": %.6f, \"seconds_kernel\": %.6f, \"seconds_main\": %.6f}\n",
+    std::fprintf(stderr, "{\"variants_kept\": %llu, \"samples_kept\": %llu, \"header_bytes\": %llu, \"body_bytes\": %llu, \"file_bytes\": %llu, %s}\n",
                  (unsigned long long)st.variants, (unsigned long long)st.samples_kept, (unsigned long long)st.header_bytes,
-                 (unsigned long long)st.body_bytes, (unsigned long long)st.file_bytes, st.seconds_filter, st.seconds_body, st.seconds_setup,
-                 st.seconds_kernel, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_main).count());
+                 (unsigned long long)st.body_bytes, (unsigned long long)st.file_bytes, seconds_json(st, t_main).c_str());
 }
 
 // The arguments of a command that takes filter's selection: the options every such command has and --stats, beside the command's
@@ -469,6 +489,7 @@ double double_value(const std::string &s, const char *name, const char *placehol
 
 constexpr unsigned long long kNoLimit = ~0ull;
 uint64_t block_rows_value(const std::string &s) { return unsigned_value(s, "block-rows", "B", 1, kNoLimit, "a number of variants from 1"); }
+uint64_t block_mib_value(const std::string &s) { return unsigned_value(s, "block-mib", "M", 1, 65536, "a number of MiB from 1 to 65536") << 20; }   // import, merge: bytes
 uint32_t sample_tile_value(const std::string &s) { return (uint32_t)unsigned_value(s, "sample-tile", "T", 1, 65536, "a number of samples from 1 to 65536"); }
 
 }  // namespace
@@ -544,12 +565,12 @@ int main(int argc, char **argv)
         }
         if (cmd == "score") {
             const SelectionArgs a(argc, argv, {{"weights", 0}}, {{"no-mean-imputation", 0}, {"avg", 0}});
-            if (!a.has("weights") || a.get("weights")->empty()) usage_error("the following required arguments were not provided: --weights <FILE>");
+            const std::string weights = a.required("weights", "--weights <FILE>");
             ScoreOptions s;
             s.mean_imputation = !a.has("no-mean-imputation");
             s.average = a.has("avg");
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
-            const OutputStats st = pfile.output_score(a.get("include-sam"), a.get("include-var"), *a.get("weights"), a.get("out").value_or(""), s, output_options(a));
+            const OutputStats st = pfile.output_score(a.get("include-sam"), a.get("include-var"), weights, a.get("out").value_or(""), s, output_options(a));
             if (a.has("stats"))
                 std::fprintf(stderr, "{\"weights_matched\": %llu, \"weights_flipped\": %llu, \"weights_skipped\": %llu}\n",
                              (unsigned long long)st.score_matched, (unsigned long long)st.score_flipped, (unsigned long long)st.score_skipped);
@@ -574,10 +595,10 @@ int main(int argc, char **argv)
             if (!a.has("logistic"))   // the options of the logistic fit do not exist without it
                 for (const char *name : {"no-mean-imputation", "max-iter", "tol"})
                     if (a.has(name)) usage_error(std::string("unexpected argument '--") + name + "' found");
-            if (!a.has("pheno") || a.get("pheno")->empty()) usage_error("the following required arguments were not provided: --pheno <FILE>");
+            const std::string pheno = a.required("pheno", "--pheno <FILE>");
             if (a.has("covar") && a.get("covar")->empty()) usage_error("a value is required for '--covar <FILE>'");
             AssocOptions ao;
-            ao.pheno_file = *a.get("pheno");
+            ao.pheno_file = pheno;
             ao.covar_file = a.get("covar").value_or("");
             if (a.has("pheno-name")) {
                 std::string name;
@@ -611,59 +632,53 @@ int main(int argc, char **argv)
         }
         if (cmd == "matrix") {
             const SelectionArgs a(argc, argv, {{"dtype", 0}, {"missing", 0}}, {{"sample-major", 0}});
-            if (!a.has("out") || a.get("out")->empty()) usage_error("the following required arguments were not provided: --out <OUT_FILE.npy>");
+            const std::string out = a.required("out", "--out <OUT_FILE.npy>");
             const MatrixOptions m = matrix_options(a);
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
-            return a.done(pfile.output_matrix(a.get("include-sam"), a.get("include-var"), *a.get("out"), m, output_options(a)), t_main);
+            return a.done(pfile.output_matrix(a.get("include-sam"), a.get("include-var"), out, m, output_options(a)), t_main);
         }
         if (cmd == "export") {
             const SelectionArgs a(argc, argv, {{"format", 0}}, {});
-            if (!a.has("out") || a.get("out")->empty()) usage_error("the following required arguments were not provided: --out <OUT_PREFIX>");
-            const std::string format = a.get("format").value_or("pgen");
-            if (format != "pgen" && format != "bed") usage_error("invalid value '" + format + "' for '--format <FORMAT>' [possible values: pgen, bed]");
+            const std::string out = a.required("out", "--out <OUT_PREFIX>");
             ExportOptions e;
-            e.bed = format == "bed";
+            e.bed = a.format("pgen", "bed") == "bed";
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
-            return a.done(pfile.output_export(a.get("include-sam"), a.get("include-var"), *a.get("out"), e, output_options(a)), t_main);
+            return a.done(pfile.output_export(a.get("include-sam"), a.get("include-var"), out, e, output_options(a)), t_main);
         }
         if (cmd == "import") {
             Args a = parse(argc, argv, 2, {{"out", 'o'}, {"block-mib", 0}}, {{"skip-multiallelic", 0}, {"stats", 0}});
             if (a.positional.size() != 1) usage_error("the following required arguments were not provided: <IN.vcf[.gz]>");
-            if (!a.has("out") || a.get("out")->empty()) usage_error("the following required arguments were not provided: --out <OUT_PREFIX>");
+            const std::string out = a.required("out", "--out <OUT_PREFIX>");
             ImportOptions io;
             io.skip_multiallelic = a.has("skip-multiallelic");
             OutputOptions opt;
-            if (auto m = a.get("block-mib")) opt.block_text_bytes = unsigned_value(*m, "block-mib", "M", 1, 65536, "a number of MiB from 1 to 65536") << 20;
-            const OutputStats st = import_vcf(a.positional[0], *a.get("out"), io, opt);
+            if (auto m = a.get("block-mib")) opt.block_text_bytes = block_mib_value(*m);
+            const OutputStats st = import_vcf(a.positional[0], out, io, opt);
             if (a.has("stats"))
                 std::fprintf(stderr,
                              "{\"variants\": %llu, \"samples\": %llu, \"skipped_multiallelic\": %llu, \"half_call_lines\": %llu, \"haploid_lines\": %llu, "
-                             "\"phased_lines\": %llu, \"file_bytes\": %llu, \"seconds_filter\": %.6f, \"seconds_body\": %.6f, \"seconds_setup\": %.6f, "
-                             "\"seconds_kernel\": %.6f, \"seconds_main\": %.6f}\n",
+                             "\"phased_lines\": %llu, \"file_bytes\": %llu, %s}\n",
                              (unsigned long long)st.variants, (unsigned long long)st.samples_kept, (unsigned long long)st.import_skipped,
                              (unsigned long long)st.import_half_call, (unsigned long long)st.import_haploid, (unsigned long long)st.import_phased,
-                             (unsigned long long)st.file_bytes, st.seconds_filter, st.seconds_body, st.seconds_setup, st.seconds_kernel,
-                             std::chrono::duration<double>(std::chrono::steady_clock::now() - t_main).count());
+                             (unsigned long long)st.file_bytes, seconds_json(st, t_main).c_str());
             return 0;
         }
         if (cmd == "merge") {
             Args a = parse(argc, argv, 2, {{"out", 'o'}, {"block-mib", 0}, {"read-threads", 0}}, {{"union", 0}, {"stats", 0}, {"dry-run", 0}});
             if (a.positional.size() < 2) usage_error("merge takes at least two <PFILE_PREFIX> arguments");
             if (a.positional.size() > PGENHIP_JOIN_MAX_PARTS) usage_error("merge takes at most eight <PFILE_PREFIX> arguments: merge in stages");
-            if (!a.has("out") || a.get("out")->empty()) usage_error("the following required arguments were not provided: --out <OUT_PREFIX>");
+            const std::string out = a.required("out", "--out <OUT_PREFIX>");
             MergeOptions mo;
             mo.with_union = a.has("union");
             mo.dry_run = a.has("dry-run");
             OutputOptions opt;
-            if (auto m = a.get("block-mib")) opt.block_text_bytes = unsigned_value(*m, "block-mib", "M", 1, 65536, "a number of MiB from 1 to 65536") << 20;
+            if (auto m = a.get("block-mib")) opt.block_text_bytes = block_mib_value(*m);
             if (auto t = a.get("read-threads")) opt.read_threads = (int)unsigned_value(*t, "read-threads", "T", 1, 256, "a number of threads from 1 to 256");
-            const MergeStats st = merge_pfiles(a.positional, *a.get("out"), mo, opt);
+            const MergeStats st = merge_pfiles(a.positional, out, mo, opt);
             if (mo.dry_run) {
                 std::printf("{%s}\n", st.json_counts().c_str());
             } else if (a.has("stats")) {
-                std::fprintf(stderr, "{%s, \"file_bytes\": %llu, \"seconds_filter\": %.6f, \"seconds_body\": %.6f, \"seconds_setup\": %.6f, \"seconds_kernel\": %.6f, \"seconds_main\": %.6f}\n",
-                             st.json_counts().c_str(), (unsigned long long)st.file_bytes, st.seconds_filter, st.seconds_body, st.seconds_setup, st.seconds_kernel,
-                             std::chrono::duration<double>(std::chrono::steady_clock::now() - t_main).count());
+                std::fprintf(stderr, "{%s, \"file_bytes\": %llu, %s}\n", st.json_counts().c_str(), (unsigned long long)st.file_bytes, seconds_json(st, t_main).c_str());
             }
             return 0;
         }
@@ -682,7 +697,7 @@ int main(int argc, char **argv)
             const SelectionArgs a(argc, argv, {{"window", 0}, {"window-kb", 0}, {"r2", 0}, {"block-rows", 0}}, {{"export", 0}});
             if (!a.has("window") && !a.has("window-kb")) usage_error("the following required arguments were not provided: --window <W> or --window-kb <KB>");
             if (!a.has("r2")) usage_error("the following required arguments were not provided: --r2 <X>");
-            if (!a.has("out") || a.get("out")->empty()) usage_error("the following required arguments were not provided: --out <OUT_PREFIX>");
+            const std::string out = a.required("out", "--out <OUT_PREFIX>");
             PruneOptions po;
             if (auto w = a.get("window")) po.window = (uint32_t)unsigned_value(*w, "window", "W", 1, 0xFFFFFFFFull, "a number of variants from 1 to 4294967295");
             if (auto k = a.get("window-kb")) {
@@ -693,7 +708,7 @@ int main(int argc, char **argv)
             if (auto b = a.get("block-rows")) po.block_rows = block_rows_value(*b);
             po.with_export = a.has("export");
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
-            const OutputStats st = pfile.output_prune(a.get("include-sam"), a.get("include-var"), *a.get("out"), po, output_options(a));
+            const OutputStats st = pfile.output_prune(a.get("include-sam"), a.get("include-var"), out, po, output_options(a));
             std::printf("{\"kept\": %llu, \"removed\": %llu, \"edges\": %llu, \"window\": %llu, \"resolve_calls\": %llu, \"mask_bytes\": %llu}\n",
                         (unsigned long long)st.prune_kept, (unsigned long long)st.prune_removed, (unsigned long long)st.prune_edges,
                         (unsigned long long)st.prune_window, (unsigned long long)st.prune_calls, (unsigned long long)st.prune_mask_bytes);
@@ -715,21 +730,19 @@ int main(int argc, char **argv)
         }
         if (cmd == "grm") {
             const SelectionArgs a(argc, argv, {{"format", 0}, {"sample-tile", 0}, {"block-rows", 0}}, {});
-            if (!a.has("out") || a.get("out")->empty()) usage_error("the following required arguments were not provided: --out <OUT_PREFIX>");
-            const std::string format = a.get("format").value_or("grm-bin");
-            if (format != "grm-bin" && format != "rel") usage_error("invalid value '" + format + "' for '--format <FORMAT>' [possible values: grm-bin, rel]");
+            const std::string out = a.required("out", "--out <OUT_PREFIX>");
             GrmOptions g;
-            g.rel = format == "rel";
+            g.rel = a.format("grm-bin", "rel") == "rel";
             if (auto t = a.get("sample-tile")) g.tile = sample_tile_value(*t);
             if (auto b = a.get("block-rows")) g.block_rows = block_rows_value(*b);
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
-            const OutputStats st = pfile.output_grm(a.get("include-sam"), a.get("include-var"), *a.get("out"), g, output_options(a));
+            const OutputStats st = pfile.output_grm(a.get("include-sam"), a.get("include-var"), out, g, output_options(a));
             if (a.has("stats")) std::fprintf(stderr, "{\"variants_skipped\": %llu}\n", (unsigned long long)st.grm_skipped);
             return a.done(st, t_main);
         }
         if (cmd == "pca") {
             const SelectionArgs a(argc, argv, {{"pcs", 0}, {"tol", 0}, {"max-passes", 0}, {"seed", 0}, {"block-rows", 0}}, {});
-            if (!a.has("out") || a.get("out")->empty()) usage_error("the following required arguments were not provided: --out <OUT_PREFIX>");
+            const std::string out = a.required("out", "--out <OUT_PREFIX>");
             PcaOptions p;
             if (auto v = a.get("pcs")) p.pcs = (uint32_t)unsigned_value(*v, "pcs", "P", 1, 32, "a number of components from 1 to 32");
             if (auto v = a.get("tol")) p.tol = double_value(*v, "tol", "X", 0.0, 1.0, "a number from 0 to 1");
@@ -737,7 +750,7 @@ int main(int argc, char **argv)
             if (auto v = a.get("seed")) p.seed = unsigned_value(*v, "seed", "S", 0, kNoLimit, "a whole number");
             if (auto b = a.get("block-rows")) p.block_rows = block_rows_value(*b);
             const Pfile pfile = Pfile::from_prefix(a.positional[0]);
-            const OutputStats st = pfile.output_pca(a.get("include-sam"), a.get("include-var"), *a.get("out"), p, output_options(a));
+            const OutputStats st = pfile.output_pca(a.get("include-sam"), a.get("include-var"), out, p, output_options(a));
             if (a.has("stats"))
                 std::fprintf(stderr, "{\"variants_skipped\": %llu, \"passes\": %llu, \"residual\": %.6g, \"converged\": %s}\n", (unsigned long long)st.pca_skipped,
                              (unsigned long long)st.pca_passes, st.pca_residual, st.pca_converged ? "true" : "false");

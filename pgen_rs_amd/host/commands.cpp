@@ -1,6 +1,6 @@
-// commands.cpp — the commands of pfile.h that the reference does not have: freq, sample-counts, score, assoc, matrix, ld, export,
-// kinship, grm and pca.  Each selects, runs its counter through the block loop (block_loop.h), calls the arithmetic (stats.h,
-// linalg.h) and prints.
+// commands.cpp — the commands of pfile.h that the reference does not have: freq, sample-counts, score, matrix, ld, export,
+// kinship, grm and pca (assoc: assoc.cpp; prune: prune.cpp; import: import.cpp; merge: merge.cpp).  Each selects, runs its counter
+// through the block loop (block_loop.h), calls the arithmetic (stats.h, linalg.h) and prints.
 #include <fcntl.h>
 
 #include <algorithm>
@@ -64,20 +64,17 @@ struct ScoreCounter : Counter {
     {
         pgenhip_ctx *ctx = b.ctx;
         if (impute) {
-            genotype_counts(b, nv, d_gc);
-            check(pgenhip_memcpy_d2h(ctx, h_gc, d_gc, (size_t)nv * 16), "D2H counts");
-            check(pgenhip_wait(ctx), "pgenhip_wait");
+            genotype_counts_now(b, nv, d_gc, h_gc);
             for (uint32_t j = 0; j < nv; j++) h_miss[j] = (float)stats::mean_dosage(h_gc + 4 * j);
             check(pgenhip_memcpy_h2d(ctx, d_miss, h_miss, (size_t)nv * sizeof(float)), "H2D mean dosages");
         }
         check(pgenhip_memcpy_h2d(ctx, d_w, w.data() + b0 * C, (size_t)nv * C * sizeof(float)), "H2D weights");
         const uint32_t acc = first ? 0u : PGENHIP_SCORE_ACCUMULATE;
-        for (size_t c0 = 0; c0 < C; c0 += PGENHIP_SCORE_MAX_COLUMNS) {
-            const uint32_t cg = (uint32_t)std::min<size_t>(PGENHIP_SCORE_MAX_COLUMNS, C - c0);
+        column_groups(C, PGENHIP_SCORE_MAX_COLUMNS, [&](size_t c0, size_t cg) {
             double *dst = d_scores + K * c0;   // group g's K x cg block behind the blocks of the groups before it
-            launch_rows(b, NAMED(pgenhip_sample_scores), NAMED(pgenhip_sample_scores_at), nv, d_w + c0, C, cg, impute ? d_miss : nullptr, dst,
+            launch_rows(b, NAMED(pgenhip_sample_scores), NAMED(pgenhip_sample_scores_at), nv, d_w + c0, C, (uint32_t)cg, impute ? d_miss : nullptr, dst,
                         PGENHIP_SCORE_AUTO | acc);
-        }
+        });
         sample_counts(b, nv, d_counts, !first);
     }
     void finish(pgenhip_ctx *ctx) const
@@ -86,102 +83,11 @@ struct ScoreCounter : Counter {
         check(pgenhip_memcpy_d2h(ctx, h_counts, d_counts, K * 16), "D2H counts");
         check(pgenhip_wait(ctx), "pgenhip_wait");
         std::lock_guard<std::mutex> lk(mu);
-        for (size_t c0 = 0; c0 < C; c0 += PGENHIP_SCORE_MAX_COLUMNS) {
-            const size_t cg = std::min<size_t>(PGENHIP_SCORE_MAX_COLUMNS, C - c0);
+        column_groups(C, PGENHIP_SCORE_MAX_COLUMNS, [&](size_t c0, size_t cg) {
             for (size_t k = 0; k < K; k++)
                 for (size_t c = 0; c < cg; c++) sums[k * C + c0 + c] += h_scores[K * c0 + k * cg + c];
-        }
+        });
         for (size_t k = 0; k < K; k++) missing[k] += h_counts[4 * k + 3];
-    }
-};
-
-// assoc's counter: per block the rows' genotype counts and their per-code sums of every value column (Q's columns, then the
-// residualised phenotypes; uploaded once per shard), sixteen columns per launch; both come back block by block.  Group g's sums of
-// a block are bv x cg x 4 doubles behind those of the groups before it.
-struct AssocCounter : Counter {
-    size_t C, bv;                     // value columns, rows of a full block
-    std::vector<uint32_t> &counts;    // 4 per kept variant
-    std::vector<double> &sums;        // per kept variant C x 4
-    const double *d_values;
-    uint32_t *d_gc, *h_gc;
-    double *d_sums, *h_sums;
-    void launch(const BlockRows &b, size_t, uint32_t nv, uint32_t, bool) const
-    {
-        genotype_counts(b, nv, d_gc);
-        for (size_t c0 = 0; c0 < C; c0 += PGENHIP_VSUM_MAX_COLUMNS) {
-            const uint32_t cg = (uint32_t)std::min<size_t>(PGENHIP_VSUM_MAX_COLUMNS, C - c0);
-            launch_rows(b, NAMED(pgenhip_variant_sums), NAMED(pgenhip_variant_sums_at), nv, d_values + c0, C, cg, d_sums + bv * 4 * c0, PGENHIP_VSUM_AUTO);
-        }
-    }
-    void copy(pgenhip_ctx *ctx, size_t nv) const
-    {
-        check(pgenhip_memcpy_d2h(ctx, h_gc, d_gc, nv * 16), "D2H counts");
-        for (size_t c0 = 0; c0 < C; c0 += PGENHIP_VSUM_MAX_COLUMNS) {
-            const size_t cg = std::min<size_t>(PGENHIP_VSUM_MAX_COLUMNS, C - c0);
-            check(pgenhip_memcpy_d2h(ctx, h_sums + bv * 4 * c0, d_sums + bv * 4 * c0, nv * cg * 4 * sizeof(double)), "D2H sums");
-        }
-    }
-    void collect(size_t b0, size_t nv) const
-    {
-        std::memcpy(counts.data() + 4 * b0, h_gc, nv * 16);
-        for (size_t c0 = 0; c0 < C; c0 += PGENHIP_VSUM_MAX_COLUMNS) {
-            const size_t cg = std::min<size_t>(PGENHIP_VSUM_MAX_COLUMNS, C - c0);
-            const double *src = h_sums + bv * 4 * c0;
-            for (size_t j = 0; j < nv; j++) std::memcpy(sums.data() + ((b0 + j) * C + c0) * 4, src + j * cg * 4, cg * 4 * sizeof(double));
-        }
-    }
-};
-
-// assoc --logistic's counter: per block the rows' genotype counts come back at once (a row's code table holds its mean dosage), the
-// tables go up, and one pgenhip_variant_logistic per phenotype follows; the genotype's coefficient and standard error and the status
-// word of every (phenotype, row) come back block by block.  The design (n x m), the 0 / 1 phenotypes (P x n) and the null models'
-// coefficients (P x m) are uploaded once per shard.
-struct LogitCounter : Counter {
-    size_t P, m, n, bv;
-    const AssocOptions &ao;
-    std::vector<uint32_t> &counts;    // 4 per kept variant
-    std::vector<double> &beta, &se;   // P per kept variant
-    std::vector<uint32_t> &status;    // P per kept variant
-    const double *d_design, *d_y, *d_start;
-    uint32_t *d_gc, *h_gc;
-    double *d_tab, *h_tab;            // 4 per row
-    double *d_coef, *h_coef;          // P x bv x (m + 1)
-    double *d_se, *h_se;              // P x bv
-    uint32_t *d_status, *h_status;    // P x bv
-    void launch(const BlockRows &b, size_t, uint32_t nv, uint32_t, bool) const
-    {
-        pgenhip_ctx *ctx = b.ctx;
-        genotype_counts(b, nv, d_gc);
-        check(pgenhip_memcpy_d2h(ctx, h_gc, d_gc, (size_t)nv * 16), "D2H counts");
-        check(pgenhip_wait(ctx), "pgenhip_wait");
-        for (uint32_t j = 0; j < nv; j++) {
-            double *t = h_tab + 4 * (size_t)j;
-            t[0] = 0.0, t[1] = 1.0, t[2] = 2.0;
-            t[3] = ao.mean_imputation ? stats::mean_dosage(h_gc + 4 * j) : std::nan("");
-        }
-        check(pgenhip_memcpy_h2d(ctx, d_tab, h_tab, (size_t)nv * 4 * sizeof(double)), "H2D code tables");
-        for (size_t p = 0; p < P; p++)
-            launch_rows(b, NAMED(pgenhip_variant_logistic), NAMED(pgenhip_variant_logistic_at), nv, d_tab, d_design, (uint64_t)m, (uint32_t)m,
-                        d_y + p * n, d_start + p * m, ao.max_iter, ao.tol, d_coef + p * bv * (m + 1), (uint64_t)(m + 1), d_se + p * bv,
-                        d_status + p * bv, PGENHIP_LOGIT_AUTO);
-    }
-    void copy(pgenhip_ctx *ctx, size_t nv) const
-    {
-        for (size_t p = 0; p < P; p++) {
-            check(pgenhip_memcpy_d2h(ctx, h_coef + p * bv * (m + 1), d_coef + p * bv * (m + 1), nv * (m + 1) * sizeof(double)), "D2H coefficients");
-            check(pgenhip_memcpy_d2h(ctx, h_se + p * bv, d_se + p * bv, nv * sizeof(double)), "D2H standard errors");
-            check(pgenhip_memcpy_d2h(ctx, h_status + p * bv, d_status + p * bv, nv * sizeof(uint32_t)), "D2H status words");
-        }
-    }
-    void collect(size_t b0, size_t nv) const
-    {
-        std::memcpy(counts.data() + 4 * b0, h_gc, nv * 16);
-        for (size_t p = 0; p < P; p++)
-            for (size_t j = 0; j < nv; j++) {
-                beta[(b0 + j) * P + p] = h_coef[(p * bv + j) * (m + 1) + m];
-                se[(b0 + j) * P + p] = h_se[p * bv + j];
-                status[(b0 + j) * P + p] = h_status[p * bv + j];
-            }
     }
 };
 
@@ -275,7 +181,6 @@ struct PairWriter : Counter {
     void collect(size_t b0, size_t nv) const
     {
         std::string text;
-        char num[32];
         for (size_t i = 0; i < nv; i++) {
             const StringRecord &ra = vars[b0 + i].second;
             // entries with b0 + i + d past the last kept variant were not written by the launch and are not read here
@@ -298,15 +203,11 @@ struct PairWriter : Counter {
                         text += r->at(col[c]);
                         text += '\t';
                     }
-                std::snprintf(num, sizeof num, "%.6g", (double)r2);
-                text += num;
+                append_double(text, (double)r2, 6);
                 if (ld.counts) {
                     text += '\t';
                     append_u64(text, n_obs);
-                    for (int c = 0; c < 16; c++) {
-                        text += '\t';
-                        append_u64(text, t[c]);
-                    }
+                    append_table_cells(text, t);
                 }
                 text += '\n';
             }
@@ -362,9 +263,7 @@ struct GramCounter : Counter {
     void launch(const BlockRows &b, size_t b0, uint32_t nv, uint32_t, bool first)
     {
         pgenhip_ctx *ctx = b.ctx;
-        genotype_counts(b, nv, d_counts);
-        check(pgenhip_memcpy_d2h(ctx, h_counts, d_counts, (size_t)nv * 16), "D2H counts");
-        check(pgenhip_wait(ctx), "pgenhip_wait");
+        genotype_counts_now(b, nv, d_counts, h_counts);
         uint64_t zero_tables = 0;
         for (size_t j = 0; j < nv; j++) zero_tables += !stats::standardized_table(h_counts + 4 * j, h_tab + 4 * j, h_tab + 4 * (bv + j));
         {
@@ -409,11 +308,10 @@ struct PcaCounter : Counter {
         check(pgenhip_memcpy_h2d(b.ctx, d_tab, tables.data() + 4 * b0, (size_t)nv * 32), "H2D code values");
         const uint32_t flags = PGENHIP_GAPPLY_AUTO | (first ? 0u : PGENHIP_GAPPLY_ACCUMULATE);
         if (first) first_b0 = b0;
-        for (size_t c0 = 0; c0 < L; c0 += PGENHIP_GAPPLY_MAX_COLUMNS) {
-            const uint32_t cg = (uint32_t)std::min<size_t>(PGENHIP_GAPPLY_MAX_COLUMNS, L - c0);
-            launch_rows(b, NAMED(pgenhip_gram_apply), NAMED(pgenhip_gram_apply_at), nv, (const double *)d_tab, (const double *)(d_q + c0), (uint64_t)L, cg,
+        column_groups(L, PGENHIP_GAPPLY_MAX_COLUMNS, [&](size_t c0, size_t cg) {
+            launch_rows(b, NAMED(pgenhip_gram_apply), NAMED(pgenhip_gram_apply_at), nv, (const double *)d_tab, (const double *)(d_q + c0), (uint64_t)L, (uint32_t)cg,
                         d_proj, d_y + c0, (uint64_t)L, flags);
-        }
+        });
     }
     void finish(pgenhip_ctx *ctx) const
     {
@@ -429,12 +327,8 @@ OutputStats Pfile::output_freq(const std::optional<std::string> &sam_query, cons
                                const std::string &filename, const OutputOptions &opt) const
 {
     OutputStats st;
-    // the five leading columns, copied verbatim from the pvar columns of these names
-    static const char *const kCols[5] = {"CHROM", "POS", "ID", "REF", "ALT"};
     size_t col[5];
-    const Opening o = open_selection(*this, sam_query, var_query, opt, st, false, [&](const Selection &sel) {
-        for (int c = 0; c < 5; c++) col[c] = column(sel.var_header, kCols[c], pvar_path());
-    });
+    const Opening o = open_selection(*this, sam_query, var_query, opt, st, false, [&](const Selection &sel) { pvar_columns(*this, sel.var_header, kVariantColumns, col); });
     const IdxRecords &var_idx_rcds = o.sel.var_idx_rcds;
     const KeptSamples &kept = o.kept;
     const size_t V = o.V;
@@ -450,11 +344,7 @@ OutputStats Pfile::output_freq(const std::optional<std::string> &sam_query, cons
     std::string text = "#CHROM\tPOS\tID\tREF\tALT\tHOM_REF_CT\tHET_REF_ALT_CTS\tTWO_ALT_GENO_CTS\tMISSING_CT\n";
     st.header_bytes = text.size();
     for (size_t j = 0; j < V; j++) {
-        const StringRecord &r = var_idx_rcds[j].second;
-        for (int c = 0; c < 5; c++) {
-            text += r.at(col[c]);
-            text += '\t';
-        }
+        append_variant_columns(text, var_idx_rcds[j].second, col);
         for (int c = 0; c < 4; c++) {
             append_u64(text, counts[4 * j + (size_t)c]);
             text += c < 3 ? '\t' : '\n';
@@ -498,52 +388,21 @@ OutputStats Pfile::output_sample_counts(const std::optional<std::string> &sam_qu
 
 ScoreWeights read_score_weights(const std::string &path)
 {
-    const std::string data = read_file(path);
     ScoreWeights sw;
-    TsvReader reader(data, !data.empty() && data[0] == '#' ? 1 : 0);
-    const StringRecord &head = reader.headers();
-    if (head.size() < 3) throw PfileError(path + " line 1: a weights file has an ID column, an effect allele column and at least one score column");
-    sw.names.assign(head.begin() + 2, head.end());
-    const size_t C = sw.names.size();
-    // the line a record starts on: the newlines in front of it, counted as the reader moves on
-    size_t counted = 0, line = 1;
-    auto line_at = [&](size_t pos) {
-        for (; counted < pos; counted++) line += data[counted] == '\n';
-        for (size_t p = pos; p < data.size() && (data[p] == '\n' || data[p] == '\r'); p++) {   // the empty lines the reader skips
-            line += data[p] == '\n';
-            counted = p + 1;
-        }
-        return line;
-    };
-    std::map<std::string, size_t> seen;   // ID -> line
-    StringRecord rec;
-    for (;;) {
-        const size_t at = line_at(reader.position());
-        bool more;
-        try {
-            more = reader.next(rec);
-        } catch (const CsvError &) {
-            throw PfileError(path + " line " + std::to_string(at) + ": expected " + std::to_string(C + 2) + " tab-separated cells like the header's");
-        }
-        if (!more) break;
-        const auto dup = seen.emplace(rec[0], at);
-        if (!dup.second)
-            throw PfileError(path + " line " + std::to_string(at) + ": variant ID '" + rec[0] + "' occurs twice (first on line " + std::to_string(dup.first->second) + ")");
-        for (size_t c = 0; c < C; c++) {
-            const std::string &cell = rec[2 + c];
-            char *end = nullptr;
-            errno = 0;
-            const double x = std::strtod(cell.c_str(), &end);
-            const bool fits = std::isfinite(x) && std::fabs(x) < 0x1.ffffffp127;   // rounds to a finite f32
-            const float f = fits ? (float)x : 0.f;                                   // rounded to f32 once, here
-            if (cell.empty() || *end != '\0' || !fits)
-                throw PfileError(path + " line " + std::to_string(at) + ": weight '" + cell + "' of score " + sw.names[c] + " is not a finite number");
-            sw.w.push_back(f);
-        }
-        sw.ids.push_back(rec[0]);
-        sw.alleles.push_back(rec[1]);
-        sw.lines.push_back(at);
-    }
+    KeyedRows t = read_keyed_rows(path, 2, "a weights file has an ID column, an effect allele column and at least one score column", "variant ID",
+                                  [&](const std::string &cell, const std::string &name, const std::string &where) {
+        char *end = nullptr;
+        errno = 0;
+        const double x = std::strtod(cell.c_str(), &end);
+        const bool fits = std::isfinite(x) && std::fabs(x) < 0x1.ffffffp127;   // rounds to a finite f32
+        const float f = fits ? (float)x : 0.f;                                   // rounded to f32 once, here
+        if (cell.empty() || *end != '\0' || !fits) throw PfileError(where + ": weight '" + cell + "' of score " + name + " is not a finite number");
+        sw.w.push_back(f);
+    });
+    sw.names = std::move(t.names);
+    sw.ids = std::move(t.lead[0]);
+    sw.alleles = std::move(t.lead[1]);
+    sw.lines = std::move(t.lines);
     return sw;
 }
 
@@ -554,54 +413,52 @@ OutputStats Pfile::output_score(const std::optional<std::string> &sam_query, con
     const double t0 = now_s();
     const ScoreWeights sw = read_score_weights(weights_file);
     const size_t C = sw.names.size();
-    Selection sel = select(sam_query, var_query, opt.filter_threads);
-    const size_t iid = iid_column(*this, sel.sam_header);
-    static const char *const kCols[3] = {"ID", "REF", "ALT"};
-    size_t col[3];
-    for (int c = 0; c < 3; c++) col[c] = column(sel.var_header, kCols[c], pvar_path());
-
-    // the kept variants the file names, in the .pgen's order: they are the selection of every launch
-    std::map<std::string, size_t> row_of;
-    for (size_t i = 0; i < sw.ids.size(); i++) row_of.emplace(sw.ids[i], i);
-    std::vector<char> used(sw.ids.size(), 0);
-    Selection msel;
+    size_t iid = 0;
     std::vector<float> w;                 // matched rows x C, REF-effect rows negated
     std::vector<double> constant(C, 0.0); // the 2w of the REF-effect rows, added to every sample
-    uint64_t flipped = 0, mismatched = 0;
-    for (const auto &vr : sel.var_idx_rcds) {
-        const auto it = row_of.find(vr.second.at(col[0]));
-        if (it == row_of.end()) continue;
-        const size_t i = it->second;
-        if (used[i])
-            throw PfileError(weights_file + " line " + std::to_string(sw.lines[i]) + ": variant ID '" + sw.ids[i] + "' occurs twice among the kept variants of " + pvar_path());
-        used[i] = 1;
-        const bool alt = sw.alleles[i] == vr.second.at(col[2]), ref = !alt && sw.alleles[i] == vr.second.at(col[1]);
-        if (!alt && !ref) {
-            mismatched++;
-            continue;
+    // the kept variants the file names, in the .pgen's order: they are the selection of every launch (the rows they replace live
+    // on in `matched` until the command ends: freeing them is no part of seconds_filter)
+    IdxRecords matched;
+    const Opening o = open_selection(*this, sam_query, var_query, opt, st, false, [&](Selection &sel) {
+        iid = iid_column(*this, sel.sam_header);
+        static const char *const kCols[3] = {"ID", "REF", "ALT"};
+        size_t col[3];
+        pvar_columns(*this, sel.var_header, kCols, col);
+        std::map<std::string, size_t> row_of;
+        for (size_t i = 0; i < sw.ids.size(); i++) row_of.emplace(sw.ids[i], i);
+        std::vector<char> used(sw.ids.size(), 0);
+        uint64_t flipped = 0, mismatched = 0;
+        for (const auto &vr : sel.var_idx_rcds) {
+            const auto it = row_of.find(vr.second.at(col[0]));
+            if (it == row_of.end()) continue;
+            const size_t i = it->second;
+            if (used[i])
+                throw PfileError(weights_file + " line " + std::to_string(sw.lines[i]) + ": variant ID '" + sw.ids[i] + "' occurs twice among the kept variants of " + pvar_path());
+            used[i] = 1;
+            const bool alt = sw.alleles[i] == vr.second.at(col[2]), ref = !alt && sw.alleles[i] == vr.second.at(col[1]);
+            if (!alt && !ref) {
+                mismatched++;
+                continue;
+            }
+            for (size_t c = 0; c < C; c++) {
+                const float x = sw.w[i * C + c];
+                w.push_back(ref ? -x : x);
+                if (ref) constant[c] += 2.0 * (double)x;
+            }
+            flipped += ref;
+            matched.emplace_back(vr.first, StringRecord());
         }
-        for (size_t c = 0; c < C; c++) {
-            const float x = sw.w[i * C + c];
-            w.push_back(ref ? -x : x);
-            if (ref) constant[c] += 2.0 * (double)x;
-        }
-        flipped += ref;
-        msel.var_idx_rcds.emplace_back(vr.first, StringRecord());
-    }
-    const size_t M = msel.var_idx_rcds.size();
-    st.score_matched = M;
-    st.score_flipped = flipped;
-    st.score_skipped = sw.ids.size() - M;
-    if (M == 0)
-        throw PfileError("no row of " + weights_file + " names a kept variant of " + pvar_path() + " by ID with its REF or ALT allele (" +
-                         std::to_string(sw.ids.size()) + " rows, " + std::to_string(mismatched) + " with another allele)");
-    msel.sam_idx_rcs = std::move(sel.sam_idx_rcs);
-    st.seconds_filter = now_s() - t0;
-
-    const KeptSamples kept = check_selection(*this, msel);
-    const size_t K = kept.rows.size();
-    st.variants = M;
-    st.samples_kept = K;
+        st.score_matched = matched.size();
+        st.score_flipped = flipped;
+        st.score_skipped = sw.ids.size() - matched.size();
+        if (matched.empty())
+            throw PfileError("no row of " + weights_file + " names a kept variant of " + pvar_path() + " by ID with its REF or ALT allele (" +
+                             std::to_string(sw.ids.size()) + " rows, " + std::to_string(mismatched) + " with another allele)");
+        sel.var_idx_rcds.swap(matched);
+    }, t0);
+    const Selection &msel = o.sel;
+    const KeptSamples &kept = o.kept;
+    const size_t M = o.V, K = o.K;
 
     std::vector<double> sums(K * C, 0.0);
     std::vector<uint64_t> missing(K, 0u);
@@ -623,7 +480,6 @@ OutputStats Pfile::output_score(const std::optional<std::string> &sam_query, con
     for (const std::string &name : sw.names) text += "\t" + name + (sopt.average ? "_AVG" : "_SUM");
     text += '\n';
     st.header_bytes = text.size();
-    char buf[64];
     for (size_t k = 0; k < K; k++) {
         const uint64_t allele_ct = 2 * ((uint64_t)M - missing[k]), denom = sopt.mean_imputation ? 2 * (uint64_t)M : allele_ct;
         text += msel.sam_idx_rcs[k].second.at(iid);
@@ -634,285 +490,10 @@ OutputStats Pfile::output_score(const std::optional<std::string> &sam_query, con
         for (size_t c = 0; c < C; c++) {
             const double sum = sums[k * C + c] + constant[c];
             text += '\t';
-            if (sopt.average && denom == 0) {
-                text += "nan";
-            } else {
-                std::snprintf(buf, sizeof buf, "%.12g", sopt.average ? sum / (double)denom : sum);
-                text += buf;
-            }
+            if (sopt.average && denom == 0) text += "nan";
+            else append_double(text, sopt.average ? sum / (double)denom : sum, 12);
         }
         text += '\n';
-    }
-    finish_text(st, text, filename, t_body);
-    return st;
-}
-
-ValueTable read_value_table(const std::string &path)
-{
-    const std::string data = read_file(path);
-    ValueTable vt;
-    TsvReader reader(data, !data.empty() && data[0] == '#' ? 1 : 0);
-    const StringRecord &head = reader.headers();
-    if (head.size() < 2) throw PfileError(path + " line 1: a value file has an IID column and at least one value column");
-    vt.names.assign(head.begin() + 1, head.end());
-    const size_t C = vt.names.size();
-    // the line a record starts on: the newlines in front of it, counted as the reader moves on
-    size_t counted = 0, line = 1;
-    auto line_at = [&](size_t pos) {
-        for (; counted < pos; counted++) line += data[counted] == '\n';
-        for (size_t p = pos; p < data.size() && (data[p] == '\n' || data[p] == '\r'); p++) {   // the empty lines the reader skips
-            line += data[p] == '\n';
-            counted = p + 1;
-        }
-        return line;
-    };
-    std::map<std::string, size_t> seen;   // IID -> line
-    StringRecord rec;
-    for (;;) {
-        const size_t at = line_at(reader.position());
-        bool more;
-        try {
-            more = reader.next(rec);
-        } catch (const CsvError &) {
-            throw PfileError(path + " line " + std::to_string(at) + ": expected " + std::to_string(C + 1) + " tab-separated cells like the header's");
-        }
-        if (!more) break;
-        const auto dup = seen.emplace(rec[0], at);
-        if (!dup.second)
-            throw PfileError(path + " line " + std::to_string(at) + ": IID '" + rec[0] + "' occurs twice (first on line " + std::to_string(dup.first->second) + ")");
-        for (size_t c = 0; c < C; c++) {
-            const std::string &cell = rec[1 + c];
-            if (cell.empty() || cell == "NA" || cell == "nan") {
-                vt.x.push_back(std::nan(""));
-                continue;
-            }
-            char *end = nullptr;
-            const double x = std::strtod(cell.c_str(), &end);
-            if (*end != '\0' || !std::isfinite(x))
-                throw PfileError(path + " line " + std::to_string(at) + ": value '" + cell + "' of column " + vt.names[c] + " is not a finite number, NA or nan");
-            vt.x.push_back(x);
-        }
-        vt.iids.push_back(rec[0]);
-    }
-    return vt;
-}
-
-OutputStats Pfile::output_assoc(const std::optional<std::string> &sam_query, const std::optional<std::string> &var_query,
-                                const AssocOptions &aopt, const std::string &filename, const OutputOptions &opt) const
-{
-    OutputStats st;
-    const double t0 = now_s();
-    const ValueTable ph = read_value_table(aopt.pheno_file);
-    ValueTable cv;
-    if (!aopt.covar_file.empty()) cv = read_value_table(aopt.covar_file);
-    std::vector<size_t> pcol;   // the chosen phenotype columns
-    if (aopt.pheno_names.empty()) {
-        for (size_t c = 0; c < ph.names.size(); c++) pcol.push_back(c);
-    } else {
-        for (const std::string &name : aopt.pheno_names) {
-            const size_t c = std::find(ph.names.begin(), ph.names.end(), name) - ph.names.begin();
-            if (c == ph.names.size()) throw PfileError(aopt.pheno_file + " line 1: no phenotype column named '" + name + "'");
-            pcol.push_back(c);
-        }
-    }
-    const size_t P = pcol.size(), ncov = cv.names.size(), m = 1 + ncov, C = m + P;
-    std::vector<stats::BinaryCoding> coding(P, stats::BinaryCoding::kNone);
-    if (aopt.logistic) {
-        if (m > PGENHIP_LOGIT_MAX_COVARIATES)
-            throw PfileError(aopt.covar_file + ": " + std::to_string(ncov) + " covariates; assoc --logistic takes " + std::to_string(PGENHIP_LOGIT_MAX_COVARIATES - 1) + " at most");
-        for (size_t p = 0; p < P; p++) {
-            coding[p] = stats::binary_coding(ph.x.data() + pcol[p], ph.iids.size(), ph.names.size());
-            if (coding[p] == stats::BinaryCoding::kNone)
-                throw PfileError(aopt.pheno_file + ": phenotype " + ph.names[pcol[p]] + " is not a case/control column (every value 1 or 2 with a 2 present, or every value 0 or 1)");
-        }
-    }
-
-    Selection sel = select(sam_query, var_query, opt.filter_threads);
-    const size_t iid = iid_column(*this, sel.sam_header);
-    static const char *const kCols[5] = {"CHROM", "POS", "ID", "REF", "ALT"};
-    size_t col[5];
-    for (int c = 0; c < 5; c++) col[c] = column(sel.var_header, kCols[c], pvar_path());
-
-    // complete cases: a kept sample stays only with every chosen phenotype and every covariate
-    std::map<std::string, size_t> ph_row, cv_row;
-    for (size_t i = 0; i < ph.iids.size(); i++) ph_row.emplace(ph.iids[i], i);
-    for (size_t i = 0; i < cv.iids.size(); i++) cv_row.emplace(cv.iids[i], i);
-    IdxRecords stay;
-    std::vector<double> y, x;   // n x P phenotypes, n x ncov covariates
-    for (auto &sr : sel.sam_idx_rcs) {
-        const auto pi = ph_row.find(sr.second.at(iid));
-        const auto ci = ncov ? cv_row.find(sr.second.at(iid)) : cv_row.end();
-        bool complete = pi != ph_row.end() && (!ncov || ci != cv_row.end());
-        for (size_t p = 0; complete && p < P; p++) complete = !std::isnan(ph.x[pi->second * ph.names.size() + pcol[p]]);
-        for (size_t c = 0; complete && c < ncov; c++) complete = !std::isnan(cv.x[ci->second * ncov + c]);
-        if (!complete) continue;
-        for (size_t p = 0; p < P; p++) y.push_back(ph.x[pi->second * ph.names.size() + pcol[p]]);
-        for (size_t c = 0; c < ncov; c++) x.push_back(cv.x[ci->second * ncov + c]);
-        stay.push_back(std::move(sr));
-    }
-    st.assoc_dropped = sel.sam_idx_rcs.size() - stay.size();
-    sel.sam_idx_rcs = std::move(stay);
-    const size_t n = sel.sam_idx_rcs.size();
-    if (n == 0) throw PfileError("no kept sample has every chosen phenotype of " + aopt.pheno_file + (ncov ? " and every covariate of " + aopt.covar_file : std::string()));
-    if (n < m + 2)
-        throw PfileError("too few samples: " + std::to_string(n) + " complete samples leave " + std::to_string((long long)n - (long long)m - 1) +
-                         " degrees of freedom for an intercept, " + std::to_string(ncov) + " covariates and the genotype");
-
-    if (aopt.logistic) {
-        // the design, n x m: Q's columns scaled by sqrt(n); the phenotypes as 0 / 1, P x n; the null models, P x m
-        std::vector<double> xq, y01(P * n), start(P * m);
-        if (const size_t c = stats::logistic_design(x, n, ncov, xq); c != stats::kNoColumn)
-            throw PfileError(aopt.covar_file + ": covariate " + (c ? cv.names[c - 1] : std::string("(intercept)")) + " is collinear with the intercept and the covariates before it");
-        for (size_t p = 0; p < P; p++) {
-            size_t cases = 0;
-            for (size_t k = 0; k < n; k++) cases += (y01[p * n + k] = stats::binary_value(y[k * P + p], coding[p])) != 0.0;
-            if (cases == 0 || cases == n)
-                throw PfileError(aopt.pheno_file + ": phenotype " + ph.names[pcol[p]] + " has no " + (cases ? "control" : "case") + " among the " + std::to_string(n) + " complete samples");
-            const stats::LogisticNull fit = stats::logistic_null(xq, n, m, y01.data() + p * n, (int)PGENHIP_LOGIT_MAX_ITER, 1e-12);
-            if (!fit.converged)
-                throw PfileError(aopt.pheno_file + ": the null model of phenotype " + ph.names[pcol[p]] + " (intercept and covariates alone) did not converge: the covariates separate it");
-            std::copy(fit.beta.begin(), fit.beta.end(), start.begin() + p * m);
-        }
-        st.seconds_filter = now_s() - t0;
-
-        const KeptSamples kept = check_selection(*this, sel);
-        const size_t V = sel.var_idx_rcds.size();
-        st.variants = V;
-        st.samples_kept = n;
-        std::vector<uint32_t> counts(4 * V, 0u), status(V * P, 0u);
-        std::vector<double> beta(V * P, 0.0), se(V * P, 0.0);
-        const double t_body = now_s();
-        if (V != 0) {   // else the header alone and no device is touched
-            count_blocks(*this, sel.var_idx_rcds, kept, opt, "no HIP device: the assoc path has no CPU fallback", st, [&](DeviceCtx &ctx, uint64_t bv) {
-                const size_t b = (size_t)bv;
-                double *d_design = ctx.device<double>(n * m * sizeof(double), "device design");
-                double *d_y = ctx.device<double>(P * n * sizeof(double), "device phenotypes");
-                double *d_start = ctx.device<double>(P * m * sizeof(double), "device null models");
-                check(pgenhip_memcpy_h2d(ctx.get(), d_design, xq.data(), n * m * sizeof(double)), "H2D design");
-                check(pgenhip_memcpy_h2d(ctx.get(), d_y, y01.data(), P * n * sizeof(double)), "H2D phenotypes");
-                check(pgenhip_memcpy_h2d(ctx.get(), d_start, start.data(), P * m * sizeof(double)), "H2D null models");
-                check(pgenhip_wait(ctx.get()), "pgenhip_wait");
-                return LogitCounter{{}, P, m, n, b, aopt, counts, beta, se, status, d_design, d_y, d_start,
-                                    ctx.device<uint32_t>(16 * b, "device variant counts"), ctx.pinned<uint32_t>(16 * b, "pinned variant counts"),
-                                    ctx.device<double>(b * 4 * sizeof(double), "device code tables"), ctx.pinned<double>(b * 4 * sizeof(double), "pinned code tables"),
-                                    ctx.device<double>(P * b * (m + 1) * sizeof(double), "device coefficients"), ctx.pinned<double>(P * b * (m + 1) * sizeof(double), "pinned coefficients"),
-                                    ctx.device<double>(P * b * sizeof(double), "device standard errors"), ctx.pinned<double>(P * b * sizeof(double), "pinned standard errors"),
-                                    ctx.device<uint32_t>(P * b * sizeof(uint32_t), "device status words"), ctx.pinned<uint32_t>(P * b * sizeof(uint32_t), "pinned status words")};
-            });
-        }
-
-        std::string text = "#CHROM\tPOS\tID\tREF\tALT\tA1\tPHENO\tOBS_CT\tMISS_CT\tA1_FREQ\tBETA\tSE\tZ_STAT\tP\tITER\tSTATUS\n";
-        st.header_bytes = text.size();
-        char buf[64];
-        auto number = [&](double v) {
-            std::snprintf(buf, sizeof buf, "%.12g", v);
-            text += '\t';
-            text += buf;
-        };
-        for (size_t j = 0; j < V; j++) {
-            const StringRecord &vr = sel.var_idx_rcds[j].second;
-            const uint32_t *ct = counts.data() + 4 * j;
-            const bool called = (uint64_t)ct[0] + ct[1] + ct[2] != 0;
-            for (size_t p = 0; p < P; p++) {
-                for (int c = 0; c < 5; c++) {
-                    if (c) text += '\t';
-                    text += vr.at(col[c]);
-                }
-                text += '\t';
-                text += vr.at(col[4]);
-                text += '\t';
-                text += ph.names[pcol[p]];
-                text += '\t';
-                append_u64(text, aopt.mean_imputation ? n : n - ct[3]);
-                text += '\t';
-                append_u64(text, ct[3]);
-                if (called) number(0.5 * stats::mean_dosage(ct));
-                else text += "\tNA";
-                const uint32_t word = status[j * P + p];
-                const bool converged = (word & PGENHIP_LOGIT_CONVERGED) != 0u;
-                if (converged) {
-                    const double b = beta[j * P + p], s = se[j * P + p], z = b / s;
-                    number(b);
-                    number(s);
-                    number(z);
-                    number(stats::wald_p(z));
-                    st.logit_converged++;
-                } else {
-                    text += "\tNA\tNA\tNA\tNA";
-                    ++((word & PGENHIP_LOGIT_SINGULAR) ? st.logit_singular : st.logit_not_converged);
-                }
-                text += '\t';
-                append_u64(text, word & 0xFFu);
-                text += converged ? "\t.\n" : (word & PGENHIP_LOGIT_SINGULAR) ? "\tSINGULAR\n" : "\tNOT_CONVERGED\n";
-            }
-        }
-        finish_text(st, text, filename, t_body);
-        return st;
-    }
-
-    // the value columns, n x C: Q's m columns, then the residualised phenotypes
-    stats::AssocDesign design;
-    if (const size_t c = stats::assoc_design(x, y, n, ncov, P, design); c != stats::kNoColumn)
-        throw PfileError(aopt.covar_file + ": covariate " + (c ? cv.names[c - 1] : std::string("(intercept)")) + " is collinear with the intercept and the covariates before it");
-    const std::vector<double> &values = design.values;
-    st.seconds_filter = now_s() - t0;
-
-    const KeptSamples kept = check_selection(*this, sel);
-    const size_t V = sel.var_idx_rcds.size();
-    st.variants = V;
-    st.samples_kept = n;
-
-    std::vector<uint32_t> counts(4 * V, 0u);
-    std::vector<double> sums(V * C * 4, 0.0);
-    const double t_body = now_s();
-    if (V != 0) {   // else the header alone and no device is touched
-        count_blocks(*this, sel.var_idx_rcds, kept, opt, "no HIP device: the assoc path has no CPU fallback", st, [&](DeviceCtx &ctx, uint64_t bv) {
-            const size_t b = (size_t)bv;
-            double *d_values = ctx.device<double>(n * C * sizeof(double), "device values");
-            check(pgenhip_memcpy_h2d(ctx.get(), d_values, values.data(), n * C * sizeof(double)), "H2D values");
-            check(pgenhip_wait(ctx.get()), "pgenhip_wait");
-            return AssocCounter{{}, C, b, counts, sums, d_values,
-                                ctx.device<uint32_t>(16 * b, "device variant counts"), ctx.pinned<uint32_t>(16 * b, "pinned variant counts"),
-                                ctx.device<double>(b * C * 4 * sizeof(double), "device sums"), ctx.pinned<double>(b * C * 4 * sizeof(double), "pinned sums")};
-        });
-    }
-
-    std::string text = "#CHROM\tPOS\tID\tREF\tALT\tA1\tPHENO\tOBS_CT\tMISS_CT\tA1_FREQ\tBETA\tSE\tT_STAT\tP\n";
-    st.header_bytes = text.size();
-    char buf[64];
-    auto number = [&](double v) {
-        std::snprintf(buf, sizeof buf, "%.12g", v);
-        text += '\t';
-        text += buf;
-    };
-    for (size_t j = 0; j < V; j++) {
-        const StringRecord &vr = sel.var_idx_rcds[j].second;
-        for (size_t p = 0; p < P; p++) {
-            const stats::AssocTest r = stats::assoc_test(design, counts.data() + 4 * j, sums.data() + j * C * 4, p);
-            for (int c = 0; c < 5; c++) {
-                if (c) text += '\t';
-                text += vr.at(col[c]);
-            }
-            text += '\t';
-            text += vr.at(col[4]);
-            text += '\t';
-            text += ph.names[pcol[p]];
-            text += '\t';
-            append_u64(text, n);
-            text += '\t';
-            append_u64(text, counts[4 * j + 3]);
-            if (r.has_freq) number(r.a1_freq);
-            else text += "\tNA";
-            if (r.na) {
-                text += "\tNA\tNA\tNA\tNA\n";
-                continue;
-            }
-            number(r.beta);
-            number(r.se);
-            number(r.t);
-            number(r.p);
-            text += '\n';
-        }
     }
     finish_text(st, text, filename, t_body);
     return st;
@@ -924,9 +505,7 @@ OutputStats Pfile::output_ld(const std::optional<std::string> &sam_query, const 
     OutputStats st;
     static const char *const kCols[3] = {"CHROM", "POS", "ID"};
     size_t col[3];
-    const Opening o = open_selection(*this, sam_query, var_query, opt, st, false, [&](const Selection &sel) {
-        for (int c = 0; c < 3; c++) col[c] = column(sel.var_header, kCols[c], pvar_path());
-    });
+    const Opening o = open_selection(*this, sam_query, var_query, opt, st, false, [&](const Selection &sel) { pvar_columns(*this, sel.var_header, kCols, col); });
     const Selection &sel = o.sel;
     const KeptSamples &kept = o.kept;
     const size_t V = o.V, K = o.K;
@@ -934,8 +513,7 @@ OutputStats Pfile::output_ld(const std::optional<std::string> &sam_query, const 
     std::string text = "#CHROM_A\tPOS_A\tID_A\tCHROM_B\tPOS_B\tID_B\tR2";
     if (ld.counts) {
         text += "\tN_OBS";
-        for (int a = 0; a < 4; a++)
-            for (int b = 0; b < 4; b++) text += std::string("\tT") + (char)('0' + a) + (char)('0' + b);
+        append_table_header(text);
     }
     text += '\n';
     st.header_bytes = text.size();
@@ -968,10 +546,7 @@ OutputStats Pfile::output_kinship(const std::optional<std::string> &sam_query, c
     const size_t iid = o.iid, V = o.V, K = o.K;
 
     std::string text = "#IID1\tIID2\tN\tHETHET\tIBS0\tHET1\tHET2\tKINSHIP";
-    if (kopt.counts) {
-        for (int a = 0; a < 4; a++)
-            for (int b = 0; b < 4; b++) text += std::string("\tT") + (char)('0' + a) + (char)('0' + b);
-    }
+    if (kopt.counts) append_table_header(text);
     text += '\n';
     st.header_bytes = text.size();
     const double t_body = now_s();
@@ -989,7 +564,6 @@ OutputStats Pfile::output_kinship(const std::optional<std::string> &sam_query, c
                 return kc;
             }, kopt.block_rows);
         }
-        char num[32];
         for (size_t a = 0; a < K; a++) {
             const size_t ta = a / tile, i = a % tile;
             for (size_t b = a + 1; b < K; b++) {
@@ -1005,18 +579,8 @@ OutputStats Pfile::output_kinship(const std::optional<std::string> &sam_query, c
                     append_u64(text, v);
                 }
                 text += '\t';
-                if (std::isnan(k.kinship)) {
-                    text += "nan";
-                } else {
-                    std::snprintf(num, sizeof num, "%.6g", k.kinship);
-                    text += num;
-                }
-                if (kopt.counts) {
-                    for (int c = 0; c < 16; c++) {
-                        text += '\t';
-                        append_u64(text, t[c]);
-                    }
-                }
+                append_double(text, k.kinship, 6, true);
+                if (kopt.counts) append_table_cells(text, t);
                 text += '\n';
             }
         }
@@ -1079,16 +643,9 @@ OutputStats Pfile::output_grm(const std::optional<std::string> &sam_query, const
     }
     if (gopt.rel) {
         std::string text;
-        char num[40];
         for (size_t a = 0; a < K; a++)
             for (size_t b = 0; b < K; b++) {
-                const double v = grm(a, b);
-                if (std::isnan(v)) {
-                    text += "nan";
-                } else {
-                    std::snprintf(num, sizeof num, "%.17g", v);
-                    text += num;
-                }
+                append_double(text, grm(a, b), 17, true);
                 text += b + 1 < K ? '\t' : '\n';
             }
         st.file_bytes = text.size();
@@ -1190,17 +747,16 @@ OutputStats Pfile::output_pca(const std::optional<std::string> &sam_query, const
                      (unsigned long long)st.pca_passes, st.pca_residual);
 
     std::string vals, vecs;
-    char num[40];
     for (size_t i = 0; i < P; i++) {
-        std::snprintf(num, sizeof num, "%.17g\n", lambda[i]);
-        vals += num;
+        append_double(vals, lambda[i], 17);
+        vals += '\n';
     }
     linalg::unit_columns_largest_positive(U, K, L, P);
     for (size_t k = 0; k < K; k++) {
         vecs += sel.sam_idx_rcs[k].second.at(iid);
         for (size_t i = 0; i < P; i++) {
-            std::snprintf(num, sizeof num, "\t%.17g", U[k * L + i]);
-            vecs += num;
+            vecs += '\t';
+            append_double(vecs, U[k * L + i], 17);
         }
         vecs += '\n';
     }

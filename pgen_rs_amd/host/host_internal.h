@@ -1,7 +1,9 @@
-// host_internal.h — what pfile.cpp (the restatement of src/pfile.rs) and commands.cpp / import.cpp (the commands the reference does
-// not have) share below the public surface of pfile.h: status checks, file spans, the checked selection, a ctx with its buffers, the shards.
+// host_internal.h — what pfile.cpp (the restatement of src/pfile.rs) and commands.cpp / assoc.cpp / prune.cpp / import.cpp (the
+// commands the reference does not have) share below the public surface of pfile.h: status checks, file spans, the keyed tables that
+// score and assoc read, the checked selection, a ctx with its buffers, the shards.
 #pragma once
 #include <algorithm>
+#include <map>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -58,6 +60,58 @@ inline size_t column(const StringRecord &header, const char *name, const std::st
 
 // vcf_header's rule (src/pfile.rs:114-126): the first .psam column named IID
 inline size_t iid_column(const Pfile &pf, const StringRecord &sam_header) { return column(sam_header, "IID", pf.psam_path()); }
+
+// The reader under read_score_weights and read_value_table: a tab-separated file with a header line (a leading '#' allowed) whose
+// rows are n_lead text columns, the first of them the row's key, and one value per header cell behind them.  A PfileError names the
+// line of a row with another number of cells than the header and of a key that occurs twice (key_name says what the key is);
+// too_narrow words the one about a header without a value column.  cell(text, name, where) takes every value cell in row order
+// with its column's header cell and "<path> line <n>", and throws what it cannot parse.
+struct KeyedRows {
+    std::vector<std::string> names;               // the value columns' header cells
+    std::vector<std::vector<std::string>> lead;   // per leading column, per row
+    std::vector<size_t> lines;                    // the file line each row starts on
+};
+template <class Cell>
+KeyedRows read_keyed_rows(const std::string &path, size_t n_lead, const char *too_narrow, const char *key_name, const Cell &cell)
+{
+    const std::string data = read_file(path);
+    KeyedRows t;
+    TsvReader reader(data, !data.empty() && data[0] == '#' ? 1 : 0);
+    const StringRecord &head = reader.headers();
+    if (head.size() < n_lead + 1) throw PfileError(path + " line 1: " + too_narrow);
+    t.names.assign(head.begin() + n_lead, head.end());
+    t.lead.resize(n_lead);
+    const size_t C = t.names.size();
+    // the line a record starts on: the newlines in front of it, counted as the reader moves on
+    size_t counted = 0, line = 1;
+    auto line_at = [&](size_t pos) {
+        for (; counted < pos; counted++) line += data[counted] == '\n';
+        for (size_t p = pos; p < data.size() && (data[p] == '\n' || data[p] == '\r'); p++) {   // the empty lines the reader skips
+            line += data[p] == '\n';
+            counted = p + 1;
+        }
+        return line;
+    };
+    std::map<std::string, size_t> seen;   // key -> line
+    StringRecord rec;
+    for (;;) {
+        const size_t at = line_at(reader.position());
+        const std::string where = path + " line " + std::to_string(at);
+        bool more;
+        try {
+            more = reader.next(rec);
+        } catch (const CsvError &) {
+            throw PfileError(where + ": expected " + std::to_string(C + n_lead) + " tab-separated cells like the header's");
+        }
+        if (!more) break;
+        const auto dup = seen.emplace(rec[0], at);
+        if (!dup.second) throw PfileError(where + ": " + key_name + " '" + rec[0] + "' occurs twice (first on line " + std::to_string(dup.first->second) + ")");
+        for (size_t c = 0; c < C; c++) cell(rec[n_lead + c], t.names[c], where);
+        for (size_t l = 0; l < n_lead; l++) t.lead[l].push_back(rec[l]);
+        t.lines.push_back(at);
+    }
+    return t;
+}
 
 struct KeptSamples {
     std::vector<uint32_t> rows;

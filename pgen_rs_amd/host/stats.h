@@ -1,4 +1,4 @@
-// stats.h — the arithmetic of the commands in commands.cpp, in plain C++: numbers in, numbers out.  Nothing here touches a file, a
+// stats.h — the arithmetic of the commands in commands.cpp and assoc.cpp, in plain C++: numbers in, numbers out.  Nothing here touches a file, a
 // device, a clock or a PfileError, so tests/stats_check.cpp runs all of it as a stand-alone program under AddressSanitizer and UBSan
 // (tests/test_host_stats.py).  A condition a command words as an error comes back as a value.
 #pragma once

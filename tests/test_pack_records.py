@@ -68,7 +68,7 @@ def test_null_ctx_is_refused():
 
 
 def test_new_kernels_stay_off_the_environment_and_the_oracle():
-    for p in (REPO / "pgen_rs_amd" / "csrc" / "gt_pack.hip", REPO / "pgen_rs_amd" / "host" / "pfile.cpp", REPO / "pgen_rs_amd" / "host" / "commands.cpp",
+    for p in (REPO / "pgen_rs_amd" / "csrc" / "gt_pack.hip", REPO / "pgen_rs_amd" / "host" / "pfile.cpp", REPO / "pgen_rs_amd" / "host" / "commands.cpp", REPO / "pgen_rs_amd" / "host" / "assoc.cpp",
               REPO / "pgen_rs_amd" / "host" / "cli.cpp"):
         text = p.read_text()
         assert "getenv" not in text and "pgen_oracle" not in text and "pgo_" not in text, p

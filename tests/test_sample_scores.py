@@ -118,6 +118,18 @@ def test_usage_errors_exit_2(args):
     assert b"error:" in p.stderr
 
 
+# the whole message behind "<path> line <n>: " for every text of the table below
+WHOLE = {
+    b"ID\tA1\tS1\nv0\tG\t0.5\nv1\tG\tabc\n": b"weight 'abc' of score S1 is not a finite number",
+    b"#ID\tA1\tS1\tS2\nv0\tG\t0.5\t1\n\nv1\tG\t1\tnan\n": b"weight 'nan' of score S2 is not a finite number",
+    b"ID\tA1\tS1\nv0\tG\t1e39\n": b"weight '1e39' of score S1 is not a finite number",
+    b"ID\tA1\tS1\nv0\tG\t\n": b"weight '' of score S1 is not a finite number",
+    b"ID\tA1\tS1\nv0\tG\t1\nv1\tG\n": b"expected 3 tab-separated cells like the header's",
+    b"ID\tA1\tS1\tS2\nv0\tG\t1\t2\nv1\tG\t1\t2\t3\n": b"expected 4 tab-separated cells like the header's",
+    b"ID\tA1\tS1\nv0\tG\t1\nv1\tG\t1\nv0\tA\t2\n": b"variant ID 'v0' occurs twice (first on line 2)",
+}
+
+
 @pytest.mark.parametrize("text,line,what", [
     (b"ID\tA1\tS1\nv0\tG\t0.5\nv1\tG\tabc\n", 3, b"not a finite number"),
     (b"#ID\tA1\tS1\tS2\nv0\tG\t0.5\t1\n\nv1\tG\t1\tnan\n", 4, b"not a finite number"),      # (an empty line is skipped, and counted)
@@ -128,9 +140,11 @@ def test_usage_errors_exit_2(args):
     (b"ID\tA1\tS1\nv0\tG\t1\nv1\tG\t1\nv0\tA\t2\n", 4, b"occurs twice"),
 ])
 def test_weights_file_errors_exit_101_and_name_the_line(tiny, tmp_path, text, line, what):
-    p = run("score", str(tiny), "--weights", weights(tmp_path, text))
-    assert p.returncode == 101, p.stderr
-    assert b"w.tsv line %d:" % line in p.stderr and what in p.stderr, p.stderr
+    """The whole line of stderr: the reader under this file and assoc's value files is one, and its wording per file kind is pinned here."""
+    w = weights(tmp_path, text)
+    p = run("score", str(tiny), "--weights", w)
+    assert p.returncode == 101 and what in p.stderr, p.stderr
+    assert p.stderr == b"pgen-hip: %s line %d: %s\n" % (w.encode(), line, WHOLE[text]), p.stderr
 
 
 def test_header_without_a_score_column_exits_101(tiny, tmp_path):

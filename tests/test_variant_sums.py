@@ -193,6 +193,16 @@ def test_usage_errors_exit_2(args):
     assert b"error:" in p.stderr
 
 
+# the whole message behind "<path> line <n>: " for every text of the table below
+WHOLE = {
+    b"IID\tY1\nS0\t0.5\nS1\tabc\n": b"value 'abc' of column Y1 is not a finite number, NA or nan",
+    b"#IID\tY1\tY2\nS0\t0.5\t1\n\nS1\t1\t1e999\n": b"value '1e999' of column Y2 is not a finite number, NA or nan",
+    b"IID\tY1\nS0\t1\nS1\n": b"expected 2 tab-separated cells like the header's",
+    b"IID\tY1\tY2\nS0\t1\t2\nS1\t1\t2\t3\n": b"expected 3 tab-separated cells like the header's",
+    b"IID\tY1\nS0\t1\nS1\t1\nS0\t2\n": b"IID 'S0' occurs twice (first on line 2)",
+}
+
+
 @pytest.mark.parametrize("text,line,what", [
     (b"IID\tY1\nS0\t0.5\nS1\tabc\n", 3, b"not a finite number"),
     (b"#IID\tY1\tY2\nS0\t0.5\t1\n\nS1\t1\t1e999\n", 4, b"not a finite number"),      # (an empty line is skipped, and counted)
@@ -201,12 +211,15 @@ def test_usage_errors_exit_2(args):
     (b"IID\tY1\nS0\t1\nS1\t1\nS0\t2\n", 4, b"occurs twice"),
 ])
 def test_value_file_errors_exit_101_and_name_the_line(tiny, tmp_path, text, line, what):
-    p = run("assoc", str(tiny), "--pheno", put(tmp_path, "p.tsv", text))
-    assert p.returncode == 101, p.stderr
-    assert b"p.tsv line %d:" % line in p.stderr and what in p.stderr, p.stderr
+    """The whole line of stderr: the reader under these files and score's weights file is one, and its wording per file kind is pinned here."""
+    bad = put(tmp_path, "p.tsv", text)
+    p = run("assoc", str(tiny), "--pheno", bad)
+    assert p.returncode == 101 and what in p.stderr, p.stderr
+    assert p.stderr == b"pgen-hip: %s line %d: %s\n" % (bad.encode(), line, WHOLE[text]), p.stderr
     # the same reader takes the covariates
-    p = run("assoc", str(tiny), "--pheno", put(tmp_path, "ok.tsv", GOOD_PHENO), "--covar", put(tmp_path, "c.tsv", text))
-    assert p.returncode == 101 and b"c.tsv line %d:" % line in p.stderr and what in p.stderr, p.stderr
+    bad = put(tmp_path, "c.tsv", text)
+    p = run("assoc", str(tiny), "--pheno", put(tmp_path, "ok.tsv", GOOD_PHENO), "--covar", bad)
+    assert p.returncode == 101 and p.stderr == b"pgen-hip: %s line %d: %s\n" % (bad.encode(), line, WHOLE[text]), p.stderr
 
 
 def test_unknown_pheno_name_exits_101(tiny, tmp_path):
