@@ -173,6 +173,13 @@ u32p = C.POINTER(C.c_uint32)
 u64p = C.POINTER(C.c_uint64)
 ctx_p = C.c_void_p
 
+
+def _twins(name: str, *tail) -> dict:
+    """An entry that reads rows, and its ``_at`` twin: rows by (records, stride, variant_idx, n) or by (base, record_off, n), then one tail."""
+    return {name: (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, *tail]),
+            name + "_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, *tail])}
+
+
 # name -> (restype, argtypes); every symbol include/pgen_hip.h declares
 PROTOTYPES = {
     "pgenhip_abi_version": (C.c_uint32, []),
@@ -193,35 +200,23 @@ PROTOTYPES = {
     "pgenhip_sample_count": (C.c_uint32, [ctx_p]),
     "pgenhip_kept_count": (C.c_uint32, [ctx_p]),
     "pgenhip_gt_row_bytes": (C.c_uint64, [ctx_p]),
-    "pgenhip_decode_emit": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32]),
-    "pgenhip_decode_emit_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32]),
+    **_twins("pgenhip_decode_emit", C.c_void_p, C.c_uint64, C.c_uint32),
     "pgenhip_emit_lines": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]),
-    "pgenhip_genotype_counts": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
-    "pgenhip_genotype_counts_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
-    "pgenhip_sample_counts": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
-    "pgenhip_sample_counts_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
-    "pgenhip_sample_scores": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]),
-    "pgenhip_sample_scores_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]),
-    "pgenhip_variant_sums": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
-    "pgenhip_variant_sums_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
-    "pgenhip_variant_logistic": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
-    "pgenhip_variant_logistic_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
-    "pgenhip_decode_matrix": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
-    "pgenhip_decode_matrix_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
-    "pgenhip_sample_pair_stats": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
-    "pgenhip_sample_pair_stats_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
-    "pgenhip_sample_gram": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32]),
-    "pgenhip_sample_gram_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32]),
-    "pgenhip_gram_apply": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]),
-    "pgenhip_gram_apply_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]),
-    "pgenhip_pair_stats": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
-    "pgenhip_pair_stats_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
-    "pgenhip_pair_mask": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]),
-    "pgenhip_pair_mask_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]),
+    **_twins("pgenhip_genotype_counts", C.c_void_p, C.c_uint32),
+    **_twins("pgenhip_sample_counts", C.c_void_p, C.c_uint32),
+    **_twins("pgenhip_sample_scores", C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32),
+    **_twins("pgenhip_variant_sums", C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32),
+    **_twins("pgenhip_variant_logistic", C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_double,
+             C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32),
+    **_twins("pgenhip_decode_matrix", C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32),
+    **_twins("pgenhip_sample_pair_stats", C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32),
+    **_twins("pgenhip_sample_gram", C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32),
+    **_twins("pgenhip_gram_apply", C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32),
+    **_twins("pgenhip_pair_stats", C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32),
+    **_twins("pgenhip_pair_mask", C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32),
     "pgenhip_prune_resolve": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "pgenhip_packed_record_size": (C.c_uint32, [ctx_p]),
-    "pgenhip_pack_records": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]),
-    "pgenhip_pack_records_at": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]),
+    **_twins("pgenhip_pack_records", C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32),
     "pgenhip_parse_gt": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]),
     "pgenhip_join_records": (C.c_int, [ctx_p, C.POINTER(JoinPart), C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32]),
     "pgenhip_vcf_index_lines": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u64p, u64p]),

@@ -9,7 +9,8 @@ Reference seam: ``/root/reference/src/pfile.rs:156-192`` (``Pfile::output_vcf`` 
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence
+import math
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -107,6 +108,18 @@ def _ptr(t: Optional[torch.Tensor], byte_offset: int = 0) -> Optional[int]:
     return t.data_ptr() + byte_offset
 
 
+class _Rows(NamedTuple):
+    """A checked row selection (``GtEngine._rows`` / ``_rows_at``), as ``GtEngine._entry`` passes it to the C ABI."""
+    n: int          # n_variants, its default filled in
+    args: tuple     # the ABI's leading row arguments: (ptr, record_stride, variant_idx ptr, n) or (base ptr, record_off ptr, n)
+    suffix: str     # which twin of an entry takes them: "" or "_at"
+
+
+# pair_tables / pair_r2: (mode, dtype, what an allocated result holds where no pair is written, the shape of one pair's entry)
+_PAIR_TABLES = (_capi.PAIR_TABLE, torch.int32, 0, (4, 4))
+_PAIR_R2 = (_capi.PAIR_R2, torch.float32, float("nan"), ())
+
+
 class GtEngine:
     """One context = one device + one kept-sample list (src/pfile.rs:128 ``sam_idx_rcs``).
 
@@ -184,9 +197,9 @@ class GtEngine:
 
     # -- which rows a call reads: one contract for every method below (csrc/kernels.h, RowSource) ------------
     def _rows(self, records: torch.Tensor, record_stride: Optional[int], variant_idx: Optional[torch.Tensor],
-              n_variants: Optional[int], records_offset: int, vidx_msg: Optional[str] = None) -> tuple[int, int]:
-        """Checks a selection by stride or ``variant_idx`` and returns ``(record_stride, n_variants)`` with their defaults filled in:
-        the record size, and ``variant_idx``'s length or else the rows ``records`` holds.  ``vidx_msg``: the caller's one message
+              n_variants: Optional[int], records_offset: int, vidx_msg: Optional[str] = None) -> _Rows:
+        """Checks a selection by stride or ``variant_idx`` and returns it with the defaults filled in: the record size as the stride,
+        and ``variant_idx``'s length or else the rows ``records`` holds as ``n_variants``.  ``vidx_msg``: the caller's one message
         for both ``variant_idx`` refusals."""
         if record_stride is None:
             record_stride = self.record_size
@@ -210,10 +223,10 @@ class GtEngine:
             need_in = records_offset + (n_variants - 1) * record_stride + self.record_size
             if records.numel() < need_in:
                 raise ValueError(f"records too small: {records.numel()} < {need_in}")
-        return record_stride, n_variants
+        return _Rows(n_variants, (_ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants), "")
 
-    def _rows_at(self, base: torch.Tensor, record_off: torch.Tensor, n_variants: Optional[int], msg: Optional[str] = None) -> int:
-        """Checks a selection by byte offsets into ``base`` and returns ``n_variants`` (default: ``record_off``'s length)."""
+    def _rows_at(self, base: torch.Tensor, record_off: torch.Tensor, n_variants: Optional[int], msg: Optional[str] = None) -> _Rows:
+        """Checks a selection by byte offsets into ``base`` and returns it (``n_variants`` defaults to ``record_off``'s length)."""
         self._check_dev(base, "base")
         self._check_dev(record_off, "record_off")
         if record_off.dtype != torch.int64:
@@ -222,7 +235,77 @@ class GtEngine:
             n_variants = record_off.numel()
         if record_off.numel() < n_variants:
             raise ValueError(msg or "record_off has fewer than n_variants entries")
-        return n_variants
+        return _Rows(n_variants, (_ptr(base), _ptr(record_off), n_variants), "_at")
+
+    def _entry(self, name: str, rows: _Rows, *tail) -> None:
+        """Calls the twin of ABI entry ``name`` that takes ``rows``, with the arguments behind the row arguments."""
+        name += rows.suffix
+        check(getattr(lib, name)(self._ctx, *rows.args, *tail), name)
+
+    # -- what the methods below share: outputs given or allocated, checked inputs ------------------------------
+    def _flat_out(self, out: Optional[torch.Tensor], dtype: torch.dtype, need: int, msg: str, *, name: str = "out", floor: int = 1,
+                  fill=None) -> torch.Tensor:
+        """The flat output of ``dtype`` with at least ``need`` entries: the caller's, checked (``msg``: the refusal of a wrong
+        dtype or size, formatted with ``name``, ``dtype`` and ``need`` only when it is raised), or one of ``max(need, floor)``
+        entries allocated here, uninitialised or holding ``fill``."""
+        if out is None:
+            size = max(need, floor)
+            if fill is None:
+                return torch.empty(size, dtype=dtype, device=self.torch_device)
+            return torch.full((size,), fill, dtype=dtype, device=self.torch_device)
+        self._check_dev(out, name)
+        if out.dtype != dtype or out.numel() < need:
+            raise ValueError(msg.format(name=name, dtype=dtype, need=need))
+        return out if out.dim() == 1 else out.view(-1)   # (a view of a flat tensor is the one step here that costs a microsecond)
+
+    def _pitched_out(self, out: Optional[torch.Tensor], n_rows: int, row_bytes: int, out_stride: Optional[int], out_offset: int):
+        """A flat uint8 output that takes ``n_rows`` rows of ``row_bytes`` at pitch ``out_stride`` (default ``row_bytes``) from byte
+        ``out_offset``, given or allocated: (the flat tensor, the pitch, the ``(n_rows, row_bytes)`` view of the rows)."""
+        if out_stride is None:
+            out_stride = row_bytes
+        if out is None:
+            out = torch.empty(out_offset + max(n_rows * out_stride, row_bytes, 1), dtype=torch.uint8, device=self.torch_device)
+        self._check_dev(out, "out")
+        if out.dtype != torch.uint8:
+            raise ValueError("out must be a uint8 tensor")
+        if n_rows and out.numel() < out_offset + (n_rows - 1) * out_stride + row_bytes:
+            raise ValueError("out too small")
+        out = out.view(-1)
+        return out, out_stride, torch.as_strided(out, (n_rows, row_bytes), (out_stride, 1), out_offset)
+
+    def _column_matrix(self, t: torch.Tensor, name: str, dtype: torch.dtype, shape_msg: str, empty_too: bool = False) -> tuple[int, int]:
+        """Checks an input of shape ``(rows, C)`` or ``(rows,)``, contiguous along its columns (``empty_too``: also where it has no
+        row), and returns ``(row stride, C)``; a tensor of one row has no stride of its own and gets C."""
+        if not t.is_cuda or t.device.index != self.device:
+            raise ValueError(f"{name} must live on cuda:{self.device}")
+        if t.dtype != dtype or t.dim() not in (1, 2):
+            raise ValueError(shape_msg)
+        n_columns = t.shape[1] if t.dim() == 2 else 1
+        if t.dim() == 2 and n_columns > 1 and (empty_too or t.shape[0] > 0) and t.stride(1) != 1:
+            raise ValueError(f"{name} must be contiguous along its columns")
+        return int(t.stride(0) if t.shape[0] > 1 else n_columns), int(n_columns)
+
+    def _code_values(self, code_values: torch.Tensor, n_variants: int, kind: str = "") -> None:
+        self._check_dev(code_values, "code_values")
+        if code_values.dtype != torch.float64 or code_values.numel() < 4 * n_variants:
+            raise ValueError(f"code_values must be a {kind}float64 tensor of shape (n_variants, 4)")
+
+    def _rank_ranges(self, a, b) -> tuple[tuple[int, int], tuple[int, int]]:
+        """Two ``(begin, count)`` ranges of ranks in the kept list, default all K."""
+        a = (0, self.kept_count) if a is None else (int(a[0]), int(a[1]))
+        b = (0, self.kept_count) if b is None else (int(b[0]), int(b[1]))
+        if min(a + b) < 0:
+            raise ValueError("sample ranges are (begin, count) with begin, count >= 0")
+        return a, b
+
+    @staticmethod
+    def _pair_window(n_variants: int, n_left: Optional[int], window: int) -> int:
+        """``n_left`` with its default, all rows."""
+        if n_left is None:
+            n_left = n_variants
+        if window < 1 or not 0 <= n_left <= n_variants:
+            raise ValueError("need window >= 1 and 0 <= n_left <= n_variants")
+        return n_left
 
     # -- the hot path -----------------------------------------------------------------------
     def decode_emit(
@@ -243,45 +326,29 @@ class GtEngine:
         ``variant_idx``: optional int32/uint32 CUDA tensor of row numbers (gapped kept-variant lists).
         Row j is written at byte ``out_offset + j*out_stride`` of ``out`` (dense 4K+1 by default).
         """
-        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset,
-                                               "variant_idx must be a 32-bit integer tensor with >= n_variants entries")
-        if out_stride is None:
-            out_stride = self.gt_row_bytes
-        if out is None:
-            out = torch.empty(out_offset + n_variants * out_stride, dtype=torch.uint8, device=self.torch_device)
-        self._check_dev(out, "out")
-        if n_variants:
-            need_out = out_offset + (n_variants - 1) * out_stride + self.gt_row_bytes
-            if out.numel() < need_out:
-                raise ValueError(f"out too small: {out.numel()} < {need_out}")
-        check(
-            lib.pgenhip_decode_emit(
-                self._ctx,
-                _ptr(records, records_offset),
-                record_stride,
-                _ptr(variant_idx),
-                n_variants,
-                _ptr(out, out_offset),
-                out_stride,
-                kernel,
-            ),
-            "pgenhip_decode_emit",
-        )
-        return out
+        rows = self._rows(records, record_stride, variant_idx, n_variants, records_offset,
+                          "variant_idx must be a 32-bit integer tensor with >= n_variants entries")
+        return self._decode_emit(rows, out, out_stride, kernel, out_offset)
 
     def decode_emit_at(self, base: torch.Tensor, record_off: torch.Tensor, n_variants: int, out: Optional[torch.Tensor] = None,
                        out_stride: Optional[int] = None, kernel: int = KERNEL_AUTO) -> torch.Tensor:
         """GT segments of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor): the
         uncompressed records of a variable-width .pgen staged to HBM as it lies on disk."""
+        rows = self._rows_at(base, record_off, n_variants, "record_off must be an int64 tensor (u64 byte offsets) with >= n_variants entries")
+        return self._decode_emit(rows, out, out_stride, kernel)
+
+    def _decode_emit(self, rows: _Rows, out: Optional[torch.Tensor], out_stride: Optional[int], kernel: int, out_offset: int = 0) -> torch.Tensor:
+        n = rows.n
         if out_stride is None:
             out_stride = self.gt_row_bytes
-        if out is None:
-            out = torch.empty(max(n_variants, 1) * out_stride, dtype=torch.uint8, device=self.torch_device)
-        self._rows_at(base, record_off, n_variants, "record_off must be an int64 tensor (u64 byte offsets) with >= n_variants entries")
+        if out is None:   # for no rows the twins have always differed: nothing by stride, one row's pitch by offset
+            out = torch.empty(out_offset + (max(n, 1) if rows.suffix else n) * out_stride, dtype=torch.uint8, device=self.torch_device)
         self._check_dev(out, "out")
-        if n_variants and out.numel() < (n_variants - 1) * out_stride + self.gt_row_bytes:
-            raise ValueError("out too small")
-        check(lib.pgenhip_decode_emit_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, _ptr(out), out_stride, kernel), "pgenhip_decode_emit_at")
+        if n:
+            need_out = out_offset + (n - 1) * out_stride + self.gt_row_bytes
+            if out.numel() < need_out:
+                raise ValueError(f"out too small: {out.numel()} < {need_out}")
+        self._entry("pgenhip_decode_emit", rows, _ptr(out, out_offset), out_stride, kernel)
         return out
 
     def emit_lines(
@@ -341,23 +408,21 @@ class GtEngine:
         Rows are selected as in ``decode_emit``: row j's record is at byte ``records_offset + r*record_stride`` of ``records``,
         ``r = variant_idx[j]`` or ``j``.  ``n_variants`` defaults to ``variant_idx``'s length, else to the rows ``records`` holds.
         ``out``: optional int32 CUDA tensor of >= 4n entries (written from its first element; nothing else is touched)."""
-        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
-        out = self._counts_out(out, n_variants)
-        check(
-            lib.pgenhip_genotype_counts(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants,
-                                        _ptr(out), kernel),
-            "pgenhip_genotype_counts",
-        )
-        return out[: 4 * n_variants].view(n_variants, 4)
+        rows = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
+        return self._counts("pgenhip_genotype_counts", rows, rows.n, out, kernel)
 
     def genotype_counts_at(self, base: torch.Tensor, record_off: torch.Tensor, n_variants: Optional[int] = None,
                            out: Optional[torch.Tensor] = None, kernel: int = _capi.COUNT_AUTO) -> torch.Tensor:
         """``genotype_counts`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
-        n_variants = self._rows_at(base, record_off, n_variants)
-        out = self._counts_out(out, n_variants)
-        check(lib.pgenhip_genotype_counts_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, _ptr(out), kernel),
-              "pgenhip_genotype_counts_at")
-        return out[: 4 * n_variants].view(n_variants, 4)
+        rows = self._rows_at(base, record_off, n_variants)
+        return self._counts("pgenhip_genotype_counts", rows, rows.n, out, kernel)
+
+    def _counts(self, name: str, rows: _Rows, n: int, out: Optional[torch.Tensor], kernel: int, accumulate: bool = False) -> torch.Tensor:
+        """Both count entries: an ``(n, 4)`` int32 result, n the selected rows or the kept samples."""
+        out = self._flat_out(out, torch.int32, 4 * n, "out must be an int32 tensor with >= 4 * n_variants entries", floor=4,
+                             fill=0 if accumulate else None)
+        self._entry(name, rows, _ptr(out), kernel | (_capi.SCOUNT_ACCUMULATE if accumulate else 0))
+        return out[: 4 * n].view(n, 4)
 
     def sample_counts(
         self,
@@ -376,25 +441,14 @@ class GtEngine:
         Rows are selected as in ``genotype_counts`` (a row named twice in ``variant_idx`` counts twice).  ``out``: optional int32
         CUDA tensor of >= 4K entries (written from its first element; nothing else is touched).  ``accumulate``: add to what
         ``out`` holds instead of overwriting it."""
-        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
-        out = self._counts_out(out, self.kept_count, accumulate)
-        flags = kernel | (_capi.SCOUNT_ACCUMULATE if accumulate else 0)
-        check(
-            lib.pgenhip_sample_counts(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants,
-                                      _ptr(out), flags),
-            "pgenhip_sample_counts",
-        )
-        return out[: 4 * self.kept_count].view(self.kept_count, 4)
+        rows = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
+        return self._counts("pgenhip_sample_counts", rows, self.kept_count, out, kernel, accumulate)
 
     def sample_counts_at(self, base: torch.Tensor, record_off: torch.Tensor, n_variants: Optional[int] = None,
                          out: Optional[torch.Tensor] = None, kernel: int = _capi.SCOUNT_AUTO, accumulate: bool = False) -> torch.Tensor:
         """``sample_counts`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
-        n_variants = self._rows_at(base, record_off, n_variants)
-        out = self._counts_out(out, self.kept_count, accumulate)
-        flags = kernel | (_capi.SCOUNT_ACCUMULATE if accumulate else 0)
-        check(lib.pgenhip_sample_counts_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, _ptr(out), flags),
-              "pgenhip_sample_counts_at")
-        return out[: 4 * self.kept_count].view(self.kept_count, 4)
+        rows = self._rows_at(base, record_off, n_variants)
+        return self._counts("pgenhip_sample_counts", rows, self.kept_count, out, kernel, accumulate)
 
     # -- per-sample weighted dosage sums (polygenic scores) --------------------------------------
     def sample_scores(
@@ -420,61 +474,34 @@ class GtEngine:
         selection.  Rows are selected as in ``sample_counts``; ``n_variants`` defaults to ``weights``' rows.  ``out``: optional
         float64 CUDA tensor of >= K * C entries (written from its first element; nothing else is touched).  ``accumulate``:
         add to what ``out`` holds instead of overwriting it.  ``flags``: a forced shape (``_capi.SCORE_*``)."""
-        w_stride, n_columns, n_variants = self._score_weights(weights, miss, n_variants)
-        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
-        out = self._scores_out(out, n_columns, accumulate)
-        check(
-            lib.pgenhip_sample_scores(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants,
-                                      _ptr(weights), w_stride, n_columns, _ptr(miss), _ptr(out),
-                                      flags | (_capi.SCORE_ACCUMULATE if accumulate else 0)),
-            "pgenhip_sample_scores",
-        )
-        return out[: self.kept_count * n_columns].view(self.kept_count, n_columns)
+        return self._sample_scores(lambda n: self._rows(records, record_stride, variant_idx, n, records_offset), weights, miss, out,
+                                   accumulate, flags, n_variants)
 
     def sample_scores_at(self, base: torch.Tensor, record_off: torch.Tensor, weights: torch.Tensor, *, miss: Optional[torch.Tensor] = None,
                          out: Optional[torch.Tensor] = None, accumulate: bool = False, flags: int = 0,
                          n_variants: Optional[int] = None) -> torch.Tensor:
         """``sample_scores`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
-        w_stride, n_columns, n_variants = self._score_weights(weights, miss, n_variants)
-        n_variants = self._rows_at(base, record_off, n_variants)
-        out = self._scores_out(out, n_columns, accumulate)
-        check(
-            lib.pgenhip_sample_scores_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, _ptr(weights), w_stride, n_columns,
-                                         _ptr(miss), _ptr(out), flags | (_capi.SCORE_ACCUMULATE if accumulate else 0)),
-            "pgenhip_sample_scores_at",
-        )
-        return out[: self.kept_count * n_columns].view(self.kept_count, n_columns)
+        return self._sample_scores(lambda n: self._rows_at(base, record_off, n), weights, miss, out, accumulate, flags, n_variants)
 
-    def _score_weights(self, weights: torch.Tensor, miss: Optional[torch.Tensor], n_variants: Optional[int]) -> tuple[int, int, int]:
-        """Checks ``weights`` / ``miss`` and returns ``(w_stride, n_columns, n_variants)``."""
-        if not weights.is_cuda or weights.device.index != self.device:
-            raise ValueError(f"weights must live on cuda:{self.device}")
-        if weights.dtype != torch.float32 or weights.dim() not in (1, 2):
-            raise ValueError("weights must be a float32 tensor of shape (V, C) or (V,)")
-        rows = weights.shape[0]
-        n_columns = weights.shape[1] if weights.dim() == 2 else 1
-        if weights.dim() == 2 and n_columns > 1 and weights.stride(1) != 1:
-            raise ValueError("weights must be contiguous along its columns")
-        w_stride = weights.stride(0) if rows > 1 else n_columns
+    def _sample_scores(self, select, weights: torch.Tensor, miss: Optional[torch.Tensor], out: Optional[torch.Tensor], accumulate: bool,
+                       flags: int, n_variants: Optional[int]) -> torch.Tensor:
+        """``select(n_variants)`` checks the rows: they come after ``weights``, whose row count is the default of ``n_variants``."""
+        w_stride, n_columns = self._column_matrix(weights, "weights", torch.float32, "weights must be a float32 tensor of shape (V, C) or (V,)",
+                                                  empty_too=True)
         if n_variants is None:
-            n_variants = rows
-        if rows < n_variants:
+            n_variants = weights.shape[0]
+        if weights.shape[0] < n_variants:
             raise ValueError("weights has fewer than n_variants rows")
         if miss is not None:
             self._check_dev(miss, "miss")
             if miss.dtype != torch.float32 or miss.numel() < n_variants:
                 raise ValueError("miss must be a float32 tensor with >= n_variants entries")
-        return int(w_stride), int(n_columns), int(n_variants)
-
-    def _scores_out(self, out: Optional[torch.Tensor], n_columns: int, accumulate: bool) -> torch.Tensor:
+        rows = select(int(n_variants))
         need = self.kept_count * n_columns
-        if out is None:
-            make = torch.zeros if accumulate else torch.empty
-            return make(max(need, 1), dtype=torch.float64, device=self.torch_device)
-        self._check_dev(out, "out")
-        if out.dtype != torch.float64 or out.numel() < need:
-            raise ValueError("out must be a float64 tensor with >= K * C entries")
-        return out.view(-1)
+        out = self._flat_out(out, torch.float64, need, "out must be a float64 tensor with >= K * C entries", fill=0 if accumulate else None)
+        self._entry("pgenhip_sample_scores", rows, _ptr(weights), w_stride, n_columns, _ptr(miss), _ptr(out),
+                    flags | (_capi.SCORE_ACCUMULATE if accumulate else 0))
+        return out[:need].view(self.kept_count, n_columns)
 
     # -- per-variant sums of per-sample values by genotype code -----------------------------------
     def variant_sums(
@@ -497,51 +524,23 @@ class GtEngine:
         from the tensor and row k belongs to the k-th kept sample.  Rows are selected as in ``genotype_counts``.  ``out``: optional
         float64 CUDA tensor of >= n_variants * C * 4 entries (written from its first element; nothing else is touched).
         ``flags``: a forced shape (``_capi.VSUM_*``)."""
-        v_stride, n_columns = self._vsum_values(values)
-        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
-        out = self._vsum_out(out, n_variants, n_columns)
-        check(
-            lib.pgenhip_variant_sums(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants,
-                                     _ptr(values), v_stride, n_columns, _ptr(out), flags),
-            "pgenhip_variant_sums",
-        )
-        return out[: n_variants * n_columns * 4].view(n_variants, n_columns, 4)
+        return self._variant_sums(lambda: self._rows(records, record_stride, variant_idx, n_variants, records_offset), values, out, flags)
 
     def variant_sums_at(self, base: torch.Tensor, record_off: torch.Tensor, values: torch.Tensor, *, out: Optional[torch.Tensor] = None,
                         flags: int = 0, n_variants: Optional[int] = None) -> torch.Tensor:
         """``variant_sums`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
-        v_stride, n_columns = self._vsum_values(values)
-        n_variants = self._rows_at(base, record_off, n_variants)
-        out = self._vsum_out(out, n_variants, n_columns)
-        check(
-            lib.pgenhip_variant_sums_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, _ptr(values), v_stride, n_columns,
-                                        _ptr(out), flags),
-            "pgenhip_variant_sums_at",
-        )
-        return out[: n_variants * n_columns * 4].view(n_variants, n_columns, 4)
+        return self._variant_sums(lambda: self._rows_at(base, record_off, n_variants), values, out, flags)
 
-    def _vsum_values(self, values: torch.Tensor) -> tuple[int, int]:
-        """Checks ``values`` and returns ``(v_stride, n_columns)``."""
-        if not values.is_cuda or values.device.index != self.device:
-            raise ValueError(f"values must live on cuda:{self.device}")
-        if values.dtype != torch.float64 or values.dim() not in (1, 2):
-            raise ValueError("values must be a float64 tensor of shape (K, C) or (K,)")
-        n_columns = values.shape[1] if values.dim() == 2 else 1
+    def _variant_sums(self, select, values: torch.Tensor, out: Optional[torch.Tensor], flags: int) -> torch.Tensor:
+        """``select()`` checks the rows, after ``values`` as ever."""
+        v_stride, n_columns = self._column_matrix(values, "values", torch.float64, "values must be a float64 tensor of shape (K, C) or (K,)")
         if values.shape[0] < self.kept_count:
             raise ValueError("values has fewer than K rows")
-        if values.dim() == 2 and n_columns > 1 and values.shape[0] > 0 and values.stride(1) != 1:
-            raise ValueError("values must be contiguous along its columns")
-        v_stride = values.stride(0) if values.shape[0] > 1 else n_columns
-        return int(v_stride), int(n_columns)
-
-    def _vsum_out(self, out: Optional[torch.Tensor], n_variants: int, n_columns: int) -> torch.Tensor:
-        need = n_variants * n_columns * 4
-        if out is None:
-            return torch.empty(max(need, 1), dtype=torch.float64, device=self.torch_device)
-        self._check_dev(out, "out")
-        if out.dtype != torch.float64 or out.numel() < need:
-            raise ValueError("out must be a float64 tensor with >= n_variants * C * 4 entries")
-        return out.view(-1)
+        rows = select()
+        need = rows.n * n_columns * 4
+        out = self._flat_out(out, torch.float64, need, "out must be a float64 tensor with >= n_variants * C * 4 entries")
+        self._entry("pgenhip_variant_sums", rows, _ptr(values), v_stride, n_columns, _ptr(out), flags)
+        return out[:need].view(rows.n, n_columns, 4)
 
     # -- per-variant logistic regression ----------------------------------------------------------
     def variant_logistic(
@@ -575,16 +574,8 @@ class GtEngine:
         float64, n_cov coefficients of the null model.  Rows are selected as in ``variant_sums``.  ``coef`` / ``se`` / ``status``:
         optional outputs (written from their first element, ``coef`` with rows of n_cov + 1).  ``flags``: a forced shape
         (``_capi.LOGIT_*``)."""
-        x_stride, n_cov = self._logit_inputs(design, y, start)
-        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
-        coef, se, status = self._logit_out(code_values, n_variants, n_cov, coef, se, status)
-        check(
-            lib.pgenhip_variant_logistic(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants,
-                                         _ptr(code_values), _ptr(design), x_stride, n_cov, _ptr(y), _ptr(start), max_iter, tol,
-                                         _ptr(coef), n_cov + 1, _ptr(se), _ptr(status), flags),
-            "pgenhip_variant_logistic",
-        )
-        return coef[: n_variants * (n_cov + 1)].view(n_variants, n_cov + 1), se[:n_variants], status[:n_variants]
+        return self._variant_logistic(lambda: self._rows(records, record_stride, variant_idx, n_variants, records_offset), code_values, design, y,
+                                      start, max_iter, tol, coef, se, status, flags)
 
     def variant_logistic_at(self, base: torch.Tensor, record_off: torch.Tensor, code_values: torch.Tensor, design: torch.Tensor,
                             y: torch.Tensor, start: torch.Tensor, *, max_iter: int = 25, tol: float = 1e-9,
@@ -592,53 +583,33 @@ class GtEngine:
                             status: Optional[torch.Tensor] = None, flags: int = 0,
                             n_variants: Optional[int] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """``variant_logistic`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
-        x_stride, n_cov = self._logit_inputs(design, y, start)
-        n_variants = self._rows_at(base, record_off, n_variants)
-        coef, se, status = self._logit_out(code_values, n_variants, n_cov, coef, se, status)
-        check(
-            lib.pgenhip_variant_logistic_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, _ptr(code_values), _ptr(design),
-                                            x_stride, n_cov, _ptr(y), _ptr(start), max_iter, tol, _ptr(coef), n_cov + 1, _ptr(se),
-                                            _ptr(status), flags),
-            "pgenhip_variant_logistic_at",
-        )
-        return coef[: n_variants * (n_cov + 1)].view(n_variants, n_cov + 1), se[:n_variants], status[:n_variants]
+        return self._variant_logistic(lambda: self._rows_at(base, record_off, n_variants), code_values, design, y, start, max_iter, tol,
+                                      coef, se, status, flags)
 
-    def _logit_inputs(self, design: torch.Tensor, y: torch.Tensor, start: torch.Tensor) -> tuple[int, int]:
-        """Checks ``design``, ``y`` and ``start`` and returns ``(x_stride, n_cov)``."""
+    def _variant_logistic(self, select, code_values: torch.Tensor, design: torch.Tensor, y: torch.Tensor, start: torch.Tensor,
+                          max_iter: int, tol: float, coef: Optional[torch.Tensor], se: Optional[torch.Tensor],
+                          status: Optional[torch.Tensor], flags: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``select()`` checks the rows, after the design, ``y`` and ``start`` as ever."""
         for t, name in ((design, "design"), (y, "y"), (start, "start")):
             if not t.is_cuda or t.device.index != self.device:
                 raise ValueError(f"{name} must live on cuda:{self.device}")
             if t.dtype != torch.float64:
                 raise ValueError(f"{name} must be a float64 tensor")
-        if design.dim() not in (1, 2):
-            raise ValueError("design must be a float64 tensor of shape (K, n_cov) or (K,)")
-        n_cov = design.shape[1] if design.dim() == 2 else 1
+        x_stride, n_cov = self._column_matrix(design, "design", torch.float64, "design must be a float64 tensor of shape (K, n_cov) or (K,)")
         if design.shape[0] < self.kept_count or y.numel() < self.kept_count:
             raise ValueError("design or y has fewer than K rows")
-        if design.dim() == 2 and n_cov > 1 and design.shape[0] > 0 and design.stride(1) != 1:
-            raise ValueError("design must be contiguous along its columns")
         if not y.is_contiguous() or not start.is_contiguous() or start.numel() < n_cov:
             raise ValueError("y and start must be contiguous, start with >= n_cov entries")
-        x_stride = design.stride(0) if design.shape[0] > 1 else n_cov
-        return int(x_stride), int(n_cov)
-
-    def _logit_out(self, code_values: torch.Tensor, n_variants: int, n_cov: int, coef: Optional[torch.Tensor],
-                   se: Optional[torch.Tensor], status: Optional[torch.Tensor]) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        self._check_dev(code_values, "code_values")
-        if code_values.dtype != torch.float64 or code_values.numel() < 4 * n_variants or not code_values.is_contiguous():
-            raise ValueError("code_values must be a contiguous float64 tensor of shape (n_variants, 4)")
-        outs = []
-        for t, name, dtype, need in ((coef, "coef", torch.float64, n_variants * (n_cov + 1)), (se, "se", torch.float64, n_variants),
-                                     (status, "status", torch.int32, n_variants)):
-            if t is None:
-                t = torch.empty(max(need, 1), dtype=dtype, device=self.torch_device)
-            else:
-                self._check_dev(t, name)
-                if t.dtype != dtype or t.numel() < need or not t.is_contiguous():
-                    raise ValueError(f"{name} must be a contiguous {dtype} tensor with >= {need} entries")
-                t = t.view(-1)
-            outs.append(t)
-        return outs[0], outs[1], outs[2]
+        rows = select()
+        n = rows.n
+        self._code_values(code_values, n, "contiguous ")
+        coef, se, status = (
+            self._flat_out(t, dtype, need, "{name} must be a contiguous {dtype} tensor with >= {need} entries", name=name)
+            for t, name, dtype, need in ((coef, "coef", torch.float64, n * (n_cov + 1)), (se, "se", torch.float64, n),
+                                         (status, "status", torch.int32, n)))
+        self._entry("pgenhip_variant_logistic", rows, _ptr(code_values), _ptr(design), x_stride, n_cov, _ptr(y), _ptr(start), max_iter,
+                    tol, _ptr(coef), n_cov + 1, _ptr(se), _ptr(status), flags)
+        return coef[: n * (n_cov + 1)].view(n, n_cov + 1), se[:n], status[:n]
 
     # -- numeric genotype matrix ---------------------------------------------------------------
     def decode_matrix(
@@ -666,23 +637,19 @@ class GtEngine:
         Without ``out`` the variant-major result is contiguous; the sample-major result is a ``[:, :V]`` view of rows allocated at
         a pitch rounded up to 128 bytes, so that the transpose kernel stores whole lines: ``.contiguous()`` is the caller's choice
         and cost."""
-        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
-        out, res, stride, tab = self._matrix_out(out, n_variants, dtype, sample_major, values)
-        flags = kernel | (_capi.MATRIX_SAMPLE_MAJOR if sample_major else 0)
-        check(lib.pgenhip_decode_matrix(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants,
-                                        out.data_ptr(), stride, out.element_size(), tab.ctypes.data_as(C.c_void_p), flags),
-              "pgenhip_decode_matrix")
-        return res
+        rows = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
+        return self._decode_matrix(rows, dtype, sample_major, values, out, kernel)
 
     def decode_matrix_at(self, base: torch.Tensor, record_off: torch.Tensor, n_variants: Optional[int] = None, *,
                          dtype: torch.dtype = torch.int8, sample_major: bool = False, values=None,
                          out: Optional[torch.Tensor] = None, kernel: int = _capi.MATRIX_AUTO) -> torch.Tensor:
         """``decode_matrix`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
-        n_variants = self._rows_at(base, record_off, n_variants)
-        out, res, stride, tab = self._matrix_out(out, n_variants, dtype, sample_major, values)
-        flags = kernel | (_capi.MATRIX_SAMPLE_MAJOR if sample_major else 0)
-        check(lib.pgenhip_decode_matrix_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, out.data_ptr(), stride,
-                                           out.element_size(), tab.ctypes.data_as(C.c_void_p), flags), "pgenhip_decode_matrix_at")
+        return self._decode_matrix(self._rows_at(base, record_off, n_variants), dtype, sample_major, values, out, kernel)
+
+    def _decode_matrix(self, rows: _Rows, dtype: torch.dtype, sample_major: bool, values, out: Optional[torch.Tensor], kernel: int) -> torch.Tensor:
+        out, res, stride, tab = self._matrix_out(out, rows.n, dtype, sample_major, values)
+        self._entry("pgenhip_decode_matrix", rows, out.data_ptr(), stride, out.element_size(), tab.ctypes.data_as(C.c_void_p),
+                    kernel | (_capi.MATRIX_SAMPLE_MAJOR if sample_major else 0))
         return res
 
     # -- packed records of the kept samples -----------------------------------------------------
@@ -703,44 +670,26 @@ class GtEngine:
         0-3 written for input codes 0-3 (``BED_CODE_MAP`` for PLINK 1 .bed), default the identity.  ``out``: a flat uint8 CUDA
         tensor; row j goes to byte ``out_offset + j*out_stride`` (default stride ``R_K``) and nothing else is touched.  The result
         is a view of ``out`` with row pitch ``out_stride``."""
-        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
-        out, stride, cmap = self._pack_out(out, n_variants, out_stride, out_offset, code_map)
-        check(lib.pgenhip_pack_records(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants,
-                                       _ptr(out, out_offset), stride, cmap, shape), "pgenhip_pack_records")
-        return self._pack_view(out, n_variants, stride, out_offset)
+        rows = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
+        return self._pack_records(rows, out, out_stride, out_offset, code_map, shape)
 
     def pack_records_at(self, base: torch.Tensor, record_off: torch.Tensor, out: Optional[torch.Tensor] = None, *,
                         out_stride: Optional[int] = None, code_map=None, shape: int = _capi.PACK_AUTO,
                         n_variants: Optional[int] = None, out_offset: int = 0) -> torch.Tensor:
         """``pack_records`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
-        n_variants = self._rows_at(base, record_off, n_variants)
-        out, stride, cmap = self._pack_out(out, n_variants, out_stride, out_offset, code_map)
-        check(lib.pgenhip_pack_records_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, _ptr(out, out_offset), stride, cmap,
-                                          shape), "pgenhip_pack_records_at")
-        return self._pack_view(out, n_variants, stride, out_offset)
+        return self._pack_records(self._rows_at(base, record_off, n_variants), out, out_stride, out_offset, code_map, shape)
 
-    def _pack_out(self, out: Optional[torch.Tensor], n_variants: int, out_stride: Optional[int], out_offset: int, code_map):
-        """(the flat output, the row stride, the map as four bytes or None)"""
-        rk = self.packed_record_size
-        if out_stride is None:
-            out_stride = rk
-        if out is None:
-            out = torch.empty(out_offset + max(n_variants * out_stride, rk, 1), dtype=torch.uint8, device=self.torch_device)
-        self._check_dev(out, "out")
-        if out.dtype != torch.uint8:
-            raise ValueError("out must be a uint8 tensor")
-        if n_variants and out.numel() < out_offset + (n_variants - 1) * out_stride + rk:
-            raise ValueError("out too small")
+    def _pack_records(self, rows: _Rows, out: Optional[torch.Tensor], out_stride: Optional[int], out_offset: int, code_map,
+                      shape: int) -> torch.Tensor:
+        out, out_stride, view = self._pitched_out(out, rows.n, self.packed_record_size, out_stride, out_offset)
         cmap = None
         if code_map is not None:
             vals = [int(v) for v in code_map]
             if len(vals) != 4 or any(not 0 <= v <= 255 for v in vals):
                 raise ValueError("code_map must hold four codes (for input codes 0, 1, 2, 3)")
             cmap = (C.c_uint8 * 4)(*vals)
-        return out.view(-1), out_stride, cmap
-
-    def _pack_view(self, out: torch.Tensor, n_variants: int, stride: int, out_offset: int) -> torch.Tensor:
-        return torch.as_strided(out, (n_variants, self.packed_record_size), (stride, 1), out_offset)
+        self._entry("pgenhip_pack_records", rows, _ptr(out, out_offset), out_stride, cmap, shape)
+        return view
 
     # -- sample-wise join of records --------------------------------------------------------------
     def join_records(self, parts, n_variants: Optional[int] = None, *, out: Optional[torch.Tensor] = None,
@@ -767,20 +716,10 @@ class GtEngine:
                 if flip.dtype != torch.uint8 or flip.numel() < n_variants:
                     raise ValueError("flip must be a uint8 tensor of n_variants entries")
             table[i] = _capi.JoinPart(_ptr(base), _ptr(record_off), _ptr(flip), int(count), 0)
-        r = self.record_size
-        if out_stride is None:
-            out_stride = r
-        if out is None:
-            out = torch.empty(out_offset + max(n_variants * out_stride, r, 1), dtype=torch.uint8, device=self.torch_device)
-        self._check_dev(out, "out")
-        if out.dtype != torch.uint8:
-            raise ValueError("out must be a uint8 tensor")
-        if n_variants and out.numel() < out_offset + (n_variants - 1) * out_stride + r:
-            raise ValueError("out too small")
-        out = out.view(-1)
+        out, out_stride, view = self._pitched_out(out, n_variants, self.record_size, out_stride, out_offset)
         check(lib.pgenhip_join_records(self._ctx, table, len(parts), n_variants, _ptr(out, out_offset), out_stride, shape),
               "pgenhip_join_records")
-        return torch.as_strided(out, (n_variants, r), (out_stride, 1), out_offset)
+        return view
 
     # -- GT text to records ---------------------------------------------------------------------
     def parse_gt(self, text: torch.Tensor, field_off: torch.Tensor, line_end: torch.Tensor, *, out: Optional[torch.Tensor] = None,
@@ -809,25 +748,15 @@ class GtEngine:
             text_len = text.numel() - text_offset
         if text_offset < 0 or text_len < 0 or text_offset + text_len > text.numel():
             raise ValueError("text_offset / text_len lie outside text")
-        r = self.record_size
-        if out_stride is None:
-            out_stride = r
-        if out is None:
-            out = torch.empty(out_offset + max(n_lines * out_stride, r, 1), dtype=torch.uint8, device=self.torch_device)
-        self._check_dev(out, "out")
-        if out.dtype != torch.uint8:
-            raise ValueError("out must be a uint8 tensor")
-        if n_lines and out.numel() < out_offset + (n_lines - 1) * out_stride + r:
-            raise ValueError("out too small")
+        out, out_stride, view = self._pitched_out(out, n_lines, self.record_size, out_stride, out_offset)
         if line_flags is None:
             line_flags = torch.empty(max(n_lines, 1), dtype=torch.int32, device=self.torch_device)
         self._check_dev(line_flags, "line_flags")
         if line_flags.dtype not in (torch.int32, torch.uint32) or line_flags.numel() < n_lines:
             raise ValueError("line_flags must be a 32-bit integer tensor of n_lines entries")
-        out = out.view(-1)
         check(lib.pgenhip_parse_gt(self._ctx, _ptr(text, text_offset), text_len, _ptr(field_off), _ptr(line_end), n_lines,
                                    _ptr(out, out_offset), out_stride, _ptr(line_flags), shape), "pgenhip_parse_gt")
-        return torch.as_strided(out, (n_lines, r), (out_stride, 1), out_offset), line_flags[:n_lines]
+        return view, line_flags[:n_lines]
 
     # -- windowed pairwise tables / r^2 ---------------------------------------------------------
     def pair_tables(self, records: torch.Tensor, record_stride: Optional[int] = None, variant_idx: Optional[torch.Tensor] = None,
@@ -841,20 +770,12 @@ class GtEngine:
         that overlap by ``window`` rows compute no pair twice.  Entries with ``i + d >= n_variants`` are NOT written by the
         library: they keep what the buffer held.  Without ``out`` the result is allocated with zeros, so that ragged end reads as
         empty tables; a caller-supplied ``out`` (int32, >= 16 * n_left * W entries, 16-byte aligned) is used as given."""
-        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
-        n_left, out = self._pair_out(out, n_variants, n_left, window, torch.int32, 16)
-        check(lib.pgenhip_pair_stats(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants, n_left,
-                                     window, _ptr(out), _capi.PAIR_TABLE), "pgenhip_pair_stats")
-        return out[: 16 * n_left * window].view(n_left, window, 4, 4)
+        return self._pair_stats(self._rows(records, record_stride, variant_idx, n_variants, records_offset), n_left, window, out, *_PAIR_TABLES)
 
     def pair_tables_at(self, base: torch.Tensor, record_off: torch.Tensor, n_variants: Optional[int] = None, *,
                        n_left: Optional[int] = None, window: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``pair_tables`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
-        n_variants = self._rows_at(base, record_off, n_variants)
-        n_left, out = self._pair_out(out, n_variants, n_left, window, torch.int32, 16)
-        check(lib.pgenhip_pair_stats_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, n_left, window, _ptr(out),
-                                        _capi.PAIR_TABLE), "pgenhip_pair_stats_at")
-        return out[: 16 * n_left * window].view(n_left, window, 4, 4)
+        return self._pair_stats(self._rows_at(base, record_off, n_variants), n_left, window, out, *_PAIR_TABLES)
 
     def pair_r2(self, records: torch.Tensor, record_stride: Optional[int] = None, variant_idx: Optional[torch.Tensor] = None,
                 n_variants: Optional[int] = None, *, n_left: Optional[int] = None, window: int,
@@ -863,36 +784,21 @@ class GtEngine:
         i + d, computed from the pair's table over the samples called in both rows; NaN where a row is monomorphic among them (or
         none is).  Entries with ``i + d >= n_variants`` are not written: NaN in a result allocated here, untouched in ``out``
         (float32, >= n_left * W entries)."""
-        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
-        n_left, out = self._pair_out(out, n_variants, n_left, window, torch.float32, 1)
-        check(lib.pgenhip_pair_stats(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants, n_left,
-                                     window, _ptr(out), _capi.PAIR_R2), "pgenhip_pair_stats")
-        return out[: n_left * window].view(n_left, window)
+        return self._pair_stats(self._rows(records, record_stride, variant_idx, n_variants, records_offset), n_left, window, out, *_PAIR_R2)
 
     def pair_r2_at(self, base: torch.Tensor, record_off: torch.Tensor, n_variants: Optional[int] = None, *,
                    n_left: Optional[int] = None, window: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``pair_r2`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
-        n_variants = self._rows_at(base, record_off, n_variants)
-        n_left, out = self._pair_out(out, n_variants, n_left, window, torch.float32, 1)
-        check(lib.pgenhip_pair_stats_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, n_left, window, _ptr(out),
-                                        _capi.PAIR_R2), "pgenhip_pair_stats_at")
-        return out[: n_left * window].view(n_left, window)
+        return self._pair_stats(self._rows_at(base, record_off, n_variants), n_left, window, out, *_PAIR_R2)
 
-    def _pair_out(self, out: Optional[torch.Tensor], n_variants: int, n_left: Optional[int], window: int, dtype: torch.dtype,
-                  per_pair: int):
-        """(n_left with its default, the flat output: given, or zeros for tables / NaN for r^2)"""
-        if n_left is None:
-            n_left = n_variants
-        if window < 1 or not 0 <= n_left <= n_variants:
-            raise ValueError("need window >= 1 and 0 <= n_left <= n_variants")
-        need = per_pair * n_left * window
-        if out is None:
-            fill = 0 if dtype == torch.int32 else float("nan")
-            return n_left, torch.full((max(need, 4),), fill, dtype=dtype, device=self.torch_device)
-        self._check_dev(out, "out")
-        if out.dtype != dtype or out.numel() < need:
-            raise ValueError(f"out must be a {dtype} tensor with >= {need} entries")
-        return n_left, out.view(-1)
+    def _pair_stats(self, rows: _Rows, n_left: Optional[int], window: int, out: Optional[torch.Tensor], mode: int, dtype: torch.dtype,
+                    fill, per_pair: tuple) -> torch.Tensor:
+        """``mode``'s result: ``per_pair`` entries of ``dtype`` for every pair, ``fill`` where the library writes none."""
+        n_left = self._pair_window(rows.n, n_left, window)
+        need = n_left * window * math.prod(per_pair)
+        out = self._flat_out(out, dtype, need, "out must be a {dtype} tensor with >= {need} entries", floor=4, fill=fill)
+        self._entry("pgenhip_pair_stats", rows, n_left, window, _ptr(out), mode)
+        return out[:need].view(n_left, window, *per_pair)
 
     # -- LD pruning: one bit per pair, the greedy independent set -------------------------------------
     def pair_mask(self, records: torch.Tensor, record_stride: Optional[int] = None, variant_idx: Optional[torch.Tensor] = None,
@@ -906,29 +812,22 @@ class GtEngine:
         of ``bwd``'s row j is then set.  The call only ORs bits in: masks that are given (int32, ``mask_stride`` words per row,
         default ``ceil(window / 32)``) keep what they hold, masks allocated here start as zeros.  ``want_bwd=False`` without
         ``bwd`` leaves the backward mask out (``None``)."""
-        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
-        n_left, mask_stride, fwd, bwd, key_p = self._mask_out(n_variants, n_left, window, key, fwd, bwd, want_bwd, mask_stride)
-        check(lib.pgenhip_pair_mask(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants, n_left,
-                                    window, min_r2, key_p, max_span, _ptr(fwd), _ptr(bwd), mask_stride, 0), "pgenhip_pair_mask")
-        return fwd, bwd
+        rows = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
+        return self._pair_mask(rows, n_left, window, min_r2, key, max_span, fwd, bwd, want_bwd, mask_stride)
 
     def pair_mask_at(self, base: torch.Tensor, record_off: torch.Tensor, n_variants: Optional[int] = None, *,
                      n_left: Optional[int] = None, window: int, min_r2: float, key: Optional[torch.Tensor] = None, max_span: int = 0,
                      fwd: Optional[torch.Tensor] = None, bwd: Optional[torch.Tensor] = None, want_bwd: bool = True,
                      mask_stride: Optional[int] = None) -> tuple[torch.Tensor, Optional[torch.Tensor]]:
         """``pair_mask`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
-        n_variants = self._rows_at(base, record_off, n_variants)
-        n_left, mask_stride, fwd, bwd, key_p = self._mask_out(n_variants, n_left, window, key, fwd, bwd, want_bwd, mask_stride)
-        check(lib.pgenhip_pair_mask_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, n_left, window, min_r2, key_p, max_span,
-                                       _ptr(fwd), _ptr(bwd), mask_stride, 0), "pgenhip_pair_mask_at")
-        return fwd, bwd
+        rows = self._rows_at(base, record_off, n_variants)
+        return self._pair_mask(rows, n_left, window, min_r2, key, max_span, fwd, bwd, want_bwd, mask_stride)
 
-    def _mask_out(self, n_variants: int, n_left: Optional[int], window: int, key, fwd, bwd, want_bwd: bool, mask_stride: Optional[int]):
-        """(n_left and mask_stride with their defaults, the masks: given, or zeros, and the key's pointer)"""
-        if n_left is None:
-            n_left = n_variants
-        if window < 1 or not 0 <= n_left <= n_variants:
-            raise ValueError("need window >= 1 and 0 <= n_left <= n_variants")
+    def _pair_mask(self, rows: _Rows, n_left: Optional[int], window: int, min_r2: float, key: Optional[torch.Tensor], max_span: int,
+                   fwd: Optional[torch.Tensor], bwd: Optional[torch.Tensor], want_bwd: bool,
+                   mask_stride: Optional[int]) -> tuple[torch.Tensor, Optional[torch.Tensor]]:
+        n = rows.n
+        n_left = self._pair_window(n, n_left, window)
         words = (window + 31) // 32
         if mask_stride is None:
             mask_stride = words
@@ -936,18 +835,18 @@ class GtEngine:
             raise ValueError(f"mask_stride must be >= ceil(window / 32) = {words}")
         if key is not None:
             self._check_dev(key, "key")
-            if key.dtype != torch.int64 or key.numel() < n_variants:
+            if key.dtype != torch.int64 or key.numel() < n:
                 raise ValueError("key must be an int64 tensor (u64 keys) with >= n_variants entries")
-        masks = []
+        masks, need = [], n * mask_stride
         for name, m, want in (("fwd", fwd, True), ("bwd", bwd, want_bwd)):
-            if m is None:
-                m = torch.zeros((n_variants, mask_stride), dtype=torch.int32, device=self.torch_device) if want else None
-            else:
-                self._check_dev(m, name)
-                if m.dtype != torch.int32 or m.numel() < n_variants * mask_stride:
-                    raise ValueError(f"{name} must be an int32 tensor with >= n_variants * mask_stride = {n_variants * mask_stride} entries")
+            if m is not None:     # a given mask is checked like a flat output and returned as it came, in its own shape
+                self._flat_out(m, torch.int32, need, "{name} must be an int32 tensor with >= n_variants * mask_stride = {need} entries", name=name)
+            elif want:
+                m = torch.zeros((n, mask_stride), dtype=torch.int32, device=self.torch_device)
             masks.append(m)
-        return n_left, mask_stride, masks[0], masks[1], _ptr(key)
+        fwd, bwd = masks
+        self._entry("pgenhip_pair_mask", rows, n_left, window, min_r2, _ptr(key), max_span, _ptr(fwd), _ptr(bwd), mask_stride, 0)
+        return fwd, bwd
 
     def prune_resolve(self, fwd: torch.Tensor, bwd: torch.Tensor, window: int, priority: Optional[torch.Tensor] = None,
                       state: Optional[torch.Tensor] = None, shape: int = _capi.PRUNE_AUTO, max_calls: Optional[int] = None,
@@ -1005,39 +904,22 @@ class GtEngine:
         ``sample_counts``.  ``out``: optional int32 CUDA tensor of >= 16 * a_count * b_count entries, 16-byte aligned (written from
         its first element; nothing else is touched).  ``accumulate``: add to what ``out`` holds instead of overwriting it.
         ``kernel``: a forced shape (``_capi.SPAIR_*``)."""
-        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
-        a, b, out = self._spair_out(a, b, out, accumulate)
-        check(lib.pgenhip_sample_pair_stats(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants,
-                                            a[0], a[1], b[0], b[1], _ptr(out), kernel | (_capi.SPAIR_ACCUMULATE if accumulate else 0)),
-              "pgenhip_sample_pair_stats")
-        return out[: 16 * a[1] * b[1]].view(a[1], b[1], 4, 4)
+        return self._sample_pair_tables(self._rows(records, record_stride, variant_idx, n_variants, records_offset), a, b, out, accumulate, kernel)
 
     def sample_pair_tables_at(self, base: torch.Tensor, record_off: torch.Tensor, n_variants: Optional[int] = None, *,
                               a: Optional[tuple[int, int]] = None, b: Optional[tuple[int, int]] = None,
                               out: Optional[torch.Tensor] = None, accumulate: bool = False,
                               kernel: int = _capi.SPAIR_AUTO) -> torch.Tensor:
         """``sample_pair_tables`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
-        n_variants = self._rows_at(base, record_off, n_variants)
-        a, b, out = self._spair_out(a, b, out, accumulate)
-        check(lib.pgenhip_sample_pair_stats_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, a[0], a[1], b[0], b[1], _ptr(out),
-                                               kernel | (_capi.SPAIR_ACCUMULATE if accumulate else 0)),
-              "pgenhip_sample_pair_stats_at")
-        return out[: 16 * a[1] * b[1]].view(a[1], b[1], 4, 4)
+        return self._sample_pair_tables(self._rows_at(base, record_off, n_variants), a, b, out, accumulate, kernel)
 
-    def _spair_out(self, a, b, out: Optional[torch.Tensor], accumulate: bool):
-        """(the two ranges with their defaults, the flat output: given, or allocated)"""
-        a = (0, self.kept_count) if a is None else (int(a[0]), int(a[1]))
-        b = (0, self.kept_count) if b is None else (int(b[0]), int(b[1]))
-        if min(a + b) < 0:
-            raise ValueError("sample ranges are (begin, count) with begin, count >= 0")
+    def _sample_pair_tables(self, rows: _Rows, a, b, out: Optional[torch.Tensor], accumulate: bool, kernel: int) -> torch.Tensor:
+        a, b = self._rank_ranges(a, b)
         need = 16 * a[1] * b[1]
-        if out is None:
-            make = torch.zeros if accumulate else torch.empty
-            return a, b, make(max(need, 4), dtype=torch.int32, device=self.torch_device)
-        self._check_dev(out, "out")
-        if out.dtype != torch.int32 or out.numel() < need:
-            raise ValueError(f"out must be an int32 tensor with >= {need} entries")
-        return a, b, out.view(-1)
+        out = self._flat_out(out, torch.int32, need, "out must be an int32 tensor with >= {need} entries", floor=4,
+                             fill=0 if accumulate else None)
+        self._entry("pgenhip_sample_pair_stats", rows, *a, *b, _ptr(out), kernel | (_capi.SPAIR_ACCUMULATE if accumulate else 0))
+        return out[:need].view(a[1], b[1], 4, 4)
 
     # -- sample Gram matrix -------------------------------------------------------------------------
     def sample_gram(self, records: torch.Tensor, record_stride: Optional[int] = None, variant_idx: Optional[torch.Tensor] = None,
@@ -1054,44 +936,27 @@ class GtEngine:
         its first element; row padding and everything else are untouched); ``out_stride``: doubles between its rows (default
         b_count).  ``accumulate``: add to what ``out`` holds instead of overwriting it.  ``kernel``: a forced shape
         (``_capi.GRAM_*``)."""
-        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
-        a, b, out, out_stride = self._gram_out(code_values, n_variants, a, b, out, out_stride, accumulate)
-        check(lib.pgenhip_sample_gram(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants,
-                                      _ptr(code_values), a[0], a[1], b[0], b[1], _ptr(out), out_stride,
-                                      kernel | (_capi.GRAM_ACCUMULATE if accumulate else 0)), "pgenhip_sample_gram")
-        return torch.as_strided(out, (a[1], b[1]), (out_stride, 1))
+        rows = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
+        return self._sample_gram(rows, code_values, a, b, out, out_stride, accumulate, kernel)
 
     def sample_gram_at(self, base: torch.Tensor, record_off: torch.Tensor, code_values: torch.Tensor, n_variants: Optional[int] = None, *,
                        a: Optional[tuple[int, int]] = None, b: Optional[tuple[int, int]] = None, out: Optional[torch.Tensor] = None,
                        out_stride: Optional[int] = None, accumulate: bool = False, kernel: int = _capi.GRAM_AUTO) -> torch.Tensor:
         """``sample_gram`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
-        n_variants = self._rows_at(base, record_off, n_variants)
-        a, b, out, out_stride = self._gram_out(code_values, n_variants, a, b, out, out_stride, accumulate)
-        check(lib.pgenhip_sample_gram_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, _ptr(code_values), a[0], a[1], b[0], b[1],
-                                         _ptr(out), out_stride, kernel | (_capi.GRAM_ACCUMULATE if accumulate else 0)),
-              "pgenhip_sample_gram_at")
-        return torch.as_strided(out, (a[1], b[1]), (out_stride, 1))
+        rows = self._rows_at(base, record_off, n_variants)
+        return self._sample_gram(rows, code_values, a, b, out, out_stride, accumulate, kernel)
 
-    def _gram_out(self, code_values: torch.Tensor, n_variants: int, a, b, out: Optional[torch.Tensor], out_stride: Optional[int],
-                  accumulate: bool):
-        """(the two ranges with their defaults, the flat output: given, or allocated, its row stride in doubles)"""
-        self._check_dev(code_values, "code_values")
-        if code_values.dtype != torch.float64 or code_values.numel() < 4 * n_variants:
-            raise ValueError("code_values must be a float64 tensor of shape (n_variants, 4)")
-        a = (0, self.kept_count) if a is None else (int(a[0]), int(a[1]))
-        b = (0, self.kept_count) if b is None else (int(b[0]), int(b[1]))
-        if min(a + b) < 0:
-            raise ValueError("sample ranges are (begin, count) with begin, count >= 0")
+    def _sample_gram(self, rows: _Rows, code_values: torch.Tensor, a, b, out: Optional[torch.Tensor], out_stride: Optional[int],
+                     accumulate: bool, kernel: int) -> torch.Tensor:
+        self._code_values(code_values, rows.n)
+        a, b = self._rank_ranges(a, b)
         if out_stride is None:
             out_stride = b[1]
         need = (a[1] - 1) * out_stride + b[1] if a[1] and b[1] else 0
-        if out is None:
-            make = torch.zeros if accumulate else torch.empty
-            return a, b, make(max(need, 1), dtype=torch.float64, device=self.torch_device), out_stride
-        self._check_dev(out, "out")
-        if out.dtype != torch.float64 or out.numel() < need:
-            raise ValueError(f"out must be a float64 tensor with >= {need} entries")
-        return a, b, out.view(-1), out_stride
+        out = self._flat_out(out, torch.float64, need, "out must be a float64 tensor with >= {need} entries", fill=0 if accumulate else None)
+        self._entry("pgenhip_sample_gram", rows, _ptr(code_values), *a, *b, _ptr(out), out_stride,
+                    kernel | (_capi.GRAM_ACCUMULATE if accumulate else 0))
+        return torch.as_strided(out, (a[1], b[1]), (out_stride, 1))
 
     # -- Gram product -------------------------------------------------------------------------------
     def gram_apply(self, records: torch.Tensor, code_values: torch.Tensor, q: torch.Tensor, *, record_stride: Optional[int] = None,
@@ -1108,33 +973,23 @@ class GtEngine:
         tensor of >= (K - 1) * out_stride + C entries (written from its first element; row padding and everything else are
         untouched); ``out_stride``: doubles between its rows (default C).  ``accumulate``: add to what ``out`` holds instead of
         overwriting it.  ``kernel``: a forced shape (``_capi.GAPPLY_*``)."""
-        record_stride, n_variants = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
-        q_stride, c, proj, out, out_stride = self._gapply_out(code_values, q, n_variants, proj, out, out_stride, accumulate)
-        check(lib.pgenhip_gram_apply(self._ctx, _ptr(records, records_offset), record_stride, _ptr(variant_idx), n_variants,
-                                     _ptr(code_values), _ptr(q), q_stride, c, _ptr(proj), _ptr(out), out_stride,
-                                     kernel | (_capi.GAPPLY_ACCUMULATE if accumulate else 0)), "pgenhip_gram_apply")
-        return proj[: n_variants * c].view(n_variants, c), torch.as_strided(out, (self.kept_count, c), (out_stride, 1))
+        rows = self._rows(records, record_stride, variant_idx, n_variants, records_offset)
+        return self._gram_apply(rows, code_values, q, proj, out, out_stride, accumulate, kernel)
 
     def gram_apply_at(self, base: torch.Tensor, record_off: torch.Tensor, code_values: torch.Tensor, q: torch.Tensor, *,
                       n_variants: Optional[int] = None, proj: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
                       out_stride: Optional[int] = None, accumulate: bool = False,
                       kernel: int = _capi.GAPPLY_AUTO) -> tuple[torch.Tensor, torch.Tensor]:
         """``gram_apply`` of records addressed by BYTE OFFSET into ``base`` (``record_off``: int64 CUDA tensor)."""
-        n_variants = self._rows_at(base, record_off, n_variants)
-        q_stride, c, proj, out, out_stride = self._gapply_out(code_values, q, n_variants, proj, out, out_stride, accumulate)
-        check(lib.pgenhip_gram_apply_at(self._ctx, _ptr(base), _ptr(record_off), n_variants, _ptr(code_values), _ptr(q), q_stride, c,
-                                        _ptr(proj), _ptr(out), out_stride, kernel | (_capi.GAPPLY_ACCUMULATE if accumulate else 0)),
-              "pgenhip_gram_apply_at")
-        return proj[: n_variants * c].view(n_variants, c), torch.as_strided(out, (self.kept_count, c), (out_stride, 1))
+        rows = self._rows_at(base, record_off, n_variants)
+        return self._gram_apply(rows, code_values, q, proj, out, out_stride, accumulate, kernel)
 
-    def _gapply_out(self, code_values: torch.Tensor, q: torch.Tensor, n_variants: int, proj: Optional[torch.Tensor],
-                    out: Optional[torch.Tensor], out_stride: Optional[int], accumulate: bool):
-        """(q's row stride, C, the flat proj and out: given, or allocated, out's row stride in doubles)"""
-        k = self.kept_count
-        self._check_dev(code_values, "code_values")
-        if code_values.dtype != torch.float64 or code_values.numel() < 4 * n_variants:
-            raise ValueError("code_values must be a float64 tensor of shape (n_variants, 4)")
-        if not q.is_cuda or q.device.index != self.device:   # (not _check_dev: q may be a view with padded rows)
+    def _gram_apply(self, rows: _Rows, code_values: torch.Tensor, q: torch.Tensor, proj: Optional[torch.Tensor], out: Optional[torch.Tensor],
+                    out_stride: Optional[int], accumulate: bool, kernel: int) -> tuple[torch.Tensor, torch.Tensor]:
+        n, k = rows.n, self.kept_count
+        self._code_values(code_values, n)
+        # q is not a _column_matrix: exactly two dimensions, exactly K rows, and a stride rule of its own that C = 1 does not escape
+        if not q.is_cuda or q.device.index != self.device:
             raise ValueError(f"q must live on cuda:{self.device}")
         if q.dtype != torch.float64 or q.dim() != 2 or q.shape[0] != k or not 1 <= q.shape[1] <= _capi.GAPPLY_MAX_COLUMNS:
             raise ValueError(f"q must be a float64 tensor of shape (K = {k}, 1 .. {_capi.GAPPLY_MAX_COLUMNS})")
@@ -1144,21 +999,12 @@ class GtEngine:
         q_stride = q.stride(0) if k > 1 else c
         if out_stride is None:
             out_stride = c
-        if proj is None:
-            proj = torch.empty(max(n_variants * c, 1), dtype=torch.float64, device=self.torch_device)
-        else:
-            self._check_dev(proj, "proj")
-            if proj.dtype != torch.float64 or proj.numel() < n_variants * c:
-                raise ValueError(f"proj must be a float64 tensor with >= {n_variants * c} entries")
-            proj = proj.view(-1)
+        proj = self._flat_out(proj, torch.float64, n * c, "proj must be a float64 tensor with >= {need} entries", name="proj")
         need = (k - 1) * out_stride + c if k else 0
-        if out is None:
-            make = torch.zeros if accumulate else torch.empty
-            return q_stride, c, proj, make(max(need, 1), dtype=torch.float64, device=self.torch_device), out_stride
-        self._check_dev(out, "out")
-        if out.dtype != torch.float64 or out.numel() < need:
-            raise ValueError(f"out must be a float64 tensor with >= {need} entries")
-        return q_stride, c, proj, out.view(-1), out_stride
+        out = self._flat_out(out, torch.float64, need, "out must be a float64 tensor with >= {need} entries", fill=0 if accumulate else None)
+        self._entry("pgenhip_gram_apply", rows, _ptr(code_values), _ptr(q), q_stride, c, _ptr(proj), _ptr(out), out_stride,
+                    kernel | (_capi.GAPPLY_ACCUMULATE if accumulate else 0))
+        return proj[: n * c].view(n, c), torch.as_strided(out, (k, c), (out_stride, 1))
 
     _MATRIX_DTYPES = {torch.int8: np.int8, torch.uint8: np.uint8, torch.int16: np.int16, torch.int32: np.int32,
                       torch.float16: np.float16, torch.bfloat16: None, torch.float32: np.float32}
@@ -1196,16 +1042,6 @@ class GtEngine:
             raise ValueError("out must have unit stride in its last dimension")
         stride = out.stride(0) * out.element_size() if rows > 1 else cols * out.element_size()
         return out, out, stride, tab
-
-    def _counts_out(self, out: Optional[torch.Tensor], n_variants: int, accumulate: bool = False) -> torch.Tensor:
-        if out is None:
-            if accumulate:
-                return torch.zeros(max(4 * n_variants, 4), dtype=torch.int32, device=self.torch_device)
-            return torch.empty(max(4 * n_variants, 4), dtype=torch.int32, device=self.torch_device)
-        self._check_dev(out, "out")
-        if out.dtype != torch.int32 or out.numel() < 4 * n_variants:
-            raise ValueError("out must be an int32 tensor with >= 4 * n_variants entries")
-        return out.view(-1)
 
     def synth_records(
         self,
